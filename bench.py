@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """bench.py — the hot path's headline metric on MI355X: Mpixels/s of the SSGI chain at 4K.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line: `value`, `ms_per_step` and the case's configuration.
+`--full` adds everything that takes runs of its own: the per-kernel durations and the roofline built on them, `ms_per_step_cold`, the
+stream-copy rate, the issue model, the CPU baselines and the extra cases (configs[4] at 8K; with N > 1 also weak scaling).
+`--dump-outputs DIR` writes, after the timed steps, the texture the effect hands its caller (the composed GI) as of the last timed step:
+DIR/<texture>.npy, float32, the whole frame (rows, cols, 4) up to OUTPUT_SAMPLE_PIXELS pixels, above that those pixels of it, chosen
+with a fixed seed (output_sample_pixels), as (pixels, 4) in frame order.  Every rank contributes its rows; rank 0 writes the file.
 
 With N > 1 and no RANK in the environment the command launches itself, one rank per GPU, as
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
@@ -21,7 +28,7 @@ Timing: `--spinup` untimed frames first (default 200 = 0.3 s: the device sat idl
 milliseconds run below the sustained clock — with --steps 20 --warmup 5 alone the step measured 1.556 ms against 1.51 sustained), then the W
 untimed warm-up steps, then EXACTLY K timed steps between barriers and device synchronisation, max over ranks.  The line says `spinup_frames`.
 
-Prints ONE JSON line (rank 0).  `kernel_ms` are the per-draw durations INSIDE the frame loop (rfx_profile: hipEvents around every draw's
+Prints ONE JSON line (rank 0).  With --full: `kernel_ms` are the per-draw durations INSIDE the frame loop (rfx_profile: hipEvents around every draw's
 launches on the stream they run on, over K more frames after the timed region — they sum to `ms_per_step`; K1's depth pre-pass runs on
 its own stream under the previous frame's later draws and is listed beside them); `roofline` is for the dominant kernel — K1, whose 68 B/px
 include the depth plane its pre-pass reads, so its duration there is march + pre-pass — next to a device-to-device stream-copy rate measured
@@ -158,6 +165,19 @@ def log(*a):
     print(*a, file=sys.stderr, flush=True)
 
 
+def host_cpus():
+    """CPUs this process may keep busy: its affinity mask, capped by a cgroup v2 CPU quota when one is set (a container's share of a
+    larger host; more dump workers than that only queue behind each other)"""
+    n = len(os.sched_getaffinity(0))
+    try:
+        quota, period = open("/sys/fs/cgroup/cpu.max").read().split()
+        if quota != "max":
+            n = min(n, max(1, int(quota) // int(period)))
+    except (OSError, ValueError):
+        pass
+    return n
+
+
 def ctl_device(dist, dev):
     """control-plane tensors (barrier payloads, the max-over-ranks reduction, set-up gathers) live where the process group's backend wants them"""
     return dev if (dist is not None and dist.get_backend() == "nccl") else "cpu"
@@ -169,7 +189,7 @@ def build_case(world, rank, local_rank, dev, dist, one_gpu, W, H, tiles, steps, 
     import torch
     y0, rows = tiles[rank]
     t0 = time.time()
-    nproc = max(1, min(32, len(os.sched_getaffinity(0)) // max(world, 1)))  # the dump is ray-cast on the host cores, split over the ranks
+    nproc = max(1, min(32, host_cpus() // max(world, 1)))  # the dump is ray-cast on the host cores, split over the ranks
     opts = dict(width=W, height=H, steps=steps, refineSteps=refine, denoiseIterations=iterations)
     # frame 1 of the orbit: non-zero velocity (camera moved 0.5 deg since frame 0).  The tile is dumped first, the
     # velocity bound over ALL tiles fixes the halo width, then the halo rows are dumped and attached.
@@ -364,6 +384,47 @@ def kernel_times_in_frame(case, n_frames):
     return kms, (pre[0] / pre[1] if pre else None)
 
 
+OUTPUT_SAMPLE_PIXELS = 1 << 21  # 32 MiB of float32 RGBA: --dump-outputs stays under its 64 MB whatever the frame
+
+
+def output_sample_pixels(W, H):
+    """Flat pixel indices (ascending) that --dump-outputs writes of a W x H frame: None = all of them, else a fixed seeded sample"""
+    if W * H <= OUTPUT_SAMPLE_PIXELS:
+        return None
+    return np.sort(np.random.default_rng(0).choice(W * H, OUTPUT_SAMPLE_PIXELS, replace=False))
+
+
+def dump_outputs(case, dist, rank, out_dir):
+    """The effect's output texture (what update() hands on as the effect's inputTexture) after the last timed step -> out_dir/<name>.npy.
+    Every rank reads its own tile rows; rank 0 writes the frame (or the seeded sample of it) in frame order."""
+    ctx, fx, W, H = case["ctx"], case["fx"], case["W"], case["H"]
+    tex = fx.denoiser.texture
+    tex = tex[0] if isinstance(tex, (tuple, list)) else tex
+    y0, rows = ctx.tile_y0, ctx.tile_rows
+    mine = ctx.download(tex, y0, rows)
+    if mine.dtype == np.uint16:  # half-float targets (denoise B): their values
+        mine = mine.view(np.float16)
+    mine = mine.astype(np.float32).reshape(rows * W, -1)
+    pick = output_sample_pixels(W, H)
+    if pick is not None:
+        lo, hi = np.searchsorted(pick, [y0 * W, (y0 + rows) * W])
+        mine = mine[pick[lo:hi] - y0 * W]
+    parts = [mine]
+    if dist is not None:
+        parts = [None] * dist.get_world_size()
+        dist.all_gather_object(parts, (y0, mine))
+        parts = [p for _, p in sorted(parts, key=lambda p: p[0])]
+    if rank != 0:
+        return
+    out = np.concatenate(parts, axis=0)
+    if pick is None:
+        out = out.reshape(H, W, -1)
+    os.makedirs(out_dir, exist_ok=True)
+    path = os.path.join(out_dir, "%s.npy" % abi.TEX_NAMES[tex])
+    np.save(path, out)
+    log("outputs: %s %s %s" % (path, out.dtype, out.shape))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -372,6 +433,9 @@ def main():
     ap.add_argument("--width", type=int, default=W4K)
     ap.add_argument("--height", type=int, default=H4K, help="frame rows (N = 1) / rows of the 4K frame that is cut into N tiles")
     ap.add_argument("--spinup", type=int, default=-1, help="untimed frames before the W warm-up steps that bring the idle device to its sustained clock (default: 200; 0 on the host simulator)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the effect's output texture of the last step to DIR/<texture>.npy")
+    ap.add_argument("--full", action="store_true", help="also measure what takes runs of its own: per-kernel durations, roofline, ms_per_step_cold, stream copy, "
+                                                        "issue model, CPU baselines, the extra cases (the --no-* switches below thin this out)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-stream-copy", action="store_true", help="skip the device-to-device copy measurement (profiling passes: only the path's own kernels)")
     ap.add_argument("--cpu-sample-rows", type=int, default=0, help="rows of the frame the CPU port baseline processes (0 = auto)")
@@ -466,7 +530,10 @@ def main():
         use_c = False
         group = dist.new_group(backend="nccl")
         case = build_case(world, rank, local_rank, dev, dist, one_gpu, W1, H1, tiles, 20, 5, 1, use_c=False, group=group)
-    dt, dt_cold = time_case(case, dist, args.steps, args.warmup, dev, spinup=args.spinup, cold=bool(args.spinup) and not args.no_cold)
+    full = args.full
+    dt, dt_cold = time_case(case, dist, args.steps, args.warmup, dev, spinup=args.spinup, cold=full and bool(args.spinup) and not args.no_cold)
+    if args.dump_outputs:
+        dump_outputs(case, dist, rank, args.dump_outputs)
     ctx = case["ctx"]
     ms_per_step = dt / args.steps * 1e3
     value = W1 * H1 * args.steps / dt / 1e6  # Mpixels/s, whole job
@@ -491,13 +558,13 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         history = {"mode": mode, "MB_received_per_frame_max_over_ranks": round(float(t.item()) / 1e6, 3),
                    "whole_frame_allgather_MB": round((H1 - min(n for _, n in tiles)) * W1 * 12 / 1e6, 3)}
-    kms_solo = {} if args.no_kernel_loops else kernel_times(case, max(5, min(args.steps, 20)))
-    kms, prepass_ms = kernel_times_in_frame(case, args.steps)
+    kms_solo = {} if (not full or args.no_kernel_loops) else kernel_times(case, max(5, min(args.steps, 20)))
+    kms, prepass_ms = kernel_times_in_frame(case, args.steps) if full else ({}, None)
     rows, halo = case["rows"], case["halo"]
-    copy_gbs = stream_copy_gbs(dev) if (rank == 0 and not args.no_stream_copy) else None  # measured here, after the timed region
+    copy_gbs = stream_copy_gbs(dev) if (full and rank == 0 and not args.no_stream_copy) else None  # measured here, after the timed region
 
     extras = {}
-    if world == 1 and not args.no_configs4 and not args.checksum and (W1, H1) == (W4K, H4K):
+    if full and world == 1 and not args.no_configs4 and not args.checksum and (W1, H1) == (W4K, H4K):
         # BASELINE configs[4] on this one GPU, beside the headline: 8K, steps 40, denoiseIterations 3 (six K3 draws), 16 frames — the configuration
         # north_star assigns to eight GPUs, and the one whose dominant kernel is NOT the 4K line's (five of its nine launches are K3's later pass)
         try:
@@ -527,6 +594,37 @@ def main():
     def emit():
         if rank != 0:
             return
+        workload = ("configs[2]: %dx%d (%.2f Mpixel) on one GPU" % (W1, H1, W1 * H1 / 1e6) if world == 1 else
+                    "configs[3]: the %dx%d frame cut into %d row tiles of %d rows" % (W1, H1, world, rows))
+        out = {
+            "metric": "Mpixels/s SSGI+denoise @4K steps=20; achieved HBM GB/s vs peak",
+            "value": round(value, 2), "unit": "Mpixels/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "spinup_frames": args.spinup,
+            "ms_per_step": round(ms_per_step, 4),
+            # the job is the same 4K frame at every N (N > 1 cuts it into N row tiles): total work fixed
+            "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+            "dtype": "f32", "data": "synthetic",
+            "config": {"workload": workload + ", steps=20 refineSteps=5 denoiseIterations=1, K1+K2+2xK3+K4 per step",
+                       "frame": "%dx%d" % (W1, H1), "tile_rows": rows, "halo_rows": halo, "direct_light": True, "half_store": "rtz", "uv_model": "reference_gl",
+                       "parallelism": "row-tiles x%d, RCCL halo send/recv after K2 and every K3 pass + composed GI (see history_exchange); exchange: %s" % (
+                           world, case_exchange(use_c, one_gpu, args)) if world > 1 else "single GPU"},
+            "halo_violations": viol,
+        }
+        if full:
+            out.update(kernel_figures())
+        if world > 1:
+            out["config"]["exchange_verified"] = bool(use_c)  # the C-ABI exchanges passed their pre-flight pattern check on every rank
+            out["config"]["history_exchange"] = history
+            if fallback_note:
+                out["config"]["exchange_fallback"] = fallback_note
+        out.update(extras)
+        if args.checksum:
+            out["compose_sha1"], out["frame_rows"] = compose_sha1, H1
+        if full and not args.no_cpu_baseline and world == 1:
+            out["cpu_baseline"] = cpu_baseline(case["frame"], case["fx"], W1, H1, args.cpu_sample_rows, not args.no_cpu_port)
+        print(json.dumps(out), flush=True)
+
+    def kernel_figures():
+        """--full: the keys of the line that rest on the per-kernel runs after the timed region"""
         px_tile = W1 * rows
         bpp = BYTES_PER_PX
         # K1's 68 B/px include the depth plane, which its PRE-PASS reads (k1_prepare + k1_pack_cells, own stream): its roofline duration is both
@@ -541,21 +639,9 @@ def main():
         ns_ms = chain_ms - k4_ms if "k4_compose" in kms else None  # the north-star quantity: K1 + K2 + 2 x K3 (268 B/px)
         ns_bytes = chain_bytes - BYTES_PER_PX["k4_compose"]
         prof = profile_meta()
-        workload = ("configs[2]: %dx%d (%.2f Mpixel) on one GPU" % (W1, H1, W1 * H1 / 1e6) if world == 1 else
-                    "configs[3]: the %dx%d frame cut into %d row tiles of %d rows" % (W1, H1, world, rows))
         out = {
-            "metric": "Mpixels/s SSGI+denoise @4K steps=20; achieved HBM GB/s vs peak",
-            "value": round(value, 2), "unit": "Mpixels/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "spinup_frames": args.spinup,
-            "ms_per_step": round(ms_per_step, 4),
             # the same W + K protocol run once BEFORE the spin-up frames, straight after the ~20 s of host-side set-up (device below its sustained clock)
             "ms_per_step_cold": round(dt_cold / args.steps * 1e3, 4) if dt_cold else None,
-            # the job is the same 4K frame at every N (N > 1 cuts it into N row tiles): total work fixed
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "config": {"workload": workload + ", steps=20 refineSteps=5 denoiseIterations=1, K1+K2+2xK3+K4 per step",
-                       "frame": "%dx%d" % (W1, H1), "tile_rows": rows, "halo_rows": halo, "direct_light": True, "half_store": "rtz", "uv_model": "reference_gl",
-                       "parallelism": "row-tiles x%d, RCCL halo send/recv after K2 and every K3 pass + composed GI (see history_exchange); exchange: %s" % (
-                           world, case_exchange(use_c, one_gpu, args)) if world > 1 else "single GPU"},
             # per-draw durations INSIDE the frame loop (rfx_profile: events around every draw on its stream, K more frames after the timed region)
             "kernel_ms": {k: round(v, 4) for k, v in kms.items()},
             "k1_prepass_ms": round(prepass_ms, 4) if prepass_ms is not None else None,
@@ -577,7 +663,6 @@ def main():
                          "avg_launch_ms_note": ("in-frame duration, rfx_profile" + (
                              ": march %.4f + depth pre-pass %.4f ms (the pre-pass reads the depth plane that is part of K1's 68 B/px; it runs on its own "
                              "stream under the previous frame's later draws)" % (kms["k1_ssgi_march"], prepass_ms) if dom == "k1_ssgi_march" and prepass_ms is not None else ""))},
-            "halo_violations": viol,
         }
         # what binds: instruction issue.  Per kernel, the ABSOLUTE time its measured dynamic instruction mix costs to issue
         # (tools/issue_model.py: class counts from rocprofv3 --pmc x the per-class issue cost measured on this part) next to the time the kernel took
@@ -595,19 +680,9 @@ def main():
                                  "events' own few microseconds; K1's depth pre-pass (k1_prepass_ms) runs on its own stream under the previous frame's K2-K4 and is not "
                                  "in that sum.  kernel_ms_solo: every kernel timed on its own, back-to-back launches of one entry point (K1 then serialises with its own "
                                  "pre-pass: longer than in a frame; K2-K4 run without a pre-pass beside them: shorter)")
-        if world > 1:
-            out["config"]["exchange_verified"] = bool(use_c)  # the C-ABI exchanges passed their pre-flight pattern check on every rank
-            out["config"]["history_exchange"] = history
-            if fallback_note:
-                out["config"]["exchange_fallback"] = fallback_note
-        out.update(extras)
-        if args.checksum:
-            out["compose_sha1"], out["frame_rows"] = compose_sha1, H1
-        if not args.no_cpu_baseline and world == 1:
-            out["cpu_baseline"] = cpu_baseline(case["frame"], case["fx"], W1, H1, args.cpu_sample_rows, not args.no_cpu_port)
-        print(json.dumps(out), flush=True)
+        return out
 
-    if world > 1 and not args.no_extras:
+    if full and world > 1 and not args.no_extras:
         ctx.close()
         case = None
         # the headline is measured: a collective that hangs in the extras (their first run on a real multi-GPU node is the driver's) must

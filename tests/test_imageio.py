@@ -1,5 +1,5 @@
 """CPU: the file formats either side of the path: EXR / PFM / PNG round trips, the AOV-EXR importer feeding the
-device-side packer's oracle, tone mapping, and — where /root/reference exists — the reference example's own Radiance .hdr environment and
+device-side packer's oracle, tone mapping, and the reference example's own Radiance .hdr environment and
 its blue-noise PNG."""
 import os
 
@@ -173,14 +173,17 @@ def test_aov_exr_import_feeds_the_packer(tmp_path):
     np.testing.assert_allclose(h.camera.projectionMatrix, f.camera.projectionMatrix)
 
 
-@pytest.mark.reference
-@pytest.mark.skipif(not os.path.isdir("/root/reference/example/public/hdr"), reason="/root/reference absent")
-def test_reference_example_assets_import(blue_noise):
-    """Non-synthetic inputs: the reference example's environment map (example/public/hdr/*.hdr, what its RGBELoader loads into
-    scene.environment) through read_hdr -> the environment chain + the importance tables; and the reference's blue-noise PNG decodes
-    to exactly the table this package ships (src/utils/blue_noise_rgba.png, flipY as BlueNoiseUtils.js:9-15)."""
+def test_reference_example_assets_import(blue_noise, tmp_path):
+    """Non-synthetic inputs: the reference example's environment map (example/public/hdr/spree_bank_1k.hdr, what its RGBELoader loads into
+    scene.environment by default; stored xz-compressed under tests/golden/) through read_hdr -> the environment chain + the importance tables;
+    and the reference's blue-noise PNG (src/utils/blue_noise_rgba.png, copied to tests/golden/) decodes to exactly the table this package
+    ships (flipY as BlueNoiseUtils.js:9-15)."""
+    import lzma
     from rfx_amd import envmap
-    env = imageio.environment_from_hdr("/root/reference/example/public/hdr/spree_bank_1k.hdr")
+    golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    hdr = tmp_path / "spree_bank_1k.hdr"
+    hdr.write_bytes(lzma.open(os.path.join(golden, "spree_bank_1k.hdr.xz")).read())
+    env = imageio.environment_from_hdr(str(hdr))
     assert env.shape == (512, 1024, 4) and np.isfinite(env).all() and env[..., :3].max() > 4.0 and (env[..., :3] >= 0).all()
     e = O.EnvMap(env, half=True)
     assert e.levels == 11 and np.isfinite(e.level(10)).all()
@@ -188,7 +191,7 @@ def test_reference_example_assets_import(blue_noise):
     assert env[256:, :, :3].mean() > env[:256, :, :3].mean()
     m, c, tot = envmap.build_importance(env[::4, ::4].astype(np.float16).astype(np.float32))
     assert m.shape == (128,) and c.shape == (128, 256) and tot > 0 and (np.diff(m) >= 0).all()
-    assert np.array_equal(imageio.read_png("/root/reference/src/utils/blue_noise_rgba.png"), blue_noise)
+    assert np.array_equal(imageio.read_png(os.path.join(golden, "blue_noise_rgba.png")), blue_noise)
 
 
 def test_node_image_writers_match_python(tmp_path):

@@ -576,7 +576,9 @@ if (isMainThread) {
     allgatherHistory() { throw new Error("not in this mode") }, gatherHistoryRows() { throw new Error("not in this mode") },
     commWait: () => addon.commWait(R.inner._h),
     peerExport: tex => addon.peerExport(R.inner._h, tex), peerOpen: (tex, blobs, r, n) => addon.peerOpen(R.inner._h, tex, blobs, r, n),
-    peerGatherHistory: tex => addon.peerGatherHistory(R.inner._h, tex), peerClose: () => addon.peerClose(R.inner._h)
+    // the two tiles issue the call together, as ranks in lock step do: each worker reads and uploads its next dump before the frame, and under a
+    // loaded host that alone can put one thread's call past the other's bounded device poll (~2 s); the kernels still meet on the device
+    peerGatherHistory: tex => { barrier(); return addon.peerGatherHistory(R.inner._h, tex) }, peerClose: () => addon.peerClose(R.inner._h)
   }
   const first = rfx.readDump(dumps[0])
   R = new rfx.TiledRenderer(first.width, first.height, rank, N, opt.halo, null, { comm, device: 0 })

@@ -22,9 +22,9 @@ PY
 $ROOT/tools/microbench/bin/valu_rates2 > $OUT/valu_rates2.txt 2>&1
 cd /tmp && export TMPDIR=/tmp
 # the profiled command: the bench's own loop after its spin-up (--spinup 50: the device at its sustained clock, as in the line), 20 timed frames
-BENCH="python $ROOT/bench.py --steps 20 --warmup 2 --spinup 50 --no-cpu-baseline --no-stream-copy --no-cold --no-kernel-loops --no-configs4"
+BENCH="python $ROOT/bench.py --full --steps 20 --warmup 2 --spinup 50 --no-cpu-baseline --no-stream-copy --no-cold --no-kernel-loops --no-configs4"
 # 1. the bench line itself (un-profiled, with the CPU baselines)
-python $ROOT/bench.py > $OUT/bench.json 2> $OUT/bench.err
+python $ROOT/bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 # 2. kernel trace + stats
 rocprofv3 --kernel-trace --stats -d $OUT/trace -o t --output-format csv -- $BENCH > $OUT/trace.log 2>&1
 cp $(find $OUT/trace -name "*kernel_stats.csv" | head -1) $OUT/kernel_stats.csv 2>/dev/null
