@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define RFX_ABI_VERSION 19
+#define RFX_ABI_VERSION 20
 
 enum {
     RFX_OK = 0,
@@ -77,6 +77,9 @@ typedef enum rfx_tex {
     RFX_TEX_FINAL,          /* RGBA32F   SSGIEffect's own fragment (ssgi_compose.frag mainImage): the effect's output colour */
     RFX_TEX_COMPOSE_RGB,    /* RGB32F    .rgb of RFX_TEX_COMPOSE as 12-byte texels, held whole: the part of `accumulatedTexture` K1 reads,
                                kept beside it (rfx_compose_params.writeHistoryRGB) so that a row-tiled run all-gathers 12 B/px, not 16 */
+    RFX_TEX_EFFECT_INPUT,   /* RGBA32F   (ABI 20) a host-filled effect input buffer: what an EffectPass reads as `inputBuffer` when it
+                               does not come out of an earlier draw (a downloaded frame, TRAA's input plane ...); rfx_motion_blur */
+    RFX_TEX_MOTION_BLUR,    /* RGBA32F   (ABI 20) MotionBlurEffect's output colour (rfx_motion_blur)                              */
     RFX_TEX_COUNT
 } rfx_tex;
 
@@ -182,6 +185,38 @@ typedef struct rfx_final_params {
     float fogNear, fogFar; /* fogMode 1 */
     float fogDensity;      /* fogMode 2 */
 } rfx_final_params;
+
+/* K6 — MotionBlurEffect (ABI 20): src/motion-blur/MotionBlurEffect.js:14-66,85-101 (uniforms / defines) and the effect's mainImage,
+ * src/motion-blur/shader/motion_blur.frag:11-45, with the blue noise of src/utils/shader/blue_noise.glsl:37-45.  Per fragment:
+ *   v = velocityTexture(vUv).xy (NEAREST, RFX_TEX_VELOCITY); dot(v, v) > 1e-9 is false (NaN included): output = inputColor.  Else
+ *   v *= intensity; jitterOffset = jitter * v * blueNoise(vUv, frame).xy; frameSpeed = 0.01 / deltaTime;
+ *   start = max(0, vUv + (jitterOffset - v * 0.5) * frameSpeed), end = min(1, vUv + (jitterOffset + v * 0.5) * frameSpeed);
+ *   rgb = (inputColor.rgb + sum_{i=0..samples} inputTexture(mix(start, end, i / samples)).rgb) / (samples + 2)  (LINEAR taps);
+ *   alpha = inputColor.a.
+ * `inputColor` is what postprocessing's EffectMaterial hands the effect's mainImage: in the effect's own EffectPass the LINEAR fetch of the
+ * pass's input buffer at vUv (the same slot as the taps); in the reference's README form EffectPass(camera, traaEffect, motionBlurEffect),
+ * TRAA's output, traa_compose.frag: the NEAREST texel of RFX_TEX_TEMPORAL0 (TemporalReprojectPass.js:66-67) with alpha 1, while the taps
+ * read the pass's input buffer (the plane TRAA's K2 took as its input: RFX_TEX_SSGI in both hosts).  Writes RFX_TEX_MOTION_BLUR.
+ * Whole-frame contexts only (a streak can reach anywhere): a row-tiled context gets RFX_EUNSUPPORTED.  Honours rfx_set_row_window and
+ * rfx_set_uv_model.  RFX_ESTATE when a host-filled input (RFX_TEX_VELOCITY, RFX_TEX_BLUE_NOISE, RFX_TEX_DIRECT_LIGHT, RFX_TEX_EFFECT_INPUT)
+ * was never uploaded, packed, staged or bound, or a drawn one (RFX_TEX_FINAL, RFX_TEX_TEMPORAL0, RFX_TEX_SSGI) holds nothing yet. */
+typedef struct rfx_motion_blur_params {
+    int32_t source;         /* the taps' `inputTexture`: RFX_TEX_FINAL, RFX_TEX_TEMPORAL0, RFX_TEX_DIRECT_LIGHT, RFX_TEX_SSGI or RFX_TEX_EFFECT_INPUT
+                               (each read as RGBA32F) */
+    int32_t center;         /* the slot `inputColor` comes from.  -1: the effect's own EffectPass, the LINEAR fetch of `source` at vUv (a
+                               `source` of RFX_TEX_TEMPORAL0 then stands for the buffer TRAA's own EffectPass wrote: pass centerAlphaOne 1).
+                               An explicit slot is read with the reference's filter: NEAREST for RFX_TEX_TEMPORAL0 (TRAA's NearestFilter
+                               target, the README form), LINEAR at vUv for the others */
+    int32_t centerAlphaOne; /* 1: inputColor.a = 1 (traa_compose.frag:6 wrote it); 0: the centre's own alpha */
+    int32_t samples;        /* #define samples, in [1, 65536] (default 16; fixed at construction, MotionBlurEffect.js:37-40) */
+    float intensity;        /* uniform intensity (default 1) */
+    float jitter;           /* uniform jitter (default 1) */
+    float deltaTime;        /* uniform deltaTime: the host passes max(1/1000, deltaTime) (:89); finite and > 0 */
+    int32_t frame;          /* uniform frame: renderer.info.render.frame % 4096 (:91); blueNoise's index, 0 = the unshifted table */
+    float resolution[2];    /* uniform resolution: window.innerWidth / innerHeight (:94): the blue-noise pixel grid; finite, in (0, 65536] */
+    int32_t targetHalf;     /* 1: the composer's buffers are HalfFloatType: the output is rounded to half precision on store */
+    int32_t halfStoreRTZ;   /* rounding of that store: 1 truncate (llvmpipe), 0 nearest-even */
+} rfx_motion_blur_params;
 
 typedef struct rfx_ctx rfx_ctx;
 
@@ -309,6 +344,8 @@ int rfx_compose(rfx_ctx *, const rfx_compose_params *);
  * SSGIEffect.update(): background texels take the scene colour (RFX_TEX_DIRECT_LIGHT = the composer's input buffer),
  * the rest the composed GI (RFX_TEX_COMPOSE), fogged when the scene has fog; alpha 1.  Writes RFX_TEX_FINAL. */
 int rfx_final_compose(rfx_ctx *, const rfx_final_params *);
+/* MotionBlurEffect's mainImage (K6, ABI 20): see rfx_motion_blur_params.  Writes RFX_TEX_MOTION_BLUR. */
+int rfx_motion_blur(rfx_ctx *, const rfx_motion_blur_params *);
 
 int rfx_sync(rfx_ctx *);
 
@@ -402,6 +439,7 @@ int rfx_time_end(rfx_ctx *, float *elapsed_ms);
  * the summed milliseconds and the number of launches since the reset (arrays of RFX_PROF_COUNT entries; either may be NULL).  The events cost
  * a few microseconds per draw: the frame's own time (`value`) is measured without them.  At most 8192 launches are recorded per reset. */
 enum { RFX_PROF_K1_PREPASS = 0, RFX_PROF_K1_MARCH, RFX_PROF_K2, RFX_PROF_K3_PASS0, RFX_PROF_K3_PASSN, RFX_PROF_K4, RFX_PROF_K5,
+       RFX_PROF_K6, /* ABI 20: rfx_motion_blur */
        RFX_PROF_COUNT };
 int rfx_profile(rfx_ctx *, int enable);
 int rfx_profile_read(rfx_ctx *, float *ms_sum, int *launches);

@@ -110,7 +110,95 @@ __global__ __launch_bounds__(256) void k5_final_compose(K5Args A) {
     rfx_flush_violations(d);
 }
 
+// K6 — MotionBlurEffect's mainImage, src/motion-blur/shader/motion_blur.frag:11-45 (blueNoise: src/utils/shader/blue_noise.glsl:37-45).
+// One lane per pixel on 16 x 16 tiles: the samples + 1 LINEAR taps of a streak in any direction stay near the tile's other taps in L1.
+// Every expression keeps the GLSL's operation order and rounding: this file is compiled with contraction on, so the arithmetic below
+// is written uncontracted and the fused operations the reference GL performs (its sampler's lerps) are explicit fmas.
+
+// textureLod(inputTexture, uv, 0.) on an RGBA32F texture, LinearFilter, CLAMP_TO_EDGE, as the reference GL's sampler computes it:
+// llvmpipe's coordinates (rfx_linear_coord_fast: rfx_linear_coord's (i0, w) for every finite coordinate; NaN clamps to texel 0)
+// and its fused lerps.  .rgb only: the effect never reads a tap's alpha.
+RFX_DEV float3 k6_tap(const float4 *t, const FrameDims &d, float u, float v) {
+#pragma clang fp contract(off)
+    const float cx = u * d.fW, cy = v * d.fH;
+    const LinearCoord lx = rfx_linear_coord_fast(cx, d.fW - 0.5f), ly = rfx_linear_coord_fast(cy, d.fH - 0.5f);
+    const int x1 = min(lx.i0 + 1, d.W - 1), y1 = min(ly.i0 + 1, d.H - 1);
+    const unsigned int r0 = (unsigned int)__mul24(ly.i0, d.W), r1 = (unsigned int)__mul24(y1, d.W);
+    const float4 t00 = rfx_gather<float4>(t, r0 + lx.i0), t10 = rfx_gather<float4>(t, r0 + x1);
+    const float4 t01 = rfx_gather<float4>(t, r1 + lx.i0), t11 = rfx_gather<float4>(t, r1 + x1);
+    const float wx = lx.w, wy = ly.w;
+    const float r0x = __builtin_fmaf(wx, t10.x - t00.x, t00.x), r1x = __builtin_fmaf(wx, t11.x - t01.x, t01.x);
+    const float r0y = __builtin_fmaf(wx, t10.y - t00.y, t00.y), r1y = __builtin_fmaf(wx, t11.y - t01.y, t01.y);
+    const float r0z = __builtin_fmaf(wx, t10.z - t00.z, t00.z), r1z = __builtin_fmaf(wx, t11.z - t01.z, t01.z);
+    return make_float3(__builtin_fmaf(wy, r1x - r0x, r0x), __builtin_fmaf(wy, r1y - r0y, r0y), __builtin_fmaf(wy, r1z - r0z, r0z));
+}
+// the same fetch with alpha: inputColor in the effect's own EffectPass, texture2D(inputBuffer, vUv)
+RFX_DEV float4 k6_center_linear(const float4 *t, const FrameDims &d, float u, float v) {
+#pragma clang fp contract(off)
+    const float cx = u * d.fW, cy = v * d.fH;
+    const LinearCoord lx = rfx_linear_coord_fast(cx, d.fW - 0.5f), ly = rfx_linear_coord_fast(cy, d.fH - 0.5f);
+    const int x1 = min(lx.i0 + 1, d.W - 1), y1 = min(ly.i0 + 1, d.H - 1);
+    const unsigned int r0 = (unsigned int)__mul24(ly.i0, d.W), r1 = (unsigned int)__mul24(y1, d.W);
+    const float4 t00 = rfx_gather<float4>(t, r0 + lx.i0), t10 = rfx_gather<float4>(t, r0 + x1);
+    const float4 t01 = rfx_gather<float4>(t, r1 + lx.i0), t11 = rfx_gather<float4>(t, r1 + x1);
+    const float wx = lx.w, wy = ly.w;
+    float4 r;
+    const float a0 = __builtin_fmaf(wx, t10.w - t00.w, t00.w), a1 = __builtin_fmaf(wx, t11.w - t01.w, t01.w);
+    const float3 c = k6_tap(t, d, u, v);
+    r.x = c.x; r.y = c.y; r.z = c.z;
+    r.w = __builtin_fmaf(wy, a1 - a0, a0);
+    return r;
+}
+
+__global__ __launch_bounds__(256) void k6_motion_blur(K6Args A) {
+#pragma clang fp contract(off)
+    const FrameDims &d = A.dims;
+    const int x = blockIdx.x * 16 + threadIdx.x, y = A.y0 + blockIdx.y * 16 + threadIdx.y;
+    if (x >= d.W || y >= A.y1) return;
+    const float u = rfx_frag_u(d.uv, x, y), v = rfx_frag_v(d.uv, y);
+    const unsigned int idx = (unsigned int)__mul24(y, d.W) + (unsigned int)x;
+    // inputColor: TRAA's NEAREST target texel (README form) or the LINEAR fetch of the pass's input buffer at vUv
+    float4 o = A.center_nearest ? rfx_gather<float4>(A.center, idx) : k6_center_linear(A.center, d, u, v);
+    if (A.center_alpha_one) o.w = 1.0f;  // traa_compose.frag:6
+    const float4 vel = rfx_gather<float4>(A.velocity, idx);  // :12 textureLod(velocityTexture, vUv, 0.0).xy, NEAREST
+    float vx = vel.x, vy = vel.y;
+    if (vx * vx + vy * vy > 0.000000001f) {  // :13-18 (NaN: not moved)
+        vx *= A.intensity;  // :20
+        vy *= A.intensity;
+        // :22 blueNoise(vUv, frame): ivec2(vUv * resolution), shifted by the frame's pcg4d round (frame 0: the table at uv * resolution /
+        // blueNoiseSize, NEAREST + REPEAT — the same texel, the division by 128 being exact); vUv * resolution >= 0: truncation = floor
+        const float4 bn = rfx_blue_noise(A.blue, (int)(u * A.resX), (int)(v * A.resY), A.shift_x, A.shift_y);
+        const float jx = (A.jitter * vx) * bn.x, jy = (A.jitter * vy) * bn.y;  // :23
+        const float hx = vx * 0.5f, hy = vy * 0.5f;
+        // :28-32
+        const float su = rfx_max_raw(0.0f, u + (jx - hx) * A.frameSpeed), sv = rfx_max_raw(0.0f, v + (jy - hy) * A.frameSpeed);
+        const float eu = rfx_min_raw(1.0f, u + (jx + hx) * A.frameSpeed), ev = rfx_min_raw(1.0f, v + (jy + hy) * A.frameSpeed);
+        const float du = eu - su, dv = ev - sv;
+        float3 acc = make_float3(o.x, o.y, o.z);  // :34
+        for (int i = 0; i <= A.samples; i++) {  // :35-40
+            const float t = rfx_div_const_impl((float)i, A.samplesF, A.rcpSamplesF);  // i / samplesFloat, correctly rounded
+            // mix(startUv, endUv, t) as the reference GL lowers it: a + t * (b - a), two roundings (tools/probe_motion_blur_gl.py)
+            const float3 c = k6_tap(A.src, d, su + t * du, sv + t * dv);
+            acc.x = acc.x + c.x;
+            acc.y = acc.y + c.y;
+            acc.z = acc.z + c.z;
+        }
+        // :42 motionBlurredColor /= samplesFloat + 2. (IEEE division: any sum, infinities and subnormal quotients included)
+        o.x = acc.x / A.div2;
+        o.y = acc.y / A.div2;
+        o.z = acc.z / A.div2;
+    }
+    if (A.target_half) o = rfx_round_half4(o, A.half_rtz != 0);  // HalfFloatType composer buffer
+    A.out[idx] = o;
+}
+
 }  // namespace
+
+hipError_t rfx_launch_k6(const K6Args &A, hipStream_t stream) {
+    dim3 block(16, 16), grid((A.dims.W + 15) / 16, (A.y1 - A.y0 + 15) / 16);
+    hipLaunchKernelGGL(k6_motion_blur, grid, block, 0, stream, A);
+    return hipGetLastError();
+}
 
 hipError_t rfx_launch_k5(const K5Args &A, hipStream_t stream) {
     dim3 block(64, 4), grid((A.dims.W + 63) / 64, (A.y1 - A.y0 + 3) / 4);

@@ -968,6 +968,61 @@ int rfx_final_compose(rfx_ctx *c, const rfx_final_params *p) {
     return RFX_OK;
 }
 
+int rfx_motion_blur(rfx_ctx *c, const rfx_motion_blur_params *p) {
+    if (!c || !p) return RFX_EINVAL;
+    RFX_ENTER(c);
+    const auto tap_slot = [](int id) {
+        return id == RFX_TEX_FINAL || id == RFX_TEX_TEMPORAL0 || id == RFX_TEX_DIRECT_LIGHT || id == RFX_TEX_SSGI || id == RFX_TEX_EFFECT_INPUT;
+    };
+    if (!tap_slot(p->source)) return fail(c, RFX_EINVAL, "rfx_motion_blur: source must be FINAL, TEMPORAL0, DIRECT_LIGHT, SSGI or EFFECT_INPUT");
+    const int center = p->center == -1 ? p->source : p->center;
+    if (!tap_slot(center)) return fail(c, RFX_EINVAL, "rfx_motion_blur: center must be -1 or one of the source slots");
+    if (p->samples < 1 || p->samples > 65536) return fail(c, RFX_EINVAL, "rfx_motion_blur: samples must be in [1, 65536]");
+    if (!(p->deltaTime > 0.0f) || !(p->deltaTime <= 3.402823466e38f)) return fail(c, RFX_EINVAL, "rfx_motion_blur: deltaTime must be finite and > 0");
+    for (int k = 0; k < 2; k++)
+        if (!(p->resolution[k] > 0.0f) || !(p->resolution[k] <= 65536.0f)) return fail(c, RFX_EINVAL, "rfx_motion_blur: resolution must be in (0, 65536]");
+    if (p->frame < 0) return fail(c, RFX_EINVAL, "rfx_motion_blur: frame must be >= 0 (the reference passes frame % 4096)");
+    if (c->tile_y0 != 0 || c->tile_rows != c->H) return fail(c, RFX_EUNSUPPORTED, "rfx_motion_blur: needs a whole-frame context (a streak can reach anywhere)");
+    // host-filled planes must have been uploaded (packed, staged or bound), as K2 / K3 require of theirs; the slots a draw writes
+    // (FINAL, TEMPORAL0, SSGI) must at least exist — a draw, an upload or a clear made them
+    const auto host_filled = [](int id) {
+        return id == RFX_TEX_VELOCITY || id == RFX_TEX_BLUE_NOISE || id == RFX_TEX_DIRECT_LIGHT || id == RFX_TEX_EFFECT_INPUT;
+    };
+    const int ins[] = {RFX_TEX_VELOCITY, RFX_TEX_BLUE_NOISE, p->source, center};
+    for (int id : ins)
+        if (host_filled(id) ? !c->slots[id].uploaded : !c->slots[id].ptr)
+            return fail(c, RFX_ESTATE, "rfx_motion_blur: an input slot holds nothing yet (upload it or draw into it first)");
+    int rc = ensure(c, RFX_TEX_MOTION_BLUR);
+    if (rc) return rc;
+    K6Args A;
+    A.dims = dims(c);
+    if (!launch_rows(c, RFX_TEX_MOTION_BLUR, 0, &A.y0, &A.y1)) return RFX_OK;
+    A.velocity = (const float4 *)c->slots[RFX_TEX_VELOCITY].ptr;
+    A.src = (const float4 *)c->slots[p->source].ptr;
+    A.center = (const float4 *)c->slots[center].ptr;
+    A.out = (float4 *)c->slots[RFX_TEX_MOTION_BLUR].ptr;
+    A.blue = (const uchar4 *)c->slots[RFX_TEX_BLUE_NOISE].ptr;
+    blue_noise_shift(p->frame, &A.shift_x, &A.shift_y);
+    // center -1: the own EffectPass, inputColor = texture2D(inputBuffer, vUv), LINEAR on the same buffer as the taps.  An explicit
+    // RFX_TEX_TEMPORAL0 is TRAA's render target itself (README form), NearestFilter (TemporalReprojectPass.js:66-67)
+    A.center_nearest = p->center == RFX_TEX_TEMPORAL0;
+    A.center_alpha_one = p->centerAlphaOne != 0;
+    A.target_half = p->targetHalf != 0;
+    A.half_rtz = p->halfStoreRTZ != 0;
+    A.samples = p->samples;
+    A.samplesF = (float)p->samples;  // #define samplesFloat samples.0
+    A.rcpSamplesF = 1.0f / A.samplesF;
+    A.div2 = A.samplesF + 2.0f;
+    A.intensity = p->intensity;
+    A.jitter = p->jitter;
+    A.frameSpeed = 0.01f / p->deltaTime;  // :25 (1. / 100.) / deltaTime
+    A.resX = p->resolution[0];
+    A.resY = p->resolution[1];
+    ProfScope prof(c, RFX_PROF_K6, c->stream);
+    HIPCHK(c, rfx_launch_k6(A, c->stream));
+    return RFX_OK;
+}
+
 int rfx_sync(rfx_ctx *c) {
     if (!c) return RFX_EINVAL;
     RFX_ENTER(c);

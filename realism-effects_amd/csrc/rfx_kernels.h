@@ -95,6 +95,25 @@ struct K5Args {
 };
 
 hipError_t rfx_launch_k5(const K5Args &, hipStream_t);
+
+// K6 (k4_compose.hip): MotionBlurEffect.  Whole-frame views only (rfx_motion_blur refuses row-tiled contexts).
+struct K6Args {
+    FrameDims dims;
+    int y0, y1;
+    const float4 *velocity;  // RFX_TEX_VELOCITY: .xy = uv-space velocity (NEAREST at vUv = the pixel's own texel)
+    const float4 *src;       // inputTexture (LINEAR taps)
+    const float4 *center;    // where inputColor comes from
+    float4 *out;             // RFX_TEX_MOTION_BLUR
+    const uchar4 *blue;      // the 128 x 128 blue-noise table
+    int shift_x, shift_y;    // blueNoise's per-frame toroidal shift (0 for frame 0: the texture path)
+    int center_nearest, center_alpha_one, target_half, half_rtz;
+    int samples;
+    float samplesF, rcpSamplesF;  // samplesFloat and RN(1 / samplesFloat): i / samplesFloat as rfx_div_const_impl
+    float div2;                   // samplesFloat + 2
+    float intensity, jitter, frameSpeed;  // frameSpeed = RN(0.01 / deltaTime), a uniform expression: the same for every fragment
+    float resX, resY;
+};
+hipError_t rfx_launch_k6(const K6Args &, hipStream_t);
 int rfx_k1_base_cell();  // edge of k1_prepare's base cells in texels
 hipError_t rfx_launch_k1_prepare(const K1Args &, hipStream_t);
 hipError_t rfx_launch_k1(const K1Args &, int stage /* 0 fused, 1 trace, 2 shade */, hipStream_t);

@@ -26,7 +26,9 @@ const TEX = {
 	FBCOPY_F16: 13,
 	FBCOPY_F32: 14,
 	FINAL: 15,
-	COMPOSE_RGB: 16
+	COMPOSE_RGB: 16,
+	EFFECT_INPUT: 17,
+	MOTION_BLUR: 18
 }
 // [TypedArray constructor, elements per texel]
 const FORMAT = {
@@ -46,7 +48,9 @@ const FORMAT = {
 	13: [Uint16Array, 4],
 	14: [Float32Array, 4],
 	15: [Float32Array, 4],
-	16: [Float32Array, 3]
+	16: [Float32Array, 3],
+	17: [Float32Array, 4],
+	18: [Float32Array, 4]
 }
 
 // 128x128 RGBA8 blue-noise table: decoded once from the reference's PNG asset, already flipY'd
@@ -194,6 +198,10 @@ class Renderer {
 	// SSGIEffect's own fragment (ssgi_compose.frag mainImage)
 	finalCompose(uniforms) {
 		addon.finalCompose(this._h, uniforms)
+	}
+	// MotionBlurEffect's fragment (K6, rfx_motion_blur) -> TEX.MOTION_BLUR
+	motionBlur(uniforms) {
+		addon.motionBlur(this._h, uniforms)
 	}
 
 	sync() {

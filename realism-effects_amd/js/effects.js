@@ -842,6 +842,88 @@ class TRAAEffect {
 }
 TRAAEffect.DefaultOptions = defaultTemporalReprojectPassOptions
 
+// src/motion-blur/MotionBlurEffect.js:14
+const defaultMotionBlurOptions = { intensity: 1, jitter: 1, samples: 16 }
+
+// src/motion-blur/MotionBlurEffect.js:16-101 (K6, rfx_motion_blur).  `samples` is a define fixed at construction: the reactive setters
+// forward only `intensity` and `jitter` (:42-45,51-66).  update(renderer, inputBuffer, deltaTime): `inputBuffer` is a slot id (TEX.FINAL
+// after SSGIEffect.mainImage: the blur stays on the device; TEX.TEMPORAL0 stands for the buffer TRAA's own EffectPass wrote, alpha 1) or a
+// host buffer { texture: { type }, data } uploaded to TEX.EFFECT_INPUT.  `frame` (renderer.info.render.frame % 4096, :91) defaults to the
+// number of updates and `resolution` (window.innerWidth / innerHeight, :94) to the frame size.  shareEffectPass(traaEffect): the README
+// form EffectPass(camera, traaEffect, motionBlurEffect) — inputColor = TRAA's output, the taps read TRAA's input plane (TEX.SSGI).
+class MotionBlurEffect {
+	// `halfStoreRTZ` is an addition for parity runs against the llvmpipe oracle (RGBA16F stores truncate there)
+	constructor(velocityPass, options, halfStoreRTZ) {
+		options = Object.assign({}, defaultMotionBlurOptions, options || defaultMotionBlurOptions)
+		this.velocityPass = velocityPass
+		this.uniforms = {
+			source: TEX.FINAL, center: -1, centerAlphaOne: 0, samples: parseInt(Number(options.samples).toFixed(0), 10), intensity: 1, jitter: 1,
+			deltaTime: 0, frame: 0, resolution: [0, 0], targetHalf: 0, halfStoreRTZ: halfStoreRTZ === false ? 0 : 1
+		}
+		this.frame = null
+		this.resolution = null
+		this._updates = 0
+		this._traa = null
+		this.makeOptionsReactive(options)
+	}
+	makeOptionsReactive(options) {
+		for (const key of Object.keys(options)) {
+			Object.defineProperty(this, key, {
+				get() {
+					return options[key]
+				},
+				set(value) {
+					options[key] = value
+					if (key === "intensity" || key === "jitter") this.uniforms[key] = value
+				}
+			})
+			this[key] = options[key]
+		}
+	}
+	shareEffectPass(traaEffect) {
+		this._traa = traaEffect || null
+	}
+	update(renderer, inputBuffer, deltaTime) {
+		const u = this.uniforms
+		u.deltaTime = Math.max(1 / 1000, deltaTime) // :89
+		u.frame = (this.frame === null ? this._updates : this.frame) % 4096 // :91
+		this._updates++
+		const res = this.resolution || [renderer.width, renderer.height] // :94
+		u.resolution = [res[0], res[1]]
+		let half = false
+		if (this._traa) {
+			const tp = this._traa.temporalReprojectPass
+			u.source = TEX.SSGI
+			u.center = this._traa.uniforms.accumulatedTexture
+			u.centerAlphaOne = 1
+			half = !!tp && tp.targetType === HalfFloatType
+		} else if (typeof inputBuffer === "number") {
+			u.source = inputBuffer
+			u.center = -1
+			u.centerAlphaOne = inputBuffer === TEX.TEMPORAL0 ? 1 : 0 // traa_compose.frag:6 wrote alpha 1 into that buffer
+		} else {
+			let data = inputBuffer.data !== undefined ? inputBuffer.data : inputBuffer
+			half = !!inputBuffer.texture && textureType(inputBuffer.texture) === HalfFloatType
+			if (half) data = toHalfPrecision(data) // a HalfFloatType buffer holds half-precision texels
+			else if (!(data instanceof Float32Array)) data = Float32Array.from(data)
+			renderer.upload(TEX.EFFECT_INPUT, data, 0, renderer.height)
+			u.source = TEX.EFFECT_INPUT
+			u.center = -1
+			u.centerAlphaOne = 0
+		}
+		u.targetHalf = half ? 1 : 0
+	}
+	// the effect's fragment (motion_blur.frag mainImage) -> TEX.MOTION_BLUR
+	mainImage(renderer) {
+		renderer.motionBlur(this.uniforms)
+		return TEX.MOTION_BLUR
+	}
+	output(renderer, row0, rows) {
+		return renderer.download(TEX.MOTION_BLUR, row0, rows)
+	}
+	dispose() {}
+}
+
 module.exports = {
 	SSGIEffect,
 	CubeToEquirectEnvPass,
@@ -850,6 +932,8 @@ module.exports = {
 	LinearMipmapLinearFilter,
 	SSREffect,
 	TRAAEffect,
+	MotionBlurEffect,
+	defaultMotionBlurOptions,
 	VelocityDepthNormalPass,
 	TemporalReprojectPass,
 	PoissonDenoisePass,

@@ -15,6 +15,9 @@
 // ncclUniqueId and hands it over through a file.  The parent stitches the tiles: the outputs are bit-identical to a --ranks 1 run.
 // --historyGather '"all"' (default) | '"bounded"' | '"peer"': how next frame's K1 gets the composed GI of the other tiles (js/tiling.js); "peer"
 // moves no collective at all — each rank's kernel loads what its rays read through HIP IPC mappings (the blobs travel through files too).
+// --motionBlur '{"intensity":1,"jitter":1,"samples":16}' [--deltaTime X] (default 1/60): MotionBlurEffect after every frame — on the device,
+// after SSGIEffect's final image, or with --traa in the README form EffectPass(camera, traaEffect, motionBlurEffect); writes motion_blur.bin
+// of the last frame, and --png / --exr / --pfm write the blurred frame instead of final.bin.  Whole-frame runs only.
 const fs = require("fs")
 const path = require("path")
 const rfx = require("./index")
@@ -83,6 +86,19 @@ const stream = !!opt.stream
 delete opt.stream
 const images = { png: opt.png, exr: opt.exr, pfm: opt.pfm, tonemap: opt.tonemap, exposure: opt.exposure }
 for (const k of Object.keys(images)) delete opt[k]
+const motionBlur = opt.motionBlur
+const deltaTime = opt.deltaTime === undefined ? 1 / 60 : opt.deltaTime
+delete opt.motionBlur
+delete opt.deltaTime
+if (motionBlur && tiled) throw new Error("--motionBlur needs a whole-frame run (a streak can reach anywhere): drop --ranks")
+// the blurred frame of the last step -> motion_blur.bin (and the images)
+function writeMotionBlur(mb) {
+	const a = mb.output(renderer)
+	fs.writeFileSync(path.join(out, "motion_blur.bin"), Buffer.from(a.buffer, a.byteOffset, a.byteLength))
+	if (images.exr) rfx.writeEXR(images.exr, a, first.width, first.height)
+	if (images.pfm) rfx.writePFM(images.pfm, a, first.width, first.height)
+	if (images.png) rfx.writePNG(images.png, rfx.tonemap(a, first.width, first.height, images.tonemap, images.exposure), first.width, first.height, 3)
+}
 const seeds = { ssgi: opt.ssgiSeed === undefined ? 11 : opt.ssgiSeed, denoise: opt.denoiseSeed === undefined ? 22 : opt.denoiseSeed }
 delete opt.ssgiSeed
 delete opt.denoiseSeed
@@ -151,21 +167,37 @@ if (tiled) {
 if (opt.uvModel) (renderer.inner || renderer).setUvModel(opt.uvModel)
 if (opt.traa) {
 	const half = opt.traa === "half"
-	const traa = new rfx.TRAAEffect(scene, camera, new rfx.VelocityDepthNormalPass(scene, camera), { fullAccumulate: true }, true)
+	const velocityPass = new rfx.VelocityDepthNormalPass(scene, camera)
+	const traa = new rfx.TRAAEffect(scene, camera, velocityPass, { fullAccumulate: true }, true)
+	const mb = motionBlur ? new rfx.MotionBlurEffect(velocityPass, motionBlur, true) : null
+	if (mb) mb.shareEffectPass(traa)
 	for (const d of dumps) {
 		const f = d === dumps[0] ? first : rfx.readDump(d)
 		scene.frame = f
 		Object.assign(camera, f.camera)
 		traa.update(renderer, { texture: { type: half ? rfx.HalfFloatType : rfx.FloatType }, width: f.width, height: f.height, data: f.direct })
+		if (mb) {
+			mb.update(renderer, null, deltaTime)
+			mb.mainImage(renderer)
+		}
 	}
 	renderer.sync()
 	fs.mkdirSync(out, { recursive: true })
 	const a = traa.output(renderer)
 	fs.writeFileSync(path.join(out, "traa.bin"), Buffer.from(a.buffer, a.byteOffset, a.byteLength))
+	if (mb) writeMotionBlur(mb)
 	console.log(JSON.stringify({ frames: dumps.length, width: first.width, height: first.height, haloViolations: renderer.haloViolations() }))
 	process.exit(0)
 }
 const effect = new rfx.SSGIEffect(null, scene, camera, Object.assign({ width: first.width, height: first.height }, opt), seeds, true)
+const mb = motionBlur ? new rfx.MotionBlurEffect(new rfx.VelocityDepthNormalPass(scene, camera), motionBlur, true) : null
+// MotionBlurEffect in the pass after SSGIEffect: its input buffer is the effect's final image, on the device
+function blurFrame() {
+	if (!mb) return
+	effect.mainImage(renderer)
+	mb.update(renderer, rfx.TEX.FINAL, deltaTime)
+	mb.mainImage(renderer)
+}
 if (stream && !tiled) {
 	if (!first.gbuffer) throw new Error("--stream needs packed gbuffer.bin / velocity.bin dumps")
 	const n = first.width * first.height
@@ -185,6 +217,7 @@ if (stream && !tiled) {
 		scene.frame = cur
 		Object.assign(camera, cur.camera)
 		effect.update(renderer, null) // ... while frame i is drawn
+		blurFrame()
 		renderer.stageFlip()
 		cur = next
 	}
@@ -194,6 +227,7 @@ if (stream && !tiled) {
 		scene.frame = f
 		Object.assign(camera, f.camera)
 		effect.update(renderer, null)
+		blurFrame()
 	}
 renderer.sync()
 fs.mkdirSync(out, { recursive: true })
@@ -204,7 +238,8 @@ for (const [name, tex] of [["final", T.FINAL], ["compose", T.COMPOSE], ["denoise
 	const a = tiled ? renderer.download(tex, renderer.tileY0, renderer.tileRows) : renderer.download(tex)
 	fs.writeFileSync(path.join(out, name + (tiled ? ".rank" + tiled.rank : "") + ".bin"), Buffer.from(a.buffer, a.byteOffset, a.byteLength))
 }
-if (!tiled && (images.png || images.exr || images.pfm)) {
+if (mb) writeMotionBlur(mb)
+else if (!tiled && (images.png || images.exr || images.pfm)) {
 	const fin = renderer.download(T.FINAL)
 	if (images.exr) rfx.writeEXR(images.exr, fin, first.width, first.height)
 	if (images.pfm) rfx.writePFM(images.pfm, fin, first.width, first.height)

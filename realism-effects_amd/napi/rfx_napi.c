@@ -712,6 +712,31 @@ static napi_value n_final(napi_env env, napi_callback_info info) {
     return NULL;
 }
 
+/* motionBlur(ctx, {source, center, centerAlphaOne, samples, intensity, jitter, deltaTime, frame, resolution[2], targetHalf, halfStoreRTZ})
+ * — MotionBlurEffect's fragment (K6, rfx_motion_blur) -> RFX_TEX_MOTION_BLUR */
+static napi_value n_motion_blur(napi_env env, napi_callback_info info) {
+    napi_value a[2];
+    if (!get_args(env, info, 2, a)) return NULL;
+    rfx_ctx *c = get_ctx(env, a[0]);
+    if (!c) return NULL;
+    rfx_motion_blur_params p;
+    memset(&p, 0, sizeof p);
+    p.source = (int32_t)prop_num(env, a[1], "source", RFX_TEX_FINAL);
+    p.center = (int32_t)prop_num(env, a[1], "center", -1);
+    p.centerAlphaOne = (int32_t)prop_num(env, a[1], "centerAlphaOne", 0);
+    p.samples = (int32_t)prop_num(env, a[1], "samples", 16);
+    p.intensity = (float)prop_num(env, a[1], "intensity", 1);
+    p.jitter = (float)prop_num(env, a[1], "jitter", 1);
+    p.deltaTime = (float)prop_num(env, a[1], "deltaTime", 0);
+    p.frame = (int32_t)prop_num(env, a[1], "frame", 0);
+    if (!prop_floats(env, a[1], "resolution", p.resolution, 2)) { napi_throw_type_error(env, NULL, "motionBlur: resolution must hold 2 numbers"); return NULL; }
+    p.targetHalf = (int32_t)prop_num(env, a[1], "targetHalf", 0);
+    p.halfStoreRTZ = (int32_t)prop_num(env, a[1], "halfStoreRTZ", 1);
+    int rc = rfx_motion_blur(c, &p);
+    if (rc) return throw_rfx(env, c, "rfx_motion_blur", rc);
+    return NULL;
+}
+
 static napi_value n_sync(napi_env env, napi_callback_info info) {
     napi_value a[1];
     if (!get_args(env, info, 1, a)) return NULL;
@@ -792,7 +817,7 @@ static napi_value n_profile_read(napi_env env, napi_callback_info info) {
 static napi_value init(napi_env env, napi_value exports) {
     static const struct { const char *name; napi_callback fn; } fns[] = {
         {"abiVersion", n_abi_version}, {"create", n_create}, {"heldRows", n_held_rows}, {"upload", n_upload}, {"download", n_download},
-        {"clear", n_clear}, {"setEnvironment", n_set_environment}, {"setEnvironmentImportance", n_set_environment_importance}, {"packGBuffer", n_pack_gbuffer}, {"packVelocity", n_pack_velocity}, {"ssgiMarch", n_ssgi}, {"ssgiTrace", n_ssgi_trace}, {"ssgiShade", n_ssgi_shade}, {"temporalReproject", n_temporal}, {"copyFramebuffer", n_copy_framebuffer}, {"poissonDenoise", n_denoise}, {"compose", n_compose}, {"finalCompose", n_final},
+        {"clear", n_clear}, {"setEnvironment", n_set_environment}, {"setEnvironmentImportance", n_set_environment_importance}, {"packGBuffer", n_pack_gbuffer}, {"packVelocity", n_pack_velocity}, {"ssgiMarch", n_ssgi}, {"ssgiTrace", n_ssgi_trace}, {"ssgiShade", n_ssgi_shade}, {"temporalReproject", n_temporal}, {"copyFramebuffer", n_copy_framebuffer}, {"poissonDenoise", n_denoise}, {"compose", n_compose}, {"finalCompose", n_final}, {"motionBlur", n_motion_blur},
         {"sync", n_sync}, {"setRowWindow", n_set_row_window}, {"setUvModel", n_set_uv_model}, {"cubeToEquirect", n_cube_to_equirect}, {"haloViolations", n_halo_violations}, {"timeBegin", n_time_begin}, {"timeEnd", n_time_end}, {"profile", n_profile}, {"profileRead", n_profile_read},
         {"stageUpload", n_stage_upload}, {"stageFlip", n_stage_flip}, {"hostAlloc", n_host_alloc},
         {"splitRows", n_split_rows}, {"commUniqueId", n_comm_unique_id}, {"commInit", n_comm_init}, {"haloExchange", n_halo_exchange},

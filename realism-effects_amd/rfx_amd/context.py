@@ -254,6 +254,10 @@ class Context:
     def final_compose(self, p: abi.FinalParams):
         self._chk(self.lib.rfx_final_compose(self._h, C.byref(p)), "rfx_final_compose")
 
+    def motion_blur(self, p: abi.MotionBlurParams):
+        """MotionBlurEffect's mainImage (K6, include/rfx.h rfx_motion_blur) -> abi.TEX_MOTION_BLUR"""
+        self._chk(self.lib.rfx_motion_blur(self._h, C.byref(p)), "rfx_motion_blur")
+
     def sync(self):
         self._chk(self.lib.rfx_sync(self._h), "rfx_sync")
 

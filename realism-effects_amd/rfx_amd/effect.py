@@ -739,3 +739,97 @@ class TRAAEffect:
         t = renderer.download(self.uniforms["accumulatedTexture"], row0, rows).copy()
         t[..., 3] = 1.0
         return t
+
+
+# src/motion-blur/MotionBlurEffect.js:14
+defaultMotionBlurOptions = dict(intensity=1, jitter=1, samples=16)
+
+
+class MotionBlurEffect:
+    """src/motion-blur/MotionBlurEffect.js:16-101 (K6, rfx_motion_blur).  `velocityPass` is the VelocityDepthNormalPass whose plane
+    (RFX_TEX_VELOCITY) the effect reads.  `samples` is a define fixed at construction: the reactive setters forward only `intensity` and
+    `jitter` (:42-45,51-66) — setting `samples` later is stored and never drawn with, as in the reference.
+
+    update(renderer, inputBuffer, deltaTime): `inputBuffer` is a slot id (abi.TEX_FINAL after SSGIEffect.mainImage: the blur stays on the
+    device; abi.TEX_TEMPORAL0 stands for the buffer TRAA's own EffectPass wrote, alpha 1) or a host buffer like TRAAEffect's (an array, or an object / dict with `data` and optionally `texture` carrying three's `type`),
+    uploaded to RFX_TEX_EFFECT_INPUT.  `frame` (renderer.info.render.frame % 4096, :91) defaults to the number of updates so far modulo 4096
+    and `resolution` (window.innerWidth / innerHeight, :94) to the frame size; both are settable.  shareEffectPass(traaEffect) draws the
+    README form EffectPass(camera, traaEffect, motionBlurEffect): inputColor is TRAA's output (its NEAREST target, alpha 1) and the taps read
+    the pass's input buffer, the plane TRAA drew from (RFX_TEX_SSGI)."""
+
+    def __init__(self, velocityPass, options=None, half_store_rtz=True):
+        o = dict(defaultMotionBlurOptions)
+        o.update(options if options is not None else defaultMotionBlurOptions)
+        self.velocityPass = velocityPass
+        self._options = o
+        self._half_store_rtz = half_store_rtz
+        self.uniforms = abi.MotionBlurParams()
+        u = self.uniforms
+        u.source, u.center, u.centerAlphaOne = abi.TEX_FINAL, -1, 0
+        u.samples = int(round(float(o["samples"])))  # options.samples.toFixed(0) (:37-40)
+        u.intensity, u.jitter = 1.0, 1.0  # the uniforms' initial values (:31-32), then makeOptionsReactive sets both (:64)
+        u.halfStoreRTZ = 1 if half_store_rtz else 0
+        for key in o:  # makeOptionsReactive (:51-66): `this[key] = options[key]`
+            setattr(self, key, o[key])
+        self.frame = None
+        self.resolution = None
+        self._updates = 0
+        self._traa = None
+
+    def __setattr__(self, key, value):
+        if key in ("intensity", "jitter", "samples") and "_options" in self.__dict__:
+            self._options[key] = value
+            if key in ("intensity", "jitter"):
+                setattr(self.uniforms, key, float(value))
+            return
+        object.__setattr__(self, key, value)
+
+    def __getattr__(self, key):
+        if key in ("intensity", "jitter", "samples"):
+            return self.__dict__["_options"][key]
+        raise AttributeError(key)
+
+    def shareEffectPass(self, traaEffect):
+        """draw as the second effect of EffectPass(camera, traaEffect, motionBlurEffect) (readme.md:60-79); None: the effect's own pass"""
+        self._traa = traaEffect
+
+    def update(self, renderer, inputBuffer, deltaTime):
+        u = self.uniforms
+        u.deltaTime = max(1 / 1000, float(deltaTime))  # :89
+        u.frame = int(self._updates if self.frame is None else self.frame) % 4096  # :91
+        self._updates += 1
+        res = (renderer.W, renderer.H) if self.resolution is None else self.resolution  # :94
+        u.resolution[:] = [float(res[0]), float(res[1])]
+        half = False
+        if self._traa is not None:  # README form: TRAA's target is the centre, its input plane (RFX_TEX_SSGI) the taps' buffer
+            tp = self._traa.temporalReprojectPass
+            u.source, u.center, u.centerAlphaOne = abi.TEX_SSGI, self._traa.uniforms["accumulatedTexture"], 1
+            half = tp is not None and tp.targetType == HalfFloatType
+        elif isinstance(inputBuffer, (int, np.integer)):
+            # abi.TEX_TEMPORAL0 stands for the buffer TRAA's own EffectPass wrote: traa_compose.frag:6 gave it alpha 1
+            u.source, u.center, u.centerAlphaOne = int(inputBuffer), -1, int(int(inputBuffer) == abi.TEX_TEMPORAL0)
+        else:
+            data = inputBuffer
+            tex = None
+            if isinstance(inputBuffer, dict):
+                data, tex = inputBuffer["data"], inputBuffer.get("texture")
+            elif hasattr(inputBuffer, "data") and not isinstance(inputBuffer, np.ndarray):
+                data, tex = inputBuffer.data, getattr(inputBuffer, "texture", None)
+            half = tex is not None and _texture_type(tex) == HalfFloatType
+            data = np.asarray(data, np.float32)
+            if half:  # a HalfFloatType buffer holds half-precision texels
+                data = data.astype(np.float16).astype(np.float32)
+            renderer.upload(abi.TEX_EFFECT_INPUT, np.ascontiguousarray(data, np.float32))
+            u.source, u.center, u.centerAlphaOne = abi.TEX_EFFECT_INPUT, -1, 0
+        u.targetHalf = 1 if half else 0
+
+    def mainImage(self, renderer):
+        """the effect's fragment (motion_blur.frag mainImage) -> RFX_TEX_MOTION_BLUR"""
+        renderer.motion_blur(self.uniforms)
+        return abi.TEX_MOTION_BLUR
+
+    def output(self, renderer, row0=None, rows=None):
+        return renderer.download(abi.TEX_MOTION_BLUR, row0, rows)
+
+    def dispose(self):
+        pass
