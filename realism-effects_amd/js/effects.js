@@ -81,18 +81,89 @@ const defaultDenosierOptions = {
 const INPUT_TYPES = ["diffuseSpecular", "diffuse", "specular"]
 const highestSignedInt = 0x7fffffff
 
+// ---- saved temporal state (state.js; Python twin: rfx_amd/effect.py + rfx_amd/state.py).  Every float is kept as the hex of its
+// little-endian IEEE bytes: bit for bit, and the same text from both hosts.
+class StateError extends Error {
+	constructor(field, message) {
+		super(field + ": " + message)
+		this.name = "StateError"
+		this.field = field
+	}
+}
+function hex32(values) {
+	const a = Float32Array.from(values)
+	return Buffer.from(a.buffer, a.byteOffset, a.byteLength).toString("hex")
+}
+function hex64(values) {
+	const a = Float64Array.from(values)
+	return Buffer.from(a.buffer, a.byteOffset, a.byteLength).toString("hex")
+}
+function unhex(text, Ctor, count, field) {
+	if (typeof text !== "string" || !/^([0-9a-fA-F]{2})*$/.test(text)) throw new StateError(field, "not the hex of " + Ctor.name + " values")
+	if (text.length !== 2 * count * Ctor.BYTES_PER_ELEMENT) throw new StateError(field, text.length / 2 / Ctor.BYTES_PER_ELEMENT + " values, expected " + count)
+	const b = Buffer.from(text, "hex")
+	return new Ctor(b.buffer.slice(b.byteOffset, b.byteOffset + b.length))
+}
+function stateInt(s, key, field, allowNull) {
+	const v = s && typeof s === "object" ? s[key] : undefined
+	if (v === null && allowNull) return null
+	if (!Number.isInteger(v)) throw new StateError(field + "." + key, "an integer is expected, got " + JSON.stringify(v))
+	return v
+}
+function stateDict(s, key, field) {
+	const v = s && typeof s === "object" ? s[key] : undefined
+	if (!v || typeof v !== "object" || Array.isArray(v)) throw new StateError(field + "." + key, "missing")
+	return v
+}
+const CAMERA_FIELDS = [["projectionMatrix", 16], ["projectionMatrixInverse", 16], ["matrixWorld", 16], ["matrixWorldInverse", 16], ["position", 3]]
+// a cloned camera (what the device is handed: float32) as saved state
+function cameraState(c) {
+	const s = {}
+	for (const f of CAMERA_FIELDS) s[f[0]] = hex32(c[f[0]])
+	s.near = hex32([c.near])
+	s.far = hex32([c.far])
+	s.isPerspective = c.isPerspectiveCamera === undefined || c.isPerspectiveCamera ? 1 : 0
+	return s
+}
+function cameraFromState(s, field) {
+	if (!s || typeof s !== "object") throw new StateError(field, "missing")
+	const c = {}
+	for (const f of CAMERA_FIELDS) c[f[0]] = unhex(s[f[0]], Float32Array, f[1], field + "." + f[0])
+	c.near = unhex(s.near, Float32Array, 1, field + ".near")[0]
+	c.far = unhex(s.far, Float32Array, 1, field + ".far")[0]
+	c.isPerspectiveCamera = stateInt(s, "isPerspective", field) !== 0
+	return c
+}
+function checkClass(effect, s, field) {
+	if (!s || s.class !== effect.constructor.name)
+		throw new StateError(field + ".class", "saved " + JSON.stringify(s && s.class) + ", the running effect is " + JSON.stringify(effect.constructor.name))
+}
+
 // src/utils/BlueNoiseUtils.js:17-33 — the uniform is a getter: every read (one per draw) advances the index
 function makeBlueNoiseIndex(startIndex) {
 	let blueNoiseIndex = 0
 	if (startIndex === undefined || startIndex === null) startIndex = Math.floor(Math.random() * highestSignedInt)
 	return {
-		startIndex,
 		get value() {
 			blueNoiseIndex = (startIndex + blueNoiseIndex + 1) % highestSignedInt
 			return blueNoiseIndex
 		},
 		set value(v) {
 			blueNoiseIndex = v
+		},
+		get startIndex() {
+			return startIndex
+		},
+		getState() {
+			return { startIndex, index: blueNoiseIndex }
+		},
+		checkState(s, field) {
+			stateInt(s, "startIndex", field)
+			stateInt(s, "index", field)
+		},
+		setState(s) {
+			startIndex = s.startIndex
+			blueNoiseIndex = s.index
 		}
 	}
 }
@@ -298,6 +369,43 @@ class TemporalReprojectPass {
 		}
 		this.uniforms.prevCamera = cloneCamera(cam.unjittered || cam) // :203-213
 	}
+	// -- saved temporal state (state.js): the slots a later frame reads before writing, or leaves partly unwritten (K2 discards background texels)
+	stateSlots() {
+		const slots = this.textureCount === 2 ? [TEX.TEMPORAL0, TEX.TEMPORAL1] : [TEX.TEMPORAL0]
+		if (this.overrideAccumulatedTextures.length === 0) slots.push(this.framebufferTexture)
+		return slots
+	}
+	getState() {
+		return {
+			frame: this.frame,
+			textureCount: this.textureCount,
+			targetType: this.targetType,
+			keepData: hex32([this.uniforms.keepData]),
+			prevCamera: cameraState(this.uniforms.prevCamera),
+			lastCameraTransform: { position: hex64(this.lastCameraTransform.position), quaternion: hex64(this.lastCameraTransform.quaternion) }
+		}
+	}
+	checkState(s, field) {
+		if (stateInt(s, "textureCount", field) !== this.textureCount)
+			throw new StateError(field + ".textureCount", "saved " + s.textureCount + ", the running pass has " + this.textureCount)
+		if (stateInt(s, "targetType", field) !== this.targetType)
+			throw new StateError(field + ".targetType", "saved " + s.targetType + ", the running pass has " + this.targetType + " (FloatType " + FloatType + ", HalfFloatType " + HalfFloatType + ")")
+		stateInt(s, "frame", field)
+		unhex(s.keepData, Float32Array, 1, field + ".keepData")
+		cameraFromState(s.prevCamera, field + ".prevCamera")
+		const t = stateDict(s, "lastCameraTransform", field)
+		unhex(t.position, Float64Array, 3, field + ".lastCameraTransform.position")
+		unhex(t.quaternion, Float64Array, 4, field + ".lastCameraTransform.quaternion")
+	}
+	setState(s) {
+		this.frame = s.frame
+		this.uniforms.keepData = unhex(s.keepData, Float32Array, 1, "keepData")[0]
+		this.uniforms.prevCamera = cameraFromState(s.prevCamera, "prevCamera")
+		this.lastCameraTransform = {
+			position: Array.from(unhex(s.lastCameraTransform.position, Float64Array, 3, "position")),
+			quaternion: Array.from(unhex(s.lastCameraTransform.quaternion, Float64Array, 4, "quaternion"))
+		}
+	}
 	jitter(jitterScale) {
 		this.unjitter() // :216-220
 		return jitter(this.width, this.height, this._camera, this.frame, jitterScale)
@@ -352,6 +460,21 @@ class PoissonDenoisePass {
 			renderer.poissonDenoise(this.uniforms)
 			if (renderer.afterDenoisePass) renderer.afterDenoisePass(i, this.uniforms)
 		}
+	}
+	// -- saved temporal state (state.js): both ping-pong targets — K3 discards background texels, which keep what the target held; B is also K2's history
+	stateSlots() {
+		return this.uniforms.textureCount === 2 ? [TEX.DENOISE_A0, TEX.DENOISE_A1, TEX.DENOISE_B0, TEX.DENOISE_B1] : [TEX.DENOISE_A0, TEX.DENOISE_B0]
+	}
+	getState() {
+		return { textureCount: this.uniforms.textureCount, blueNoiseIndex: this.blueNoiseIndex.getState() }
+	}
+	checkState(s, field) {
+		if (stateInt(s, "textureCount", field) !== this.uniforms.textureCount)
+			throw new StateError(field + ".textureCount", "saved " + s.textureCount + ", the running pass has " + this.uniforms.textureCount)
+		this.blueNoiseIndex.checkState(stateDict(s, "blueNoiseIndex", field), field + ".blueNoiseIndex")
+	}
+	setState(s) {
+		this.blueNoiseIndex.setState(s.blueNoiseIndex)
 	}
 	dispose() {}
 }
@@ -429,6 +552,30 @@ class Denoiser {
 	reset() {
 		this.temporalReprojectPass.reset()
 	}
+	// -- saved temporal state (state.js)
+	stateSlots() {
+		let slots = this.temporalReprojectPass.stateSlots()
+		if (this.denoisePass) slots = slots.concat(this.denoisePass.stateSlots())
+		if (this.denoiserComposePass) slots.push(this.denoiserComposePass.texture) // K1's history; K4 discards background texels
+		return slots
+	}
+	getState() {
+		return {
+			denoiseMode: this.options.denoiseMode,
+			temporalReprojectPass: this.temporalReprojectPass.getState(),
+			denoisePass: this.denoisePass ? this.denoisePass.getState() : null
+		}
+	}
+	checkState(s, field) {
+		if (s.denoiseMode !== this.options.denoiseMode)
+			throw new StateError(field + ".denoiseMode", "saved " + JSON.stringify(s.denoiseMode) + ", the running effect has " + JSON.stringify(this.options.denoiseMode))
+		this.temporalReprojectPass.checkState(stateDict(s, "temporalReprojectPass", field), field + ".temporalReprojectPass")
+		if (this.denoisePass) this.denoisePass.checkState(stateDict(s, "denoisePass", field), field + ".denoisePass")
+	}
+	setState(s) {
+		this.temporalReprojectPass.setState(s.temporalReprojectPass)
+		if (this.denoisePass) this.denoisePass.setState(s.denoisePass)
+	}
 	setSize(width, height) {
 		for (const p of [this.velocityDepthNormalPass, this.temporalReprojectPass, this.denoisePass, this.denoiserComposePass])
 			if (p) p.setSize(width, height)
@@ -496,6 +643,18 @@ class SSGIPass {
 			renderer.beforeSsgiShade()
 			renderer.ssgiShade(this.uniforms)
 		} else renderer.ssgiMarch(this.uniforms) // :93-94
+	}
+	// -- saved temporal state (state.js); K1 writes every texel of its target, so the pass keeps no slot
+	getState() {
+		return { frame: this.frame, blueNoiseIndex: this.blueNoiseIndex.getState() }
+	}
+	checkState(s, field) {
+		stateInt(s, "frame", field)
+		this.blueNoiseIndex.checkState(stateDict(s, "blueNoiseIndex", field), field + ".blueNoiseIndex")
+	}
+	setState(s) {
+		this.frame = s.frame
+		this.blueNoiseIndex.setState(s.blueNoiseIndex)
 	}
 	dispose() {}
 }
@@ -598,6 +757,40 @@ class SSGIEffect {
 
 	reset() {
 		this.denoiser.reset()
+	}
+
+	// -- saved temporal state (state.js).  Options that are plain uniforms (radius, phi, steps, ...) are not part of it: they may be changed
+	// between frames, as in the reference.  The environment and its importance tables are inputs: the caller sets scene.environment again
+	// and the first update() after setState() hands it to the device WITHOUT the reset of :356.
+	stateSlots() {
+		return this.denoiser.stateSlots()
+	}
+	getState() {
+		return {
+			class: this.constructor.name,
+			resolutionScale: hex64([this._options.resolutionScale]),
+			ssgiPass: this.ssgiPass.getState(),
+			denoiser: this.denoiser.getState(),
+			finalCamera: cameraState(this.uniforms.camera),
+			useEnvMap: this.ssgiPass.uniforms.useEnvMap ? 1 : 0
+		}
+	}
+	checkState(s, field) {
+		field = field || "effect"
+		checkClass(this, s, field)
+		const scale = unhex(s.resolutionScale, Float64Array, 1, field + ".resolutionScale")[0]
+		if (scale !== Number(this._options.resolutionScale))
+			throw new StateError(field + ".resolutionScale", "saved " + scale + ", the running effect has " + this._options.resolutionScale)
+		this.denoiser.checkState(stateDict(s, "denoiser", field), field + ".denoiser")
+		this.ssgiPass.checkState(stateDict(s, "ssgiPass", field), field + ".ssgiPass")
+		cameraFromState(s.finalCamera, field + ".finalCamera")
+		stateInt(s, "useEnvMap", field)
+	}
+	setState(s) {
+		this.ssgiPass.setState(s.ssgiPass)
+		this.denoiser.setState(s.denoiser)
+		this.uniforms.camera = cameraFromState(s.finalCamera, "finalCamera")
+		this._envRestored = !!s.useEnvMap
 	}
 
 	// :157-268
@@ -725,7 +918,8 @@ class SSGIEffect {
 				}
 				this._envUuid = env
 				u.useEnvMap = 1 // defines.USE_ENVMAP :344
-				this.reset() // :356
+				if (this._envRestored) this._envRestored = false // (setState: the map returns to a fresh device, the accumulation goes on)
+				else this.reset() // :356
 			}
 		} else if (u.useEnvMap) {
 			u.useEnvMap = 0 // :361-366
@@ -830,6 +1024,57 @@ class TRAAEffect {
 		this.temporalReprojectPass.jitter()
 		this.temporalReprojectPass.render(renderer) // :75
 	}
+	// -- saved temporal state (state.js).  The pass is built by the first update(), from the composer buffer's type: a state saved after
+	// that builds it in a fresh effect (same type, same size); a state saved before it holds no pass.
+	stateSlots() {
+		return this.temporalReprojectPass ? this.temporalReprojectPass.stateSlots() : []
+	}
+	// the slots this effect keeps once setState(s) has run
+	stateSlotsOf(s) {
+		const t = s.temporalReprojectPass
+		return t ? [TEX.TEMPORAL0, t.targetType === HalfFloatType ? TEX.FBCOPY_F16 : TEX.FBCOPY_F32] : []
+	}
+	getState() {
+		const tp = this.temporalReprojectPass
+		const m = this.unjitteredProjectionMatrix
+		return {
+			class: this.constructor.name,
+			temporalReprojectPass: tp ? Object.assign(tp.getState(), { width: tp.width, height: tp.height }) : null,
+			unjitteredProjectionMatrix: m ? hex64(m) : null
+		}
+	}
+	checkState(s, field) {
+		field = field || "effect"
+		checkClass(this, s, field)
+		const t = s.temporalReprojectPass
+		const f = field + ".temporalReprojectPass"
+		if (t !== null && t !== undefined) {
+			if (typeof t !== "object" || (t.targetType !== FloatType && t.targetType !== HalfFloatType))
+				throw new StateError(f + ".targetType", "FloatType (" + FloatType + ") or HalfFloatType (" + HalfFloatType + ") is expected")
+			const tp = this.temporalReprojectPass || new TemporalReprojectPass(this._scene, this._camera, this.velocityDepthNormalPass, { type: t.targetType }, 1, this.options, this._halfStoreRTZ)
+			tp.checkState(t, f)
+			stateInt(t, "width", f)
+			stateInt(t, "height", f)
+		}
+		if (s.unjitteredProjectionMatrix !== null && s.unjitteredProjectionMatrix !== undefined)
+			unhex(s.unjitteredProjectionMatrix, Float64Array, 16, field + ".unjitteredProjectionMatrix")
+	}
+	setState(s) {
+		const t = s.temporalReprojectPass
+		if (!t) {
+			this.temporalReprojectPass = null
+			this.uniforms.accumulatedTexture = null
+		} else {
+			if (!this.temporalReprojectPass) {
+				this.temporalParams({ type: t.targetType }) // :53-66, from the saved type instead of the first input buffer's
+				this.uniforms.accumulatedTexture = this.temporalReprojectPass.texture
+			}
+			this.temporalReprojectPass.setSize(t.width, t.height)
+			this.temporalReprojectPass.setState(t)
+		}
+		const m = s.unjitteredProjectionMatrix
+		this.unjitteredProjectionMatrix = m ? Array.from(unhex(m, Float64Array, 16, "unjitteredProjectionMatrix")) : null
+	}
 	// traa_compose.frag:3-7 — outputColor = vec4(accumulatedTexel.rgb, 1.)
 	output(renderer, row0, rows) {
 		const t = renderer.download(this.uniforms.accumulatedTexture, row0, rows)
@@ -913,6 +1158,23 @@ class MotionBlurEffect {
 		}
 		u.targetHalf = half ? 1 : 0
 	}
+	// -- saved temporal state (state.js): the frame counter behind the jitter; K6 writes every texel, so the effect keeps no slot
+	stateSlots() {
+		return []
+	}
+	getState() {
+		return { class: this.constructor.name, frame: this.frame === null || this.frame === undefined ? null : this.frame, updates: this._updates }
+	}
+	checkState(s, field) {
+		field = field || "effect"
+		checkClass(this, s, field)
+		stateInt(s, "frame", field, true)
+		stateInt(s, "updates", field)
+	}
+	setState(s) {
+		this.frame = s.frame
+		this._updates = s.updates
+	}
 	// the effect's fragment (motion_blur.frag mainImage) -> TEX.MOTION_BLUR
 	mainImage(renderer) {
 		renderer.motionBlur(this.uniforms)
@@ -951,5 +1213,6 @@ module.exports = {
 	r2Sequence,
 	jitter,
 	makeBlueNoiseIndex,
-	didCameraMove
+	didCameraMove,
+	StateError
 }

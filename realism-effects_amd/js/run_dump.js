@@ -18,6 +18,10 @@
 // --motionBlur '{"intensity":1,"jitter":1,"samples":16}' [--deltaTime X] (default 1/60): MotionBlurEffect after every frame — on the device,
 // after SSGIEffect's final image, or with --traa in the README form EffectPass(camera, traaEffect, motionBlurEffect); writes motion_blur.bin
 // of the last frame, and --png / --exr / --pfm write the blurred frame instead of final.bin.  Whole-frame runs only.
+// --saveState DIR [--saveEvery N]: write a checkpoint of the temporal state (js/state.js) into DIR after every N-th frame and after the last;
+// --loadState DIR: restore one first — the dump directories given are then the REMAINING frames, and the outputs are byte-identical to an
+// uninterrupted run.  Both work with --ranks (every rank writes its rows of the whole-frame planes; any rank count loads them), --traa,
+// --motionBlur and --stream (the save waits for the frame boundary).  A checkpoint written by the Python host loads here, and the reverse.
 const fs = require("fs")
 const path = require("path")
 const rfx = require("./index")
@@ -28,7 +32,12 @@ const opt = {}
 let out = "."
 for (let i = 0; i < args.length; i++) {
 	if (args[i] === "--out") out = args[++i]
-	else if (args[i].startsWith("--")) opt[args[i].slice(2)] = JSON.parse(args[++i])
+	else if (args[i] === "--saveState" || args[i] === "--loadState") {
+		// a directory, plain or JSON-quoted like the other path options
+		let v = args[i + 1]
+		try { v = JSON.parse(v) } catch (e) { /* plain */ }
+		opt[args[i++].slice(2)] = String(v)
+	} else if (args[i].startsWith("--")) opt[args[i].slice(2)] = JSON.parse(args[++i])
 	else dumps.push(args[i])
 }
 if (!dumps.length) {
@@ -44,7 +53,7 @@ if (opt.ranks > 1 && opt.rank === undefined) {
 	const idFile = path.join(idDir, "nccl_id")
 	const cleanup = () => {
 		try { fs.unlinkSync(idFile) } catch (e) { /* never written */ }
-		for (let r = 0; r < opt.ranks; r++) try { fs.unlinkSync(idFile + ".peer" + r) } catch (e) { /* not that mode */ }
+		try { for (const f of fs.readdirSync(idDir)) if (f.startsWith("nccl_id.peer")) fs.unlinkSync(path.join(idDir, f)) } catch (e) { /* not that mode */ }
 		try { fs.rmdirSync(idDir) } catch (e) { /* not empty: leave it */ }
 	}
 	const kids = []
@@ -86,6 +95,14 @@ const stream = !!opt.stream
 delete opt.stream
 const images = { png: opt.png, exr: opt.exr, pfm: opt.pfm, tonemap: opt.tonemap, exposure: opt.exposure }
 for (const k of Object.keys(images)) delete opt[k]
+const checkpoint = { save: opt.saveState, every: opt.saveEvery, load: opt.loadState }
+delete opt.saveState
+delete opt.saveEvery
+delete opt.loadState
+// after frame n of this run (1-based): every --saveEvery-th frame and the last
+function saveAfter(n, effects) {
+	if (checkpoint.save && ((checkpoint.every && n % checkpoint.every === 0) || n === dumps.length)) rfx.saveState(checkpoint.save, renderer, effects)
+}
 const motionBlur = opt.motionBlur
 const deltaTime = opt.deltaTime === undefined ? 1 / 60 : opt.deltaTime
 delete opt.motionBlur
@@ -154,12 +171,16 @@ if (tiled) {
 	renderer = new rfx.TiledRenderer(first.width, first.height, tiled.rank, tiled.ranks, halo, id,
 		{ device: process.env.RFX_ONE_GPU === "1" ? 0 : tiled.rank, historyGather: tiled.historyGather === "peer" ? "all" : tiled.historyGather })
 	// --historyGather '"peer"': the ranks' export blobs (192 plain bytes each) travel once, through files next to the id file
+	// (called again by a checkpoint, where the ranks only meet: every round has its own files)
+	let round = 0
 	if (tiled.historyGather === "peer")
 		renderer.usePeerHistory(blob => {
-			fs.writeFileSync(tiled.idFile + ".peer" + tiled.rank + ".tmp", blob)
-			fs.renameSync(tiled.idFile + ".peer" + tiled.rank + ".tmp", tiled.idFile + ".peer" + tiled.rank)
+			const base = tiled.idFile + ".peer" + (round ? "_" + round + "_" : "")
+			round++
+			fs.writeFileSync(base + tiled.rank + ".tmp", blob)
+			fs.renameSync(base + tiled.rank + ".tmp", base + tiled.rank)
 			const all = []
-			for (let r = 0; r < tiled.ranks; r++) all.push(waitFor(tiled.idFile + ".peer" + r, "peer blob of rank " + r))
+			for (let r = 0; r < tiled.ranks; r++) all.push(waitFor(base + r, "peer blob of rank " + r))
 			return all
 		})
 } else renderer = new rfx.Renderer(first.width, first.height)
@@ -171,7 +192,9 @@ if (opt.traa) {
 	const traa = new rfx.TRAAEffect(scene, camera, velocityPass, { fullAccumulate: true }, true)
 	const mb = motionBlur ? new rfx.MotionBlurEffect(velocityPass, motionBlur, true) : null
 	if (mb) mb.shareEffectPass(traa)
-	for (const d of dumps) {
+	const effects = mb ? [traa, mb] : [traa]
+	if (checkpoint.load) rfx.loadState(checkpoint.load, renderer, effects)
+	dumps.forEach((d, i) => {
 		const f = d === dumps[0] ? first : rfx.readDump(d)
 		scene.frame = f
 		Object.assign(camera, f.camera)
@@ -180,7 +203,8 @@ if (opt.traa) {
 			mb.update(renderer, null, deltaTime)
 			mb.mainImage(renderer)
 		}
-	}
+		saveAfter(i + 1, effects)
+	})
 	renderer.sync()
 	fs.mkdirSync(out, { recursive: true })
 	const a = traa.output(renderer)
@@ -198,6 +222,8 @@ function blurFrame() {
 	mb.update(renderer, rfx.TEX.FINAL, deltaTime)
 	mb.mainImage(renderer)
 }
+const effects = mb ? [effect, mb] : [effect]
+if (checkpoint.load) rfx.loadState(checkpoint.load, renderer, effects)
 if (stream && !tiled) {
 	if (!first.gbuffer) throw new Error("--stream needs packed gbuffer.bin / velocity.bin dumps")
 	const n = first.width * first.height
@@ -219,16 +245,18 @@ if (stream && !tiled) {
 		effect.update(renderer, null) // ... while frame i is drawn
 		blurFrame()
 		renderer.stageFlip()
+		saveAfter(i + 1, effects) // at the frame boundary: the save waits for the draws; the staged planes of frame i+1 are inputs, not state
 		cur = next
 	}
 } else
-	for (const d of dumps) {
+	dumps.forEach((d, i) => {
 		const f = d === dumps[0] ? first : rfx.readDump(d)
 		scene.frame = f
 		Object.assign(camera, f.camera)
 		effect.update(renderer, null)
 		blurFrame()
-	}
+		saveAfter(i + 1, effects)
+	})
 renderer.sync()
 fs.mkdirSync(out, { recursive: true })
 const T = rfx.TEX

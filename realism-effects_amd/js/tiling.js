@@ -85,6 +85,23 @@ class TiledRenderer {
 		if (!Array.isArray(blobs) || blobs.length !== this.nranks) throw new RangeError("usePeerHistory: allGather returns one blob per rank, in rank order")
 		this._comm.peerOpen(TEX.COMPOSE_RGB, Buffer.concat(blobs), this.rank, this.nranks)
 		this.historyGather = "peer"
+		this._allGather = allGather
+	}
+	// state.js: every rank has reached this point (its rows of a checkpoint are on disk / the header is written).  The ranks meet in a
+	// collective — the all-gather of the composed GI, which leaves every rank with the rows it would be handed anyway — waited for on the
+	// host; with "peer" history no communicator moves the planes, and they meet in the host channel that carried the export blobs
+	stateBarrier() {
+		if (this.nranks === 1) return
+		this.commWait()
+		if (this.historyGather === "peer") {
+			this.inner.sync()
+			this._allGather(Buffer.alloc(0))
+			return
+		}
+		this._comm.allgatherHistory(TEX.COMPOSE_RGB)
+		this._gatherPending = true
+		this.commWait()
+		this.inner.sync()
 	}
 	exchange(texs) {
 		if (this.nranks === 1 || this.haloRows === 0) return

@@ -6,5 +6,6 @@
     tiling   row tiles over the GPUs of a node, halo exchange through torch.distributed
     scene    synthetic G-buffer dumps in the reference's texel formats
     dump     on-disk dump format shared with the Node host (../js)
+    state    checkpoint / resume of the temporal state (save_state / load_state), shared with the Node host
 """
-__all__ = ["abi", "context", "effect", "tiling", "scene", "dump"]
+__all__ = ["abi", "context", "effect", "tiling", "scene", "dump", "state"]

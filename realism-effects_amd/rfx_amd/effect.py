@@ -62,6 +62,71 @@ def _texture_type(texture) -> int:
     return FloatType if t is None else int(t)
 
 
+class StateError(ValueError):
+    """A saved temporal state (rfx_amd.state) that does not fit the running effect; `field` names what differs."""
+
+    def __init__(self, field, message):
+        super().__init__("%s: %s" % (field, message))
+        self.field = field
+
+
+# Saved host state keeps every float as the hex of its little-endian IEEE bytes: bit for bit, and the same text from both hosts
+def _hex32(values) -> str:
+    return np.asarray(values, "<f4").tobytes().hex()
+
+
+def _hex64(values) -> str:
+    return np.asarray(values, "<f8").tobytes().hex()
+
+
+def _unhex(text, dtype, count, field):
+    try:
+        a = np.frombuffer(bytes.fromhex(text), dtype)
+    except (TypeError, ValueError):
+        raise StateError(field, "not the hex of %s values" % np.dtype(dtype).name)
+    if a.size != count:
+        raise StateError(field, "%d values, expected %d" % (a.size, count))
+    return a
+
+
+_CAMERA_FIELDS = (("projectionMatrix", 16), ("projectionMatrixInverse", 16), ("matrixWorld", 16), ("matrixWorldInverse", 16), ("position", 3))
+
+
+def _camera_state(c: abi.Camera) -> dict:
+    """An abi.Camera (what the device is handed: float32) as saved state."""
+    s = {name: _hex32(list(getattr(c, name))) for name, _ in _CAMERA_FIELDS}
+    s.update(near=_hex32([c.near_]), far=_hex32([c.far_]), isPerspective=int(c.isPerspective))
+    return s
+
+
+def _camera_from_state(s, field) -> abi.Camera:
+    c = abi.Camera()
+    if not isinstance(s, dict):
+        raise StateError(field, "missing")
+    for name, n in _CAMERA_FIELDS:
+        getattr(c, name)[:] = [float(x) for x in _unhex(s.get(name), "<f4", n, field + "." + name)]
+    c.near_ = float(_unhex(s.get("near"), "<f4", 1, field + ".near")[0])
+    c.far_ = float(_unhex(s.get("far"), "<f4", 1, field + ".far")[0])
+    c.isPerspective = _state_int(s, "isPerspective", field)
+    return c
+
+
+def _state_int(s, key, field, allow_none=False):
+    v = s.get(key) if isinstance(s, dict) else None
+    if v is None and allow_none and isinstance(s, dict) and key in s:
+        return None
+    if isinstance(v, bool) or not isinstance(v, int):
+        raise StateError(field + "." + key, "an integer is expected, got %r" % (v,))
+    return v
+
+
+def _state_dict(s, key, field):
+    v = s.get(key) if isinstance(s, dict) else None
+    if not isinstance(v, dict):
+        raise StateError(field + "." + key, "missing")
+    return v
+
+
 # src/taa/TAAUtils.js:3 + src/temporal-reproject/utils/QuasirandomGenerator.js:12-27 (JS doubles)
 def _generate_r2(count):
     g = 1.32471795724474602596090885447809
@@ -99,6 +164,16 @@ class BlueNoiseIndex:
     @value.setter
     def value(self, v: int):
         self._idx = int(v)
+
+    def get_state(self) -> dict:
+        return dict(startIndex=self.start_index, index=self._idx)
+
+    def check_state(self, s, field):
+        _state_int(s, "startIndex", field)
+        _state_int(s, "index", field)
+
+    def set_state(self, s):
+        self.start_index, self._idx = int(s["startIndex"]), int(s["index"])
 
 
 def didCameraMove(camera, last_position, last_quaternion) -> bool:
@@ -255,6 +330,41 @@ class TemporalReprojectPass:
                 hook(self.framebufferTexture)  # multi-GPU: halo exchange of the history rows
         self._prev = abi.Camera.from_scene(getattr(cam, "unjittered", cam))  # :203-213
 
+    # -- saved temporal state (rfx_amd.state)
+    def state_slots(self):
+        """The slots a later frame reads before writing, or leaves partly unwritten (K2 discards background texels)."""
+        slots = [abi.TEX_TEMPORAL0] + ([abi.TEX_TEMPORAL1] if self.textureCount == 2 else [])
+        if len(self.overrideAccumulatedTextures) == 0:
+            slots.append(self.framebufferTexture)
+        return slots
+
+    def get_state(self) -> dict:
+        return dict(frame=self.frame, textureCount=self.textureCount, targetType=self.targetType, keepData=_hex32([self.uniforms.keepData]),
+                    prevCamera=_camera_state(self._prev),
+                    lastCameraTransform=dict(position=_hex64(self.lastCameraTransform["position"]),
+                                             quaternion=_hex64(self.lastCameraTransform["quaternion"])))
+
+    def check_state(self, s, field):
+        if _state_int(s, "textureCount", field) != self.textureCount:
+            raise StateError(field + ".textureCount", "saved %d, the running pass has %d" % (s["textureCount"], self.textureCount))
+        if _state_int(s, "targetType", field) != self.targetType:
+            raise StateError(field + ".targetType", "saved %d, the running pass has %d (FloatType %d, HalfFloatType %d)" % (
+                s["targetType"], self.targetType, FloatType, HalfFloatType))
+        _state_int(s, "frame", field)
+        _unhex(s.get("keepData"), "<f4", 1, field + ".keepData")
+        _camera_from_state(s.get("prevCamera"), field + ".prevCamera")
+        t = _state_dict(s, "lastCameraTransform", field)
+        _unhex(t.get("position"), "<f8", 3, field + ".lastCameraTransform.position")
+        _unhex(t.get("quaternion"), "<f8", 4, field + ".lastCameraTransform.quaternion")
+
+    def set_state(self, s):
+        self.frame = int(s["frame"])
+        self.uniforms.keepData = float(_unhex(s["keepData"], "<f4", 1, "keepData")[0])
+        self._prev = _camera_from_state(s["prevCamera"], "prevCamera")
+        t = s["lastCameraTransform"]
+        self.lastCameraTransform = dict(position=_unhex(t["position"], "<f8", 3, "position").astype(np.float64),
+                                        quaternion=_unhex(t["quaternion"], "<f8", 4, "quaternion").astype(np.float64))
+
     def jitter(self, jitterScale=1):  # :216-220
         self.unjitter()
         return jitter(self.width, self.height, self._camera, self.frame, jitterScale)
@@ -308,6 +418,23 @@ class PoissonDenoisePass:
             hook = getattr(renderer, "after_denoise_pass", None)
             if hook:
                 hook(i, self.uniforms)  # multi-GPU: halo exchange of the target just written
+
+    # -- saved temporal state (rfx_amd.state)
+    def state_slots(self):
+        """Both ping-pong targets: K3 discards background texels, which keep what the target held; B is also K2's history."""
+        n = self.uniforms.textureCount
+        return [abi.TEX_DENOISE_A0, abi.TEX_DENOISE_A1][:n] + [abi.TEX_DENOISE_B0, abi.TEX_DENOISE_B1][:n]
+
+    def get_state(self) -> dict:
+        return dict(textureCount=int(self.uniforms.textureCount), blueNoiseIndex=self.blueNoiseIndex.get_state())
+
+    def check_state(self, s, field):
+        if _state_int(s, "textureCount", field) != self.uniforms.textureCount:
+            raise StateError(field + ".textureCount", "saved %d, the running pass has %d" % (s["textureCount"], self.uniforms.textureCount))
+        self.blueNoiseIndex.check_state(_state_dict(s, "blueNoiseIndex", field), field + ".blueNoiseIndex")
+
+    def set_state(self, s):
+        self.blueNoiseIndex.set_state(s["blueNoiseIndex"])
 
     def dispose(self):
         pass
@@ -380,6 +507,31 @@ class Denoiser:
     def reset(self):
         self.temporalReprojectPass.reset()
 
+    # -- saved temporal state (rfx_amd.state)
+    def state_slots(self):
+        slots = self.temporalReprojectPass.state_slots()
+        if self.denoisePass:
+            slots += self.denoisePass.state_slots()
+        if self.denoiserComposePass:
+            slots.append(self.denoiserComposePass.texture)  # K1's history; K4 discards background texels
+        return slots
+
+    def get_state(self) -> dict:
+        return dict(denoiseMode=self.options["denoiseMode"], temporalReprojectPass=self.temporalReprojectPass.get_state(),
+                    denoisePass=self.denoisePass.get_state() if self.denoisePass else None)
+
+    def check_state(self, s, field):
+        if s.get("denoiseMode") != self.options["denoiseMode"]:
+            raise StateError(field + ".denoiseMode", "saved %r, the running effect has %r" % (s.get("denoiseMode"), self.options["denoiseMode"]))
+        self.temporalReprojectPass.check_state(_state_dict(s, "temporalReprojectPass", field), field + ".temporalReprojectPass")
+        if self.denoisePass:
+            self.denoisePass.check_state(_state_dict(s, "denoisePass", field), field + ".denoisePass")
+
+    def set_state(self, s):
+        self.temporalReprojectPass.set_state(s["temporalReprojectPass"])
+        if self.denoisePass:
+            self.denoisePass.set_state(s["denoisePass"])
+
     def setSize(self, width, height):
         for p in (self.velocityDepthNormalPass, self.temporalReprojectPass, self.denoisePass, self.denoiserComposePass):
             if p:
@@ -445,6 +597,18 @@ class SSGIPass:
             renderer.ssgi_shade(self.uniforms)
         else:
             renderer.ssgi_march(self.uniforms)  # :93-94
+
+    # -- saved temporal state (rfx_amd.state); K1 writes every texel of its target, so the pass keeps no slot
+    def get_state(self) -> dict:
+        return dict(frame=self.frame, blueNoiseIndex=self.blueNoiseIndex.get_state())
+
+    def check_state(self, s, field):
+        _state_int(s, "frame", field)
+        self.blueNoiseIndex.check_state(_state_dict(s, "blueNoiseIndex", field), field + ".blueNoiseIndex")
+
+    def set_state(self, s):
+        self.frame = int(s["frame"])
+        self.blueNoiseIndex.set_state(s["blueNoiseIndex"])
 
     def dispose(self):
         pass
@@ -578,6 +742,34 @@ class SSGIEffect:
     def reset(self):
         self.denoiser.reset()
 
+    # -- saved temporal state (rfx_amd.state).  Options that are plain uniforms (radius, phi, steps, ...) are not part of it: they may be
+    # changed between frames, as in the reference.  The environment and its importance tables are inputs: the caller sets
+    # scene.environment again and the first update() after set_state() hands it to the device WITHOUT the reset of :356.
+    def state_slots(self):
+        return self.denoiser.state_slots()
+
+    def get_state(self) -> dict:
+        return {"class": type(self).__name__, "resolutionScale": _hex64([self._options["resolutionScale"]]), "ssgiPass": self.ssgiPass.get_state(),
+                "denoiser": self.denoiser.get_state(), "finalCamera": _camera_state(self.uniforms.camera),
+                "useEnvMap": int(self.ssgiPass.uniforms.useEnvMap)}
+
+    def check_state(self, s, field="effect"):
+        if s.get("class") != type(self).__name__:
+            raise StateError(field + ".class", "saved %r, the running effect is %r" % (s.get("class"), type(self).__name__))
+        scale = float(_unhex(s.get("resolutionScale"), "<f8", 1, field + ".resolutionScale")[0])
+        if scale != float(self._options["resolutionScale"]):
+            raise StateError(field + ".resolutionScale", "saved %r, the running effect has %r" % (scale, self._options["resolutionScale"]))
+        self.denoiser.check_state(_state_dict(s, "denoiser", field), field + ".denoiser")
+        self.ssgiPass.check_state(_state_dict(s, "ssgiPass", field), field + ".ssgiPass")
+        _camera_from_state(s.get("finalCamera"), field + ".finalCamera")
+        _state_int(s, "useEnvMap", field)
+
+    def set_state(self, s):
+        self.ssgiPass.set_state(s["ssgiPass"])
+        self.denoiser.set_state(s["denoiser"])
+        self.uniforms.camera = _camera_from_state(s["finalCamera"], "finalCamera")
+        object.__setattr__(self, "_env_restored", bool(s["useEnvMap"]))
+
     def setSize(self, width, height, force=False):
         if width is None and height is None:
             return
@@ -628,7 +820,8 @@ class SSGIEffect:
                     u.importanceSampling = 1
                 object.__setattr__(self, "_env_uuid", env)
                 u.useEnvMap = 1  # defines.USE_ENVMAP :344
-                self.reset()     # :356
+                if not self.__dict__.pop("_env_restored", False):  # (set_state: the map returns to a fresh device, the accumulation goes on)
+                    self.reset()  # :356
         elif u.useEnvMap:  # :361-366
             u.useEnvMap = u.importanceSampling = 0
             renderer.set_environment(None)
@@ -734,6 +927,55 @@ class TRAAEffect:
         self.temporalReprojectPass.jitter()
         self.temporalReprojectPass.render(renderer)  # :75
 
+    # -- saved temporal state (rfx_amd.state).  The pass is built by the first update(), from the composer buffer's type: a state saved
+    # after that builds it in a fresh effect (same type, same size); a state saved before it holds no pass.
+    def state_slots(self):
+        return self.temporalReprojectPass.state_slots() if self.temporalReprojectPass else []
+
+    def state_slots_of(self, s):
+        """the slots this effect keeps once set_state(s) has run"""
+        t = s.get("temporalReprojectPass")
+        if t is None:
+            return []
+        return [abi.TEX_TEMPORAL0, abi.TEX_FBCOPY_F16 if t.get("targetType") == HalfFloatType else abi.TEX_FBCOPY_F32]
+
+    def get_state(self) -> dict:
+        tp = self.temporalReprojectPass
+        m = self.unjitteredProjectionMatrix
+        return {"class": type(self).__name__,
+                "temporalReprojectPass": dict(tp.get_state(), width=int(tp.width), height=int(tp.height)) if tp else None,
+                "unjitteredProjectionMatrix": None if m is None else _hex64(np.asarray(m, np.float64).ravel())}
+
+    def check_state(self, s, field="effect"):
+        if s.get("class") != type(self).__name__:
+            raise StateError(field + ".class", "saved %r, the running effect is %r" % (s.get("class"), type(self).__name__))
+        t, f = s.get("temporalReprojectPass"), field + ".temporalReprojectPass"
+        if t is not None:
+            if not isinstance(t, dict) or t.get("targetType") not in (FloatType, HalfFloatType):
+                raise StateError(f + ".targetType", "FloatType (%d) or HalfFloatType (%d) is expected" % (FloatType, HalfFloatType))
+            tp = self.temporalReprojectPass or TemporalReprojectPass(self._scene, self._camera, self.velocityDepthNormalPass,
+                                                                     dict(type=t["targetType"]), 1, self.options)
+            tp.check_state(t, f)
+            _state_int(t, "width", f)
+            _state_int(t, "height", f)
+        if s.get("unjitteredProjectionMatrix") is not None:
+            _unhex(s["unjitteredProjectionMatrix"], "<f8", 16, field + ".unjitteredProjectionMatrix")
+
+    def set_state(self, s):
+        t = s["temporalReprojectPass"]
+        if t is None:
+            self.temporalReprojectPass = None
+            self.uniforms["accumulatedTexture"] = None
+        else:
+            if self.temporalReprojectPass is None:  # :53-66, from the saved type instead of the first input buffer's
+                self.temporal_params(dict(type=int(t["targetType"])))
+                self.uniforms["accumulatedTexture"] = self.temporalReprojectPass.texture
+            self.temporalReprojectPass.setSize(int(t["width"]), int(t["height"]))
+            self.temporalReprojectPass.set_state(t)
+        m = s.get("unjitteredProjectionMatrix")
+        self.unjitteredProjectionMatrix = None if m is None else _unhex(m, "<f8", 16, "unjitteredProjectionMatrix").astype(np.float32).reshape(
+            np.shape(self._camera.projectionMatrix))
+
     def output(self, renderer, row0=None, rows=None):
         """traa_compose.frag (src/traa/shader/traa_compose.frag:3-7): outputColor = vec4(accumulatedTexel.rgb, 1.)."""
         t = renderer.download(self.uniforms["accumulatedTexture"], row0, rows).copy()
@@ -822,6 +1064,23 @@ class MotionBlurEffect:
             renderer.upload(abi.TEX_EFFECT_INPUT, np.ascontiguousarray(data, np.float32))
             u.source, u.center, u.centerAlphaOne = abi.TEX_EFFECT_INPUT, -1, 0
         u.targetHalf = 1 if half else 0
+
+    # -- saved temporal state (rfx_amd.state): the frame counter behind the jitter; K6 writes every texel, so the effect keeps no slot
+    def state_slots(self):
+        return []
+
+    def get_state(self) -> dict:
+        return {"class": type(self).__name__, "frame": None if self.frame is None else int(self.frame), "updates": int(self._updates)}
+
+    def check_state(self, s, field="effect"):
+        if s.get("class") != type(self).__name__:
+            raise StateError(field + ".class", "saved %r, the running effect is %r" % (s.get("class"), type(self).__name__))
+        _state_int(s, "frame", field, allow_none=True)
+        _state_int(s, "updates", field)
+
+    def set_state(self, s):
+        self.frame = s["frame"]
+        self._updates = int(s["updates"])
 
     def mainImage(self, renderer):
         """the effect's fragment (motion_blur.frag mainImage) -> RFX_TEX_MOTION_BLUR"""

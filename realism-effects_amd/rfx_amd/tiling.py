@@ -215,6 +215,11 @@ class TiledRenderer:
         self.finish_halo()
         return self.inner.sync()
 
+    def state_barrier(self):
+        """rfx_amd.state: every rank has reached this point (its rows of a checkpoint are on disk / the header is written)"""
+        if self.world > 1:
+            self._dist.barrier(group=self.group)
+
     def finish_halo(self):
         pending, self._halo_pending = self._halo_pending, []
         for works, tensor in pending:
@@ -367,6 +372,13 @@ class CommTiledRenderer(TiledRenderer):
             self.inner.allgather_history(self._history_tex())
             self._pending = [True]
             self.finish_pending()
+
+    def state_barrier(self):
+        """rfx_amd.state: every rank has reached this point.  No host channel exists here, so the ranks meet in a collective: the all-gather
+        of the composed GI (which leaves every rank with the rows it would be handed anyway), waited for on the host."""
+        if self.world > 1:
+            self.gather_whole_history()
+            self.inner.sync()
 
     def finish_halo(self):
         if self._halo_pending or self._pending:
