@@ -781,9 +781,13 @@ __global__ __launch_bounds__(256) void k1_hit_mask(FrameDims d, int y0, int y1, 
 // lane and row, when the row pitch keeps them aligned), so a cell's (min, max) is a register reduction plus log2(BASE / VEC) lane exchanges: no
 // LDS, no barrier.  (Rounds 1-4 drew one texel per thread in 64 x 16-thread workgroups with an LDS reduction: 0.109 ms at 4K = 0.6 TB/s, hidden
 // under the previous frame's later draws on its own stream but taking its CU time from them.)
+// The same pass writes K3's foreground map `fg` (rfx_kernels.h K3Args::fg_tiles): one byte per frame-aligned 64 x 8-texel tile, 1 when some depth
+// texel of the tile is != 1.0 (a NaN counts: the denoiser's `discard` test sees it the same way), 0 when every pixel of the tile will discard.  A
+// wavefront's strip is VEC tiles wide and two tiles high; the 64 / VEC lanes of a tile OR their flags with lane exchanges.
 template <int VEC>
 __global__ __launch_bounds__(256) void k1_prepare(const float *depth, float *viewz, float2 *base, int W, int H, int base_w, float nearMulFar,
-                                                   float farMinusNear, float cameraFar, float nearMinusFar, float cameraNear, int perspective) {
+                                                   float farMinusNear, float cameraFar, float nearMinusFar, float cameraNear, int perspective,
+                                                   unsigned char *fg, int fg_w) {
     static_assert(VEC == 1 || VEC == 4, "one texel or one aligned float4 per lane and row");
     const int x0 = (blockIdx.x * 64 + threadIdx.x) * VEC, cy = blockIdx.y * 4 + threadIdx.y, y0 = cy * BASE;
     if (y0 >= H) return;  // (wave-uniform: threadIdx.y is the wavefront)
@@ -827,6 +831,18 @@ __global__ __launch_bounds__(256) void k1_prepare(const float *depth, float *vie
     }
     const int cx = x0 / BASE;
     if ((threadIdx.x & (BASE / VEC - 1)) == 0 && cx < base_w) base[(size_t)cy * base_w + cx] = make_float2(mn, mx);
+    // the foreground map: bit h of `any` = rows 8 h .. 8 h + 7 of this lane's columns hold a texel != 1.0 (texels beyond the frame were preset to 1.0)
+    static_assert(BASE == 16, "a strip is two 8-row map tiles high");
+    int any = 0;
+#pragma unroll
+    for (int r = 0; r < BASE; r++)
+#pragma unroll
+        for (int k = 0; k < VEC; k++) any |= (d[r][k] != 1.0f ? 1 : 0) << (r >> 3);
+#pragma unroll
+    for (int o = 1; o < 64 / VEC; o <<= 1) any |= __shfl_xor(any, o);
+    // lanes 0 and 1 of a tile's lanes store the bytes of the strip's first and second tile row
+    const int h = threadIdx.x & (64 / VEC - 1), tx = x0 >> 6, ty = 2 * cy + h;
+    if (h < 2 && tx < fg_w && ty * 8 < H) fg[(size_t)ty * fg_w + tx] = (unsigned char)((any >> h) & 1);
 }
 
 // ... and the march's table: cell (cx, cy) of edge BASE << up = the (min, max) of its (1 << up)^2 base cells, packed to two halfs
@@ -899,10 +915,10 @@ hipError_t rfx_launch_k1_prepare(const K1Args &A, hipStream_t stream) {
     const dim3 block(64, 4);
     if (W % 4 == 0 && ((uintptr_t)A.depth.ptr & 15u) == 0 && ((uintptr_t)A.viewz & 15u) == 0)  // (a caller's depth buffer may sit at any address)
         hipLaunchKernelGGL(k1_prepare<4>, dim3((W + 255) / 256, ((H + BASE - 1) / BASE + 3) / 4), block, 0, stream, (const float *)A.depth.ptr, A.viewz, A.coarse, W, H, A.coarse_w,
-                           A.nearMulFar, A.farMinusNear, A.p.camera.far_, A.nearMinusFar, A.p.camera.near_, A.p.camera.isPerspective);
+                           A.nearMulFar, A.farMinusNear, A.p.camera.far_, A.nearMinusFar, A.p.camera.near_, A.p.camera.isPerspective, A.fg_tiles, A.fg_w);
     else
         hipLaunchKernelGGL(k1_prepare<1>, dim3((W + 63) / 64, ((H + BASE - 1) / BASE + 3) / 4), block, 0, stream, (const float *)A.depth.ptr, A.viewz, A.coarse, W, H, A.coarse_w,
-                           A.nearMulFar, A.farMinusNear, A.p.camera.far_, A.nearMinusFar, A.p.camera.near_, A.p.camera.isPerspective);
+                           A.nearMulFar, A.farMinusNear, A.p.camera.far_, A.nearMinusFar, A.p.camera.near_, A.p.camera.isPerspective, A.fg_tiles, A.fg_w);
     int up = 0;
     while ((BASE << up) < (1 << A.cell_shift)) up++;
     const int padded = A.cells_vec4 * 4;

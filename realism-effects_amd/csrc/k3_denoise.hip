@@ -113,6 +113,17 @@ RFX_DEV rfx_f2 k3_luma2(rfx_f2 r, rfx_f2 g, rfx_f2 b) {
 // what the copy gives) — one LDS address per footprint, its four texels at compile-time offsets (two ds_read2_b64).
 // PITCH is a template parameter for that reason: LW = 64 + 2 Rx rounded up to 72 / 74 / 76 / 80 / 96 texels (Rx <= 4 / 5 / 6 / 8 / 16).
 
+// The foreground map (K3Args::fg_tiles, written by K1's depth pre-pass): is the frame-aligned 64 x 8-texel tile that holds pixel rows y0 .. of tile
+// column bx all background?  Then every pixel of it takes the `discard` below — depth 1.0, and fwidth(depth) == 0 because a pixel's 2x2-quad
+// partners (x ^ 1, y ^ 1, clamped to the frame) lie in its own tile — and the workgroup has nothing to stage or write.  The byte is fetched as
+// part of its aligned word: a workgroup-uniform address, i.e. one scalar load.
+RFX_DEV bool k3_tile_is_background(const K3Args &A, const FrameDims &d, int bx, int y0) {
+    if (!A.fg_tiles) return false;
+    const unsigned int i = (unsigned int)((y0 >> 3) * ((d.W + 63) >> 6) + bx);
+    const unsigned int w = reinterpret_cast<const unsigned int *>(A.fg_tiles)[i >> 2];
+    return ((w >> ((i & 3u) * 8u)) & 0xffu) == 0u;
+}
+
 // WHOLE: every view is the whole frame (a context that owns no row tile): rows need no rebasing and no halo accounting
 template <bool IN_TEMPORAL, int TC, int PITCH, bool WHOLE>
 RFX_DEV void k3_tiled_body(const K3Args &A, const FrameDims &d) {
@@ -140,6 +151,10 @@ RFX_DEV void k3_tiled_body(const K3Args &A, const FrameDims &d) {
         s_in0 = lds + 1 + nal / 4 + nal - 2 * skip;
     }
     const rfx_denoise_params &p = A.p;
+    const TileXY tile = rfx_xcd_tile<K3_XCD_G>((d.W + TW - 1) / TW, (A.y1 - A.y0 + TH - 1) / TH);
+    if (!tile.valid) return;  // grid padding (uniform per workgroup, before any barrier)
+    const int tx0 = tile.bx * TW, ty0 = A.y0 + tile.by * TH;
+    if (k3_tile_is_background(A, d, tile.bx, ty0)) return;  // (uniform per workgroup too: nothing is staged for a tile whose every pixel discards)
     if (PAIR && IN_TEMPORAL && skip > 0) {
         // ... and the two pads hold zeros, not what the previous workgroup left in LDS: a frame with a NaN / inf depth or normal stays deterministic
         const int t = threadIdx.y * TW + threadIdx.x, nal = ntex - 2 * skip;
@@ -147,9 +162,6 @@ RFX_DEV void k3_tiled_body(const K3Args &A, const FrameDims &d) {
         if (t < 4) f[t] = 0.0f;
         if (t < 8 * skip) f[4 + nal * 13 + t] = 0.0f;  // behind depth (1) + geometry (4) + interleaved inputs (8 floats per texel)
     }
-    const TileXY tile = rfx_xcd_tile<K3_XCD_G>((d.W + TW - 1) / TW, (A.y1 - A.y0 + TH - 1) / TH);
-    if (!tile.valid) return;  // grid padding (uniform per workgroup, before any barrier)
-    const int tx0 = tile.bx * TW, ty0 = A.y0 + tile.by * TH;
     const int tid = threadIdx.y * TW + threadIdx.x;
     const float *depthp = (const float *)A.depth.ptr;
     const uint4 *gbp = (const uint4 *)A.gbuffer.ptr;
@@ -416,6 +428,7 @@ RFX_DEV float4 k3_input(const TexView &t, const FrameDims &d, float u, float v) 
 
 template <bool IN_TEMPORAL, int TC>
 RFX_DEV void k3_generic_body(const K3Args &A, const FrameDims &d) {
+    if (k3_tile_is_background(A, d, blockIdx.x, A.y0 + blockIdx.y * 4)) return;  // (a 64 x 4 block lies in one map tile: y0 is a multiple of 8)
     const int x = blockIdx.x * 64 + threadIdx.x;
     const int y = A.y0 + blockIdx.y * 4 + threadIdx.y;
     if (x >= d.W || y >= A.y1) return;
@@ -571,6 +584,7 @@ hipError_t rfx_launch_k3(const K3Args &A_in, hipStream_t stream) {
     const bool whole = whole_view(A.depth.ptr, A.depth.row0, A.depth.rows) && whole_view(A.gbuffer.ptr, A.gbuffer.row0, A.gbuffer.rows) &&
                        whole_view(A.in0.ptr, A.in0.row0, A.in0.rows) && whole_view(A.in1.ptr, A.in1.row0, A.in1.rows) &&
                        whole_view(A.out0.ptr, A.out0.row0, A.out0.rows) && whole_view(A.out1.ptr, A.out1.row0, A.out1.rows);
+    if (!whole) A.fg_tiles = nullptr;  // the map is indexed by frame-aligned tiles of whole-frame planes
     if (tiled) {
         dim3 block(TW, TH), grid(rfx_xcd_grid(K3_XCD_G, (A.dims.W + TW - 1) / TW, (A.y1 - A.y0 + TH - 1) / TH));
         // the attribute is per device (a process may hold contexts on several): remembered per device ordinal

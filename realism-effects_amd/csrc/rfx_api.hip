@@ -134,6 +134,7 @@ void rfx_destroy(rfx_ctx *c) {
     if (c->coarse) hipFree(c->coarse);
     if (c->cells) hipFree(c->cells);
     if (c->k1_tiles) hipFree(c->k1_tiles);
+    if (c->fg_tiles) hipFree(c->fg_tiles);
     if (c->env) hipFree(c->env);
     if (c->env_marginal) hipFree(c->env_marginal);
     if (c->env_conditional) hipFree(c->env_conditional);
@@ -220,7 +221,10 @@ int rfx_upload(rfx_ctx *c, rfx_tex id, const void *host, int row0, int rows) {
     HIPCHK(c, hipMemcpyAsync((char *)s.ptr + (size_t)(row0 - s.row0) * pitch, host, (size_t)rows * pitch, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));  // the caller may free `host` as soon as we return
     s.uploaded = true;
-    if (id == RFX_TEX_DEPTH) c->depth_event_set = false;  // complete: nothing for the depth pre-pass to wait for
+    if (id == RFX_TEX_DEPTH) {
+        c->depth_event_set = false;  // complete: nothing for the depth pre-pass to wait for
+        c->depth_gen++;              // ... and the foreground map of the last pre-pass no longer describes the plane (rfx_ctx.h)
+    }
     return RFX_OK;
 }
 
@@ -300,6 +304,7 @@ int rfx_stage_flip(rfx_ctx *c) {
         if (id == RFX_TEX_DEPTH) {  // the depth pre-pass of the next K1 waits for this copy on its own stream
             HIPCHK(c, hipEventRecord(c->ev_depth, c->upload_stream));
             c->depth_event_set = true;
+            c->depth_gen++;  // another plane is the depth slot now
         }
         void *t = s.ptr; s.ptr = s.back; s.back = t;
         s.back_filled = false;
@@ -318,6 +323,7 @@ int rfx_clear(rfx_ctx *c, rfx_tex id) {
     if (id == RFX_TEX_DEPTH) {
         HIPCHK(c, hipEventRecord(c->ev_depth, c->stream));
         c->depth_event_set = true;
+        c->depth_gen++;
     }
     return RFX_OK;
 }
@@ -328,7 +334,7 @@ void *rfx_tex_device_ptr(rfx_ctx *c, rfx_tex id) {
     if (ensure(c, id)) return nullptr;
     // whoever takes the depth plane's address may write it with work this library cannot see (ordered against the draw stream only, as a
     // bound external buffer is): the pre-pass then stays in the draw stream
-    if (id == RFX_TEX_DEPTH) c->depth_external = true;
+    if (id == RFX_TEX_DEPTH) { c->depth_external = true; c->depth_gen++; }
     return c->slots[id].ptr;
 }
 
@@ -343,7 +349,7 @@ int rfx_bind_external(rfx_ctx *c, rfx_tex id, void *device_ptr) {
     s.ptr = device_ptr;
     s.owned = false;
     s.uploaded = true;
-    if (id == RFX_TEX_DEPTH) c->depth_external = true;  // written by whoever owns the buffer, ordered against the draw stream only
+    if (id == RFX_TEX_DEPTH) { c->depth_external = true; c->depth_gen++; }  // written by whoever owns the buffer, ordered against the draw stream only
     return RFX_OK;
 }
 
@@ -678,12 +684,17 @@ static int ssgi_draw(rfx_ctx *c, const rfx_ssgi_params *p, int stage) {
         if (e == hipSuccess) e = hipMalloc((void **)&c->coarse, (size_t)A.coarse_w * A.coarse_h * sizeof(float2));
         if (e == hipSuccess) e = hipMalloc((void **)&c->cells, (size_t)A.cells_vec4 * 16);
         if (e == hipSuccess) e = hipMalloc((void **)&c->k1_tiles, 64 * 128);
-        if (e != hipSuccess) {  // all four or none: a later draw must not find viewz set and the tables missing
+        // the two foreground maps (rfx_ctx.h): ceil(W / 64) x ceil(H / 8) bytes each, 16 KiB at 4K, in whole 256-byte units (K3 reads a byte's word)
+        c->fg_w = (c->W + 63) / 64;
+        c->fg_stride = (((size_t)c->fg_w * ((c->H + 7) / 8)) + 255) & ~(size_t)255;
+        if (e == hipSuccess) e = hipMalloc((void **)&c->fg_tiles, 2 * c->fg_stride);
+        if (e != hipSuccess) {  // all five or none: a later draw must not find viewz set and the tables missing
             if (c->viewz) hipFree(c->viewz);
             if (c->coarse) hipFree(c->coarse);
             if (c->cells) hipFree(c->cells);
             if (c->k1_tiles) hipFree(c->k1_tiles);
-            c->viewz = nullptr; c->coarse = nullptr; c->cells = nullptr; c->k1_tiles = nullptr;
+            if (c->fg_tiles) hipFree(c->fg_tiles);
+            c->viewz = nullptr; c->coarse = nullptr; c->cells = nullptr; c->k1_tiles = nullptr; c->fg_tiles = nullptr;
             return fail(c, RFX_ENOMEM, "hipMalloc(K1 scratch)", e);
         }
     }
@@ -692,6 +703,11 @@ static int ssgi_draw(rfx_ctx *c, const rfx_ssgi_params *p, int stage) {
     A.cells = c->cells;
     A.tile_counter = c->k1_tiles;
     A.n_cu = c->n_cu;
+    // the pre-pass fills the foreground map the previous pre-pass did not: that one is still read by the K3 draws queued since (the pre-pass
+    // runs under them; it waits for ev_k1_done, i.e. for every draw that read the map it overwrites)
+    const int fg_next = c->fg_cur ^ 1;
+    A.fg_tiles = c->fg_tiles + (size_t)fg_next * c->fg_stride;
+    A.fg_w = c->fg_w;
     A.env = c->env;
     A.env_w = c->env_w; A.env_h = c->env_h; A.env_levels = c->env_levels;
     A.env_marginal = c->env_marginal; A.env_conditional = c->env_conditional;
@@ -734,6 +750,8 @@ static int ssgi_draw(rfx_ctx *c, const rfx_ssgi_params *p, int stage) {
             HIPCHK(c, hipEventRecord(c->ev_prep_done, c->prep_stream));
             HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_prep_done, 0));
         }
+        c->fg_cur = fg_next;
+        c->fg_gen = c->depth_gen;  // the map describes the depth plane as it is now: every later writer of the slot bumps depth_gen
     }
     // the march kernel hands its tiles out from a counter: the pre-pass zeroes it; the shade stage has no pre-pass of its own
     if (any && stage == 2) HIPCHK(c, hipMemsetAsync(c->k1_tiles, 0, 64 * 128, c->stream));
@@ -905,6 +923,10 @@ int rfx_poisson_denoise(rfx_ctx *c, const rfx_denoise_params *p) {
     blue_noise_shift(p->blueNoiseIndex, &A.shift_x, &A.shift_y);
     A.out0 = wview(c, out0); A.out1 = wview(c, out1);
     A.p = *p;
+    // the foreground map of the last K1 pre-pass, while it still describes the depth plane these draws read: no writer of the slot since
+    // (depth_gen), not a caller's buffer (written by work this library cannot see), and tile rows that are the map's (launch rows from a
+    // multiple of 8: a row window or a row tile may start anywhere).  rfx_launch_k3 drops it unless every view is the whole frame.
+    A.fg_tiles = (c->fg_tiles && c->fg_gen == c->depth_gen && !c->depth_external && (A.y0 & 7) == 0) ? c->fg_tiles + (size_t)c->fg_cur * c->fg_stride : nullptr;
     ProfScope prof(c, p->inputIsTemporal ? RFX_PROF_K3_PASS0 : RFX_PROF_K3_PASSN, c->stream);
     HIPCHK(c, rfx_launch_k3(A, c->stream));
     return RFX_OK;

@@ -49,6 +49,14 @@ struct rfx_ctx {
     unsigned int *cells = nullptr;  // K1 scratch: the march's half-packed (min,max) table
     unsigned int *k1_tiles = nullptr;  // K1 scratch: the persistent march kernel's tile counter
     int n_cu = 0;                      // compute units of the device
+    // K3's foreground map: one byte per frame-aligned 64 x 8-texel tile, 0 = every depth texel of the tile is 1.0 (all of its
+    // pixels discard), written by K1's depth pre-pass.  TWO maps in one allocation, fg_stride bytes apart: the pre-pass of frame n + 1 runs
+    // under frame n's K3 draws, so it fills the map the previous pre-pass did not (fg_cur: the one the last pre-pass filled).
+    unsigned char *fg_tiles = nullptr;
+    size_t fg_stride = 0;
+    int fg_w = 0, fg_cur = 0;
+    // ... and its validity: every entry point that can write the DEPTH slot bumps depth_gen; the pre-pass records the value it read (fg_gen)
+    unsigned long long depth_gen = 1, fg_gen = 0;
     float4 *env = nullptr;     // scene.environment: the whole mip chain, float4 texels
     float *env_marginal = nullptr, *env_conditional = nullptr;  // EquirectHdrInfo inverse-CDF tables (importanceSampling)
     float env_sum_whole = 1.0f, env_sum_decimal = 0.0f;

@@ -39,6 +39,8 @@ struct K1Args {
     float4 *hits;      // trace -> shade hand-over (2 texels per output pixel, indexed like `out`); null for the fused launch
     unsigned int *tile_counter;  // the persistent march kernel's work counter (context scratch; zero when the launch starts)
     int n_cu;                    // compute units of the device (sizes the persistent grid)
+    unsigned char *fg_tiles;     // k1_prepare also writes K3's foreground map: one byte per 64 x 8-texel tile, rows of fg_w = ceil(W / 64) bytes
+    int fg_w;
 };
 
 // one level of the environment's mip chain from the one above (glGenerateMipmap on the oracle's GL: 2x2 bilinear centre)
@@ -67,6 +69,10 @@ struct K3Args {
     rfx_denoise_params p;
     struct { int Rx, Ry, LW, LH, skip; } tile;  // filled by the launcher (skip: texels shaved off each end of the staged rectangle, k3_tiled_body)
     float tap_ox[8], tap_oy[8];           // POISSON[k] / resolution, filled by the launcher
+    // K1's foreground map of the depth plane (ceil(W / 64) bytes per row of frame-aligned 64 x 8-texel tiles; 4-byte aligned, padded to whole
+    // words) or null: a workgroup whose tile's byte is 0 returns at once — every pixel of it would discard.  The caller passes it only while it
+    // describes `depth` and y0 is a multiple of 8; the launcher drops it unless every view is the whole frame.
+    const unsigned char *fg_tiles;
 };
 
 struct K4Args {
