@@ -18,19 +18,20 @@
 // k1_ssgi_march.  Measurements: profiles/r04_k1, profiles/r05_k1; DESIGN.md §4.
 #include "rfx_brdf.h"
 #include "rfx_kernels.h"
+#include "rfx_launch.h"
 
 namespace {
 
 // The (min, max) view-Z table the march consults before touching a texel: one 4-byte cell = two halfs, min rounded
 // DOWN and max rounded UP, so a widened range can only reject fewer taps — the rejection tests stay exact.  The cell edge is
-// 2^cell_shift texels, chosen per frame size so that the whole table stays <= 36 KiB (rfx_api, which also picks the row layout; 4K: 32-texel cells): every workgroup of the
+// 2^cell_shift texels, chosen per frame size so that the whole table stays <= 36 KiB (rfx_k1_table, which also picks the row layout; 4K: 32-texel cells): every workgroup of the
 // march keeps its own copy in LDS.
 constexpr int BASE = 16;  // edge of the pre-pass's exact (float) cells, reduced to the final cells by k1_pack_cells
 constexpr int K1_TH = 1;               // rows of 64 pixels per tile a wavefront takes from its queue (2 / 4 measured slower: profiles/r04_k1)
 typedef uint32_t k1_cell_t;
 constexpr int K1_WAVES = 8;            // wavefronts per workgroup of the persistent march kernel
 constexpr int K1_COUNTERS = 64;        // tile queues of the persistent march kernel (one queue: +1/3 time; XCD-grouped or static dealing: slower — profiles/r04_k1, r05_k1)
-constexpr int K1_TABLE_CELLS = 9216;   // 36 KiB: rfx_api keeps the table within it for every frame size (cell edge doubled until it fits)
+constexpr int K1_TABLE_CELLS = RFX_K1_TABLE_BYTES / (int)sizeof(k1_cell_t);  // 36 KiB: rfx_k1_table keeps the table within it for every frame size (cell edge doubled until it fits)
 RFX_DEV uint32_t k1_half_toward(float v, bool up) {  // nearest half not below (up) / not above (!up) v
     uint32_t h = rfx_f2h_rne(v) & 0xffffu;
     const float f = rfx_h2f((unsigned short)h);
@@ -932,44 +933,32 @@ hipError_t rfx_launch_k1(const K1Args &A, int stage, hipStream_t stream) {
     // surplus workgroups start late and find the counter exhausted), never more workgroups than there are tiles for their waves
     const int nbx = (A.out_w + 63) / 64, nby = (A.y1 - A.y0 + K1_TH - 1) / K1_TH;
     const int want = (nbx * nby + K1_WAVES - 1) / K1_WAVES, n_cu = A.n_cu > 0 ? A.n_cu : 256;
-    dim3 block(64 * K1_WAVES), grid(1);
+    dim3 block(64 * K1_WAVES);
     const float *P = A.p.camera.projectionMatrix;
     const bool persp = P[1] == 0.f && P[2] == 0.f && P[3] == 0.f && P[4] == 0.f && P[6] == 0.f && P[7] == 0.f && P[12] == 0.f && P[13] == 0.f &&
                        P[15] == 0.f && P[11] == -1.f;
     const bool env = A.p.useEnvMap != 0, mis = env && A.p.importanceSampling != 0;
-    // the persistent grid: what the chip holds of THIS specialisation at once — the runtime's occupancy figure for its registers and static LDS
-    // (4 workgroups per CU at <= 64 VGPRs; fewer with an environment map), asked once per specialisation and device
-#define K1_GO_S(P, E, M, S)                                                                                                   \
-    do {                                                                                                                      \
-        static int per_cu[64] = {0};                                                                                          \
-        int dev = 0;                                                                                                          \
-        hipGetDevice(&dev);                                                                                                   \
-        int nb = (dev >= 0 && dev < 64) ? per_cu[dev] : 0;                                                                    \
-        if (nb <= 0) {                                                                                                        \
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)k1_ssgi_march<P, E, M, S>, 64 * K1_WAVES, 0) != hipSuccess || nb <= 0) \
-                nb = 32 / K1_WAVES;                                                                                           \
-            if (dev >= 0 && dev < 64) per_cu[dev] = nb;                                                                       \
-        }                                                                                                                     \
-        const int fit = n_cu * (nb > 0 ? nb : 1);                                                                             \
-        grid = dim3(want < fit ? want : fit);                                                                                 \
-        hipLaunchKernelGGL((k1_ssgi_march<P, E, M, S>), grid, block, 0, stream, A);                                           \
-    } while (0)
-#define K1_GO(P, E, M)                            \
-    do {                                          \
-        if (stage == 0) K1_GO_S(P, E, M, 0);      \
-        else if (stage == 1) K1_GO_S(P, E, M, 1); \
-        else K1_GO_S(P, E, M, 2);                 \
-    } while (0)
     const bool centred = persp && P[8] == 0.f && P[9] == 0.f;
-#define K1_GO_P(PJ) do { if (mis) K1_GO(PJ, true, true); else if (env) K1_GO(PJ, true, false); else K1_GO(PJ, false, false); } while (0)
-    // (the table's layout is a template argument too: PROJ_TABLE_POW2)
-#define K1_GO_T(PJ) do { if (A.cells_pow2) K1_GO_P((PJ) | PROJ_TABLE_POW2); else K1_GO_P(PJ); } while (0)
-    if (centred) K1_GO_T(PROJ_CENTRED);
-    else if (persp) K1_GO_T(PROJ_PERSPECTIVE);
-    else K1_GO_T(PROJ_GENERAL);
-#undef K1_GO_T
-#undef K1_GO_P
-#undef K1_GO
-#undef K1_GO_S
+    // four template arguments: the projection, the table's layout (PROJ_TABLE_POW2, a bit of the same argument), the (ENV, MIS) pair — plain,
+    // environment, environment with importance sampling; MIS without ENV does not exist — and the stage
+    rfx_with_int<PROJ_GENERAL, PROJ_PERSPECTIVE, PROJ_CENTRED>(centred ? PROJ_CENTRED : persp ? PROJ_PERSPECTIVE : PROJ_GENERAL, [&](auto proj) {
+        rfx_with_bool(A.cells_pow2 != 0, [&](auto pow2) {
+            rfx_with_int<0, 1, 2>(mis ? 2 : env ? 1 : 0, [&](auto em) {
+                rfx_with_int<0, 1, 2>(stage == 0 || stage == 1 ? stage : 2, [&](auto st) {
+                    constexpr auto kernel = k1_ssgi_march<decltype(proj)::value | (decltype(pow2)::value ? PROJ_TABLE_POW2 : 0), decltype(em)::value >= 1,
+                                                          decltype(em)::value == 2, decltype(st)::value>;
+                    // the persistent grid: what the chip holds of THIS specialisation at once — the runtime's occupancy figure for its registers and
+                    // static LDS (4 workgroups per CU at <= 64 VGPRs; fewer with an environment map), asked once per specialisation and device
+                    const int nb = rfx_per_device<kernel, int>([&] {
+                        int n = 0;
+                        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)kernel, 64 * K1_WAVES, 0) != hipSuccess || n <= 0) n = 32 / K1_WAVES;
+                        return n;
+                    });
+                    const int fit = n_cu * nb;
+                    hipLaunchKernelGGL(kernel, dim3(want < fit ? want : fit), block, 0, stream, A);
+                });
+            });
+        });
+    });
     return hipGetLastError();
 }

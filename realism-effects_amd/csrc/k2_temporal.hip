@@ -16,6 +16,7 @@
 // of 50, bit-identical — was built and measured in round 5: no faster, 13 % more VALU instructions; profiles/r05_k2/.)
 #include "rfx_device.h"
 #include "rfx_kernels.h"
+#include "rfx_launch.h"
 
 namespace {
 
@@ -378,39 +379,24 @@ __global__ __launch_bounds__(256) void k2_copy_framebuffer(FrameDims d, int y0, 
 
 hipError_t rfx_launch_copy_fb(const FrameDims &d, int y0, int y1, TexView src, TexViewW dst, bool to_half, hipStream_t stream) {
     dim3 block(64, 4), grid((d.W + 63) / 64, (y1 - y0 + 3) / 4);
-    if (to_half) hipLaunchKernelGGL(k2_copy_framebuffer<true>, grid, block, 0, stream, d, y0, y1, src, dst);
-    else hipLaunchKernelGGL(k2_copy_framebuffer<false>, grid, block, 0, stream, d, y0, y1, src, dst);
+    rfx_with_bool(to_half, [&](auto h) { hipLaunchKernelGGL(k2_copy_framebuffer<decltype(h)::value>, grid, block, 0, stream, d, y0, y1, src, dst); });
     return hipGetLastError();
 }
 
 hipError_t rfx_launch_k2(const K2Args &A, hipStream_t stream) {
     dim3 block(TW, TH), grid(rfx_xcd_grid(K2_XCD_G, (A.dims.W + TW - 1) / TW, (A.y1 - A.y0 + TH - 1) / TH));
-    const bool lt = A.p.logTransform != 0;
-    // every view is the whole frame (a context that owns no row tile): no row rebasing, no halo accounting in the kernel
-    const auto whole_view = [&](const void *ptr, int row0, int rows) { return ptr == nullptr || (row0 == 0 && rows == A.dims.H); };
-    const bool whole = whole_view(A.ssgi.ptr, A.ssgi.row0, A.ssgi.rows) && whole_view(A.velocity.ptr, A.velocity.row0, A.velocity.rows) &&
-                       whole_view(A.hist0.ptr, A.hist0.row0, A.hist0.rows) && whole_view(A.hist1.ptr, A.hist1.row0, A.hist1.rows) &&
-                       whole_view(A.out0.ptr, A.out0.row0, A.out0.rows) && whole_view(A.out1.ptr, A.out1.row0, A.out1.rows);
-#define K2_LAUNCH_W(IT, TC, LT, HF)                                                                                         \
-    do {                                                                                                                    \
-        if (whole) hipLaunchKernelGGL((k2_temporal_reproject<IT, TC, LT, HF, true>), grid, block, 0, stream, A);            \
-        else hipLaunchKernelGGL((k2_temporal_reproject<IT, TC, LT, HF, false>), grid, block, 0, stream, A);                 \
-    } while (0)
-#define K2_LAUNCH(IT, TC)                               \
-    do {                                                \
-        if (A.hist_f32) {                               \
-            if (lt) K2_LAUNCH_W(IT, TC, true, true);    \
-            else K2_LAUNCH_W(IT, TC, false, true);      \
-        } else {                                        \
-            if (lt) K2_LAUNCH_W(IT, TC, true, false);   \
-            else K2_LAUNCH_W(IT, TC, false, false);     \
-        }                                               \
-    } while (0)
-    if (A.p.inputType == 0 && A.p.textureCount == 2) K2_LAUNCH(0, 2);
-    else if (A.p.inputType == 1 && A.p.textureCount == 1) K2_LAUNCH(1, 1);
-    else if (A.p.inputType == 2 && A.p.textureCount == 1) K2_LAUNCH(2, 1);
-    else return hipErrorInvalidValue;
-#undef K2_LAUNCH
-#undef K2_LAUNCH_W
-    return hipGetLastError();
+    const bool whole = rfx_views_whole(A.dims.H, A.ssgi, A.velocity, A.hist0, A.hist1, A.out0, A.out1);
+    // three (INPUT_TYPE, TC) pairs exist: diffuseSpecular with two textures, diffuse or specular with one
+    if (A.p.textureCount != (A.p.inputType == 0 ? 2 : 1)) return hipErrorInvalidValue;
+    const bool known = rfx_with_int<0, 1, 2>(A.p.inputType, [&](auto it) {
+        rfx_with_bool(A.p.logTransform != 0, [&](auto lt) {
+            rfx_with_bool(A.hist_f32 != 0, [&](auto hf) {
+                rfx_with_bool(whole, [&](auto wh) {
+                    constexpr int IT = decltype(it)::value;
+                    hipLaunchKernelGGL((k2_temporal_reproject<IT, IT == 0 ? 2 : 1, decltype(lt)::value, decltype(hf)::value, decltype(wh)::value>), grid, block, 0, stream, A);
+                });
+            });
+        });
+    });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }

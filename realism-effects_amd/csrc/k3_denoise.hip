@@ -14,16 +14,15 @@
 #include <type_traits>
 #include "rfx_device.h"
 #include "rfx_kernels.h"
+#include "rfx_launch.h"
 #include "k3_rotation_table.h"
 
 namespace {
 
-constexpr int TW = 64, TH = 8;                 // pixels per workgroup tile (64 x 16, 128 x 8, 64 x 7 measured slower: profiles/r05_k3)
+constexpr int TW = RFX_K3_TW, TH = RFX_K3_TH;  // pixels per workgroup tile (rfx_launch.h, with K3_LDS_MAX: the launch plan sizes the staged tile from them)
 constexpr int NT = TW * TH;                    // threads per workgroup
 static_assert(TW % 64 == 0 && NT <= 1024, "a tile row is whole wavefronts; at most 16 wavefronts per workgroup");
 constexpr int K3_XCD_G = 1;                    // tile rows per XCD group (rfx_xcd_tile); 0 = plain row-major
-constexpr int K3_LDS_MAX = 80 * 1024;          // dynamic LDS a tiled launch may ask for (80 KiB: at least two workgroups per CU; the CU has 160 KiB, handed out in
-                                               // 1 280-byte granules: <= 53 760 B fit three times, <= 40 960 B four times — profiles/r05_microbench/lds_occupancy.txt)
 // The tile is staged with an apron of (Rx, Ry) texels.  The reference rotates the Poisson offsets in UV space
 // (`rm * (offset / resolution)`, poisson_denoise.frag:183-189), so on a W x H frame a tap lies within
 // r = radius * max(1, W/H) pixels horizontally and radius * max(1, H/W) vertically of the pixel centre — NOT in a circle of
@@ -530,10 +529,6 @@ __global__ __launch_bounds__(256) void k3_generic(K3Args A) {
 
 hipError_t rfx_launch_k3(const K3Args &A_in, hipStream_t stream) {
     K3Args A = A_in;
-    const bool temporal = A.p.inputIsTemporal != 0;
-    // apron of the tap footprint: anisotropic because the reference rotates in UV space
-    const float aspect = A.dims.fW / A.dims.fH;
-    const float rx = A.p.radius * fmaxf(1.0f, aspect), ry = A.p.radius * fmaxf(1.0f, 1.0f / aspect);
     {
         const float SQ = 0.25f * 1.41421356237f;
         const float pox[8] = {-1.f, 0.f, 1.f, 0.f, -SQ, SQ, SQ, -SQ};
@@ -544,89 +539,28 @@ hipError_t rfx_launch_k3(const K3Args &A_in, hipStream_t stream) {
             A.tap_oy[k] = oy;
         }
     }
-    // the apron the taps can address (file header); SLACK covers the rounding of the tap coordinate itself (one ulp of vUv * size: 1e-3 pixel
-    // on a 16K frame) — a tap offset that close to a half-integer (nearest) or an integer (linear) boundary stages one texel more
-    const float SLACK = 4e-3f;
-    const auto k3_apron = [&](float r) {  // (never below 1: the 2x2-quad partners and the centre's own LINEAR fetch)
-        const int a = temporal ? (int)floorf(r + 0.5f + SLACK) : (int)floorf(r + SLACK) + 1;
-        return a < 1 ? 1 : a;
-    };
-    A.tile.Rx = k3_apron(rx);
-    A.tile.Ry = k3_apron(ry);
-    A.tile.LW = TW + 2 * A.tile.Rx;
-    A.tile.LH = TH + 2 * A.tile.Ry;
-    A.tile.skip = 0;
-    // LDS row pitch: a compile-time constant of the tiled kernels (the footprint's second row is an immediate offset; padding it by 1 / 2 / 4 texels
-    // moves neither the time nor the bank-conflict share: the conflicts are collisions of per-pixel-rotated taps, profiles/r04_k3)
-    const int pitch = A.tile.LW <= TW + 8 ? TW + 8 : A.tile.LW <= TW + 10 ? TW + 10 : A.tile.LW <= TW + 12 ? TW + 12 : A.tile.LW <= TW + 16 ? TW + 16 : A.tile.LW <= TW + 32 ? TW + 32 : 0;
-    size_t lds = (size_t)pitch * A.tile.LH * (16 + 4 + 2 * (temporal ? 16 : 8));
-    if (temporal && A.p.textureCount == 2 && pitch == A.tile.LW && pitch != 0) {
-        // The corners of the staged rectangle no tap reaches: a tap's offset from its pixel, in pixels, lies in the ellipse (dx / rx)^2 + (dy / ry)^2 <= 1
-        // (the rotation acts in UV space, flatness <= 1, |POISSON[k]| <= 1), and the rectangle's first row is addressed only by the tile's first
-        // row of pixels with dy in [-Ry - 0.5, -Ry + 0.5): there |dx| <= rx * sqrt(1 - ((Ry - 0.5) / ry)^2), i.e. a NEAREST tap reaches at most X texels
-        // sideways and the first Rx - X texels of that row (and, mirrored, the last Rx - X of the last row) are never read.  Pass 0 only (the later
-        // passes' LINEAR footprints reach further and their LDS size is nowhere near a granule boundary).
-        const float t = ((float)A.tile.Ry - 0.5f - SLACK) / ry;
-        const int X = (int)floorf(0.5f + rx * sqrtf(fmaxf(0.0f, 1.0f - t * t)) + SLACK);
-        int skip = A.tile.Rx - X;
-        if (skip > 4) skip = 4;  // (the pad in front of the depth array holds four floats)
-        const int ntex = pitch * A.tile.LH;
-        while (skip > 0 && ((ntex - 2 * skip) & 3) != 0) skip--;  // the float4 arrays behind the depth array stay 16-byte aligned
-        if (skip > 0) {
-            A.tile.skip = skip;
-            lds = 16 + (size_t)(ntex - 2 * skip) * (4 + 16 + 32) + (size_t)skip * 32;  // pad | depth | geometry | interleaved inputs | pad
-        }
-    }
-    // at least two workgroups per CU (160 KiB LDS) keep the staging of one tile under the arithmetic of another (4K: three of either pass kind)
-    const bool tiled = A.p.radius >= 0.0f && pitch != 0 && lds <= (size_t)K3_LDS_MAX;
-    // every view the whole frame (a context that owns no row tile): the kernels skip row rebasing and halo accounting
-    const auto whole_view = [&](const void *ptr, int row0, int rows) { return ptr == nullptr || (row0 == 0 && rows == A.dims.H); };
-    const bool whole = whole_view(A.depth.ptr, A.depth.row0, A.depth.rows) && whole_view(A.gbuffer.ptr, A.gbuffer.row0, A.gbuffer.rows) &&
-                       whole_view(A.in0.ptr, A.in0.row0, A.in0.rows) && whole_view(A.in1.ptr, A.in1.row0, A.in1.rows) &&
-                       whole_view(A.out0.ptr, A.out0.row0, A.out0.rows) && whole_view(A.out1.ptr, A.out1.row0, A.out1.rows);
+    const rfx_k3_tile_plan T = rfx_k3_tile(A.dims.fW, A.dims.fH, A.p.radius, A.p.inputIsTemporal != 0, A.p.textureCount);
+    A.tile.Rx = T.Rx; A.tile.Ry = T.Ry; A.tile.LW = T.LW; A.tile.LH = T.LH; A.tile.skip = T.skip;
+    const bool whole = rfx_views_whole(A.dims.H, A.depth, A.gbuffer, A.in0, A.in1, A.out0, A.out1);
     if (!whole) A.fg_tiles = nullptr;  // the map is indexed by frame-aligned tiles of whole-frame planes
-    if (tiled) {
-        dim3 block(TW, TH), grid(rfx_xcd_grid(K3_XCD_G, (A.dims.W + TW - 1) / TW, (A.y1 - A.y0 + TH - 1) / TH));
-        // the attribute is per device (a process may hold contexts on several): remembered per device ordinal
-#define K3_TILED(T, C, P, WH)                                                                                                \
-    do {                                                                                                                     \
-        static bool attr_set[64] = {false};                                                                                  \
-        int dev = 0;                                                                                                         \
-        hipGetDevice(&dev);                                                                                                  \
-        if (dev < 0 || dev >= 64 || !attr_set[dev]) {                                                                        \
-            hipFuncSetAttribute((const void *)k3_tiled<T, C, P, WH>, hipFuncAttributeMaxDynamicSharedMemorySize, K3_LDS_MAX); \
-            if (dev >= 0 && dev < 64) attr_set[dev] = true;                                                                  \
-        }                                                                                                                    \
-        hipLaunchKernelGGL((k3_tiled<T, C, P, WH>), grid, block, lds, stream, A);                                            \
-    } while (0)
-#define K3_TILED_W(T, C, P) do { if (whole) K3_TILED(T, C, P, true); else K3_TILED(T, C, P, false); } while (0)
-#define K3_TILED_P(T, C)                    \
-    do {                                    \
-        if (pitch == TW + 8) K3_TILED_W(T, C, TW + 8); \
-        else if (pitch == TW + 10) K3_TILED_W(T, C, TW + 10); \
-        else if (pitch == TW + 12) K3_TILED_W(T, C, TW + 12); \
-        else if (pitch == TW + 16) K3_TILED_W(T, C, TW + 16); \
-        else K3_TILED_W(T, C, TW + 32);          \
-    } while (0)
-        if (A.p.textureCount == 2) {
-            if (temporal) K3_TILED_P(true, 2);
-            else K3_TILED_P(false, 2);
-        } else {
-            if (temporal) K3_TILED_P(true, 1);
-            else K3_TILED_P(false, 1);
-        }
-#undef K3_TILED_P
-#undef K3_TILED_W
-#undef K3_TILED
-    } else {
-        dim3 block(64, 4), grid((A.dims.W + 63) / 64, (A.y1 - A.y0 + 3) / 4);
-        if (A.p.textureCount == 2) {
-            if (temporal) hipLaunchKernelGGL((k3_generic<true, 2>), grid, block, 0, stream, A);
-            else hipLaunchKernelGGL((k3_generic<false, 2>), grid, block, 0, stream, A);
-        } else {
-            if (temporal) hipLaunchKernelGGL((k3_generic<true, 1>), grid, block, 0, stream, A);
-            else hipLaunchKernelGGL((k3_generic<false, 1>), grid, block, 0, stream, A);
-        }
-    }
+    rfx_with_bool(A.p.inputIsTemporal != 0, [&](auto temporal) {
+        rfx_with_bool(A.p.textureCount == 2, [&](auto two) {
+            constexpr bool IN_T = decltype(temporal)::value;
+            constexpr int TC = decltype(two)::value ? 2 : 1;
+            if (!T.tiled) {
+                dim3 block(64, 4), grid((A.dims.W + 63) / 64, (A.y1 - A.y0 + 3) / 4);
+                hipLaunchKernelGGL((k3_generic<IN_T, TC>), grid, block, 0, stream, A);
+                return;
+            }
+            dim3 block(TW, TH), grid(rfx_xcd_grid(K3_XCD_G, (A.dims.W + TW - 1) / TW, (A.y1 - A.y0 + TH - 1) / TH));
+            rfx_with_int<TW + 8, TW + 10, TW + 12, TW + 16, TW + 32>(T.pitch, [&](auto pitch) {
+                rfx_with_bool(whole, [&](auto wh) {
+                    constexpr auto kernel = k3_tiled<IN_T, TC, decltype(pitch)::value, decltype(wh)::value>;
+                    rfx_per_device<kernel, bool>([&] { return hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, K3_LDS_MAX) == hipSuccess; });
+                    hipLaunchKernelGGL(kernel, grid, block, T.lds_bytes, stream, A);
+                });
+            });
+        });
+    });
     return hipGetLastError();
 }

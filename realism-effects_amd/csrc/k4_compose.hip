@@ -3,6 +3,7 @@
 // the inline shader :36-86 and src/denoise/shader/denoiser_compose_functions.glsl:53-108.
 // Pure streaming kernel: 52 B/px (4 depth + 16 gbuffer + 2x8 GI in, 16 out).
 #include "k4_compose_texel.h"
+#include "rfx_launch.h"
 
 namespace {
 
@@ -208,8 +209,6 @@ hipError_t rfx_launch_k5(const K5Args &A, hipStream_t stream) {
 
 hipError_t rfx_launch_k4(const K4Args &A, hipStream_t stream) {
     dim3 block(64, 4), grid((A.dims.W + 63) / 64, (A.y1 - A.y0 + 3) / 4);
-    const auto whole_view = [&](const void *ptr, int row0, int rows) { return ptr == nullptr || (row0 == 0 && rows == A.dims.H); };
-    if (whole_view(A.gi0.ptr, A.gi0.row0, A.gi0.rows) && whole_view(A.gi1.ptr, A.gi1.row0, A.gi1.rows)) hipLaunchKernelGGL(k4_compose<true>, grid, block, 0, stream, A);
-    else hipLaunchKernelGGL(k4_compose<false>, grid, block, 0, stream, A);
+    rfx_with_bool(rfx_views_whole(A.dims.H, A.gi0, A.gi1), [&](auto wh) { hipLaunchKernelGGL(k4_compose<decltype(wh)::value>, grid, block, 0, stream, A); });
     return hipGetLastError();
 }

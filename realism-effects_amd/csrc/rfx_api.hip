@@ -7,6 +7,7 @@
 #include <string>
 #include "../../include/rfx.h"
 #include "rfx_kernels.h"
+#include "rfx_launch.h"
 
 #include "rfx_ctx.h"
 
@@ -190,6 +191,19 @@ int rfx_tex_held_rows(const rfx_ctx *c, rfx_tex id, int *row0, int *rows) {
     return RFX_OK;
 }
 
+// The depth slot has a new writer.  Every entry point that can write the slot calls this: the foreground map of the last K1 pre-pass no
+// longer describes the plane (depth_gen, rfx_ctx.h), and the next pre-pass must know what to wait for.
+enum DepthWriter {
+    DEPTH_WRITTEN,   // the write is complete: nothing for the pre-pass to wait for
+    DEPTH_PENDING,   // the caller has just recorded ev_depth behind the write: the pre-pass waits for it on its own stream
+    DEPTH_EXTERNAL,  // written by work this library cannot see, ordered against the draw stream only: the pre-pass stays in the draw stream
+};
+static void depth_new_writer(rfx_ctx *c, DepthWriter w) {
+    if (w == DEPTH_EXTERNAL) c->depth_external = true;
+    else c->depth_event_set = w == DEPTH_PENDING;
+    c->depth_gen++;
+}
+
 static int ensure(rfx_ctx *c, int id) {
     Slot &s = c->slots[id];
     if (s.ptr) return RFX_OK;
@@ -221,10 +235,7 @@ int rfx_upload(rfx_ctx *c, rfx_tex id, const void *host, int row0, int rows) {
     HIPCHK(c, hipMemcpyAsync((char *)s.ptr + (size_t)(row0 - s.row0) * pitch, host, (size_t)rows * pitch, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));  // the caller may free `host` as soon as we return
     s.uploaded = true;
-    if (id == RFX_TEX_DEPTH) {
-        c->depth_event_set = false;  // complete: nothing for the depth pre-pass to wait for
-        c->depth_gen++;              // ... and the foreground map of the last pre-pass no longer describes the plane (rfx_ctx.h)
-    }
+    if (id == RFX_TEX_DEPTH) depth_new_writer(c, DEPTH_WRITTEN);
     return RFX_OK;
 }
 
@@ -303,8 +314,7 @@ int rfx_stage_flip(rfx_ctx *c) {
         if (!s.back_filled) continue;
         if (id == RFX_TEX_DEPTH) {  // the depth pre-pass of the next K1 waits for this copy on its own stream
             HIPCHK(c, hipEventRecord(c->ev_depth, c->upload_stream));
-            c->depth_event_set = true;
-            c->depth_gen++;  // another plane is the depth slot now
+            depth_new_writer(c, DEPTH_PENDING);  // another plane is the depth slot now
         }
         void *t = s.ptr; s.ptr = s.back; s.back = t;
         s.back_filled = false;
@@ -322,8 +332,7 @@ int rfx_clear(rfx_ctx *c, rfx_tex id) {
     HIPCHK(c, hipMemsetAsync(s.ptr, 0, (size_t)s.rows * s.width * s.texel, c->stream));
     if (id == RFX_TEX_DEPTH) {
         HIPCHK(c, hipEventRecord(c->ev_depth, c->stream));
-        c->depth_event_set = true;
-        c->depth_gen++;
+        depth_new_writer(c, DEPTH_PENDING);
     }
     return RFX_OK;
 }
@@ -334,7 +343,7 @@ void *rfx_tex_device_ptr(rfx_ctx *c, rfx_tex id) {
     if (ensure(c, id)) return nullptr;
     // whoever takes the depth plane's address may write it with work this library cannot see (ordered against the draw stream only, as a
     // bound external buffer is): the pre-pass then stays in the draw stream
-    if (id == RFX_TEX_DEPTH) { c->depth_external = true; c->depth_gen++; }
+    if (id == RFX_TEX_DEPTH) depth_new_writer(c, DEPTH_EXTERNAL);
     return c->slots[id].ptr;
 }
 
@@ -349,20 +358,12 @@ int rfx_bind_external(rfx_ctx *c, rfx_tex id, void *device_ptr) {
     s.ptr = device_ptr;
     s.owned = false;
     s.uploaded = true;
-    if (id == RFX_TEX_DEPTH) { c->depth_external = true; c->depth_gen++; }  // written by whoever owns the buffer, ordered against the draw stream only
+    if (id == RFX_TEX_DEPTH) depth_new_writer(c, DEPTH_EXTERNAL);  // written by whoever owns the buffer
     return RFX_OK;
 }
 
-static TexView view(rfx_ctx *c, int id) {
-    TexView v;
-    v.ptr = c->slots[id].ptr; v.row0 = c->slots[id].row0; v.rows = c->slots[id].rows;
-    return v;
-}
-static TexViewW wview(rfx_ctx *c, int id) {
-    TexViewW v;
-    v.ptr = c->slots[id].ptr; v.row0 = c->slots[id].row0; v.rows = c->slots[id].rows;
-    return v;
-}
+static TexView view(rfx_ctx *c, int id) { return {c->slots[id].ptr, c->slots[id].row0, c->slots[id].rows}; }
+static TexViewW wview(rfx_ctx *c, int id) { return {c->slots[id].ptr, c->slots[id].row0, c->slots[id].rows}; }
 // The plane equations of a w x h render target's vUv (rfx_device.h UvPlanes; this file is compiled with -ffp-contract=off: every product
 // below is rounded on its own, as the reference GL's triangle setup rounds them)
 static UvPlanes rfx_uv_planes(int model, int w, int h) {
@@ -475,16 +476,24 @@ int rfx_pack_velocity(rfx_ctx *c, const rfx_aov_velocity *a, int row0, int rows)
     return RFX_OK;
 }
 
+// the importance tables of an environment, and the environment with them
+static void env_tables_release(rfx_ctx *c) {
+    if (c->env_marginal) hipFree(c->env_marginal);
+    if (c->env_conditional) hipFree(c->env_conditional);
+    c->env_marginal = c->env_conditional = nullptr;
+}
+static void env_release(rfx_ctx *c) {
+    if (c->env) hipFree(c->env);
+    c->env = nullptr; c->env_w = c->env_h = c->env_levels = 0;
+    env_tables_release(c);
+}
+
 int rfx_set_environment(rfx_ctx *c, const float *rgba, int width, int height, int halfFloatType, int halfStoreRTZ) {
     if (!c) return RFX_EINVAL;
     RFX_ENTER(c);
     if (!rgba) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (c->env) hipFree(c->env);
-        c->env = nullptr; c->env_w = c->env_h = c->env_levels = 0;
-        if (c->env_marginal) hipFree(c->env_marginal);
-        if (c->env_conditional) hipFree(c->env_conditional);
-        c->env_marginal = c->env_conditional = nullptr;
+        env_release(c);
         return RFX_OK;
     }
     if (width < 1 || height < 1 || width > 16384 || height > 16384 || (width & (width - 1)) || (height & (height - 1)))
@@ -498,19 +507,14 @@ int rfx_set_environment(rfx_ctx *c, const float *rgba, int width, int height, in
         if (w == 1 && h == 1) break;
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->env) hipFree(c->env);
-    c->env = nullptr; c->env_w = c->env_h = c->env_levels = 0;
-    if (c->env_marginal) hipFree(c->env_marginal);  // tables of the previous map: a new one needs its own
-    if (c->env_conditional) hipFree(c->env_conditional);
-    c->env_marginal = c->env_conditional = nullptr;
+    env_release(c);  // (the tables of the previous map too: a new one needs its own)
     hipError_t e = hipMalloc((void **)&c->env, total * sizeof(float4));
     if (e != hipSuccess) return fail(c, RFX_ENOMEM, "hipMalloc(environment)", e);
     // staging copy of the base level, then level 0 = the texels in the texture's type, then the chain
     float4 *stage = nullptr;
     e = hipMalloc((void **)&stage, (size_t)width * height * sizeof(float4));
     if (e != hipSuccess) {
-        hipFree(c->env);
-        c->env = nullptr; c->env_w = c->env_h = c->env_levels = 0;
+        env_release(c);
         return fail(c, RFX_ENOMEM, "hipMalloc(environment staging)", e);
     }
     e = hipMemcpyAsync(stage, rgba, (size_t)width * height * sizeof(float4), hipMemcpyHostToDevice, c->stream);
@@ -524,8 +528,7 @@ int rfx_set_environment(rfx_ctx *c, const float *rgba, int width, int height, in
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // the caller may free `rgba` as soon as we return
     hipFree(stage);
     if (e != hipSuccess) {
-        hipFree(c->env);
-        c->env = nullptr; c->env_w = c->env_h = c->env_levels = 0;
+        env_release(c);
         return fail(c, RFX_EDEVICE, "rfx_set_environment: building the mip chain", e);
     }
     c->env_w = width; c->env_h = height; c->env_levels = levels;
@@ -568,22 +571,18 @@ int rfx_set_environment_importance(rfx_ctx *c, const float *marginal, size_t mar
         return fail(c, RFX_EINVAL, "rfx_set_environment_importance: marginalWeights must hold height floats and conditionalWeights width*height");
     RFX_ENTER(c);
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->env_marginal) hipFree(c->env_marginal);
-    if (c->env_conditional) hipFree(c->env_conditional);
-    c->env_marginal = c->env_conditional = nullptr;
+    env_tables_release(c);
     hipError_t e = hipMalloc((void **)&c->env_marginal, (size_t)c->env_h * sizeof(float));
     if (e == hipSuccess) e = hipMalloc((void **)&c->env_conditional, (size_t)c->env_w * c->env_h * sizeof(float));
     if (e != hipSuccess) {
-        if (c->env_marginal) hipFree(c->env_marginal);
-        c->env_marginal = c->env_conditional = nullptr;
+        env_tables_release(c);
         return fail(c, RFX_ENOMEM, "hipMalloc(environment importance tables)", e);
     }
     e = hipMemcpyAsync(c->env_marginal, marginal, (size_t)c->env_h * sizeof(float), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(c->env_conditional, conditional, (size_t)c->env_w * c->env_h * sizeof(float), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) {  // tables with undefined contents must not pass the importanceSampling validation
-        hipFree(c->env_marginal); hipFree(c->env_conditional);
-        c->env_marginal = c->env_conditional = nullptr;
+        env_tables_release(c);
         return fail(c, RFX_EDEVICE, "rfx_set_environment_importance: copying the tables", e);
     }
     c->env_sum_whole = totalSumWhole; c->env_sum_decimal = totalSumDecimal;
@@ -602,8 +601,14 @@ int rfx_download_environment(rfx_ctx *c, int level, float *rgba, int *levels) {
     return RFX_OK;
 }
 
-// stage 0: rfx_ssgi_march (one launch); 1: rfx_ssgi_trace; 2: rfx_ssgi_shade
-static int ssgi_draw(rfx_ctx *c, const rfx_ssgi_params *p, int stage) {
+// ---- K1: rfx_ssgi_march / _trace / _shade.  ssgi_draw (below) runs these steps in order.
+static int ssgi_history_slot(const rfx_ssgi_params *p) {
+    return p->historySource == 1 ? RFX_TEX_TEMPORAL0 : (p->historySource == 3 ? RFX_TEX_COMPOSE_RGB : RFX_TEX_COMPOSE);
+}
+static float ssgi_resolution_scale(const rfx_ssgi_params *p) { return p->resolutionScale == 0.0f ? 1.0f : p->resolutionScale; }
+
+// step 1: the parameters and the context's state; makes the slots the draw touches
+static int ssgi_validate(rfx_ctx *c, const rfx_ssgi_params *p) {
     if (!c || !p) return RFX_EINVAL;
     if (p->mode != 0 && p->mode != 1) return fail(c, RFX_EINVAL, "rfx_ssgi_march/trace/shade: mode must be 0 (MODE_SSGI) or 1 (MODE_SSR)");
     if (p->importanceSampling && (!p->useEnvMap || !c->env_marginal))
@@ -614,30 +619,71 @@ static int ssgi_draw(rfx_ctx *c, const rfx_ssgi_params *p, int stage) {
     if (p->historySource < 0 || p->historySource > 3) return fail(c, RFX_EINVAL, "rfx_ssgi_march/trace/shade: historySource");
     if (p->historySource == 1 && (c->tile_y0 != 0 || c->tile_rows != c->H))
         return fail(c, RFX_EUNSUPPORTED, "rfx_ssgi_march/trace/shade: historySource TEMPORAL0 (denoiseMode \"temporal\") needs a whole-frame context: K1 gathers it anywhere on screen");
-    const int hist = p->historySource == 1 ? RFX_TEX_TEMPORAL0 : (p->historySource == 3 ? RFX_TEX_COMPOSE_RGB : RFX_TEX_COMPOSE);
-    const int ids[] = {RFX_TEX_DEPTH, RFX_TEX_GBUFFER, RFX_TEX_DIRECT_LIGHT, hist, RFX_TEX_BLUE_NOISE, RFX_TEX_SSGI};
+    const int ids[] = {RFX_TEX_DEPTH, RFX_TEX_GBUFFER, RFX_TEX_DIRECT_LIGHT, ssgi_history_slot(p), RFX_TEX_BLUE_NOISE, RFX_TEX_SSGI};
     int rc = need(c, ids, 6);
     if (rc) return rc;
     if (!c->slots[RFX_TEX_DEPTH].uploaded || !c->slots[RFX_TEX_GBUFFER].uploaded || !c->slots[RFX_TEX_BLUE_NOISE].uploaded)
         return fail(c, RFX_ESTATE, "rfx_ssgi_march/trace/shade: depth / gbuffer / blue-noise not uploaded");
-    K1Args A;
-    A.dims = dims(c);
-    // K2's neighbourhood clamp reads +-2 rows of K1's output: produce them redundantly in the halo
-    bool any = launch_rows(c, RFX_TEX_SSGI, c->halo < 2 ? c->halo : 2, &A.y0, &A.y1);
-    A.out_w = c->W; A.out_h = c->H;
-    const float rs = p->resolutionScale == 0.0f ? 1.0f : p->resolutionScale;
+    const float rs = ssgi_resolution_scale(p);
     if (rs != 1.0f) {  // SSGIPass.setSize :52-57
         const float fw = (float)c->W * rs, fh = (float)c->H * rs;
         if (!(rs > 0.0f && rs <= 1.0f) || fw != floorf(fw) || fh != floorf(fh) || fw < 1.0f || fh < 1.0f)
             return fail(c, RFX_EINVAL, "rfx_ssgi_march/trace/shade: resolutionScale must be in (0, 1] with whole W*s and H*s");
         if (c->tile_y0 != 0 || c->tile_rows != c->H) return fail(c, RFX_EUNSUPPORTED, "rfx_ssgi_march/trace/shade: resolutionScale != 1 needs a whole-frame context");
-        A.out_w = (int)fw; A.out_h = (int)fh;
+    }
+    return RFX_OK;
+}
+
+// step 3: K1's scratch — the view-Z plane, the base cells, the march's table, the tile counter, the foreground maps: all five buffers or none
+static int k1_scratch(rfx_ctx *c, const rfx_k1_table_plan &T, int coarse_w, int coarse_h) {
+    if (c->viewz) return RFX_OK;
+    hipError_t e = hipMalloc((void **)&c->viewz, (size_t)c->W * c->H * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void **)&c->coarse, (size_t)coarse_w * coarse_h * sizeof(float2));
+    if (e == hipSuccess) e = hipMalloc((void **)&c->cells, (size_t)T.vec4 * 16);
+    if (e == hipSuccess) e = hipMalloc((void **)&c->k1_tiles, 64 * 128);
+    // the two foreground maps (rfx_ctx.h): ceil(W / 64) x ceil(H / 8) bytes each, 16 KiB at 4K, in whole 256-byte units (K3 reads a byte's word)
+    c->fg_w = (c->W + 63) / 64;
+    c->fg_stride = (((size_t)c->fg_w * ((c->H + 7) / 8)) + 255) & ~(size_t)255;
+    if (e == hipSuccess) e = hipMalloc((void **)&c->fg_tiles, 2 * c->fg_stride);
+    if (e == hipSuccess) return RFX_OK;
+    // a later draw must not find viewz set and the tables missing
+    if (c->viewz) hipFree(c->viewz);
+    if (c->coarse) hipFree(c->coarse);
+    if (c->cells) hipFree(c->cells);
+    if (c->k1_tiles) hipFree(c->k1_tiles);
+    if (c->fg_tiles) hipFree(c->fg_tiles);
+    c->viewz = nullptr; c->coarse = nullptr; c->cells = nullptr; c->k1_tiles = nullptr; c->fg_tiles = nullptr;
+    return fail(c, RFX_ENOMEM, "hipMalloc(K1 scratch)", e);
+}
+
+// ... and, for a split draw, the trace -> shade hand-over plane
+static int k1_hand_over(rfx_ctx *c, int stage) {
+    if (stage == 0) return RFX_OK;
+    // indexed like the output texture (resolutionScale needs a whole-frame context, so W * held rows covers it)
+    const size_t n = (size_t)c->W * c->slots[RFX_TEX_SSGI].rows * 2;
+    if (stage == 2 && (!c->hits || !c->hits_traced)) return fail(c, RFX_ESTATE, "rfx_ssgi_shade: no rfx_ssgi_trace of this frame to finish");
+    if (!c->hits) {
+        hipError_t e = hipMalloc((void **)&c->hits, n * sizeof(float4));
+        if (e != hipSuccess) return fail(c, RFX_ENOMEM, "hipMalloc(K1 trace hand-over)", e);
+    }
+    return RFX_OK;
+}
+
+// step 4: the argument block (no HIP call).  Returns whether the march has rows to produce.
+static bool k1_args(rfx_ctx *c, const rfx_ssgi_params *p, int stage, const rfx_k1_table_plan &T, int coarse_w, int coarse_h, K1Args &A) {
+    A.dims = dims(c);
+    // K2's neighbourhood clamp reads +-2 rows of K1's output: produce them redundantly in the halo
+    bool any = launch_rows(c, RFX_TEX_SSGI, c->halo < 2 ? c->halo : 2, &A.y0, &A.y1);
+    A.out_w = c->W; A.out_h = c->H;
+    const float rs = ssgi_resolution_scale(p);
+    if (rs != 1.0f) {  // (validated: whole W * rs and H * rs, a whole-frame context)
+        A.out_w = (int)((float)c->W * rs); A.out_h = (int)((float)c->H * rs);
         A.y0 = 0; A.y1 = A.out_h;
         any = true;  // whole-frame contexts only: the row window does not apply to the scaled target
     }
     A.out_uv = rfx_uv_planes(c->uv_model, A.out_w, A.out_h);
     A.depth = view(c, RFX_TEX_DEPTH); A.gbuffer = view(c, RFX_TEX_GBUFFER); A.direct = view(c, RFX_TEX_DIRECT_LIGHT);
-    A.history = view(c, hist);
+    A.history = view(c, ssgi_history_slot(p));
     A.blue = c->slots[RFX_TEX_BLUE_NOISE].ptr;
     blue_noise_shift(p->blueNoiseIndex, &A.shift_x, &A.shift_y);
     A.out = wview(c, RFX_TEX_SSGI);
@@ -646,67 +692,14 @@ static int ssgi_draw(rfx_ctx *c, const rfx_ssgi_params *p, int stage) {
     A.nearMulFar = (float)((double)p->camera.near_ * (double)p->camera.far_);
     A.farMinusNear = (float)((double)p->camera.far_ - (double)p->camera.near_);
     A.nearMinusFar = (float)((double)p->camera.near_ - (double)p->camera.far_);
-    const int base = rfx_k1_base_cell();
-    A.coarse_w = (c->W + base - 1) / base;
-    A.coarse_h = (c->H + base - 1) / base;
-    // the march's table lives in every workgroup's LDS (four workgroups per CU): the cell edge is doubled until the table fits.  Two layouts
-    // (k1_tap_at): rows padded to a power of two, at least 2^cell_shift cells — a tap's LDS address is then two shifts and one v_bitop3_b32 — when
-    // that fits the 36 KiB at the SAME cell size as plain rows of cells_w cells would (4K: 32-texel cells, 128 x 68 cells = 34 KiB; every 16:9
-    // frame); plain rows otherwise (an ultrawide frame, a frame taller than 9216 rows: the padded table of such a frame holds at least H cells)
-    const int table_budget = 36864;
-    const auto k1_table = [&](int shift, bool pow2, int &cw, int &ch, int &pitch, int &pitch_log2) {
-        cw = (c->W + (1 << shift) - 1) >> shift;
-        ch = (c->H + (1 << shift) - 1) >> shift;
-        pitch = cw;
-        pitch_log2 = 0;
-        if (pow2) {
-            pitch_log2 = shift;  // (at least 2^cell_shift cells per row: the row term of k1_tap_at is then a LEFT shift by >= 2)
-            while ((1 << pitch_log2) < cw) pitch_log2++;
-            pitch = 1 << pitch_log2;
-        }
-        return (size_t)((pitch * ch + 3) / 4) * 16;  // bytes, whole uint4s
-    };
-    A.cells_pow2 = 0;
-    for (A.cell_shift = 4;; A.cell_shift++) {
-        if (k1_table(A.cell_shift, false, A.cells_w, A.cells_h, A.cells_pitch, A.cells_pitch_log2) <= (size_t)table_budget || A.cell_shift >= 12) break;
-    }
-    if (RFX_K1_POW2) {
-        int cw, ch, pitch, pl2;
-        if (k1_table(A.cell_shift, true, cw, ch, pitch, pl2) <= (size_t)table_budget) {
-            A.cells_pow2 = 1;
-            A.cells_pitch = pitch;
-            A.cells_pitch_log2 = pl2;
-        }
-    }
-    A.cells_vec4 = (A.cells_pitch * A.cells_h + 3) / 4;
-    if (!c->viewz) {
-        hipError_t e = hipMalloc((void **)&c->viewz, (size_t)c->W * c->H * sizeof(float));
-        if (e == hipSuccess) e = hipMalloc((void **)&c->coarse, (size_t)A.coarse_w * A.coarse_h * sizeof(float2));
-        if (e == hipSuccess) e = hipMalloc((void **)&c->cells, (size_t)A.cells_vec4 * 16);
-        if (e == hipSuccess) e = hipMalloc((void **)&c->k1_tiles, 64 * 128);
-        // the two foreground maps (rfx_ctx.h): ceil(W / 64) x ceil(H / 8) bytes each, 16 KiB at 4K, in whole 256-byte units (K3 reads a byte's word)
-        c->fg_w = (c->W + 63) / 64;
-        c->fg_stride = (((size_t)c->fg_w * ((c->H + 7) / 8)) + 255) & ~(size_t)255;
-        if (e == hipSuccess) e = hipMalloc((void **)&c->fg_tiles, 2 * c->fg_stride);
-        if (e != hipSuccess) {  // all five or none: a later draw must not find viewz set and the tables missing
-            if (c->viewz) hipFree(c->viewz);
-            if (c->coarse) hipFree(c->coarse);
-            if (c->cells) hipFree(c->cells);
-            if (c->k1_tiles) hipFree(c->k1_tiles);
-            if (c->fg_tiles) hipFree(c->fg_tiles);
-            c->viewz = nullptr; c->coarse = nullptr; c->cells = nullptr; c->k1_tiles = nullptr; c->fg_tiles = nullptr;
-            return fail(c, RFX_ENOMEM, "hipMalloc(K1 scratch)", e);
-        }
-    }
-    A.viewz = c->viewz;
-    A.coarse = c->coarse;
-    A.cells = c->cells;
-    A.tile_counter = c->k1_tiles;
-    A.n_cu = c->n_cu;
+    A.coarse_w = coarse_w; A.coarse_h = coarse_h;
+    A.cell_shift = T.cell_shift; A.cells_w = T.cells_w; A.cells_h = T.cells_h;
+    A.cells_pitch = T.pitch; A.cells_pitch_log2 = T.pitch_log2; A.cells_pow2 = T.pow2; A.cells_vec4 = T.vec4;
+    A.viewz = c->viewz; A.coarse = c->coarse; A.cells = c->cells;
+    A.tile_counter = c->k1_tiles; A.n_cu = c->n_cu;
     // the pre-pass fills the foreground map the previous pre-pass did not: that one is still read by the K3 draws queued since (the pre-pass
     // runs under them; it waits for ev_k1_done, i.e. for every draw that read the map it overwrites)
-    const int fg_next = c->fg_cur ^ 1;
-    A.fg_tiles = c->fg_tiles + (size_t)fg_next * c->fg_stride;
+    A.fg_tiles = c->fg_tiles + (size_t)(c->fg_cur ^ 1) * c->fg_stride;
     A.fg_w = c->fg_w;
     A.env = c->env;
     A.env_w = c->env_w; A.env_h = c->env_h; A.env_levels = c->env_levels;
@@ -718,42 +711,44 @@ static int ssgi_draw(rfx_ctx *c, const rfx_ssgi_params *p, int stage) {
         while ((m >> (lg + 1)) > 0) lg++;
         A.maxEnvMapMipLevel = c->env ? (float)(lg + 1) : 0.0f;
     }
-    A.hits = nullptr;
-    if (stage != 0) {
-        // hand-over plane, indexed like the output texture (resolutionScale needs a whole-frame context, so W * held rows covers it)
-        const size_t n = (size_t)c->W * c->slots[RFX_TEX_SSGI].rows * 2;
-        if (stage == 2 && (!c->hits || !c->hits_traced))
-            return fail(c, RFX_ESTATE, "rfx_ssgi_shade: no rfx_ssgi_trace of this frame to finish");
-        if (!c->hits) {
-            hipError_t e = hipMalloc((void **)&c->hits, n * sizeof(float4));
-            if (e != hipSuccess) return fail(c, RFX_ENOMEM, "hipMalloc(K1 trace hand-over)", e);
+    A.hits = stage != 0 ? c->hits : nullptr;
+    return any;
+}
+
+// step 5: the depth pre-pass.  It runs on EVERY draw but the shade stage's (which reuses the trace's): the depth plane is an input that changes
+// every frame.  On its own stream (rfx_ctx.h prep_stream) unless the depth plane lives in a caller's buffer: after the depth plane's last
+// writer and after the previous K1 launch (which read the scratch planes), NOT after the draws queued since — it overlaps them.
+static int k1_prepass(rfx_ctx *c, const K1Args &A) {
+    if (c->depth_external) {
+        ProfScope prof(c, RFX_PROF_K1_PREPASS, c->stream);
+        HIPCHK(c, rfx_launch_k1_prepare(A, c->stream));
+    } else {
+        if (c->depth_event_set) HIPCHK(c, hipStreamWaitEvent(c->prep_stream, c->ev_depth, 0));
+        if (c->k1_event_set) HIPCHK(c, hipStreamWaitEvent(c->prep_stream, c->ev_k1_done, 0));
+        {
+            ProfScope prof(c, RFX_PROF_K1_PREPASS, c->prep_stream);
+            HIPCHK(c, rfx_launch_k1_prepare(A, c->prep_stream));
         }
-        A.hits = c->hits;
+        HIPCHK(c, hipEventRecord(c->ev_prep_done, c->prep_stream));
+        HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_prep_done, 0));
     }
-    // the pre-pass runs on EVERY draw: the depth plane is an input that changes every frame (the shade stage reuses the trace's).
-    // On its own stream (rfx_ctx.h prep_stream) unless the depth plane lives in a caller's buffer: after the depth plane's last writer and
-    // after the previous K1 launch (which read the scratch planes), NOT after the draws queued since — it overlaps them.
-    if (stage != 2) {
-#ifndef RFX_K1_PREP_STREAM
-#define RFX_K1_PREP_STREAM 1  // build knob: 0 = the pre-pass in the draw stream (A/B measurements)
-#endif
-        if (c->depth_external || !RFX_K1_PREP_STREAM) {
-            ProfScope prof(c, RFX_PROF_K1_PREPASS, c->stream);
-            HIPCHK(c, rfx_launch_k1_prepare(A, c->stream));
-        } else {
-            if (c->depth_event_set) HIPCHK(c, hipStreamWaitEvent(c->prep_stream, c->ev_depth, 0));
-            if (c->k1_event_set) HIPCHK(c, hipStreamWaitEvent(c->prep_stream, c->ev_k1_done, 0));
-            {
-                ProfScope prof(c, RFX_PROF_K1_PREPASS, c->prep_stream);
-                HIPCHK(c, rfx_launch_k1_prepare(A, c->prep_stream));
-            }
-            HIPCHK(c, hipEventRecord(c->ev_prep_done, c->prep_stream));
-            HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_prep_done, 0));
-        }
-        c->fg_cur = fg_next;
-        c->fg_gen = c->depth_gen;  // the map describes the depth plane as it is now: every later writer of the slot bumps depth_gen
-    }
-    // the march kernel hands its tiles out from a counter: the pre-pass zeroes it; the shade stage has no pre-pass of its own
+    c->fg_cur ^= 1;            // (the map k1_args pointed the pre-pass at)
+    c->fg_gen = c->depth_gen;  // the map describes the depth plane as it is now: every later writer of the slot bumps depth_gen
+    return RFX_OK;
+}
+
+// stage 0: rfx_ssgi_march (one launch); 1: rfx_ssgi_trace; 2: rfx_ssgi_shade
+static int ssgi_draw(rfx_ctx *c, const rfx_ssgi_params *p, int stage) {
+    int rc = ssgi_validate(c, p);
+    if (rc) return rc;
+    const rfx_k1_table_plan T = rfx_k1_table(c->W, c->H);  // step 2
+    const int base = rfx_k1_base_cell(), coarse_w = (c->W + base - 1) / base, coarse_h = (c->H + base - 1) / base;
+    if ((rc = k1_scratch(c, T, coarse_w, coarse_h))) return rc;
+    if ((rc = k1_hand_over(c, stage))) return rc;
+    K1Args A;
+    const bool any = k1_args(c, p, stage, T, coarse_w, coarse_h, A);
+    if (stage != 2 && (rc = k1_prepass(c, A))) return rc;
+    // step 6: the march.  Its kernel hands its tiles out from a counter: the pre-pass zeroes it; the shade stage has no pre-pass of its own
     if (any && stage == 2) HIPCHK(c, hipMemsetAsync(c->k1_tiles, 0, 64 * 128, c->stream));
     if (any) {
         ProfScope prof(c, RFX_PROF_K1_MARCH, c->stream);
@@ -762,7 +757,17 @@ static int ssgi_draw(rfx_ctx *c, const rfx_ssgi_params *p, int stage) {
     HIPCHK(c, hipEventRecord(c->ev_k1_done, c->stream));  // the next pre-pass overwrites what this launch reads
     c->k1_event_set = true;
     c->hits_traced = stage == 1;
-    if (stage == 1) { c->trace_y0 = A.y0; c->trace_y1 = any ? A.y1 : A.y0; c->trace_missed = p->missedRays; c->trace_scaled = rs != 1.0f; }
+    if (stage == 1) { c->trace_y0 = A.y0; c->trace_y1 = any ? A.y1 : A.y0; c->trace_missed = p->missedRays; c->trace_scaled = ssgi_resolution_scale(p) != 1.0f; }
+    return RFX_OK;
+}
+
+// the two launch plans as built, for the CPU tests (rfx_launch.h)
+int rfx_internal_k1_table(int W, int H, struct rfx_k1_table_plan *out) {
+    *out = rfx_k1_table(W, H);
+    return RFX_OK;
+}
+int rfx_internal_k3_tile(int W, int H, float radius, int inputIsTemporal, int textureCount, struct rfx_k3_tile_plan *out) {
+    *out = rfx_k3_tile((float)W, (float)H, radius, inputIsTemporal != 0, textureCount);
     return RFX_OK;
 }
 

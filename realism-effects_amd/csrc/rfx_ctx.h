@@ -99,6 +99,9 @@ void rfx_peer_release(rfx_ctx *c);  // rfx_peer.hip: called by rfx_destroy (befo
 extern "C" int rfx_internal_hit_rows_enqueue(rfx_ctx *c, int *rows_dev);  // (internal: not part of include/rfx.h)
 // ... and of the traced rays' row masks into the first H words of c->hit_mask_dev (allocated here for `ranks` gathered copies)
 extern "C" int rfx_internal_hit_mask_enqueue(rfx_ctx *c, int ranks);
+// ... and, for the CPU tests: the launch plans of rfx_launch.h as the library computes them (K1's table layout, K3's tile geometry)
+extern "C" int rfx_internal_k1_table(int W, int H, struct rfx_k1_table_plan *out);
+extern "C" int rfx_internal_k3_tile(int W, int H, float radius, int inputIsTemporal, int textureCount, struct rfx_k3_tile_plan *out);
 
 extern thread_local std::string g_create_err;
 

@@ -1,0 +1,127 @@
+// rfx_launch.h — what a launch decides on the host before it launches: K1's table layout, K3's tile geometry, the "whole frame" test, the step
+// from a run-time option to a template argument, and what is remembered per kernel and device.  Host only.  The two plans are pure functions
+// of their arguments (no HIP call, no context): rfx_api.hip exports them as rfx_internal_k1_table / rfx_internal_k3_tile and the CPU tests
+// call them as built (tests/test_k1_table_layout.py, tests/test_k3_tile_geometry.py).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <type_traits>
+
+// ---------------------------------------------------------------- K1: the march's (min, max) table
+// The table lives in every workgroup's LDS (four workgroups per CU): the cell edge is doubled until the table fits.  Two layouts (k1_tap_at):
+// rows padded to a power of two, at least 2^cell_shift cells — a tap's LDS address is then two shifts and one v_bitop3_b32 — when that fits the
+// 36 KiB at the SAME cell size as plain rows of cells_w cells would (4K: 32-texel cells, 128 x 68 cells = 34 KiB; every 16:9 frame); plain rows
+// otherwise (an ultrawide frame, a frame taller than 9216 rows: the padded table of such a frame holds at least H cells)
+constexpr int RFX_K1_TABLE_BYTES = 36864;
+// cells_w x cells_h cells of 2^cell_shift texels; pitch: cells per table row — cells_w (pitch_log2 0) or, pow2, the next power of two, at
+// least 2^cell_shift; vec4: the table in whole uint4s
+struct rfx_k1_table_plan { int cell_shift, cells_w, cells_h, pitch, pitch_log2, pow2, vec4; };
+inline rfx_k1_table_plan rfx_k1_table(int W, int H) {
+    const auto k1_table = [&](int shift, bool pow2, int &cw, int &ch, int &pitch, int &pitch_log2) {
+        cw = (W + (1 << shift) - 1) >> shift;
+        ch = (H + (1 << shift) - 1) >> shift;
+        pitch = cw;
+        pitch_log2 = 0;
+        if (pow2) {
+            pitch_log2 = shift;  // (at least 2^cell_shift cells per row: the row term of k1_tap_at is then a LEFT shift by >= 2)
+            while ((1 << pitch_log2) < cw) pitch_log2++;
+            pitch = 1 << pitch_log2;
+        }
+        return (size_t)((pitch * ch + 3) / 4) * 16;  // bytes, whole uint4s
+    };
+    rfx_k1_table_plan t;
+    t.pow2 = 0;
+    for (t.cell_shift = 4;; t.cell_shift++) {
+        if (k1_table(t.cell_shift, false, t.cells_w, t.cells_h, t.pitch, t.pitch_log2) <= (size_t)RFX_K1_TABLE_BYTES || t.cell_shift >= 12) break;
+    }
+    int cw, ch, pitch, pl2;
+    if (k1_table(t.cell_shift, true, cw, ch, pitch, pl2) <= (size_t)RFX_K1_TABLE_BYTES) {
+        t.pow2 = 1;
+        t.pitch = pitch;
+        t.pitch_log2 = pl2;
+    }
+    t.vec4 = (t.pitch * t.cells_h + 3) / 4;
+    return t;
+}
+
+// ---------------------------------------------------------------- K3: the staged tile
+constexpr int RFX_K3_TW = 64, RFX_K3_TH = 8;  // pixels per workgroup tile (64 x 16, 128 x 8, 64 x 7 measured slower: profiles/r05_k3)
+constexpr int K3_LDS_MAX = 80 * 1024;         // dynamic LDS a tiled launch may ask for (80 KiB: at least two workgroups per CU; the CU has 160 KiB, handed out in
+                                              // 1 280-byte granules: <= 53 760 B fit three times, <= 40 960 B four times — profiles/r05_microbench/lds_occupancy.txt)
+// (Rx, Ry): the apron, LW x LH: the staged rectangle, texels; pitch: its LDS row pitch, a template argument of the tiled kernels (0: the
+// rectangle is wider than any of them); skip: texels shaved off each end of the rectangle (k3_tiled_body); tiled 0: k3_generic
+struct rfx_k3_tile_plan { int Rx, Ry, LW, LH, pitch, skip; size_t lds_bytes; int tiled; };
+inline rfx_k3_tile_plan rfx_k3_tile(float fW, float fH, float radius, bool temporal, int textureCount) {
+    constexpr int TW = RFX_K3_TW, TH = RFX_K3_TH;
+    rfx_k3_tile_plan t;
+    // apron of the tap footprint: anisotropic because the reference rotates in UV space
+    const float aspect = fW / fH;
+    const float rx = radius * fmaxf(1.0f, aspect), ry = radius * fmaxf(1.0f, 1.0f / aspect);
+    // the apron the taps can address (k3_denoise.hip); SLACK covers the rounding of the tap coordinate itself (one ulp of vUv * size: 1e-3 pixel
+    // on a 16K frame) — a tap offset that close to a half-integer (nearest) or an integer (linear) boundary stages one texel more
+    const float SLACK = 4e-3f;
+    const auto k3_apron = [&](float r) {  // (never below 1: the 2x2-quad partners and the centre's own LINEAR fetch)
+        const int a = temporal ? (int)floorf(r + 0.5f + SLACK) : (int)floorf(r + SLACK) + 1;
+        return a < 1 ? 1 : a;
+    };
+    t.Rx = k3_apron(rx);
+    t.Ry = k3_apron(ry);
+    t.LW = TW + 2 * t.Rx;
+    t.LH = TH + 2 * t.Ry;
+    t.skip = 0;
+    // LDS row pitch: a compile-time constant of the tiled kernels (the footprint's second row is an immediate offset; padding it by 1 / 2 / 4 texels
+    // moves neither the time nor the bank-conflict share: the conflicts are collisions of per-pixel-rotated taps, profiles/r04_k3)
+    t.pitch = t.LW <= TW + 8 ? TW + 8 : t.LW <= TW + 10 ? TW + 10 : t.LW <= TW + 12 ? TW + 12 : t.LW <= TW + 16 ? TW + 16 : t.LW <= TW + 32 ? TW + 32 : 0;
+    t.lds_bytes = (size_t)t.pitch * t.LH * (16 + 4 + 2 * (temporal ? 16 : 8));
+    if (temporal && textureCount == 2 && t.pitch == t.LW && t.pitch != 0) {
+        // The corners of the staged rectangle no tap reaches: a tap's offset from its pixel, in pixels, lies in the ellipse (dx / rx)^2 + (dy / ry)^2 <= 1
+        // (the rotation acts in UV space, flatness <= 1, |POISSON[k]| <= 1), and the rectangle's first row is addressed only by the tile's first
+        // row of pixels with dy in [-Ry - 0.5, -Ry + 0.5): there |dx| <= rx * sqrt(1 - ((Ry - 0.5) / ry)^2), i.e. a NEAREST tap reaches at most X texels
+        // sideways and the first Rx - X texels of that row (and, mirrored, the last Rx - X of the last row) are never read.  Pass 0 only (the later
+        // passes' LINEAR footprints reach further and their LDS size is nowhere near a granule boundary).
+        const float q = ((float)t.Ry - 0.5f - SLACK) / ry;
+        const int X = (int)floorf(0.5f + rx * sqrtf(fmaxf(0.0f, 1.0f - q * q)) + SLACK);
+        int skip = t.Rx - X;
+        if (skip > 4) skip = 4;  // (the pad in front of the depth array holds four floats)
+        const int ntex = t.pitch * t.LH;
+        while (skip > 0 && ((ntex - 2 * skip) & 3) != 0) skip--;  // the float4 arrays behind the depth array stay 16-byte aligned
+        if (skip > 0) {
+            t.skip = skip;
+            t.lds_bytes = 16 + (size_t)(ntex - 2 * skip) * (4 + 16 + 32) + (size_t)skip * 32;  // pad | depth | geometry | interleaved inputs | pad
+        }
+    }
+    // at least two workgroups per CU (160 KiB LDS) keep the staging of one tile under the arithmetic of another (4K: three of either pass kind)
+    t.tiled = radius >= 0.0f && t.pitch != 0 && t.lds_bytes <= (size_t)K3_LDS_MAX;
+    return t;
+}
+
+// ---------------------------------------------------------------- shared by the launchers
+// Every view is the whole frame (a context that owns no row tile; a null pointer counts as whole): the kernels then skip row rebasing and
+// halo accounting.  TexView and TexViewW alike.
+template <class... V>
+inline bool rfx_views_whole(int H, const V &...v) {
+    return ((v.ptr == nullptr || (v.row0 == 0 && v.rows == H)) && ...);
+}
+
+// A run-time option becomes a template argument: f is called with the std::integral_constant of the value, and a kernel is instantiated for
+// exactly the values a call lists.  rfx_with_int returns false (and calls nothing) when x is none of Vs.
+template <class F>
+inline void rfx_with_bool(bool b, F &&f) {
+    b ? f(std::true_type{}) : f(std::false_type{});
+}
+template <int... Vs, class F>
+inline bool rfx_with_int(int x, F &&f) {
+    return ((x == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...);
+}
+
+// A value asked for once per kernel and device (a process may hold contexts on several devices): K3's "dynamic-LDS attribute set", K1's
+// blocks per CU.  Beyond 64 device ordinals nothing is remembered.
+template <auto Kernel, class T, class F>
+inline T rfx_per_device(F &&get) {
+    static T value[64];
+    static bool have[64] = {false};
+    int dev = 0;
+    hipGetDevice(&dev);
+    if (dev < 0 || dev >= 64) return get();
+    if (!have[dev]) { value[dev] = get(); have[dev] = true; }
+    return value[dev];
+}

@@ -1,34 +1,36 @@
-"""CPU: the geometry behind K3's staged tile (realism-effects_amd/csrc/k3_denoise.hip, rfx_launch_k3).  The launcher sizes the apron of the
-LDS tile from the taps' reach and — pass 0 — does not hold the corners of the staged rectangle no tap can address (three workgroups per CU
-instead of two at 4K: profiles/r05_k3).  Both are claims about where `rm * (offset / resolution)` (poisson_denoise.frag:183-189)
-can land; this test enumerates the taps — every rotation, every Poisson sample, the whole flatness range — and holds the launcher's formulas,
-restated here line by line, against what it finds."""
-import math
-
+"""CPU: the geometry behind K3's staged tile (realism-effects_amd/csrc/rfx_launch.h, rfx_k3_tile: the plan rfx_launch_k3 launches from).  The
+plan sizes the apron of the LDS tile from the taps' reach and — pass 0 — does not hold the corners of the staged rectangle no tap can address
+(three workgroups per CU instead of two at 4K: profiles/r05_k3).  Both are claims about where `rm * (offset / resolution)`
+(poisson_denoise.frag:183-189) can land; this test enumerates the taps — every rotation, every Poisson sample, the whole flatness range — and
+holds the plan, as the library computes it (the host-simulator build's rfx_internal_k3_tile), against what it finds."""
 import numpy as np
 import pytest
 
-SLACK = 4e-3  # k3_denoise.hip rfx_launch_k3: the rounding of the tap coordinate itself
+from launch_plans import k3_tiles, needs_hostsim
+
+SLACK = 4e-3  # rfx_k3_tile: the rounding of the tap coordinate itself
 SQ = 0.25 * 1.41421356237
 POISSON = [(-1.0, 0.0), (0.0, -1.0), (1.0, 0.0), (0.0, 1.0), (-SQ, -SQ), (SQ, -SQ), (SQ, SQ), (-SQ, SQ)]  # poisson_denoise.frag:91-92
 
+PASS0_SIZES = [(3840, 2160), (1920, 1080), (7680, 4320), (1024, 1024), (1080, 1920), (2560, 1080), (333, 187)]
+PASS0_RADII = [1.0, 1.7, 2.5, 3.0]
+LATER_SIZES = [(3840, 2160), (1024, 1024), (1080, 1920)]
+LATER_RADII = [1.0, 2.5, 3.0]
 
-def launcher_tile(W, H, radius, temporal):
-    """(Rx, Ry, skip) as rfx_launch_k3 computes them (k3_apron, the corner shave)."""
+
+@pytest.fixture(scope="module")
+def plans():
+    """every plan the tests below ask for (two textures), from one child process: (W, H, radius, temporal) -> the plan"""
+    keys = [(W, H, r, True) for W, H in PASS0_SIZES for r in PASS0_RADII] + [(W, H, r, False) for W, H in LATER_SIZES for r in LATER_RADII]
+    return dict(zip(keys, k3_tiles([k + (2,) for k in keys])))
+
+
+def launcher_tile(plans, W, H, radius, temporal):
+    """(Rx, Ry, skip) as rfx_launch_k3 launches with them, and the half-axes of the ellipse the plan's comment claims the taps lie in"""
+    t = plans[(W, H, radius, temporal)]
     aspect = W / H
     rx, ry = radius * max(1.0, aspect), radius * max(1.0, 1.0 / aspect)
-
-    def apron(r):
-        a = int(math.floor(r + 0.5 + SLACK)) if temporal else int(math.floor(r + SLACK)) + 1
-        return max(a, 1)
-
-    Rx, Ry = apron(rx), apron(ry)
-    skip = 0
-    if temporal:
-        t = (Ry - 0.5 - SLACK) / ry
-        X = int(math.floor(0.5 + rx * math.sqrt(max(0.0, 1.0 - t * t)) + SLACK))
-        skip = min(max(Rx - X, 0), 4)
-    return Rx, Ry, skip, rx, ry
+    return t["Rx"], t["Ry"], t["skip"], rx, ry
 
 
 def tap_texel_offsets(W, H, radius):
@@ -46,10 +48,11 @@ def tap_texel_offsets(W, H, radius):
     return dx, dy
 
 
-@pytest.mark.parametrize("W,H", [(3840, 2160), (1920, 1080), (7680, 4320), (1024, 1024), (1080, 1920), (2560, 1080), (333, 187)])
-@pytest.mark.parametrize("radius", [1.0, 1.7, 2.5, 3.0])
-def test_pass0_apron_holds_every_tap_and_the_shaved_corners_hold_none(W, H, radius):
-    Rx, Ry, skip, rx, ry = launcher_tile(W, H, radius, temporal=True)
+@needs_hostsim
+@pytest.mark.parametrize("W,H", PASS0_SIZES)
+@pytest.mark.parametrize("radius", PASS0_RADII)
+def test_pass0_apron_holds_every_tap_and_the_shaved_corners_hold_none(plans, W, H, radius):
+    Rx, Ry, skip, rx, ry = launcher_tile(plans, W, H, radius, temporal=True)
     dx, dy = tap_texel_offsets(W, H, radius)
     # the taps lie in the ellipse the launcher's comment claims
     assert float(((dx / rx) ** 2 + (dy / ry) ** 2).max()) <= 1.0 + 1e-9
@@ -67,20 +70,39 @@ def test_pass0_apron_holds_every_tap_and_the_shaved_corners_hold_none(W, H, radi
             assert not np.any(last_row & (cx > Rx - skip)), "a tap reaches a shaved texel of the last staged row"
 
 
-def test_the_4k_frame_is_the_case_the_shave_was_made_for():
+@needs_hostsim
+def test_the_4k_frame_is_the_case_the_shave_was_made_for(plans):
     """4K, radius 3: 74 x 14 staged texels, two texels shaved at each end -> 53 744 B of LDS, under the 53 760 B that fit three times into a
     CU's 160 KiB of 1 280-byte granules (profiles/r05_microbench/lds_occupancy.txt)."""
-    Rx, Ry, skip, _, _ = launcher_tile(3840, 2160, 3.0, temporal=True)
+    Rx, Ry, skip, _, _ = launcher_tile(plans, 3840, 2160, 3.0, temporal=True)
     assert (Rx, Ry, skip) == (5, 3, 2)
     ntex = (64 + 2 * Rx) * (8 + 2 * Ry)
     lds = 16 + (ntex - 2 * skip) * (4 + 16 + 32) + skip * 32
     assert ntex == 1036 and lds == 53744 and lds <= 42 * 1280 < 1036 * 52
+    # ... and that is what the plan asks for, on every 16:9 frame; a later pass: 76 x 16 texels of 36 B
+    for W, H in ((3840, 2160), (1920, 1080), (7680, 4320)):
+        assert plans[(W, H, 3.0, True)]["lds_bytes"] == 53744 and plans[(W, H, 3.0, True)]["tiled"] == 1
+    assert plans[(3840, 2160, 3.0, False)]["lds_bytes"] == 43776 and plans[(3840, 2160, 3.0, False)]["tiled"] == 1
 
 
-@pytest.mark.parametrize("W,H", [(3840, 2160), (1024, 1024), (1080, 1920)])
-@pytest.mark.parametrize("radius", [1.0, 2.5, 3.0])
-def test_later_passes_apron_holds_every_bilinear_footprint(W, H, radius):
-    Rx, Ry, _, _, _ = launcher_tile(W, H, radius, temporal=False)
+@needs_hostsim
+def test_a_tiled_plan_has_a_row_pitch_that_holds_the_staged_row(plans):
+    extra = [(W, H, r, t, tc) for W, H in ((3840, 2160), (5120, 1440), (1080, 1920), (64, 9300), (97, 55)) for r in (0.0, 0.5, 3.0, 6.0, 12.0, 40.0)
+             for t in (0, 1) for tc in (1, 2)]
+    seen = set()
+    for t in list(plans.values()) + k3_tiles(extra):
+        seen.add(t["tiled"])
+        assert (t["LW"], t["LH"]) == (64 + 2 * t["Rx"], 8 + 2 * t["Ry"]), t
+        if t["tiled"]:
+            assert t["pitch"] >= t["LW"] and t["pitch"] in (72, 74, 76, 80, 96) and t["lds_bytes"] <= 80 * 1024, t
+    assert seen == {0, 1}  # (the generic kernel's cases are among them)
+
+
+@needs_hostsim
+@pytest.mark.parametrize("W,H", LATER_SIZES)
+@pytest.mark.parametrize("radius", LATER_RADII)
+def test_later_passes_apron_holds_every_bilinear_footprint(plans, W, H, radius):
+    Rx, Ry, _, _, _ = launcher_tile(plans, W, H, radius, temporal=False)
     dx, dy = tap_texel_offsets(W, H, radius)
     for s in (-SLACK, 0.0, SLACK):
         # LINEAR: the footprint's lower texel is floor(x + 0.5 + d - 0.5) = x + floor(d), its upper one + 1

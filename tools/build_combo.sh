@@ -1,11 +1,11 @@
 #!/bin/bash
-# development helper: build tuning variants of librfx_hip.so that swap SEVERAL objects at once into variants/ (git-ignored; they travel with
-# gpurun).  Complements build_variants.sh (one file, several define sets).
-#   ./build_combo.sh obj  <objname> <source.hip> "<extra flags>"      compile one object into variants/<objname>.o
-#   ./build_combo.sh link <libname> k1_ssgi=<objname> k3_denoise=<objname> ...   link variants/librfx_<libname>.so, the named objects swapped in
+# development helper: build tuning variants of librfx_hip.so that swap SEVERAL objects at once into realism-effects_amd/csrc/variants/
+# (git-ignored).  Complements build_variants.sh (one file, several define sets).
+#   tools/build_combo.sh obj  <objname> <source.hip> "<extra flags>"      compile one object into variants/<objname>.o
+#   tools/build_combo.sh link <libname> k1_ssgi=<objname> k3_denoise=<objname> ...   link variants/librfx_<libname>.so, the named objects swapped in
 # contraction follows csrc/Makefile (K3 / K4 contract, the rest do not) unless the extra flags say otherwise.
 set -e
-cd "$(dirname "$0")"
+cd "$(dirname "$0")/../realism-effects_amd/csrc"
 mkdir -p variants
 F="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -fno-slp-vectorize -I. -Wno-unused-function -Wno-unused-value -Wno-unused-result"
 case $1 in

@@ -1,9 +1,9 @@
 #!/bin/bash
-# development helper: build tuning variants of librfx_hip.so into variants/ (git-ignored; they travel with gpurun).
-#   ./build_variants.sh <kernel-file-stem> <name>:"<defines>" ...     e.g.  ./build_variants.sh k1_ssgi th4:"-DRFX_K1_TH=4" th8:"-DRFX_K1_TH=8"
+# development helper: build tuning variants of librfx_hip.so into realism-effects_amd/csrc/variants/ (git-ignored).
+#   tools/build_variants.sh <kernel-file-stem> <name>:"<defines>" ...     e.g.  tools/build_variants.sh k1_ssgi th4:"-DRFX_K1_TH=4" th8:"-DRFX_K1_TH=8"
 # time them on the GPU box with tools/time_variants.sh
 set -e
-cd "$(dirname "$0")"
+cd "$(dirname "$0")/../realism-effects_amd/csrc"
 make -s
 mkdir -p variants
 stem=$1; shift

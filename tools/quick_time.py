@@ -8,7 +8,7 @@ from rfx_amd import abi
 from rfx_amd.context import Context
 from rfx_amd.scene import synthetic_frame
 
-if "--lib" in sys.argv:  # a tuning variant of the library (csrc/build_variants.sh) instead of the in-tree build
+if "--lib" in sys.argv:  # a tuning variant of the library (tools/build_variants.sh) instead of the in-tree build
     i = sys.argv.index("--lib")
     abi.set_library_path(sys.argv[i + 1])
     del sys.argv[i:i + 2]
