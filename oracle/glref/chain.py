@@ -357,7 +357,8 @@ class Program:
 
 DEFAULTS = dict(  # src/ssgi/SSGIOptions.js:26-48
     distance=10.0, thickness=10.0, denoiseIterations=1, radius=3.0, phi=0.5, lumaPhi=5.0, depthPhi=2.0, normalPhi=50.0,
-    roughnessPhi=50.0, specularPhi=50.0, envBlur=0.5, steps=20, refineSteps=5, missedRays=False, mode="ssgi", denoiseMode="full", resolutionScale=1.0, orthographic=False)
+    roughnessPhi=50.0, specularPhi=50.0, envBlur=0.5, steps=20, refineSteps=5, missedRays=False, mode="ssgi", denoiseMode="full", resolutionScale=1.0, orthographic=False,
+    logTransform=True)  # (the temporal pass's option as SSGIEffect's Denoiser sets it; false: TemporalReprojectPass.js's own default)
 
 
 class GLRefChain:
@@ -384,8 +385,8 @@ class GLRefChain:
             def rd(name):
                 with open(os.path.join(shader_dir, name + ".frag")) as f:
                     return f.read()
-            if self.o["missedRays"]:
-                raise RuntimeError("prebuilt shaders cover missedRays=false only")
+            if self.o["missedRays"] or not self.o["logTransform"]:
+                raise RuntimeError("prebuilt shaders cover missedRays=false, logTransform=true only")
             self.p_ssgi = Program(rd("ssgi%s%s_%d_%d" % (sfx, ("_envmis" if self.importance is not None else "_env") if env is not None else "",
                                                             self.o["steps"], self.o["refineSteps"])))
             self.p_temporal, self.p_denoise, self.p_compose = Program(rd("temporal" + sfx)), Program(rd("denoise" + sfx)), Program(rd("compose" + sfx))
@@ -398,7 +399,7 @@ class GLRefChain:
             persp = not self.o["orthographic"]  # camera.isPerspectiveCamera -> every pass's PERSPECTIVE_CAMERA define
             self.p_ssgi = Program(assemble_ssgi(self.o["steps"], self.o["refineSteps"], 0, True, self.o["missedRays"], use_envmap=env is not None, perspective=persp,
                                                 importance_sampling=self.importance is not None))
-            self.p_temporal = Program(assemble_temporal(perspective=persp))
+            self.p_temporal = Program(assemble_temporal(perspective=persp, log_transform=bool(self.o["logTransform"])))
             self.p_denoise = Program(assemble_denoise())
             self.p_compose = Program(assemble_compose(perspective=persp))
         W, H = width, height

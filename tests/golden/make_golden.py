@@ -22,6 +22,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.abspath(os.path.join(HERE, "..", ".."))
 sys.path.insert(0, os.path.join(ROOT, "realism-effects_amd"))
 sys.path.insert(0, os.path.join(ROOT, "oracle", "glref"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from rfx_amd.scene import synthetic_frame  # noqa: E402  (input generator only)
 import chain  # noqa: E402
@@ -56,14 +57,18 @@ def cam_arrays(cam, prefix):
 
 
 def run(name, W, H, frames, steps, refine, iterations, ssgi_start=1000, denoise_start=2000, mode="ssgi", missed_rays=False, denoise_mode="full",
-        environment=None, env_blur=0.5, resolution_scale=1.0, ortho_half_height=None, importance_sampling=False):
+        environment=None, env_blur=0.5, resolution_scale=1.0, ortho_half_height=None, importance_sampling=False, log_transform=True,
+        view_offset=False):
+    """log_transform False: the temporal pass without its logTransform define (TemporalReprojectPass.js:24, the pass's own default).
+    view_offset: every frame's camera carries TRAAEffect's jitter of that frame (TAAUtils.js:5-11 setViewOffset: projectionMatrix[8] and [9]
+    are no longer zero) — what SSGIEffect marches with whenever a TRAAEffect is in the chain; the planes are the unjittered camera's."""
     bn = np.fromfile(os.path.join(ROOT, "realism-effects_amd", "data", "blue_noise_128_rgba8.bin"), np.uint8).reshape(128, 128, 4)
     importance = None
     if importance_sampling:  # the half-float map's texels, as the worker converts them (fromHalfFloat) before the CDF pass
         importance = reference_importance(np.ascontiguousarray(environment, np.float32).astype(np.float16).astype(np.float32))
     c = chain.GLRefChain(W, H, bn, steps=steps, refineSteps=refine, denoiseIterations=iterations, mode=mode, missedRays=missed_rays, importance=importance,
                          denoiseMode=denoise_mode, environment=environment, envBlur=env_blur, resolutionScale=resolution_scale,
-                         orthographic=ortho_half_height is not None)
+                         orthographic=ortho_half_height is not None, logTransform=log_transform)
     tc = c.tc
     out = dict(width=W, height=H, frames=frames, steps=steps, refineSteps=refine, denoiseIterations=iterations, ssgi_start=ssgi_start,
                denoise_start=denoise_start, gl_info=chain.GL.info(), mode=mode, textureCount=tc, missedRays=int(missed_rays), denoiseMode=denoise_mode)
@@ -72,11 +77,16 @@ def run(name, W, H, frames, steps, refine, iterations, ssgi_start=1000, denoise_
     if environment is not None:  # scene.environment (HalfFloatType, mipmapped by the effect) + the envBlur option
         out["environment"], out["envBlur"] = environment, env_blur
     out["importanceSampling"] = int(importance_sampling)
+    out["logTransform"], out["viewOffset"] = int(log_transform), int(view_offset)
     if importance is not None:  # what the reference's own JS produced: pins rfx_amd.envmap / js/envmap.js
         out["marginalWeights"], out["conditionalWeights"], out["totalSumValue"] = importance
     si = di = 0
     for fi in range(frames):
         f = synthetic_frame(W, H, fi, ortho_half_height=ortho_half_height)
+        if view_offset:
+            from rfx_amd.effect import r2Sequence
+            from specialisations import view_offset_camera
+            f.camera = view_offset_camera(f.camera, W, H, *r2Sequence[fi + 1])
         c.upload_frame(f)
         k = "f%d_" % fi
         out[k + "depth"], out[k + "gbuffer"], out[k + "velocity"], out[k + "direct"] = f.depth, f.gbuffer, f.velocity, f.direct
@@ -223,6 +233,9 @@ if __name__ == "__main__":
     # reference itself is implementation-defined.
     run("chain_rs050_128x72_s12r3_it1", 128, 72, frames=2, steps=12, refine=3, iterations=1, resolution_scale=0.5)
     run("chain_ortho_120x68_s12r3_it1", 120, 68, frames=3, steps=12, refine=3, iterations=1, ortho_half_height=3.2)  # OrthographicCamera
+    # the two K2 / K1 specialisations no other file reaches: logTransform off, a camera with a view offset
+    run("chain_nolog_96x54_s8r2_it1", 96, 54, frames=2, steps=8, refine=2, iterations=1, log_transform=False)
+    run("chain_viewoffset_96x54_s8r2_it1", 96, 54, frames=2, steps=8, refine=2, iterations=1, view_offset=True)
     for dm in ("full_temporal", "temporal", "denoised"):  # the other Denoiser modes (Denoiser.js:7,41-78)
         run("chain_%s_104x58_s10r2" % dm, 104, 58, frames=3, steps=10, refine=2, iterations=1, denoise_mode=dm)
     run_traa("traa_half_128x72", 128, 72, frames=3, half=True)

@@ -6,6 +6,9 @@ import numpy as np
 
 GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 GOLDENS = ["chain_160x90_s20r5_it1", "chain_97x55_s8r2_it2", "chain_missed_96x54_s12r3_it1"]
+# the same chain with the temporal pass's logTransform off / with TRAAEffect's view offset on every frame's camera (stage-wise only: SSGIEffect
+# itself always sets logTransform and never jitters)
+GOLDEN_VARIANTS = ["chain_nolog_96x54_s8r2_it1", "chain_viewoffset_96x54_s8r2_it1"]
 GOLDEN_SSR = "chain_ssr_128x72_s20r5_it1"
 GOLDEN_ENV = ["chain_env_128x72_s12r3_it1", "chain_envsharp_96x54_s12r3_it1"]  # scene.environment (USE_ENVMAP), envBlur 0.5 / 0.1
 GOLDEN_ORTHO = "chain_ortho_120x68_s12r3_it1"  # OrthographicCamera: every pass without its PERSPECTIVE_CAMERA define

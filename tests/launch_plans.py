@@ -24,6 +24,18 @@ class K3(ctypes.Structure):
 lib.rfx_internal_k1_table.argtypes = [I, I, ctypes.POINTER(K1)]
 lib.rfx_internal_k3_tile.argtypes = [I, I, ctypes.c_float, I, I, ctypes.POINTER(K3)]
 kind, cases = json.load(sys.stdin)
+if kind == "k3_layouts":  # a sweep: only the (pitch, skip) pairs it selects travel back, each with the first case that selected it
+    ws, hs, radii = cases
+    seen = {}
+    t = K3()
+    for W in range(*ws):
+        for H in range(*hs):
+            for r in radii:
+                assert lib.rfx_internal_k3_tile(W, H, r, 1, 2, ctypes.byref(t)) == 0
+                if t.tiled and (t.pitch, t.skip) not in seen:
+                    seen[(t.pitch, t.skip)] = [W, H, r]
+    json.dump([[p, s] + c for (p, s), c in sorted(seen.items())], sys.stdout)
+    sys.exit(0)
 fn, T = (lib.rfx_internal_k1_table, K1) if kind == "k1" else (lib.rfx_internal_k3_tile, K3)
 out = []
 for case in cases:
@@ -53,3 +65,9 @@ def k1_tables(sizes):
 def k3_tiles(cases):
     """[(W, H, radius, inputIsTemporal, textureCount), ...] -> one dict per case: Rx, Ry, LW, LH, pitch, skip, lds_bytes, tiled"""
     return _plans("k3", [[W, H, float(r), int(t), tc] for W, H, r, t, tc in cases])
+
+
+def k3_pass0_layouts(widths, heights, radii):
+    """The (pitch, skip) layouts of the staged rectangle that pass 0 with two textures (the only draw that shaves corners) is planned with
+    over range(*widths) x range(*heights) x radii, tiled plans only: {(pitch, skip): the first (W, H, radius) that selected it}"""
+    return {(p, s): (W, H, r) for p, s, W, H, r in _plans("k3_layouts", [list(widths), list(heights), [float(r) for r in radii]])}

@@ -1,0 +1,161 @@
+"""Test helper (pure Python): which kernel specialisation do the arguments of a draw select?
+
+The launchers of realism-effects_amd/csrc turn run-time options into template arguments (rfx_launch.h rfx_with_bool / rfx_with_int): 54
+k1_ssgi_march kernels, 24 k2_temporal_reproject kernels, 4 k3_generic + 40 k3_tiled kernels, and the staged rectangle of a k3_tiled pass 0 has
+one of a handful of (pitch, skip) layouts.  The functions below return, from what a test hands a draw, the key of the kernel the launcher
+will pick, so that a test can say which specialisation it runs and tests/test_specialisation_cases.py can hold the tables of
+tests/test_gpu_specialisations.py against the full cross products.
+
+What depends on a launch plan — K1's table layout (pow2), K3's tiled / pitch / skip — is asked of the library AS BUILT (rfx_internal_k1_table,
+rfx_internal_k3_tile: `Plans`); the other conditions are written down here a second time, on purpose: rfx_launch_k1's projection test,
+K2's `hist_f32 = historySource == 2`, rfx_views_whole."""
+import ctypes
+import itertools
+
+PROJ = ("general", "perspective", "centred")  # PROJ_GENERAL / PROJ_PERSPECTIVE / PROJ_CENTRED
+STAGES = ("march", "trace", "shade")          # rfx_ssgi_march / rfx_ssgi_trace / rfx_ssgi_shade
+PITCHES = (72, 74, 76, 80, 96)                # the LDS row pitches k3_tiled is instantiated for
+
+# the full cross products
+K1_KEYS = [("k1", proj, pow2, em, stage) for proj in PROJ for pow2 in (0, 1) for em in (0, 1, 2) for stage in STAGES]
+K2_KEYS = [("k2", it, lt, hf, wh) for it, lt, hf, wh in itertools.product((0, 1, 2), (0, 1), (0, 1), (0, 1))]
+K3_GENERIC_KEYS = [("k3_generic", in_t, tc) for in_t in (0, 1) for tc in (1, 2)]
+K3_TILED_KEYS = [("k3_tiled", in_t, tc, pitch, wh) for in_t in (0, 1) for tc in (1, 2) for pitch in PITCHES for wh in (0, 1)]
+K3_KEYS = K3_GENERIC_KEYS + K3_TILED_KEYS
+# what a sweep for the (pitch, skip) layouts of pass 0 covers (test_specialisation_cases.py runs it through the plan export)
+LAYOUT_SWEEP = dict(widths=(2, 261), heights=(2, 201), radii=[0.5 * k for k in range(17)])
+assert (len(K1_KEYS), len(K2_KEYS), len(K3_GENERIC_KEYS), len(K3_TILED_KEYS)) == (54, 24, 4, 40)
+
+
+def key_id(key):
+    """a key as a pytest id: k1-perspective-pow2_0-em2-trace, k2-it0-lt0-hf1-wh0, k3_tiled-in_t1-tc2-pitch74-wh1, k3_generic-in_t0-tc1"""
+    names = {"k1": ("", "pow2_", "em", ""), "k2": ("it", "lt", "hf", "wh"), "k3_generic": ("in_t", "tc"), "k3_tiled": ("in_t", "tc", "pitch", "wh"),
+             "layout": ("pitch", "skip")}[key[0]]
+    return "-".join([key[0]] + ["%s%s" % (n, v) for n, v in zip(names, key[1:])])
+
+
+class _K1Plan(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int) for n in ("cell_shift", "cells_w", "cells_h", "pitch", "pitch_log2", "pow2", "vec4")]
+
+
+class _K3Plan(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int) for n in ("Rx", "Ry", "LW", "LH", "pitch", "skip")] + [("lds_bytes", ctypes.c_size_t), ("tiled", ctypes.c_int)]
+
+
+class Plans:
+    """The two launch plans as built, remembered per argument list.  Plans(lib): from a library loaded in this process (the two exports make
+    no HIP call) — what the -m gpu tests use, on the device and under --hostsim alike.  Plans(): from a child process that loads the
+    host-simulator build (tests/launch_plans.py) — the CPU tests; prime_k1 / prime_k3 ask for a whole list in one child."""
+
+    def __init__(self, lib=None):
+        self.lib, self._k1, self._k3 = lib, {}, {}
+        if lib is not None:
+            lib.rfx_internal_k1_table.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(_K1Plan)]
+            lib.rfx_internal_k3_tile.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_K3Plan)]
+
+    @staticmethod
+    def _k3_args(W, H, radius, temporal, tc):
+        return (int(W), int(H), ctypes.c_float(radius).value, int(bool(temporal)), int(tc))
+
+    def prime_k1(self, sizes):
+        todo = [s for s in {(int(W), int(H)) for W, H in sizes} if s not in self._k1]
+        if self.lib is None and todo:
+            import launch_plans
+            self._k1.update(zip(todo, launch_plans.k1_tables(todo)))
+
+    def prime_k3(self, cases):
+        todo = [c for c in {self._k3_args(*c) for c in cases} if c not in self._k3]
+        if self.lib is None and todo:
+            import launch_plans
+            self._k3.update(zip(todo, launch_plans.k3_tiles(todo)))
+
+    def k1(self, W, H):
+        k = (int(W), int(H))
+        if k not in self._k1 and self.lib is not None:
+            t = _K1Plan()
+            assert self.lib.rfx_internal_k1_table(k[0], k[1], ctypes.byref(t)) == 0
+            self._k1[k] = {n: getattr(t, n) for n, _ in _K1Plan._fields_}
+        self.prime_k1([k])
+        return self._k1[k]
+
+    def k3(self, W, H, radius, temporal, tc):
+        k = self._k3_args(W, H, radius, temporal, tc)
+        if k not in self._k3 and self.lib is not None:
+            t = _K3Plan()
+            assert self.lib.rfx_internal_k3_tile(k[0], k[1], k[2], k[3], k[4], ctypes.byref(t)) == 0
+            self._k3[k] = {n: getattr(t, n) for n, _ in _K3Plan._fields_}
+        self.prime_k3([k])
+        return self._k3[k]
+
+
+def views_whole(H, held):
+    """rfx_views_whole: every view a launch is handed covers the whole frame; `held`: the (row0, rows) of each, as rfx_tex_held_rows reports"""
+    return all((int(r0), int(n)) == (0, int(H)) for r0, n in held)
+
+
+def k2_textures(abi, tp):
+    """the slots rfx_temporal_reproject hands rfx_launch_k2: input, velocity, the two histories, the two targets"""
+    h0 = {0: abi.TEX_DENOISE_B0, 1: abi.TEX_FBCOPY_F16, 2: abi.TEX_FBCOPY_F32}[tp.historySource]
+    h1 = abi.TEX_DENOISE_B1 if (tp.historySource == 0 and tp.textureCount == 2) else h0
+    return (abi.TEX_SSGI, abi.TEX_VELOCITY, h0, h1, abi.TEX_TEMPORAL0, abi.TEX_TEMPORAL1 if tp.textureCount == 2 else abi.TEX_TEMPORAL0)
+
+
+def k3_textures(abi, dp):
+    """the slots rfx_poisson_denoise hands rfx_launch_k3: depth, G-buffer, the two inputs, the two targets"""
+    a, b = (abi.TEX_DENOISE_A0, abi.TEX_DENOISE_A1), (abi.TEX_DENOISE_B0, abi.TEX_DENOISE_B1)
+    ins = (abi.TEX_TEMPORAL0, abi.TEX_TEMPORAL1) if dp.inputIsTemporal else (a if dp.writeToB else b)
+    return (abi.TEX_DEPTH, abi.TEX_GBUFFER) + ins + (b if dp.writeToB else a)
+
+
+def k1_key(plans, sp, W, H, entry):
+    """sp: abi.SsgiParams (its camera carries the projection matrix, its useEnvMap / importanceSampling the environment pair); W x H: the
+    frame; entry: "march" | "trace" | "shade" """
+    assert entry in STAGES
+    P = list(sp.camera.projectionMatrix)
+    persp = all(P[i] == 0.0 for i in (1, 2, 3, 4, 6, 7, 12, 13, 15)) and P[11] == -1.0
+    centred = persp and P[8] == 0.0 and P[9] == 0.0
+    env = sp.useEnvMap != 0
+    mis = env and sp.importanceSampling != 0
+    return ("k1", "centred" if centred else "perspective" if persp else "general", plans.k1(W, H)["pow2"], 2 if mis else 1 if env else 0, entry)
+
+
+def k2_key(tp, whole):
+    """tp: abi.TemporalParams; whole: views_whole of k2_textures"""
+    return ("k2", int(tp.inputType), int(tp.logTransform != 0), int(tp.historySource == 2), int(bool(whole)))
+
+
+def k3_key(plans, dp, W, H, whole):
+    """dp: abi.DenoiseParams; whole: views_whole of k3_textures"""
+    t = plans.k3(W, H, dp.radius, dp.inputIsTemporal != 0, dp.textureCount)
+    in_t, tc = int(dp.inputIsTemporal != 0), 2 if dp.textureCount == 2 else 1
+    return ("k3_tiled", in_t, tc, t["pitch"], int(bool(whole))) if t["tiled"] else ("k3_generic", in_t, tc)
+
+
+def k3_layout(plans, dp, W, H):
+    """("layout", pitch, skip) of the staged rectangle of a tiled draw, None for a k3_generic draw"""
+    t = plans.k3(W, H, dp.radius, dp.inputIsTemporal != 0, dp.textureCount)
+    return ("layout", t["pitch"], t["skip"]) if t["tiled"] else None
+
+
+def view_offset_camera(cam, W, H, x, y, fov_deg=40.0):
+    """`cam` (rfx_amd.scene.Camera, perspective, vertical fov `fov_deg`) after three's PerspectiveCamera.setViewOffset(W, H, x, y, W, H) and
+    updateProjectionMatrix (r151) — what TRAAEffect's jitter does to the camera every frame (TAAUtils.js:5-11): the frustum slides by
+    (x, y) pixels, so projectionMatrix[8] = 2x / W and [9] = -2y / H are no longer zero.  Everything else of the camera is kept."""
+    import dataclasses
+    import math
+
+    import numpy as np
+    from rfx_amd.scene import col_major32
+    near, far, aspect = float(cam.near), float(cam.far), W / H
+    top = near * math.tan(math.radians(fov_deg) * 0.5)
+    height = 2.0 * top
+    width = aspect * height
+    left = -0.5 * width + x * width / W
+    top -= y * height / H
+    right, bottom = left + width, top - height
+    m = np.zeros((4, 4), np.float64)  # Matrix4.makePerspective, m[row, col]
+    m[0, 0], m[0, 2] = 2 * near / (right - left), (right + left) / (right - left)
+    m[1, 1], m[1, 2] = 2 * near / (top - bottom), (top + bottom) / (top - bottom)
+    m[2, 2], m[2, 3] = -(far + near) / (far - near), -2 * far * near / (far - near)
+    m[3, 2] = -1
+    return dataclasses.replace(cam, projectionMatrix=col_major32(m), projectionMatrixInverse=col_major32(np.linalg.inv(m)))

@@ -6,13 +6,18 @@ discarded texel keeps it).  The K3 outputs are also held against the C restateme
 tests/test_gpu_parity.py.
 
 The frames are small (the cases also run thread by thread under --hostsim): 128 x 16 = 2 x 2 map tiles, 97 x 55 = partial tiles at the
-right and top edges."""
+right and top edges.  At 128 x 16 the aspect is 8 and the taps reach 24 texels sideways: no tiled pitch fits and both K3 passes draw k3_generic; the
+same cases therefore also run at 128 x 72, where both passes draw k3_tiled — the kernel whose early return the production frame runs
+(K3_KERNELS below, asserted through tests/specialisations.py from the plans of the loaded library)."""
 import numpy as np
 import pytest
 
 pytestmark = [pytest.mark.gpu, pytest.mark.quick]
 
 STEPS, REFINE = 8, 2
+# the frames of the one-tile cases and the K3 kernel both passes draw there; the carved tile is rows 8-16 x columns 0-64 at either size
+SIZES = [(128, 16), (128, 72)]
+K3_KERNELS = {(128, 16): "k3_generic", (128, 72): "k3_tiled"}
 ONE = np.float32(1.0).view(np.uint32)
 
 
@@ -168,6 +173,20 @@ def check_k3_against_restatement(what, f, blue, sent, out, fi=0):
             assert np.array_equal((g == s).all(-1), (w == s).all(-1)), "%s: the set of discarded texels differs from the restatement's" % what
 
 
+def assert_k3_kernels(W, H):
+    """both K3 passes of draw_frame on a whole-frame W x H context select the kernel K3_KERNELS names"""
+    import specialisations as SP
+    abi = _abi()
+    plans = SP.Plans(abi.load_library())
+    f = ground_frame(W, H)
+    _, _, dp, _ = params(f, f.camera, 0.0)
+    for i in range(2):
+        dp.inputIsTemporal, dp.writeToB = (1, 0)[i], i
+        key = SP.k3_key(plans, dp, W, H, whole=True)
+        assert key[:3] == (K3_KERNELS[(W, H)], (1, 0)[i], 2), key
+        assert key[0] == "k3_generic" or key[4] == 1
+
+
 def one_frame(cls, f, sent, **kw):
     r = cls(f.width, f.height, **kw)
     fill(r.ctx, sent)
@@ -196,9 +215,11 @@ def _variant(name, W, H):
     return f
 
 
-@pytest.mark.parametrize("name", ["background_tile", "corner_pixel", "nan_texel", "all_foreground"])
-def test_one_tile_variants(blue_noise, name):
-    W, H = 128, 16
+# (the 128 x 16 cases keep the ids they had before the second size existed)
+@pytest.mark.parametrize("name,W,H", [pytest.param(n, W, H, id=n if (W, H) == SIZES[0] else "%s-%dx%d" % (n, W, H))
+                                      for W, H in SIZES for n in ("background_tile", "corner_pixel", "nan_texel", "all_foreground")])
+def test_one_tile_variants(blue_noise, name, W, H):
+    assert_k3_kernels(W, H)
     f, sent = _variant(name, W, H), sentinel(W, H)
     got, want = one_frame(WithMap, f, sent), one_frame(NoMap, f, sent)
     assert_same(got, want, name)
@@ -234,10 +255,11 @@ def test_partial_edge_tiles(blue_noise):
     check_k3_against_restatement("partial tiles", f, blue_noise, sent, got)
 
 
-def test_stale_map_is_not_used(blue_noise):
+@pytest.mark.parametrize("W,H", SIZES, ids=["%dx%d" % s for s in SIZES])
+def test_stale_map_is_not_used(blue_noise, W, H):
     """the map describes the depth plane of the last K1 pre-pass: after rfx_upload of another plane (foreground where there was background) a
     K3 draw without a new K1 draw must process those tiles"""
-    W, H = 128, 16
+    assert_k3_kernels(W, H)
     abi = _abi()
     f0, f1 = carve(ground_frame(W, H), slice(8, 16), slice(0, 64)), carve(ground_frame(W, H), slice(0, 8), slice(64, 128))
     sent = sentinel(W, H)
@@ -261,10 +283,11 @@ def test_stale_map_is_not_used(blue_noise):
     check_k3_against_restatement("stale map", f1, blue_noise, sent, outs[0])
 
 
-def test_three_queued_frames_with_a_moving_background():
+@pytest.mark.parametrize("W,H", SIZES, ids=["%dx%d" % s for s in SIZES])
+def test_three_queued_frames_with_a_moving_background(W, H):
     """three frames queued without a synchronisation in between (staged uploads: no entry point waits for the draws): the pre-pass of frame
     n + 1 runs under frame n's K3 draws and must not touch the map they read"""
-    W, H = 128, 16
+    assert_k3_kernels(W, H)
     abi = _abi()
     frames = [carve(ground_frame(W, H, 0), slice(8, 16), slice(0, 64)), carve(ground_frame(W, H, 1), slice(0, 8), slice(0, 128)),
               carve(ground_frame(W, H, 2), slice(8, 16), slice(64, 128))]

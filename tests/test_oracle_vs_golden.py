@@ -35,8 +35,8 @@ def stage_params(g, fi, keep):
     sp = abi.SsgiParams(camera=cam, steps=int(g["steps"]), refineSteps=int(g["refineSteps"]), mode=0, useDirectLight=1, rayDistance=10,
                         thickness=10, envBlur=0.5, blueNoiseIndex=int(g["f%d_ssgi_index" % fi]),
                         missedRays=int(g["missedRays"]) if "missedRays" in g.files else 0)
-    tp = abi.TemporalParams(camera=cam, prevCamera=prev, textureCount=2, inputType=0, logTransform=1, fullAccumulate=0, confidencePower=0.75,
-                            neighborhoodClampIntensity=0.5, maxBlend=1.0, keepData=keep)
+    tp = abi.TemporalParams(camera=cam, prevCamera=prev, textureCount=2, inputType=0, logTransform=int(g["logTransform"]) if "logTransform" in g.files else 1,
+                            fullAccumulate=0, confidencePower=0.75, neighborhoodClampIntensity=0.5, maxBlend=1.0, keepData=keep)
     tp.reprojectSpecular[:] = [0, 1]
     tp.neighborhoodClamp[:] = [0, 1]
     dp = abi.DenoiseParams(radius=3, phi=0.5, lumaPhi=5, depthPhi=2, normalPhi=50, roughnessPhi=50, specularPhi=50, textureCount=2,
@@ -92,7 +92,7 @@ def test_k3_rotation_table_against_libm_sincos(blue_noise):
     assert moved <= 0.01 * 2 * W * H
 
 
-@pytest.mark.parametrize("name", G.GOLDENS)
+@pytest.mark.parametrize("name", G.GOLDENS + G.GOLDEN_VARIANTS)
 def test_stagewise(name, blue_noise):
     """Every pass fed with the GOLDEN outputs of the previous passes."""
     g = G.load(name)
@@ -672,7 +672,7 @@ def _unstable(fn, half, H, W, seeds=24):
     return u
 
 
-@pytest.mark.parametrize("name", G.GOLDENS)
+@pytest.mark.parametrize("name", G.GOLDENS + G.GOLDEN_VARIANTS)
 def test_stagewise_strict_metric_every_flip_proven(name, blue_noise):
     """The golden vectors again, under the round-2 metric (tests/parity.py `strict`): absolute 1e-3 — or adjacent binary16 values for the
     half-stored targets, 1e-5 relative for fp32 ones — and EVERY out-of-tolerance pixel proven unstable by the oracle itself.  No flip
