@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define RFX_ABI_VERSION 20
+#define RFX_ABI_VERSION 21
 
 enum {
     RFX_OK = 0,
@@ -80,6 +80,11 @@ typedef enum rfx_tex {
     RFX_TEX_EFFECT_INPUT,   /* RGBA32F   (ABI 20) a host-filled effect input buffer: what an EffectPass reads as `inputBuffer` when it
                                does not come out of an earlier draw (a downloaded frame, TRAA's input plane ...); rfx_motion_blur */
     RFX_TEX_MOTION_BLUR,    /* RGBA32F   (ABI 20) MotionBlurEffect's output colour (rfx_motion_blur)                              */
+    RFX_TEX_BLUR_SOURCE,    /* RGBA32F   (ABI 21) the plane a ROW-TILED rfx_motion_blur takes its taps from, held WHOLE like RFX_TEX_COMPOSE (frame
+                               row y at y * W): the tile's own rows of the source (rfx_motion_blur_stage) plus the foreign texels the streaks
+                               reach (rfx_motion_blur_gather, or rfx_upload by a host with its own transport).  Allocated on first use: a
+                               whole-frame context and a run without motion blur never pay for it.  Not checkpoint state: rewritten before
+                               every draw that reads it */
     RFX_TEX_COUNT
 } rfx_tex;
 
@@ -197,8 +202,8 @@ typedef struct rfx_final_params {
  * pass's input buffer at vUv (the same slot as the taps); in the reference's README form EffectPass(camera, traaEffect, motionBlurEffect),
  * TRAA's output, traa_compose.frag: the NEAREST texel of RFX_TEX_TEMPORAL0 (TemporalReprojectPass.js:66-67) with alpha 1, while the taps
  * read the pass's input buffer (the plane TRAA's K2 took as its input: RFX_TEX_SSGI in both hosts).  Writes RFX_TEX_MOTION_BLUR.
- * Whole-frame contexts only (a streak can reach anywhere): a row-tiled context gets RFX_EUNSUPPORTED.  Honours rfx_set_row_window and
- * rfx_set_uv_model.  RFX_ESTATE when a host-filled input (RFX_TEX_VELOCITY, RFX_TEX_BLUE_NOISE, RFX_TEX_DIRECT_LIGHT, RFX_TEX_EFFECT_INPUT)
+ * A streak can reach anywhere on screen: a row-tiled context draws only after rfx_motion_blur_stage or rfx_motion_blur_gather armed it for
+ * `source` (below), and gets RFX_EUNSUPPORTED otherwise.  Honours rfx_set_row_window and rfx_set_uv_model.  RFX_ESTATE when a host-filled input (RFX_TEX_VELOCITY, RFX_TEX_BLUE_NOISE, RFX_TEX_DIRECT_LIGHT, RFX_TEX_EFFECT_INPUT)
  * was never uploaded, packed, staged or bound, or a drawn one (RFX_TEX_FINAL, RFX_TEX_TEMPORAL0, RFX_TEX_SSGI) holds nothing yet. */
 typedef struct rfx_motion_blur_params {
     int32_t source;         /* the taps' `inputTexture`: RFX_TEX_FINAL, RFX_TEX_TEMPORAL0, RFX_TEX_DIRECT_LIGHT, RFX_TEX_SSGI or RFX_TEX_EFFECT_INPUT
@@ -344,8 +349,34 @@ int rfx_compose(rfx_ctx *, const rfx_compose_params *);
  * SSGIEffect.update(): background texels take the scene colour (RFX_TEX_DIRECT_LIGHT = the composer's input buffer),
  * the rest the composed GI (RFX_TEX_COMPOSE), fogged when the scene has fog; alpha 1.  Writes RFX_TEX_FINAL. */
 int rfx_final_compose(rfx_ctx *, const rfx_final_params *);
-/* MotionBlurEffect's mainImage (K6, ABI 20): see rfx_motion_blur_params.  Writes RFX_TEX_MOTION_BLUR. */
+/* MotionBlurEffect's mainImage (K6, ABI 20): see rfx_motion_blur_params.  Writes RFX_TEX_MOTION_BLUR.
+ * On a ROW-TILED context (ABI 21) the draw produces the tile rows (row window honoured) once rfx_motion_blur_stage or rfx_motion_blur_gather has
+ * armed it for p->source: the taps, and the `center == -1` fetch, read RFX_TEX_BLUR_SOURCE with whole-frame addressing; velocity, an explicit
+ * centre slot and the output go through the band views like every other tiled draw.  The explicit centre of a row-tiled context is
+ * RFX_TEX_TEMPORAL0 only (NEAREST: the pixel's own texel); any other slot is fetched LINEAR, its footprint leaves the rows the tile draws and no
+ * mask names it: RFX_EUNSUPPORTED, from all four calls.  Arming lasts until the next stage or gather (a gather whose exchange fails disarms), so
+ * a host may draw in row windows.  Not armed: RFX_EUNSUPPORTED (call rfx_motion_blur_stage or rfx_motion_blur_gather first); armed for another
+ * source: RFX_ESTATE.  Bit-identical to the whole-frame context's rows when RFX_TEX_BLUR_SOURCE holds every texel rfx_motion_blur_reach_mask names. */
 int rfx_motion_blur(rfx_ctx *, const rfx_motion_blur_params *);
+/* Which texels of `source` will rfx_motion_blur with these params LOAD for the context's tile rows (intersected with the row window)?  Any
+ * context, no communicator; blocks like rfx_ssgi_hit_mask and uses its format: `rows` must be the frame height, row_mask[y] gets bit b set when
+ * a texel of frame row y in column block b (texel x is in block x * 32 / width) is loaded.  The mask encloses exactly the fetches of
+ * motion_blur.frag:28-40 — all four texels of the LINEAR footprint of each of the samples + 1 taps at mix(startUv, endUv, i / samples), zero-weight
+ * texels included (the kernel loads them and 0 * NaN is NaN) — and, when center == -1, the four texels of the LINEAR `inputColor` fetch at vUv.
+ * A fragment that is not moved (dot(v, v) > 1e-9 false, NaN included) contributes its centre fetch only.  It is not a velocity BOUND: the
+ * reduction (k6_motion_blur_reach) runs the draw's own streak set-up and tap addressing on the tile's velocity texels, the blue-noise table and
+ * the uniforms, without the loads.  Validation and error codes are rfx_motion_blur's. */
+int rfx_motion_blur_reach_mask(rfx_ctx *, const rfx_motion_blur_params *, unsigned int *row_mask, int rows);
+/* Copy the context's tile rows of p->source into RFX_TEX_BLUR_SOURCE at their frame position (on the draw stream) and arm the tiled draw for
+ * that source.  The piece a host with its own transport uses: it then fills the foreign texels the reach mask names with rfx_upload.  On a
+ * whole-frame context: validates and returns (nothing to stage). */
+int rfx_motion_blur_stage(rfx_ctx *, const rfx_motion_blur_params *);
+/* Stage, reach mask, all-gather of the N masks, grouped ncclSend / ncclRecv of the named column blocks from their owners into
+ * RFX_TEX_BLUR_SOURCE: the exchange of rfx_gather_history_rows on this plane.  Runs on the exchange stream, ordered after the draws enqueued so
+ * far (the owners' rows of the source are current once their draw has executed); rfx_comm_wait orders the blur after it.  Waits on the host for
+ * the N masks.  `bytes_received` (may be NULL): what this rank receives.  More than 64 ranks, no RCCL, no communicator: as
+ * rfx_gather_history_rows. */
+int rfx_motion_blur_gather(rfx_ctx *, const rfx_motion_blur_params *, void *ncclComm, size_t *bytes_received);
 
 int rfx_sync(rfx_ctx *);
 
@@ -440,6 +471,7 @@ int rfx_time_end(rfx_ctx *, float *elapsed_ms);
  * a few microseconds per draw: the frame's own time (`value`) is measured without them.  At most 8192 launches are recorded per reset. */
 enum { RFX_PROF_K1_PREPASS = 0, RFX_PROF_K1_MARCH, RFX_PROF_K2, RFX_PROF_K3_PASS0, RFX_PROF_K3_PASSN, RFX_PROF_K4, RFX_PROF_K5,
        RFX_PROF_K6, /* ABI 20: rfx_motion_blur */
+       RFX_PROF_K6_REACH, /* ABI 21: the reach reduction of rfx_motion_blur_reach_mask / rfx_motion_blur_gather */
        RFX_PROF_COUNT };
 int rfx_profile(rfx_ctx *, int enable);
 int rfx_profile_read(rfx_ctx *, float *ms_sum, int *launches);

@@ -97,7 +97,8 @@ rfx_ctx *rfx_create(int device, int width, int height, int tile_y0, int tile_row
         s.texel = texel_bytes(i);
         s.width = width;
         // K1 gathers depth and last frame's composed GI anywhere on screen -> held whole
-        const bool whole = (i == RFX_TEX_DEPTH || i == RFX_TEX_COMPOSE || i == RFX_TEX_COMPOSE_RGB);
+        // ... and a row-tiled motion blur its source (RFX_TEX_BLUR_SOURCE: allocated, like every slot, on first use)
+        const bool whole = (i == RFX_TEX_DEPTH || i == RFX_TEX_COMPOSE || i == RFX_TEX_COMPOSE_RGB || i == RFX_TEX_BLUR_SOURCE);
         s.row0 = whole ? 0 : b0;
         s.rows = whole ? height : b1 - b0;
         if (i == RFX_TEX_BLUE_NOISE) { s.row0 = 0; s.rows = 128; s.width = 128; }
@@ -785,10 +786,8 @@ int rfx_internal_hit_rows_enqueue(rfx_ctx *c, int *rows_dev) {
     return RFX_OK;
 }
 
-int rfx_internal_hit_mask_enqueue(rfx_ctx *c, int ranks) {
-    if (!c->hits || !c->hits_traced) return fail(c, RFX_ESTATE, "rfx_gather_history_rows / rfx_ssgi_hit_mask: no rfx_ssgi_trace of this frame is waiting for its shade");
-    if (c->trace_scaled) return fail(c, RFX_EUNSUPPORTED, "rfx_ssgi_hit_mask / rfx_gather_history_rows: the last rfx_ssgi_trace ran with resolutionScale != 1");
-    RFX_ENTER(c);
+// the row-mask scratch of the bounded gathers (rfx_ctx.h hit_mask_dev / hit_mask_host), sized for `ranks` gathered copies
+static int hit_mask_scratch(rfx_ctx *c, int ranks) {
     if (ranks < 1) ranks = 1;
     if (!c->hit_mask_dev || c->hit_mask_ranks < ranks) {
         if (c->hit_mask_dev) {
@@ -804,6 +803,15 @@ int rfx_internal_hit_mask_enqueue(rfx_ctx *c, int ranks) {
         if (e != hipSuccess) return fail(c, RFX_ENOMEM, "rfx_ssgi_hit_mask: scratch", e);
         c->hit_mask_ranks = ranks;
     }
+    return RFX_OK;
+}
+
+int rfx_internal_hit_mask_enqueue(rfx_ctx *c, int ranks) {
+    if (!c->hits || !c->hits_traced) return fail(c, RFX_ESTATE, "rfx_gather_history_rows / rfx_ssgi_hit_mask: no rfx_ssgi_trace of this frame is waiting for its shade");
+    if (c->trace_scaled) return fail(c, RFX_EUNSUPPORTED, "rfx_ssgi_hit_mask / rfx_gather_history_rows: the last rfx_ssgi_trace ran with resolutionScale != 1");
+    RFX_ENTER(c);
+    int rc = hit_mask_scratch(c, ranks);
+    if (rc) return rc;
     HIPCHK(c, hipMemsetAsync(c->hit_mask_dev, 0, (size_t)c->H * sizeof(unsigned int), c->stream));
     if (c->trace_y1 > c->trace_y0)
         HIPCHK(c, rfx_launch_k1_hit_mask(dims(c), c->trace_y0, c->trace_y1, view(c, RFX_TEX_DEPTH), wview(c, RFX_TEX_SSGI), c->hits, c->trace_missed != 0, c->hit_mask_dev, c->stream));
@@ -995,9 +1003,11 @@ int rfx_final_compose(rfx_ctx *c, const rfx_final_params *p) {
     return RFX_OK;
 }
 
-int rfx_motion_blur(rfx_ctx *c, const rfx_motion_blur_params *p) {
-    if (!c || !p) return RFX_EINVAL;
-    RFX_ENTER(c);
+// ---- K6: rfx_motion_blur and, for row-tiled contexts, its reach mask / stage (the gather is in rfx_comm.hip)
+static bool is_tiled(const rfx_ctx *c) { return c->tile_y0 != 0 || c->tile_rows != c->H; }
+
+// the parameters, then (the draw only) whether a row-tiled context is armed, then the input slots: rfx_motion_blur's codes for all four calls
+static int k6_validate(rfx_ctx *c, const rfx_motion_blur_params *p, bool draw) {
     const auto tap_slot = [](int id) {
         return id == RFX_TEX_FINAL || id == RFX_TEX_TEMPORAL0 || id == RFX_TEX_DIRECT_LIGHT || id == RFX_TEX_SSGI || id == RFX_TEX_EFFECT_INPUT;
     };
@@ -1009,7 +1019,17 @@ int rfx_motion_blur(rfx_ctx *c, const rfx_motion_blur_params *p) {
     for (int k = 0; k < 2; k++)
         if (!(p->resolution[k] > 0.0f) || !(p->resolution[k] <= 65536.0f)) return fail(c, RFX_EINVAL, "rfx_motion_blur: resolution must be in (0, 65536]");
     if (p->frame < 0) return fail(c, RFX_EINVAL, "rfx_motion_blur: frame must be >= 0 (the reference passes frame % 4096)");
-    if (c->tile_y0 != 0 || c->tile_rows != c->H) return fail(c, RFX_EUNSUPPORTED, "rfx_motion_blur: needs a whole-frame context (a streak can reach anywhere)");
+    // a LINEAR footprint at a tile's edge reaches a row the tile does not draw: the source's is gathered (the reach mask names it), another
+    // slot's is not.  TRAA's target is NEAREST: the pixel's own texel
+    if (is_tiled(c) && p->center != -1 && p->center != RFX_TEX_TEMPORAL0)
+        return fail(c, RFX_EUNSUPPORTED, "rfx_motion_blur: on a row-tiled context center must be -1 or RFX_TEX_TEMPORAL0 (another slot is fetched LINEAR, "
+                                         "past the rows the tile draws)");
+    if (draw && is_tiled(c)) {
+        if (c->blur_armed < 0)
+            return fail(c, RFX_EUNSUPPORTED, "rfx_motion_blur: needs a whole-frame context (a streak can reach anywhere), or a row-tiled one armed by "
+                                             "rfx_motion_blur_stage / rfx_motion_blur_gather");
+        if (c->blur_armed != p->source) return fail(c, RFX_ESTATE, "rfx_motion_blur: the row-tiled draw is armed (rfx_motion_blur_stage / rfx_motion_blur_gather) for another source");
+    }
     // host-filled planes must have been uploaded (packed, staged or bound), as K2 / K3 require of theirs; the slots a draw writes
     // (FINAL, TEMPORAL0, SSGI) must at least exist — a draw, an upload or a clear made them
     const auto host_filled = [](int id) {
@@ -1019,15 +1039,21 @@ int rfx_motion_blur(rfx_ctx *c, const rfx_motion_blur_params *p) {
     for (int id : ins)
         if (host_filled(id) ? !c->slots[id].uploaded : !c->slots[id].ptr)
             return fail(c, RFX_ESTATE, "rfx_motion_blur: an input slot holds nothing yet (upload it or draw into it first)");
-    int rc = ensure(c, RFX_TEX_MOTION_BLUR);
-    if (rc) return rc;
-    K6Args A;
+    return RFX_OK;
+}
+
+// the argument block of the draw and of the reach reduction (no HIP call).  Returns whether there are rows to produce.
+static bool k6_args(rfx_ctx *c, const rfx_motion_blur_params *p, K6Args &A) {
+    const int center = p->center == -1 ? p->source : p->center;
+    const bool tiled = is_tiled(c);
     A.dims = dims(c);
-    if (!launch_rows(c, RFX_TEX_MOTION_BLUR, 0, &A.y0, &A.y1)) return RFX_OK;
-    A.velocity = (const float4 *)c->slots[RFX_TEX_VELOCITY].ptr;
-    A.src = (const float4 *)c->slots[p->source].ptr;
-    A.center = (const float4 *)c->slots[center].ptr;
-    A.out = (float4 *)c->slots[RFX_TEX_MOTION_BLUR].ptr;
+    const bool any = launch_rows(c, RFX_TEX_MOTION_BLUR, 0, &A.y0, &A.y1);
+    const Slot &vs = c->slots[RFX_TEX_VELOCITY], &cs = c->slots[center], &os = c->slots[RFX_TEX_MOTION_BLUR];
+    A.velocity = (const float4 *)vs.ptr;
+    // a row-tiled draw takes its taps — and the own-pass centre, the same buffer — from the whole-frame plane the stage / gather filled
+    A.src = (const float4 *)c->slots[tiled ? RFX_TEX_BLUR_SOURCE : p->source].ptr;
+    A.center = (tiled && p->center == -1) ? A.src : (const float4 *)cs.ptr;
+    A.out = (float4 *)os.ptr;
     A.blue = (const uchar4 *)c->slots[RFX_TEX_BLUE_NOISE].ptr;
     blue_noise_shift(p->frame, &A.shift_x, &A.shift_y);
     // center -1: the own EffectPass, inputColor = texture2D(inputBuffer, vUv), LINEAR on the same buffer as the taps.  An explicit
@@ -1045,8 +1071,69 @@ int rfx_motion_blur(rfx_ctx *c, const rfx_motion_blur_params *p) {
     A.frameSpeed = 0.01f / p->deltaTime;  // :25 (1. / 100.) / deltaTime
     A.resX = p->resolution[0];
     A.resY = p->resolution[1];
+    A.tiled = tiled;
+    A.vel_row0 = vs.row0; A.vel_rows = vs.rows;
+    A.center_row0 = cs.row0; A.center_rows = cs.rows;  // (read by the row-tiled draw's NEAREST centre only)
+    A.out_row0 = os.row0; A.out_rows = os.rows;
+    A.center_is_source = p->center == -1;
+    A.reach_mask = nullptr;
+    return any;
+}
+
+int rfx_motion_blur(rfx_ctx *c, const rfx_motion_blur_params *p) {
+    if (!c || !p) return RFX_EINVAL;
+    RFX_ENTER(c);
+    int rc = k6_validate(c, p, true);
+    if (rc) return rc;
+    if ((rc = ensure(c, RFX_TEX_MOTION_BLUR))) return rc;
+    if (is_tiled(c) && (rc = ensure(c, RFX_TEX_BLUR_SOURCE))) return rc;
+    K6Args A;
+    if (!k6_args(c, p, A)) return RFX_OK;
     ProfScope prof(c, RFX_PROF_K6, c->stream);
     HIPCHK(c, rfx_launch_k6(A, c->stream));
+    return RFX_OK;
+}
+
+// enqueue on the draw stream the reach reduction of the tile rows (row window honoured) into the first H words of c->hit_mask_dev
+// (allocated here for `ranks` gathered copies); for rfx_motion_blur_gather in rfx_comm.hip too
+int rfx_internal_blur_reach_enqueue(rfx_ctx *c, const rfx_motion_blur_params *p, int ranks) {
+    RFX_ENTER(c);
+    int rc = hit_mask_scratch(c, ranks);
+    if (rc) return rc;
+    HIPCHK(c, hipMemsetAsync(c->hit_mask_dev, 0, (size_t)c->H * sizeof(unsigned int), c->stream));
+    K6Args A;
+    if (!k6_args(c, p, A)) return RFX_OK;
+    A.reach_mask = c->hit_mask_dev;
+    ProfScope prof(c, RFX_PROF_K6_REACH, c->stream);
+    HIPCHK(c, rfx_launch_k6_reach(A, c->stream));
+    return RFX_OK;
+}
+
+int rfx_motion_blur_reach_mask(rfx_ctx *c, const rfx_motion_blur_params *p, unsigned int *row_mask, int rows) {
+    if (!c || !p || !row_mask) return RFX_EINVAL;
+    RFX_ENTER(c);
+    int rc = k6_validate(c, p, false);
+    if (rc) return rc;
+    if (rows != c->H) return fail(c, RFX_EINVAL, "rfx_motion_blur_reach_mask: one word per frame row (rows == height)");
+    if ((rc = rfx_internal_blur_reach_enqueue(c, p, 1))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->hit_mask_host, c->hit_mask_dev, (size_t)c->H * sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    memcpy(row_mask, c->hit_mask_host, (size_t)c->H * sizeof(unsigned int));
+    return RFX_OK;
+}
+
+int rfx_motion_blur_stage(rfx_ctx *c, const rfx_motion_blur_params *p) {
+    if (!c || !p) return RFX_EINVAL;
+    RFX_ENTER(c);
+    int rc = k6_validate(c, p, false);
+    if (rc) return rc;
+    if (!is_tiled(c)) return RFX_OK;  // the whole-frame draw reads the source itself
+    if ((rc = ensure(c, RFX_TEX_BLUR_SOURCE))) return rc;
+    const Slot &s = c->slots[p->source], &b = c->slots[RFX_TEX_BLUR_SOURCE];
+    const size_t pitch = (size_t)c->W * 16;  // every source slot is read as RGBA32F
+    HIPCHK(c, hipMemcpyAsync((char *)b.ptr + (size_t)c->tile_y0 * pitch, (const char *)s.ptr + (size_t)(c->tile_y0 - s.row0) * pitch, (size_t)c->tile_rows * pitch,
+                             hipMemcpyDeviceToDevice, c->stream));
+    c->blur_armed = p->source;
     return RFX_OK;
 }
 

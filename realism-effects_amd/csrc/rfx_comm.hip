@@ -166,6 +166,105 @@ void rfx_comm_release(rfx_ctx *c) {
     c->comm_pending = false;
 }
 
+// The exchange both bounded gathers share (rfx_gather_history_rows: last frame's composed GI, 3 or 4 floats per texel; rfx_motion_blur_gather:
+// RFX_TEX_BLUR_SOURCE, 4): this tile's row mask is in the first H words of c->hit_mask_dev, enqueued on the draw stream; `id` is a plane held
+// whole whose tile rows every rank owns; `who` is the entry point, for its failure messages.
+static int gather_masked_blocks(rfx_ctx *c, const char *who, Rccl *r, NcclComm comm, rfx_tex id, size_t *bytes_received) {
+    const int n = c->comm_nranks, me = c->comm_rank;
+    int rc;
+    char what[96];
+    char *base = (char *)c->slots[id].ptr;  // held whole: frame row y at y * pitch
+    const Slot &s = c->slots[id];
+    const int H = c->H;
+    // 2. every rank's mask -> host.  The one host-side wait of the exchange: the plan below needs them (H words per rank: 8.6 KB at 4K).
+    if ((rc = comm_begin(c))) return rc;
+    NCCLCHK(c, r->AllGather(c->hit_mask_dev, c->hit_mask_dev + H, (size_t)H, kNcclUint32, comm, c->comm_stream));
+    HIPCHK(c, hipMemcpyAsync(c->hit_mask_host, c->hit_mask_dev + H, sizeof(unsigned int) * (size_t)n * H, hipMemcpyDeviceToHost, c->comm_stream));
+    HIPCHK(c, hipStreamSynchronize(c->comm_stream));
+    // 3. rank p needs the column blocks its mask names; whoever owns their rows packs them into ONE message for p (the owner's rows of last
+    //    frame's composed GI are current: K4 wrote them), p scatters them back.  Both ends walk the same masks in the same order (row by
+    //    row, block by block), so the two sides of every message agree on its size and layout.  Measured on the synthetic orbit
+    //    (tools/history_rows_report.py): the blocks are a quarter of the bytes of the rows they lie in — reflections reach most ROWS
+    //    below the horizon but only part of each.  (Round 3's plan was the (min, max) row interval per rank.)
+    const int W = c->W, fpt = (int)(s.texel / sizeof(float));
+    const unsigned int *mine = c->hit_mask_host + (size_t)me * H;
+    // row offsets (texels) into the per-peer segments of the two stagings; segment bases per peer
+    int *off_host = (int *)(c->hit_mask_host + (size_t)n * H);          // [0, n H): send offsets per peer; [n H, (n + 1) H): receive offsets
+    size_t send_base[65], recv_base[65], send_tex = 0, recv_tex = 0;  // [p]: first texel of peer p's segment, [n]: the total
+    for (int p = 0; p < n; p++) {
+        int py0 = 0, prows = 0;
+        rfx_split_rows(H, n, p, &py0, &prows);
+        const unsigned int *theirs = c->hit_mask_host + (size_t)p * H;
+        send_base[p] = send_tex;
+        recv_base[p] = recv_tex;
+        int *so = off_host + (size_t)p * H;
+        for (int y = 0; y < H; y++) so[y] = -1;
+        if (p == me) continue;
+        size_t k = 0;
+        for (int y = c->tile_y0; y < c->tile_y0 + c->tile_rows; y++)  // what p needs of MY rows
+            if (theirs[y]) { so[y] = (int)k; k += (size_t)hist_row_texels(theirs[y], W); }
+        send_tex += k;
+        k = 0;
+        int *ro = off_host + (size_t)n * H;
+        for (int y = py0; y < py0 + prows; y++) {  // what I need of p's rows
+            ro[y] = -1;
+            if (mine[y]) { ro[y] = (int)k; k += (size_t)hist_row_texels(mine[y], W); }
+        }
+        recv_tex += k;
+    }
+    for (int y = c->tile_y0; y < c->tile_y0 + c->tile_rows; y++) off_host[(size_t)n * H + y] = -1;  // (my own rows: nothing to receive)
+    send_base[n] = send_tex;
+    recv_base[n] = recv_tex;
+    const size_t need = (send_tex + recv_tex) * s.texel;
+    if (need > c->hist_staging_bytes) {
+        if (c->hist_staging) { HIPCHK(c, hipStreamSynchronize(c->comm_stream)); hipFree(c->hist_staging); c->hist_staging = nullptr; c->hist_staging_bytes = 0; }
+        const size_t cap = need + need / 4 + 4096;
+        hipError_t he = hipMalloc((void **)&c->hist_staging, cap);
+        if (he != hipSuccess) {
+            snprintf(what, sizeof what, "%s: staging", who);
+            return fail(c, RFX_ENOMEM, what, he);
+        }
+        c->hist_staging_bytes = cap;
+    }
+    char *send_stage = (char *)c->hist_staging, *recv_stage = send_stage + send_tex * s.texel;
+    int *off_dev = (int *)(c->hit_mask_dev + (size_t)(n + 1) * H);
+    HIPCHK(c, hipMemcpyAsync(off_dev, off_host, sizeof(int) * (size_t)(n + 1) * H, hipMemcpyHostToDevice, c->comm_stream));
+    const dim3 blk(64, 4);
+    for (int p = 0; p < n; p++) {  // pack: one launch per peer over my tile's rows
+        const size_t cnt = send_base[p + 1] - send_base[p];
+        if (p == me || cnt == 0) continue;
+        hipLaunchKernelGGL(hist_pack_rows<true>, dim3((W + 63) / 64, (c->tile_rows + 3) / 4), blk, 0, c->comm_stream, (float *)base, (float *)(send_stage + send_base[p] * s.texel),
+                           (const unsigned int *)(c->hit_mask_dev + (size_t)(1 + p) * H), (const int *)(off_dev + (size_t)p * H), W, c->tile_y0, c->tile_y0 + c->tile_rows, fpt);
+    }
+    HIPCHK(c, hipGetLastError());
+    size_t got = 0;
+    NCCLCHK(c, r->GroupStart());
+    NcclResult e = 0;
+    for (int p = 0; p < n && !e; p++) {
+        if (p == me) continue;
+        const size_t sb = (send_base[p + 1] - send_base[p]) * s.texel, rb = (recv_base[p + 1] - recv_base[p]) * s.texel;
+        if (sb) e = r->Send(send_stage + send_base[p] * s.texel, sb, kNcclUint8, p, comm, c->comm_stream);
+        if (rb && !e) e = r->Recv(recv_stage + recv_base[p] * s.texel, rb, kNcclUint8, p, comm, c->comm_stream);
+        got += rb;
+    }
+    NcclResult e2 = r->GroupEnd();
+    if (e || e2) {
+        snprintf(what, sizeof what, e ? "%s: ncclSend/ncclRecv" : "%s: ncclGroupEnd", who);
+        return nccl_fail(c, what, e ? e : e2);
+    }
+    for (int p = 0; p < n; p++) {  // scatter what arrived: one launch per owner over its rows
+        const size_t cnt = recv_base[p + 1] - recv_base[p];
+        if (p == me || cnt == 0) continue;
+        int py0 = 0, prows = 0;
+        rfx_split_rows(H, n, p, &py0, &prows);
+        hipLaunchKernelGGL(hist_pack_rows<false>, dim3((W + 63) / 64, (prows + 3) / 4), blk, 0, c->comm_stream, (float *)base, (float *)(recv_stage + recv_base[p] * s.texel),
+                           (const unsigned int *)(c->hit_mask_dev + (size_t)(1 + me) * H), (const int *)(off_dev + (size_t)n * H), W, py0, py0 + prows, fpt);
+    }
+    HIPCHK(c, hipGetLastError());
+    if (bytes_received) *bytes_received = got;
+    return comm_end(c);
+}
+
 extern "C" {
 
 int rfx_split_rows(int height, int nranks, int rank, int *tile_y0, int *tile_rows) {
@@ -326,99 +425,36 @@ int rfx_gather_history_rows(rfx_ctx *c, rfx_tex id, void *nccl_comm, size_t *byt
     NcclComm comm = nccl_comm ? nccl_comm : c->comm;
     if (!comm) return fail(c, RFX_ESTATE, "rfx_gather_history_rows: no communicator (rfx_comm_init, or pass one)");
     if (nccl_comm && !c->comm) return fail(c, RFX_ESTATE, "rfx_gather_history_rows: rank and size come from rfx_comm_init");
-    const int n = c->comm_nranks, me = c->comm_rank;
     int rc = ensure_streams(c);
     if (rc) return rc;
     hipSetDevice(c->device);
-    char *base = (char *)rfx_tex_device_ptr(c, id);  // held whole: frame row y at y * pitch
-    if (!base) return RFX_ENOMEM;
-    const Slot &s = c->slots[id];
-    const int H = c->H;
-    if (n > 64) return fail(c, RFX_EUNSUPPORTED, "rfx_gather_history_rows: more than 64 ranks");
+    if (!rfx_tex_device_ptr(c, id)) return RFX_ENOMEM;
+    if (c->comm_nranks > 64) return fail(c, RFX_EUNSUPPORTED, "rfx_gather_history_rows: more than 64 ranks");
     // 1. this tile's row mask (device reduction over the trace's hand-over plane: one word per frame row, a bit per column block), on the draw stream
-    if ((rc = rfx_internal_hit_mask_enqueue(c, n))) return rc;
-    // 2. every rank's mask -> host.  The one host-side wait of the exchange: the plan below needs them (H words per rank: 8.6 KB at 4K).
-    if ((rc = comm_begin(c))) return rc;
-    NCCLCHK(c, r->AllGather(c->hit_mask_dev, c->hit_mask_dev + H, (size_t)H, kNcclUint32, comm, c->comm_stream));
-    HIPCHK(c, hipMemcpyAsync(c->hit_mask_host, c->hit_mask_dev + H, sizeof(unsigned int) * (size_t)n * H, hipMemcpyDeviceToHost, c->comm_stream));
-    HIPCHK(c, hipStreamSynchronize(c->comm_stream));
-    // 3. rank p needs the column blocks its mask names; whoever owns their rows packs them into ONE message for p (the owner's rows of last
-    //    frame's composed GI are current: K4 wrote them), p scatters them back.  Both ends walk the same masks in the same order (row by
-    //    row, block by block), so the two sides of every message agree on its size and layout.  Measured on the synthetic orbit
-    //    (tools/history_rows_report.py): the blocks are a quarter of the bytes of the rows they lie in — reflections reach most ROWS
-    //    below the horizon but only part of each.  (Round 3's plan was the (min, max) row interval per rank.)
-    const int W = c->W, fpt = (int)(s.texel / sizeof(float));
-    const unsigned int *mine = c->hit_mask_host + (size_t)me * H;
-    // row offsets (texels) into the per-peer segments of the two stagings; segment bases per peer
-    int *off_host = (int *)(c->hit_mask_host + (size_t)n * H);          // [0, n H): send offsets per peer; [n H, (n + 1) H): receive offsets
-    size_t send_base[65], recv_base[65], send_tex = 0, recv_tex = 0;  // [p]: first texel of peer p's segment, [n]: the total
-    for (int p = 0; p < n; p++) {
-        int py0 = 0, prows = 0;
-        rfx_split_rows(H, n, p, &py0, &prows);
-        const unsigned int *theirs = c->hit_mask_host + (size_t)p * H;
-        send_base[p] = send_tex;
-        recv_base[p] = recv_tex;
-        int *so = off_host + (size_t)p * H;
-        for (int y = 0; y < H; y++) so[y] = -1;
-        if (p == me) continue;
-        size_t k = 0;
-        for (int y = c->tile_y0; y < c->tile_y0 + c->tile_rows; y++)  // what p needs of MY rows
-            if (theirs[y]) { so[y] = (int)k; k += (size_t)hist_row_texels(theirs[y], W); }
-        send_tex += k;
-        k = 0;
-        int *ro = off_host + (size_t)n * H;
-        for (int y = py0; y < py0 + prows; y++) {  // what I need of p's rows
-            ro[y] = -1;
-            if (mine[y]) { ro[y] = (int)k; k += (size_t)hist_row_texels(mine[y], W); }
-        }
-        recv_tex += k;
-    }
-    for (int y = c->tile_y0; y < c->tile_y0 + c->tile_rows; y++) off_host[(size_t)n * H + y] = -1;  // (my own rows: nothing to receive)
-    send_base[n] = send_tex;
-    recv_base[n] = recv_tex;
-    const size_t need = (send_tex + recv_tex) * s.texel;
-    if (need > c->hist_staging_bytes) {
-        if (c->hist_staging) { HIPCHK(c, hipStreamSynchronize(c->comm_stream)); hipFree(c->hist_staging); c->hist_staging = nullptr; c->hist_staging_bytes = 0; }
-        const size_t cap = need + need / 4 + 4096;
-        hipError_t he = hipMalloc((void **)&c->hist_staging, cap);
-        if (he != hipSuccess) return fail(c, RFX_ENOMEM, "rfx_gather_history_rows: staging", he);
-        c->hist_staging_bytes = cap;
-    }
-    char *send_stage = (char *)c->hist_staging, *recv_stage = send_stage + send_tex * s.texel;
-    int *off_dev = (int *)(c->hit_mask_dev + (size_t)(n + 1) * H);
-    HIPCHK(c, hipMemcpyAsync(off_dev, off_host, sizeof(int) * (size_t)(n + 1) * H, hipMemcpyHostToDevice, c->comm_stream));
-    const dim3 blk(64, 4);
-    for (int p = 0; p < n; p++) {  // pack: one launch per peer over my tile's rows
-        const size_t cnt = send_base[p + 1] - send_base[p];
-        if (p == me || cnt == 0) continue;
-        hipLaunchKernelGGL(hist_pack_rows<true>, dim3((W + 63) / 64, (c->tile_rows + 3) / 4), blk, 0, c->comm_stream, (float *)base, (float *)(send_stage + send_base[p] * s.texel),
-                           (const unsigned int *)(c->hit_mask_dev + (size_t)(1 + p) * H), (const int *)(off_dev + (size_t)p * H), W, c->tile_y0, c->tile_y0 + c->tile_rows, fpt);
-    }
-    HIPCHK(c, hipGetLastError());
-    size_t got = 0;
-    NCCLCHK(c, r->GroupStart());
-    NcclResult e = 0;
-    for (int p = 0; p < n && !e; p++) {
-        if (p == me) continue;
-        const size_t sb = (send_base[p + 1] - send_base[p]) * s.texel, rb = (recv_base[p + 1] - recv_base[p]) * s.texel;
-        if (sb) e = r->Send(send_stage + send_base[p] * s.texel, sb, kNcclUint8, p, comm, c->comm_stream);
-        if (rb && !e) e = r->Recv(recv_stage + recv_base[p] * s.texel, rb, kNcclUint8, p, comm, c->comm_stream);
-        got += rb;
-    }
-    NcclResult e2 = r->GroupEnd();
-    if (e) return nccl_fail(c, "rfx_gather_history_rows: ncclSend/ncclRecv", e);
-    if (e2) return nccl_fail(c, "rfx_gather_history_rows: ncclGroupEnd", e2);
-    for (int p = 0; p < n; p++) {  // scatter what arrived: one launch per owner over its rows
-        const size_t cnt = recv_base[p + 1] - recv_base[p];
-        if (p == me || cnt == 0) continue;
-        int py0 = 0, prows = 0;
-        rfx_split_rows(H, n, p, &py0, &prows);
-        hipLaunchKernelGGL(hist_pack_rows<false>, dim3((W + 63) / 64, (prows + 3) / 4), blk, 0, c->comm_stream, (float *)base, (float *)(recv_stage + recv_base[p] * s.texel),
-                           (const unsigned int *)(c->hit_mask_dev + (size_t)(1 + me) * H), (const int *)(off_dev + (size_t)n * H), W, py0, py0 + prows, fpt);
-    }
-    HIPCHK(c, hipGetLastError());
-    if (bytes_received) *bytes_received = got;
-    return comm_end(c);
+    if ((rc = rfx_internal_hit_mask_enqueue(c, c->comm_nranks))) return rc;
+    return gather_masked_blocks(c, "rfx_gather_history_rows", r, comm, id, bytes_received);
+}
+
+int rfx_motion_blur_gather(rfx_ctx *c, const rfx_motion_blur_params *p, void *nccl_comm, size_t *bytes_received) {
+    if (!c || !p) return RFX_EINVAL;
+    if (bytes_received) *bytes_received = 0;
+    Rccl *r = rccl();
+    if (!r) return fail(c, RFX_EUNSUPPORTED, "rfx_motion_blur_gather: RCCL cannot be loaded on this host");
+    NcclComm comm = nccl_comm ? nccl_comm : c->comm;
+    if (!comm) return fail(c, RFX_ESTATE, "rfx_motion_blur_gather: no communicator (rfx_comm_init, or pass one)");
+    if (nccl_comm && !c->comm) return fail(c, RFX_ESTATE, "rfx_motion_blur_gather: rank and size come from rfx_comm_init");
+    int rc = ensure_streams(c);
+    if (rc) return rc;
+    hipSetDevice(c->device);
+    if (c->comm_nranks > 64) return fail(c, RFX_EUNSUPPORTED, "rfx_motion_blur_gather: more than 64 ranks");
+    // the tile's own rows of the source into the plane (validates the params; arms the draw), then its reach mask: both on the draw stream
+    if ((rc = rfx_motion_blur_stage(c, p))) return rc;
+    // (the stage allocated the plane — except on a whole-frame context, which is a ring of one: no block travels and no plane is needed)
+    if (c->tile_rows != c->H && !c->slots[RFX_TEX_BLUR_SOURCE].ptr) return fail(c, RFX_ESTATE, "rfx_motion_blur_gather: RFX_TEX_BLUR_SOURCE was not staged");
+    if ((rc = rfx_internal_blur_reach_enqueue(c, p, c->comm_nranks)) ||
+        (rc = gather_masked_blocks(c, "rfx_motion_blur_gather", r, comm, RFX_TEX_BLUR_SOURCE, bytes_received)))
+        c->blur_armed = -1;  // the plane holds the tile's own rows only: a draw from it would read stale texels
+    return rc;
 }
 
 int rfx_comm_wait(rfx_ctx *c) {

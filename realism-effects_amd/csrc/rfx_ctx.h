@@ -44,6 +44,7 @@ struct rfx_ctx {
     hipEvent_t ev_depth = nullptr, ev_k1_done = nullptr, ev_prep_done = nullptr;
     bool depth_event_set = false, k1_event_set = false, depth_external = false;
     int win_y0 = 0, win_y1 = 0x7fffffff;  // rfx_set_row_window: rows the draws may produce
+    int blur_armed = -1;  // row-tiled rfx_motion_blur: the source slot RFX_TEX_BLUR_SOURCE was last staged for (rfx_motion_blur_stage / _gather), -1 = none
     int uv_model = RFX_UV_REFERENCE_GL;    // rfx_set_uv_model (the default: the vUv the parity oracle's GL interpolates)
     float2 *coarse = nullptr;  // K1 scratch: exact (min,max) view Z per 16x16 base cell
     unsigned int *cells = nullptr;  // K1 scratch: the march's half-packed (min,max) table
@@ -99,6 +100,8 @@ void rfx_peer_release(rfx_ctx *c);  // rfx_peer.hip: called by rfx_destroy (befo
 extern "C" int rfx_internal_hit_rows_enqueue(rfx_ctx *c, int *rows_dev);  // (internal: not part of include/rfx.h)
 // ... and of the traced rays' row masks into the first H words of c->hit_mask_dev (allocated here for `ranks` gathered copies)
 extern "C" int rfx_internal_hit_mask_enqueue(rfx_ctx *c, int ranks);
+// ... and of the texels a row-tiled rfx_motion_blur with these (validated) params will load, in the same words
+extern "C" int rfx_internal_blur_reach_enqueue(rfx_ctx *c, const rfx_motion_blur_params *p, int ranks);
 // ... and, for the CPU tests: the launch plans of rfx_launch.h as the library computes them (K1's table layout, K3's tile geometry)
 extern "C" int rfx_internal_k1_table(int W, int H, struct rfx_k1_table_plan *out);
 extern "C" int rfx_internal_k3_tile(int W, int H, float radius, int inputIsTemporal, int textureCount, struct rfx_k3_tile_plan *out);

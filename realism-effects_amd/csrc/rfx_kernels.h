@@ -97,7 +97,9 @@ struct K5Args {
 
 hipError_t rfx_launch_k5(const K5Args &, hipStream_t);
 
-// K6 (k4_compose.hip): MotionBlurEffect.  Whole-frame views only (rfx_motion_blur refuses row-tiled contexts).
+// K6 (k4_compose.hip): MotionBlurEffect.  The whole-frame launch addresses every plane by frame row; the row-tiled launch (tiled != 0) reads
+// velocity and an explicit centre, and writes the output, through their held bands (the *_row0 / *_rows pairs at the end of the block) while
+// `src` is RFX_TEX_BLUR_SOURCE, held whole.
 struct K6Args {
     FrameDims dims;
     int y0, y1;
@@ -113,8 +115,16 @@ struct K6Args {
     float div2;                   // samplesFloat + 2
     float intensity, jitter, frameSpeed;  // frameSpeed = RN(0.01 / deltaTime), a uniform expression: the same for every fragment
     float resX, resY;
+    // row-tiled launches and the reach reduction (appended: the whole-frame kernel reads nothing past resY)
+    int tiled;                 // select the band-view kernel
+    int vel_row0, vel_rows, center_row0, center_rows, out_row0, out_rows;  // held bands of velocity / center / out
+    int center_is_source;      // center == -1: inputColor is the LINEAR fetch of `src` at vUv (the reach mask then names its footprint)
+    unsigned int *reach_mask;  // k6_motion_blur_reach: H words, zeroed (one per frame row, a bit per column block)
 };
 hipError_t rfx_launch_k6(const K6Args &, hipStream_t);
+// mask[row] |= 1 << column block for every texel of `src` that rfx_launch_k6 with the same block loads for rows [y0, y1): the draw's streak
+// set-up and tap addressing without the loads (velocity is always read through its band view)
+hipError_t rfx_launch_k6_reach(const K6Args &, hipStream_t);
 int rfx_k1_base_cell();  // edge of k1_prepare's base cells in texels
 hipError_t rfx_launch_k1_prepare(const K1Args &, hipStream_t);
 hipError_t rfx_launch_k1(const K1Args &, int stage /* 0 fused, 1 trace, 2 shade */, hipStream_t);

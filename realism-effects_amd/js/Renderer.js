@@ -28,7 +28,8 @@ const TEX = {
 	FINAL: 15,
 	COMPOSE_RGB: 16,
 	EFFECT_INPUT: 17,
-	MOTION_BLUR: 18
+	MOTION_BLUR: 18,
+	BLUR_SOURCE: 19
 }
 // [TypedArray constructor, elements per texel]
 const FORMAT = {
@@ -50,7 +51,8 @@ const FORMAT = {
 	15: [Float32Array, 4],
 	16: [Float32Array, 3],
 	17: [Float32Array, 4],
-	18: [Float32Array, 4]
+	18: [Float32Array, 4],
+	19: [Float32Array, 4]
 }
 
 // 128x128 RGBA8 blue-noise table: decoded once from the reference's PNG asset, already flipY'd
@@ -202,6 +204,20 @@ class Renderer {
 	// MotionBlurEffect's fragment (K6, rfx_motion_blur) -> TEX.MOTION_BLUR
 	motionBlur(uniforms) {
 		addon.motionBlur(this._h, uniforms)
+	}
+	// a row tile: its rows of the source into TEX.BLUR_SOURCE; arms the tiled motionBlur for that source (rfx_motion_blur_stage)
+	motionBlurStage(uniforms) {
+		addon.motionBlurStage(this._h, uniforms)
+	}
+	// -> Uint32Array(height): bit b of entry y = motionBlur(uniforms) loads a source texel of frame row y in column block b (rfx_motion_blur_reach_mask)
+	motionBlurReachMask(uniforms) {
+		const mask = new Uint32Array(this.height)
+		addon.motionBlurReachMask(this._h, uniforms, mask)
+		return mask
+	}
+	// stage + reach mask + the exchange of the named column blocks over the context's communicator -> bytes received (rfx_motion_blur_gather)
+	motionBlurGather(uniforms) {
+		return addon.motionBlurGather(this._h, uniforms)
 	}
 
 	sync() {

@@ -17,7 +17,9 @@
 // moves no collective at all — each rank's kernel loads what its rays read through HIP IPC mappings (the blobs travel through files too).
 // --motionBlur '{"intensity":1,"jitter":1,"samples":16}' [--deltaTime X] (default 1/60): MotionBlurEffect after every frame — on the device,
 // after SSGIEffect's final image, or with --traa in the README form EffectPass(camera, traaEffect, motionBlurEffect); writes motion_blur.bin
-// of the last frame, and --png / --exr / --pfm write the blurred frame instead of final.bin.  Whole-frame runs only.
+// of the last frame, and --png / --exr / --pfm write the blurred frame instead of final.bin.  With --ranks every rank gathers the source texels
+// its streaks reach from their owners (rfx_motion_blur_gather, js/tiling.js) and writes its rows as motion_blur.rank<r>.bin, which the parent
+// stitches like the other outputs; the image writers stay whole-frame-only, as they are for every tiled run.
 // --saveState DIR [--saveEvery N]: write a checkpoint of the temporal state (js/state.js) into DIR after every N-th frame and after the last;
 // --loadState DIR: restore one first — the dump directories given are then the REMAINING frames, and the outputs are byte-identical to an
 // uninterrupted run.  Both work with --ranks (every rank writes its rows of the whole-frame planes; any rank count loads them), --traa,
@@ -74,7 +76,7 @@ if (opt.ranks > 1 && opt.rank === undefined) {
 			cleanup()
 			if (failed) process.exit(1)
 			// stitch the row tiles (rank order = ascending rows)
-			for (const name of ["final", "compose", "denoise_b0", "denoise_b1", "temporal0", "ssgi"]) {
+			for (const name of ["final", "compose", "denoise_b0", "denoise_b1", "temporal0", "ssgi"].concat(opt.motionBlur ? ["motion_blur"] : [])) {
 				const parts = kids.map((_, q) => fs.readFileSync(path.join(out, name + ".rank" + q + ".bin")))
 				fs.writeFileSync(path.join(out, name + ".bin"), Buffer.concat(parts))
 				kids.forEach((_, q) => fs.unlinkSync(path.join(out, name + ".rank" + q + ".bin")))
@@ -107,11 +109,11 @@ const motionBlur = opt.motionBlur
 const deltaTime = opt.deltaTime === undefined ? 1 / 60 : opt.deltaTime
 delete opt.motionBlur
 delete opt.deltaTime
-if (motionBlur && tiled) throw new Error("--motionBlur needs a whole-frame run (a streak can reach anywhere): drop --ranks")
-// the blurred frame of the last step -> motion_blur.bin (and the images)
+// the blurred frame of the last step -> motion_blur.bin (and the images); a tile writes its own rows, the parent stitches them
 function writeMotionBlur(mb) {
-	const a = mb.output(renderer)
-	fs.writeFileSync(path.join(out, "motion_blur.bin"), Buffer.from(a.buffer, a.byteOffset, a.byteLength))
+	const a = tiled ? mb.output(renderer, renderer.tileY0, renderer.tileRows) : mb.output(renderer)
+	fs.writeFileSync(path.join(out, "motion_blur" + (tiled ? ".rank" + tiled.rank : "") + ".bin"), Buffer.from(a.buffer, a.byteOffset, a.byteLength))
+	if (tiled) return
 	if (images.exr) rfx.writeEXR(images.exr, a, first.width, first.height)
 	if (images.pfm) rfx.writePFM(images.pfm, a, first.width, first.height)
 	if (images.png) rfx.writePNG(images.png, rfx.tonemap(a, first.width, first.height, images.tonemap, images.exposure), first.width, first.height, 3)

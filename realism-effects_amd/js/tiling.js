@@ -11,6 +11,10 @@
 //                                      the traced rays will read, from their owners (rfx_gather_history_rows); "peer" (usePeerHistory)
 //                                      has this rank's own kernel load those column blocks out of the owners' planes through HIP IPC
 //                                      mappings (rfx_peer_*): no collective, no host wait
+//   before a motion blur (K6)        : a streak's taps can land anywhere on screen, but where is known before the draw: the tile's rows of
+//                                      the source are staged into the whole-frame plane TEX.BLUR_SOURCE, the device reduces the mask of
+//                                      source texels the draw will load, the masks are all-gathered and only the named column blocks travel
+//                                      from their owners (rfx_motion_blur_gather); then commWait and the draw
 const addon = require("../napi/rfx_napi.node")
 const { Renderer, TEX } = require("./Renderer")
 
@@ -39,6 +43,7 @@ class TiledRenderer {
 			haloExchange: (tex, up, down) => addon.haloExchange(this.inner._h, tex, up, down),
 			allgatherHistory: tex => addon.allgatherHistory(this.inner._h, tex),
 			gatherHistoryRows: tex => addon.gatherHistoryRows(this.inner._h, tex),
+			motionBlurGather: u => addon.motionBlurGather(this.inner._h, u),
 			peerExport: tex => addon.peerExport(this.inner._h, tex),
 			peerOpen: (tex, blobs, rank, nranks) => addon.peerOpen(this.inner._h, tex, blobs, rank, nranks),
 			peerGatherHistory: tex => addon.peerGatherHistory(this.inner._h, tex),
@@ -59,6 +64,7 @@ class TiledRenderer {
 		this.historyGather = nranks > 1 ? (options.historyGather || "all") : "all"
 		if (this.historyGather !== "bounded" && this.historyGather !== "all") throw new RangeError("historyGather: \"bounded\" or \"all\" (\"peer\": usePeerHistory)")
 		this.historyBytesReceived = []
+		this.blurBytesReceived = [] // per motionBlur(): the source texels this rank received
 		this._haloPending = false
 		this._gatherPending = false
 		this.exchangeCount = 0
@@ -163,6 +169,13 @@ class TiledRenderer {
 	finalCompose(u) {
 		this.commWait()
 		this.inner.finalCompose(u)
+	}
+	// K6 behind the C ABI: rfx_motion_blur_gather (stage, reach mask, the column blocks from their owners), rfx_comm_wait, the draw
+	motionBlur(u) {
+		this.blurBytesReceived.push(this._comm.motionBlurGather(u))
+		this._gatherPending = true
+		this.commWait()
+		this.inner.motionBlur(u)
 	}
 	_interiorFirst(draw) {
 		if (!this._haloPending) return draw()

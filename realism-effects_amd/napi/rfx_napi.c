@@ -712,29 +712,84 @@ static napi_value n_final(napi_env env, napi_callback_info info) {
     return NULL;
 }
 
-/* motionBlur(ctx, {source, center, centerAlphaOne, samples, intensity, jitter, deltaTime, frame, resolution[2], targetHalf, halfStoreRTZ})
- * — MotionBlurEffect's fragment (K6, rfx_motion_blur) -> RFX_TEX_MOTION_BLUR */
+/* the uniforms object of the four motion-blur calls: {source, center, centerAlphaOne, samples, intensity, jitter, deltaTime, frame, resolution[2],
+ * targetHalf, halfStoreRTZ} -> rfx_motion_blur_params.  Returns 0 (a type error is pending) when `resolution` is malformed. */
+static int motion_blur_params(napi_env env, napi_value o, const char *who, rfx_motion_blur_params *p) {
+    memset(p, 0, sizeof *p);
+    p->source = (int32_t)prop_num(env, o, "source", RFX_TEX_FINAL);
+    p->center = (int32_t)prop_num(env, o, "center", -1);
+    p->centerAlphaOne = (int32_t)prop_num(env, o, "centerAlphaOne", 0);
+    p->samples = (int32_t)prop_num(env, o, "samples", 16);
+    p->intensity = (float)prop_num(env, o, "intensity", 1);
+    p->jitter = (float)prop_num(env, o, "jitter", 1);
+    p->deltaTime = (float)prop_num(env, o, "deltaTime", 0);
+    p->frame = (int32_t)prop_num(env, o, "frame", 0);
+    if (!prop_floats(env, o, "resolution", p->resolution, 2)) {
+        char msg[96];
+        snprintf(msg, sizeof msg, "%s: resolution must hold 2 numbers", who);
+        napi_throw_type_error(env, NULL, msg);
+        return 0;
+    }
+    p->targetHalf = (int32_t)prop_num(env, o, "targetHalf", 0);
+    p->halfStoreRTZ = (int32_t)prop_num(env, o, "halfStoreRTZ", 1);
+    return 1;
+}
+/* motionBlur(ctx, uniforms) — MotionBlurEffect's fragment (K6, rfx_motion_blur) -> RFX_TEX_MOTION_BLUR */
 static napi_value n_motion_blur(napi_env env, napi_callback_info info) {
     napi_value a[2];
     if (!get_args(env, info, 2, a)) return NULL;
     rfx_ctx *c = get_ctx(env, a[0]);
     if (!c) return NULL;
     rfx_motion_blur_params p;
-    memset(&p, 0, sizeof p);
-    p.source = (int32_t)prop_num(env, a[1], "source", RFX_TEX_FINAL);
-    p.center = (int32_t)prop_num(env, a[1], "center", -1);
-    p.centerAlphaOne = (int32_t)prop_num(env, a[1], "centerAlphaOne", 0);
-    p.samples = (int32_t)prop_num(env, a[1], "samples", 16);
-    p.intensity = (float)prop_num(env, a[1], "intensity", 1);
-    p.jitter = (float)prop_num(env, a[1], "jitter", 1);
-    p.deltaTime = (float)prop_num(env, a[1], "deltaTime", 0);
-    p.frame = (int32_t)prop_num(env, a[1], "frame", 0);
-    if (!prop_floats(env, a[1], "resolution", p.resolution, 2)) { napi_throw_type_error(env, NULL, "motionBlur: resolution must hold 2 numbers"); return NULL; }
-    p.targetHalf = (int32_t)prop_num(env, a[1], "targetHalf", 0);
-    p.halfStoreRTZ = (int32_t)prop_num(env, a[1], "halfStoreRTZ", 1);
+    if (!motion_blur_params(env, a[1], "motionBlur", &p)) return NULL;
     int rc = rfx_motion_blur(c, &p);
     if (rc) return throw_rfx(env, c, "rfx_motion_blur", rc);
     return NULL;
+}
+/* motionBlurStage(ctx, uniforms): rfx_motion_blur_stage (a row tile's rows of the source into RFX_TEX_BLUR_SOURCE; arms the tiled draw) */
+static napi_value n_motion_blur_stage(napi_env env, napi_callback_info info) {
+    napi_value a[2];
+    if (!get_args(env, info, 2, a)) return NULL;
+    rfx_ctx *c = get_ctx(env, a[0]);
+    if (!c) return NULL;
+    rfx_motion_blur_params p;
+    if (!motion_blur_params(env, a[1], "motionBlurStage", &p)) return NULL;
+    int rc = rfx_motion_blur_stage(c, &p);
+    if (rc) return throw_rfx(env, c, "rfx_motion_blur_stage", rc);
+    return NULL;
+}
+/* motionBlurReachMask(ctx, uniforms, Uint32Array of frame-height entries): rfx_motion_blur_reach_mask (blocks) */
+static napi_value n_motion_blur_reach_mask(napi_env env, napi_callback_info info) {
+    napi_value a[3], ab;
+    napi_typedarray_type type;
+    size_t len = 0, off = 0;
+    void *data = NULL;
+    if (!get_args(env, info, 3, a)) return NULL;
+    rfx_ctx *c = get_ctx(env, a[0]);
+    if (!c) return NULL;
+    rfx_motion_blur_params p;
+    if (!motion_blur_params(env, a[1], "motionBlurReachMask", &p)) return NULL;
+    if (napi_get_typedarray_info(env, a[2], &type, &len, &data, &ab, &off) != napi_ok || type != napi_uint32_array) {
+        napi_throw_type_error(env, NULL, "motionBlurReachMask: a Uint32Array with one entry per frame row");
+        return NULL;
+    }
+    int rc = rfx_motion_blur_reach_mask(c, &p, (unsigned int *)data, (int)len);
+    if (rc) return throw_rfx(env, c, "rfx_motion_blur_reach_mask", rc);
+    return NULL;
+}
+/* motionBlurGather(ctx, uniforms) -> bytes this rank receives (rfx_motion_blur_gather over the context's communicator; commWait before the draw) */
+static napi_value n_motion_blur_gather(napi_env env, napi_callback_info info) {
+    napi_value a[2], out;
+    size_t got = 0;
+    if (!get_args(env, info, 2, a)) return NULL;
+    rfx_ctx *c = get_ctx(env, a[0]);
+    if (!c) return NULL;
+    rfx_motion_blur_params p;
+    if (!motion_blur_params(env, a[1], "motionBlurGather", &p)) return NULL;
+    int rc = rfx_motion_blur_gather(c, &p, NULL, &got);
+    if (rc) return throw_rfx(env, c, "rfx_motion_blur_gather", rc);
+    napi_create_double(env, (double)got, &out);
+    return out;
 }
 
 static napi_value n_sync(napi_env env, napi_callback_info info) {
@@ -818,6 +873,7 @@ static napi_value init(napi_env env, napi_value exports) {
     static const struct { const char *name; napi_callback fn; } fns[] = {
         {"abiVersion", n_abi_version}, {"create", n_create}, {"heldRows", n_held_rows}, {"upload", n_upload}, {"download", n_download},
         {"clear", n_clear}, {"setEnvironment", n_set_environment}, {"setEnvironmentImportance", n_set_environment_importance}, {"packGBuffer", n_pack_gbuffer}, {"packVelocity", n_pack_velocity}, {"ssgiMarch", n_ssgi}, {"ssgiTrace", n_ssgi_trace}, {"ssgiShade", n_ssgi_shade}, {"temporalReproject", n_temporal}, {"copyFramebuffer", n_copy_framebuffer}, {"poissonDenoise", n_denoise}, {"compose", n_compose}, {"finalCompose", n_final}, {"motionBlur", n_motion_blur},
+        {"motionBlurStage", n_motion_blur_stage}, {"motionBlurReachMask", n_motion_blur_reach_mask}, {"motionBlurGather", n_motion_blur_gather},
         {"sync", n_sync}, {"setRowWindow", n_set_row_window}, {"setUvModel", n_set_uv_model}, {"cubeToEquirect", n_cube_to_equirect}, {"haloViolations", n_halo_violations}, {"timeBegin", n_time_begin}, {"timeEnd", n_time_end}, {"profile", n_profile}, {"profileRead", n_profile_read},
         {"stageUpload", n_stage_upload}, {"stageFlip", n_stage_flip}, {"hostAlloc", n_host_alloc},
         {"splitRows", n_split_rows}, {"commUniqueId", n_comm_unique_id}, {"commInit", n_comm_init}, {"haloExchange", n_halo_exchange},

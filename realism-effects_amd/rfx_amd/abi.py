@@ -13,27 +13,28 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "..", "csrc", "librfx_hip.so")
 
-RFX_ABI_VERSION = 20
+RFX_ABI_VERSION = 21
 PEER_BLOB_BYTES = 192  # include/rfx.h RFX_PEER_BLOB_BYTES
 # rfx_profile_read's kinds (include/rfx.h RFX_PROF_*)
-PROF_KINDS = ("k1_prepass", "k1_ssgi_march", "k2_temporal_reproject", "k3_poisson_denoise_pass0", "k3_poisson_denoise_passN", "k4_compose", "k5_final_compose", "k6_motion_blur")
+PROF_KINDS = ("k1_prepass", "k1_ssgi_march", "k2_temporal_reproject", "k3_poisson_denoise_pass0", "k3_poisson_denoise_passN", "k4_compose", "k5_final_compose", "k6_motion_blur",
+              "k6_motion_blur_reach")
 RFX_UV_IDEAL, RFX_UV_REFERENCE_GL = 0, 1  # rfx_set_uv_model
 RFX_OK, RFX_EINVAL, RFX_ENOMEM, RFX_EDEVICE, RFX_ESTATE, RFX_EUNSUPPORTED = 0, -1, -2, -3, -4, -5
 
 (TEX_DEPTH, TEX_GBUFFER, TEX_VELOCITY, TEX_DIRECT_LIGHT, TEX_BLUE_NOISE, TEX_SSGI, TEX_TEMPORAL0, TEX_TEMPORAL1,
  TEX_DENOISE_A0, TEX_DENOISE_A1, TEX_DENOISE_B0, TEX_DENOISE_B1, TEX_COMPOSE, TEX_FBCOPY_F16, TEX_FBCOPY_F32, TEX_FINAL, TEX_COMPOSE_RGB,
- TEX_EFFECT_INPUT, TEX_MOTION_BLUR, TEX_COUNT) = range(20)
+ TEX_EFFECT_INPUT, TEX_MOTION_BLUR, TEX_BLUR_SOURCE, TEX_COUNT) = range(21)
 
 TEX_NAMES = ["depth", "gbuffer", "velocity", "direct_light", "blue_noise", "ssgi", "temporal0", "temporal1",
              "denoise_a0", "denoise_a1", "denoise_b0", "denoise_b1", "compose", "fbcopy_f16", "fbcopy_f32", "final", "compose_rgb",
-             "effect_input", "motion_blur"]
+             "effect_input", "motion_blur", "blur_source"]
 # (numpy dtype, channels) per slot, matching rfx_tex_texel_bytes()
 TEX_FORMAT = {
     TEX_DEPTH: (np.float32, 1), TEX_GBUFFER: (np.uint32, 4), TEX_VELOCITY: (np.uint32, 4), TEX_DIRECT_LIGHT: (np.float32, 4),
     TEX_BLUE_NOISE: (np.uint8, 4), TEX_SSGI: (np.uint32, 4), TEX_TEMPORAL0: (np.float32, 4), TEX_TEMPORAL1: (np.float32, 4),
     TEX_DENOISE_A0: (np.uint16, 4), TEX_DENOISE_A1: (np.uint16, 4), TEX_DENOISE_B0: (np.uint16, 4), TEX_DENOISE_B1: (np.uint16, 4),
     TEX_COMPOSE: (np.float32, 4), TEX_FBCOPY_F16: (np.uint16, 4), TEX_FBCOPY_F32: (np.float32, 4), TEX_FINAL: (np.float32, 4),
-    TEX_COMPOSE_RGB: (np.float32, 3), TEX_EFFECT_INPUT: (np.float32, 4), TEX_MOTION_BLUR: (np.float32, 4),
+    TEX_COMPOSE_RGB: (np.float32, 3), TEX_EFFECT_INPUT: (np.float32, 4), TEX_MOTION_BLUR: (np.float32, 4), TEX_BLUR_SOURCE: (np.float32, 4),
 }
 
 M16 = C.c_float * 16
@@ -108,6 +109,7 @@ EXPORTS = [
     "rfx_upload", "rfx_download", "rfx_clear", "rfx_tex_device_ptr", "rfx_bind_external", "rfx_pack_gbuffer", "rfx_pack_velocity", "rfx_set_environment", "rfx_set_environment_importance", "rfx_download_environment", "rfx_cube_to_equirect", "rfx_set_row_window", "rfx_set_uv_model", "rfx_ssgi_march", "rfx_ssgi_trace", "rfx_ssgi_shade", "rfx_temporal_reproject",
     "rfx_copy_framebuffer", "rfx_poisson_denoise", "rfx_compose", "rfx_final_compose", "rfx_motion_blur", "rfx_sync", "rfx_halo_violations", "rfx_time_begin", "rfx_time_end", "rfx_profile", "rfx_profile_read",
     "rfx_host_alloc", "rfx_host_free", "rfx_stage_upload", "rfx_stage_flip", "rfx_split_rows", "rfx_comm_unique_id", "rfx_comm_init", "rfx_comm_destroy", "rfx_halo_exchange", "rfx_allgather_history", "rfx_gather_history_rows", "rfx_peer_export", "rfx_peer_open", "rfx_peer_gather_history", "rfx_peer_close", "rfx_ssgi_hit_rows", "rfx_ssgi_hit_mask", "rfx_comm_wait",
+    "rfx_motion_blur_reach_mask", "rfx_motion_blur_stage", "rfx_motion_blur_gather",
 ]
 
 _lib = None
@@ -200,6 +202,9 @@ def load_library(path: str | None = None) -> C.CDLL:
     lib.rfx_ssgi_hit_rows.argtypes = [vp, C.POINTER(i), C.POINTER(i)]
     lib.rfx_ssgi_hit_mask.argtypes = [vp, C.POINTER(C.c_uint32), i]
     lib.rfx_comm_wait.argtypes = [vp]
+    lib.rfx_motion_blur_reach_mask.argtypes = [vp, C.POINTER(MotionBlurParams), C.POINTER(C.c_uint32), i]
+    lib.rfx_motion_blur_stage.argtypes = [vp, C.POINTER(MotionBlurParams)]
+    lib.rfx_motion_blur_gather.argtypes = [vp, C.POINTER(MotionBlurParams), vp, C.POINTER(C.c_size_t)]
     if lib.rfx_abi_version() != RFX_ABI_VERSION:
         raise ImportError("librfx_hip.so ABI version %d != %d" % (lib.rfx_abi_version(), RFX_ABI_VERSION))
     if path is None:

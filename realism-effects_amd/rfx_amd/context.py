@@ -258,6 +258,24 @@ class Context:
         """MotionBlurEffect's mainImage (K6, include/rfx.h rfx_motion_blur) -> abi.TEX_MOTION_BLUR"""
         self._chk(self.lib.rfx_motion_blur(self._h, C.byref(p)), "rfx_motion_blur")
 
+    def motion_blur_reach_mask(self, p: abi.MotionBlurParams) -> np.ndarray:
+        """rfx_motion_blur_reach_mask: one uint32 per frame row — bit b set when motion_blur(p) loads a texel of `p.source` in column block b
+        of that row (32 blocks across the frame) for this context's tile rows (row window honoured)."""
+        m = np.zeros(self.H, np.uint32)
+        self._chk(self.lib.rfx_motion_blur_reach_mask(self._h, C.byref(p), m.ctypes.data_as(C.POINTER(C.c_uint32)), self.H), "rfx_motion_blur_reach_mask")
+        return m
+
+    def motion_blur_stage(self, p: abi.MotionBlurParams):
+        """rfx_motion_blur_stage: the tile rows of `p.source` into abi.TEX_BLUR_SOURCE; arms the row-tiled motion_blur for that source."""
+        self._chk(self.lib.rfx_motion_blur_stage(self._h, C.byref(p)), "rfx_motion_blur_stage")
+
+    def motion_blur_gather(self, p: abi.MotionBlurParams) -> int:
+        """rfx_motion_blur_gather: stage + reach mask + the exchange of the named column blocks over the context's communicator (comm_wait
+        before the draw).  Returns the bytes this rank receives."""
+        n = C.c_size_t(0)
+        self._chk(self.lib.rfx_motion_blur_gather(self._h, C.byref(p), None, C.byref(n)), "rfx_motion_blur_gather")
+        return int(n.value)
+
     def sync(self):
         self._chk(self.lib.rfx_sync(self._h), "rfx_sync")
 

@@ -20,6 +20,12 @@ rows above and below and three exchange steps keep them current:
                                      between rfx_ssgi_trace and rfx_ssgi_shade: it overlaps the next
                                      frame's depth pre-pass and ray march
   after a framebuffer copy (TRAA)  : the same neighbour Send/Recv for the pass's own history
+  before a motion blur (K6)        : a streak's taps can land anywhere on screen, but WHERE is a pure function of the tile's own
+                                     velocity texels, the blue-noise table and the draw's uniforms: the tile's rows of the source are
+                                     staged into the whole-frame plane RFX_TEX_BLUR_SOURCE, the device reduces the mask of source
+                                     texels the draw will load (rfx_motion_blur_reach_mask: one word per row, a bit per column block),
+                                     the masks are all-gathered and only the named texels travel from their owners (whole rows over
+                                     the tensor transport, column blocks behind the C ABI: rfx_motion_blur_gather)
 
 K1 needs no exchange: it recomputes the +-2 rows K2's neighbourhood clamp reads, from the
 read-only dump planes every rank holds for its band, and reads depth / last frame's composed GI
@@ -118,6 +124,7 @@ class TiledRenderer:
         self.gather_history_rgb = world > 1 and abi.TEX_COMPOSE_RGB in tensors
         self.history_gather = "all"
         self.history_bytes_received = []  # per frame, "bounded" / "peer" modes (what "all" receives: the other tiles, every frame)
+        self.blur_bytes_received = []  # per motion_blur(): the source texels this rank received
 
     def use_peer_history(self, all_gather_object):
         """Switch the composed-GI exchange to the DEVICE-DRIVEN pull (include/rfx.h rfx_peer_*): between a frame's trace and its shade this
@@ -182,6 +189,58 @@ class TiledRenderer:
     def final_compose(self, p):
         self.finish_halo()
         return self.inner.final_compose(p)
+
+    # K6: stage + reach mask + all-gather of the masks + Send/Recv of the rows that carry any bit + upload, then the draw
+    def motion_blur(self, p):
+        if self.world == 1:
+            return self.inner.motion_blur(p)
+        import torch
+        dist = self._dist
+        self.finish_halo()
+        self.inner.motion_blur_stage(p)
+        mine = np.ascontiguousarray(self.inner.motion_blur_reach_mask(p), np.uint32)  # blocks: the tile's rows of the source are complete
+        dev = "cuda" if dist.get_backend(self.group) == "nccl" else "cpu"
+        to_t = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
+        gathered = [torch.zeros(self.H, dtype=torch.int32, device=dev) for _ in range(self.world)]
+        dist.all_gather(gathered, to_t(mine.view(np.int32)), group=self.group)
+        masks = [g.cpu().numpy().view(np.uint32) for g in gathered]
+        tiles = split_rows(self.H, self.world)
+        y0, n = tiles[self.rank]
+        own = None
+        ops, keep, recvs = [], [], []
+        for q, (qy0, qn) in enumerate(tiles):
+            if q == self.rank:
+                continue
+            send = [y for y in range(y0, y0 + n) if masks[q][y]]     # what q's streaks reach of MY rows
+            recv = [y for y in range(qy0, qy0 + qn) if mine[y]]      # what mine reach of q's
+            if send:
+                if own is None:
+                    own = np.ascontiguousarray(self.inner.download(abi.TEX_BLUR_SOURCE, y0, n), np.float32)
+                t = to_t(np.ascontiguousarray(own[[y - y0 for y in send]]))
+                keep.append(t)
+                ops.append(dist.P2POp(dist.isend, t, q, self.group))
+            if recv:
+                t = torch.empty((len(recv), self.W, 4), dtype=torch.float32, device=dev)
+                recvs.append((recv, t))
+                ops.append(dist.P2POp(dist.irecv, t, q, self.group))
+        if ops:
+            for w in dist.batch_isend_irecv(ops):
+                w.wait()
+            if dev == "cuda":
+                torch.cuda.current_stream().synchronize()
+        got = 0
+        for rows, t in recvs:
+            a = t.cpu().numpy()
+            got += a.nbytes
+            i = 0
+            while i < len(rows):  # runs of consecutive rows: one upload each
+                j = i
+                while j + 1 < len(rows) and rows[j + 1] == rows[j] + 1:
+                    j += 1
+                self.inner.upload(abi.TEX_BLUR_SOURCE, a[i:j + 1], rows[i], j + 1 - i)
+                i = j + 1
+        self.blur_bytes_received.append(got)
+        return self.inner.motion_blur(p)
 
     def _interior_first(self, draw):
         if not self._halo_pending:
@@ -363,6 +422,13 @@ class CommTiledRenderer(TiledRenderer):
         if self.world > 1 and self.history_gather in ("bounded", "peer"):
             raise RuntimeError("CommTiledRenderer(history_gather=\"bounded\"): K1 must run as ssgi_trace / ssgi_shade (the gather sits between them)")
         return super().ssgi_march(p)
+
+    def motion_blur(self, p):
+        """K6 behind the C ABI: rfx_motion_blur_gather (stage, reach mask, the column blocks from their owners), rfx_comm_wait, the draw"""
+        self.blur_bytes_received.append(self.inner.motion_blur_gather(p))
+        self._pending = [True]
+        self.finish_pending()
+        return self.inner.motion_blur(p)
 
     def gather_whole_history(self):
         """every rank's rows of the composed GI to every rank, now (a host that wants the whole frame on one rank — bench.py's checksum)"""
