@@ -447,7 +447,8 @@ int rfx_peer_open(rfx_ctx *, rfx_tex id, const void *blobs, int rank, int nranks
 int rfx_peer_gather_history(rfx_ctx *, rfx_tex id, size_t *bytes_pulled_previous_call);
 int rfx_peer_close(rfx_ctx *);
 /* The reduction on its own (any context, no communicator): after rfx_ssgi_trace, the inclusive range of history rows the shade of the
- * traced rows will read; row_hi < row_lo when it reads none.  Blocks until the trace has finished. */
+ * traced rows will read; row_hi < row_lo when it reads none (0x7fffffff, -1).  Blocks until the trace has finished.  A diagnostic: it is the
+ * first and the last non-zero word of rfx_ssgi_hit_mask's mask, which it reads back whole (one word per frame row) to find them. */
 int rfx_ssgi_hit_rows(rfx_ctx *, int *row_lo, int *row_hi);
 /* ... and the mask form (ABI 16): row_mask[y], y in [0, height), gets bit b set when the shade of the traced rows reads a history texel of
  * frame row y in column block b (32 equal blocks across the frame: texel x is in block x * 32 / width); a row that is not read at all

@@ -3,6 +3,7 @@
 // the inline shader :36-86 and src/denoise/shader/denoiser_compose_functions.glsl:53-108.
 // Pure streaming kernel: 52 B/px (4 depth + 16 gbuffer + 2x8 GI in, 16 out).
 #include "k4_compose_texel.h"
+#include "rfx_blocks.h"
 #include "rfx_launch.h"
 
 namespace {
@@ -247,7 +248,7 @@ __global__ __launch_bounds__(256) void k6_motion_blur_tiled(K6Args A) {
 
 // ---- the reach reduction of a row-tiled blur (rfx_motion_blur_reach_mask / rfx_motion_blur_gather): the texels of `src` the draw above will
 // LOAD for rows [y0, y1), as the bounded history gather's row mask (k1_hit_mask in k1_ssgi.hip: one word per frame row, bit b = column block
-// b, texel x in block x * 32 / W).  The same k6_moved / k6_streak / k6_tap_uv / k6_footprint as the draw, without the loads — so the mask is
+// b, rfx_blocks.h).  The same k6_moved / k6_streak / k6_tap_uv / k6_footprint as the draw, without the loads — so the mask is
 // exact (zero-weight footprint texels included: the draw loads them, and 0 * NaN is NaN), not a bound derived from the velocity's magnitude.
 // One lane per pixel, one wave per 64 pixels of a row.
 // Guarded as k1_hit_mask's: a set bit is never set again.  The test is a plain load, which the L1 may serve from a stale copy (the atomics
@@ -283,7 +284,7 @@ RFX_DEV void k6_flush_wave(unsigned int *mask, const K6Pending &p, bool want) {
 }
 // name the four texels of a footprint (`live`: this lane loads it)
 RFX_DEV void k6_name(unsigned int *mask, K6Pending &p, const K6Foot &f, int W, bool live) {
-    const unsigned int bits = (1u << ((unsigned int)(f.x0 * 32) / (unsigned int)W)) | (1u << ((unsigned int)(f.x1 * 32) / (unsigned int)W));
+    const unsigned int bits = (1u << rfx_block_of_col(f.x0, W)) | (1u << rfx_block_of_col(f.x1, W));
     const int rows = f.y0 | (f.y1 << 16);  // rows are < 2^15 (rfx_create)
     k6_flush_wave(mask, p, live && p.rows >= 0 && p.rows != rows);
     if (live) {

@@ -128,8 +128,6 @@ void rfx_destroy(rfx_ctx *c) {
     for (hipEvent_t e : {c->ev_depth, c->ev_k1_done, c->ev_prep_done})
         if (e) hipEventDestroy(e);
     if (c->hits) hipFree(c->hits);
-    if (c->hit_rows_dev) hipFree(c->hit_rows_dev);
-    if (c->hit_rows_host) hipHostFree(c->hit_rows_host);
     if (c->hit_mask_dev) hipFree(c->hit_mask_dev);
     if (c->hit_mask_host) hipHostFree(c->hit_mask_host);
     if (c->hist_staging) hipFree(c->hist_staging);
@@ -772,20 +770,6 @@ int rfx_internal_k3_tile(int W, int H, float radius, int inputIsTemporal, int te
     return RFX_OK;
 }
 
-// between rfx_ssgi_trace and rfx_ssgi_shade (rfx_gather_history_rows): which rows of last frame's composed GI will the shade read?
-int rfx_internal_hit_rows_enqueue(rfx_ctx *c, int *rows_dev) {
-    if (!c->hits || !c->hits_traced) return fail(c, RFX_ESTATE, "rfx_gather_history_rows: no rfx_ssgi_trace of this frame is waiting for its shade");
-    // the hand-over plane of a resolutionScale != 1 trace is indexed by the SMALLER target (and such a trace needs a whole-frame context, which
-    // has no history to gather): the row reduction below reads it with the frame's pitch
-    if (c->trace_scaled) return fail(c, RFX_EUNSUPPORTED, "rfx_ssgi_hit_rows / rfx_gather_history_rows: the last rfx_ssgi_trace ran with resolutionScale != 1");
-    RFX_ENTER(c);
-    static const int preset[2] = {0x7fffffff, -1};
-    HIPCHK(c, hipMemcpyAsync(rows_dev, preset, sizeof preset, hipMemcpyHostToDevice, c->stream));
-    if (c->trace_y1 > c->trace_y0)
-        HIPCHK(c, rfx_launch_k1_hit_rows(dims(c), c->trace_y0, c->trace_y1, view(c, RFX_TEX_DEPTH), wview(c, RFX_TEX_SSGI), c->hits, c->trace_missed != 0, rows_dev, c->stream));
-    return RFX_OK;
-}
-
 // the row-mask scratch of the bounded gathers (rfx_ctx.h hit_mask_dev / hit_mask_host), sized for `ranks` gathered copies
 static int hit_mask_scratch(rfx_ctx *c, int ranks) {
     if (ranks < 1) ranks = 1;
@@ -818,31 +802,36 @@ int rfx_internal_hit_mask_enqueue(rfx_ctx *c, int ranks) {
     return RFX_OK;
 }
 
+// the first H words of hit_mask_dev (the mask an enqueue above left on the draw stream) -> hit_mask_host, and into row_mask when given
+static int hit_mask_read_back(rfx_ctx *c, unsigned int *row_mask) {
+    const size_t bytes = (size_t)c->H * sizeof(unsigned int);
+    HIPCHK(c, hipMemcpyAsync(c->hit_mask_host, c->hit_mask_dev, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (row_mask) memcpy(row_mask, c->hit_mask_host, bytes);
+    return RFX_OK;
+}
+
 int rfx_ssgi_hit_mask(rfx_ctx *c, unsigned int *row_mask, int rows) {
     if (!c || !row_mask) return RFX_EINVAL;
     if (rows != c->H) return fail(c, RFX_EINVAL, "rfx_ssgi_hit_mask: one word per frame row (rows == height)");
     int rc = rfx_internal_hit_mask_enqueue(c, 1);
     if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->hit_mask_host, c->hit_mask_dev, (size_t)c->H * sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    memcpy(row_mask, c->hit_mask_host, (size_t)c->H * sizeof(unsigned int));
-    return RFX_OK;
+    return hit_mask_read_back(c, row_mask);
 }
 
+// the first and the last row of that mask with a bit set (a diagnostic: the gathers plan with the mask itself)
 int rfx_ssgi_hit_rows(rfx_ctx *c, int *row_lo, int *row_hi) {
     if (!c || !row_lo || !row_hi) return RFX_EINVAL;
-    RFX_ENTER(c);
-    if (!c->hit_rows_dev) {  // sized for any communicator this context may get later: 2 + 2 * 64 ranks
-        hipError_t e = hipMalloc((void **)&c->hit_rows_dev, sizeof(int) * 130);
-        if (e == hipSuccess) e = hipHostMalloc((void **)&c->hit_rows_host, sizeof(int) * 128, hipHostMallocDefault);
-        if (e != hipSuccess) return fail(c, RFX_ENOMEM, "rfx_ssgi_hit_rows: scratch", e);
-    }
-    int rc = rfx_internal_hit_rows_enqueue(c, c->hit_rows_dev);
-    if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->hit_rows_host, c->hit_rows_dev, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    *row_lo = c->hit_rows_host[0];
-    *row_hi = c->hit_rows_host[1];
+    int rc = rfx_internal_hit_mask_enqueue(c, 1);
+    if (rc || (rc = hit_mask_read_back(c, nullptr))) return rc;
+    int lo = 0x7fffffff, hi = -1;
+    for (int y = 0; y < c->H; y++)
+        if (c->hit_mask_host[y]) {
+            if (hi < 0) lo = y;
+            hi = y;
+        }
+    *row_lo = lo;
+    *row_hi = hi;
     return RFX_OK;
 }
 
@@ -1116,10 +1105,7 @@ int rfx_motion_blur_reach_mask(rfx_ctx *c, const rfx_motion_blur_params *p, unsi
     if (rc) return rc;
     if (rows != c->H) return fail(c, RFX_EINVAL, "rfx_motion_blur_reach_mask: one word per frame row (rows == height)");
     if ((rc = rfx_internal_blur_reach_enqueue(c, p, 1))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->hit_mask_host, c->hit_mask_dev, (size_t)c->H * sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    memcpy(row_mask, c->hit_mask_host, (size_t)c->H * sizeof(unsigned int));
-    return RFX_OK;
+    return hit_mask_read_back(c, row_mask);
 }
 
 int rfx_motion_blur_stage(rfx_ctx *c, const rfx_motion_blur_params *p) {

@@ -10,6 +10,7 @@
 #include <dlfcn.h>
 #include <string.h>
 #include <mutex>
+#include "rfx_blocks.h"
 #include "rfx_ctx.h"
 
 namespace {
@@ -82,44 +83,16 @@ int nccl_fail(rfx_ctx *c, const char *what, NcclResult rc) {
         if (rc__ != 0) return nccl_fail(c, #call, rc__);   \
     } while (0)
 
-// the exchange stream starts after everything enqueued on the draw stream so far.
-// ONE ev_draws / ev_comm pair per context serves every exchange: each call re-records both.  That is correct because the exchange stream is
-// in-order — an exchange enqueued later also runs later, so waiting for the LAST recorded ev_comm (rfx_comm_wait) covers every exchange
-// issued before it, and a re-recorded ev_draws only ever moves the exchange stream's starting point forward.  (A host that wanted to wait for
-// an EARLIER exchange while a later one is still in flight would need one event per exchange; the protocols here never do.)
-int comm_begin(rfx_ctx *c) {
-    hipSetDevice(c->device);
-    hipError_t e = hipEventRecord(c->ev_draws, c->stream);
-    if (e == hipSuccess) e = hipStreamWaitEvent(c->comm_stream, c->ev_draws, 0);
-    return e == hipSuccess ? RFX_OK : fail(c, RFX_EDEVICE, "rfx_comm: ordering the exchange stream after the draws", e);
-}
-int comm_end(rfx_ctx *c) {
-    hipError_t e = hipEventRecord(c->ev_comm, c->comm_stream);
-    if (e != hipSuccess) return fail(c, RFX_EDEVICE, "rfx_comm: hipEventRecord", e);
-    c->comm_pending = true;
-    return RFX_OK;
-}
-int ensure_streams(rfx_ctx *c) {
-    if (c->comm_stream) return RFX_OK;
-    hipSetDevice(c->device);
-    hipError_t e = hipStreamCreateWithFlags(&c->comm_stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_draws, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_comm, hipEventDisableTiming);
-    return e == hipSuccess ? RFX_OK : fail(c, RFX_EDEVICE, "rfx_comm: stream/event creation", e);
-}
-
-
 // ---- the bounded gather's packed transfer (rfx_gather_history_rows): the history texels a rank needs are column blocks of rows (a bit per
-// block in the row's mask word, 32 blocks across the frame).  The owner packs the blocks a peer's mask asks for, row by row and block by
-// block, into one contiguous message per peer; the receiver scatters them back.  Both ends derive the layout from the same gathered masks.
-__device__ __host__ inline int hist_block_x0(int b, int W) { return (b * W + 31) / 32; }  // first texel of column block b: texel x is in block x * 32 / W
+// block in the row's mask word, 32 blocks across the frame: rfx_blocks.h).  The owner packs the blocks a peer's mask asks for, row by row and
+// block by block, into one contiguous message per peer; the receiver scatters them back.  Both ends derive the layout from the same gathered masks.
 // texel offset of frame column x inside the packed form of a row whose mask is m (x's block bit is set)
 __device__ inline int hist_packed_x(unsigned int m, int x, int W) {
-    const int b = (x * 32) / W;
-    int off = x - hist_block_x0(b, W);
+    const int b = rfx_block_of_col(x, W);
+    int off = x - rfx_block_col0(b, W);
     for (unsigned int below = m & ((1u << b) - 1u); below; below &= below - 1u) {
         const int j = __builtin_ctz(below);
-        off += hist_block_x0(j + 1, W) - hist_block_x0(j, W);
+        off += rfx_block_col0(j + 1, W) - rfx_block_col0(j, W);
     }
     return off;
 }
@@ -130,7 +103,7 @@ __global__ __launch_bounds__(256) void hist_pack_rows(float *tex, float *staging
     const int x = blockIdx.x * 64 + threadIdx.x, y = y0 + blockIdx.y * 4 + threadIdx.y;
     if (x >= W || y >= y1) return;
     const unsigned int m = mask[y];
-    if (!((m >> ((x * 32) / W)) & 1u) || row_off[y] < 0) return;
+    if (!((m >> rfx_block_of_col(x, W)) & 1u) || row_off[y] < 0) return;
     float *t = tex + ((size_t)y * W + x) * floats_per_texel;
     float *q = staging + ((size_t)row_off[y] + hist_packed_x(m, x, W)) * floats_per_texel;
     for (int k = 0; k < floats_per_texel; k++) {
@@ -142,12 +115,38 @@ inline int hist_row_texels(unsigned int m, int W) {  // texels of a row the mask
     int n = 0;
     for (; m; m &= m - 1u) {
         const int j = __builtin_ctz(m);
-        n += hist_block_x0(j + 1, W) - hist_block_x0(j, W);
+        n += rfx_block_col0(j + 1, W) - rfx_block_col0(j, W);
     }
     return n;
 }
 
 }  // namespace
+
+// the exchange stream starts after everything enqueued on the draw stream so far.
+// ONE ev_draws / ev_comm pair per context serves every exchange: each call re-records both.  That is correct because the exchange stream is
+// in-order — an exchange enqueued later also runs later, so waiting for the LAST recorded ev_comm (rfx_comm_wait) covers every exchange
+// issued before it, and a re-recorded ev_draws only ever moves the exchange stream's starting point forward.  (A host that wanted to wait for
+// an EARLIER exchange while a later one is still in flight would need one event per exchange; the protocols here never do.)
+int rfx_comm_begin(rfx_ctx *c) {
+    hipSetDevice(c->device);
+    hipError_t e = hipEventRecord(c->ev_draws, c->stream);
+    if (e == hipSuccess) e = hipStreamWaitEvent(c->comm_stream, c->ev_draws, 0);
+    return e == hipSuccess ? RFX_OK : fail(c, RFX_EDEVICE, "rfx_comm: ordering the exchange stream after the draws", e);
+}
+int rfx_comm_end(rfx_ctx *c) {
+    hipError_t e = hipEventRecord(c->ev_comm, c->comm_stream);
+    if (e != hipSuccess) return fail(c, RFX_EDEVICE, "rfx_comm: hipEventRecord", e);
+    c->comm_pending = true;
+    return RFX_OK;
+}
+int rfx_ensure_streams(rfx_ctx *c) {
+    hipSetDevice(c->device);
+    if (c->comm_stream) return RFX_OK;
+    hipError_t e = hipStreamCreateWithFlags(&c->comm_stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_draws, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_comm, hipEventDisableTiming);
+    return e == hipSuccess ? RFX_OK : fail(c, RFX_EDEVICE, "rfx_comm: stream/event creation", e);
+}
 
 void rfx_comm_release(rfx_ctx *c) {
     if (!c) return;
@@ -166,56 +165,64 @@ void rfx_comm_release(rfx_ctx *c) {
     c->comm_pending = false;
 }
 
-// The exchange both bounded gathers share (rfx_gather_history_rows: last frame's composed GI, 3 or 4 floats per texel; rfx_motion_blur_gather:
-// RFX_TEX_BLUR_SOURCE, 4): this tile's row mask is in the first H words of c->hit_mask_dev, enqueued on the draw stream; `id` is a plane held
-// whole whose tile rows every rank owns; `who` is the entry point, for its failure messages.
-static int gather_masked_blocks(rfx_ctx *c, const char *who, Rccl *r, NcclComm comm, rfx_tex id, size_t *bytes_received) {
-    const int n = c->comm_nranks, me = c->comm_rank;
-    int rc;
-    char what[96];
-    char *base = (char *)c->slots[id].ptr;  // held whole: frame row y at y * pitch
-    const Slot &s = c->slots[id];
-    const int H = c->H;
-    // 2. every rank's mask -> host.  The one host-side wait of the exchange: the plan below needs them (H words per rank: 8.6 KB at 4K).
-    if ((rc = comm_begin(c))) return rc;
-    NCCLCHK(c, r->AllGather(c->hit_mask_dev, c->hit_mask_dev + H, (size_t)H, kNcclUint32, comm, c->comm_stream));
-    HIPCHK(c, hipMemcpyAsync(c->hit_mask_host, c->hit_mask_dev + H, sizeof(unsigned int) * (size_t)n * H, hipMemcpyDeviceToHost, c->comm_stream));
-    HIPCHK(c, hipStreamSynchronize(c->comm_stream));
-    // 3. rank p needs the column blocks its mask names; whoever owns their rows packs them into ONE message for p (the owner's rows of last
-    //    frame's composed GI are current: K4 wrote them), p scatters them back.  Both ends walk the same masks in the same order (row by
-    //    row, block by block), so the two sides of every message agree on its size and layout.  Measured on the synthetic orbit
-    //    (tools/history_rows_report.py): the blocks are a quarter of the bytes of the rows they lie in — reflections reach most ROWS
-    //    below the horizon but only part of each.  (Round 3's plan was the (min, max) row interval per rank.)
-    const int W = c->W, fpt = (int)(s.texel / sizeof(float));
-    const unsigned int *mine = c->hit_mask_host + (size_t)me * H;
-    // row offsets (texels) into the per-peer segments of the two stagings; segment bases per peer
-    int *off_host = (int *)(c->hit_mask_host + (size_t)n * H);          // [0, n H): send offsets per peer; [n H, (n + 1) H): receive offsets
-    size_t send_base[65], recv_base[65], send_tex = 0, recv_tex = 0;  // [p]: first texel of peer p's segment, [n]: the total
+constexpr int kMaskedRing = 64;      // ranks the bounded gathers plan for (comm_enter's max_ranks)
+constexpr int kAnyRing = 0x7fffffff;  // ... and an exchange that needs rank and size but has no limit of its own
+
+// The plan of the bounded gathers' exchange, from every rank's row mask (masks[p * H + y]; rank p owns the rows rfx_split_rows gives it, this
+// rank `me` owns [tile_y0, tile_y0 + tile_rows)).  Rank p needs the column blocks its mask names; whoever owns their rows packs them into
+// ONE message for p, p scatters them back.  Both ends walk the same masks in the same order (row by row, block by block), so the two sides
+// of every message agree on its size and layout.
+//   off[p * H + y], p < n: texel offset of my row y inside the message for p, -1 when nothing of it travels;  off[n * H + y]: of row y inside
+//   the message from its owner, -1 when I need nothing of it (my own rows too);
+//   send_base[p] / recv_base[p]: first texel of p's message in the send / receive staging, [n]: the totals.
+static void plan_masked_blocks(const unsigned int *masks, int H, int W, int n, int me, int tile_y0, int tile_rows, int *off, size_t *send_base, size_t *recv_base) {
+    const unsigned int *mine = masks + (size_t)me * H;
+    int *ro = off + (size_t)n * H;
+    for (size_t i = 0; i < (size_t)(n + 1) * H; i++) off[i] = -1;
+    size_t send_tex = 0, recv_tex = 0;
     for (int p = 0; p < n; p++) {
-        int py0 = 0, prows = 0;
-        rfx_split_rows(H, n, p, &py0, &prows);
-        const unsigned int *theirs = c->hit_mask_host + (size_t)p * H;
         send_base[p] = send_tex;
         recv_base[p] = recv_tex;
-        int *so = off_host + (size_t)p * H;
-        for (int y = 0; y < H; y++) so[y] = -1;
         if (p == me) continue;
+        const unsigned int *theirs = masks + (size_t)p * H;
+        int *so = off + (size_t)p * H, py0 = 0, prows = 0;
+        rfx_split_rows(H, n, p, &py0, &prows);
         size_t k = 0;
-        for (int y = c->tile_y0; y < c->tile_y0 + c->tile_rows; y++)  // what p needs of MY rows
+        for (int y = tile_y0; y < tile_y0 + tile_rows; y++)  // what p needs of MY rows
             if (theirs[y]) { so[y] = (int)k; k += (size_t)hist_row_texels(theirs[y], W); }
         send_tex += k;
         k = 0;
-        int *ro = off_host + (size_t)n * H;
-        for (int y = py0; y < py0 + prows; y++) {  // what I need of p's rows
-            ro[y] = -1;
+        for (int y = py0; y < py0 + prows; y++)  // what I need of p's rows
             if (mine[y]) { ro[y] = (int)k; k += (size_t)hist_row_texels(mine[y], W); }
-        }
         recv_tex += k;
     }
-    for (int y = c->tile_y0; y < c->tile_y0 + c->tile_rows; y++) off_host[(size_t)n * H + y] = -1;  // (my own rows: nothing to receive)
     send_base[n] = send_tex;
     recv_base[n] = recv_tex;
-    const size_t need = (send_tex + recv_tex) * s.texel;
+}
+
+// The exchange both bounded gathers share (rfx_gather_history_rows: last frame's composed GI, 3 or 4 floats per texel; rfx_motion_blur_gather:
+// RFX_TEX_BLUR_SOURCE, 4): this tile's row mask is in the first H words of c->hit_mask_dev, enqueued on the draw stream; `id` is a plane held
+// whole whose tile rows every rank owns (the owner's rows of last frame's composed GI are current: K4 wrote them); `who` is the entry point,
+// for its failure messages.  Measured on the synthetic orbit (tools/history_rows_report.py): the blocks are a quarter of the bytes of the rows
+// they lie in — reflections reach most ROWS below the horizon but only part of each.
+static int gather_masked_blocks(rfx_ctx *c, const char *who, Rccl *r, NcclComm comm, rfx_tex id, size_t *bytes_received) {
+    const int n = c->comm_nranks, me = c->comm_rank, H = c->H, W = c->W;
+    const Slot &s = c->slots[id];
+    const int fpt = (int)(s.texel / sizeof(float));
+    char *base = (char *)s.ptr;  // held whole: frame row y at y * pitch
+    char what[96];
+    int rc;
+    // every rank's mask -> host.  The one host-side wait of the exchange: the plan needs them (H words per rank: 8.6 KB at 4K).
+    if ((rc = rfx_comm_begin(c))) return rc;
+    NCCLCHK(c, r->AllGather(c->hit_mask_dev, c->hit_mask_dev + H, (size_t)H, kNcclUint32, comm, c->comm_stream));
+    HIPCHK(c, hipMemcpyAsync(c->hit_mask_host, c->hit_mask_dev + H, sizeof(unsigned int) * (size_t)n * H, hipMemcpyDeviceToHost, c->comm_stream));
+    HIPCHK(c, hipStreamSynchronize(c->comm_stream));
+    // the plan: row offsets behind the masks in both buffers, [0, n H) per peer I send to, [n H, (n + 1) H) what I receive
+    int *off_host = (int *)(c->hit_mask_host + (size_t)n * H), *off_dev = (int *)(c->hit_mask_dev + (size_t)(n + 1) * H);
+    size_t send_base[kMaskedRing + 1], recv_base[kMaskedRing + 1];
+    plan_masked_blocks(c->hit_mask_host, H, W, n, me, c->tile_y0, c->tile_rows, off_host, send_base, recv_base);
+    // the staging: what this rank sends, then what it receives
+    const size_t need = (send_base[n] + recv_base[n]) * s.texel;
     if (need > c->hist_staging_bytes) {
         if (c->hist_staging) { HIPCHK(c, hipStreamSynchronize(c->comm_stream)); hipFree(c->hist_staging); c->hist_staging = nullptr; c->hist_staging_bytes = 0; }
         const size_t cap = need + need / 4 + 4096;
@@ -226,8 +233,7 @@ static int gather_masked_blocks(rfx_ctx *c, const char *who, Rccl *r, NcclComm c
         }
         c->hist_staging_bytes = cap;
     }
-    char *send_stage = (char *)c->hist_staging, *recv_stage = send_stage + send_tex * s.texel;
-    int *off_dev = (int *)(c->hit_mask_dev + (size_t)(n + 1) * H);
+    char *send_stage = (char *)c->hist_staging, *recv_stage = send_stage + send_base[n] * s.texel;
     HIPCHK(c, hipMemcpyAsync(off_dev, off_host, sizeof(int) * (size_t)(n + 1) * H, hipMemcpyHostToDevice, c->comm_stream));
     const dim3 blk(64, 4);
     for (int p = 0; p < n; p++) {  // pack: one launch per peer over my tile's rows
@@ -262,7 +268,25 @@ static int gather_masked_blocks(rfx_ctx *c, const char *who, Rccl *r, NcclComm c
     }
     HIPCHK(c, hipGetLastError());
     if (bytes_received) *bytes_received = got;
-    return comm_end(c);
+    return rfx_comm_end(c);
+}
+
+// What the exchanges' entry points share: RCCL, the communicator (a passed one, or rfx_comm_init's), the exchange stream.  max_ranks: 0 = the
+// exchange needs neither rank nor size, so a passed communicator will do without rfx_comm_init; otherwise both come from rfx_comm_init, and
+// the ring has at most max_ranks ranks.
+static int comm_enter(rfx_ctx *c, const char *who, void *nccl_comm, int max_ranks, Rccl **r, NcclComm *comm) {
+    char what[96];
+    const auto refuse = [&](int code, const char *fmt) {
+        snprintf(what, sizeof what, fmt, who, max_ranks);
+        return fail(c, code, what);
+    };
+    if (!(*r = rccl())) return refuse(RFX_EUNSUPPORTED, "%s: RCCL cannot be loaded on this host");
+    if (!(*comm = nccl_comm ? nccl_comm : c->comm)) return refuse(RFX_ESTATE, "%s: no communicator (rfx_comm_init, or pass one)");
+    if (max_ranks && nccl_comm && !c->comm) return refuse(RFX_ESTATE, "%s: rank and size come from rfx_comm_init");
+    int rc = rfx_ensure_streams(c);
+    if (rc) return rc;
+    if (max_ranks && c->comm_nranks > max_ranks) return refuse(RFX_EUNSUPPORTED, "%s: more than %d ranks");
+    return RFX_OK;
 }
 
 extern "C" {
@@ -294,7 +318,7 @@ int rfx_comm_init(rfx_ctx *c, const void *id128, int rank, int nranks) {
     int y0 = 0, rows = 0;
     if (rfx_split_rows(c->H, nranks, rank, &y0, &rows) != RFX_OK || y0 != c->tile_y0 || rows != c->tile_rows)
         return fail(c, RFX_EINVAL, "rfx_comm_init: the context's tile is not rfx_split_rows(height, nranks, rank)");
-    int rc = ensure_streams(c);
+    int rc = rfx_ensure_streams(c);
     if (rc) return rc;
     hipSetDevice(c->device);
     NcclUniqueId id;
@@ -317,13 +341,11 @@ int rfx_comm_destroy(rfx_ctx *c) {
 
 int rfx_halo_exchange(rfx_ctx *c, rfx_tex id, void *nccl_comm, int up_rank, int down_rank) {
     if (!c || id < 0 || id >= RFX_TEX_COUNT) return RFX_EINVAL;
-    Rccl *r = rccl();
-    if (!r) return fail(c, RFX_EUNSUPPORTED, "rfx_halo_exchange: RCCL cannot be loaded on this host");
-    NcclComm comm = nccl_comm ? nccl_comm : c->comm;
-    if (!comm) return fail(c, RFX_ESTATE, "rfx_halo_exchange: no communicator (rfx_comm_init, or pass one)");
-    if (c->halo == 0 || (up_rank < 0 && down_rank < 0)) return RFX_OK;
-    int rc = ensure_streams(c);
+    Rccl *r;
+    NcclComm comm;
+    int rc = comm_enter(c, "rfx_halo_exchange", nccl_comm, 0, &r, &comm);
     if (rc) return rc;
+    if (c->halo == 0 || (up_rank < 0 && down_rank < 0)) return RFX_OK;
     char *base = (char *)rfx_tex_device_ptr(c, id);
     if (!base) return RFX_ENOMEM;
     const Slot &s = c->slots[id];
@@ -348,7 +370,7 @@ int rfx_halo_exchange(rfx_ctx *c, rfx_tex id, void *nccl_comm, int up_rank, int 
         if ((up_rank >= 0 && up_rank != c->comm_rank + 1) || (down_rank >= 0 && down_rank != c->comm_rank - 1))
             return fail(c, RFX_EINVAL, "rfx_halo_exchange: halo_rows taller than a tile: up / down must be the split's neighbours (rank + 1 / rank - 1) or -1");
     }
-    if ((rc = comm_begin(c))) return rc;
+    if ((rc = rfx_comm_begin(c))) return rc;
     const size_t bytes = (size_t)h * pitch;
     NCCLCHK(c, r->GroupStart());
     NcclResult e = 0;
@@ -376,25 +398,22 @@ int rfx_halo_exchange(rfx_ctx *c, rfx_tex id, void *nccl_comm, int up_rank, int 
     NcclResult e2 = r->GroupEnd();
     if (e) return nccl_fail(c, "rfx_halo_exchange: ncclSend/ncclRecv", e);
     if (e2) return nccl_fail(c, "rfx_halo_exchange: ncclGroupEnd", e2);
-    return comm_end(c);
+    return rfx_comm_end(c);
 }
 
 int rfx_allgather_history(rfx_ctx *c, rfx_tex id, void *nccl_comm) {
     if (!c) return RFX_EINVAL;
     if (id != RFX_TEX_COMPOSE && id != RFX_TEX_COMPOSE_RGB) return fail(c, RFX_EINVAL, "rfx_allgather_history: RFX_TEX_COMPOSE or RFX_TEX_COMPOSE_RGB");
-    Rccl *r = rccl();
-    if (!r) return fail(c, RFX_EUNSUPPORTED, "rfx_allgather_history: RCCL cannot be loaded on this host");
-    NcclComm comm = nccl_comm ? nccl_comm : c->comm;
-    if (!comm) return fail(c, RFX_ESTATE, "rfx_allgather_history: no communicator (rfx_comm_init, or pass one)");
-    const int n = c->comm_nranks;
-    if (nccl_comm && !c->comm) return fail(c, RFX_ESTATE, "rfx_allgather_history: rank and size come from rfx_comm_init");
-    int rc = ensure_streams(c);
+    Rccl *r;
+    NcclComm comm;
+    int rc = comm_enter(c, "rfx_allgather_history", nccl_comm, kAnyRing, &r, &comm);
     if (rc) return rc;
+    const int n = c->comm_nranks;
     char *base = (char *)rfx_tex_device_ptr(c, id);  // held whole: frame row y at y * pitch
     if (!base) return RFX_ENOMEM;
     const Slot &s = c->slots[id];
     const size_t pitch = (size_t)s.width * s.texel;
-    if ((rc = comm_begin(c))) return rc;
+    if ((rc = rfx_comm_begin(c))) return rc;
     int y0 = 0, rows = 0, last_rows = 0;
     rfx_split_rows(c->H, n, 0, &y0, &rows);
     rfx_split_rows(c->H, n, n - 1, nullptr, &last_rows);
@@ -413,24 +432,19 @@ int rfx_allgather_history(rfx_ctx *c, rfx_tex id, void *nccl_comm) {
         if (e) return nccl_fail(c, "rfx_allgather_history: ncclBroadcast", e);
         if (e2) return nccl_fail(c, "rfx_allgather_history: ncclGroupEnd", e2);
     }
-    return comm_end(c);
+    return rfx_comm_end(c);
 }
 
 int rfx_gather_history_rows(rfx_ctx *c, rfx_tex id, void *nccl_comm, size_t *bytes_received) {
     if (!c) return RFX_EINVAL;
     if (bytes_received) *bytes_received = 0;
     if (id != RFX_TEX_COMPOSE && id != RFX_TEX_COMPOSE_RGB) return fail(c, RFX_EINVAL, "rfx_gather_history_rows: RFX_TEX_COMPOSE or RFX_TEX_COMPOSE_RGB");
-    Rccl *r = rccl();
-    if (!r) return fail(c, RFX_EUNSUPPORTED, "rfx_gather_history_rows: RCCL cannot be loaded on this host");
-    NcclComm comm = nccl_comm ? nccl_comm : c->comm;
-    if (!comm) return fail(c, RFX_ESTATE, "rfx_gather_history_rows: no communicator (rfx_comm_init, or pass one)");
-    if (nccl_comm && !c->comm) return fail(c, RFX_ESTATE, "rfx_gather_history_rows: rank and size come from rfx_comm_init");
-    int rc = ensure_streams(c);
+    Rccl *r;
+    NcclComm comm;
+    int rc = comm_enter(c, "rfx_gather_history_rows", nccl_comm, kMaskedRing, &r, &comm);
     if (rc) return rc;
-    hipSetDevice(c->device);
     if (!rfx_tex_device_ptr(c, id)) return RFX_ENOMEM;
-    if (c->comm_nranks > 64) return fail(c, RFX_EUNSUPPORTED, "rfx_gather_history_rows: more than 64 ranks");
-    // 1. this tile's row mask (device reduction over the trace's hand-over plane: one word per frame row, a bit per column block), on the draw stream
+    // this tile's row mask (device reduction over the trace's hand-over plane: one word per frame row, a bit per column block), on the draw stream
     if ((rc = rfx_internal_hit_mask_enqueue(c, c->comm_nranks))) return rc;
     return gather_masked_blocks(c, "rfx_gather_history_rows", r, comm, id, bytes_received);
 }
@@ -438,15 +452,10 @@ int rfx_gather_history_rows(rfx_ctx *c, rfx_tex id, void *nccl_comm, size_t *byt
 int rfx_motion_blur_gather(rfx_ctx *c, const rfx_motion_blur_params *p, void *nccl_comm, size_t *bytes_received) {
     if (!c || !p) return RFX_EINVAL;
     if (bytes_received) *bytes_received = 0;
-    Rccl *r = rccl();
-    if (!r) return fail(c, RFX_EUNSUPPORTED, "rfx_motion_blur_gather: RCCL cannot be loaded on this host");
-    NcclComm comm = nccl_comm ? nccl_comm : c->comm;
-    if (!comm) return fail(c, RFX_ESTATE, "rfx_motion_blur_gather: no communicator (rfx_comm_init, or pass one)");
-    if (nccl_comm && !c->comm) return fail(c, RFX_ESTATE, "rfx_motion_blur_gather: rank and size come from rfx_comm_init");
-    int rc = ensure_streams(c);
+    Rccl *r;
+    NcclComm comm;
+    int rc = comm_enter(c, "rfx_motion_blur_gather", nccl_comm, kMaskedRing, &r, &comm);
     if (rc) return rc;
-    hipSetDevice(c->device);
-    if (c->comm_nranks > 64) return fail(c, RFX_EUNSUPPORTED, "rfx_motion_blur_gather: more than 64 ranks");
     // the tile's own rows of the source into the plane (validates the params; arms the draw), then its reach mask: both on the draw stream
     if ((rc = rfx_motion_blur_stage(c, p))) return rc;
     // (the stage allocated the plane — except on a whole-frame context, which is a ring of one: no block travels and no plane is needed)

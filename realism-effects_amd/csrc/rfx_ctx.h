@@ -30,8 +30,6 @@ struct rfx_ctx {
     bool hits_traced = false;  // a trace is waiting for its shade
     int trace_y0 = 0, trace_y1 = 0, trace_missed = 0;  // the rows and the missedRays option of that trace (rfx_gather_history_rows)
     bool trace_scaled = false;                         // ... and whether it drew a smaller target (resolutionScale != 1)
-    int *hit_rows_dev = nullptr;   // device: [0..1] this tile's (min, max) needed history row, [2..2n+1] every rank's
-    int *hit_rows_host = nullptr;  // pinned mirror of the gathered part
     // the bounded gather's row masks (rfx_gather_history_rows, rfx_ssgi_hit_mask): one word per frame row; device: [0, H) this tile's, [H, (n+1) H) every rank's
     unsigned int *hit_mask_dev = nullptr, *hit_mask_host = nullptr;
     int hit_mask_ranks = 0;  // ranks the two buffers are sized for (each holds (2 n + 2) H words: the masks, then the packed transfer's row offsets)
@@ -95,11 +93,15 @@ struct rfx_ctx {
     std::string err;
 };
 void rfx_comm_release(rfx_ctx *c);  // rfx_comm.hip: called by rfx_destroy
+// rfx_comm.hip, for rfx_peer.hip too: create the exchange stream and its two events once; order the exchange stream after every draw enqueued
+// so far; record the exchange issued since as pending for rfx_comm_wait
+int rfx_ensure_streams(rfx_ctx *c);
+int rfx_comm_begin(rfx_ctx *c);
+int rfx_comm_end(rfx_ctx *c);
 void rfx_peer_release(rfx_ctx *c);  // rfx_peer.hip: called by rfx_destroy (before rfx_comm_release: it drains the exchange stream)
-// rfx_api.hip, for rfx_comm.hip: enqueue on the draw stream the reduction of the traced rays' history rows into rows_dev[0..1] (min, max)
-extern "C" int rfx_internal_hit_rows_enqueue(rfx_ctx *c, int *rows_dev);  // (internal: not part of include/rfx.h)
-// ... and of the traced rays' row masks into the first H words of c->hit_mask_dev (allocated here for `ranks` gathered copies)
-extern "C" int rfx_internal_hit_mask_enqueue(rfx_ctx *c, int ranks);
+// rfx_api.hip, for rfx_comm.hip / rfx_peer.hip: enqueue on the draw stream the reduction of the traced rays' row masks into the first H words
+// of c->hit_mask_dev (allocated here for `ranks` gathered copies)
+extern "C" int rfx_internal_hit_mask_enqueue(rfx_ctx *c, int ranks);  // (internal: not part of include/rfx.h)
 // ... and of the texels a row-tiled rfx_motion_blur with these (validated) params will load, in the same words
 extern "C" int rfx_internal_blur_reach_enqueue(rfx_ctx *c, const rfx_motion_blur_params *p, int ranks);
 // ... and, for the CPU tests: the launch plans of rfx_launch.h as the library computes them (K1's table layout, K3's tile geometry)

@@ -17,6 +17,7 @@
 // exactly as N devices would: that is how the tests hold this mode bit-identical to the all-gather; only its xGMI rate needs a second GPU.
 #include <string.h>
 #include <unistd.h>
+#include "rfx_blocks.h"
 #include "rfx_ctx.h"
 
 namespace {
@@ -56,7 +57,7 @@ __global__ __launch_bounds__(256) void peer_pull(float *mine, float *const *plan
     if (x < W && y < H) {
         int owner = y / tile_base;  // rfx_split_rows: equal tiles of tile_base rows, the last one takes the rest
         if (owner > n - 1) owner = n - 1;
-        if (owner != me && ((mask[y] >> ((x * 32) / W)) & 1u)) {
+        if (owner != me && ((mask[y] >> rfx_block_of_col(x, W)) & 1u)) {
             take = true;
             const size_t i = ((size_t)y * W + x) * fpt;
             const float *src = planes[owner] + i;
@@ -67,14 +68,9 @@ __global__ __launch_bounds__(256) void peer_pull(float *mine, float *const *plan
     if ((threadIdx.x & 63) == 0 && b) atomicAdd(pulled, (unsigned long long)__popcll(b));
 }
 
-int ensure_peer_streams(rfx_ctx *c) {
-    hipSetDevice(c->device);
-    if (!c->comm_stream) {
-        hipError_t e = hipStreamCreateWithFlags(&c->comm_stream, hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_draws, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_comm, hipEventDisableTiming);
-        if (e != hipSuccess) return fail(c, RFX_EDEVICE, "rfx_peer: stream/event creation", e);
-    }
+int ensure_peer_streams(rfx_ctx *c) {  // the exchange stream (rfx_comm.hip) and this mode's own event
+    int rc = rfx_ensure_streams(c);
+    if (rc) return rc;
     if (!c->ev_peer_release) {
         hipError_t e = hipEventCreateWithFlags(&c->ev_peer_release, hipEventDisableTiming);
         if (e != hipSuccess) return fail(c, RFX_EDEVICE, "rfx_peer: event creation", e);
@@ -213,9 +209,7 @@ int rfx_peer_gather_history(rfx_ctx *c, rfx_tex id, size_t *bytes_pulled_previou
     int rc = rfx_internal_hit_mask_enqueue(c, 1);
     if (rc) return rc;
     // the exchange stream starts after every draw enqueued so far: last frame's compose draw, this frame's trace, the mask
-    hipError_t e = hipEventRecord(c->ev_draws, c->stream);
-    if (e == hipSuccess) e = hipStreamWaitEvent(c->comm_stream, c->ev_draws, 0);
-    if (e != hipSuccess) return fail(c, RFX_EDEVICE, "rfx_peer_gather_history: ordering the exchange stream after the draws", e);
+    if ((rc = rfx_comm_begin(c))) return rc;
     unsigned long long *const *flags = (unsigned long long *const *)(c->peer_table_dev + n);
     unsigned int *status = (unsigned int *)c->peer_status_dev;
     unsigned long long *pulled = c->peer_status_dev + 1;
@@ -229,8 +223,7 @@ int rfx_peer_gather_history(rfx_ctx *c, rfx_tex id, size_t *bytes_pulled_previou
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(c->peer_status_host, c->peer_status_dev, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->comm_stream));
     // the shade (rfx_comm_wait) needs the pull only ...
-    HIPCHK(c, hipEventRecord(c->ev_comm, c->comm_stream));
-    c->comm_pending = true;
+    if ((rc = rfx_comm_end(c))) return rc;
     // ... the next compose draw needs every rank to have pulled (rfx_compose waits for this event)
     hipLaunchKernelGGL(peer_barrier, dim3(1), dim3(64), 0, c->comm_stream, flags, me, n, pulled_everywhere, status);
     HIPCHK(c, hipGetLastError());

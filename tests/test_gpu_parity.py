@@ -1444,6 +1444,11 @@ def test_hit_rows_bound_what_the_shade_reads(blue_noise, missed):
             got = ctx.download(abi.TEX_SSGI, y0, rows)
             assert np.array_equal(got, want[y0:y0 + rows]), "tile rows [%d, %d): the shade read a history texel whose mask bit is clear" % (y0, y0 + rows)
     ctx.set_row_window(0, 0)
+    # nothing read at all (every fragment is background): the empty answer keeps its two preset values, and the mask is all zero
+    ctx.upload(abi.TEX_DEPTH, np.ones_like(f.depth))
+    ctx.ssgi_trace(sp)
+    assert ctx.ssgi_hit_rows() == (0x7fffffff, -1)
+    assert not ctx.ssgi_hit_mask().any()
     assert seen_partial  # (the test would be vacuous if every range were the whole frame)
     assert seen_sparse_row  # ... or if every used row had every block bit set
     assert ctx.halo_violations() == 0
