@@ -117,8 +117,9 @@ typedef struct rfx_ssgi_params {
     float envBlur;            /* uniform envBlur: mip = envBlur * maxEnvMapMipLevel (ssgi.frag:322); unused without USE_ENVMAP */
     int32_t blueNoiseIndex;   /* uniform blueNoiseIndex (BlueNoiseUtils.js:24-32 recurrence, host side) */
     float resolutionScale;    /* SSGIPass.setSize (SSGIPass.js:52-57): the pass renders into a (W*s) x (H*s) target and `resolution` is that size;
-                                 0 is read as 1.  W*s and H*s must be whole numbers; s != 1 needs a whole-frame context.  The target's
-                                 texels are stored row-major at the start of RFX_TEX_SSGI (pitch W*s).                               */
+                                 0 is read as 1.  W*s and H*s must be whole numbers (RFX_EINVAL otherwise).  The target's texels are
+                                 stored row-major at the start of RFX_TEX_SSGI (pitch W*s): every row on a whole-frame context, the
+                                 rows rfx_ssgi_target_rows names on a row tile (see there for the layout and the halo rule).         */
     int32_t historySource;    /* uniform accumulatedTexture = ssgiEffect.denoiser.texture (SSGIPass.js:89, Denoiser.js:67-78):
                                  0  denoiseMode "full" / "full_temporal": K4's output, RFX_TEX_COMPOSE;
                                  1  "temporal": K2's texture[0], RFX_TEX_TEMPORAL0 (whole-frame contexts only);
@@ -240,7 +241,9 @@ int rfx_set_stream(rfx_ctx *, void *hip_stream);
 /* Restrict the rows the following draws PRODUCE to frame rows [y0, y1) (intersected with what each draw would produce anyway);
  * y1 <= y0 resets.  Every pixel's result is independent of how the rows are split over launches, so a row-tiled run can draw the
  * interior of its tile while the halo rows of the input are still being exchanged, then the two boundary strips (rfx_amd/tiling.py).
- * Draws whose window is empty return RFX_OK without launching.  Ignored by rfx_ssgi_* with resolutionScale != 1 (whole-frame only). */
+ * Draws whose window is empty return RFX_OK without launching.  Ignored by rfx_ssgi_* with resolutionScale != 1, on whole-frame and
+ * row-tiled contexts alike: the smaller target is always drawn whole (rfx_ssgi_target_rows), and rfx_temporal_reproject under a window
+ * reads target rows that draw has left regardless. */
 int rfx_set_row_window(rfx_ctx *, int y0, int y1);
 /* Which vUv the draws' fragments see (every full-screen pass of the reference reads its inputs at the interpolated varying vUv,
  * src/utils/shader/basic.vert; e.g. ssgi.frag:107, temporal_reproject.frag:118, poisson_denoise.frag:128, DenoiserComposePass.js:58).
@@ -336,6 +339,21 @@ int rfx_ssgi_march(rfx_ctx *, const rfx_ssgi_params *);
  * result in RFX_TEX_SSGI is bit-identical to rfx_ssgi_march's.  rfx_ssgi_shade without a pending trace: RFX_ESTATE. */
 int rfx_ssgi_trace(rfx_ctx *, const rfx_ssgi_params *);
 int rfx_ssgi_shade(rfx_ctx *, const rfx_ssgi_params *);
+/* resolutionScale != 1 on a row tile (added to ABI 21 without a new version number: one more entry point and three refusals fewer, nothing an
+ * existing caller sees differently; a host checks for the symbol).  rfx_temporal_reproject reads the (W*s) x (H*s) target NEAREST at the full-resolution vUv:
+ * frame row gy takes target row iy(gy) = nearest(vUv.y(gy) * H*s).  Its neighbourhood reads +-2 frame rows around the tile, so a tile
+ * context draws exactly the target rows [row0, row0 + rows) that the frame rows [tile_y0 - e, tile_y0 + tile_rows + e), e = min(halo_rows, 2),
+ * clipped to the frame, map to — under the context's vUv model — and stores them from the START of RFX_TEX_SSGI with pitch W*s: the
+ * whole-frame layout shifted by row0.  Neighbouring tiles draw overlapping target rows redundantly (a fragment depends on its own
+ * coordinates and the per-draw blue-noise shift only: the overlap is bit-identical).  The trace -> shade hand-over, rfx_ssgi_hit_mask,
+ * rfx_gather_history_rows and rfx_peer_gather_history follow the same rows.
+ * Halo rule: a fragment of target row j fetches the G-buffer and the direct light of frame row nearest(vUv.y(j) * H) through the held band.
+ * That row lies within ceil(1 / (2 s)) rows of a frame row that maps to j, so the band must hold 2 + ceil(1 / (2 s)) rows around the tile
+ * (rfx_amd/tiling.py required_halo(resolution_scale=s)); a fetch outside the band is clamped and counted by rfx_halo_violations.  A tile whose
+ * target rows do not fit the slot (held rows * W texels) is refused with RFX_EINVAL.
+ * rfx_ssgi_target_rows reports row0 / rows for a scale: 0, H*s on a whole-frame context; the held band of RFX_TEX_SSGI at scale 1 (or 0).
+ * W*s or H*s not whole: RFX_EINVAL.  A host downloads a tile's target rows as the first rows * W*s texels of the slot. */
+int rfx_ssgi_target_rows(rfx_ctx *, float resolutionScale, int *row0, int *rows);
 int rfx_temporal_reproject(rfx_ctx *, const rfx_temporal_params *);
 /* renderer.copyFramebufferToTexture(tmpVec2, this.framebufferTexture), TemporalReprojectPass.js:198-201: the tile rows of
  * the pass's render target RFX_TEX_TEMPORAL0 become the history the NEXT rfx_temporal_reproject samples (linear filter).

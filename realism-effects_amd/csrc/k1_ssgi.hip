@@ -514,7 +514,9 @@ RFX_DEV void k1_ssgi_march_body(const K1Args &A, const FrameDims &d, const k1_ce
     const float *C = p.camera.matrixWorld, *Vw = p.camera.matrixWorldInverse;
     const float *P = p.camera.projectionMatrix, *Pi = p.camera.projectionMatrixInverse;
 
-    // vUv of the (possibly smaller, resolutionScale) render target; the full-resolution inputs are fetched NEAREST at vUv
+    // vUv of the (possibly smaller, resolutionScale) render target; the full-resolution inputs are fetched NEAREST at vUv.  y is a row of that
+    // target: a row tile draws its rows [j0, j1) (rfx_launch.h rfx_scaled_rows) into the start of its slot, and the host hands `out.ptr` and `hits`
+    // over rebased by j0 rows (k1_args in rfx_api.hip), so that row y sits at y * out_w here whatever the tile
     const bool scaled = A.out_w != d.W || A.out_h != d.H;
     const float u = rfx_frag_u(A.out_uv, x, y), v = rfx_frag_v(A.out_uv, y);
     const int sx = scaled ? rfx_nearest_idx(u, d.fW, d.W) : x, sy = scaled ? rfx_nearest_idx(v, d.fH, d.H) : y;
@@ -717,6 +719,22 @@ __global__ __launch_bounds__(64 * K1_WAVES) RFX_WAVES_PER_EU(ENV ? 1 : 8) void k
     rfx_flush_violations(d);
 }
 
+// The two rays of hand-over texel i -> the mask words of the history texels their shading fetches: the ONE statement of the predicate the two
+// reductions below share (what the mask is, and why it must stay k1_shade's predicate: the comment that follows)
+RFX_DEV void k1_mask_rays(const FrameDims &d, const float4 *hits, size_t i, int allow_missed, unsigned int *mask) {
+    const float4 h0 = hits[2 * i], h1 = hits[2 * i + 1];
+    const float u[2] = {h0.x, h0.z}, v[2] = {h0.y, h0.w}, px[2] = {h1.x, h1.y};
+#pragma unroll
+    for (int r = 0; r < 2; r++) {
+        const bool missed = px[r] == 10.0e9f;
+        if ((allow_missed || !missed) && u[r] >= 0.0f && u[r] <= 1.0f && v[r] >= 0.0f && v[r] <= 1.0f) {
+            const int row = rfx_nearest_idx(v[r], d.fH, d.H), col = rfx_nearest_idx(u[r], d.fW, d.W);
+            const unsigned int bit = 1u << rfx_block_of_col(col, d.W);
+            if (!(mask[row] & bit)) atomicOr(&mask[row], bit);
+        }
+    }
+}
+
 // Row-tiled runs, between trace and shade: the texels of the history texture (last frame's composed GI) that the shading of THESE rays will
 // fetch — k1_shade reads it NEAREST at a ray's final uv when that uv is on screen and the ray hit (or missed rays are allowed), ssgi.frag:396-427
 // (k1_shade states this predicate itself: keep the two alike).  ONE 32-bit word per frame row (zeroed by the caller), bit b = some ray
@@ -730,17 +748,22 @@ __global__ __launch_bounds__(256) void k1_hit_mask(FrameDims d, int y0, int y1, 
     const float dp = ((const float *)depth.ptr)[rfx_xy_index(d, depth.row0, depth.rows, x, y)];
     if (dp == 1.0f) return;  // background fragments return before tracing (their hand-over texels are stale)
     const size_t i = (size_t)rfx_local_row(d, out.row0, out.rows, y) * d.W + x;
-    const float4 h0 = hits[2 * i], h1 = hits[2 * i + 1];
-    const float u[2] = {h0.x, h0.z}, v[2] = {h0.y, h0.w}, px[2] = {h1.x, h1.y};
-#pragma unroll
-    for (int r = 0; r < 2; r++) {
-        const bool missed = px[r] == 10.0e9f;
-        if ((allow_missed || !missed) && u[r] >= 0.0f && u[r] <= 1.0f && v[r] >= 0.0f && v[r] <= 1.0f) {
-            const int row = rfx_nearest_idx(v[r], d.fH, d.H), col = rfx_nearest_idx(u[r], d.fW, d.W);
-            const unsigned int bit = 1u << rfx_block_of_col(col, d.W);
-            if (!(mask[row] & bit)) atomicOr(&mask[row], bit);
-        }
-    }
+    k1_mask_rays(d, hits, i, allow_missed, mask);
+}
+
+// The same reduction after a trace at resolutionScale != 1: a fragment is texel (x, y) of the out_w-wide target, y in [j0, j1) (rfx_launch.h
+// rfx_scaled_rows); its depth is the frame texel k1_ssgi_march_body fetches for it, its rays sit at the shifted index of the hand-over plane.  The
+// rays' uv addresses the full-resolution history either way: the same rows, the same column blocks, the same predicate.
+__global__ __launch_bounds__(256) void k1_hit_mask_scaled(FrameDims d, UvPlanes out_uv, int out_w, int j0, int j1, TexView depth, const float4 *hits, int allow_missed,
+                                                          unsigned int *mask) {
+    const int x = blockIdx.x * 64 + threadIdx.x, y = j0 + blockIdx.y * 4 + threadIdx.y;
+    d.viol = 0;
+    if (x >= out_w || y >= j1) return;
+    const int sx = rfx_nearest_idx(rfx_frag_u(out_uv, x, y), d.fW, d.W), sy = rfx_nearest_idx(rfx_frag_v(out_uv, y), d.fH, d.H);
+    const float dp = ((const float *)depth.ptr)[rfx_xy_index(d, depth.row0, depth.rows, sx, sy)];
+    if (dp == 1.0f) return;  // background fragments return before tracing (their hand-over texels are stale)
+    const size_t i = (size_t)(y - j0) * out_w + x;
+    k1_mask_rays(d, hits, i, allow_missed, mask);
 }
 
 // Pre-pass: view-space Z per texel (getViewZ, ssgi_utils.frag:9: nearMulFar / (farMinusNear * depth - cameraFar), IEEE) and its exact
@@ -868,6 +891,13 @@ int rfx_k1_base_cell() { return BASE; }
 hipError_t rfx_launch_k1_hit_mask(const FrameDims &d, int y0, int y1, TexView depth, TexViewW out, const float4 *hits, bool allow_missed, unsigned int *mask, hipStream_t stream) {
     dim3 block(64, 4), grid((d.W + 63) / 64, (y1 - y0 + 3) / 4);
     hipLaunchKernelGGL(k1_hit_mask, grid, block, 0, stream, d, y0, y1, depth, out, hits, allow_missed ? 1 : 0, mask);
+    return hipGetLastError();
+}
+
+hipError_t rfx_launch_k1_hit_mask_scaled(const FrameDims &d, const UvPlanes &out_uv, int out_w, int j0, int j1, TexView depth, const float4 *hits, bool allow_missed,
+                                         unsigned int *mask, hipStream_t stream) {
+    dim3 block(64, 4), grid((out_w + 63) / 64, (j1 - j0 + 3) / 4);
+    hipLaunchKernelGGL(k1_hit_mask_scaled, grid, block, 0, stream, d, out_uv, out_w, j0, j1, depth, hits, allow_missed ? 1 : 0, mask);
     return hipGetLastError();
 }
 

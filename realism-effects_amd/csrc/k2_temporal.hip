@@ -183,11 +183,12 @@ RFX_DEV void k2_body(const K2Args &A, const FrameDims &d) {
         const int gx = tx0 - AP + lx, gy = ty0 - AP + ly;
         if (gx < 0 || gx >= d.W || gy < 0 || gy >= d.H || gy > A.y1 - 1 + AP) continue;
         // the input texel this full-resolution position samples: itself, or — K1 drawn at resolutionScale < 1 — the NEAREST texel of the
-        // smaller target at this pixel's vUv (whole-frame contexts only; the target is stored at the start of the slot, pitch in_w)
+        // smaller target at this pixel's vUv (the slot holds the target rows [in_j0, in_j0 + in_rows) from its start, pitch in_w: every row on a
+        // whole-frame context, the rows this tile's staging addresses on a row tile — a row outside them is a halo violation, clamped and counted)
         uint4 t;
         if (A.in_w != d.W || A.in_h != d.H) {
             const int ix = rfx_nearest_idx(rfx_frag_u(d.uv, gx, gy), (float)A.in_w, A.in_w), iy = rfx_nearest_idx(rfx_frag_v(d.uv, gy), (float)A.in_h, A.in_h);
-            t = ((const uint4 *)A.ssgi.ptr)[(size_t)iy * A.in_w + ix];
+            t = ((const uint4 *)A.ssgi.ptr)[(size_t)(WHOLE ? iy : rfx_local_row(d, A.in_j0, A.in_rows, iy)) * A.in_w + ix];
         } else {
             t = rfx_gather<uint4>(A.ssgi.ptr, (unsigned int)(__mul24(rfx_view_row<WHOLE>(d, A.ssgi, gy), d.W) + gx));
         }

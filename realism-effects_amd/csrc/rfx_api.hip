@@ -384,6 +384,17 @@ static FrameDims dims(rfx_ctx *c) {
     d.halo_violations = c->halo_violations;
     return d;
 }
+// The rows of an Hs-row smaller target (resolutionScale != 1) this context's RFX_TEX_SSGI holds, stored from the start of the slot: all of them on
+// a whole-frame context; on a row tile the rows K2's staging of the tile addresses (rfx_launch.h rfx_scaled_rows), with the apron min(halo, 2)
+// K1 widens its launch by at scale 1.  rfx_set_row_window does not apply: K2 under a window reads rows K1 has drawn regardless.
+static rfx_scaled_rows_plan ctx_scaled_rows(const rfx_ctx *c, int Hs) {
+    if (c->tile_y0 == 0 && c->tile_rows == c->H) return {0, Hs};
+    return rfx_scaled_rows(rfx_uv_planes(c->uv_model, c->W, c->H), Hs, c->tile_y0, c->tile_y0 + c->tile_rows, c->halo < 2 ? c->halo : 2);
+}
+// ... and whether they fit the slot (sized for the held band at full width) and the trace -> shade hand-over plane (sized like it)
+static bool scaled_rows_fit(const rfx_ctx *c, int Ws, const rfx_scaled_rows_plan &t) {
+    return (size_t)(t.j1 - t.j0) * Ws <= (size_t)c->slots[RFX_TEX_SSGI].rows * c->W;
+}
 static int need(rfx_ctx *c, const int *ids, int n) {
     for (int i = 0; i < n; i++) {
         int rc = ensure(c, ids[i]);
@@ -628,7 +639,8 @@ static int ssgi_validate(rfx_ctx *c, const rfx_ssgi_params *p) {
         const float fw = (float)c->W * rs, fh = (float)c->H * rs;
         if (!(rs > 0.0f && rs <= 1.0f) || fw != floorf(fw) || fh != floorf(fh) || fw < 1.0f || fh < 1.0f)
             return fail(c, RFX_EINVAL, "rfx_ssgi_march/trace/shade: resolutionScale must be in (0, 1] with whole W*s and H*s");
-        if (c->tile_y0 != 0 || c->tile_rows != c->H) return fail(c, RFX_EUNSUPPORTED, "rfx_ssgi_march/trace/shade: resolutionScale != 1 needs a whole-frame context");
+        if (!scaled_rows_fit(c, (int)fw, ctx_scaled_rows(c, (int)fh)))
+            return fail(c, RFX_EINVAL, "rfx_ssgi_march/trace/shade: the target rows of this tile at this resolutionScale do not fit the held band (more halo rows)");
     }
     return RFX_OK;
 }
@@ -658,7 +670,7 @@ static int k1_scratch(rfx_ctx *c, const rfx_k1_table_plan &T, int coarse_w, int 
 // ... and, for a split draw, the trace -> shade hand-over plane
 static int k1_hand_over(rfx_ctx *c, int stage) {
     if (stage == 0) return RFX_OK;
-    // indexed like the output texture (resolutionScale needs a whole-frame context, so W * held rows covers it)
+    // indexed like the output texture (a scaled target's rows are checked against W * held rows: ssgi_validate)
     const size_t n = (size_t)c->W * c->slots[RFX_TEX_SSGI].rows * 2;
     if (stage == 2 && (!c->hits || !c->hits_traced)) return fail(c, RFX_ESTATE, "rfx_ssgi_shade: no rfx_ssgi_trace of this frame to finish");
     if (!c->hits) {
@@ -675,10 +687,12 @@ static bool k1_args(rfx_ctx *c, const rfx_ssgi_params *p, int stage, const rfx_k
     bool any = launch_rows(c, RFX_TEX_SSGI, c->halo < 2 ? c->halo : 2, &A.y0, &A.y1);
     A.out_w = c->W; A.out_h = c->H;
     const float rs = ssgi_resolution_scale(p);
-    if (rs != 1.0f) {  // (validated: whole W * rs and H * rs, a whole-frame context)
+    int out_j0 = 0;
+    if (rs != 1.0f) {  // (validated: whole W * rs and H * rs, target rows that fit the slot)
         A.out_w = (int)((float)c->W * rs); A.out_h = (int)((float)c->H * rs);
-        A.y0 = 0; A.y1 = A.out_h;
-        any = true;  // whole-frame contexts only: the row window does not apply to the scaled target
+        const rfx_scaled_rows_plan t = ctx_scaled_rows(c, A.out_h);  // TARGET rows: every one, or the rows K2's staging of this tile addresses
+        A.y0 = out_j0 = t.j0; A.y1 = t.j1;
+        any = t.j1 > t.j0;  // the row window does not apply to the scaled target
     }
     A.out_uv = rfx_uv_planes(c->uv_model, A.out_w, A.out_h);
     A.depth = view(c, RFX_TEX_DEPTH); A.gbuffer = view(c, RFX_TEX_GBUFFER); A.direct = view(c, RFX_TEX_DIRECT_LIGHT);
@@ -686,6 +700,9 @@ static bool k1_args(rfx_ctx *c, const rfx_ssgi_params *p, int stage, const rfx_k
     A.blue = c->slots[RFX_TEX_BLUE_NOISE].ptr;
     blue_noise_shift(p->blueNoiseIndex, &A.shift_x, &A.shift_y);
     A.out = wview(c, RFX_TEX_SSGI);
+    // a scaled tile keeps its target rows [j0, j1) at the start of the slot: the kernel addresses target row y at y * out_w, so it is handed the
+    // address row 0 WOULD have (never dereferenced below row j0: the launch draws [j0, j1), which scaled_rows_fit has checked against the slot)
+    A.out.ptr = (void *)((uintptr_t)A.out.ptr - (size_t)out_j0 * A.out_w * sizeof(uint4));
     A.p = *p;
     // SSGIPass.js:84-87: computed in JS doubles, then rounded to float uniforms
     A.nearMulFar = (float)((double)p->camera.near_ * (double)p->camera.far_);
@@ -710,7 +727,7 @@ static bool k1_args(rfx_ctx *c, const rfx_ssgi_params *p, int stage, const rfx_k
         while ((m >> (lg + 1)) > 0) lg++;
         A.maxEnvMapMipLevel = c->env ? (float)(lg + 1) : 0.0f;
     }
-    A.hits = stage != 0 ? c->hits : nullptr;
+    A.hits = stage != 0 ? (float4 *)((uintptr_t)c->hits - (size_t)out_j0 * A.out_w * 2 * sizeof(float4)) : nullptr;  // (rebased like `out`)
     return any;
 }
 
@@ -756,13 +773,18 @@ static int ssgi_draw(rfx_ctx *c, const rfx_ssgi_params *p, int stage) {
     HIPCHK(c, hipEventRecord(c->ev_k1_done, c->stream));  // the next pre-pass overwrites what this launch reads
     c->k1_event_set = true;
     c->hits_traced = stage == 1;
-    if (stage == 1) { c->trace_y0 = A.y0; c->trace_y1 = any ? A.y1 : A.y0; c->trace_missed = p->missedRays; c->trace_scaled = ssgi_resolution_scale(p) != 1.0f; }
+    if (stage == 1) { c->trace_y0 = A.y0; c->trace_y1 = any ? A.y1 : A.y0; c->trace_missed = p->missedRays; c->trace_scaled = ssgi_resolution_scale(p) != 1.0f; c->trace_out_w = A.out_w; c->trace_out_h = A.out_h; }
     return RFX_OK;
 }
 
 // the two launch plans as built, for the CPU tests (rfx_launch.h)
 int rfx_internal_k1_table(int W, int H, struct rfx_k1_table_plan *out) {
     *out = rfx_k1_table(W, H);
+    return RFX_OK;
+}
+int rfx_internal_scaled_rows(int W, int H, int Hs, int uv_model, int y0, int y1, int apron, int *j0, int *j1) {
+    const rfx_scaled_rows_plan t = rfx_scaled_rows(rfx_uv_planes(uv_model, W, H), Hs, y0, y1, apron);
+    *j0 = t.j0; *j1 = t.j1;
     return RFX_OK;
 }
 int rfx_internal_k3_tile(int W, int H, float radius, int inputIsTemporal, int textureCount, struct rfx_k3_tile_plan *out) {
@@ -792,12 +814,14 @@ static int hit_mask_scratch(rfx_ctx *c, int ranks) {
 
 int rfx_internal_hit_mask_enqueue(rfx_ctx *c, int ranks) {
     if (!c->hits || !c->hits_traced) return fail(c, RFX_ESTATE, "rfx_gather_history_rows / rfx_ssgi_hit_mask: no rfx_ssgi_trace of this frame is waiting for its shade");
-    if (c->trace_scaled) return fail(c, RFX_EUNSUPPORTED, "rfx_ssgi_hit_mask / rfx_gather_history_rows: the last rfx_ssgi_trace ran with resolutionScale != 1");
     RFX_ENTER(c);
     int rc = hit_mask_scratch(c, ranks);
     if (rc) return rc;
     HIPCHK(c, hipMemsetAsync(c->hit_mask_dev, 0, (size_t)c->H * sizeof(unsigned int), c->stream));
-    if (c->trace_y1 > c->trace_y0)
+    if (c->trace_y1 > c->trace_y0 && c->trace_scaled)  // trace_y0 / trace_y1 are TARGET rows then
+        HIPCHK(c, rfx_launch_k1_hit_mask_scaled(dims(c), rfx_uv_planes(c->uv_model, c->trace_out_w, c->trace_out_h), c->trace_out_w, c->trace_y0, c->trace_y1,
+                                                view(c, RFX_TEX_DEPTH), c->hits, c->trace_missed != 0, c->hit_mask_dev, c->stream));
+    else if (c->trace_y1 > c->trace_y0)
         HIPCHK(c, rfx_launch_k1_hit_mask(dims(c), c->trace_y0, c->trace_y1, view(c, RFX_TEX_DEPTH), wview(c, RFX_TEX_SSGI), c->hits, c->trace_missed != 0, c->hit_mask_dev, c->stream));
     return RFX_OK;
 }
@@ -835,6 +859,21 @@ int rfx_ssgi_hit_rows(rfx_ctx *c, int *row_lo, int *row_hi) {
     return RFX_OK;
 }
 
+int rfx_ssgi_target_rows(rfx_ctx *c, float resolutionScale, int *row0, int *rows) {
+    if (!c) return RFX_EINVAL;
+    const float rs = resolutionScale == 0.0f ? 1.0f : resolutionScale;
+    rfx_scaled_rows_plan t = {c->slots[RFX_TEX_SSGI].row0, c->slots[RFX_TEX_SSGI].row0 + c->slots[RFX_TEX_SSGI].rows};  // scale 1: the held band
+    if (rs != 1.0f) {
+        const float fw = (float)c->W * rs, fh = (float)c->H * rs;
+        if (!(rs > 0.0f && rs <= 1.0f) || fw != floorf(fw) || fh != floorf(fh) || fw < 1.0f || fh < 1.0f)
+            return fail(c, RFX_EINVAL, "rfx_ssgi_target_rows: resolutionScale must be in (0, 1] with whole W*s and H*s");
+        t = ctx_scaled_rows(c, (int)fh);
+    }
+    if (row0) *row0 = t.j0;
+    if (rows) *rows = t.j1 - t.j0;
+    return RFX_OK;
+}
+
 int rfx_ssgi_march(rfx_ctx *c, const rfx_ssgi_params *p) { return ssgi_draw(c, p, 0); }
 int rfx_ssgi_trace(rfx_ctx *c, const rfx_ssgi_params *p) { return ssgi_draw(c, p, 1); }
 int rfx_ssgi_shade(rfx_ctx *c, const rfx_ssgi_params *p) { return ssgi_draw(c, p, 2); }
@@ -864,8 +903,12 @@ int rfx_temporal_reproject(rfx_ctx *c, const rfx_temporal_params *p) {
     A.in_w = p->inputWidth > 0 ? p->inputWidth : c->W;
     A.in_h = p->inputHeight > 0 ? p->inputHeight : c->H;
     if (A.in_w > c->W || A.in_h > c->H) return fail(c, RFX_EINVAL, "rfx_temporal_reproject: inputWidth/inputHeight larger than the frame");
-    if ((A.in_w != c->W || A.in_h != c->H) && (c->tile_y0 != 0 || c->tile_rows != c->H))
-        return fail(c, RFX_EUNSUPPORTED, "rfx_temporal_reproject: a smaller input texture (resolutionScale != 1) needs a whole-frame context");
+    {   // a smaller input texture: the target rows K1 left at the start of the slot (every row on a whole-frame context)
+        const rfx_scaled_rows_plan t = ctx_scaled_rows(c, A.in_h);
+        A.in_j0 = t.j0; A.in_rows = t.j1 - t.j0;
+        if ((A.in_w != c->W || A.in_h != c->H) && (A.in_rows < 1 || !scaled_rows_fit(c, A.in_w, t)))
+            return fail(c, RFX_EINVAL, "rfx_temporal_reproject: the input texture's rows of this tile do not fit the held band (more halo rows)");
+    }
     A.out0 = wview(c, RFX_TEX_TEMPORAL0); A.out1 = wview(c, o1);
     A.p = *p;
     // TemporalReprojectPass.js:135: invTexSize.set(1 / width, 1 / height) in doubles

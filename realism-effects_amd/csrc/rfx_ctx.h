@@ -29,7 +29,8 @@ struct rfx_ctx {
     float4 *hits = nullptr;    // K1 trace -> shade hand-over (rfx_ssgi_trace), 2 texels per SSGI texel
     bool hits_traced = false;  // a trace is waiting for its shade
     int trace_y0 = 0, trace_y1 = 0, trace_missed = 0;  // the rows and the missedRays option of that trace (rfx_gather_history_rows)
-    bool trace_scaled = false;                         // ... and whether it drew a smaller target (resolutionScale != 1)
+    bool trace_scaled = false;                         // ... and whether it drew a smaller target (resolutionScale != 1):
+    int trace_out_w = 0, trace_out_h = 0;              //     its size; trace_y0 / trace_y1 are then TARGET rows (rfx_launch.h rfx_scaled_rows)
     // the bounded gather's row masks (rfx_gather_history_rows, rfx_ssgi_hit_mask): one word per frame row; device: [0, H) this tile's, [H, (n+1) H) every rank's
     unsigned int *hit_mask_dev = nullptr, *hit_mask_host = nullptr;
     int hit_mask_ranks = 0;  // ranks the two buffers are sized for (each holds (2 n + 2) H words: the masks, then the packed transfer's row offsets)
@@ -106,6 +107,7 @@ extern "C" int rfx_internal_hit_mask_enqueue(rfx_ctx *c, int ranks);  // (intern
 extern "C" int rfx_internal_blur_reach_enqueue(rfx_ctx *c, const rfx_motion_blur_params *p, int ranks);
 // ... and, for the CPU tests: the launch plans of rfx_launch.h as the library computes them (K1's table layout, K3's tile geometry)
 extern "C" int rfx_internal_k1_table(int W, int H, struct rfx_k1_table_plan *out);
+extern "C" int rfx_internal_scaled_rows(int W, int H, int Hs, int uv_model, int y0, int y1, int apron, int *j0, int *j1);
 extern "C" int rfx_internal_k3_tile(int W, int H, float radius, int inputIsTemporal, int textureCount, struct rfx_k3_tile_plan *out);
 
 extern thread_local std::string g_create_err;

@@ -69,9 +69,10 @@ __device__ __forceinline__ float rfx_frag_u(const UvPlanes &q, int x, int y) {
     const bool upper = __mul24(2 * y + 1, q.W) > __mul24(2 * x + 1, q.H);  // < 2^31: rfx_create bounds W, H
     return __fmaf_rn(q.du, (float)x, upper ? q.u0_upper : q.u0_lower);
 }
-__device__ __forceinline__ float rfx_frag_v(const UvPlanes &q, int y) {
+// (host too: rfx_launch.h rfx_scaled_rows plans a scaled tile's rows with the expression the kernels evaluate)
+__host__ __device__ __forceinline__ float rfx_frag_v(const UvPlanes &q, int y) {
     if (q.model == RFX_UV_IDEAL) return ((float)y + 0.5f) / q.fH;
-    return __fmaf_rn(q.dv, (float)y, q.v0);
+    return __builtin_fmaf(q.dv, (float)y, q.v0);
 }
 
 struct FrameDims {
@@ -127,11 +128,17 @@ inline int rfx_xcd_grid(int G, int nbx, int nby) {
 
 // nearest CLAMP_TO_EDGE index as x86 cvttss2si + clamp computes it:
 // NaN and |c| >= 2^31 give INT_MIN -> texel 0 (AMD's v_cvt_i32_f32 would saturate to size-1).
-RFX_DEV int rfx_nearest_idx(float u, float fsize, int size) {
+// (host too, for rfx_launch.h rfx_scaled_rows: there the one v_med3_f32 is spelled as the two comparisons it performs — c is never NaN here)
+__host__ __device__ __forceinline__ int rfx_nearest_idx(float u, float fsize, int size) {
     float c = u * fsize;
     c = (c < 2147483648.0f) ? c : 0.0f;  // NaN compares false -> 0
     // clamp in float, then truncate: the same index as max((int)c, 0) then min(.., size - 1) for every finite c (size <= 2^24)
+#if defined(__HIP_DEVICE_COMPILE__)
     return (int)__builtin_amdgcn_fmed3f(c, 0.0f, (float)(size - 1));
+#else
+    const float hi = (float)(size - 1);
+    return (int)(c < 0.0f ? 0.0f : (c > hi ? hi : c));
+#endif
 }
 
 RFX_DEV size_t rfx_texel_index(const FrameDims &d, int row0, int rows, float u, float v) {

@@ -29,7 +29,9 @@ struct K1Args {
     float maxEnvMapMipLevel;
     const float *env_marginal, *env_conditional;  // EquirectHdrInfo.marginalWeights (env_h) / conditionalWeights (env_w x env_h), importanceSampling
     float totalSumWhole, totalSumDecimal;
-    int out_w, out_h;  // the pass's render target = `resolution` (frame size unless resolutionScale != 1)
+    int out_w, out_h;  // the pass's render target = `resolution` (frame size unless resolutionScale != 1: [y0, y1) are then rows of THAT target, texel
+                       // (x, y) is stored at y * out_w + x of `out.ptr` and `hits`, and a row tile — which holds the target rows [j0, j1) of rfx_launch.h
+                       // rfx_scaled_rows from the start of its slot — passes both pointers rebased by -j0 rows; out.row0 / out.rows are not read)
     UvPlanes out_uv;   // that target's vUv
     float4 *hits;      // trace -> shade hand-over (2 texels per output pixel, indexed like `out`); null for the fused launch
     unsigned int *tile_counter;  // the persistent march kernel's work counter (context scratch; zero when the launch starts)
@@ -52,6 +54,9 @@ struct K2Args {
     float invW, invH;        // invTexSize (TemporalReprojectPass.js:135)
     float rcpInvW, rcpInvH;  // RN(1 / invTexSize): the constant of the exact quotient P / invTexSize (RFX_DIV_CONST's form, k2_bicubic)
     float prevPV[16];  // prevProjectionMatrix * prevViewMatrix, multiplied in fp32 like the shader does per fragment
+    // a smaller input texture on a row tile (appended, for in_w / in_h above: nothing in front of it moves): `ssgi` holds the target rows
+    // [in_j0, in_j0 + in_rows) from the start of the slot, pitch in_w (rfx_launch.h rfx_scaled_rows); 0, in_h on a whole-frame context
+    int in_j0, in_rows;
 };
 
 struct K3Args {
@@ -130,6 +135,10 @@ hipError_t rfx_launch_k1_prepare(const K1Args &, hipStream_t);
 hipError_t rfx_launch_k1(const K1Args &, int stage /* 0 fused, 1 trace, 2 shade */, hipStream_t);
 // mask[row] |= 1 << column block (32 blocks across the frame) for every history texel the shade stage of the traced rays of rows [y0, y1) will read (H words, zeroed)
 hipError_t rfx_launch_k1_hit_mask(const FrameDims &, int y0, int y1, TexView depth, TexViewW out, const float4 *hits, bool allow_missed, unsigned int *mask, hipStream_t);
+// ... after a trace at resolutionScale != 1: the fragments are the out_w x [j0, j1) target rows (vUv planes out_uv), their hand-over texels sit at
+// (y - j0) * out_w + x, their depth at the NEAREST frame texel of their vUv; rows and column blocks are named at full resolution, as k1_shade reads them
+hipError_t rfx_launch_k1_hit_mask_scaled(const FrameDims &, const UvPlanes &out_uv, int out_w, int j0, int j1, TexView depth, const float4 *hits, bool allow_missed,
+                                         unsigned int *mask, hipStream_t);
 hipError_t rfx_launch_k2(const K2Args &, hipStream_t);
 hipError_t rfx_launch_k3(const K3Args &, hipStream_t);
 hipError_t rfx_launch_k4(const K4Args &, hipStream_t);

@@ -1,10 +1,13 @@
-// rfx_launch.h — what a launch decides on the host before it launches: K1's table layout, K3's tile geometry, the "whole frame" test, the step
-// from a run-time option to a template argument, and what is remembered per kernel and device.  Host only.  The two plans are pure functions
-// of their arguments (no HIP call, no context): rfx_api.hip exports them as rfx_internal_k1_table / rfx_internal_k3_tile and the CPU tests
-// call them as built (tests/test_k1_table_layout.py, tests/test_k3_tile_geometry.py).
+// rfx_launch.h — what a launch decides on the host before it launches: K1's table layout, a scaled tile's target rows, K3's tile geometry, the
+// "whole frame" test, the step from a run-time option to a template argument, and what is remembered per kernel and device.  Host code
+// (rfx_device.h comes in for UvPlanes and the two vUv expressions the kernels and the row plan share).  The plans are pure functions of their
+// arguments (no HIP call, no context): rfx_api.hip exports them as rfx_internal_k1_table / rfx_internal_k3_tile / rfx_internal_scaled_rows and
+// the CPU tests call them as built (tests/test_k1_table_layout.py, tests/test_k3_tile_geometry.py, tests/test_resolution_scale_rows_cpu.py).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <type_traits>
+#include "rfx_device.h"
 
 // ---------------------------------------------------------------- K1: the march's (min, max) table
 // The table lives in every workgroup's LDS (four workgroups per CU): the cell edge is doubled until the table fits.  Two layouts (k1_tap_at):
@@ -40,6 +43,27 @@ inline rfx_k1_table_plan rfx_k1_table(int W, int H) {
         t.pitch_log2 = pl2;
     }
     t.vec4 = (t.pitch * t.cells_h + 3) / 4;
+    return t;
+}
+
+// ---------------------------------------------------------------- resolutionScale < 1: the rows of the smaller target a row tile draws
+// K1 draws a Ws x Hs target, K2 reads it NEAREST at the full-resolution vUv: position (gx, gy) of the frame takes target row
+// iy(gy) = rfx_nearest_idx(rfx_frag_v(frame uv, gy), Hs, Hs) (k2_body's staging loop).  K2 stages the rows gy of [y0 - apron, y1 - 1 + apron]
+// that lie in the frame for its launch rows [y0, y1), so a tile has to draw exactly the target rows [j0, j1) those positions address: iy is
+// monotonic in gy and, Hs <= H, moves by at most one row per frame row — the range has no gap.  The plan calls rfx_device.h rfx_frag_v /
+// rfx_nearest_idx themselves (declared for the host too); it is a pure function of its arguments, exported as rfx_internal_scaled_rows and held
+// against a brute force over gy under both vUv models (tests/test_resolution_scale_rows_cpu.py).  Everything that addresses a scaled tile's
+// target — K1's launch, K2's argument block, the hit mask, the trace -> shade hand-over plane — takes (j0, j1) from here.
+struct rfx_scaled_rows_plan { int j0, j1; };
+// frame_uv: the planes of the W x H frame (rfx_uv_planes); Hs: rows of the target
+inline rfx_scaled_rows_plan rfx_scaled_rows(const UvPlanes &frame_uv, int Hs, int y0, int y1, int apron) {
+    int lo = y0 - apron, hi = y1 - 1 + apron;
+    if (lo < 0) lo = 0;
+    if (hi > frame_uv.H - 1) hi = frame_uv.H - 1;
+    rfx_scaled_rows_plan t = {0, 0};
+    if (hi < lo) return t;
+    t.j0 = rfx_nearest_idx(rfx_frag_v(frame_uv, lo), (float)Hs, Hs);
+    t.j1 = rfx_nearest_idx(rfx_frag_v(frame_uv, hi), (float)Hs, Hs) + 1;
     return t;
 }
 

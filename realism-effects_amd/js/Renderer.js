@@ -80,6 +80,12 @@ class Renderer {
 		return addon.heldRows(this._h, tex)
 	}
 
+	// [row0, rows] of the K1 target TEX.SSGI holds after a draw at `resolutionScale` (rfx_ssgi_target_rows): the whole (W*s) x (H*s) target
+	// on a whole-frame context, the rows K2's staging of the tile addresses on a row tile; stored from the start of the slot, pitch W*s
+	ssgiTargetRows(resolutionScale) {
+		return addon.ssgiTargetRows(this._h, resolutionScale === undefined ? 1 : resolutionScale)
+	}
+
 	// rows [row0, row0+rows) in FRAME rows; `array` holds exactly those rows
 	upload(tex, array, row0, rows) {
 		const held = this.heldRows(tex)

@@ -145,7 +145,7 @@ if (opt.envCube) {
 const camera = Object.assign({}, first.camera)
 let renderer
 if (tiled) {
-	// halo: the K3 tap footprint and the largest vertical motion of the sequence (rfx_amd/tiling.py required_halo)
+	// halo: the K3 tap footprint, the largest vertical motion of the sequence and K1's source rows at --resolutionScale (rfx_amd/tiling.py required_halo)
 	let vmax = 0
 	for (const d of dumps) {
 		const f = d === dumps[0] ? first : rfx.readDump(d)
@@ -153,7 +153,7 @@ if (tiled) {
 		const v = new Float32Array(f.velocity.buffer, f.velocity.byteOffset, f.velocity.length)
 		for (let i = 1; i < v.length; i += 4) if (Math.abs(v[i]) > vmax) vmax = Math.abs(v[i])
 	}
-	const halo = rfx.requiredHalo(opt.radius === undefined ? 3 : opt.radius, vmax, first.height, first.width)
+	const halo = rfx.requiredHalo(opt.radius === undefined ? 3 : opt.radius, vmax, first.height, first.width, opt.resolutionScale)
 	const waitFor = (file, what) => {
 		const t0 = Date.now()
 		while (!fs.existsSync(file)) {
@@ -263,9 +263,25 @@ renderer.sync()
 fs.mkdirSync(out, { recursive: true })
 const T = rfx.TEX
 effect.mainImage(renderer) // the effect's own fragment -> final.bin
+// --resolutionScale S < 1: ssgi.bin is the (W*S) x (H*S) target K1 drew, nothing else of the slot.  A tile holds the target rows
+// ssgiTargetRows names from the start of its slot (include/rfx.h rfx_ssgi_target_rows) and contributes the ones whose nearest full-resolution
+// row, floor((j + 0.5) * H / (H*S)), is one of its own: every target row exactly once, in rank order
+const scale = opt.resolutionScale === undefined ? 1 : Number(opt.resolutionScale)
+function scaledTarget() {
+	const ws = Math.round(first.width * scale), hs = Math.round(first.height * scale)
+	const held = (renderer.inner || renderer).ssgiTargetRows(scale)
+	const y0 = tiled ? renderer.tileY0 : 0, y1 = tiled ? renderer.tileY0 + renderer.tileRows : first.height
+	const owner = j => Math.min(first.height - 1, Math.floor(((j + 0.5) * first.height) / hs))
+	let lo = 0
+	while (lo < hs && owner(lo) < y0) lo++
+	let hi = lo
+	while (hi < hs && owner(hi) < y1) hi++
+	if (hi > lo && (lo < held[0] || hi > held[0] + held[1])) throw new Error("target rows [" + lo + ", " + hi + ") are not all among the rows this tile drew")
+	return renderer.download(T.SSGI).subarray((lo - held[0]) * ws * 4, (hi - held[0]) * ws * 4)
+}
 for (const [name, tex] of [["final", T.FINAL], ["compose", T.COMPOSE], ["denoise_b0", T.DENOISE_B0], ["denoise_b1", T.DENOISE_B1], ["temporal0", T.TEMPORAL0], ["ssgi", T.SSGI]]) {
 	// a tile writes its own rows; the parent stitches them
-	const a = tiled ? renderer.download(tex, renderer.tileY0, renderer.tileRows) : renderer.download(tex)
+	const a = tex === T.SSGI && scale !== 1 ? scaledTarget() : tiled ? renderer.download(tex, renderer.tileY0, renderer.tileRows) : renderer.download(tex)
 	fs.writeFileSync(path.join(out, name + (tiled ? ".rank" + tiled.rank : "") + ".bin"), Buffer.from(a.buffer, a.byteOffset, a.byteLength))
 }
 if (mb) writeMotionBlur(mb)

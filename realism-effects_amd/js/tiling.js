@@ -23,11 +23,15 @@ function splitRows(height, nranks, rank) {
 }
 
 // rows of halo that make the tiled result exact (rfx_amd/tiling.py required_halo)
-function requiredHalo(radius, maxAbsVelocityY, frameHeight, frameWidth) {
+// resolutionScale s < 1: K1 fetches the G-buffer at the NEAREST frame row of a target row's vUv, within ceil(1 / (2 s)) rows of a frame row
+// that maps to it: 2 + ceil(1 / (2 s)) rows (include/rfx.h rfx_ssgi_target_rows)
+function requiredHalo(radius, maxAbsVelocityY, frameHeight, frameWidth, resolutionScale) {
 	const aspectRows = frameWidth ? Math.max(1, frameHeight / frameWidth) : 1
 	const k3 = Math.ceil(radius * aspectRows) + 2
 	const k2 = Math.ceil(Math.abs(maxAbsVelocityY) * frameHeight) + 4
-	return Math.max(k3, k2, 2)
+	const s = resolutionScale === undefined ? 1 : Number(resolutionScale)
+	const k1 = s === 1 ? 2 : 2 + Math.ceil(1 / (2 * s))
+	return Math.max(k3, k2, k1)
 }
 
 class TiledRenderer {
@@ -200,6 +204,10 @@ class TiledRenderer {
 		} finally {
 			this.inner.setRowWindow(0, 0)
 		}
+	}
+	// the rows of the K1 target this tile holds at a resolutionScale (Renderer.ssgiTargetRows)
+	ssgiTargetRows(resolutionScale) {
+		return this.inner.ssgiTargetRows(resolutionScale)
 	}
 	download(tex, row0, rows) {
 		this.commWait()

@@ -166,6 +166,26 @@ static napi_value n_held_rows(napi_env env, napi_callback_info info) {
     return arr;
 }
 
+/* ssgiTargetRows(ctx, resolutionScale) -> [row0, rows]: rfx_ssgi_target_rows */
+static napi_value n_ssgi_target_rows(napi_env env, napi_callback_info info) {
+    napi_value a[2], arr, e;
+    double scale = 1.0;
+    if (!get_args(env, info, 2, a)) return NULL;
+    rfx_ctx *c = get_ctx(env, a[0]);
+    if (!c) return NULL;
+    if (napi_get_value_double(env, a[1], &scale) != napi_ok) {
+        napi_throw_type_error(env, NULL, "ssgiTargetRows: resolutionScale must be a number");
+        return NULL;
+    }
+    int r0 = 0, n = 0;
+    int rc = rfx_ssgi_target_rows(c, (float)scale, &r0, &n);
+    if (rc) return throw_rfx(env, c, "rfx_ssgi_target_rows", rc);
+    NAPI_CALL(env, napi_create_array_with_length(env, 2, &arr));
+    napi_create_int32(env, r0, &e); napi_set_element(env, arr, 0, e);
+    napi_create_int32(env, n, &e); napi_set_element(env, arr, 1, e);
+    return arr;
+}
+
 /* upload(ctx, tex, typedArray, row0, rows) / download(ctx, tex, typedArray, row0, rows) */
 static napi_value xfer(napi_env env, napi_callback_info info, int up) {
     napi_value a[5];
@@ -871,7 +891,7 @@ static napi_value n_profile_read(napi_env env, napi_callback_info info) {
 
 static napi_value init(napi_env env, napi_value exports) {
     static const struct { const char *name; napi_callback fn; } fns[] = {
-        {"abiVersion", n_abi_version}, {"create", n_create}, {"heldRows", n_held_rows}, {"upload", n_upload}, {"download", n_download},
+        {"abiVersion", n_abi_version}, {"create", n_create}, {"heldRows", n_held_rows}, {"ssgiTargetRows", n_ssgi_target_rows}, {"upload", n_upload}, {"download", n_download},
         {"clear", n_clear}, {"setEnvironment", n_set_environment}, {"setEnvironmentImportance", n_set_environment_importance}, {"packGBuffer", n_pack_gbuffer}, {"packVelocity", n_pack_velocity}, {"ssgiMarch", n_ssgi}, {"ssgiTrace", n_ssgi_trace}, {"ssgiShade", n_ssgi_shade}, {"temporalReproject", n_temporal}, {"copyFramebuffer", n_copy_framebuffer}, {"poissonDenoise", n_denoise}, {"compose", n_compose}, {"finalCompose", n_final}, {"motionBlur", n_motion_blur},
         {"motionBlurStage", n_motion_blur_stage}, {"motionBlurReachMask", n_motion_blur_reach_mask}, {"motionBlurGather", n_motion_blur_gather},
         {"sync", n_sync}, {"setRowWindow", n_set_row_window}, {"setUvModel", n_set_uv_model}, {"cubeToEquirect", n_cube_to_equirect}, {"haloViolations", n_halo_violations}, {"timeBegin", n_time_begin}, {"timeEnd", n_time_end}, {"profile", n_profile}, {"profileRead", n_profile_read},

@@ -108,7 +108,7 @@ EXPORTS = [
     "rfx_abi_version", "rfx_create", "rfx_destroy", "rfx_last_error", "rfx_get_geometry", "rfx_set_stream", "rfx_tex_texel_bytes", "rfx_tex_held_rows",
     "rfx_upload", "rfx_download", "rfx_clear", "rfx_tex_device_ptr", "rfx_bind_external", "rfx_pack_gbuffer", "rfx_pack_velocity", "rfx_set_environment", "rfx_set_environment_importance", "rfx_download_environment", "rfx_cube_to_equirect", "rfx_set_row_window", "rfx_set_uv_model", "rfx_ssgi_march", "rfx_ssgi_trace", "rfx_ssgi_shade", "rfx_temporal_reproject",
     "rfx_copy_framebuffer", "rfx_poisson_denoise", "rfx_compose", "rfx_final_compose", "rfx_motion_blur", "rfx_sync", "rfx_halo_violations", "rfx_time_begin", "rfx_time_end", "rfx_profile", "rfx_profile_read",
-    "rfx_host_alloc", "rfx_host_free", "rfx_stage_upload", "rfx_stage_flip", "rfx_split_rows", "rfx_comm_unique_id", "rfx_comm_init", "rfx_comm_destroy", "rfx_halo_exchange", "rfx_allgather_history", "rfx_gather_history_rows", "rfx_peer_export", "rfx_peer_open", "rfx_peer_gather_history", "rfx_peer_close", "rfx_ssgi_hit_rows", "rfx_ssgi_hit_mask", "rfx_comm_wait",
+    "rfx_host_alloc", "rfx_host_free", "rfx_stage_upload", "rfx_stage_flip", "rfx_split_rows", "rfx_comm_unique_id", "rfx_comm_init", "rfx_comm_destroy", "rfx_halo_exchange", "rfx_allgather_history", "rfx_gather_history_rows", "rfx_peer_export", "rfx_peer_open", "rfx_peer_gather_history", "rfx_peer_close", "rfx_ssgi_hit_rows", "rfx_ssgi_hit_mask", "rfx_ssgi_target_rows", "rfx_comm_wait",
     "rfx_motion_blur_reach_mask", "rfx_motion_blur_stage", "rfx_motion_blur_gather",
 ]
 
@@ -200,6 +200,7 @@ def load_library(path: str | None = None) -> C.CDLL:
     lib.rfx_peer_gather_history.argtypes = [vp, i, C.POINTER(C.c_size_t)]
     lib.rfx_peer_close.argtypes = [vp]
     lib.rfx_ssgi_hit_rows.argtypes = [vp, C.POINTER(i), C.POINTER(i)]
+    lib.rfx_ssgi_target_rows.argtypes = [vp, C.c_float, C.POINTER(i), C.POINTER(i)]
     lib.rfx_ssgi_hit_mask.argtypes = [vp, C.POINTER(C.c_uint32), i]
     lib.rfx_comm_wait.argtypes = [vp]
     lib.rfx_motion_blur_reach_mask.argtypes = [vp, C.POINTER(MotionBlurParams), C.POINTER(C.c_uint32), i]

@@ -315,6 +315,20 @@ class Context:
         self._chk(self.lib.rfx_ssgi_hit_rows(self._h, C.byref(lo), C.byref(hi)), "rfx_ssgi_hit_rows")
         return int(lo.value), int(hi.value)
 
+    def ssgi_target_rows(self, resolution_scale: float = 1.0):
+        """rfx_ssgi_target_rows: (row0, rows) of the K1 target this context's TEX_SSGI holds after a draw at that resolutionScale — every row
+        of the (W*s) x (H*s) target on a whole-frame context, the rows K2's staging of the tile addresses on a row tile (include/rfx.h);
+        the held band at scale 1."""
+        r0, n = C.c_int(0), C.c_int(0)
+        self._chk(self.lib.rfx_ssgi_target_rows(self._h, float(resolution_scale), C.byref(r0), C.byref(n)), "rfx_ssgi_target_rows")
+        return int(r0.value), int(n.value)
+
+    def download_ssgi_target(self, resolution_scale: float):
+        """The target rows of a draw at resolutionScale != 1 as (row0, array of (rows, W*s, 4) uint32): the first rows * W*s texels of TEX_SSGI."""
+        r0, n = self.ssgi_target_rows(resolution_scale)
+        ws = int(np.float32(self.W) * np.float32(resolution_scale))  # (float)W * s, as the library forms it
+        return r0, np.ascontiguousarray(self.download(abi.TEX_SSGI)).reshape(-1)[:n * ws * 4].reshape(n, ws, 4).copy()
+
     def ssgi_hit_mask(self) -> np.ndarray:
         """rfx_ssgi_hit_mask: after ssgi_trace, one uint32 per frame row — bit b set when the shade reads a history texel of that row in column
         block b (32 blocks across the frame); 0 = the row is not read."""

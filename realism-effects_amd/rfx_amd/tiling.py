@@ -29,7 +29,8 @@ rows above and below and three exchange steps keep them current:
 
 K1 needs no exchange: it recomputes the +-2 rows K2's neighbourhood clamp reads, from the
 read-only dump planes every rank holds for its band, and reads depth / last frame's composed GI
-whole-frame.  The tiled result is bit-identical to the single-GPU result as long as the halo
+whole-frame.  With resolutionScale < 1 the same holds for the rows of the smaller target those
++-2 rows map to (rfx_ssgi_target_rows): the effect's params carry the scale, nothing here changes.  The tiled result is bit-identical to the single-GPU result as long as the halo
 covers the gather footprints: `required_halo()`.
 
 The exchanger is written against torch tensors so the same code runs over RCCL on device
@@ -58,17 +59,23 @@ def split_rows(height: int, world: int):
     return list(zip(starts, rows))
 
 
-def required_halo(radius: float, max_abs_velocity_y: float, frame_height: int, frame_width: int | None = None) -> int:
+def required_halo(radius: float, max_abs_velocity_y: float, frame_height: int, frame_width: int | None = None, resolution_scale: float = 1.0) -> int:
     """Rows of halo that make the tiled result exact:
        K3: the reference rotates the Poisson offsets in UV space (`rm * (offset / resolution)`,
            poisson_denoise.frag:183-189), so the tap footprint is radius*max(1, H/W) ROWS high
            (and radius*max(1, W/H) columns wide), +1 for the bilinear footprint, +1 for rounding
        K2: history bicubic at vUv - velocity: |v_y|*H rows + 2 texels of Catmull-Rom + 1 bilinear;
-           K1 output neighbourhood +-2 rows (recomputed locally)."""
+           K1 output neighbourhood +-2 rows (recomputed locally)
+       K1 at resolutionScale s < 1: the tile draws the target rows those +-2 rows map to, and a target row's fragment fetches the G-buffer
+           and the direct light at the NEAREST frame row of its own vUv, which lies within ceil(1 / (2 s)) rows of a frame row that maps to
+           it (include/rfx.h rfx_ssgi_target_rows): 2 + ceil(1 / (2 s)) rows.  Held against a brute force under both vUv models
+           (tests/test_resolution_scale_rows_cpu.py)."""
     aspect_rows = max(1.0, frame_height / frame_width) if frame_width else 1.0
     k3 = int(math.ceil(radius * aspect_rows)) + 2
     k2 = int(math.ceil(abs(max_abs_velocity_y) * frame_height)) + 4
-    return max(k3, k2, 2)
+    s = float(resolution_scale)
+    k1 = 2 if s == 1.0 else 2 + int(math.ceil(1.0 / (2.0 * s)))
+    return max(k3, k2, k1)
 
 
 def halo_plan(height: int, world: int, rank: int, halo: int):
