@@ -224,6 +224,26 @@ typedef struct rfx_motion_blur_params {
     int32_t halfStoreRTZ;   /* rounding of that store: 1 truncate (llvmpipe), 0 nearest-even */
 } rfx_motion_blur_params;
 
+/* K7 — streamed frame export: the importer run in reverse.  The context's tile rows [tile_y0, tile_y0 + tile_rows) of an RGBA32F slot
+ * are encoded ON THE DEVICE into a tightly packed interleaved stream — frame row order, row 0 = bottom, no pitch padding, no flip: the order
+ * rfx_download uses — and only the encoded bytes cross PCIe: 3 B/px for a display image instead of the 16 B/px of rfx_download.
+ *   RFX_EXPORT_F32      4 B per element: the source's bits, unchanged
+ *   RFX_EXPORT_F16      2 B: IEEE binary16, round to nearest even; overflow -> +-inf, NaN stays NaN, subnormal halfs are produced
+ *   RFX_EXPORT_U8_SRGB  1 B: the display encoding of rfx_amd/imageio.py tonemap(linear, operator, exposure) (js/imageio.js mirrors it), in fp32:
+ *                       NaN -> 0, +inf -> 65504, -inf -> 0, clip to [0, 65504], times `exposure`; operator 0 "linear" / 1 "aces" (three's
+ *                       ACESFilmicToneMapping: / 0.6, input matrix, rational fit, output matrix); NaN -> 0, inf -> 1, clip to [0, 1]; the sRGB
+ *                       transfer function (branch at 0.0031308); (s * 255 + 0.5) truncated.  A fourth channel is alpha: NaN -> 0, clip to
+ *                       [0, 1], (a * 255 + 0.5) truncated — no operator, no transfer function.
+ * rfx_set_row_window does not apply: an export always covers the tile rows. */
+enum { RFX_EXPORT_F32 = 0, RFX_EXPORT_F16 = 1, RFX_EXPORT_U8_SRGB = 2 };
+typedef struct rfx_export_params {
+    int32_t source;    /* RFX_TEX_FINAL, RFX_TEX_MOTION_BLUR, RFX_TEX_COMPOSE, RFX_TEX_TEMPORAL0, RFX_TEX_DIRECT_LIGHT or RFX_TEX_EFFECT_INPUT */
+    int32_t format;    /* RFX_EXPORT_F32 / _F16 / _U8_SRGB */
+    int32_t channels;  /* 3 (.rgb) or 4 (.rgba) */
+    int32_t tonemap;   /* U8_SRGB only: 0 linear, 1 ACES filmic; must be 0 otherwise */
+    float exposure;    /* U8_SRGB only: finite, >= 0.  Otherwise not given: 0 (a zeroed struct) or 1 (the hosts' default) */
+} rfx_export_params;
+
 typedef struct rfx_ctx rfx_ctx;
 
 /* ---- lifetime (Pass ctor / setSize / dispose) */
@@ -396,6 +416,29 @@ int rfx_motion_blur_stage(rfx_ctx *, const rfx_motion_blur_params *);
  * rfx_gather_history_rows. */
 int rfx_motion_blur_gather(rfx_ctx *, const rfx_motion_blur_params *, void *ncclComm, size_t *bytes_received);
 
+/* ---- streamed frame export (K7, rfx_export_params above): per-frame output of an offline run without a full-width blocking read-back.
+ * Added to ABI 21 without a new version number, like rfx_ssgi_target_rows: four more entry points and one more profile kind, nothing an existing
+ * call does differently; a host checks for the symbol.  (RFX_PROF_COUNT grew by one: a caller of rfx_profile_read sizes its arrays with the
+ * RFX_PROF_COUNT of the header its library was built from.)
+ * rfx_export_bytes: tile_rows * W * channels * element bytes; 0 on bad params.  `bytes` of the other calls must equal it.
+ * rfx_stage_export enqueues the encode on the DRAW stream — ordered after every draw enqueued so far — into one of two internal device staging
+ * buffers (not texture slots, not checkpoint state: allocated on first use, grown when a later call needs more, freed by rfx_destroy), then the
+ * device-to-host copy on the context's DOWNLOAD stream (its own, so both PCIe directions run at once with rfx_stage_upload), which waits for an
+ * event recorded after the kernel; it returns without waiting for either.  Tickets count up from 1 per context.
+ *     draws(0); stage_export(A) -> 1;   loop: draws(n+1); stage_export(n+1 into the other buffer); export_wait(n); write frame n
+ * Two orders hold: on the device, the encode of export n+2 waits for the copy of export n (they share a staging buffer); on the host,
+ * rfx_stage_flip's rule — the call returns only once export n-2 has completed, so a host with two alternating pinned buffers never runs more
+ * than two exports ahead.  `host` must stay valid until rfx_export_wait(ticket) returns.  Pinned memory (rfx_host_alloc) makes the copy
+ * asynchronous; a pageable buffer is accepted and simply does not overlap.
+ * rfx_export_wait returns when that export's bytes are in `host`: at once for a ticket that has retired, RFX_EINVAL for one never issued.
+ * rfx_export = rfx_stage_export + rfx_export_wait (it takes a ticket of its own).  rfx_sync and rfx_destroy drain the download stream.
+ * RFX_EINVAL: a source that is not one of the listed RGBA32F slots, a bad format / channel count / operator, an operator or exposure given with
+ * a non-U8 format, bytes != rfx_export_bytes.  RFX_ESTATE: the source was never drawn, uploaded or bound (rfx_motion_blur's rule). */
+size_t rfx_export_bytes(const rfx_ctx *, const rfx_export_params *);
+int rfx_export(rfx_ctx *, const rfx_export_params *, void *host, size_t bytes);
+int rfx_stage_export(rfx_ctx *, const rfx_export_params *, void *host, size_t bytes, int *ticket);
+int rfx_export_wait(rfx_ctx *, int ticket);
+
 int rfx_sync(rfx_ctx *);
 
 /* ---- streaming dumps: host buffers that cross PCIe every frame (an offline run over a dumped sequence).  rfx_upload is synchronous
@@ -491,6 +534,7 @@ int rfx_time_end(rfx_ctx *, float *elapsed_ms);
 enum { RFX_PROF_K1_PREPASS = 0, RFX_PROF_K1_MARCH, RFX_PROF_K2, RFX_PROF_K3_PASS0, RFX_PROF_K3_PASSN, RFX_PROF_K4, RFX_PROF_K5,
        RFX_PROF_K6, /* ABI 20: rfx_motion_blur */
        RFX_PROF_K6_REACH, /* ABI 21: the reach reduction of rfx_motion_blur_reach_mask / rfx_motion_blur_gather */
+       RFX_PROF_K7, /* the encode of rfx_export / rfx_stage_export */
        RFX_PROF_COUNT };
 int rfx_profile(rfx_ctx *, int enable);
 int rfx_profile_read(rfx_ctx *, float *ms_sum, int *launches);

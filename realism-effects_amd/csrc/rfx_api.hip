@@ -114,6 +114,13 @@ void rfx_destroy(rfx_ctx *c) {
     rfx_comm_release(c);
     // a staged copy may still be writing a back buffer: drain the upload stream before any buffer goes
     if (c->upload_stream) { hipStreamSynchronize(c->upload_stream); hipStreamDestroy(c->upload_stream); }
+    // ... and a staged export may still be copying out of a staging buffer
+    if (c->download_stream) { hipStreamSynchronize(c->download_stream); hipStreamDestroy(c->download_stream); }
+    for (int b = 0; b < 2; b++) {
+        if (c->export_buf[b]) hipFree(c->export_buf[b]);
+        if (c->ev_export_encoded[b]) hipEventDestroy(c->ev_export_encoded[b]);
+        if (c->ev_export_copied[b]) hipEventDestroy(c->ev_export_copied[b]);
+    }
     for (int i = 0; i < RFX_TEX_COUNT; i++) {
         if (c->slots[i].owned && c->slots[i].ptr) hipFree(c->slots[i].ptr);
         if (c->slots[i].back) hipFree(c->slots[i].back);
@@ -787,6 +794,9 @@ int rfx_internal_scaled_rows(int W, int H, int Hs, int uv_model, int y0, int y1,
     *j0 = t.j0; *j1 = t.j1;
     return RFX_OK;
 }
+int rfx_internal_export_plan(int pixels, int format, int channels, struct rfx_export_plan *out) {
+    return rfx_export_plan_for(pixels, format, channels, out) ? RFX_OK : RFX_EINVAL;
+}
 int rfx_internal_k3_tile(int W, int H, float radius, int inputIsTemporal, int textureCount, struct rfx_k3_tile_plan *out) {
     *out = rfx_k3_tile((float)W, (float)H, radius, inputIsTemporal != 0, textureCount);
     return RFX_OK;
@@ -1166,10 +1176,117 @@ int rfx_motion_blur_stage(rfx_ctx *c, const rfx_motion_blur_params *p) {
     return RFX_OK;
 }
 
+// ---- K7: streamed frame export (include/rfx.h "streamed frame export"; the kernel is in k0_import.hip)
+// the parameters alone: what rfx_export_bytes can judge without a context's state.  Returns nullptr when they are good.
+static const char *export_params_error(const rfx_export_params *p) {
+    const int s = p->source;
+    if (s != RFX_TEX_FINAL && s != RFX_TEX_MOTION_BLUR && s != RFX_TEX_COMPOSE && s != RFX_TEX_TEMPORAL0 && s != RFX_TEX_DIRECT_LIGHT && s != RFX_TEX_EFFECT_INPUT)
+        return "source must be FINAL, MOTION_BLUR, COMPOSE, TEMPORAL0, DIRECT_LIGHT or EFFECT_INPUT";
+    if (p->format != RFX_EXPORT_F32 && p->format != RFX_EXPORT_F16 && p->format != RFX_EXPORT_U8_SRGB) return "format must be RFX_EXPORT_F32, _F16 or _U8_SRGB";
+    if (p->channels != 3 && p->channels != 4) return "channels must be 3 or 4";
+    if (p->format == RFX_EXPORT_U8_SRGB) {
+        if (p->tonemap != 0 && p->tonemap != 1) return "tonemap must be 0 (linear) or 1 (ACES filmic)";
+        if (!(p->exposure >= 0.0f) || !(p->exposure <= 3.402823466e38f)) return "exposure must be finite and >= 0";
+    } else {
+        if (p->tonemap != 0) return "tonemap belongs to RFX_EXPORT_U8_SRGB: must be 0 with another format";
+        if (p->exposure != 0.0f && p->exposure != 1.0f) return "exposure belongs to RFX_EXPORT_U8_SRGB: must be 0 or 1 with another format";
+    }
+    return nullptr;
+}
+static int export_fail(rfx_ctx *c, int code, const char *fn, const char *what) {
+    char buf[384];
+    snprintf(buf, sizeof buf, "%s: %s", fn, what);
+    return fail(c, code, buf);
+}
+
+size_t rfx_export_bytes(const rfx_ctx *c, const rfx_export_params *p) {
+    rfx_export_plan t;
+    if (!c || !p || export_params_error(p) || !rfx_export_plan_for(c->tile_rows * c->W, p->format, p->channels, &t)) return 0;
+    return (size_t)t.bytes;
+}
+
+static int export_enqueue(rfx_ctx *c, const rfx_export_params *p, void *host, size_t bytes, int *ticket, const char *fn) {
+    if (!c || !p || !host) return RFX_EINVAL;
+    RFX_ENTER(c);
+    if (const char *bad = export_params_error(p)) return export_fail(c, RFX_EINVAL, fn, bad);
+    rfx_export_plan t;
+    if (!rfx_export_plan_for(c->tile_rows * c->W, p->format, p->channels, &t)) return export_fail(c, RFX_EINVAL, fn, "bad format or channel count");
+    if (bytes != (size_t)t.bytes) return export_fail(c, RFX_EINVAL, fn, "bytes != rfx_export_bytes(ctx, params)");
+    // rfx_motion_blur's rule: a host-filled plane must have been uploaded (staged, bound); a slot a draw writes must at least exist
+    const Slot &s = c->slots[p->source];
+    const bool host_filled = p->source == RFX_TEX_DIRECT_LIGHT || p->source == RFX_TEX_EFFECT_INPUT;
+    if (host_filled ? !s.uploaded : !s.ptr) return export_fail(c, RFX_ESTATE, fn, "the source slot holds nothing yet (upload it or draw into it first)");
+    if (!c->download_stream) {
+        hipError_t e = hipStreamCreateWithFlags(&c->download_stream, hipStreamNonBlocking);
+        for (int b = 0; b < 2; b++) {
+            if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_export_encoded[b], hipEventDisableTiming);
+            if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_export_copied[b], hipEventDisableTiming);
+        }
+        if (e != hipSuccess) return fail(c, RFX_EDEVICE, "rfx_stage_export: stream/event creation", e);
+    }
+    const unsigned int n = c->exports;
+    const int b = (int)(n & 1u);
+    if (n >= 2) {
+        // host-side back pressure (rfx_stage_flip's rule): export n - 2 — the last user of this staging buffer and, with two alternating host
+        // buffers, of `host` — has completed before this call returns
+        HIPCHK(c, hipEventSynchronize(c->ev_export_copied[b]));
+        // ... and the order on the device: this encode overwrites the buffer that copy read
+        HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_export_copied[b], 0));
+    }
+    if (c->export_cap[b] < bytes) {  // (idle: its last copy has completed)
+        if (c->export_buf[b]) hipFree(c->export_buf[b]);
+        c->export_buf[b] = nullptr;
+        c->export_cap[b] = 0;
+        hipError_t e = hipMalloc(&c->export_buf[b], bytes);
+        if (e != hipSuccess) return fail(c, RFX_ENOMEM, "rfx_stage_export: hipMalloc(staging buffer)", e);
+        c->export_cap[b] = bytes;
+    }
+    K7Args A;
+    A.src = (const uint4 *)s.ptr + (size_t)(c->tile_y0 - s.row0) * c->W;
+    A.dst = c->export_buf[b];
+    A.groups = t.groups;
+    A.tail_start = t.tail_start;
+    A.tail_pixels = t.tail_pixels;
+    A.exposure = p->exposure;
+    {
+        ProfScope prof(c, RFX_PROF_K7, c->stream);
+        HIPCHK(c, rfx_launch_k7(A, t.blocks, p->format, p->channels, p->tonemap, c->stream));
+    }
+    HIPCHK(c, hipEventRecord(c->ev_export_encoded[b], c->stream));
+    HIPCHK(c, hipStreamWaitEvent(c->download_stream, c->ev_export_encoded[b], 0));
+    HIPCHK(c, hipMemcpyAsync(host, c->export_buf[b], bytes, hipMemcpyDeviceToHost, c->download_stream));
+    HIPCHK(c, hipEventRecord(c->ev_export_copied[b], c->download_stream));
+    c->exports = n + 1;
+    if (ticket) *ticket = (int)(n + 1);
+    return RFX_OK;
+}
+
+int rfx_stage_export(rfx_ctx *c, const rfx_export_params *p, void *host, size_t bytes, int *ticket) {
+    if (!ticket) return RFX_EINVAL;
+    return export_enqueue(c, p, host, bytes, ticket, "rfx_stage_export");
+}
+
+int rfx_export_wait(rfx_ctx *c, int ticket) {
+    if (!c) return RFX_EINVAL;
+    RFX_ENTER(c);
+    if (ticket < 1 || (unsigned int)ticket > c->exports) return fail(c, RFX_EINVAL, "rfx_export_wait: no such ticket");
+    // every export but the last two retired when a later rfx_stage_export returned (its back pressure)
+    if ((unsigned int)ticket + 2 <= c->exports) return RFX_OK;
+    HIPCHK(c, hipEventSynchronize(c->ev_export_copied[(ticket - 1) & 1]));
+    return RFX_OK;
+}
+
+int rfx_export(rfx_ctx *c, const rfx_export_params *p, void *host, size_t bytes) {
+    int ticket = 0;
+    const int rc = export_enqueue(c, p, host, bytes, &ticket, "rfx_export");
+    return rc ? rc : rfx_export_wait(c, ticket);
+}
+
 int rfx_sync(rfx_ctx *c) {
     if (!c) return RFX_EINVAL;
     RFX_ENTER(c);
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->download_stream) HIPCHK(c, hipStreamSynchronize(c->download_stream));  // staged exports: their bytes are in the host buffers
     return RFX_OK;
 }
 

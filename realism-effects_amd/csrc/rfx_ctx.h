@@ -76,6 +76,13 @@ struct rfx_ctx {
     hipEvent_t ev_staged = nullptr, ev_frame_done = nullptr;
     hipEvent_t ev_batch[2] = {nullptr, nullptr};  // the copies published by the last two flips (recorded on upload_stream)
     unsigned int flips = 0;
+    // streamed export (rfx_stage_export): a fourth stream for the device-to-host copies, two device staging buffers the encodes alternate
+    // between (export n uses buffer n & 1), and per buffer the event behind its last encode (draw stream) and its last copy (download stream)
+    hipStream_t download_stream = nullptr;
+    void *export_buf[2] = {nullptr, nullptr};
+    size_t export_cap[2] = {0, 0};
+    hipEvent_t ev_export_encoded[2] = {nullptr, nullptr}, ev_export_copied[2] = {nullptr, nullptr};
+    unsigned int exports = 0;  // tickets issued so far (ticket t = export t - 1)
     // the peer-load history gather (rfx_peer.hip): this rank's flag block (fine-grained), the device table of every rank's plane and flag block
     // ([0, n) planes, [n, 2 n) flag blocks), what the last call's kernels reported ([0] status bits, [1] texels pulled), the mappings to close
     unsigned long long *peer_flags = nullptr;
@@ -108,6 +115,7 @@ extern "C" int rfx_internal_blur_reach_enqueue(rfx_ctx *c, const rfx_motion_blur
 // ... and, for the CPU tests: the launch plans of rfx_launch.h as the library computes them (K1's table layout, K3's tile geometry)
 extern "C" int rfx_internal_k1_table(int W, int H, struct rfx_k1_table_plan *out);
 extern "C" int rfx_internal_scaled_rows(int W, int H, int Hs, int uv_model, int y0, int y1, int apron, int *j0, int *j1);
+extern "C" int rfx_internal_export_plan(int pixels, int format, int channels, struct rfx_export_plan *out);
 extern "C" int rfx_internal_k3_tile(int W, int H, float radius, int inputIsTemporal, int textureCount, struct rfx_k3_tile_plan *out);
 
 extern thread_local std::string g_create_err;

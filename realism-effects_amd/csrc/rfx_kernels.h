@@ -92,6 +92,17 @@ hipError_t rfx_launch_pack_velocity(int W, int rows, const float *velocity, cons
 // CubeToEquirectEnvPass (k0_import.hip): six S x S RGBA32F faces -> a W x H RGBA32F equirectangular image
 hipError_t rfx_launch_cube_to_equirect(float4 *chain, int size, int levels, float4 *out, int W, int H, const UvPlanes &uv, hipStream_t);
 
+// K7 export (k0_import.hip): `pixels` RGBA32F texels from `src` -> the packed stream at `dst`, laid out by rfx_launch.h rfx_export_plan_for
+struct K7Args {
+    const uint4 *src;  // first exported texel
+    void *dst;         // staging buffer (at least 16-byte aligned)
+    int groups;        // lanes [0, groups) own four pixels each
+    int tail_start, tail_pixels;  // lane `groups` writes these with element-wide stores
+    float exposure;
+};
+// format / channels / tonemap select the specialisation (hipErrorInvalidValue for a combination the export does not have); `blocks` from the plan
+hipError_t rfx_launch_k7(const K7Args &, int blocks, int format, int channels, int tonemap, hipStream_t);
+
 struct K5Args {
     FrameDims dims;
     int y0, y1;

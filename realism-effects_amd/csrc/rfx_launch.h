@@ -1,7 +1,7 @@
 // rfx_launch.h — what a launch decides on the host before it launches: K1's table layout, a scaled tile's target rows, K3's tile geometry, the
 // "whole frame" test, the step from a run-time option to a template argument, and what is remembered per kernel and device.  Host code
 // (rfx_device.h comes in for UvPlanes and the two vUv expressions the kernels and the row plan share).  The plans are pure functions of their
-// arguments (no HIP call, no context): rfx_api.hip exports them as rfx_internal_k1_table / rfx_internal_k3_tile / rfx_internal_scaled_rows and
+// arguments (no HIP call, no context): rfx_api.hip exports them as rfx_internal_k1_table / rfx_internal_k3_tile / rfx_internal_scaled_rows / rfx_internal_export_plan and
 // the CPU tests call them as built (tests/test_k1_table_layout.py, tests/test_k3_tile_geometry.py, tests/test_resolution_scale_rows_cpu.py).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -116,6 +116,39 @@ inline rfx_k3_tile_plan rfx_k3_tile(float fW, float fH, float radius, bool tempo
     // at least two workgroups per CU (160 KiB LDS) keep the staging of one tile under the arithmetic of another (4K: three of either pass kind)
     t.tiled = radius >= 0.0f && t.pitch != 0 && t.lds_bytes <= (size_t)K3_LDS_MAX;
     return t;
+}
+
+// ---------------------------------------------------------------- K7: the export's flat stream
+// The exported rows are one flat run of `pixels` = tile_rows * W texels (source and destination are both contiguous: row ends need no case of
+// their own).  Lane t < groups owns the pixels [4 t, 4 t + 4): four 16-byte loads and group_bytes = 4 * pixel_bytes = 12, 16, 24, 32, 48 or 64
+// bytes stored at t * group_bytes — always whole dwords at a dword-aligned offset.  The pixels [tail_start, pixels), pixels mod 4 of them, are
+// written by ONE lane (t == groups) with element-wide stores.  A pure function of its arguments, exported as rfx_internal_export_plan and held
+// against a brute force over the output bytes (tests/test_export_cpu.py).
+constexpr int RFX_K7_BLOCK = 256;
+struct rfx_export_plan {
+    int pixels, groups, blocks;    // groups of four pixels; workgroups of RFX_K7_BLOCK lanes (the tail's lane included)
+    int tail_start, tail_pixels;   // pixels - pixels mod 4, pixels mod 4
+    int elem_bytes, pixel_bytes, group_bytes;
+    unsigned long long bytes;      // pixels * pixel_bytes: rfx_export_bytes
+};
+// false (and *out untouched) for a format or channel count the export does not have
+inline bool rfx_export_plan_for(int pixels, int format, int channels, rfx_export_plan *out) {
+    if (pixels <= 0 || (channels != 3 && channels != 4)) return false;
+    const int elem = format == RFX_EXPORT_F32 ? 4 : format == RFX_EXPORT_F16 ? 2 : format == RFX_EXPORT_U8_SRGB ? 1 : 0;
+    if (!elem) return false;
+    rfx_export_plan t;
+    t.pixels = pixels;
+    t.groups = pixels / 4;
+    t.tail_start = t.groups * 4;
+    t.tail_pixels = pixels - t.tail_start;
+    const int lanes = t.groups + (t.tail_pixels ? 1 : 0);
+    t.blocks = (lanes + RFX_K7_BLOCK - 1) / RFX_K7_BLOCK;
+    t.elem_bytes = elem;
+    t.pixel_bytes = elem * channels;
+    t.group_bytes = 4 * t.pixel_bytes;
+    t.bytes = (unsigned long long)pixels * (unsigned long long)t.pixel_bytes;
+    *out = t;
+    return true;
 }
 
 // ---------------------------------------------------------------- shared by the launchers

@@ -55,6 +55,14 @@ const FORMAT = {
 	19: [Float32Array, 4]
 }
 
+// rfx_export_params.format (include/rfx.h RFX_EXPORT_*): [value, TypedArray constructor of the exported elements]
+const EXPORT = { F32: 0, F16: 1, U8_SRGB: 2 }
+const EXPORT_ARRAY = { 0: Float32Array, 1: Uint16Array, 2: Uint8Array }
+const EXPORT_TONEMAP = { linear: 0, aces: 1 }
+// rfx_profile_read's kinds (include/rfx.h RFX_PROF_*), the index of profileRead()'s arrays
+const PROF_KINDS = ["k1_prepass", "k1_ssgi_march", "k2_temporal_reproject", "k3_poisson_denoise_pass0", "k3_poisson_denoise_passN", "k4_compose", "k5_final_compose",
+	"k6_motion_blur", "k6_motion_blur_reach", "k7_export"]
+
 // 128x128 RGBA8 blue-noise table: decoded once from the reference's PNG asset, already flipY'd
 // (tools/make_blue_noise_table.py; src/utils/BlueNoiseUtils.js:9-15)
 function loadBlueNoiseTable() {
@@ -123,6 +131,39 @@ class Renderer {
 	}
 	stageFlip() {
 		addon.stageFlip(this._h)
+	}
+
+	// streamed frame export (rfx.h "streamed frame export"): the tile rows of `source`, encoded on the device.  params: { source, format: EXPORT.*
+	// or "f32" / "f16" / "u8_srgb", channels: 3 | 4, tonemap: "linear" | "aces" (u8_srgb only), exposure }
+	exportParams(params) {
+		const p = Object.assign({ channels: 3, tonemap: 0, exposure: 1 }, params)
+		if (typeof p.format === "string") p.format = EXPORT[p.format.toUpperCase()]
+		if (typeof p.tonemap === "string") p.tonemap = EXPORT_TONEMAP[p.tonemap]
+		if (p.format === undefined || p.tonemap === undefined) throw new RangeError("export: unknown format or tonemap")
+		return p
+	}
+	exportBytes(params) {
+		return addon.exportBytes(this._h, this.exportParams(params))
+	}
+	// -> Float32Array / Uint16Array (half bits) / Uint8Array of tileRows * width * channels elements, row 0 = bottom; blocks (rfx_export)
+	exportFrame(params, out) {
+		const p = this.exportParams(params)
+		if (!out) out = new (EXPORT_ARRAY[p.format] || Uint8Array)(Math.max(1, addon.exportBytes(this._h, p) / (EXPORT_ARRAY[p.format] || Uint8Array).BYTES_PER_ELEMENT))
+		addon.exportFrame(this._h, p, out)
+		return out
+	}
+	// enqueue the encode and the copy into `out` (a Renderer.hostAlloc array for an asynchronous copy) -> ticket; `out` is complete once
+	// exportWait(ticket) has returned.  Returns only when the export two tickets earlier has completed: alternate two buffers (rfx_stage_export)
+	stageExport(params, out) {
+		const ticket = addon.stageExport(this._h, this.exportParams(params), out)
+		if (!this._exports) this._exports = new Map()
+		this._exports.set(ticket, out) // the copy writes `out` until its ticket retires
+		for (const t of this._exports.keys()) if (t <= ticket - 2) this._exports.delete(t)
+		return ticket
+	}
+	exportWait(ticket) {
+		addon.exportWait(this._h, ticket)
+		if (this._exports) this._exports.delete(ticket)
 	}
 
 	download(tex, row0, rows) {
@@ -250,4 +291,4 @@ class Renderer {
 	}
 }
 
-module.exports = { Renderer, TEX, FORMAT, loadBlueNoiseTable, abiVersion: addon.abiVersion }
+module.exports = { Renderer, TEX, FORMAT, EXPORT, EXPORT_ARRAY, PROF_KINDS, loadBlueNoiseTable, abiVersion: addon.abiVersion, constants: addon.constants }

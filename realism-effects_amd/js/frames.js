@@ -1,0 +1,60 @@
+"use strict"
+// Per-frame output of an offline run (run_dump.js --framesOut): every frame leaves the device through the streamed export (rfx.h "streamed
+// frame export") — encoded by K7, copied on the download stream into one of two pinned buffers — and is written by the existing writers,
+// which take the device's bytes as they are.  Python twin: rfx_amd/frames.py.
+//   png -> RFX_EXPORT_U8_SRGB x 3 (tonemap / exposure)     exr -> RFX_EXPORT_F16 x 4     pfm -> RFX_EXPORT_F32 x 3
+// submit(source) is called once per frame AFTER the frame's draws are enqueued: it stages this frame's export, then waits for the PREVIOUS
+// frame's ticket — which has had this frame's draws to hide behind — and writes it.  At most two exports are in flight; finish() waits for
+// the last one.
+const path = require("path")
+const { Renderer, EXPORT, EXPORT_ARRAY } = require("./Renderer")
+const io = require("./imageio")
+
+const FRAME_FORMATS = { png: [EXPORT.U8_SRGB, 3], exr: [EXPORT.F16, 4], pfm: [EXPORT.F32, 3] }
+
+class FrameExporter {
+	// options: { format: "png" | "exr" | "pfm", tonemap: "aces" | "linear", exposure, hostAlloc, write }
+	constructor(renderer, dir, options) {
+		options = options || {}
+		this.renderer = renderer
+		this.dir = dir
+		this.format = options.format || "png"
+		const f = FRAME_FORMATS[this.format]
+		if (!f) throw new RangeError("framesFormat: \"png\", \"exr\" or \"pfm\"")
+		const tonemap = options.tonemap === undefined ? "aces" : options.tonemap
+		if (tonemap !== "aces" && tonemap !== "linear") throw new RangeError("tonemap: \"aces\" or \"linear\"")
+		this.params = { format: f[0], channels: f[1], tonemap: f[0] === EXPORT.U8_SRGB ? tonemap : 0, exposure: f[0] === EXPORT.U8_SRGB && options.exposure !== undefined ? options.exposure : 1 }
+		const n = renderer.width * renderer.tileRows * f[1]
+		const alloc = options.hostAlloc || Renderer.hostAlloc
+		this.buffers = [0, 1].map(() => alloc(EXPORT_ARRAY[f[0]], n))
+		this.write = options.write || ((index, data) => this.writeFrame(index, data))
+		this.count = 0
+		this.pending = null // { ticket, index, buffer }
+	}
+	writeFrame(index, data) {
+		const file = path.join(this.dir, "frame_" + String(index).padStart(5, "0") + "." + this.format)
+		const w = this.renderer.width, h = this.renderer.tileRows
+		if (this.format === "png") io.writePNG(file, data, w, h, 3)
+		else if (this.format === "exr") io.writeEXR(file, data, w, h, true)
+		else io.writePFM(file, data, w, h, 3)
+	}
+	submit(source) {
+		const index = this.count++
+		const buffer = this.buffers[index & 1]
+		const ticket = this.renderer.stageExport(Object.assign({ source }, this.params), buffer)
+		this.retire()
+		this.pending = { ticket, index, buffer }
+	}
+	retire() {
+		const p = this.pending
+		if (!p) return
+		this.pending = null
+		this.renderer.exportWait(p.ticket)
+		this.write(p.index, p.buffer)
+	}
+	finish() {
+		this.retire()
+	}
+}
+
+module.exports = { FrameExporter, FRAME_FORMATS }

@@ -73,11 +73,14 @@ function tonemap(rgba, width, height, operator, exposure) {
 	return out
 }
 
-// scene-linear RGBA32F -> single-part scanline OpenEXR, FLOAT channels A B G R, no compression
-function writeEXR(file, rgba, width, height) {
+// scene-linear RGBA32F -> single-part scanline OpenEXR, FLOAT channels A B G R, no compression.  half: `rgba` is a Uint16Array of binary16
+// BITS (the device's RFX_EXPORT_F16 stream as it is: no float round trip) and the channels are HALF — byte for byte what
+// rfx_amd/imageio.py write_exr(compression="none", half=True) writes for the same plane
+function writeEXR(file, rgba, width, height, half) {
+	const sz = half ? 2 : 4
 	const names = ["A", "B", "G", "R"], src = [3, 2, 1, 0]
 	const attr = (name, type, payload) => Buffer.concat([Buffer.from(name + "\0" + type + "\0", "ascii"), (() => { const b = Buffer.alloc(4); b.writeInt32LE(payload.length, 0); return b })(), payload])
-	const chlist = Buffer.concat(names.map(n => { const b = Buffer.alloc(n.length + 1 + 16); b.write(n, 0, "ascii"); b.writeInt32LE(2, n.length + 1); b.writeInt32LE(1, n.length + 9); b.writeInt32LE(1, n.length + 13); return b }).concat([Buffer.from([0])]))
+	const chlist = Buffer.concat(names.map(n => { const b = Buffer.alloc(n.length + 1 + 16); b.write(n, 0, "ascii"); b.writeInt32LE(half ? 1 : 2, n.length + 1); b.writeInt32LE(1, n.length + 9); b.writeInt32LE(1, n.length + 13); return b }).concat([Buffer.from([0])]))
 	const box = Buffer.alloc(16)
 	box.writeInt32LE(width - 1, 8)
 	box.writeInt32LE(height - 1, 12)
@@ -85,23 +88,29 @@ function writeEXR(file, rgba, width, height) {
 	const header = Buffer.concat([Buffer.from([0x76, 0x2f, 0x31, 0x01, 2, 0, 0, 0]), attr("channels", "chlist", chlist), attr("compression", "compression", Buffer.from([0])),
 		attr("dataWindow", "box2i", box), attr("displayWindow", "box2i", box), attr("lineOrder", "lineOrder", Buffer.from([0])), attr("pixelAspectRatio", "float", f32(1)),
 		attr("screenWindowCenter", "v2f", Buffer.concat([f32(0), f32(0)])), attr("screenWindowWidth", "float", f32(1)), Buffer.from([0])])
-	const lineBytes = 8 + 16 * width
+	const lineBytes = 8 + 4 * sz * width
 	const table = Buffer.alloc(8 * height), body = Buffer.alloc(lineBytes * height)
 	for (let y = 0; y < height; y++) {
 		const off = header.length + table.length + y * lineBytes
 		table.writeUInt32LE(off >>> 0, 8 * y)
 		table.writeUInt32LE(Math.floor(off / 4294967296), 8 * y + 4)
 		body.writeInt32LE(y, y * lineBytes)
-		body.writeInt32LE(16 * width, y * lineBytes + 4)
+		body.writeInt32LE(4 * sz * width, y * lineBytes + 4)
 		const row = height - 1 - y // EXR y = 0 is the top row
-		for (let c = 0; c < 4; c++) for (let x = 0; x < width; x++) body.writeFloatLE(rgba[4 * (row * width + x) + src[c]], y * lineBytes + 8 + 4 * (c * width + x))
+		if (half) for (let c = 0; c < 4; c++) for (let x = 0; x < width; x++) body.writeUInt16LE(rgba[4 * (row * width + x) + src[c]], y * lineBytes + 8 + 2 * (c * width + x))
+		else for (let c = 0; c < 4; c++) for (let x = 0; x < width; x++) body.writeFloatLE(rgba[4 * (row * width + x) + src[c]], y * lineBytes + 8 + 4 * (c * width + x))
 	}
 	fs.writeFileSync(file, Buffer.concat([header, table, body]))
 }
 
-function writePFM(file, rgba, width, height) {
-	const body = Buffer.alloc(12 * width * height)
-	for (let i = 0; i < width * height; i++) for (let c = 0; c < 3; c++) body.writeFloatLE(rgba[4 * i + c], 4 * (3 * i + c))
+// channels 3: `rgba` is already the file's body, tightly packed RGB float32 (the device's RFX_EXPORT_F32 x 3 stream), written as it is
+function writePFM(file, rgba, width, height, channels) {
+	let body
+	if (channels === 3) body = Buffer.from(rgba.buffer, rgba.byteOffset, 12 * width * height)
+	else {
+		body = Buffer.alloc(12 * width * height)
+		for (let i = 0; i < width * height; i++) for (let c = 0; c < 3; c++) body.writeFloatLE(rgba[4 * i + c], 4 * (3 * i + c))
+	}
 	fs.writeFileSync(file, Buffer.concat([Buffer.from("PF\n" + width + " " + height + "\n-1.0\n", "ascii"), body]))
 }
 

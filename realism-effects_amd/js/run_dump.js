@@ -20,6 +20,11 @@
 // of the last frame, and --png / --exr / --pfm write the blurred frame instead of final.bin.  With --ranks every rank gathers the source texels
 // its streaks reach from their owners (rfx_motion_blur_gather, js/tiling.js) and writes its rows as motion_blur.rank<r>.bin, which the parent
 // stitches like the other outputs; the image writers stay whole-frame-only, as they are for every tiled run.
+// --framesOut DIR [--framesFormat '"png"'|'"exr"'|'"pfm"'] [--tonemap ... --exposure X]: EVERY frame leaves the device — encoded there (K7: 8-bit
+// sRGB x 3, half x 4 or float x 3) and copied on the context's download stream into one of two pinned buffers while the next frame is drawn
+// (rfx_stage_export, js/frames.js) — and is written as DIR/frame_%05d.<ext>: the blurred frame with --motionBlur, else the effect's final image
+// (with --traa alone: TRAA's accumulated colour, png / pfm).  Every other output is byte-identical with and without it.  Whole-frame runs only:
+// with --ranks it throws, like the other image writers.
 // --saveState DIR [--saveEvery N]: write a checkpoint of the temporal state (js/state.js) into DIR after every N-th frame and after the last;
 // --loadState DIR: restore one first — the dump directories given are then the REMAINING frames, and the outputs are byte-identical to an
 // uninterrupted run.  Both work with --ranks (every rank writes its rows of the whole-frame planes; any rank count loads them), --traa,
@@ -34,7 +39,7 @@ const opt = {}
 let out = "."
 for (let i = 0; i < args.length; i++) {
 	if (args[i] === "--out") out = args[++i]
-	else if (args[i] === "--saveState" || args[i] === "--loadState") {
+	else if (args[i] === "--saveState" || args[i] === "--loadState" || args[i] === "--framesOut") {
 		// a directory, plain or JSON-quoted like the other path options
 		let v = args[i + 1]
 		try { v = JSON.parse(v) } catch (e) { /* plain */ }
@@ -46,6 +51,7 @@ if (!dumps.length) {
 	console.error("usage: run_dump.js <dumpdir>... --out <dir> [--steps N ...]")
 	process.exit(2)
 }
+if (opt.framesOut !== undefined && opt.ranks > 1) throw new Error("--framesOut writes whole frames: not with --ranks (the image writers are whole-frame-only for every tiled run)")
 // ---- row-tiled run: parent process
 if (opt.ranks > 1 && opt.rank === undefined) {
 	const cp = require("child_process")
@@ -97,6 +103,15 @@ const stream = !!opt.stream
 delete opt.stream
 const images = { png: opt.png, exr: opt.exr, pfm: opt.pfm, tonemap: opt.tonemap, exposure: opt.exposure }
 for (const k of Object.keys(images)) delete opt[k]
+const framesOut = opt.framesOut === undefined ? null : { dir: String(opt.framesOut), format: opt.framesFormat || "png" }
+delete opt.framesOut
+delete opt.framesFormat
+let frames = null
+function openFrames() {
+	if (!framesOut) return
+	fs.mkdirSync(framesOut.dir, { recursive: true })
+	frames = new rfx.FrameExporter(renderer, framesOut.dir, { format: framesOut.format, tonemap: images.tonemap, exposure: images.exposure })
+}
 const checkpoint = { save: opt.saveState, every: opt.saveEvery, load: opt.loadState }
 delete opt.saveState
 delete opt.saveEvery
@@ -196,6 +211,8 @@ if (opt.traa) {
 	if (mb) mb.shareEffectPass(traa)
 	const effects = mb ? [traa, mb] : [traa]
 	if (checkpoint.load) rfx.loadState(checkpoint.load, renderer, effects)
+	if (framesOut && !mb && framesOut.format === "exr") throw new Error("--framesOut with --traa alone: png or pfm (TRAA's alpha of 1 is written by the host's traa_compose)")
+	openFrames()
 	dumps.forEach((d, i) => {
 		const f = d === dumps[0] ? first : rfx.readDump(d)
 		scene.frame = f
@@ -205,8 +222,13 @@ if (opt.traa) {
 			mb.update(renderer, null, deltaTime)
 			mb.mainImage(renderer)
 		}
+		if (frames) {
+			if (!mb && traa.uniforms.accumulatedTexture !== rfx.TEX.TEMPORAL0) throw new Error("--framesOut with --traa: the accumulated colour is not in TEX.TEMPORAL0")
+			frames.submit(mb ? rfx.TEX.MOTION_BLUR : rfx.TEX.TEMPORAL0)
+		}
 		saveAfter(i + 1, effects)
 	})
+	if (frames) frames.finish()
 	renderer.sync()
 	fs.mkdirSync(out, { recursive: true })
 	const a = traa.output(renderer)
@@ -224,8 +246,15 @@ function blurFrame() {
 	mb.update(renderer, rfx.TEX.FINAL, deltaTime)
 	mb.mainImage(renderer)
 }
+// --framesOut: after the frame's draws the effect's own fragment (it writes TEX.FINAL only), then the staged export of what the frame shows
+function exportFrame() {
+	if (!frames) return
+	if (!mb) effect.mainImage(renderer)
+	frames.submit(mb ? rfx.TEX.MOTION_BLUR : rfx.TEX.FINAL)
+}
 const effects = mb ? [effect, mb] : [effect]
 if (checkpoint.load) rfx.loadState(checkpoint.load, renderer, effects)
+openFrames()
 if (stream && !tiled) {
 	if (!first.gbuffer) throw new Error("--stream needs packed gbuffer.bin / velocity.bin dumps")
 	const n = first.width * first.height
@@ -246,6 +275,7 @@ if (stream && !tiled) {
 		Object.assign(camera, cur.camera)
 		effect.update(renderer, null) // ... while frame i is drawn
 		blurFrame()
+		exportFrame() // (before the flip: the effect's fragment reads this frame's planes)
 		renderer.stageFlip()
 		saveAfter(i + 1, effects) // at the frame boundary: the save waits for the draws; the staged planes of frame i+1 are inputs, not state
 		cur = next
@@ -257,8 +287,10 @@ if (stream && !tiled) {
 		Object.assign(camera, f.camera)
 		effect.update(renderer, null)
 		blurFrame()
+		exportFrame()
 		saveAfter(i + 1, effects)
 	})
+if (frames) frames.finish()
 renderer.sync()
 fs.mkdirSync(out, { recursive: true })
 const T = rfx.TEX

@@ -812,6 +812,82 @@ static napi_value n_motion_blur_gather(napi_env env, napi_callback_info info) {
     return out;
 }
 
+/* the params object of the export calls: {source, format, channels, tonemap, exposure} -> rfx_export_params (include/rfx.h) */
+static void export_params(napi_env env, napi_value o, rfx_export_params *p) {
+    memset(p, 0, sizeof *p);
+    p->source = (int32_t)prop_num(env, o, "source", RFX_TEX_FINAL);
+    p->format = (int32_t)prop_num(env, o, "format", RFX_EXPORT_U8_SRGB);
+    p->channels = (int32_t)prop_num(env, o, "channels", 3);
+    p->tonemap = (int32_t)prop_num(env, o, "tonemap", 0);
+    p->exposure = (float)prop_num(env, o, "exposure", 1);
+}
+/* exportBytes(ctx, params) -> rfx_export_bytes (0: bad params) */
+static napi_value n_export_bytes(napi_env env, napi_callback_info info) {
+    napi_value a[2], out;
+    if (!get_args(env, info, 2, a)) return NULL;
+    rfx_ctx *c = get_ctx(env, a[0]);
+    if (!c) return NULL;
+    rfx_export_params p;
+    export_params(env, a[1], &p);
+    NAPI_CALL(env, napi_create_double(env, (double)rfx_export_bytes(c, &p), &out));
+    return out;
+}
+/* exportFrame(ctx, params, typedArray): rfx_export (blocks) / stageExport(ctx, params, typedArray) -> ticket: rfx_stage_export — the array,
+ * ideally a view of hostAlloc() memory, must stay alive until exportWait(ctx, ticket) has returned.  The library checks the byte count. */
+static napi_value export_into(napi_env env, napi_callback_info info, int staged) {
+    napi_value a[3], ab, out;
+    napi_typedarray_type type;
+    size_t len = 0, off = 0;
+    void *data = NULL;
+    if (!get_args(env, info, 3, a)) return NULL;
+    rfx_ctx *c = get_ctx(env, a[0]);
+    if (!c) return NULL;
+    rfx_export_params p;
+    export_params(env, a[1], &p);
+    bool is_ta = false;
+    napi_is_typedarray(env, a[2], &is_ta);
+    if (!is_ta || napi_get_typedarray_info(env, a[2], &type, &len, &data, &ab, &off) != napi_ok || !data) {
+        napi_throw_type_error(env, NULL, staged ? "stageExport: TypedArray expected" : "exportFrame: TypedArray expected");
+        return NULL;
+    }
+    static const size_t esz[] = {1, 1, 1, 2, 2, 4, 4, 4, 8, 8, 8};
+    int ticket = 0;
+    int rc = staged ? rfx_stage_export(c, &p, data, len * esz[type], &ticket) : rfx_export(c, &p, data, len * esz[type]);
+    if (rc) return throw_rfx(env, c, staged ? "rfx_stage_export" : "rfx_export", rc);
+    if (!staged) return NULL;
+    NAPI_CALL(env, napi_create_int32(env, ticket, &out));
+    return out;
+}
+static napi_value n_export_frame(napi_env env, napi_callback_info info) { return export_into(env, info, 0); }
+static napi_value n_stage_export(napi_env env, napi_callback_info info) { return export_into(env, info, 1); }
+/* exportWait(ctx, ticket): rfx_export_wait */
+static napi_value n_export_wait(napi_env env, napi_callback_info info) {
+    napi_value a[2];
+    int32_t ticket = 0;
+    if (!get_args(env, info, 2, a)) return NULL;
+    rfx_ctx *c = get_ctx(env, a[0]);
+    if (!c || !get_int(env, a[1], &ticket)) return NULL;
+    int rc = rfx_export_wait(c, ticket);
+    if (rc) return throw_rfx(env, c, "rfx_export_wait", rc);
+    return NULL;
+}
+/* constants() -> the header's values the JS side mirrors (js/Renderer.js EXPORT, PROF_KINDS): checked against each other by the tests */
+static napi_value n_constants(napi_env env, napi_callback_info info) {
+    (void)info;
+    static const struct { const char *name; int v; } k[] = {
+        {"EXPORT_F32", RFX_EXPORT_F32}, {"EXPORT_F16", RFX_EXPORT_F16}, {"EXPORT_U8_SRGB", RFX_EXPORT_U8_SRGB},
+        {"PROF_K7", RFX_PROF_K7}, {"PROF_COUNT", RFX_PROF_COUNT}, {"TEX_COUNT", RFX_TEX_COUNT}, {"ABI_VERSION", RFX_ABI_VERSION},
+    };
+    napi_value out;
+    NAPI_CALL(env, napi_create_object(env, &out));
+    for (size_t i = 0; i < sizeof k / sizeof k[0]; i++) {
+        napi_value v;
+        NAPI_CALL(env, napi_create_int32(env, k[i].v, &v));
+        NAPI_CALL(env, napi_set_named_property(env, out, k[i].name, v));
+    }
+    return out;
+}
+
 static napi_value n_sync(napi_env env, napi_callback_info info) {
     napi_value a[1];
     if (!get_args(env, info, 1, a)) return NULL;
@@ -896,6 +972,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"motionBlurStage", n_motion_blur_stage}, {"motionBlurReachMask", n_motion_blur_reach_mask}, {"motionBlurGather", n_motion_blur_gather},
         {"sync", n_sync}, {"setRowWindow", n_set_row_window}, {"setUvModel", n_set_uv_model}, {"cubeToEquirect", n_cube_to_equirect}, {"haloViolations", n_halo_violations}, {"timeBegin", n_time_begin}, {"timeEnd", n_time_end}, {"profile", n_profile}, {"profileRead", n_profile_read},
         {"stageUpload", n_stage_upload}, {"stageFlip", n_stage_flip}, {"hostAlloc", n_host_alloc},
+        {"exportBytes", n_export_bytes}, {"exportFrame", n_export_frame}, {"stageExport", n_stage_export}, {"exportWait", n_export_wait}, {"constants", n_constants},
         {"splitRows", n_split_rows}, {"commUniqueId", n_comm_unique_id}, {"commInit", n_comm_init}, {"haloExchange", n_halo_exchange},
         {"allgatherHistory", n_allgather_history}, {"gatherHistoryRows", n_gather_history_rows}, {"commWait", n_comm_wait}, {"commDestroy", n_comm_destroy},
         {"peerExport", n_peer_export}, {"peerOpen", n_peer_open}, {"peerGatherHistory", n_peer_gather_history}, {"peerClose", n_peer_close}, {"ssgiHitMask", n_ssgi_hit_mask},

@@ -17,7 +17,11 @@ RFX_ABI_VERSION = 21
 PEER_BLOB_BYTES = 192  # include/rfx.h RFX_PEER_BLOB_BYTES
 # rfx_profile_read's kinds (include/rfx.h RFX_PROF_*)
 PROF_KINDS = ("k1_prepass", "k1_ssgi_march", "k2_temporal_reproject", "k3_poisson_denoise_pass0", "k3_poisson_denoise_passN", "k4_compose", "k5_final_compose", "k6_motion_blur",
-              "k6_motion_blur_reach")
+              "k6_motion_blur_reach", "k7_export")
+EXPORT_F32, EXPORT_F16, EXPORT_U8_SRGB = 0, 1, 2  # rfx_export_params.format (include/rfx.h RFX_EXPORT_*)
+EXPORT_FORMATS = {"f32": EXPORT_F32, "f16": EXPORT_F16, "u8_srgb": EXPORT_U8_SRGB}
+EXPORT_DTYPE = {EXPORT_F32: np.float32, EXPORT_F16: np.float16, EXPORT_U8_SRGB: np.uint8}
+EXPORT_TONEMAP = {"linear": 0, "aces": 1}  # rfx_export_params.tonemap: imageio.tonemap's operators
 RFX_UV_IDEAL, RFX_UV_REFERENCE_GL = 0, 1  # rfx_set_uv_model
 RFX_OK, RFX_EINVAL, RFX_ENOMEM, RFX_EDEVICE, RFX_ESTATE, RFX_EUNSUPPORTED = 0, -1, -2, -3, -4, -5
 
@@ -104,12 +108,17 @@ class MotionBlurParams(C.Structure):
                 ("halfStoreRTZ", C.c_int32)]
 
 
+class ExportParams(C.Structure):
+    _fields_ = [("source", C.c_int32), ("format", C.c_int32), ("channels", C.c_int32), ("tonemap", C.c_int32), ("exposure", C.c_float)]
+
+
 EXPORTS = [
     "rfx_abi_version", "rfx_create", "rfx_destroy", "rfx_last_error", "rfx_get_geometry", "rfx_set_stream", "rfx_tex_texel_bytes", "rfx_tex_held_rows",
     "rfx_upload", "rfx_download", "rfx_clear", "rfx_tex_device_ptr", "rfx_bind_external", "rfx_pack_gbuffer", "rfx_pack_velocity", "rfx_set_environment", "rfx_set_environment_importance", "rfx_download_environment", "rfx_cube_to_equirect", "rfx_set_row_window", "rfx_set_uv_model", "rfx_ssgi_march", "rfx_ssgi_trace", "rfx_ssgi_shade", "rfx_temporal_reproject",
     "rfx_copy_framebuffer", "rfx_poisson_denoise", "rfx_compose", "rfx_final_compose", "rfx_motion_blur", "rfx_sync", "rfx_halo_violations", "rfx_time_begin", "rfx_time_end", "rfx_profile", "rfx_profile_read",
     "rfx_host_alloc", "rfx_host_free", "rfx_stage_upload", "rfx_stage_flip", "rfx_split_rows", "rfx_comm_unique_id", "rfx_comm_init", "rfx_comm_destroy", "rfx_halo_exchange", "rfx_allgather_history", "rfx_gather_history_rows", "rfx_peer_export", "rfx_peer_open", "rfx_peer_gather_history", "rfx_peer_close", "rfx_ssgi_hit_rows", "rfx_ssgi_hit_mask", "rfx_ssgi_target_rows", "rfx_comm_wait",
     "rfx_motion_blur_reach_mask", "rfx_motion_blur_stage", "rfx_motion_blur_gather",
+    "rfx_export_bytes", "rfx_export", "rfx_stage_export", "rfx_export_wait",
 ]
 
 _lib = None
@@ -206,6 +215,11 @@ def load_library(path: str | None = None) -> C.CDLL:
     lib.rfx_motion_blur_reach_mask.argtypes = [vp, C.POINTER(MotionBlurParams), C.POINTER(C.c_uint32), i]
     lib.rfx_motion_blur_stage.argtypes = [vp, C.POINTER(MotionBlurParams)]
     lib.rfx_motion_blur_gather.argtypes = [vp, C.POINTER(MotionBlurParams), vp, C.POINTER(C.c_size_t)]
+    lib.rfx_export_bytes.argtypes = [vp, C.POINTER(ExportParams)]
+    lib.rfx_export_bytes.restype = C.c_size_t
+    lib.rfx_export.argtypes = [vp, C.POINTER(ExportParams), vp, C.c_size_t]
+    lib.rfx_stage_export.argtypes = [vp, C.POINTER(ExportParams), vp, C.c_size_t, C.POINTER(i)]
+    lib.rfx_export_wait.argtypes = [vp, i]
     if lib.rfx_abi_version() != RFX_ABI_VERSION:
         raise ImportError("librfx_hip.so ABI version %d != %d" % (lib.rfx_abi_version(), RFX_ABI_VERSION))
     if path is None:

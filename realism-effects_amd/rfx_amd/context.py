@@ -42,6 +42,7 @@ class Context:
             self.lib.rfx_destroy(self._h)
             self._h = None
             self.__dict__.pop("_staged_keepalive", None)
+            self.__dict__.pop("_export_keepalive", None)
 
     def __del__(self):
         try:
@@ -124,6 +125,54 @@ class Context:
         gens = self.__dict__.setdefault("_staged_keepalive", [])
         gens.append(self.__dict__.pop("_staged_now", []))
         del gens[:-2]
+
+    # -- streamed frame export (rfx.h "streamed frame export"): the encode runs on the device, only the encoded bytes cross PCIe
+    @staticmethod
+    def export_params(source: int, format, channels: int = 3, tonemap="linear", exposure: float = 1.0) -> abi.ExportParams:
+        """`format`: "f32" / "f16" / "u8_srgb" or abi.EXPORT_*; `tonemap`: "linear" / "aces" (imageio.tonemap's operators) or 0 / 1"""
+        return abi.ExportParams(int(source), int(abi.EXPORT_FORMATS.get(format, format)), int(channels), int(abi.EXPORT_TONEMAP.get(tonemap, tonemap)),
+                                float(exposure))
+
+    def export_bytes(self, p: abi.ExportParams) -> int:
+        return int(self.lib.rfx_export_bytes(self._h, C.byref(p)))
+
+    def _export_out(self, p: abi.ExportParams, out, what):
+        n = self.export_bytes(p)
+        dtype = abi.EXPORT_DTYPE.get(p.format)
+        if out is None:
+            # (bad params: any non-empty buffer will do, the library names the fault)
+            return np.empty((self.tile_rows, self.W, p.channels) if n else (1,), dtype or np.uint8), n
+        if not isinstance(out, np.ndarray) or not out.flags["C_CONTIGUOUS"] or not out.flags["WRITEABLE"]:
+            raise TypeError("%s: out must be a writeable C-contiguous ndarray" % what)
+        if n and (out.dtype != dtype or out.nbytes != n):
+            raise ValueError("%s: out must hold %d bytes of %s, got %d of %s" % (what, n, np.dtype(dtype), out.nbytes, out.dtype))
+        return out, n
+
+    def export(self, source: int, format, channels: int = 3, tonemap="linear", exposure: float = 1.0, out=None) -> np.ndarray:
+        """rfx_export: the context's tile rows of `source`, encoded on the device -> (rows, W, channels) uint8 / float16 / float32, row 0 =
+        bottom (the order download() uses).  Blocks until the bytes are there."""
+        p = self.export_params(source, format, channels, tonemap, exposure)
+        out, n = self._export_out(p, out, "export")
+        self._chk(self.lib.rfx_export(self._h, C.byref(p), out.ctypes.data_as(C.c_void_p), n), "rfx_export")
+        return out.reshape(self.tile_rows, self.W, p.channels)
+
+    def stage_export(self, source: int, format, channels: int = 3, tonemap="linear", exposure: float = 1.0, *, out: np.ndarray) -> int:
+        """rfx_stage_export: enqueue the encode (after every draw enqueued so far) and the copy into `out` — a host_alloc() array for an
+        asynchronous copy — and return the ticket.  `out` is complete once export_wait(ticket) has returned; the call itself returns only when
+        the export two tickets earlier has completed (alternate two buffers)."""
+        p = self.export_params(source, format, channels, tonemap, exposure)
+        out, n = self._export_out(p, out, "stage_export")
+        t = C.c_int(0)
+        self._chk(self.lib.rfx_stage_export(self._h, C.byref(p), out.ctypes.data_as(C.c_void_p), n, C.byref(t)), "rfx_stage_export")
+        keep = self.__dict__.setdefault("_export_keepalive", {})  # the copy writes `out` until its ticket retires
+        keep[t.value] = out
+        for old in [k for k in keep if k <= t.value - 2]:
+            del keep[old]
+        return int(t.value)
+
+    def export_wait(self, ticket: int):
+        self._chk(self.lib.rfx_export_wait(self._h, int(ticket)), "rfx_export_wait")
+        self.__dict__.get("_export_keepalive", {}).pop(int(ticket), None)
 
     def clear(self, tex: int):
         self._chk(self.lib.rfx_clear(self._h, tex), "rfx_clear")

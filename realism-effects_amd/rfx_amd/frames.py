@@ -1,0 +1,56 @@
+"""Per-frame output of an offline run through the streamed export (include/rfx.h "streamed frame export"): the Python twin of js/frames.js.
+
+    png -> EXPORT_U8_SRGB x 3 (tonemap / exposure)     exr -> EXPORT_F16 x 4     pfm -> EXPORT_F32 x 3
+
+submit(source) is called once per frame AFTER the frame's draws are enqueued: it stages this frame's export into one of two pinned buffers,
+then waits for the PREVIOUS frame's ticket — which has had this frame's draws to hide behind — and hands its bytes to `write`.  At most two
+exports are in flight; finish() waits for the last one."""
+from __future__ import annotations
+
+import os
+
+import numpy as np
+
+from . import abi, imageio
+
+FRAME_FORMATS = {"png": ("u8_srgb", 3), "exr": ("f16", 4), "pfm": ("f32", 3)}
+
+
+class FrameExporter:
+    def __init__(self, ctx, directory: str, format: str = "png", tonemap: str = "aces", exposure: float = 1.0, write=None):
+        if format not in FRAME_FORMATS:
+            raise ValueError('format: "png", "exr" or "pfm"')
+        self.ctx, self.dir, self.format = ctx, directory, format
+        self.kind, self.channels = FRAME_FORMATS[format]
+        u8 = self.kind == "u8_srgb"
+        self.tonemap, self.exposure = (tonemap if u8 else "linear"), (float(exposure) if u8 else 1.0)
+        dtype = abi.EXPORT_DTYPE[abi.EXPORT_FORMATS[self.kind]]
+        self.buffers = [ctx.host_alloc((ctx.tile_rows, ctx.W, self.channels), dtype) for _ in range(2)]
+        self.write = write or self.write_frame
+        self.count, self.pending = 0, None
+
+    def write_frame(self, index: int, data: np.ndarray):
+        path = os.path.join(self.dir, "frame_%05d.%s" % (index, self.format))
+        if self.format == "png":
+            imageio.write_png(path, data)
+        elif self.format == "exr":
+            imageio.write_exr(path, {n: data[..., k] for k, n in enumerate("RGBA")}, compression="none", half=True)
+        else:
+            imageio.write_pfm(path, data)
+
+    def submit(self, source: int):
+        index, self.count = self.count, self.count + 1
+        buf = self.buffers[index & 1]
+        ticket = self.ctx.stage_export(source, self.kind, self.channels, self.tonemap, self.exposure, out=buf)
+        self._retire()
+        self.pending = (ticket, index, buf)
+
+    def _retire(self):
+        if self.pending is None:
+            return
+        (ticket, index, buf), self.pending = self.pending, None
+        self.ctx.export_wait(ticket)
+        self.write(index, buf)
+
+    def finish(self):
+        self._retire()

@@ -1,0 +1,138 @@
+"""Shared by tests/test_export_cpu.py and tests/test_gpu_export.py: the inputs of the export tests, imageio.tonemap's arithmetic kept in
+float64 up to the value that is truncated (v = s * 255 + 0.5), and the margin rule that holds an fp32 evaluation against it.
+
+Margin rule.  A byte whose v lies more than DELTA = 2^-10 from the nearest integer must equal imageio.tonemap's byte; any other byte may differ
+by 1; none by more.  DELTA: an fp32 evaluation of the chain emulated in numpy float32 (powf and exp2(log2)) differed from the float64 bytes
+only within 3.5e-5 code values of a boundary, so 2^-10 leaves about 28x headroom.  The share of bytes the margin excuses is capped at 1 % per
+case (a uniform v would put 2 * DELTA = 0.2 % there), so the rule can never become vacuous; the CPU suite checks that premise on these inputs."""
+import zlib
+
+import numpy as np
+
+from rfx_amd import imageio
+
+DELTA = 2.0 ** -10
+SHARE_CAP = 0.01
+OPERATORS = ("linear", "aces")
+EXPOSURES = (1.0, 0.37, 2.5)
+FAMILIES = ("lognormal", "uniform_1p2", "uniform_0p01")
+SIZES = ((5, 3), (97, 55), (128, 72))  # (W, H): the tail only plus one group; odd width, pixels mod 4 = 3; more than one block per row of groups
+
+
+def u8_cases():
+    """(W, H, channels, family, exposure, operator): the whole matrix at 97x55 (channel count alternating), both channel counts and both
+    operators at the other two sizes"""
+    cases, k = [], 0
+    for op in OPERATORS:
+        for ex in EXPOSURES:
+            for fam in FAMILIES:
+                cases.append((97, 55, 3 + (k & 1), fam, ex, op))
+                k += 1
+    for (w, h) in ((5, 3), (128, 72)):
+        for ch in (3, 4):
+            for op in OPERATORS:
+                cases.append((w, h, ch, "lognormal", 1.0, op))
+    return cases
+
+
+def case_id(c):
+    return "%dx%dx%d-%s-%g-%s" % c
+
+
+def linear_input(W, H, family, planted=True):
+    """(H, W, 4) float32: rgb of the family, alpha uniform in [-0.2, 1.2]; NaN, +-inf, negatives and values above 65504 planted in every
+    channel (frames of 64 pixels and more: a 5x3 frame keeps its 15 pixels for the arithmetic)"""
+    rng = np.random.default_rng(zlib.crc32(("%d %d %s" % (W, H, family)).encode()))
+    if family == "lognormal":
+        rgb = rng.lognormal(-1.0, 1.5, (H, W, 3))
+    elif family == "uniform_1p2":
+        rgb = rng.uniform(0.0, 1.2, (H, W, 3))
+    elif family == "uniform_0p01":
+        rgb = rng.uniform(0.0, 0.01, (H, W, 3))
+    else:
+        raise ValueError(family)
+    a = np.concatenate([rgb, rng.uniform(-0.2, 1.2, (H, W, 1))], -1).astype(np.float32)
+    if planted and W * H >= 64:
+        flat = a.reshape(-1)
+        pos = rng.choice(flat.size, 40, replace=False)
+        flat[pos] = np.tile(np.array([np.nan, np.inf, -np.inf, -0.5, -1e30, 65504.0, 65505.0, 1e30, 0.0, -0.0], np.float32), 4)
+    return a
+
+
+def tonemap_v(linear, operator, exposure):
+    """imageio.tonemap line by line in float64, stopped before the truncation: v = s * 255 + 0.5, (H, W, 3)"""
+    c = np.nan_to_num(np.asarray(linear, np.float64)[..., :3], nan=0.0, posinf=65504.0, neginf=0.0)
+    c = np.clip(c, 0.0, 65504.0) * exposure
+    if operator == "aces":
+        m_in = np.array([[0.59719, 0.35458, 0.04823], [0.07600, 0.90834, 0.01566], [0.02840, 0.13383, 0.83777]])
+        m_out = np.array([[1.60475, -0.53108, -0.07367], [-0.10208, 1.10813, -0.00605], [-0.00327, -0.07276, 1.07602]])
+        c = (c / 0.6) @ m_in.T
+        c = (c * (c + 0.0245786) - 0.000090537) / (c * (0.983729 * c + 0.4329510) + 0.238081)
+        c = c @ m_out.T
+    elif operator != "linear":
+        raise ValueError(operator)
+    c = np.clip(np.nan_to_num(c, nan=0.0, posinf=1.0, neginf=0.0), 0.0, 1.0)
+    s = np.where(c <= 0.0031308, c * 12.92, 1.055 * np.power(c, 1.0 / 2.4) - 0.055)
+    return s * 255.0 + 0.5
+
+
+def alpha_v(alpha):
+    """the fourth channel's own definition: NaN -> 0, clip to [0, 1], v = a * 255 + 0.5"""
+    a = np.asarray(alpha, np.float64)
+    a = np.clip(np.where(np.isnan(a), 0.0, a), 0.0, 1.0)
+    return a * 255.0 + 0.5
+
+
+def reference_v(linear, channels, operator, exposure):
+    """(H, W, channels) float64 v and its bytes; the colour bytes ARE imageio.tonemap's"""
+    v = tonemap_v(linear, operator, exposure)
+    ref = v.astype(np.uint8)
+    assert np.array_equal(ref, imageio.tonemap(linear, operator, exposure))  # the restatement above has not drifted from the definition
+    if channels == 4:
+        va = alpha_v(linear[..., 3:4])
+        v, ref = np.concatenate([v, va], -1), np.concatenate([ref, va.astype(np.uint8)], -1)
+    return v, ref
+
+
+def excluded(v):
+    """bytes the margin rule excuses: v within DELTA of an integer"""
+    return np.abs(v - np.rint(v)) <= DELTA
+
+
+def check_margin(got, v, ref):
+    """assert the margin rule and the cap; -> (share excused, bytes that differ)"""
+    got = np.asarray(got)
+    assert got.dtype == np.uint8 and got.shape == ref.shape, (got.dtype, got.shape, ref.shape)
+    ex = excluded(v)
+    diff = np.abs(got.astype(np.int32) - ref.astype(np.int32))
+    share = float(ex.mean())
+    print("export u8: excused share %.5f, differing bytes %d of %d, max diff %d" % (share, int((diff != 0).sum()), diff.size, int(diff.max())))
+    assert diff.max() <= 1, np.argwhere(diff > 1)[:5]
+    bad = (diff != 0) & ~ex
+    assert not bad.any(), (np.argwhere(bad)[:5], v[bad][:5], got[bad][:5], ref[bad][:5])
+    assert share <= SHARE_CAP, share
+    return share, int((diff != 0).sum())
+
+
+# ---------------------------------------------------------------- F16
+def f16_input(W, H):
+    """(H, W, 4) float32 with the roundings that matter planted from the first texel on (a 5x3 frame holds them all)"""
+    rng = np.random.default_rng(zlib.crc32(("f16 %d %d" % (W, H)).encode()))
+    a = (rng.standard_normal((H, W, 4)) * np.exp(rng.uniform(-12, 12, (H, W, 4)))).astype(np.float32)
+    special = np.array([np.nan, np.inf, -np.inf, 0.0, -0.0, 65504.0, 65519.996, 65520.0, 2.0 ** -24, 2.0 ** -25, 1.0 + 2.0 ** -11, 1.0 + 3 * 2.0 ** -11,
+                        3 * 2.0 ** -24, -(2.0 ** -15 + 2.0 ** -26), 2.0 ** -25 * (1 + 2.0 ** -20), -65520.0], np.float32)
+    flat = a.reshape(-1)
+    flat[:special.size] = special
+    flat[-special.size:] = special[::-1]  # ... and in the tail's pixels
+    return a
+
+
+def check_f16(got, linear, channels):
+    got = np.asarray(got)
+    assert got.dtype == np.float16
+    with np.errstate(over="ignore"):
+        ref = np.asarray(linear[..., :channels], np.float32).astype(np.float16)
+    assert got.shape == ref.shape
+    nan = np.isnan(ref)
+    assert np.array_equal(np.isnan(got), nan)
+    assert np.array_equal(got.view(np.uint16)[~nan], ref.view(np.uint16)[~nan])

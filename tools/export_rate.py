@@ -1,0 +1,149 @@
+#!/usr/bin/env python3
+"""What per-frame output costs at 4K (GPU box; fails without a device): wall time per frame of the SSGI chain + the effect's own fragment with
+
+    T0  no per-frame output
+    T1  a blocking download(TEX_FINAL) every frame — RGBA32F, 133 MB, into a pinned buffer: the most a host could do before the export
+    T2  stage_export U8_SRGB x 3 every frame into two alternating pinned buffers, export_wait one frame late (rfx_amd/frames.py's order)
+
+each with the dump resident on the device and streamed (rfx_stage_upload / rfx_stage_flip from two pinned sets), in ONE process: every shape is
+warmed first, then three alternating rounds of the three modes, each a steady state of at least --seconds with a device synchronise at the end.
+K7's own time comes from rfx_profile, next to its bytes over the 8 TB/s HBM peak.
+
+    python tools/export_rate.py [--out profiles/export/rates.json] [--seconds 1.0]
+"""
+import argparse
+import copy
+import ctypes as C
+import json
+import math
+import os
+import sys
+import time
+import types
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "realism-effects_amd"))
+
+from rfx_amd import abi, effect  # noqa: E402
+from rfx_amd.context import Context  # noqa: E402
+from rfx_amd.scene import synthetic_frame_parallel  # noqa: E402
+
+W, H = 3840, 2160
+HBM_PEAK = 8e12  # bytes / s
+MODES = ("T0", "T1", "T2")
+
+
+class Run:
+    def __init__(self, seed):
+        self.ctx = Context(W, H)  # raises without a device
+        self.frames = [synthetic_frame_parallel(W, H, i, seed=seed, workers=16) for i in range(2)]
+        self.scene = types.SimpleNamespace(frame=None)
+        self.cam = types.SimpleNamespace(**vars(self.frames[0].camera))
+        self.fx = effect.SSGIEffect(None, self.scene, self.cam, dict(width=W, height=H), seeds=dict(ssgi=11, denoise=22), half_store_rtz=True)
+        ctx = self.ctx
+        self.sets = []
+        for f in self.frames:  # two pinned sets of the four planes: what a streamed run alternates between
+            s = copy.copy(f)
+            for k in ("depth", "gbuffer", "velocity", "direct"):
+                p = ctx.host_alloc(getattr(f, k).shape, getattr(f, k).dtype)
+                p[...] = getattr(f, k)
+                setattr(s, k, p)
+            s.static = "resident"  # the effect does not upload it again: it is staged, or already there
+            self.sets.append(s)
+        self.final = ctx.host_alloc((H, W, 4), np.float32)
+        self.u8 = [ctx.host_alloc((H, W, 3), np.uint8) for _ in range(2)]
+
+    def frame(self, f):
+        self.scene.frame = f
+        for k, v in vars(f.camera).items():
+            setattr(self.cam, k, v)
+        self.fx.update(self.ctx, None)
+        self.fx.mainImage(self.ctx)
+
+    def loop(self, mode, streamed, n):
+        """n frames; returns wall seconds, the last export waited for and the device synchronised inside the clock"""
+        ctx, sets = self.ctx, self.sets
+        pending = None
+        if streamed:
+            ctx.stage_frame(sets[0])
+            ctx.stage_flip()
+        else:
+            ctx.upload_frame(self.frames[0])
+        ctx.sync()
+        t0 = time.perf_counter()
+        for i in range(n):
+            cur = sets[i & 1] if streamed else sets[0]
+            if streamed:
+                ctx.stage_frame(sets[(i + 1) & 1])
+            self.frame(cur)
+            if mode == "T1":
+                ctx._chk(ctx.lib.rfx_download(ctx._h, abi.TEX_FINAL, self.final.ctypes.data_as(C.c_void_p), 0, H), "rfx_download")
+            elif mode == "T2":
+                t = ctx.stage_export(abi.TEX_FINAL, "u8_srgb", 3, "aces", 1.0, out=self.u8[i & 1])
+                if pending is not None:
+                    ctx.export_wait(pending)
+                pending = t
+            if streamed:
+                ctx.stage_flip()
+        if pending is not None:
+            ctx.export_wait(pending)
+        ctx.sync()
+        return time.perf_counter() - t0
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "export", "rates.json"))
+    ap.add_argument("--seconds", type=float, default=1.0, help="steady state per measurement, at least")
+    ap.add_argument("--seed", type=int, default=1234)
+    ap.add_argument("--size", default="3840x2160", help="frame size (the committed numbers are 4K; a small size checks the script itself)")
+    a = ap.parse_args()
+    global W, H
+    W, H = (int(v) for v in a.size.split("x"))
+    run = Run(a.seed)
+    result = dict(width=W, height=H, seed=a.seed, seconds=a.seconds, rounds={}, frames={})
+    for streamed in (False, True):
+        key = "streamed" if streamed else "resident"
+        n = {}
+        for mode in MODES:  # warm every shape, and size its loop from the warm rate
+            run.loop(mode, streamed, 5)
+            per = run.loop(mode, streamed, 20) / 20
+            n[mode] = max(20, int(math.ceil(a.seconds / per)))
+        rounds = []
+        for r in range(3):
+            row = {}
+            for mode in MODES:
+                row[mode] = round(run.loop(mode, streamed, n[mode]) / n[mode] * 1e3, 4)
+            row["T2_minus_T0"] = round(row["T2"] - row["T0"], 4)
+            row["T1_minus_T0"] = round(row["T1"] - row["T0"], 4)
+            row["T2_below_T1"] = row["T2"] < row["T1"]
+            rounds.append(row)
+            print(key, json.dumps(row), flush=True)
+        result["rounds"][key] = rounds
+        result["frames"][key] = n
+    # K7 alone, inside a loop of exports
+    ctx = run.ctx
+    for _ in range(5):
+        ctx.export_wait(ctx.stage_export(abi.TEX_FINAL, "u8_srgb", 3, "aces", 1.0, out=run.u8[0]))
+    ctx.sync()
+    ctx.profile(True)
+    for i in range(20):
+        ctx.export_wait(ctx.stage_export(abi.TEX_FINAL, "u8_srgb", 3, "aces", 1.0, out=run.u8[i & 1]))
+    ms, launches = ctx.profile_read()["k7_export"]
+    ctx.profile(False)
+    moved = W * H * (16 + 3)
+    result["k7_u8x3"] = dict(ms=round(ms / launches, 5), launches=launches, bytes=moved, ms_at_hbm_peak=round(moved / HBM_PEAK * 1e3, 5),
+                             frac_of_hbm_peak=round(moved / HBM_PEAK * 1e3 / (ms / launches), 4))
+    result["T2_below_T1_every_round"] = all(r["T2_below_T1"] for rs in result["rounds"].values() for r in rs)
+    print(json.dumps(result["k7_u8x3"]), flush=True)
+    ctx.close()
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
