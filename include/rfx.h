@@ -439,6 +439,53 @@ int rfx_export(rfx_ctx *, const rfx_export_params *, void *host, size_t bytes);
 int rfx_stage_export(rfx_ctx *, const rfx_export_params *, void *host, size_t bytes, int *ticket);
 int rfx_export_wait(rfx_ctx *, int ticket);
 
+/* ---- PNG fragments (K8): the U8_SRGB export leaves the device as a finished PNG data stream.  Additive to ABI 21 like the export: three
+ * more entry points and one more profile kind (RFX_PROF_K8, read through rfx_profile_read_n); a host checks for the symbol.  K7 runs exactly as for rfx_stage_export, so the pixels in the
+ * PNG are by construction the bytes rfx_export returns; K8 then encodes them on the DOWNLOAD stream, behind the "encoded" event, into a device
+ * buffer of its own, and the device-to-host copy of the WHOLE bound follows.  (Copying only fragment_bytes would need the host to wait for the
+ * header or the kernel to store into pinned memory; the downward PCIe direction is idle and the copy is already hidden, so it is left out.)
+ *
+ * THE FRAGMENT is the IDAT chunks of the context's tile rows and nothing else.
+ *   Scanlines run top first: frame row tile_y0 + tile_rows - 1 down to tile_y0.  One scanline = one deflate chunk = one IDAT chunk:
+ *       length (big-endian) | "IDAT" | payload | CRC-32("IDAT" + payload)
+ *   Filter.  The scanline's FILTERED BYTES are the filter type byte followed by the n - 1 = W * channels residuals (n = 1 + W * channels).
+ *     filter 0 (adaptive): the type with the smallest sum of |residual as int8| among None (0), Sub (1), Up (2), Paeth (4); a tie goes to the
+ *     lowest type number.  The tile's FIRST scanline chooses between None and Sub only: its upper neighbour belongs to another tile (a
+ *     whole-frame context is the one-tile case of the same rule).  filter 1..4 forces None, Sub, Up, Paeth; a forced Up or Paeth falls back
+ *     to Sub on the tile's first scanline.  Avg is not offered.
+ *   Payload: the smaller of two forms, a tie going to (a).  Both end on a byte boundary, so the payloads concatenate into one raw deflate stream.
+ *     (a) one non-final dynamic-Huffman block of the n literals and the end-of-block symbol — no length / distance codes — then, after the
+ *         three header bits 0 0 0 and padding to a byte, the empty non-final stored block 00 00 FF FF.  HLIT declares 257 codes, HDIST one
+ *         distance code of length 0.  Size: ceil((block bits + 3) / 8) + 4.
+ *     (b) ceil(n / 65535) non-final stored blocks (00 | LEN | ~LEN | bytes).  Size: n + 5 * ceil(n / 65535).
+ *   THE CODE-LENGTH RULE (literal code: 257 symbols, limit 15, end-of-block counted once; code-length code: 19 symbols, limit 7):
+ *     1. rank the symbols of non-zero frequency by (frequency descending, symbol number ascending);
+ *     2. minimum-redundancy lengths by Moffat and Katajainen's in-place method over the frequencies in ascending order (the reverse of the
+ *        ranking), where an internal node is taken before a leaf of equal weight;
+ *     3. count the codes per length, a length above the limit counting at the limit; while the Kraft sum sum(count[i] << (limit - i)) exceeds
+ *        1 << limit: take one code from count[limit], take one from the longest shorter length i that has one and add two to count[i + 1];
+ *     4. hand the lengths out by rank, shortest first: the count[1] highest-ranked symbols get 1 bit, the next count[2] get 2, and so on;
+ *     5. deflate's canonical codes from those lengths.
+ *   The block header of (a): the 258 code lengths (257 literal / length codes, then the distance code's 0) as ONE sequence of run-length
+ *     tokens — a run of r zeros: 18 (11..138) while r >= 11, then 17 (3..10) if r >= 3, else single 0s; a run of r equal non-zero lengths:
+ *     the length once, then 16 (3..6) while 3 or more remain, then single lengths — coded with the code-length code built by the same rule
+ *     from the tokens' frequencies; HCLEN = the last used entry of deflate's order 16 17 18 0 8 7 9 6 10 5 11 4 12 3 13 2 14 1 15, at least 4.
+ *     (A decoder accepts any valid header; this one is fixed so that the fragment is a pure function of the pixels — tests/png_device_ref.py
+ *     restates it and the device's fragment equals it byte for byte.)
+ * THE RESULT BUFFER (`host`, rfx_png_bound bytes): a 32-byte little-endian header, the fragment from offset 32, unspecified bytes after it.
+ *       uint64 fragment_bytes | uint32 adler_a | uint32 adler_b | uint64 raw_bytes | 8 bytes of zero
+ *   adler_a / adler_b: the stand-alone Adler-32 (initial value 1) of the tile's filtered bytes, low and high half; raw_bytes = tile_rows * n.
+ * THE HOST'S WRAP: signature; IHDR; IDAT(78 01); the fragments, TOP TILE FIRST; IDAT(03 00 | Adler-32 big-endian) — the final empty block and
+ *   the tiles' Adlers combined in that order as A = (A1 + A2 - 1) mod 65521, B = (B1 + B2 + len2 * (A1 - 1)) mod 65521; IEND.
+ * rfx_png_bound = 32 + tile_rows * (12 + 5 * ceil(n / 65535) + n): every chunk in form (b).  0 on bad params or a format other than U8_SRGB.
+ * `filter`: 0..4 as above.  Tickets come from rfx_stage_export's sequence and rfx_export_wait retires both kinds; the back pressure and the
+ * two-buffer rule apply to the mixed sequence.  rfx_png = rfx_stage_png + rfx_export_wait.
+ * RFX_EINVAL: what rfx_stage_export refuses, a format other than RFX_EXPORT_U8_SRGB, a filter outside 0..4, bytes != rfx_png_bound.
+ * RFX_ESTATE: rfx_stage_export's rule. */
+size_t rfx_png_bound(const rfx_ctx *, const rfx_export_params *);
+int rfx_stage_png(rfx_ctx *, const rfx_export_params *, int filter, void *host, size_t bytes, int *ticket);
+int rfx_png(rfx_ctx *, const rfx_export_params *, int filter, void *host, size_t bytes);
+
 int rfx_sync(rfx_ctx *);
 
 /* ---- streaming dumps: host buffers that cross PCIe every frame (an offline run over a dumped sequence).  rfx_upload is synchronous
@@ -536,8 +583,14 @@ enum { RFX_PROF_K1_PREPASS = 0, RFX_PROF_K1_MARCH, RFX_PROF_K2, RFX_PROF_K3_PASS
        RFX_PROF_K6_REACH, /* ABI 21: the reach reduction of rfx_motion_blur_reach_mask / rfx_motion_blur_gather */
        RFX_PROF_K7, /* the encode of rfx_export / rfx_stage_export */
        RFX_PROF_COUNT };
+/* Kinds added from here on do not grow RFX_PROF_COUNT: rfx_profile_read has no size argument and keeps filling exactly RFX_PROF_COUNT entries, so
+ * a caller built against an earlier header is never overrun.  rfx_profile_read_n fills min(entries, RFX_PROF_COUNT_ALL) entries of each array
+ * (the first RFX_PROF_COUNT are rfx_profile_read's) and is how the kinds below are read. */
+enum { RFX_PROF_K8 = RFX_PROF_COUNT, /* the PNG encode of rfx_png / rfx_stage_png: its three launches on the download stream */
+       RFX_PROF_COUNT_ALL };
 int rfx_profile(rfx_ctx *, int enable);
 int rfx_profile_read(rfx_ctx *, float *ms_sum, int *launches);
+int rfx_profile_read_n(rfx_ctx *, float *ms_sum, int *launches, int entries);
 
 #ifdef __cplusplus
 }

@@ -340,6 +340,8 @@ __global__ __launch_bounds__(RFX_K7_BLOCK) void k7_export(K7Args A) {
 
 }  // namespace
 
+#include "k8_png.h"  // K8: the PNG fragment of K7's U8 stream
+
 template <int FMT, int CH, int TM>
 static void k7_launch(const K7Args &A, int blocks, hipStream_t stream) {
     hipLaunchKernelGGL((k7_export<FMT, CH, TM>), dim3(blocks), dim3(RFX_K7_BLOCK), 0, stream, A);

@@ -118,6 +118,7 @@ void rfx_destroy(rfx_ctx *c) {
     if (c->download_stream) { hipStreamSynchronize(c->download_stream); hipStreamDestroy(c->download_stream); }
     for (int b = 0; b < 2; b++) {
         if (c->export_buf[b]) hipFree(c->export_buf[b]);
+        if (c->png_buf[b]) hipFree(c->png_buf[b]);
         if (c->ev_export_encoded[b]) hipEventDestroy(c->ev_export_encoded[b]);
         if (c->ev_export_copied[b]) hipEventDestroy(c->ev_export_copied[b]);
     }
@@ -1205,13 +1206,22 @@ size_t rfx_export_bytes(const rfx_ctx *c, const rfx_export_params *p) {
     return (size_t)t.bytes;
 }
 
-static int export_enqueue(rfx_ctx *c, const rfx_export_params *p, void *host, size_t bytes, int *ticket, const char *fn) {
+// png_filter < 0: the plain export (K7's bytes cross PCIe); 0..4: rfx_stage_png — K7 as ever, then K8 on the download stream and its result buffer
+static int export_enqueue(rfx_ctx *c, const rfx_export_params *p, void *host, size_t bytes, int *ticket, const char *fn, int png_filter = -1) {
     if (!c || !p || !host) return RFX_EINVAL;
     RFX_ENTER(c);
     if (const char *bad = export_params_error(p)) return export_fail(c, RFX_EINVAL, fn, bad);
     rfx_export_plan t;
     if (!rfx_export_plan_for(c->tile_rows * c->W, p->format, p->channels, &t)) return export_fail(c, RFX_EINVAL, fn, "bad format or channel count");
-    if (bytes != (size_t)t.bytes) return export_fail(c, RFX_EINVAL, fn, "bytes != rfx_export_bytes(ctx, params)");
+    const bool png = png_filter >= 0;
+    rfx_png_plan g = {};
+    if (png) {
+        if (p->format != RFX_EXPORT_U8_SRGB) return export_fail(c, RFX_EINVAL, fn, "format must be RFX_EXPORT_U8_SRGB");
+        if (png_filter > 4) return export_fail(c, RFX_EINVAL, fn, "filter must be 0 (adaptive) or 1..4 (None, Sub, Up, Paeth)");
+        if (!rfx_png_plan_for(c->tile_rows, c->W, p->channels, &g)) return export_fail(c, RFX_EINVAL, fn, "bad channel count");
+        if (bytes != (size_t)g.bound) return export_fail(c, RFX_EINVAL, fn, "bytes != rfx_png_bound(ctx, params)");
+    } else if (bytes != (size_t)t.bytes) return export_fail(c, RFX_EINVAL, fn, "bytes != rfx_export_bytes(ctx, params)");
+    const size_t stream_bytes = (size_t)t.bytes;  // K7's output
     // rfx_motion_blur's rule: a host-filled plane must have been uploaded (staged, bound); a slot a draw writes must at least exist
     const Slot &s = c->slots[p->source];
     const bool host_filled = p->source == RFX_TEX_DIRECT_LIGHT || p->source == RFX_TEX_EFFECT_INPUT;
@@ -1233,13 +1243,21 @@ static int export_enqueue(rfx_ctx *c, const rfx_export_params *p, void *host, si
         // ... and the order on the device: this encode overwrites the buffer that copy read
         HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_export_copied[b], 0));
     }
-    if (c->export_cap[b] < bytes) {  // (idle: its last copy has completed)
+    if (c->export_cap[b] < stream_bytes) {  // (idle: its last copy has completed)
         if (c->export_buf[b]) hipFree(c->export_buf[b]);
         c->export_buf[b] = nullptr;
         c->export_cap[b] = 0;
-        hipError_t e = hipMalloc(&c->export_buf[b], bytes);
+        hipError_t e = hipMalloc(&c->export_buf[b], stream_bytes);
         if (e != hipSuccess) return fail(c, RFX_ENOMEM, "rfx_stage_export: hipMalloc(staging buffer)", e);
-        c->export_cap[b] = bytes;
+        c->export_cap[b] = stream_bytes;
+    }
+    if (png && c->png_cap[b] < (size_t)g.device_bytes) {  // (idle by the same event: K8 and its copy ran behind that buffer's last encode)
+        if (c->png_buf[b]) hipFree(c->png_buf[b]);
+        c->png_buf[b] = nullptr;
+        c->png_cap[b] = 0;
+        hipError_t e = hipMalloc(&c->png_buf[b], (size_t)g.device_bytes);
+        if (e != hipSuccess) return fail(c, RFX_ENOMEM, "rfx_stage_png: hipMalloc(PNG buffer)", e);
+        c->png_cap[b] = (size_t)g.device_bytes;
     }
     K7Args A;
     A.src = (const uint4 *)s.ptr + (size_t)(c->tile_y0 - s.row0) * c->W;
@@ -1254,7 +1272,24 @@ static int export_enqueue(rfx_ctx *c, const rfx_export_params *p, void *host, si
     }
     HIPCHK(c, hipEventRecord(c->ev_export_encoded[b], c->stream));
     HIPCHK(c, hipStreamWaitEvent(c->download_stream, c->ev_export_encoded[b], 0));
-    HIPCHK(c, hipMemcpyAsync(host, c->export_buf[b], bytes, hipMemcpyDeviceToHost, c->download_stream));
+    const void *from = c->export_buf[b];
+    if (png) {
+        unsigned char *base = (unsigned char *)c->png_buf[b];
+        K8Args E;
+        E.src = (const unsigned char *)c->export_buf[b];
+        E.result = base;
+        E.slots = base + g.slots_at;
+        E.meta = (unsigned *)(base + g.meta_at);
+        E.offsets = (unsigned long long *)(base + g.offsets_at);
+        E.fragment_cap = g.bound - 32ull;
+        E.rows = g.rows; E.rowbytes = g.rowbytes; E.bpp = p->channels; E.filter = png_filter;
+        E.slot_stride = g.slot_stride;
+        ProfScope prof(c, RFX_PROF_K8, c->download_stream);
+        HIPCHK(c, rfx_launch_k8(E, c->download_stream));
+        from = base;
+    }
+    // (the whole bound crosses for a PNG: copying only fragment_bytes would need the host to wait for the header first — rfx.h)
+    HIPCHK(c, hipMemcpyAsync(host, from, bytes, hipMemcpyDeviceToHost, c->download_stream));
     HIPCHK(c, hipEventRecord(c->ev_export_copied[b], c->download_stream));
     c->exports = n + 1;
     if (ticket) *ticket = (int)(n + 1);
@@ -1279,6 +1314,26 @@ int rfx_export_wait(rfx_ctx *c, int ticket) {
 int rfx_export(rfx_ctx *c, const rfx_export_params *p, void *host, size_t bytes) {
     int ticket = 0;
     const int rc = export_enqueue(c, p, host, bytes, &ticket, "rfx_export");
+    return rc ? rc : rfx_export_wait(c, ticket);
+}
+
+// ---- K8: the same export as a finished PNG fragment (include/rfx.h "PNG fragments"; the kernels are in k8_png.h)
+size_t rfx_png_bound(const rfx_ctx *c, const rfx_export_params *p) {
+    rfx_png_plan g;
+    if (!c || !p || export_params_error(p) || p->format != RFX_EXPORT_U8_SRGB || !rfx_png_plan_for(c->tile_rows, c->W, p->channels, &g)) return 0;
+    return (size_t)g.bound;
+}
+
+int rfx_stage_png(rfx_ctx *c, const rfx_export_params *p, int filter, void *host, size_t bytes, int *ticket) {
+    if (!ticket) return RFX_EINVAL;
+    if (filter < 0 || filter > 4) return c ? export_fail(c, RFX_EINVAL, "rfx_stage_png", "filter must be 0 (adaptive) or 1..4 (None, Sub, Up, Paeth)") : RFX_EINVAL;
+    return export_enqueue(c, p, host, bytes, ticket, "rfx_stage_png", filter);
+}
+
+int rfx_png(rfx_ctx *c, const rfx_export_params *p, int filter, void *host, size_t bytes) {
+    if (filter < 0 || filter > 4) return c ? export_fail(c, RFX_EINVAL, "rfx_png", "filter must be 0 (adaptive) or 1..4 (None, Sub, Up, Paeth)") : RFX_EINVAL;
+    int ticket = 0;
+    const int rc = export_enqueue(c, p, host, bytes, &ticket, "rfx_png", filter);
     return rc ? rc : rfx_export_wait(c, ticket);
 }
 
@@ -1311,18 +1366,20 @@ int rfx_profile(rfx_ctx *c, int enable) {
     if (enable) {  // events of an earlier run may still be pending: let them execute before they are recorded again
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if (c->prep_stream) HIPCHK(c, hipStreamSynchronize(c->prep_stream));
+        if (c->download_stream) HIPCHK(c, hipStreamSynchronize(c->download_stream));  // (K8's pairs are recorded there)
         prof_recycle(c);
     }
     c->profiling = enable != 0;
     return RFX_OK;
 }
-int rfx_profile_read(rfx_ctx *c, float *ms_sum, int *launches) {
-    if (!c) return RFX_EINVAL;
+int rfx_profile_read(rfx_ctx *c, float *ms_sum, int *launches) { return rfx_profile_read_n(c, ms_sum, launches, RFX_PROF_COUNT); }
+int rfx_profile_read_n(rfx_ctx *c, float *ms_sum, int *launches, int entries) {
+    if (!c || entries < 0) return RFX_EINVAL;
     RFX_ENTER(c);
     // every pair is waited for on its own: the draws may have been enqueued on a stream that is no longer the current one (rfx_set_stream between
     // the draws and this call), which a synchronisation of today's streams would not cover; a pair that cannot be read is skipped, not fatal
-    float ms[RFX_PROF_COUNT] = {0};
-    int n[RFX_PROF_COUNT] = {0};
+    float ms[RFX_PROF_COUNT_ALL] = {0};
+    int n[RFX_PROF_COUNT_ALL] = {0};
     for (const rfx_ctx::ProfRec &r : c->prof_recs) {
         float t = 0.0f;
         if (hipEventSynchronize(r.b) != hipSuccess || hipEventElapsedTime(&t, r.a, r.b) != hipSuccess) {
@@ -1332,7 +1389,7 @@ int rfx_profile_read(rfx_ctx *c, float *ms_sum, int *launches) {
         ms[r.kind] += t;
         n[r.kind]++;
     }
-    for (int i = 0; i < RFX_PROF_COUNT; i++) {
+    for (int i = 0; i < RFX_PROF_COUNT_ALL && i < entries; i++) {
         if (ms_sum) ms_sum[i] = ms[i];
         if (launches) launches[i] = n[i];
     }

@@ -83,6 +83,9 @@ struct rfx_ctx {
     size_t export_cap[2] = {0, 0};
     hipEvent_t ev_export_encoded[2] = {nullptr, nullptr}, ev_export_copied[2] = {nullptr, nullptr};
     unsigned int exports = 0;  // tickets issued so far (ticket t = export t - 1)
+    // rfx_stage_png: K8's device buffers (result + scratch, rfx_launch.h rfx_png_plan), one per staging buffer; same owner, same growth rule
+    void *png_buf[2] = {nullptr, nullptr};
+    size_t png_cap[2] = {0, 0};
     // the peer-load history gather (rfx_peer.hip): this rank's flag block (fine-grained), the device table of every rank's plane and flag block
     // ([0, n) planes, [n, 2 n) flag blocks), what the last call's kernels reported ([0] status bits, [1] texels pulled), the mappings to close
     unsigned long long *peer_flags = nullptr;

@@ -103,6 +103,20 @@ struct K7Args {
 // format / channels / tonemap select the specialisation (hipErrorInvalidValue for a combination the export does not have); `blocks` from the plan
 hipError_t rfx_launch_k7(const K7Args &, int blocks, int format, int channels, int tonemap, hipStream_t);
 
+// K8 PNG encode (k8_png.h, built into k0_import.hip): K7's staged U8 stream -> the result buffer of include/rfx.h "PNG fragments", laid out by
+// rfx_launch.h rfx_png_plan_for.  Three launches on `stream`: one wave per scanline into the scratch slots, the scan, the gather.
+struct K8Args {
+    const unsigned char *src;     // K7's stream: `rows` rows of `rowbytes` bytes, row 0 = bottom
+    unsigned char *result;        // 32-byte header, then the fragment
+    unsigned char *slots;         // rows * slot_stride bytes of scratch: one whole chunk per scanline
+    unsigned *meta;               // rows * 4: chunk bytes, the two Adler partial sums, 0
+    unsigned long long *offsets;  // rows: where each chunk starts in the fragment
+    unsigned long long fragment_cap;  // bound - 32
+    int rows, rowbytes, bpp, filter;
+    unsigned slot_stride;
+};
+hipError_t rfx_launch_k8(const K8Args &, hipStream_t);
+
 struct K5Args {
     FrameDims dims;
     int y0, y1;

@@ -151,6 +151,33 @@ inline bool rfx_export_plan_for(int pixels, int format, int channels, rfx_export
     return true;
 }
 
+// ---------------------------------------------------------------- K8: the PNG fragment's buffers
+// rfx_png_bound and the layout of the device buffer behind one staged PNG: the result (header + fragment, `bound` bytes), one scratch slot
+// per scanline (a whole chunk in its stored form, rounded up to dwords, plus one dword: the bit window leaves as whole dwords), the per-scanline
+// sizes and Adler partial sums, the chunk offsets.  A pure function of its arguments.
+struct rfx_png_plan {
+    int rows, rowbytes, line_bytes, stored_blocks;  // line_bytes = n = 1 + W * channels
+    unsigned slot_stride;
+    unsigned long long bound, slots_at, meta_at, offsets_at, device_bytes;
+};
+inline bool rfx_png_plan_for(int rows, int W, int channels, rfx_png_plan *out) {
+    if (rows <= 0 || W <= 0 || (channels != 3 && channels != 4)) return false;
+    rfx_png_plan t;
+    t.rows = rows;
+    t.rowbytes = W * channels;
+    t.line_bytes = t.rowbytes + 1;
+    t.stored_blocks = (t.line_bytes + 65534) / 65535;
+    const unsigned long long chunk = 12ull + 5ull * (unsigned long long)t.stored_blocks + (unsigned long long)t.line_bytes;
+    t.bound = 32ull + (unsigned long long)rows * chunk;
+    t.slot_stride = (unsigned)((chunk + 3ull) & ~3ull) + 4u;
+    t.slots_at = (t.bound + 255ull) & ~255ull;
+    t.meta_at = t.slots_at + (((unsigned long long)rows * t.slot_stride + 255ull) & ~255ull);
+    t.offsets_at = t.meta_at + (((unsigned long long)rows * 16ull + 255ull) & ~255ull);
+    t.device_bytes = t.offsets_at + (unsigned long long)rows * 8ull;
+    *out = t;
+    return true;
+}
+
 // ---------------------------------------------------------------- shared by the launchers
 // Every view is the whole frame (a context that owns no row tile; a null pointer counts as whole): the kernels then skip row rebasing and
 // halo accounting.  TexView and TexViewW alike.

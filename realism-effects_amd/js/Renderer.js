@@ -62,6 +62,10 @@ const EXPORT_TONEMAP = { linear: 0, aces: 1 }
 // rfx_profile_read's kinds (include/rfx.h RFX_PROF_*), the index of profileRead()'s arrays
 const PROF_KINDS = ["k1_prepass", "k1_ssgi_march", "k2_temporal_reproject", "k3_poisson_denoise_pass0", "k3_poisson_denoise_passN", "k4_compose", "k5_final_compose",
 	"k6_motion_blur", "k6_motion_blur_reach", "k7_export"]
+// ... and the kinds behind RFX_PROF_COUNT (rfx_profile_read_n): profileRead()'s arrays have PROF_KINDS_ALL.length entries
+const PROF_KINDS_ALL = PROF_KINDS.concat(["k8_png"])
+// rfx_stage_png's `filter` (include/rfx.h "PNG fragments")
+const PNG_FILTERS = { adaptive: 0, none: 1, sub: 2, up: 3, paeth: 4 }
 
 // 128x128 RGBA8 blue-noise table: decoded once from the reference's PNG asset, already flipY'd
 // (tools/make_blue_noise_table.py; src/utils/BlueNoiseUtils.js:9-15)
@@ -158,6 +162,34 @@ class Renderer {
 		const ticket = addon.stageExport(this._h, this.exportParams(params), out)
 		if (!this._exports) this._exports = new Map()
 		this._exports.set(ticket, out) // the copy writes `out` until its ticket retires
+		for (const t of this._exports.keys()) if (t <= ticket - 2) this._exports.delete(t)
+		return ticket
+	}
+	// PNG fragments (rfx.h "PNG fragments"): the U8_SRGB export encoded on the device as the IDAT chunks of the tile rows.  params as for
+	// exportFrame (format is U8_SRGB); filter: "adaptive" | "none" | "sub" | "up" | "paeth" or 0..4.  io.pngFromFragments wraps the result.
+	pngParams(params) {
+		return this.exportParams(Object.assign({}, params, { format: EXPORT.U8_SRGB }))
+	}
+	pngFilter(filter) {
+		const f = filter === undefined ? 0 : typeof filter === "string" ? PNG_FILTERS[filter] : filter
+		if (f === undefined) throw new RangeError("png: unknown filter")
+		return f
+	}
+	pngBound(params) {
+		return addon.pngBound(this._h, this.pngParams(params || {}))
+	}
+	// -> the result buffer (Uint8Array of pngBound bytes: 32-byte header, fragment, slack); blocks (rfx_png)
+	png(params, filter, out) {
+		const p = this.pngParams(params)
+		if (!out) out = new Uint8Array(Math.max(1, addon.pngBound(this._h, p)))
+		addon.pngFrame(this._h, p, this.pngFilter(filter), out)
+		return out
+	}
+	// stageExport's contract with a PNG fragment as the payload; the ticket is one of the same sequence and exportWait retires it (rfx_stage_png)
+	stagePng(params, filter, out) {
+		const ticket = addon.stagePng(this._h, this.pngParams(params), this.pngFilter(filter), out)
+		if (!this._exports) this._exports = new Map()
+		this._exports.set(ticket, out)
 		for (const t of this._exports.keys()) if (t <= ticket - 2) this._exports.delete(t)
 		return ticket
 	}
@@ -291,4 +323,4 @@ class Renderer {
 	}
 }
 
-module.exports = { Renderer, TEX, FORMAT, EXPORT, EXPORT_ARRAY, PROF_KINDS, loadBlueNoiseTable, abiVersion: addon.abiVersion, constants: addon.constants }
+module.exports = { Renderer, TEX, FORMAT, EXPORT, EXPORT_ARRAY, PROF_KINDS, PROF_KINDS_ALL, PNG_FILTERS, loadBlueNoiseTable, abiVersion: addon.abiVersion, constants: addon.constants }

@@ -6,6 +6,7 @@
 // submit(source) is called once per frame AFTER the frame's draws are enqueued: it stages this frame's export, then waits for the PREVIOUS
 // frame's ticket — which has had this frame's draws to hide behind — and writes it.  At most two exports are in flight; finish() waits for
 // the last one.
+const fs = require("fs")
 const path = require("path")
 const { Renderer, EXPORT, EXPORT_ARRAY } = require("./Renderer")
 const io = require("./imageio")
@@ -13,7 +14,9 @@ const io = require("./imageio")
 const FRAME_FORMATS = { png: [EXPORT.U8_SRGB, 3], exr: [EXPORT.F16, 4], pfm: [EXPORT.F32, 3] }
 
 class FrameExporter {
-	// options: { format: "png" | "exr" | "pfm", tonemap: "aces" | "linear", exposure, hostAlloc, write }
+	// options: { format: "png" | "exr" | "pfm", tonemap: "aces" | "linear", exposure, hostAlloc, write,
+	//            encode: "host" (default) | "device" — png only: the frame leaves the device as a PNG fragment (rfx_stage_png, K8) and the host
+	//            only wraps and writes it; filter: the fragment's filter, "adaptive" by default }
 	constructor(renderer, dir, options) {
 		options = options || {}
 		this.renderer = renderer
@@ -24,7 +27,11 @@ class FrameExporter {
 		const tonemap = options.tonemap === undefined ? "aces" : options.tonemap
 		if (tonemap !== "aces" && tonemap !== "linear") throw new RangeError("tonemap: \"aces\" or \"linear\"")
 		this.params = { format: f[0], channels: f[1], tonemap: f[0] === EXPORT.U8_SRGB ? tonemap : 0, exposure: f[0] === EXPORT.U8_SRGB && options.exposure !== undefined ? options.exposure : 1 }
-		const n = renderer.width * renderer.tileRows * f[1]
+		this.encode = options.encode === undefined ? "host" : options.encode
+		if (this.encode !== "host" && this.encode !== "device") throw new RangeError("framesEncode: \"host\" or \"device\"")
+		if (this.encode === "device" && this.format !== "png") throw new RangeError("framesEncode \"device\" is for framesFormat \"png\" only")
+		this.filter = options.filter === undefined ? "adaptive" : options.filter
+		const n = this.encode === "device" ? renderer.pngBound(this.params) : renderer.width * renderer.tileRows * f[1]
 		const alloc = options.hostAlloc || Renderer.hostAlloc
 		this.buffers = [0, 1].map(() => alloc(EXPORT_ARRAY[f[0]], n))
 		this.write = options.write || ((index, data) => this.writeFrame(index, data))
@@ -34,14 +41,16 @@ class FrameExporter {
 	writeFrame(index, data) {
 		const file = path.join(this.dir, "frame_" + String(index).padStart(5, "0") + "." + this.format)
 		const w = this.renderer.width, h = this.renderer.tileRows
-		if (this.format === "png") io.writePNG(file, data, w, h, 3)
+		if (this.encode === "device") fs.writeFileSync(file, io.pngFromFragments(w, h, 3, [data]))
+		else if (this.format === "png") io.writePNG(file, data, w, h, 3)
 		else if (this.format === "exr") io.writeEXR(file, data, w, h, true)
 		else io.writePFM(file, data, w, h, 3)
 	}
 	submit(source) {
 		const index = this.count++
 		const buffer = this.buffers[index & 1]
-		const ticket = this.renderer.stageExport(Object.assign({ source }, this.params), buffer)
+		const ticket = this.encode === "device" ? this.renderer.stagePng(Object.assign({ source }, this.params), this.filter, buffer)
+			: this.renderer.stageExport(Object.assign({ source }, this.params), buffer)
 		this.retire()
 		this.pending = { ticket, index, buffer }
 	}

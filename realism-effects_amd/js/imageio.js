@@ -20,6 +20,43 @@ function crc32(buf) {
 	return (c ^ -1) >>> 0
 }
 
+function pngChunk(tag, payload) {
+	const body = Buffer.concat([Buffer.from(tag, "ascii"), payload])
+	const out = Buffer.alloc(8 + payload.length + 4)
+	out.writeUInt32BE(payload.length, 0)
+	body.copy(out, 4)
+	out.writeUInt32BE(crc32(body), 8 + payload.length)
+	return out
+}
+
+// The host's wrap of include/rfx.h "PNG fragments": `fragments` are the result buffers of Renderer.png / stagePng (32-byte header, then the IDAT
+// chunks of a tile's rows), TOP TILE FIRST -> the file's bytes (a Buffer).  The tiles' Adler-32s are combined, never recomputed.
+function pngFromFragments(width, height, channels, fragments) {
+	if (channels !== 3 && channels !== 4) throw new RangeError("PNG: 3 or 4 channels")
+	const ihdr = Buffer.alloc(13)
+	ihdr.writeUInt32BE(width, 0)
+	ihdr.writeUInt32BE(height, 4)
+	ihdr[8] = 8
+	ihdr[9] = channels === 3 ? 2 : 6
+	const parts = [Buffer.from([0x89, 0x50, 0x4e, 0x47, 0x0d, 0x0a, 0x1a, 0x0a]), pngChunk("IHDR", ihdr), pngChunk("IDAT", Buffer.from([0x78, 0x01]))]
+	let A = 1, B = 0, raw = 0
+	for (const f of fragments) {
+		const b = Buffer.from(f.buffer, f.byteOffset, f.byteLength)
+		const n = Number(b.readBigUInt64LE(0)), a2 = b.readUInt32LE(8), b2 = b.readUInt32LE(12), len2 = Number(b.readBigUInt64LE(16))
+		if (32 + n > b.length) throw new RangeError("PNG fragment: header says " + n + " bytes, buffer holds " + (b.length - 32))
+		parts.push(b.subarray(32, 32 + n))
+		B = (B + b2 + (len2 % 65521) * (A + 65520)) % 65521 // B1 + B2 + len2 * (A1 - 1)   (below 2^53: 65520 * 131040)
+		A = (A + a2 + 65520) % 65521 // A1 + A2 - 1
+		raw += len2
+	}
+	if (raw !== height * (1 + width * channels)) throw new RangeError("PNG fragments: " + raw + " filtered bytes do not make a " + width + " x " + height + " x " + channels + " image")
+	const tail = Buffer.alloc(6)
+	tail[0] = 0x03
+	tail.writeUInt32BE(((B << 16) | A) >>> 0, 2)
+	parts.push(pngChunk("IDAT", tail), pngChunk("IEND", Buffer.alloc(0)))
+	return Buffer.concat(parts)
+}
+
 // rgba8: Uint8Array(H*W*channels), row 0 = bottom
 function writePNG(file, rgb8, width, height, channels) {
 	const stride = width * channels
@@ -114,4 +151,4 @@ function writePFM(file, rgba, width, height, channels) {
 	fs.writeFileSync(file, Buffer.concat([Buffer.from("PF\n" + width + " " + height + "\n-1.0\n", "ascii"), body]))
 }
 
-module.exports = { writePNG, writeEXR, writePFM, tonemap }
+module.exports = { writePNG, pngFromFragments, writeEXR, writePFM, tonemap }

@@ -860,6 +860,45 @@ static napi_value export_into(napi_env env, napi_callback_info info, int staged)
 }
 static napi_value n_export_frame(napi_env env, napi_callback_info info) { return export_into(env, info, 0); }
 static napi_value n_stage_export(napi_env env, napi_callback_info info) { return export_into(env, info, 1); }
+/* pngBound(ctx, params) -> rfx_png_bound (0: bad params or a format other than U8_SRGB) */
+static napi_value n_png_bound(napi_env env, napi_callback_info info) {
+    napi_value a[2], out;
+    if (!get_args(env, info, 2, a)) return NULL;
+    rfx_ctx *c = get_ctx(env, a[0]);
+    if (!c) return NULL;
+    rfx_export_params p;
+    export_params(env, a[1], &p);
+    NAPI_CALL(env, napi_create_double(env, (double)rfx_png_bound(c, &p), &out));
+    return out;
+}
+/* pngFrame(ctx, params, filter, Uint8Array): rfx_png (blocks) / stagePng(ctx, params, filter, Uint8Array) -> ticket: rfx_stage_png — the result
+ * buffer of include/rfx.h "PNG fragments"; the array must stay alive until exportWait(ctx, ticket) has returned.  The library checks the byte count. */
+static napi_value png_into(napi_env env, napi_callback_info info, int staged) {
+    napi_value a[4], ab, out;
+    napi_typedarray_type type;
+    size_t len = 0, off = 0;
+    void *data = NULL;
+    int32_t filter = 0;
+    if (!get_args(env, info, 4, a)) return NULL;
+    rfx_ctx *c = get_ctx(env, a[0]);
+    if (!c || !get_int(env, a[2], &filter)) return NULL;
+    rfx_export_params p;
+    export_params(env, a[1], &p);
+    bool is_ta = false;
+    napi_is_typedarray(env, a[3], &is_ta);
+    if (!is_ta || napi_get_typedarray_info(env, a[3], &type, &len, &data, &ab, &off) != napi_ok || !data || type != napi_uint8_array) {
+        napi_throw_type_error(env, NULL, staged ? "stagePng: Uint8Array expected" : "pngFrame: Uint8Array expected");
+        return NULL;
+    }
+    int ticket = 0;
+    int rc = staged ? rfx_stage_png(c, &p, filter, data, len, &ticket) : rfx_png(c, &p, filter, data, len);
+    if (rc) return throw_rfx(env, c, staged ? "rfx_stage_png" : "rfx_png", rc);
+    if (!staged) return NULL;
+    NAPI_CALL(env, napi_create_int32(env, ticket, &out));
+    return out;
+}
+static napi_value n_png_frame(napi_env env, napi_callback_info info) { return png_into(env, info, 0); }
+static napi_value n_stage_png(napi_env env, napi_callback_info info) { return png_into(env, info, 1); }
 /* exportWait(ctx, ticket): rfx_export_wait */
 static napi_value n_export_wait(napi_env env, napi_callback_info info) {
     napi_value a[2];
@@ -929,7 +968,7 @@ static napi_value n_time_end(napi_env env, napi_callback_info info) {
     return out;
 }
 
-/* profile(ctx, enable) / profileRead(ctx) -> { ms: Float64Array(RFX_PROF_COUNT), launches: Int32Array-like array } (rfx_profile, rfx_profile_read) */
+/* profile(ctx, enable) / profileRead(ctx) -> { ms, launches }: arrays of RFX_PROF_COUNT_ALL entries (rfx_profile, rfx_profile_read_n) */
 static napi_value n_profile(napi_env env, napi_callback_info info) {
     napi_value a[2];
     if (!get_args(env, info, 2, a)) return NULL;
@@ -946,14 +985,14 @@ static napi_value n_profile_read(napi_env env, napi_callback_info info) {
     if (!get_args(env, info, 1, a)) return NULL;
     rfx_ctx *c = get_ctx(env, a[0]);
     if (!c) return NULL;
-    float ms[RFX_PROF_COUNT];
-    int n[RFX_PROF_COUNT];
-    int rc = rfx_profile_read(c, ms, n);
+    float ms[RFX_PROF_COUNT_ALL];
+    int n[RFX_PROF_COUNT_ALL];
+    int rc = rfx_profile_read_n(c, ms, n, RFX_PROF_COUNT_ALL);
     if (rc) return throw_rfx(env, c, "rfx_profile_read", rc);
     NAPI_CALL(env, napi_create_object(env, &out));
-    NAPI_CALL(env, napi_create_array_with_length(env, RFX_PROF_COUNT, &ms_arr));
-    NAPI_CALL(env, napi_create_array_with_length(env, RFX_PROF_COUNT, &n_arr));
-    for (uint32_t i = 0; i < RFX_PROF_COUNT; i++) {
+    NAPI_CALL(env, napi_create_array_with_length(env, RFX_PROF_COUNT_ALL, &ms_arr));
+    NAPI_CALL(env, napi_create_array_with_length(env, RFX_PROF_COUNT_ALL, &n_arr));
+    for (uint32_t i = 0; i < RFX_PROF_COUNT_ALL; i++) {
         napi_value v;
         NAPI_CALL(env, napi_create_double(env, ms[i], &v));
         NAPI_CALL(env, napi_set_element(env, ms_arr, i, v));
@@ -973,6 +1012,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"sync", n_sync}, {"setRowWindow", n_set_row_window}, {"setUvModel", n_set_uv_model}, {"cubeToEquirect", n_cube_to_equirect}, {"haloViolations", n_halo_violations}, {"timeBegin", n_time_begin}, {"timeEnd", n_time_end}, {"profile", n_profile}, {"profileRead", n_profile_read},
         {"stageUpload", n_stage_upload}, {"stageFlip", n_stage_flip}, {"hostAlloc", n_host_alloc},
         {"exportBytes", n_export_bytes}, {"exportFrame", n_export_frame}, {"stageExport", n_stage_export}, {"exportWait", n_export_wait}, {"constants", n_constants},
+        {"pngBound", n_png_bound}, {"pngFrame", n_png_frame}, {"stagePng", n_stage_png},
         {"splitRows", n_split_rows}, {"commUniqueId", n_comm_unique_id}, {"commInit", n_comm_init}, {"haloExchange", n_halo_exchange},
         {"allgatherHistory", n_allgather_history}, {"gatherHistoryRows", n_gather_history_rows}, {"commWait", n_comm_wait}, {"commDestroy", n_comm_destroy},
         {"peerExport", n_peer_export}, {"peerOpen", n_peer_open}, {"peerGatherHistory", n_peer_gather_history}, {"peerClose", n_peer_close}, {"ssgiHitMask", n_ssgi_hit_mask},

@@ -18,9 +18,13 @@ PEER_BLOB_BYTES = 192  # include/rfx.h RFX_PEER_BLOB_BYTES
 # rfx_profile_read's kinds (include/rfx.h RFX_PROF_*)
 PROF_KINDS = ("k1_prepass", "k1_ssgi_march", "k2_temporal_reproject", "k3_poisson_denoise_pass0", "k3_poisson_denoise_passN", "k4_compose", "k5_final_compose", "k6_motion_blur",
               "k6_motion_blur_reach", "k7_export")
+# ... and the kinds behind RFX_PROF_COUNT, read by rfx_profile_read_n (RFX_PROF_COUNT_ALL entries)
+PROF_KINDS_ALL = PROF_KINDS + ("k8_png",)
 EXPORT_F32, EXPORT_F16, EXPORT_U8_SRGB = 0, 1, 2  # rfx_export_params.format (include/rfx.h RFX_EXPORT_*)
 EXPORT_FORMATS = {"f32": EXPORT_F32, "f16": EXPORT_F16, "u8_srgb": EXPORT_U8_SRGB}
 EXPORT_DTYPE = {EXPORT_F32: np.float32, EXPORT_F16: np.float16, EXPORT_U8_SRGB: np.uint8}
+PNG_FILTERS = {"adaptive": 0, "none": 1, "sub": 2, "up": 3, "paeth": 4}  # rfx_stage_png's `filter`
+PNG_HEADER_BYTES = 32  # rfx_stage_png's result buffer: the fragment starts here
 EXPORT_TONEMAP = {"linear": 0, "aces": 1}  # rfx_export_params.tonemap: imageio.tonemap's operators
 RFX_UV_IDEAL, RFX_UV_REFERENCE_GL = 0, 1  # rfx_set_uv_model
 RFX_OK, RFX_EINVAL, RFX_ENOMEM, RFX_EDEVICE, RFX_ESTATE, RFX_EUNSUPPORTED = 0, -1, -2, -3, -4, -5
@@ -119,6 +123,7 @@ EXPORTS = [
     "rfx_host_alloc", "rfx_host_free", "rfx_stage_upload", "rfx_stage_flip", "rfx_split_rows", "rfx_comm_unique_id", "rfx_comm_init", "rfx_comm_destroy", "rfx_halo_exchange", "rfx_allgather_history", "rfx_gather_history_rows", "rfx_peer_export", "rfx_peer_open", "rfx_peer_gather_history", "rfx_peer_close", "rfx_ssgi_hit_rows", "rfx_ssgi_hit_mask", "rfx_ssgi_target_rows", "rfx_comm_wait",
     "rfx_motion_blur_reach_mask", "rfx_motion_blur_stage", "rfx_motion_blur_gather",
     "rfx_export_bytes", "rfx_export", "rfx_stage_export", "rfx_export_wait",
+    "rfx_png_bound", "rfx_stage_png", "rfx_png", "rfx_profile_read_n",
 ]
 
 _lib = None
@@ -191,6 +196,7 @@ def load_library(path: str | None = None) -> C.CDLL:
     lib.rfx_time_end.argtypes = [vp, C.POINTER(f)]
     lib.rfx_profile.argtypes = [vp, i]
     lib.rfx_profile_read.argtypes = [vp, C.POINTER(f), C.POINTER(i)]
+    lib.rfx_profile_read_n.argtypes = [vp, C.POINTER(f), C.POINTER(i), i]
     lib.rfx_host_alloc.argtypes = [C.c_size_t]
     lib.rfx_host_alloc.restype = vp
     lib.rfx_host_free.argtypes = [vp]
@@ -220,6 +226,10 @@ def load_library(path: str | None = None) -> C.CDLL:
     lib.rfx_export.argtypes = [vp, C.POINTER(ExportParams), vp, C.c_size_t]
     lib.rfx_stage_export.argtypes = [vp, C.POINTER(ExportParams), vp, C.c_size_t, C.POINTER(i)]
     lib.rfx_export_wait.argtypes = [vp, i]
+    lib.rfx_png_bound.argtypes = [vp, C.POINTER(ExportParams)]
+    lib.rfx_png_bound.restype = C.c_size_t
+    lib.rfx_stage_png.argtypes = [vp, C.POINTER(ExportParams), i, vp, C.c_size_t, C.POINTER(i)]
+    lib.rfx_png.argtypes = [vp, C.POINTER(ExportParams), i, vp, C.c_size_t]
     if lib.rfx_abi_version() != RFX_ABI_VERSION:
         raise ImportError("librfx_hip.so ABI version %d != %d" % (lib.rfx_abi_version(), RFX_ABI_VERSION))
     if path is None:

@@ -174,6 +174,44 @@ class Context:
         self._chk(self.lib.rfx_export_wait(self._h, int(ticket)), "rfx_export_wait")
         self.__dict__.get("_export_keepalive", {}).pop(int(ticket), None)
 
+    # -- PNG fragments (rfx.h "PNG fragments"): the same export, encoded on the device as the IDAT chunks of the tile rows
+    def png_bound(self, channels: int = 3) -> int:
+        """rfx_png_bound: the bytes of a result buffer (32-byte header + the fragment at its largest)"""
+        return int(self.lib.rfx_png_bound(self._h, C.byref(self.export_params(abi.TEX_FINAL, "u8_srgb", channels))))
+
+    def _png_out(self, p: abi.ExportParams, out, what):
+        n = int(self.lib.rfx_png_bound(self._h, C.byref(p)))
+        if out is None:
+            return np.empty(max(n, 1), np.uint8), n  # (bad params: any non-empty buffer will do, the library names the fault)
+        if not isinstance(out, np.ndarray) or not out.flags["C_CONTIGUOUS"] or not out.flags["WRITEABLE"]:
+            raise TypeError("%s: out must be a writeable C-contiguous ndarray" % what)
+        if n and (out.dtype != np.uint8 or out.nbytes != n):
+            raise ValueError("%s: out must hold %d bytes of uint8, got %d of %s" % (what, n, out.nbytes, out.dtype))
+        return out, n
+
+    def png(self, source: int, channels: int = 3, tonemap="linear", exposure: float = 1.0, filter=0, out=None) -> np.ndarray:
+        """rfx_png: the tile rows of `source` as a PNG fragment -> the result buffer (png_bound() bytes of uint8: header, fragment, slack);
+        imageio.png_from_fragments wraps one or more of them into a file.  `filter`: "adaptive" / "none" / "sub" / "up" / "paeth" or 0..4.
+        Blocks until the bytes are there."""
+        p = self.export_params(source, "u8_srgb", channels, tonemap, exposure)
+        out, n = self._png_out(p, out, "png")
+        self._chk(self.lib.rfx_png(self._h, C.byref(p), int(abi.PNG_FILTERS.get(filter, filter)), out.ctypes.data_as(C.c_void_p), n), "rfx_png")
+        return out
+
+    def stage_png(self, source: int, channels: int = 3, tonemap="linear", exposure: float = 1.0, filter=0, *, out: np.ndarray) -> int:
+        """rfx_stage_png: stage_export's contract with a PNG fragment as the payload; the ticket is one of the same sequence and
+        export_wait(ticket) retires it."""
+        p = self.export_params(source, "u8_srgb", channels, tonemap, exposure)
+        out, n = self._png_out(p, out, "stage_png")
+        t = C.c_int(0)
+        self._chk(self.lib.rfx_stage_png(self._h, C.byref(p), int(abi.PNG_FILTERS.get(filter, filter)), out.ctypes.data_as(C.c_void_p), n, C.byref(t)),
+                  "rfx_stage_png")
+        keep = self.__dict__.setdefault("_export_keepalive", {})
+        keep[t.value] = out
+        for old in [k for k in keep if k <= t.value - 2]:
+            del keep[old]
+        return int(t.value)
+
     def clear(self, tex: int):
         self._chk(self.lib.rfx_clear(self._h, tex), "rfx_clear")
 
@@ -432,11 +470,11 @@ class Context:
         self._chk(self.lib.rfx_profile(self._h, 1 if enable else 0), "rfx_profile")
 
     def profile_read(self):
-        """-> {kind: (summed ms, launches)} since the last profile(True), for the kinds that launched (abi.PROF_KINDS)"""
-        n = len(abi.PROF_KINDS)
+        """-> {kind: (summed ms, launches)} since the last profile(True), for the kinds that launched (abi.PROF_KINDS_ALL)"""
+        n = len(abi.PROF_KINDS_ALL)
         ms, cnt = (C.c_float * n)(), (C.c_int * n)()
-        self._chk(self.lib.rfx_profile_read(self._h, ms, cnt), "rfx_profile_read")
-        return {abi.PROF_KINDS[k]: (float(ms[k]), int(cnt[k])) for k in range(n) if cnt[k]}
+        self._chk(self.lib.rfx_profile_read_n(self._h, ms, cnt, n), "rfx_profile_read_n")
+        return {abi.PROF_KINDS_ALL[k]: (float(ms[k]), int(cnt[k])) for k in range(n) if cnt[k]}
 
     def halo_violations(self) -> int:
         return int(self.lib.rfx_halo_violations(self._h))

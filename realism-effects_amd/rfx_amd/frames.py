@@ -17,21 +17,33 @@ FRAME_FORMATS = {"png": ("u8_srgb", 3), "exr": ("f16", 4), "pfm": ("f32", 3)}
 
 
 class FrameExporter:
-    def __init__(self, ctx, directory: str, format: str = "png", tonemap: str = "aces", exposure: float = 1.0, write=None):
+    def __init__(self, ctx, directory: str, format: str = "png", tonemap: str = "aces", exposure: float = 1.0, write=None, encode: str = "host",
+                 filter="adaptive"):
         if format not in FRAME_FORMATS:
             raise ValueError('format: "png", "exr" or "pfm"')
+        if encode not in ("host", "device"):
+            raise ValueError('encode: "host" or "device"')
+        if encode == "device" and format != "png":
+            raise ValueError('encode "device" is for format "png" only')
+        self.encode, self.filter = encode, filter
         self.ctx, self.dir, self.format = ctx, directory, format
         self.kind, self.channels = FRAME_FORMATS[format]
         u8 = self.kind == "u8_srgb"
         self.tonemap, self.exposure = (tonemap if u8 else "linear"), (float(exposure) if u8 else 1.0)
         dtype = abi.EXPORT_DTYPE[abi.EXPORT_FORMATS[self.kind]]
-        self.buffers = [ctx.host_alloc((ctx.tile_rows, ctx.W, self.channels), dtype) for _ in range(2)]
+        if encode == "device":  # the payload is a PNG fragment (Context.stage_png): the host wraps it and writes
+            self.buffers = [ctx.host_alloc((ctx.png_bound(self.channels),), np.uint8) for _ in range(2)]
+        else:
+            self.buffers = [ctx.host_alloc((ctx.tile_rows, ctx.W, self.channels), dtype) for _ in range(2)]
         self.write = write or self.write_frame
         self.count, self.pending = 0, None
 
     def write_frame(self, index: int, data: np.ndarray):
         path = os.path.join(self.dir, "frame_%05d.%s" % (index, self.format))
-        if self.format == "png":
+        if self.encode == "device":
+            with open(path, "wb") as f:
+                f.write(imageio.png_from_fragments(self.ctx.W, self.ctx.tile_rows, self.channels, [data]))
+        elif self.format == "png":
             imageio.write_png(path, data)
         elif self.format == "exr":
             imageio.write_exr(path, {n: data[..., k] for k, n in enumerate("RGBA")}, compression="none", half=True)
@@ -41,7 +53,10 @@ class FrameExporter:
     def submit(self, source: int):
         index, self.count = self.count, self.count + 1
         buf = self.buffers[index & 1]
-        ticket = self.ctx.stage_export(source, self.kind, self.channels, self.tonemap, self.exposure, out=buf)
+        if self.encode == "device":
+            ticket = self.ctx.stage_png(source, self.channels, self.tonemap, self.exposure, self.filter, out=buf)
+        else:
+            ticket = self.ctx.stage_export(source, self.kind, self.channels, self.tonemap, self.exposure, out=buf)
         self._retire()
         self.pending = (ticket, index, buf)
 

@@ -123,6 +123,32 @@ def write_png(path: str, rgb8: np.ndarray):
         f.write(chunk(b"IEND", b""))
 
 
+def png_from_fragments(W: int, H: int, channels: int, fragments) -> bytes:
+    """The host's wrap of include/rfx.h "PNG fragments": `fragments` are the result buffers of Context.png / stage_png (32-byte header, then
+    the IDAT chunks of a tile's rows), TOP TILE FIRST -> the file's bytes.  The tiles' Adler-32s are combined, never recomputed."""
+    if channels not in (3, 4):
+        raise ValueError("PNG: 3 or 4 channels")
+
+    def chunk(tag, payload):
+        return struct.pack(">I", len(payload)) + tag + payload + struct.pack(">I", zlib.crc32(tag + payload) & 0xFFFFFFFF)
+
+    parts = [b"\x89PNG\r\n\x1a\n", chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 8, 2 if channels == 3 else 6, 0, 0, 0)), chunk(b"IDAT", b"\x78\x01")]
+    A, B, raw = 1, 0, 0
+    for f in fragments:
+        f = memoryview(np.ascontiguousarray(f).view(np.uint8).reshape(-1)) if isinstance(f, np.ndarray) else memoryview(f)
+        n, a2, b2, len2, _ = struct.unpack("<QIIQQ", f[:32])
+        if 32 + n > len(f):
+            raise ValueError("PNG fragment: header says %d bytes, buffer holds %d" % (n, len(f) - 32))
+        parts.append(bytes(f[32:32 + n]))
+        B = (B + b2 + len2 % 65521 * (A + 65520)) % 65521  # B1 + B2 + len2 * (A1 - 1)
+        A = (A + a2 + 65520) % 65521                        # A1 + A2 - 1
+        raw += len2
+    if raw != H * (1 + W * channels):
+        raise ValueError("PNG fragments: %d filtered bytes, a %d x %d x %d image has %d" % (raw, W, H, channels, H * (1 + W * channels)))
+    parts += [chunk(b"IDAT", b"\x03\x00" + struct.pack(">I", (B << 16) | A)), chunk(b"IEND", b"")]
+    return b"".join(parts)
+
+
 def read_png(path: str) -> np.ndarray:
     """8-bit RGB / RGBA, non-interlaced (what write_png writes and what the reference's blue-noise asset is) -> (H, W, C) uint8, row 0 = bottom."""
     with open(path, "rb") as f:

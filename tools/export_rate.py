@@ -4,10 +4,14 @@
     T0  no per-frame output
     T1  a blocking download(TEX_FINAL) every frame — RGBA32F, 133 MB, into a pinned buffer: the most a host could do before the export
     T2  stage_export U8_SRGB x 3 every frame into two alternating pinned buffers, export_wait one frame late (rfx_amd/frames.py's order)
+    T2h T2, and the waited frame goes through the host's imageio.write_png (zlib level 6, one thread) to /dev/null: FrameExporter(encode="host")
+    T3  stage_png (K8: the frame leaves the device as a PNG fragment), waited one frame late, wrapped by imageio.png_from_fragments and written
+        to /dev/null: FrameExporter(encode="device")
 
 each with the dump resident on the device and streamed (rfx_stage_upload / rfx_stage_flip from two pinned sets), in ONE process: every shape is
 warmed first, then three alternating rounds of the three modes, each a steady state of at least --seconds with a device synchronise at the end.
-K7's own time comes from rfx_profile, next to its bytes over the 8 TB/s HBM peak.
+(T2h takes seconds per frame at 4K: its loops are a few frames long.)  K7's and K8's own times come from rfx_profile, next to the bytes they
+read and write; the fragment's size per frame is recorded with K8's.
 
     python tools/export_rate.py [--out profiles/export/rates.json] [--seconds 1.0]
 """
@@ -26,13 +30,15 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "realism-effects_amd"))
 
-from rfx_amd import abi, effect  # noqa: E402
+from rfx_amd import abi, effect, imageio  # noqa: E402
 from rfx_amd.context import Context  # noqa: E402
 from rfx_amd.scene import synthetic_frame_parallel  # noqa: E402
 
 W, H = 3840, 2160
 HBM_PEAK = 8e12  # bytes / s
-MODES = ("T0", "T1", "T2")
+MODES = ("T0", "T1", "T2", "T2h", "T3")
+WARM = {"T2h": (1, 2)}   # frames of the two warming loops (default 5 and 20)
+MIN_FRAMES = {"T2h": 3}  # ... and the fewest of a measured loop (default 20)
 
 
 class Run:
@@ -54,6 +60,18 @@ class Run:
             self.sets.append(s)
         self.final = ctx.host_alloc((H, W, 4), np.float32)
         self.u8 = [ctx.host_alloc((H, W, 3), np.uint8) for _ in range(2)]
+        self.png = [ctx.host_alloc((ctx.png_bound(3),), np.uint8) for _ in range(2)]
+        self.fragment_bytes = []
+
+    def write(self, mode, buf):
+        """what the host does with a waited frame"""
+        if mode == "T2h":
+            imageio.write_png(os.devnull, buf)
+        elif mode == "T3":
+            data = imageio.png_from_fragments(W, H, 3, [buf])
+            self.fragment_bytes.append(len(data))
+            with open(os.devnull, "wb") as f:
+                f.write(data)
 
     def frame(self, f):
         self.scene.frame = f
@@ -80,15 +98,22 @@ class Run:
             self.frame(cur)
             if mode == "T1":
                 ctx._chk(ctx.lib.rfx_download(ctx._h, abi.TEX_FINAL, self.final.ctypes.data_as(C.c_void_p), 0, H), "rfx_download")
-            elif mode == "T2":
-                t = ctx.stage_export(abi.TEX_FINAL, "u8_srgb", 3, "aces", 1.0, out=self.u8[i & 1])
+            elif mode in ("T2", "T2h", "T3"):
+                if mode == "T3":
+                    buf = self.png[i & 1]
+                    t = ctx.stage_png(abi.TEX_FINAL, 3, "aces", 1.0, out=buf)
+                else:
+                    buf = self.u8[i & 1]
+                    t = ctx.stage_export(abi.TEX_FINAL, "u8_srgb", 3, "aces", 1.0, out=buf)
                 if pending is not None:
-                    ctx.export_wait(pending)
-                pending = t
+                    ctx.export_wait(pending[0])
+                    self.write(mode, pending[1])
+                pending = (t, buf)
             if streamed:
                 ctx.stage_flip()
         if pending is not None:
-            ctx.export_wait(pending)
+            ctx.export_wait(pending[0])
+            self.write(mode, pending[1])
         ctx.sync()
         return time.perf_counter() - t0
 
@@ -108,9 +133,10 @@ def main():
         key = "streamed" if streamed else "resident"
         n = {}
         for mode in MODES:  # warm every shape, and size its loop from the warm rate
-            run.loop(mode, streamed, 5)
-            per = run.loop(mode, streamed, 20) / 20
-            n[mode] = max(20, int(math.ceil(a.seconds / per)))
+            w0, w1 = WARM.get(mode, (5, 20))
+            run.loop(mode, streamed, w0)
+            per = run.loop(mode, streamed, w1) / w1
+            n[mode] = max(MIN_FRAMES.get(mode, 20), int(math.ceil(a.seconds / per)))
         rounds = []
         for r in range(3):
             row = {}
@@ -119,6 +145,7 @@ def main():
             row["T2_minus_T0"] = round(row["T2"] - row["T0"], 4)
             row["T1_minus_T0"] = round(row["T1"] - row["T0"], 4)
             row["T2_below_T1"] = row["T2"] < row["T1"]
+            row["T3_below_T2h"] = row["T3"] < row["T2h"]
             rounds.append(row)
             print(key, json.dumps(row), flush=True)
         result["rounds"][key] = rounds
@@ -138,6 +165,22 @@ def main():
                              frac_of_hbm_peak=round(moved / HBM_PEAK * 1e3 / (ms / launches), 4))
     result["T2_below_T1_every_round"] = all(r["T2_below_T1"] for rs in result["rounds"].values() for r in rs)
     print(json.dumps(result["k7_u8x3"]), flush=True)
+    # K8 alone (its three launches on the download stream), inside a loop of staged PNGs
+    for _ in range(5):
+        ctx.export_wait(ctx.stage_png(abi.TEX_FINAL, 3, "aces", 1.0, out=run.png[0]))
+    ctx.sync()
+    ctx.profile(True)
+    for i in range(20):
+        ctx.export_wait(ctx.stage_png(abi.TEX_FINAL, 3, "aces", 1.0, out=run.png[i & 1]))
+    ms, launches = ctx.profile_read()["k8_png"]
+    ctx.profile(False)
+    fragment = int(np.frombuffer(run.png[1][:8].tobytes(), np.uint64)[0])
+    stream = W * H * 3
+    result["k8_png_u8x3"] = dict(ms=round(ms / launches, 5), launches=launches, bytes_read=stream, bytes_written=fragment, fragment_of_raw=round(fragment / stream, 4),
+                                 bound=int(ctx.png_bound(3)), ms_at_hbm_peak=round((stream + fragment) / HBM_PEAK * 1e3, 5))
+    result["fragment_bytes_per_frame"] = dict(min=min(run.fragment_bytes), max=max(run.fragment_bytes), frames=len(run.fragment_bytes)) if run.fragment_bytes else None
+    result["T3_below_T2h_every_round"] = all(r["T3_below_T2h"] for rs in result["rounds"].values() for r in rs)
+    print(json.dumps(result["k8_png_u8x3"]), flush=True)
     ctx.close()
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
