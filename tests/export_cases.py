@@ -18,6 +18,15 @@ EXPOSURES = (1.0, 0.37, 2.5)
 FAMILIES = ("lognormal", "uniform_1p2", "uniform_0p01")
 SIZES = ((5, 3), (97, 55), (128, 72))  # (W, H): the tail only plus one group; odd width, pixels mod 4 = 3; more than one block per row of groups
 
+# (W, H) whose pixel counts 1, 2, 6, 1025, 1025 leave tails of 1, 2, 2, 1, 1 pixels behind the dword-store body; at 1025 pixels there are exactly
+# 256 groups, so the tail's lane is the only live lane of a second block (tests/test_gpu_export_edges.py and its CPU twin)
+EDGE_SIZES = ((1, 1), (2, 1), (3, 2), (205, 5), (41, 25))
+
+
+def edge_u8_cases():
+    """(W, H, channels, family, exposure, operator): both channel counts and both operators at every edge size"""
+    return [(w, h, ch, "lognormal", 1.0, op) for (w, h) in EDGE_SIZES for ch in (3, 4) for op in OPERATORS]
+
 
 def u8_cases():
     """(W, H, channels, family, exposure, operator): the whole matrix at 97x55 (channel count alternating), both channel counts and both
@@ -125,6 +134,14 @@ def f16_input(W, H):
     flat[:special.size] = special
     flat[-special.size:] = special[::-1]  # ... and in the tail's pixels
     return a
+
+
+def f16_edge_input(W, H):
+    """f16_input for any frame: one of fewer than 16 elements takes as many of the planted values as it holds"""
+    if W * H * 4 >= 32:
+        return f16_input(W, H)
+    a = f16_input(4, 2).reshape(-1)[:W * H * 4].copy()
+    return a.reshape(H, W, 4)
 
 
 def check_f16(got, linear, channels):

@@ -16,13 +16,14 @@ STORED_MAX = 65535
 
 # ---------------------------------------------------------------- filters
 def residuals(cur, up, bpp, ftype):
-    """cur, up: 1-D uint8 (up None = the tile's first scanline); -> the residual bytes of PNG filter type `ftype`"""
+    """cur, up: uint8 with the row's bytes along the last axis (up None = the tile's first scanline); -> the residual bytes of PNG filter
+    type `ftype`"""
     x = cur.astype(np.int32)
     a = np.zeros_like(x)
-    a[bpp:] = x[:-bpp]
+    a[..., bpp:] = x[..., :-bpp]
     b = np.zeros_like(x) if up is None else up.astype(np.int32)
     c = np.zeros_like(x)
-    c[bpp:] = b[:-bpp]
+    c[..., bpp:] = b[..., :-bpp]
     if ftype == 0:
         p = 0
     elif ftype == 1:
@@ -38,8 +39,10 @@ def residuals(cur, up, bpp, ftype):
 
 
 def cost(res):
+    """the sum of |residual as int8| along the last axis: an int for one row, an array for a stack of rows"""
     r = res.astype(np.int64)
-    return int(np.minimum(r, 256 - r).sum())
+    k = np.minimum(r, 256 - r).sum(-1)
+    return int(k) if k.ndim == 0 else k
 
 
 def choose_filter(cur, up, bpp, filt):
@@ -58,16 +61,24 @@ def choose_filter(cur, up, bpp, filt):
 
 
 def filtered_rows(tile, filt):
-    """tile: (rows, W, channels) uint8, row 0 = bottom -> the filtered scanlines, top first: a list of 1-D uint8 (type byte + residuals)"""
+    """tile: (rows, W, channels) uint8, row 0 = bottom -> the filtered scanlines, top first: a list of 1-D uint8 (type byte + residuals).
+    choose_filter's rule for every scanline, evaluated for all of them at once (a tile of 32768 rows would otherwise take its time)"""
     rows, W, ch = tile.shape
-    flat = np.ascontiguousarray(tile).reshape(rows, W * ch)
-    out = []
-    for s in range(rows):
-        r = rows - 1 - s
-        cur, up = flat[r], (flat[r + 1] if s else None)
-        t = choose_filter(cur, up, ch, filt)
-        out.append(np.concatenate([np.array([t], np.uint8), residuals(cur, up, ch, t)]))
-    return out
+    cur = np.ascontiguousarray(tile).reshape(rows, W * ch)[::-1]  # top first
+    up = np.concatenate([np.zeros_like(cur[:1]), cur[:-1]])  # (zeros above the first scanline: what residuals() takes for up = None)
+    if filt:
+        t = FILTER_TYPES[filt - 1]
+        types = np.full(rows, t)
+        types[0] = 1 if t in (2, 4) else t
+        wanted = sorted(set(types.tolist()))
+    else:
+        wanted = list(FILTER_TYPES)
+    res = {t: residuals(cur, up, ch, t) for t in wanted}
+    if not filt:
+        costs = np.stack([cost(res[t]) for t in FILTER_TYPES])
+        types = np.asarray(FILTER_TYPES)[np.argmin(costs, 0)]  # (argmin: the first of equal costs, so the lowest type number)
+        types[0] = FILTER_TYPES[int(np.argmin(costs[:2, 0]))]  # None / Sub only
+    return [np.concatenate([np.array([t], np.uint8), res[int(t)][s]]) for s, t in enumerate(types)]
 
 
 # ---------------------------------------------------------------- the code-length rule
@@ -234,9 +245,22 @@ def stored_payload(line):
     return out
 
 
+def min_compressed_bytes(n):
+    """A lower bound on form (a) for a line of n bytes, so that payload() need not build it for a line too short to gain (n <= 5).  17 bits
+    stand in front of the code-length code's lengths, and at least four of those follow (12).  The 258 code lengths hold at most n + 1 used
+    symbols, so at least 257 - n zeros; a token spells at most 138 of them and costs at least one bit.  The used symbols (two or more: a
+    byte and the end of block) take at least two tokens more.  Every literal and the end of block cost a bit or more (n + 1); then the
+    stored block's 3 bits, the padding, and its 4 bytes."""
+    zero_tokens = max(0, -(-(257 - n) // 138))
+    return (17 + 12 + zero_tokens + 2 + (n + 1) + 3 + 7) // 8 + 4
+
+
 def payload(line):
     """the smaller of the two forms; a tie goes to the compressed one"""
-    a, b = compressed_payload(line), stored_payload(line)
+    b = stored_payload(line)
+    if len(b) < min_compressed_bytes(len(line)):
+        return b
+    a = compressed_payload(line)
     return a if len(a) <= len(b) else b
 
 
