@@ -503,6 +503,41 @@ void rfx_host_free(void *);
 int rfx_stage_upload(rfx_ctx *, rfx_tex id, const void *host, int row0, int rows);
 int rfx_stage_flip(rfx_ctx *);
 
+/* ---- streamed AOV frames (additive to ABI 21: a host checks for the symbol): the importer's planes staged like a packed dump.
+ * rfx_stage_aov is rfx_stage_upload for an engine's UNPACKED attribute planes: every needed plane crosses PCIe once, on the upload stream,
+ * into a staging area the context owns (allocated on first use, grown when a later call needs more, freed by rfx_destroy; at most 76 bytes
+ * per band pixel), and one fused pack kernel behind the copies writes the BACK buffers of the dump's input slots, which rfx_stage_flip
+ * publishes as ever.  Nothing is allocated, freed or synchronised per call.  Host-pointer lifetime and back pressure are rfx_stage_upload's:
+ * a plane must stay valid and unchanged until the flip AFTER the one that publishes it has returned; pinned planes (rfx_host_alloc) make
+ * the copies asynchronous, a pageable plane is accepted and simply does not overlap.
+ * A plane is `rows` x width x channels tightly packed elements, row `row0` of the frame first (row 0 = bottom), float32 or IEEE half: an F16
+ * element means (float)half, which is exact, so a half plane costs two bytes per element on the bus and gives the texels the widened plane
+ * gives.  A plane that is not given has data == NULL.
+ *   DEPTH         always written: the widened depth plane (required).
+ *   GBUFFER       written iff diffuse, normal, roughness, metalness and emissive are ALL given (some of them: RFX_EINVAL): the texels
+ *                 rfx_pack_gbuffer writes for those floats with the depth plane as coverage.  A 3-channel diffuse has alpha 1.
+ *   VELOCITY      written iff velocity is given (normal is then required): rfx_pack_velocity's texels.
+ *   DIRECT_LIGHT  written iff direct is given: the widened rgb(a); a 3-channel plane has alpha 1.
+ * A slot that is not written keeps what rfx_stage_upload staged for it: the two forms mix within one batch.  NaN payloads are not specified.
+ * Rows: the band must lie inside the rows DEPTH holds (the whole frame, on every context); each written slot receives band ∩ the rows it
+ * holds, and a plane row no written row needs is not copied: rfx_aov_stage_bytes returns exactly the bytes the call copies host -> device
+ * (0 on bad parameters).  RFX_EINVAL: a bad type or channel count, no depth, a partial G-buffer set, velocity without normal, a band outside
+ * DEPTH's rows; RFX_ESTATE: a slot to be written is bound to an external buffer; RFX_ENOMEM: the staging area. */
+typedef enum rfx_plane_type { RFX_PLANE_F32 = 0, RFX_PLANE_F16 = 1 } rfx_plane_type;
+typedef struct rfx_plane { const void *data; int type; int channels; } rfx_plane;
+typedef struct rfx_aov_frame {
+    rfx_plane diffuse;    /* 3 or 4 (3: alpha = 1) */
+    rfx_plane normal;     /* 3, world space */
+    rfx_plane roughness;  /* 1 */
+    rfx_plane metalness;  /* 1 */
+    rfx_plane emissive;   /* 3 */
+    rfx_plane velocity;   /* 2 */
+    rfx_plane depth;      /* 1, required */
+    rfx_plane direct;     /* 3 or 4 (3: alpha = 1) */
+} rfx_aov_frame;
+size_t rfx_aov_stage_bytes(const rfx_ctx *, const rfx_aov_frame *, int row0, int rows);
+int rfx_stage_aov(rfx_ctx *, const rfx_aov_frame *, int row0, int rows);
+
 /* ---- row-tiled runs: the exchanges, one process per GPU, RCCL over xGMI.  RCCL is bound at run time (a
  * single-GPU host needs none; a process that already maps an RCCL — e.g. torch's — shares it).
  * Tiles: rank r of n owns rfx_split_rows(height, n, r) — boundaries on even rows, the last tile takes the remainder.  The exchanges run on a second stream of the context: each call orders itself AFTER all draws

@@ -79,6 +79,146 @@ __global__ __launch_bounds__(256) void k0_pack_velocity(K0Velocity A) {
     A.out[i] = o;
 }
 
+// ---------------------------------------------------------------- K0 AOV pack: the two packers above, fused, for rfx_stage_aov (include/rfx.h "streamed AOV frames")
+// One pass over the flat pixel run of a segment (rfx_launch.h rfx_aov_plan_for): 44 .. 76 B in per pixel, 52 B out.  Lane t owns the four
+// consecutive pixels [4 t, 4 t + 4), as K7's does: a float plane of C channels is C 16-byte loads, a half plane C 8-byte loads (C / 2 16-byte
+// loads for an even C), and every slot leaves as 16-byte stores — four G-buffer, four velocity and four direct-light texels and the four depth
+// values.  Normal and depth are read once for both packed texels.  The pixels mod 4 left over go to the lane after the last group, element by
+// element.  Which planes hold halves is uniform over a launch: SET 0 = none, SET 1 = every plane but velocity and depth (the 44 B/px frame of a
+// renderer that writes HALF colour AOVs), SET 2 = whatever half_mask says, decided by branches on the argument block.  Nothing is decided per
+// pixel but coverage.  The arithmetic is k0_pack_gbuffer's and k0_pack_velocity's own device functions on the widened values, and this file is
+// built uncontracted: the texels are theirs bit for bit.
+template <int SET>
+RFX_DEV bool k0_aov_half(const K0AovArgs &A, int i) {
+    if (SET == 0) return false;
+    if (SET == 1) return i != RFX_AOV_VELOCITY && i != RFX_AOV_DEPTH;
+    return ((A.half_mask >> i) & 1u) != 0u;
+}
+RFX_DEV void k0_aov_widen2(uint32_t w, float *v) { v[0] = rfx_h2f((unsigned short)(w & 0xffffu)); v[1] = rfx_h2f((unsigned short)(w >> 16)); }
+// the 4 * C elements of lane t's four pixels, widened
+template <int C>
+RFX_DEV void k0_aov_load4(const void *base, bool half, size_t t, float *v) {
+    if (!half) {
+        const uint4 *p = (const uint4 *)base + t * C;
+#pragma unroll
+        for (int i = 0; i < C; i++) {
+            const uint4 w = p[i];
+            v[4 * i] = __uint_as_float(w.x); v[4 * i + 1] = __uint_as_float(w.y); v[4 * i + 2] = __uint_as_float(w.z); v[4 * i + 3] = __uint_as_float(w.w);
+        }
+    } else if (C % 2 == 0) {
+        const uint4 *p = (const uint4 *)base + t * (C / 2);
+#pragma unroll
+        for (int i = 0; i < C / 2; i++) {
+            const uint4 w = p[i];
+            k0_aov_widen2(w.x, v + 8 * i); k0_aov_widen2(w.y, v + 8 * i + 2); k0_aov_widen2(w.z, v + 8 * i + 4); k0_aov_widen2(w.w, v + 8 * i + 6);
+        }
+    } else {
+        const uint2 *p = (const uint2 *)base + t * C;
+#pragma unroll
+        for (int i = 0; i < C; i++) {
+            const uint2 w = p[i];
+            k0_aov_widen2(w.x, v + 4 * i); k0_aov_widen2(w.y, v + 4 * i + 2);
+        }
+    }
+}
+// ... of an rgb(a) plane: always four channels out, alpha 1 where the plane has three
+RFX_DEV void k0_aov_load4_rgba(const void *base, bool half, int channels, size_t t, float *v) {
+    if (channels == 4) {
+        k0_aov_load4<4>(base, half, t, v);
+    } else {
+        float c[12];
+        k0_aov_load4<3>(base, half, t, c);
+#pragma unroll
+        for (int k = 0; k < 4; k++) { v[4 * k] = c[3 * k]; v[4 * k + 1] = c[3 * k + 1]; v[4 * k + 2] = c[3 * k + 2]; v[4 * k + 3] = 1.0f; }
+    }
+}
+RFX_DEV float k0_aov_elem(const void *base, bool half, size_t i) { return half ? rfx_h2f(((const unsigned short *)base)[i]) : ((const float *)base)[i]; }
+RFX_DEV uint4 k0_aov_gbuffer_texel(float depth, const float *rgba, uint32_t normal, float roughness, float metalness, const float *emissive) {
+    if (depth == 1.0f) return make_uint4(0u, 0u, 0u, 0x3f800000u);  // the clear colour (0, 0, 0, 1)
+    return make_uint4(k0_vec4_to_float(rgba[0], rgba[1], rgba[2], rgba[3]), normal, __float_as_uint(k0_color2float(roughness, metalness, 0.0f)),
+                      k0_rgbe8(make_float3(emissive[0], emissive[1], emissive[2])));
+}
+RFX_DEV uint4 k0_aov_velocity_texel(float depth, float vx, float vy, uint32_t normal) {
+    if (depth == 1.0f) return make_uint4(0u, 0u, 0u, 0x3f800000u);
+    return make_uint4(__float_as_uint(vx), __float_as_uint(vy), normal, __float_as_uint(depth));
+}
+template <int SET>
+__global__ __launch_bounds__(RFX_K0_AOV_BLOCK) void k0_aov_pack(K0AovArgs A) {
+    const int t = blockIdx.x * RFX_K0_AOV_BLOCK + threadIdx.x;
+    const bool packs = A.gbuffer || A.velocity;
+    if (t < A.groups) {
+        const size_t g = (size_t)t;
+        float d[4];
+        k0_aov_load4<1>(A.plane[RFX_AOV_DEPTH], k0_aov_half<SET>(A, RFX_AOV_DEPTH), g, d);
+        float *od = A.depth + g * 4;  // (dword-aligned only when the segment's first texel is not a multiple of four: four dwords, one store where the target allows)
+        od[0] = d[0]; od[1] = d[1]; od[2] = d[2]; od[3] = d[3];
+        uint32_t nrm[4] = {0u, 0u, 0u, 0u};
+        if (packs) {
+            float n[12];
+            k0_aov_load4<3>(A.plane[RFX_AOV_NORMAL], k0_aov_half<SET>(A, RFX_AOV_NORMAL), g, n);
+#pragma unroll
+            for (int k = 0; k < 4; k++) nrm[k] = k0_pack_normal(make_float3(n[3 * k], n[3 * k + 1], n[3 * k + 2]));
+        }
+        if (A.gbuffer) {
+            float c[16], r[4], m[4], e[12];
+            k0_aov_load4_rgba(A.plane[RFX_AOV_DIFFUSE], k0_aov_half<SET>(A, RFX_AOV_DIFFUSE), A.diffuse_ch, g, c);
+            k0_aov_load4<1>(A.plane[RFX_AOV_ROUGHNESS], k0_aov_half<SET>(A, RFX_AOV_ROUGHNESS), g, r);
+            k0_aov_load4<1>(A.plane[RFX_AOV_METALNESS], k0_aov_half<SET>(A, RFX_AOV_METALNESS), g, m);
+            k0_aov_load4<3>(A.plane[RFX_AOV_EMISSIVE], k0_aov_half<SET>(A, RFX_AOV_EMISSIVE), g, e);
+            uint4 *o = A.gbuffer + g * 4;
+#pragma unroll
+            for (int k = 0; k < 4; k++) o[k] = k0_aov_gbuffer_texel(d[k], c + 4 * k, nrm[k], r[k], m[k], e + 3 * k);
+        }
+        if (A.velocity) {
+            float v[8];
+            k0_aov_load4<2>(A.plane[RFX_AOV_VELOCITY], k0_aov_half<SET>(A, RFX_AOV_VELOCITY), g, v);
+            uint4 *o = A.velocity + g * 4;
+#pragma unroll
+            for (int k = 0; k < 4; k++) o[k] = k0_aov_velocity_texel(d[k], v[2 * k], v[2 * k + 1], nrm[k]);
+        }
+        if (A.direct) {
+            float q[16];
+            k0_aov_load4_rgba(A.plane[RFX_AOV_DIRECT], k0_aov_half<SET>(A, RFX_AOV_DIRECT), A.direct_ch, g, q);
+            uint4 *o = A.direct + g * 4;
+#pragma unroll
+            for (int k = 0; k < 4; k++) o[k] = make_uint4(__float_as_uint(q[4 * k]), __float_as_uint(q[4 * k + 1]), __float_as_uint(q[4 * k + 2]), __float_as_uint(q[4 * k + 3]));
+        }
+    } else if (t == A.groups) {
+        for (int k = 0; k < A.tail_pixels; k++) {
+            const size_t px = (size_t)A.tail_start + k;
+            const float d = k0_aov_elem(A.plane[RFX_AOV_DEPTH], k0_aov_half<SET>(A, RFX_AOV_DEPTH), px);
+            A.depth[px] = d;
+            uint32_t nrm = 0u;
+            if (packs) {
+                const bool h = k0_aov_half<SET>(A, RFX_AOV_NORMAL);
+                const void *p = A.plane[RFX_AOV_NORMAL];
+                nrm = k0_pack_normal(make_float3(k0_aov_elem(p, h, 3 * px), k0_aov_elem(p, h, 3 * px + 1), k0_aov_elem(p, h, 3 * px + 2)));
+            }
+            if (A.gbuffer) {
+                const bool hc = k0_aov_half<SET>(A, RFX_AOV_DIFFUSE), he = k0_aov_half<SET>(A, RFX_AOV_EMISSIVE);
+                const void *pc = A.plane[RFX_AOV_DIFFUSE], *pe = A.plane[RFX_AOV_EMISSIVE];
+                const size_t ci = px * A.diffuse_ch;
+                const float c[4] = {k0_aov_elem(pc, hc, ci), k0_aov_elem(pc, hc, ci + 1), k0_aov_elem(pc, hc, ci + 2), A.diffuse_ch == 4 ? k0_aov_elem(pc, hc, ci + 3) : 1.0f};
+                const float e[3] = {k0_aov_elem(pe, he, 3 * px), k0_aov_elem(pe, he, 3 * px + 1), k0_aov_elem(pe, he, 3 * px + 2)};
+                A.gbuffer[px] = k0_aov_gbuffer_texel(d, c, nrm, k0_aov_elem(A.plane[RFX_AOV_ROUGHNESS], k0_aov_half<SET>(A, RFX_AOV_ROUGHNESS), px),
+                                                     k0_aov_elem(A.plane[RFX_AOV_METALNESS], k0_aov_half<SET>(A, RFX_AOV_METALNESS), px), e);
+            }
+            if (A.velocity) {
+                const bool h = k0_aov_half<SET>(A, RFX_AOV_VELOCITY);
+                const void *p = A.plane[RFX_AOV_VELOCITY];
+                A.velocity[px] = k0_aov_velocity_texel(d, k0_aov_elem(p, h, 2 * px), k0_aov_elem(p, h, 2 * px + 1), nrm);
+            }
+            if (A.direct) {
+                const bool h = k0_aov_half<SET>(A, RFX_AOV_DIRECT);
+                const void *p = A.plane[RFX_AOV_DIRECT];
+                const size_t qi = px * A.direct_ch;
+                A.direct[px] = make_uint4(__float_as_uint(k0_aov_elem(p, h, qi)), __float_as_uint(k0_aov_elem(p, h, qi + 1)), __float_as_uint(k0_aov_elem(p, h, qi + 2)),
+                                          __float_as_uint(A.direct_ch == 4 ? k0_aov_elem(p, h, qi + 3) : 1.0f));
+            }
+        }
+    }
+}
+
 // ---------------------------------------------------------------- CubeToEquirectEnvPass (src/ssgi/pass/CubeToEquirectEnvPass.js:21-42)
 // One `textureCube(cubeMap, dir)` per texel of the equirectangular render target, with the lookup rules of the oracle's GL (measured
 // bit-exact on every interior lookup, oracle/glref/probes/probe_cube.py): major axis by >= in x, y, z order,
@@ -386,6 +526,17 @@ hipError_t rfx_launch_pack_gbuffer(int W, int rows, const float *diffuse, const 
     K0GBuffer A = {W, rows, diffuse, normal, roughness, metalness, emissive, depth, (uint4 *)out};
     dim3 block(64, 4), grid((W + 63) / 64, (rows + 3) / 4);
     hipLaunchKernelGGL(k0_pack_gbuffer, grid, block, 0, stream, A);
+    return hipGetLastError();
+}
+// the three specialisations: no half plane, the typed set (every plane the segment reads but velocity and depth), any other mix
+hipError_t rfx_launch_k0_aov(const K0AovArgs &A, int blocks, hipStream_t stream) {
+    if (!A.plane[RFX_AOV_DEPTH] || !A.depth || blocks <= 0) return hipErrorInvalidValue;
+    unsigned int given = 0;
+    for (int i = 0; i < RFX_AOV_PLANES; i++) given |= A.plane[i] ? 1u << i : 0u;
+    const unsigned int halves = A.half_mask & given, typed = given & ~((1u << RFX_AOV_VELOCITY) | (1u << RFX_AOV_DEPTH));
+    if (halves == 0u) hipLaunchKernelGGL(k0_aov_pack<0>, dim3(blocks), dim3(RFX_K0_AOV_BLOCK), 0, stream, A);
+    else if (halves == typed) hipLaunchKernelGGL(k0_aov_pack<1>, dim3(blocks), dim3(RFX_K0_AOV_BLOCK), 0, stream, A);
+    else hipLaunchKernelGGL(k0_aov_pack<2>, dim3(blocks), dim3(RFX_K0_AOV_BLOCK), 0, stream, A);
     return hipGetLastError();
 }
 hipError_t rfx_launch_pack_velocity(int W, int rows, const float *velocity, const float *normal, const float *depth, void *out, hipStream_t stream) {

@@ -126,6 +126,7 @@ void rfx_destroy(rfx_ctx *c) {
         if (c->slots[i].owned && c->slots[i].ptr) hipFree(c->slots[i].ptr);
         if (c->slots[i].back) hipFree(c->slots[i].back);
     }
+    if (c->aov_stage) hipFree(c->aov_stage);
     for (hipEvent_t e : c->ev_batch)
         if (e) hipEventDestroy(e);
     if (c->ev_staged) hipEventDestroy(c->ev_staged);
@@ -270,6 +271,27 @@ void rfx_host_free(void *p) {
 
 static bool is_dump_input(int id) { return id == RFX_TEX_DEPTH || id == RFX_TEX_GBUFFER || id == RFX_TEX_VELOCITY || id == RFX_TEX_DIRECT_LIGHT; }
 
+// the upload stream and the events that order it against the draws, created by the first staged call
+static int stage_streams(rfx_ctx *c) {
+    if (c->upload_stream) return RFX_OK;
+    hipError_t e = hipStreamCreateWithFlags(&c->upload_stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_staged, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_frame_done, hipEventDisableTiming);
+    for (hipEvent_t &b : c->ev_batch)
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&b, hipEventDisableTiming);
+    if (e != hipSuccess) return fail(c, RFX_EDEVICE, "rfx_stage_upload: stream/event creation", e);
+    // nothing of an earlier frame can still be reading a back buffer: there is none yet
+    HIPCHK(c, hipEventRecord(c->ev_frame_done, c->stream));
+    return RFX_OK;
+}
+// ... and a slot's back buffer
+static int stage_back(rfx_ctx *c, Slot &s) {
+    if (s.back) return RFX_OK;
+    hipError_t e = hipMalloc(&s.back, (size_t)s.rows * s.width * s.texel);
+    if (e != hipSuccess) return fail(c, RFX_ENOMEM, "hipMalloc(back buffer)", e);
+    return RFX_OK;
+}
+
 int rfx_stage_upload(rfx_ctx *c, rfx_tex id, const void *host, int row0, int rows) {
     if (!c || !host) return RFX_EINVAL;
     if (!is_dump_input(id)) return fail(c, RFX_EINVAL, "rfx_stage_upload: only the dump's input planes (depth, gbuffer, velocity, direct light) are double-buffered");
@@ -279,25 +301,89 @@ int rfx_stage_upload(rfx_ctx *c, rfx_tex id, const void *host, int row0, int row
     RFX_ENTER(c);
     Slot &s = c->slots[id];
     if (!s.owned) return fail(c, RFX_ESTATE, "rfx_stage_upload: the slot is bound to an external buffer");
-    const size_t pitch = (size_t)s.width * s.texel, bytes = (size_t)s.rows * pitch;
-    if (!c->upload_stream) {
-        hipError_t e = hipStreamCreateWithFlags(&c->upload_stream, hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_staged, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_frame_done, hipEventDisableTiming);
-        for (hipEvent_t &b : c->ev_batch)
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&b, hipEventDisableTiming);
-        if (e != hipSuccess) return fail(c, RFX_EDEVICE, "rfx_stage_upload: stream/event creation", e);
-        // nothing of an earlier frame can still be reading a back buffer: there is none yet
-        HIPCHK(c, hipEventRecord(c->ev_frame_done, c->stream));
-    }
-    if (!s.back) {
-        hipError_t e = hipMalloc(&s.back, bytes);
-        if (e != hipSuccess) return fail(c, RFX_ENOMEM, "hipMalloc(back buffer)", e);
-    }
+    const size_t pitch = (size_t)s.width * s.texel;
+    if ((rc = stage_streams(c))) return rc;
+    if ((rc = stage_back(c, s))) return rc;
     // the buffer being filled was the FRONT buffer until the last flip: the draws that read it were enqueued before that flip
     HIPCHK(c, hipStreamWaitEvent(c->upload_stream, c->ev_frame_done, 0));
     HIPCHK(c, hipMemcpyAsync((char *)s.back + (size_t)(row0 - s.row0) * pitch, host, (size_t)rows * pitch, hipMemcpyHostToDevice, c->upload_stream));
     s.back_filled = true;
+    return RFX_OK;
+}
+
+// ---- streamed AOV frames (include/rfx.h): the planes of rfx_pack_gbuffer / rfx_pack_velocity / the depth and direct uploads, staged once on the
+// upload stream and packed by one fused kernel (k0_import.hip k0_aov_pack) into the back buffers rfx_stage_flip publishes
+static int export_fail(rfx_ctx *c, int code, const char *fn, const char *what);  // ("fn: what" into the context's error text; defined with the export)
+static const rfx_plane *aov_planes(const rfx_aov_frame *f) { return &f->diffuse; }  // eight rfx_plane in RFX_AOV_* order
+static const char *aov_plan(const rfx_ctx *c, const rfx_aov_frame *f, int row0, int rows, rfx_aov_plan *t) {
+    static_assert(sizeof(rfx_aov_frame) == RFX_AOV_PLANES * sizeof(rfx_plane), "rfx_aov_frame is eight planes");
+    int type[RFX_AOV_PLANES], channels[RFX_AOV_PLANES];
+    for (int i = 0; i < RFX_AOV_PLANES; i++) {
+        const rfx_plane &p = aov_planes(f)[i];
+        type[i] = p.type;
+        channels[i] = p.data ? p.channels : 0;
+        if (p.data && p.channels <= 0) return "a plane's channel count";
+    }
+    const Slot &g = c->slots[RFX_TEX_GBUFFER];  // (VELOCITY and DIRECT_LIGHT hold the same rows)
+    return rfx_aov_plan_for(c->W, c->H, g.row0, g.rows, type, channels, row0, rows, t);
+}
+
+size_t rfx_aov_stage_bytes(const rfx_ctx *c, const rfx_aov_frame *f, int row0, int rows) {
+    rfx_aov_plan t;
+    if (!c || !f || aov_plan(c, f, row0, rows, &t)) return 0;
+    return (size_t)t.copy_bytes;
+}
+
+int rfx_stage_aov(rfx_ctx *c, const rfx_aov_frame *f, int row0, int rows) {
+    if (!c || !f) return RFX_EINVAL;
+    RFX_ENTER(c);
+    rfx_aov_plan t;
+    if (const char *bad = aov_plan(c, f, row0, rows, &t)) return export_fail(c, RFX_EINVAL, "rfx_stage_aov", bad);
+    const int ids[4] = {RFX_TEX_DEPTH, RFX_TEX_GBUFFER, RFX_TEX_VELOCITY, RFX_TEX_DIRECT_LIGHT};
+    const bool writes[4] = {true, t.write_gbuffer != 0, t.write_velocity != 0, t.write_direct != 0};
+    int rc;
+    for (int k = 0; k < 4; k++) {  // every check before anything is enqueued
+        if (!writes[k]) continue;
+        if ((rc = ensure(c, ids[k]))) return rc;
+        if (!c->slots[ids[k]].owned) return export_fail(c, RFX_ESTATE, "rfx_stage_aov", "a slot to be written is bound to an external buffer");
+    }
+    if ((rc = stage_streams(c))) return rc;
+    for (int k = 0; k < 4; k++)
+        if (writes[k] && (rc = stage_back(c, c->slots[ids[k]]))) return rc;
+    if (c->aov_stage_cap < (size_t)t.stage_bytes) {
+        // (the one wait of this path, paid when the area grows: an earlier call's kernel may still be reading the area that goes)
+        if (c->aov_stage) { HIPCHK(c, hipStreamSynchronize(c->upload_stream)); hipFree(c->aov_stage); }
+        c->aov_stage = nullptr;
+        c->aov_stage_cap = 0;
+        hipError_t e = hipMalloc(&c->aov_stage, (size_t)t.stage_bytes);
+        if (e != hipSuccess) return fail(c, RFX_ENOMEM, "rfx_stage_aov: hipMalloc(staging area)", e);
+        c->aov_stage_cap = (size_t)t.stage_bytes;
+    }
+    // rfx_stage_upload's order: the back buffers were the front buffers until the last flip
+    HIPCHK(c, hipStreamWaitEvent(c->upload_stream, c->ev_frame_done, 0));
+    for (int k = 0; k < t.nseg; k++) {
+        const rfx_aov_segment &g = t.seg[k];
+        K0AovArgs A = {};
+        for (int i = 0; i < RFX_AOV_PLANES; i++) {
+            if (g.offset[i] == ~0ull) continue;
+            const rfx_plane &p = aov_planes(f)[i];
+            const size_t texel = (size_t)p.channels * t.elem_bytes[i];
+            void *dev = (char *)c->aov_stage + g.offset[i];
+            HIPCHK(c, hipMemcpyAsync(dev, (const char *)p.data + (size_t)(g.row0 - row0) * c->W * texel, (size_t)g.pixels * texel, hipMemcpyHostToDevice, c->upload_stream));
+            A.plane[i] = dev;
+            if (p.type == RFX_PLANE_F16) A.half_mask |= 1u << i;
+        }
+        A.diffuse_ch = f->diffuse.channels; A.direct_ch = f->direct.channels;
+        const auto first = [&](int id) { const Slot &s = c->slots[id]; return (char *)s.back + (size_t)(g.row0 - s.row0) * s.width * s.texel; };
+        A.depth = (float *)first(RFX_TEX_DEPTH);
+        if (g.full && t.write_gbuffer) A.gbuffer = (uint4 *)first(RFX_TEX_GBUFFER);
+        if (g.full && t.write_velocity) A.velocity = (uint4 *)first(RFX_TEX_VELOCITY);
+        if (g.full && t.write_direct) A.direct = (uint4 *)first(RFX_TEX_DIRECT_LIGHT);
+        A.groups = g.groups; A.tail_start = g.tail_start; A.tail_pixels = g.tail_pixels;
+        HIPCHK(c, rfx_launch_k0_aov(A, g.blocks, c->upload_stream));
+    }
+    for (int k = 0; k < 4; k++)
+        if (writes[k]) c->slots[ids[k]].back_filled = true;
     return RFX_OK;
 }
 
@@ -797,6 +883,9 @@ int rfx_internal_scaled_rows(int W, int H, int Hs, int uv_model, int y0, int y1,
 }
 int rfx_internal_export_plan(int pixels, int format, int channels, struct rfx_export_plan *out) {
     return rfx_export_plan_for(pixels, format, channels, out) ? RFX_OK : RFX_EINVAL;
+}
+int rfx_internal_aov_plan(int W, int H, int held_row0, int held_rows, const int *type, const int *channels, int row0, int rows, struct rfx_aov_plan *out) {
+    return rfx_aov_plan_for(W, H, held_row0, held_rows, type, channels, row0, rows, out) ? RFX_EINVAL : RFX_OK;
 }
 int rfx_internal_k3_tile(int W, int H, float radius, int inputIsTemporal, int textureCount, struct rfx_k3_tile_plan *out) {
     *out = rfx_k3_tile((float)W, (float)H, radius, inputIsTemporal != 0, textureCount);

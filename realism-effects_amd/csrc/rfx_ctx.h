@@ -76,6 +76,11 @@ struct rfx_ctx {
     hipEvent_t ev_staged = nullptr, ev_frame_done = nullptr;
     hipEvent_t ev_batch[2] = {nullptr, nullptr};  // the copies published by the last two flips (recorded on upload_stream)
     unsigned int flips = 0;
+    // rfx_stage_aov: the staging area the planes of an AOV frame are copied into on the upload stream and its pack kernel reads (rfx_launch.h
+    // rfx_aov_plan).  One is enough: the stream is in order, the next call's copies queue behind this call's kernel.  Grown on demand; neither a
+    // texture slot nor checkpoint state
+    void *aov_stage = nullptr;
+    size_t aov_stage_cap = 0;
     // streamed export (rfx_stage_export): a fourth stream for the device-to-host copies, two device staging buffers the encodes alternate
     // between (export n uses buffer n & 1), and per buffer the event behind its last encode (draw stream) and its last copy (download stream)
     hipStream_t download_stream = nullptr;
@@ -119,6 +124,8 @@ extern "C" int rfx_internal_blur_reach_enqueue(rfx_ctx *c, const rfx_motion_blur
 extern "C" int rfx_internal_k1_table(int W, int H, struct rfx_k1_table_plan *out);
 extern "C" int rfx_internal_scaled_rows(int W, int H, int Hs, int uv_model, int y0, int y1, int apron, int *j0, int *j1);
 extern "C" int rfx_internal_export_plan(int pixels, int format, int channels, struct rfx_export_plan *out);
+// (held_row0, held_rows: the rows GBUFFER / VELOCITY / DIRECT_LIGHT hold; type, channels: eight entries in rfx_aov_frame's order, channels 0 = not given)
+extern "C" int rfx_internal_aov_plan(int W, int H, int held_row0, int held_rows, const int *type, const int *channels, int row0, int rows, struct rfx_aov_plan *out);
 extern "C" int rfx_internal_k3_tile(int W, int H, float radius, int inputIsTemporal, int textureCount, struct rfx_k3_tile_plan *out);
 
 extern thread_local std::string g_create_err;

@@ -89,6 +89,17 @@ struct K4Args {
 hipError_t rfx_launch_pack_gbuffer(int W, int rows, const float *diffuse, const float *normal, const float *roughness, const float *metalness,
                                    const float *emissive, const float *depth, void *out, hipStream_t);
 hipError_t rfx_launch_pack_velocity(int W, int rows, const float *velocity, const float *normal, const float *depth, void *out, hipStream_t);
+// K0 AOV pack (k0_import.hip): one segment of rfx_stage_aov (rfx_launch.h rfx_aov_plan_for) — the staged planes of its flat pixel run -> the
+// segment's first texel of every slot it writes.  Planes in rfx_aov_frame's order (RFX_AOV_*); a null output is not written.
+struct K0AovArgs {
+    const void *plane[8];      // 256-byte-aligned staging pieces; null: not read
+    unsigned int half_mask;    // bit i: plane i holds IEEE halves
+    int diffuse_ch, direct_ch; // 3 or 4
+    uint4 *gbuffer, *velocity, *direct;
+    float *depth;
+    int groups, tail_start, tail_pixels;  // lanes [0, groups) own four pixels each; lane `groups` the tail
+};
+hipError_t rfx_launch_k0_aov(const K0AovArgs &, int blocks, hipStream_t);
 // CubeToEquirectEnvPass (k0_import.hip): six S x S RGBA32F faces -> a W x H RGBA32F equirectangular image
 hipError_t rfx_launch_cube_to_equirect(float4 *chain, int size, int levels, float4 *out, int W, int H, const UvPlanes &uv, hipStream_t);
 

@@ -1,7 +1,7 @@
 // rfx_launch.h — what a launch decides on the host before it launches: K1's table layout, a scaled tile's target rows, K3's tile geometry, the
 // "whole frame" test, the step from a run-time option to a template argument, and what is remembered per kernel and device.  Host code
 // (rfx_device.h comes in for UvPlanes and the two vUv expressions the kernels and the row plan share).  The plans are pure functions of their
-// arguments (no HIP call, no context): rfx_api.hip exports them as rfx_internal_k1_table / rfx_internal_k3_tile / rfx_internal_scaled_rows / rfx_internal_export_plan and
+// arguments (no HIP call, no context): rfx_api.hip exports them as rfx_internal_k1_table / rfx_internal_k3_tile / rfx_internal_scaled_rows / rfx_internal_export_plan / rfx_internal_aov_plan and
 // the CPU tests call them as built (tests/test_k1_table_layout.py, tests/test_k3_tile_geometry.py, tests/test_resolution_scale_rows_cpu.py).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -176,6 +176,80 @@ inline bool rfx_png_plan_for(int rows, int W, int channels, rfx_png_plan *out) {
     t.device_bytes = t.offsets_at + (unsigned long long)rows * 8ull;
     *out = t;
     return true;
+}
+
+// ---------------------------------------------------------------- K0 AOV staging: rfx_stage_aov's rows, staging area and launches
+// The planes of an AOV frame (include/rfx.h rfx_aov_frame, in the struct's order) cover the band [row0, row0 + rows) of the frame.  DEPTH is held
+// whole, GBUFFER / VELOCITY / DIRECT_LIGHT hold the rows [held_row0, held_row0 + held_rows), so the band falls into at most three SEGMENTS of
+// whole rows: the rows below the held ones and the rows above them, where only depth is written (`full` 0), and the rows in between, where every
+// slot the frame names is written (`full` 1).  On a whole-frame context, or when the frame names no slot but DEPTH, there is one segment.  A
+// plane is copied for the rows of the segments that read it — depth for all of them, every other plane for the full one — each piece to a
+// 256-byte-aligned offset of the context's staging area, and every segment is one launch over its flat run of `pixels` = rows * W texels: lane
+// t < groups owns the pixels [4 t, 4 t + 4), the pixels [tail_start, pixels) go to the lane after the last group (rfx_export_plan_for's shape).
+// A pure function of its arguments, exported as rfx_internal_aov_plan (tests/test_stage_aov_cpu.py restates the row rule).
+enum { RFX_AOV_DIFFUSE, RFX_AOV_NORMAL, RFX_AOV_ROUGHNESS, RFX_AOV_METALNESS, RFX_AOV_EMISSIVE, RFX_AOV_VELOCITY, RFX_AOV_DEPTH, RFX_AOV_DIRECT, RFX_AOV_PLANES };
+constexpr int RFX_K0_AOV_BLOCK = 256;
+struct rfx_aov_segment {
+    int row0, rows, full;
+    int pixels, groups, blocks, tail_start, tail_pixels;
+    unsigned long long offset[RFX_AOV_PLANES];  // of the plane's rows of this segment in the staging area; ~0: the segment does not read the plane
+};
+struct rfx_aov_plan {
+    int nseg;
+    rfx_aov_segment seg[3];
+    int plane_row0[RFX_AOV_PLANES], plane_rows[RFX_AOV_PLANES];  // the frame rows of each plane that are copied (rows 0: none)
+    int elem_bytes[RFX_AOV_PLANES];                              // 4 / 2 / 0 (the plane is not given)
+    int write_gbuffer, write_velocity, write_direct;            // the slots the frame names besides DEPTH
+    unsigned long long copy_bytes, stage_bytes;                  // host -> device bytes (rfx_aov_stage_bytes); the staging area
+};
+// type / channels: per plane, channels 0 = the plane is not given.  0, or the RFX_EINVAL case in words.
+inline const char *rfx_aov_plan_for(int W, int H, int held_row0, int held_rows, const int *type, const int *channels, int row0, int rows, rfx_aov_plan *out) {
+    static const int want[RFX_AOV_PLANES] = {4, 3, 1, 1, 3, 2, 1, 4};
+    if (W <= 0 || H <= 0 || held_rows < 0) return "bad geometry";
+    rfx_aov_plan t = {};
+    for (int i = 0; i < RFX_AOV_PLANES; i++) {
+        if (!channels[i]) continue;
+        if (type[i] != RFX_PLANE_F32 && type[i] != RFX_PLANE_F16) return "a plane's type must be RFX_PLANE_F32 or RFX_PLANE_F16";
+        const bool rgb_or_rgba = i == RFX_AOV_DIFFUSE || i == RFX_AOV_DIRECT;
+        if (channels[i] != want[i] && !(rgb_or_rgba && channels[i] == 3)) return "a plane's channel count (diffuse, direct: 3 or 4; normal, emissive: 3; velocity: 2; the others: 1)";
+        t.elem_bytes[i] = type[i] == RFX_PLANE_F16 ? 2 : 4;
+    }
+    if (!channels[RFX_AOV_DEPTH]) return "the depth plane is required";
+    const bool normal = channels[RFX_AOV_NORMAL] != 0;
+    const int g = (channels[RFX_AOV_DIFFUSE] != 0) + (channels[RFX_AOV_ROUGHNESS] != 0) + (channels[RFX_AOV_METALNESS] != 0) + (channels[RFX_AOV_EMISSIVE] != 0);
+    t.write_gbuffer = g == 4 && normal;
+    t.write_velocity = channels[RFX_AOV_VELOCITY] != 0;
+    t.write_direct = channels[RFX_AOV_DIRECT] != 0;
+    if (t.write_velocity && !normal) return "a velocity plane needs the normal plane";
+    if (!t.write_gbuffer && (g != 0 || (normal && !t.write_velocity)))
+        return "diffuse, normal, roughness, metalness and emissive come together (all five write GBUFFER) or not at all";
+    if (rows <= 0 || row0 < 0 || row0 + rows > H) return "row band outside the rows DEPTH holds";
+    // band ∩ held rows
+    int a = row0 > held_row0 ? row0 : held_row0, b = row0 + rows < held_row0 + held_rows ? row0 + rows : held_row0 + held_rows;
+    if (!(t.write_gbuffer || t.write_velocity || t.write_direct) || b <= a) a = b = row0 + rows;  // (no full segment: the band is "below")
+    const int cut[4] = {row0, a, b, row0 + rows};
+    for (int k = 0; k < 3; k++) {
+        if (cut[k + 1] <= cut[k]) continue;
+        rfx_aov_segment &s = t.seg[t.nseg++];
+        s.row0 = cut[k]; s.rows = cut[k + 1] - cut[k]; s.full = k == 1;
+        s.pixels = s.rows * W;  // (< 2^28: rfx_create)
+        s.groups = s.pixels / 4;
+        s.tail_start = s.groups * 4;
+        s.tail_pixels = s.pixels - s.tail_start;
+        s.blocks = (s.groups + (s.tail_pixels ? 1 : 0) + RFX_K0_AOV_BLOCK - 1) / RFX_K0_AOV_BLOCK;
+        for (int i = 0; i < RFX_AOV_PLANES; i++) {
+            s.offset[i] = ~0ull;
+            if (!channels[i] || (i != RFX_AOV_DEPTH && !s.full)) continue;
+            s.offset[i] = t.stage_bytes;
+            const unsigned long long bytes = (unsigned long long)s.pixels * (unsigned long long)(channels[i] * t.elem_bytes[i]);
+            t.copy_bytes += bytes;
+            t.stage_bytes += (bytes + 255ull) & ~255ull;
+            if (!t.plane_rows[i]) t.plane_row0[i] = s.row0;
+            t.plane_rows[i] += s.rows;  // (depth's segments are adjacent: one run of rows)
+        }
+    }
+    *out = t;
+    return nullptr;
 }
 
 // ---------------------------------------------------------------- shared by the launchers

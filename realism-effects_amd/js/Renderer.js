@@ -123,7 +123,23 @@ class Renderer {
 	static hostAlloc(Ctor, length) {
 		return new Ctor(addon.hostAlloc(length * Ctor.BYTES_PER_ELEMENT))
 	}
+	// streamed AOV frames (rfx.h): the attribute planes of FRAME rows [row0, row0 + rows) (default: the whole frame) — Float32Array, or Uint16Array
+	// of IEEE half bits — are staged once and packed on the upload stream into the back buffers of DEPTH and of the slots the planes name
+	// { diffuse, normal, roughness, metalness, emissive, velocity, depth, direct }; stageFlip() publishes them
+	stageAov(planes, row0, rows) {
+		addon.stageAov(this._h, planes, row0 === undefined ? 0 : row0, rows === undefined ? this.height - (row0 || 0) : rows)
+		this._stagedAov = planes // keep the planes alive while they are in flight
+	}
+	aovStageBytes(planes, row0, rows) {
+		return addon.aovStageBytes(this._h, planes, row0 === undefined ? 0 : row0, rows === undefined ? this.height - (row0 || 0) : rows)
+	}
+	// a frame with packed planes, or — no `gbuffer` — with `aov` attribute planes
 	stageFrame(frame) {
+		if (!frame.gbuffer) {
+			this.stageAov(Object.assign({ depth: frame.depth, direct: frame.direct }, frame.aov))
+			this._staged = frame
+			return
+		}
 		for (const pt of [[TEX.DEPTH, frame.depth], [TEX.GBUFFER, frame.gbuffer], [TEX.VELOCITY, frame.velocity], [TEX.DIRECT_LIGHT, frame.direct]]) {
 			const held = this.heldRows(pt[0])
 			const per = FORMAT[pt[0]][1] * this.width

@@ -15,6 +15,7 @@
 // src/traa/TRAAEffect.js, src/utils/BlueNoiseUtils.js, src/utils/SceneUtils.js
 const { TEX } = require("./Renderer")
 const { buildImportance } = require("./envmap")
+const { floatPlane } = require("./dump")
 
 // src/ssgi/SSGIOptions.js:26-48
 const defaultSSGIOptions = {
@@ -210,9 +211,13 @@ class GBufferPass {
 		const f = this._scene.frame
 		renderer.uploadPlane(TEX.DEPTH, f.depth, f.static)
 		if (f.gbuffer) renderer.uploadPlane(TEX.GBUFFER, f.gbuffer, f.static)
-		else if (renderer._packedGBuffer !== f.aov) {
-			// an engine dump of UNPACKED whole-frame attribute planes: the device packs them (rfx_pack_gbuffer = the pass's fragment epilogue)
-			renderer.packGBuffer(Object.assign({ depth: f.depth }, f.aov), 0, renderer.height)
+		else if (f.static !== "resident" && renderer._packedGBuffer !== f.aov) {
+			// an engine dump of UNPACKED whole-frame attribute planes: the device packs them (rfx_pack_gbuffer = the pass's fragment epilogue);
+			// the half planes of a typed frame are widened first (a frame streamed through Renderer.stageAov is "resident": packed already)
+			const n = renderer.width * renderer.height
+			const a = f.aov
+			renderer.packGBuffer({ depth: f.depth, diffuse: floatPlane(a.diffuse, n, 4), normal: floatPlane(a.normal, n, 3), roughness: floatPlane(a.roughness, n, 1),
+				metalness: floatPlane(a.metalness, n, 1), emissive: floatPlane(a.emissive, n, 3) }, 0, renderer.height)
 			renderer._packedGBuffer = f.aov
 		}
 	}
@@ -236,8 +241,9 @@ class VelocityDepthNormalPass {
 	render(renderer) {
 		const f = this._scene.frame
 		if (f.velocity) renderer.uploadPlane(TEX.VELOCITY, f.velocity, f.static)
-		else if (renderer._packedVelocity !== f.aov) {
-			renderer.packVelocity({ velocity: f.aov.velocity, normal: f.aov.normal, depth: f.depth }, 0, renderer.height)
+		else if (f.static !== "resident" && renderer._packedVelocity !== f.aov) {
+			const n = renderer.width * renderer.height
+			renderer.packVelocity({ velocity: floatPlane(f.aov.velocity, n, 2), normal: floatPlane(f.aov.normal, n, 3), depth: f.depth }, 0, renderer.height)
 			renderer._packedVelocity = f.aov
 		}
 	}
@@ -931,8 +937,10 @@ class SSGIEffect {
 
 	update(renderer, inputBuffer) {
 		this.keepEnvMapUpdated(renderer)
-		const direct = inputBuffer || this._scene.frame.direct
-		renderer.uploadPlane(TEX.DIRECT_LIGHT, direct, this._scene.frame && this._scene.frame.static)
+		const isStatic = this._scene.frame && this._scene.frame.static
+		// (a typed frame's direct plane: halves, or rgb — widened for the synchronous upload; a streamed frame's is resident already)
+		const direct = inputBuffer || (isStatic === "resident" ? this._scene.frame.direct : floatPlane(this._scene.frame.direct, renderer.width * renderer.height, 4))
+		renderer.uploadPlane(TEX.DIRECT_LIGHT, direct, isStatic)
 		this.ssgiPass.render(renderer)
 		this.denoiser.render(renderer, inputBuffer)
 		// :400-417 the effect's own uniforms: inputTexture = the denoiser's texture, sceneTexture = the input buffer, fog from the scene

@@ -8,7 +8,8 @@
 // --png <file> [--tonemap '"aces"'|'"linear"' --exposure X] / --exr <file> / --pfm <file>: also write final.bin as an image (tone-mapped
 // 8-bit sRGB PNG; scene-linear float OpenEXR / PFM) — js/imageio.js.
 // --uvModel '"reference_gl"': the reference GL's own vUv instead of (i + 0.5) / n (parity runs against the reference on llvmpipe).
-// --stream true: the dumps cross PCIe on the context's upload stream from pinned planes, frame n+1 while frame n is drawn
+// --stream true: the dumps cross PCIe on the context's upload stream from pinned planes, frame n+1 while frame n is drawn (packed dumps through
+// rfx_stage_upload; unpacked and typed ones — aov_*.bin / aov_*.f16.bin — through rfx_stage_aov, which packs them on that stream)
 // (rfx_stage_upload / rfx_stage_flip); same outputs.
 // With --ranks N (N > 1): the frame is cut into N row tiles, ONE NODE PROCESS PER GPU (this process spawns them: rank r drives
 // device r), which exchange halo rows and the composed GI over RCCL through the C ABI (js/tiling.js); rank 0 creates the
@@ -219,7 +220,7 @@ if (opt.traa) {
 		const f = d === dumps[0] ? first : rfx.readDump(d)
 		scene.frame = f
 		Object.assign(camera, f.camera)
-		traa.update(renderer, { texture: { type: half ? rfx.HalfFloatType : rfx.FloatType }, width: f.width, height: f.height, data: f.direct })
+		traa.update(renderer, { texture: { type: half ? rfx.HalfFloatType : rfx.FloatType }, width: f.width, height: f.height, data: rfx.floatPlane(f.direct, f.width * f.height, 4) })
 		if (mb) {
 			mb.update(renderer, null, deltaTime)
 			mb.mainImage(renderer)
@@ -258,13 +259,27 @@ const effects = mb ? [effect, mb] : [effect]
 if (checkpoint.load) rfx.loadState(checkpoint.load, renderer, effects)
 openFrames()
 if (stream && !tiled) {
-	if (!first.gbuffer) throw new Error("--stream needs packed gbuffer.bin / velocity.bin dumps")
-	const n = first.width * first.height
-	const sets = [0, 1].map(() => ({ depth: rfx.Renderer.hostAlloc(Float32Array, n), gbuffer: rfx.Renderer.hostAlloc(Uint32Array, 4 * n),
-		velocity: rfx.Renderer.hostAlloc(Uint32Array, 4 * n), direct: rfx.Renderer.hostAlloc(Float32Array, 4 * n) }))
+	// two alternating sets of pinned planes shaped like the first dump's: packed planes, or — an unpacked / typed dump — its attribute planes
+	// as they are on disk (Float32Array, or Uint16Array of halves), which Renderer.stageFrame hands to rfx_stage_aov
+	const pinned = a => rfx.Renderer.hostAlloc(a.constructor, a.length)
+	const top = first.gbuffer ? ["depth", "gbuffer", "velocity", "direct"] : ["depth", "direct"]
+	const sets = [0, 1].map(() => {
+		const set = {}
+		for (const k of top) set[k] = pinned(first[k])
+		if (!first.gbuffer) {
+			set.aov = {}
+			for (const k of Object.keys(first.aov)) set.aov[k] = pinned(first.aov[k])
+		}
+		return set
+	})
+	const fill = (dst, src, what) => {
+		if (!src || src.constructor !== dst.constructor || src.length !== dst.length) throw new Error("--stream: " + what + " differs in type or size from the first dump's")
+		dst.set(src)
+	}
 	const load = (d, set) => { // disk -> pinned planes (a reader thread's job in a long run)
 		const f = d === dumps[0] ? first : rfx.readDump(d)
-		for (const k of ["depth", "gbuffer", "velocity", "direct"]) set[k].set(f[k])
+		for (const k of top) fill(set[k], f[k], d + " " + k)
+		if (set.aov) for (const k of Object.keys(set.aov)) fill(set.aov[k], f.aov && f.aov[k], d + " aov " + k)
 		return Object.assign({}, f, set, { static: "resident" })
 	}
 	let cur = load(dumps[0], sets[0])

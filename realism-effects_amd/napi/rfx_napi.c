@@ -243,6 +243,58 @@ static napi_value n_host_alloc(napi_env env, napi_callback_info info) {
     }
     return ab;
 }
+/* an AOV frame from {diffuse, normal, roughness, metalness, emissive, velocity, depth, direct}: a Float32Array is RFX_PLANE_F32, a Uint16Array
+ * (IEEE half bits) RFX_PLANE_F16; the channel count is the length over rows * width.  Returns 0 after throwing. */
+static int read_aov_frame(napi_env env, rfx_ctx *c, napi_value obj, int32_t rows, rfx_aov_frame *f) {
+    static const char *names[8] = {"diffuse", "normal", "roughness", "metalness", "emissive", "velocity", "depth", "direct"};
+    rfx_plane *planes = &f->diffuse;
+    int32_t W = 0;
+    rfx_get_geometry(c, &W, NULL, NULL, NULL, NULL);
+    const size_t n = rows > 0 ? (size_t)rows * (size_t)W : 0;
+    memset(f, 0, sizeof *f);
+    for (int i = 0; i < 8; i++) {
+        napi_value v;
+        bool has = false;
+        napi_valuetype vt = napi_undefined;
+        if (napi_has_named_property(env, obj, names[i], &has) == napi_ok && has && napi_get_named_property(env, obj, names[i], &v) == napi_ok) napi_typeof(env, v, &vt);
+        if (!has || vt == napi_null || vt == napi_undefined) continue;
+        napi_typedarray_type tt;
+        size_t len;
+        void *ptr;
+        if (napi_get_typedarray_info(env, v, &tt, &len, &ptr, NULL, NULL) != napi_ok || (tt != napi_float32_array && tt != napi_uint16_array)) {
+            napi_throw_type_error(env, NULL, "AOV plane: a Float32Array or a Uint16Array of half bits expected");
+            return 0;
+        }
+        if (n == 0 || len == 0 || len % n) {
+            napi_throw_range_error(env, NULL, "AOV plane: length is no multiple of rows * width");
+            return 0;
+        }
+        planes[i].data = ptr;
+        planes[i].type = tt == napi_uint16_array ? RFX_PLANE_F16 : RFX_PLANE_F32;
+        planes[i].channels = (int)(len / n);
+    }
+    return 1;
+}
+/* stageAov(ctx, planes, row0, rows): rfx_stage_aov (rfx.h "streamed AOV frames"); the arrays — ideally views of hostAlloc() memory — must stay
+ * alive and unchanged like stageUpload's.  aovStageBytes(ctx, planes, row0, rows) -> the bytes that call copies (0: it would be refused) */
+static napi_value aov_call(napi_env env, napi_callback_info info, int stage) {
+    napi_value a[4], out;
+    int32_t row0, rows;
+    rfx_aov_frame f;
+    if (!get_args(env, info, 4, a)) return NULL;
+    rfx_ctx *c = get_ctx(env, a[0]);
+    if (!c || !get_int(env, a[2], &row0) || !get_int(env, a[3], &rows)) return NULL;
+    if (!read_aov_frame(env, c, a[1], rows, &f)) return NULL;
+    if (!stage) {
+        NAPI_CALL(env, napi_create_double(env, (double)rfx_aov_stage_bytes(c, &f, row0, rows), &out));
+        return out;
+    }
+    int rc = rfx_stage_aov(c, &f, row0, rows);
+    if (rc) return throw_rfx(env, c, "rfx_stage_aov", rc);
+    return NULL;
+}
+static napi_value n_stage_aov(napi_env env, napi_callback_info info) { return aov_call(env, info, 1); }
+static napi_value n_aov_stage_bytes(napi_env env, napi_callback_info info) { return aov_call(env, info, 0); }
 static napi_value n_upload(napi_env env, napi_callback_info info) { return xfer(env, info, 1); }
 static napi_value n_download(napi_env env, napi_callback_info info) { return xfer(env, info, 0); }
 
@@ -1010,7 +1062,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"clear", n_clear}, {"setEnvironment", n_set_environment}, {"setEnvironmentImportance", n_set_environment_importance}, {"packGBuffer", n_pack_gbuffer}, {"packVelocity", n_pack_velocity}, {"ssgiMarch", n_ssgi}, {"ssgiTrace", n_ssgi_trace}, {"ssgiShade", n_ssgi_shade}, {"temporalReproject", n_temporal}, {"copyFramebuffer", n_copy_framebuffer}, {"poissonDenoise", n_denoise}, {"compose", n_compose}, {"finalCompose", n_final}, {"motionBlur", n_motion_blur},
         {"motionBlurStage", n_motion_blur_stage}, {"motionBlurReachMask", n_motion_blur_reach_mask}, {"motionBlurGather", n_motion_blur_gather},
         {"sync", n_sync}, {"setRowWindow", n_set_row_window}, {"setUvModel", n_set_uv_model}, {"cubeToEquirect", n_cube_to_equirect}, {"haloViolations", n_halo_violations}, {"timeBegin", n_time_begin}, {"timeEnd", n_time_end}, {"profile", n_profile}, {"profileRead", n_profile_read},
-        {"stageUpload", n_stage_upload}, {"stageFlip", n_stage_flip}, {"hostAlloc", n_host_alloc},
+        {"stageUpload", n_stage_upload}, {"stageFlip", n_stage_flip}, {"hostAlloc", n_host_alloc}, {"stageAov", n_stage_aov}, {"aovStageBytes", n_aov_stage_bytes},
         {"exportBytes", n_export_bytes}, {"exportFrame", n_export_frame}, {"stageExport", n_stage_export}, {"exportWait", n_export_wait}, {"constants", n_constants},
         {"pngBound", n_png_bound}, {"pngFrame", n_png_frame}, {"stagePng", n_stage_png},
         {"splitRows", n_split_rows}, {"commUniqueId", n_comm_unique_id}, {"commInit", n_comm_init}, {"haloExchange", n_halo_exchange},

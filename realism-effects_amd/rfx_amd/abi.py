@@ -101,6 +101,20 @@ class AovVelocity(C.Structure):
     _fields_ = [("velocity", FP), ("normal", FP), ("depth", FP)]
 
 
+PLANE_F32, PLANE_F16 = 0, 1  # rfx_plane.type (include/rfx.h RFX_PLANE_*)
+PLANE_TYPES = {np.dtype(np.float32): PLANE_F32, np.dtype(np.float16): PLANE_F16}
+AOV_PLANES = ("diffuse", "normal", "roughness", "metalness", "emissive", "velocity", "depth", "direct")  # rfx_aov_frame's fields, in order
+AOV_CHANNELS = {"diffuse": (3, 4), "normal": (3,), "roughness": (1,), "metalness": (1,), "emissive": (3,), "velocity": (2,), "depth": (1,), "direct": (3, 4)}
+
+
+class Plane(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("type", C.c_int32), ("channels", C.c_int32)]
+
+
+class AovFrame(C.Structure):
+    _fields_ = [(name, Plane) for name in AOV_PLANES]
+
+
 class FinalParams(C.Structure):
     _fields_ = [("camera", Camera), ("isDebug", C.c_int32), ("inputSource", C.c_int32), ("fogMode", C.c_int32), ("fogColor", C.c_float * 3), ("fogNear", C.c_float),
                 ("fogFar", C.c_float), ("fogDensity", C.c_float)]
@@ -124,6 +138,7 @@ EXPORTS = [
     "rfx_motion_blur_reach_mask", "rfx_motion_blur_stage", "rfx_motion_blur_gather",
     "rfx_export_bytes", "rfx_export", "rfx_stage_export", "rfx_export_wait",
     "rfx_png_bound", "rfx_stage_png", "rfx_png", "rfx_profile_read_n",
+    "rfx_aov_stage_bytes", "rfx_stage_aov",
 ]
 
 _lib = None
@@ -230,6 +245,9 @@ def load_library(path: str | None = None) -> C.CDLL:
     lib.rfx_png_bound.restype = C.c_size_t
     lib.rfx_stage_png.argtypes = [vp, C.POINTER(ExportParams), i, vp, C.c_size_t, C.POINTER(i)]
     lib.rfx_png.argtypes = [vp, C.POINTER(ExportParams), i, vp, C.c_size_t]
+    lib.rfx_aov_stage_bytes.argtypes = [vp, C.POINTER(AovFrame), i, i]
+    lib.rfx_aov_stage_bytes.restype = C.c_size_t
+    lib.rfx_stage_aov.argtypes = [vp, C.POINTER(AovFrame), i, i]
     if lib.rfx_abi_version() != RFX_ABI_VERSION:
         raise ImportError("librfx_hip.so ABI version %d != %d" % (lib.rfx_abi_version(), RFX_ABI_VERSION))
     if path is None:

@@ -114,10 +114,55 @@ class Context:
         self._chk(self.lib.rfx_stage_upload(self._h, tex, a.ctypes.data_as(C.c_void_p), row0, rows), "rfx_stage_upload")
 
     def stage_frame(self, frame):
+        """Stage a whole dumped frame: its packed planes, or — a frame with `aov` instead of `gbuffer` — its attribute planes (stage_aov)."""
+        if getattr(frame, "gbuffer", None) is None:
+            planes = dict(frame.aov)
+            planes["depth"] = frame.depth
+            if getattr(frame, "direct", None) is not None:
+                planes["direct"] = frame.direct
+            self.stage_aov(planes)
+            return
         for tex, plane in ((abi.TEX_DEPTH, frame.depth), (abi.TEX_GBUFFER, frame.gbuffer), (abi.TEX_VELOCITY, frame.velocity),
                            (abi.TEX_DIRECT_LIGHT, frame.direct)):
             r0, n = self.held_rows(tex)
             self.stage_upload(tex, plane[r0:r0 + n] if plane.shape[0] != n else plane, r0, n)
+
+    # -- streamed AOV frames (rfx.h "streamed AOV frames"): the importer's planes staged once and packed on the upload stream
+    def _aov_frame(self, planes: dict, row0, rows):
+        """-> (abi.AovFrame, row0, rows, the arrays it points into).  `planes`: name -> array of the band's rows; the type comes from the
+        dtype (float32 / float16), the channel count from the size."""
+        row0 = 0 if row0 is None else int(row0)
+        rows = self.H - row0 if rows is None else int(rows)
+        unknown = set(planes) - set(abi.AOV_PLANES)
+        if unknown:
+            raise ValueError("AOV frame: unknown planes %s" % sorted(unknown))
+        f, keep = abi.AovFrame(), []
+        texels = max(rows, 0) * self.W
+        for name in abi.AOV_PLANES:
+            a = planes.get(name)
+            if a is None:
+                continue
+            if not isinstance(a, np.ndarray) or a.dtype not in abi.PLANE_TYPES:
+                raise TypeError("AOV plane %s: a float32 or float16 ndarray, got %s" % (name, getattr(a, "dtype", type(a))))
+            a = a if a.flags["C_CONTIGUOUS"] else np.ascontiguousarray(a)
+            if texels == 0 or a.size % texels:
+                raise ValueError("AOV plane %s: %s does not cover %d rows of %d texels" % (name, a.shape, rows, self.W))
+            keep.append(a)
+            setattr(f, name, abi.Plane(a.ctypes.data, abi.PLANE_TYPES[a.dtype], a.size // texels))
+        return f, row0, rows, keep
+
+    def aov_stage_bytes(self, planes: dict, row0: int | None = None, rows: int | None = None) -> int:
+        """rfx_aov_stage_bytes: the bytes stage_aov(planes, row0, rows) copies host -> device (0: the library would refuse the frame)"""
+        f, row0, rows, _ = self._aov_frame(planes, row0, rows)
+        return int(self.lib.rfx_aov_stage_bytes(self._h, C.byref(f), row0, rows))
+
+    def stage_aov(self, planes: dict, row0: int | None = None, rows: int | None = None):
+        """rfx_stage_aov: the attribute planes of rows [row0, row0+rows) of the FRAME (default: all of it) -> the back buffers of DEPTH and of
+        the slots the planes name (GBUFFER: diffuse, normal, roughness, metalness, emissive; VELOCITY: velocity, normal; DIRECT_LIGHT: direct);
+        published by stage_flip().  host_alloc() planes make the copies asynchronous."""
+        f, row0, rows, keep = self._aov_frame(planes, row0, rows)
+        self.__dict__.setdefault("_staged_now", []).extend(keep)  # kept alive until the copies of this batch have executed
+        self._chk(self.lib.rfx_stage_aov(self._h, C.byref(f), row0, rows), "rfx_stage_aov")
 
     def stage_flip(self):
         self._chk(self.lib.rfx_stage_flip(self._h), "rfx_stage_flip")
@@ -238,7 +283,9 @@ class Context:
     # -- importer: engine-side attribute planes -> packed render targets, on the device
     @staticmethod
     def _plane(a, ch, rows, width):
-        a = np.ascontiguousarray(a, np.float32)
+        a = np.ascontiguousarray(a, np.float32)  # (a float16 plane of a typed frame is widened here: exact)
+        if ch == 4 and a.size == rows * width * 3:  # an rgb diffuse plane: alpha 1 (imageio.exr_to_dump_planes' rule)
+            a = np.concatenate([a.reshape(rows, width, 3), np.ones((rows, width, 1), np.float32)], -1)
         if a.size != rows * width * ch:
             raise ValueError("AOV plane: expected %d x %d x %d floats, got %s" % (rows, width, ch, a.shape))
         return a

@@ -8,7 +8,10 @@ planes, row 0 = bottom (the "pre-dumped Float32/Uint8 arrays" of the north star)
 An engine that exports UNPACKED attribute planes writes, instead of gbuffer.bin and velocity.bin (write_dump(..., packed=False)):
   aov_diffuse.bin float32 W*H*4   aov_normal.bin float32 W*H*3 (world space)   aov_roughness.bin / aov_metalness.bin float32 W*H
   aov_emissive.bin float32 W*H*3  aov_velocity.bin float32 W*H*2 (uv units)
-and the device packs them (rfx_pack_gbuffer / rfx_pack_velocity).
+and the device packs them (rfx_pack_gbuffer / rfx_pack_velocity, or rfx_stage_aov on the upload stream).  A plane whose values are halves may be
+stored as such — aov_<name>.f16.bin / direct.f16.bin, IEEE binary16, instead of the .bin (write_dump(..., packed=False, half=(names))) — and is
+read back as float16: the typed frame Context.stage_aov sends at two bytes per element.  diffuse and direct may have three channels (alpha 1):
+the count follows from the file size.
 
 A renderer's usual AOV container is one multi-layer OpenEXR per frame: read_exr_dump() / write_exr_dump() map it onto the same frame
 object (layer names: rfx_amd.imageio.AOV_LAYOUT; the cameras travel in the EXR's side-car `<name>.json`, same fields as frame.json).
@@ -40,8 +43,22 @@ def _cam_from_json(d):
 _AOV = (("diffuse", 4), ("normal", 3), ("roughness", 1), ("metalness", 1), ("emissive", 3), ("velocity", 2))
 
 
-def write_dump(dirname: str, frame, packed: bool = True) -> None:
+def _plane_file(dirname, stem, half=None):
+    """(path, dtype) of a plane's file: `half` True / False names the one to write; None finds the one that exists (.f16.bin first)"""
+    f16 = os.path.join(dirname, stem + ".f16.bin")
+    if half or (half is None and os.path.exists(f16)):
+        return f16, np.float16
+    return os.path.join(dirname, stem + ".bin"), np.float32
+
+
+def write_dump(dirname: str, frame, packed: bool = True, half=()) -> None:
+    """`half` (unpacked dumps): the names among the AOV planes and "direct" to store as binary16 (the values are rounded if they are no halves)"""
     os.makedirs(dirname, exist_ok=True)
+    if packed and half:
+        raise ValueError("write_dump: half planes belong to an unpacked dump (packed=False)")
+    unknown = set(half) - {k for k, _ in _AOV} - {"direct"}
+    if unknown:
+        raise ValueError("write_dump: no such plane to store as half: %s" % sorted(unknown))
     meta = dict(width=int(frame.width), height=int(frame.height), camera=_cam_to_json(frame.camera),
                 prevCamera=_cam_to_json(getattr(frame, "prev_camera", frame.camera)))
     with open(os.path.join(dirname, "frame.json"), "w") as f:
@@ -52,8 +69,10 @@ def write_dump(dirname: str, frame, packed: bool = True) -> None:
         np.ascontiguousarray(frame.velocity).view(np.uint32).tofile(os.path.join(dirname, "velocity.bin"))
     else:
         for k, _ in _AOV:
-            np.ascontiguousarray(frame.aov[k], np.float32).tofile(os.path.join(dirname, "aov_%s.bin" % k))
-    np.ascontiguousarray(frame.direct, np.float32).tofile(os.path.join(dirname, "direct.bin"))
+            path, dt = _plane_file(dirname, "aov_" + k, k in half)
+            np.ascontiguousarray(frame.aov[k], dt).tofile(path)
+    path, dt = _plane_file(dirname, "direct", "direct" in half)
+    np.ascontiguousarray(frame.direct, dt).tofile(path)
 
 
 def read_dump(dirname: str):
@@ -61,13 +80,22 @@ def read_dump(dirname: str):
         meta = json.load(f)
     W, H = meta["width"], meta["height"]
     rd = lambda n, dt, shape: np.fromfile(os.path.join(dirname, n), dt).reshape(shape)  # noqa: E731
+
+    def typed(stem, channels):  # .f16.bin or .bin, whichever exists; `channels`: the counts the plane may have
+        path, dt = _plane_file(dirname, stem)
+        a = np.fromfile(path, dt)
+        ch = a.size // (W * H) if W * H else 0
+        if ch not in channels or a.size != W * H * ch:
+            raise ValueError("%s: %d elements do not make %s channel(s) of a %d x %d frame" % (path, a.size, " or ".join(map(str, channels)), W, H))
+        return a.reshape((H, W, ch) if max(channels) > 1 else (H, W))
+
     fr = types.SimpleNamespace(width=W, height=H, camera=_cam_from_json(meta["camera"]), prev_camera=_cam_from_json(meta["prevCamera"]),
-                               depth=rd("depth.bin", np.float32, (H, W)), direct=rd("direct.bin", np.float32, (H, W, 4)), gbuffer=None, velocity=None,
+                               depth=rd("depth.bin", np.float32, (H, W)), direct=typed("direct", (3, 4)), gbuffer=None, velocity=None,
                                aov=None)
     if os.path.exists(os.path.join(dirname, "gbuffer.bin")):
         fr.gbuffer, fr.velocity = rd("gbuffer.bin", np.uint32, (H, W, 4)), rd("velocity.bin", np.uint32, (H, W, 4))
     else:
-        fr.aov = {k: rd("aov_%s.bin" % k, np.float32, (H, W, ch) if ch > 1 else (H, W)) for k, ch in _AOV}
+        fr.aov = {k: typed("aov_" + k, (3, 4) if k == "diffuse" else (ch,)) for k, ch in _AOV}
     return fr
 
 
@@ -88,10 +116,11 @@ def write_exr_dump(path: str, frame, compression: str = "zip") -> None:
         json.dump(meta, f)
 
 
-def read_exr_dump(path: str, names: dict | None = None):
-    """The inverse: a frame whose G-buffer / velocity come as unpacked attribute planes (frame.aov) for the device-side importer."""
+def read_exr_dump(path: str, names: dict | None = None, typed: bool = False):
+    """The inverse: a frame whose G-buffer / velocity come as unpacked attribute planes (frame.aov) for the device-side importer.  `typed`:
+    layers stored HALF stay float16 (imageio.exr_to_typed_planes): the frame Context.stage_aov sends at two bytes per half element."""
     from . import imageio
-    planes = imageio.exr_to_dump_planes(path, names)
+    planes = (imageio.exr_to_typed_planes if typed else imageio.exr_to_dump_planes)(path, names)
     with open(path + ".json") as f:
         meta = json.load(f)
     H, W = planes["depth"].shape

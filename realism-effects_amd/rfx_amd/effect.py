@@ -204,9 +204,10 @@ def _upload_plane(renderer, tex, plane, static=False):
 
 
 def _pack_planes(renderer, tex, aov, depth, pack, static=False):
-    """Device-side packing of a dumped frame's attribute planes into `tex` (skipped only for a `static` frame's resident aov, like _upload_plane)."""
+    """Device-side packing of a dumped frame's attribute planes into `tex` (skipped only for a `static` frame's resident aov and for a frame
+    the caller streamed itself — "resident": Context.stage_aov / stage_flip — like _upload_plane)."""
     cache = renderer.__dict__.setdefault("_resident_planes", {})
-    if static and cache.get(tex) is aov:
+    if static == "resident" or (static and cache.get(tex) is aov):
         return
     r0, n = renderer.held_rows(tex)
     full = depth.shape[0] != n  # the caller dumped the whole frame: hand over the band this tile holds

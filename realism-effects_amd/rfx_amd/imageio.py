@@ -698,15 +698,15 @@ def _exr_attr(name: bytes, typ: bytes, payload: bytes) -> bytes:
 
 def write_exr(path: str, channels: dict, compression: str = "zip", half: bool = False, tiles=None):
     """channels: name -> (H, W) array (row 0 = bottom); e.g. {"R": .., "G": .., "B": ..} or layered AOVs {"normal.X": .., "depth.Z": ..}.
-    float32 (or half=True: binary16) samples, compression "none" | "rle" | "zips" | "zip" | "piz" | "pxr24" (the last one keeps 24 bits
+    float32 (or half=True: binary16; or half = the names of the channels to store as binary16, the rest float32) samples, compression "none" | "rle" | "zips" | "zip" | "piz" | "pxr24" (the last one keeps 24 bits
     of a float32 sample: lossy).  A scanline file, or with tiles=(tile_w, tile_h) a single-level tiled one (what some renderers write
     by default)."""
     names = sorted(channels)  # the format requires alphabetical channel order
     planes = [np.asarray(channels[n]) for n in names]
     H, W = planes[0].shape
-    pt = _PT_HALF if half else _PT_FLOAT
+    pts = [_PT_HALF if (half is True or (half and not isinstance(half, bool) and n in half)) else _PT_FLOAT for n in names]
     comp = {"none": _COMP_NONE, "rle": _COMP_RLE, "zips": _COMP_ZIPS, "zip": _COMP_ZIP, "piz": _COMP_PIZ, "pxr24": _COMP_PXR24}[compression]
-    chlist = b"".join(n.encode() + b"\0" + struct.pack("<iBBBBii", pt, 0, 0, 0, 0, 1, 1) for n in names) + b"\0"
+    chlist = b"".join(n.encode() + b"\0" + struct.pack("<iBBBBii", pt, 0, 0, 0, 0, 1, 1) for n, pt in zip(names, pts)) + b"\0"
     box = struct.pack("<iiii", 0, 0, W - 1, H - 1)
     header = (b"\x76\x2f\x31\x01" + struct.pack("<i", 2 | (0x200 if tiles else 0)) +
               _exr_attr(b"channels", b"chlist", chlist) + _exr_attr(b"compression", b"compression", bytes([comp])) +
@@ -714,9 +714,8 @@ def write_exr(path: str, channels: dict, compression: str = "zip", half: bool = 
               _exr_attr(b"lineOrder", b"lineOrder", b"\0") + _exr_attr(b"pixelAspectRatio", b"float", struct.pack("<f", 1.0)) +
               _exr_attr(b"screenWindowCenter", b"v2f", struct.pack("<ff", 0.0, 0.0)) + _exr_attr(b"screenWindowWidth", b"float", struct.pack("<f", 1.0)) +
               (_exr_attr(b"tiles", b"tiledesc", struct.pack("<IIB", tiles[0], tiles[1], 0)) if tiles else b"") + b"\0")
-    dt = _PT_DTYPE[pt]
-    chans = [(n, pt) for n in names]
-    top_down = [np.ascontiguousarray(p[::-1].astype(dt)) for p in planes]  # EXR y = 0 is the TOP row
+    chans = list(zip(names, pts))
+    top_down = [np.ascontiguousarray(p[::-1].astype(_PT_DTYPE[pt])) for p, pt in zip(planes, pts)]  # EXR y = 0 is the TOP row
     blocks = []
     if tiles:
         tw, th = tiles
@@ -857,6 +856,27 @@ def read_exr(path: str) -> dict:
     return out
 
 
+def exr_channel_types(path: str) -> dict:
+    """-> {channel name, as read_exr names it: "half" | "float" | "uint"}: the sample type each channel is STORED with"""
+    with open(path, "rb") as f:
+        d = f.read()
+    if d[:4] != b"\x76\x2f\x31\x01":
+        raise ValueError("%s: not an OpenEXR file" % path)
+    version = struct.unpack("<i", d[4:8])[0]
+    kind = {_PT_HALF: "half", _PT_FLOAT: "float", _PT_UINT: "uint"}
+    if not version & 0x1000:
+        attrs, _ = _exr_parse_header(d, 8)
+        return {nm: kind[pt] for nm, pt in _exr_part_layout(path, attrs, bool(version & 0x200))["chans"]}
+    out, pos = {}, 8
+    while d[pos] != 0:
+        attrs, pos = _exr_parse_header(d, pos)
+        typ = attrs.get(b"type", (b"", b"scanlineimage"))[1].rstrip(b"\0")
+        name = attrs[b"name"][1].rstrip(b"\0").decode()
+        for ch, pt in _exr_part_layout(path, attrs, typ == b"tiledimage")["chans"]:
+            out[ch if ("." in ch or not name) else name + "." + ch] = kind[pt]
+    return out
+
+
 def write_exr_multipart(path: str, parts: dict, compression: str = "zip", half: bool = False):
     """parts: part name -> {channel: (H, W) array}: one scanline part per entry (how several renderers lay out AOVs)."""
     comp = {"none": _COMP_NONE, "rle": _COMP_RLE, "zips": _COMP_ZIPS, "zip": _COMP_ZIP, "piz": _COMP_PIZ, "pxr24": _COMP_PXR24}[compression]
@@ -933,3 +953,30 @@ def exr_to_dump_planes(path: str, names: dict | None = None) -> dict:
         planes[key] = a[..., 0] if len(cn) == 1 else a
     depth, direct = planes.pop("depth"), planes.pop("direct")
     return {"aov": planes, "depth": np.ascontiguousarray(depth), "direct": np.ascontiguousarray(direct)}
+
+
+def narrow_exact(plane: np.ndarray) -> np.ndarray:
+    """The float16 copy of a float32 plane iff widening it gives back the same bits — every value is a half already, the plane can cross the
+    bus at two bytes per element (Context.stage_aov) and nothing changes; else the plane itself."""
+    a = np.asarray(plane)
+    if a.dtype != np.float32:
+        return plane
+    with np.errstate(over="ignore", invalid="ignore"):
+        h = a.astype(np.float16)
+    same = np.array_equal(np.ascontiguousarray(h.astype(np.float32)).view(np.uint32), np.ascontiguousarray(a).view(np.uint32))
+    return h if same else plane
+
+
+def exr_to_typed_planes(path: str, names: dict | None = None) -> dict:
+    """exr_to_dump_planes, but a layer whose channels are all stored HALF stays float16 (an alpha the rule adds takes the layer's type): the
+    typed frame Context.stage_aov sends at two bytes per half element.  Widening any of its planes gives exr_to_dump_planes' plane, bit for bit."""
+    planes = exr_to_dump_planes(path, names)
+    types_ = exr_channel_types(path)
+    layout = dict(AOV_LAYOUT)
+    layout.update(names or {})
+    flat = dict(planes["aov"], depth=planes["depth"], direct=planes["direct"])
+    for key, cn in layout.items():
+        if all(types_.get(c, "half") == "half" for c in cn) and any(c in types_ for c in cn):
+            flat[key] = np.ascontiguousarray(flat[key].astype(np.float16))
+    depth, direct = flat.pop("depth"), flat.pop("direct")
+    return {"aov": flat, "depth": depth, "direct": direct}

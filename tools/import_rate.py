@@ -1,0 +1,171 @@
+#!/usr/bin/env python3
+"""What the input side of a run over a dumped sequence costs at 4K (GPU box; fails without a device): wall time per frame of the SSGI chain
+(steps 20 / refineSteps 5) when every frame's planes cross PCIe as
+
+    P0  a packed dump, stage_upload from two pinned sets (52 B/px)
+    A0  an AOV frame through the synchronous importer: pack_gbuffer + pack_velocity + upload of depth and direct, float32, pageable (96 B/px)
+    A1  an AOV frame through stage_aov, every plane float32, two pinned sets (76 B/px)
+    A2  the typed AOV frame through stage_aov: diffuse, normal, roughness, metalness, emissive, direct as halves, velocity and depth float32 (44 B/px)
+
+on the seeded dump whose AOV planes are rounded to half wherever A2 sends halves (all four modes see the same values), in ONE process: every
+mode is warmed first, then three alternating rounds, each mode a steady state of at least --seconds with a device synchronise inside the clock.
+
+    python tools/import_rate.py [--out profiles/import/rates.json] [--seconds 1.0]
+    rocprofv3 --kernel-trace --stats -d DIR -- python tools/import_rate.py --kernel-only      (the pack kernel's own time: a run of its own)
+"""
+import argparse
+import json
+import math
+import os
+import sys
+import time
+import types
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "realism-effects_amd"))
+
+from rfx_amd import abi, effect  # noqa: E402
+from rfx_amd.context import Context  # noqa: E402
+from rfx_amd.scene import AnalyticScene, _pool_worker_init  # noqa: E402
+
+W, H = 3840, 2160
+MODES = ("P0", "A0", "A1", "A2")
+BYTES_PER_PIXEL = dict(P0=52, A0=96, A1=76, A2=44)
+HALF = ("diffuse", "normal", "roughness", "metalness", "emissive", "direct")
+AOV = ("diffuse", "normal", "roughness", "metalness", "emissive", "velocity")
+
+
+def _band(args):
+    seed, index, row0, rows = args
+    f = AnalyticScene(seed).render(W, rows, index, row0=row0, rows=rows, frame_height=H, aov=True)
+    return f.depth, f.gbuffer, f.velocity, f.direct, f.aov, f.camera
+
+
+def render(seed, index, workers=16):
+    """frame `index` of the seeded scene with its unpacked planes, ray-cast by a pool of processes"""
+    import multiprocessing as mp
+    edges = [H * i // workers for i in range(workers + 1)]
+    jobs = [(seed, index, edges[i], edges[i + 1] - edges[i]) for i in range(workers) if edges[i + 1] > edges[i]]
+    pool = mp.get_context("fork").Pool(len(jobs), initializer=_pool_worker_init)
+    try:
+        parts = pool.map(_band, jobs)
+        pool.close()
+        pool.join()
+    except BaseException:
+        pool.terminate()
+        raise
+    cat = lambda get: np.ascontiguousarray(np.concatenate([get(p) for p in parts], axis=0))  # noqa: E731
+    planes = {k: cat(lambda p, k=k: p[4][k]) for k in AOV}
+    planes["depth"], planes["direct"] = cat(lambda p: p[0]), cat(lambda p: p[3])
+    return planes, parts[0][5]
+
+
+class Run:
+    def __init__(self, seed):
+        self.ctx = ctx = Context(W, H)  # raises without a device
+        self.scene = types.SimpleNamespace(frame=None)
+        self.frames = {m: [] for m in MODES}
+
+        def pin(a):  # a pinned copy: what makes the staged copies asynchronous
+            p = ctx.host_alloc(a.shape, a.dtype)
+            p[...] = a
+            return p
+        for i in range(2):
+            planes, camera = render(seed, i)
+            wide = {k: (v.astype(np.float16).astype(np.float32) if k in HALF else v) for k, v in planes.items()}
+            typed = {k: (v.astype(np.float16) if k in HALF else v) for k, v in planes.items()}
+            # the packed planes of the same values: the device's own importer
+            ctx.pack_gbuffer(wide, wide["depth"])
+            ctx.pack_velocity(wide, wide["depth"])
+            gbuffer, velocity = ctx.download(abi.TEX_GBUFFER), ctx.download(abi.TEX_VELOCITY)
+            ns = lambda static, depth, direct, **kw: types.SimpleNamespace(camera=camera, static=static, depth=depth, direct=direct, **kw)  # noqa: E731
+            self.frames["P0"].append(ns("resident", pin(wide["depth"]), pin(wide["direct"]), gbuffer=pin(gbuffer), velocity=pin(velocity), aov=None))
+            self.frames["A0"].append(ns(False, wide["depth"], wide["direct"], gbuffer=None, velocity=None, aov={k: wide[k] for k in AOV}))
+            self.frames["A1"].append(ns("resident", pin(wide["depth"]), pin(wide["direct"]), gbuffer=None, velocity=None, aov={k: pin(wide[k]) for k in AOV}))
+            self.frames["A2"].append(ns("resident", pin(typed["depth"]), pin(typed["direct"]), gbuffer=None, velocity=None, aov={k: pin(typed[k]) for k in AOV}))
+        self.cam = types.SimpleNamespace(**vars(self.frames["P0"][0].camera))
+        self.fx = effect.SSGIEffect(None, self.scene, self.cam, dict(width=W, height=H, steps=20, refineSteps=5), seeds=dict(ssgi=11, denoise=22), half_store_rtz=True)
+        for m in ("A1", "A2"):
+            f = self.frames[m][0]
+            assert ctx.aov_stage_bytes(dict(f.aov, depth=f.depth, direct=f.direct)) == BYTES_PER_PIXEL[m] * W * H
+
+    def draw(self, f):
+        self.scene.frame = f
+        for k, v in vars(f.camera).items():
+            setattr(self.cam, k, v)
+        self.fx.update(self.ctx, None)
+
+    def loop(self, mode, n):
+        """n frames; wall seconds, the device synchronised inside the clock"""
+        ctx, fr = self.ctx, self.frames[mode]
+        staged = mode != "A0"
+        if staged:
+            ctx.stage_frame(fr[0])
+            ctx.stage_flip()
+        ctx.sync()
+        t0 = time.perf_counter()
+        for i in range(n):
+            if staged:
+                ctx.stage_frame(fr[(i + 1) & 1])  # frame i + 1 crosses while frame i draws
+            self.draw(fr[i & 1])
+            if staged:
+                ctx.stage_flip()
+        ctx.sync()
+        return time.perf_counter() - t0
+
+    def kernel_only(self, n=20):
+        """stage_aov + flip alone, for a kernel trace: A1's frame, then A2's"""
+        ctx = self.ctx
+        for mode in ("A1", "A2"):
+            for i in range(n):
+                ctx.stage_frame(self.frames[mode][i & 1])
+                ctx.stage_flip()
+            ctx.sync()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "import", "rates.json"))
+    ap.add_argument("--seconds", type=float, default=1.0, help="steady state per measurement, at least")
+    ap.add_argument("--seed", type=int, default=1234)
+    ap.add_argument("--size", default="3840x2160", help="frame size (the committed numbers are 4K; a small size checks the script itself)")
+    ap.add_argument("--kernel-only", action="store_true", help="only stage and flip AOV frames (under rocprofv3 --kernel-trace --stats)")
+    a = ap.parse_args()
+    global W, H
+    W, H = (int(v) for v in a.size.split("x"))
+    run = Run(a.seed)
+    if a.kernel_only:
+        run.kernel_only()
+        run.ctx.close()
+        return
+    result = dict(width=W, height=H, seed=a.seed, seconds=a.seconds, steps=20, refineSteps=5,
+                  bytes_per_frame={m: BYTES_PER_PIXEL[m] * W * H for m in MODES}, rounds=[], frames={})
+    n = {}
+    for mode in MODES:  # warm every mode, and size its loop from the warm rate
+        run.loop(mode, 5)
+        per = run.loop(mode, 20) / 20
+        n[mode] = max(20, int(math.ceil(a.seconds / per)))
+    result["frames"] = n
+    for r in range(3):
+        row = {mode: round(run.loop(mode, n[mode]) / n[mode] * 1e3, 4) for mode in MODES}
+        row["A1_below_A0"] = row["A1"] < row["A0"]
+        row["A2_below_A0"] = row["A2"] < row["A0"]
+        row["A2_over_P0"] = round(row["A2"] / row["P0"], 4)
+        row["A1_over_P0"] = round(row["A1"] / row["P0"], 4)
+        result["rounds"].append(row)
+        print(json.dumps(row), flush=True)
+    result["required_A1_and_A2_below_A0_every_round"] = all(r["A1_below_A0"] and r["A2_below_A0"] for r in result["rounds"])
+    assert run.ctx.halo_violations() == 0
+    run.ctx.close()
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+    if not result["required_A1_and_A2_below_A0_every_round"]:
+        sys.exit("import_rate: stage_aov is not faster than the synchronous importer in every round: the staging does not overlap")
+
+
+if __name__ == "__main__":
+    main()
