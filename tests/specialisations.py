@@ -2,13 +2,13 @@
 
 The launchers of realism-effects_amd/csrc turn run-time options into template arguments (rfx_launch.h rfx_with_bool / rfx_with_int): 54
 k1_ssgi_march kernels, 24 k2_temporal_reproject kernels, 4 k3_generic + 40 k3_tiled kernels, and the staged rectangle of a k3_tiled pass 0 has
-one of a handful of (pitch, skip) layouts.  The functions below return, from what a test hands a draw, the key of the kernel the launcher
+one of a handful of (pitch, skip) layouts; 3 k0_aov_pack kernels for the plane types of a streamed AOV frame.  The functions below return, from what a test hands a draw, the key of the kernel the launcher
 will pick, so that a test can say which specialisation it runs and tests/test_specialisation_cases.py can hold the tables of
 tests/test_gpu_specialisations.py against the full cross products.
 
 What depends on a launch plan — K1's table layout (pow2), K3's tiled / pitch / skip — is asked of the library AS BUILT (rfx_internal_k1_table,
 rfx_internal_k3_tile: `Plans`); the other conditions are written down here a second time, on purpose: rfx_launch_k1's projection test,
-K2's `hist_f32 = historySource == 2`, rfx_views_whole."""
+K2's `hist_f32 = historySource == 2`, rfx_views_whole; K0 AOV pack's `halves == 0` / `halves == typed` (tests/aov_cases.py select)."""
 import ctypes
 import itertools
 
@@ -22,6 +22,7 @@ K2_KEYS = [("k2", it, lt, hf, wh) for it, lt, hf, wh in itertools.product((0, 1,
 K3_GENERIC_KEYS = [("k3_generic", in_t, tc) for in_t in (0, 1) for tc in (1, 2)]
 K3_TILED_KEYS = [("k3_tiled", in_t, tc, pitch, wh) for in_t in (0, 1) for tc in (1, 2) for pitch in PITCHES for wh in (0, 1)]
 K3_KEYS = K3_GENERIC_KEYS + K3_TILED_KEYS
+K0_AOV_KEYS = [("k0_aov", s) for s in (0, 1, 2)]  # k0_aov_pack<SET>: no half plane, the typed set, any other mix
 # what a sweep for the (pitch, skip) layouts of pass 0 covers (test_specialisation_cases.py runs it through the plan export)
 LAYOUT_SWEEP = dict(widths=(2, 261), heights=(2, 201), radii=[0.5 * k for k in range(17)])
 assert (len(K1_KEYS), len(K2_KEYS), len(K3_GENERIC_KEYS), len(K3_TILED_KEYS)) == (54, 24, 4, 40)
@@ -30,7 +31,7 @@ assert (len(K1_KEYS), len(K2_KEYS), len(K3_GENERIC_KEYS), len(K3_TILED_KEYS)) ==
 def key_id(key):
     """a key as a pytest id: k1-perspective-pow2_0-em2-trace, k2-it0-lt0-hf1-wh0, k3_tiled-in_t1-tc2-pitch74-wh1, k3_generic-in_t0-tc1"""
     names = {"k1": ("", "pow2_", "em", ""), "k2": ("it", "lt", "hf", "wh"), "k3_generic": ("in_t", "tc"), "k3_tiled": ("in_t", "tc", "pitch", "wh"),
-             "layout": ("pitch", "skip")}[key[0]]
+             "layout": ("pitch", "skip"), "k0_aov": ("set",)}[key[0]]
     return "-".join([key[0]] + ["%s%s" % (n, v) for n, v in zip(names, key[1:])])
 
 
@@ -129,6 +130,13 @@ def k3_key(plans, dp, W, H, whole):
     t = plans.k3(W, H, dp.radius, dp.inputIsTemporal != 0, dp.textureCount)
     in_t, tc = int(dp.inputIsTemporal != 0), 2 if dp.textureCount == 2 else 1
     return ("k3_tiled", in_t, tc, t["pitch"], int(bool(whole))) if t["tiled"] else ("k3_generic", in_t, tc)
+
+
+def k0_aov_key(staged):
+    """staged: {plane name: array} as handed to Context.stage_aov for a whole frame (float16 = a half plane)"""
+    import aov_cases
+    import numpy as np
+    return ("k0_aov", aov_cases.select(aov_cases.mask_of(staged), aov_cases.mask_of(k for k, v in staged.items() if v.dtype == np.float16)))
 
 
 def k3_layout(plans, dp, W, H):

@@ -1,6 +1,6 @@
 """-m gpu: every kernel specialisation the launchers can select (realism-effects_amd/csrc/rfx_launch.h: a run-time option becomes a template
 argument), one test per kernel, the test's id the kernel's key (tests/specialisations.py): 54 k1_ssgi_march, 24 k2_temporal_reproject, 4 k3_generic
-+ 40 k3_tiled, and every (pitch, skip) layout of k3_tiled's staged rectangle.  Each case is the device against the C restatement on identical
++ 40 k3_tiled, every (pitch, skip) layout of k3_tiled's staged rectangle, and 3 k0_aov_pack.  Each case is the device against the C restatement on identical
 inputs through assert_close of tests/test_gpu_parity.py — its metric, its bounds, every out-of-tolerance pixel proven — or, where the
 specialisation differs from one held that way only in how the work is cut (trace + shade for march, row tiles for the whole frame),
 bit-identical to that one.  tests/test_specialisation_cases.py (CPU) holds the tables below against the full cross products: a template
@@ -108,6 +108,16 @@ def k3_inputs(key, frame, tag=""):
                            blueNoiseIndex=31, inputIsTemporal=in_t, writeToB=0 if in_t else 1, halfStoreRTZ=1)
     dp.isTextureSpecular[:] = [0, 1] if tc == 2 else [0, 0]
     return dp, W, H, bool(wh)
+
+
+# ---------------------------------------------------------------- K0 AOV pack
+K0_AOV_CASES = list(SP.K0_AOV_KEYS)
+
+
+def k0_aov_inputs(key):
+    """the staged planes of a K0 AOV pack case: the 7 x 3 frame of tests/aov_cases.py (five groups and a tail) all float32, as the typed set, all halves"""
+    import aov_cases as AC
+    return AC.stage(AC.form_frame(0), {0: 0, 1: AC.TYPED, 2: AC.ALL}[key[1]])
 
 
 # ---------------------------------------------------------------- shared by the tests
@@ -400,3 +410,21 @@ def test_k3_pass0_layout(blue_noise, key, frame):
     """pass 0 with two textures: `skip` texels shaved off each end of the staged rectangle, on every pitch"""
     dp, W, H, whole = k3_inputs(key, frame)
     _k3_case(blue_noise, SP.key_id(key), dp, W, H, whole, ("k3_tiled", 1, 2, key[1], 1), want_layout=key)
+
+
+# ---------------------------------------------------------------- K0 AOV pack
+@pytest.mark.parametrize("key", K0_AOV_CASES, ids=SP.key_id)
+def test_k0_aov(key):
+    """the staged frame's four slots against the C restatement's packers on the widened planes, byte for byte"""
+    from rfx_amd import abi
+    from rfx_amd.context import Context
+    import aov_cases as AC
+    staged = k0_aov_inputs(key)
+    assert SP.k0_aov_key(staged) == key
+    ctx = Context(AC.FORM_W, AC.FORM_H)
+    ctx.stage_aov(staged)
+    ctx.stage_flip()
+    got = [ctx.download(t) for t in (abi.TEX_DEPTH, abi.TEX_GBUFFER, abi.TEX_VELOCITY, abi.TEX_DIRECT_LIGHT)]
+    diff = AC.differing(got, AC.reference(AC.widen(staged)))
+    assert not diff, "%s: %s" % (SP.key_id(key), diff)
+    _close_all(ctx)

@@ -53,6 +53,16 @@ def test_k2_cases_select_their_kernels_and_cover_the_cross_product():
     assert sorted(keys) == sorted(SP.K2_KEYS) and len(set(keys)) == 24
 
 
+def test_k0_aov_cases_select_their_kernels_and_cover_the_cross_product():
+    keys = []
+    for key in T.K0_AOV_CASES:
+        staged = T.k0_aov_inputs(key)
+        assert SP.k0_aov_key(staged) == key and len(staged) == 8  # (a whole frame: every plane is given)
+        keys.append(key)
+    assert sorted(keys) == sorted(SP.K0_AOV_KEYS) and len(set(keys)) == 3
+    assert [SP.key_id(k) for k in SP.K0_AOV_KEYS] == ["k0_aov-set0", "k0_aov-set1", "k0_aov-set2"]
+
+
 @needs_hostsim
 def test_k3_cases_select_their_kernels_and_cover_the_cross_product(plans):
     keys = set()
