@@ -1,5 +1,5 @@
-// rfx_api.hip — the C ABI of librfx_hip.so (include/rfx.h): context, texture slots, the four
-// draw entry points.  Host side only; kernels live in k1..k4_*.hip.
+// rfx_api.hip — the C ABI of librfx_hip.so (include/rfx.h) but for the exchanges of a row-tiled run (rfx_comm.hip, rfx_peer.hip).
+// Host side only; the kernels live in the k*.hip files.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -231,6 +231,22 @@ static int band_check(rfx_ctx *c, int id, int row0, int rows) {
     if (rows <= 0 || row0 < s.row0 || row0 + rows > s.row0 + s.rows) return fail(c, RFX_EINVAL, "row band outside the rows this context holds");
     return RFX_OK;
 }
+// where frame row `frame_row` (a row of the held band) starts in a slot's buffer, and in its back buffer
+static size_t slot_row_offset(const Slot &s, int frame_row) { return (size_t)(frame_row - s.row0) * s.width * s.texel; }
+static char *slot_row(const Slot &s, int frame_row) { return (char *)s.ptr + slot_row_offset(s, frame_row); }
+static char *slot_back_row(const Slot &s, int frame_row) { return (char *)s.back + slot_row_offset(s, frame_row); }
+// An input slot holds something: a host-filled plane must have been uploaded (packed, staged or bound), as K2 / K3 require of theirs; a slot a
+// draw writes must at least exist — a draw, an upload or a clear made it
+static bool slot_filled(const rfx_ctx *c, int id) {
+    const bool host_filled = id == RFX_TEX_VELOCITY || id == RFX_TEX_BLUE_NOISE || id == RFX_TEX_DIRECT_LIGHT || id == RFX_TEX_EFFECT_INPUT;
+    return host_filled ? c->slots[id].uploaded : c->slots[id].ptr != nullptr;
+}
+// "fn: what" into the context's error text
+static int fail_in(rfx_ctx *c, int code, const char *fn, const char *what) {
+    char buf[384];
+    snprintf(buf, sizeof buf, "%s: %s", fn, what);
+    return fail(c, code, buf);
+}
 
 int rfx_upload(rfx_ctx *c, rfx_tex id, const void *host, int row0, int rows) {
     if (!c || !host) return RFX_EINVAL;
@@ -240,7 +256,7 @@ int rfx_upload(rfx_ctx *c, rfx_tex id, const void *host, int row0, int rows) {
     RFX_ENTER(c);
     Slot &s = c->slots[id];
     const size_t pitch = (size_t)s.width * s.texel;
-    HIPCHK(c, hipMemcpyAsync((char *)s.ptr + (size_t)(row0 - s.row0) * pitch, host, (size_t)rows * pitch, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(slot_row(s, row0), host, (size_t)rows * pitch, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));  // the caller may free `host` as soon as we return
     s.uploaded = true;
     if (id == RFX_TEX_DEPTH) depth_new_writer(c, DEPTH_WRITTEN);
@@ -255,7 +271,7 @@ int rfx_download(rfx_ctx *c, rfx_tex id, void *host, int row0, int rows) {
     RFX_ENTER(c);
     Slot &s = c->slots[id];
     const size_t pitch = (size_t)s.width * s.texel;
-    HIPCHK(c, hipMemcpyAsync(host, (char *)s.ptr + (size_t)(row0 - s.row0) * pitch, (size_t)rows * pitch, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(host, slot_row(s, row0), (size_t)rows * pitch, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return RFX_OK;
 }
@@ -306,14 +322,13 @@ int rfx_stage_upload(rfx_ctx *c, rfx_tex id, const void *host, int row0, int row
     if ((rc = stage_back(c, s))) return rc;
     // the buffer being filled was the FRONT buffer until the last flip: the draws that read it were enqueued before that flip
     HIPCHK(c, hipStreamWaitEvent(c->upload_stream, c->ev_frame_done, 0));
-    HIPCHK(c, hipMemcpyAsync((char *)s.back + (size_t)(row0 - s.row0) * pitch, host, (size_t)rows * pitch, hipMemcpyHostToDevice, c->upload_stream));
+    HIPCHK(c, hipMemcpyAsync(slot_back_row(s, row0), host, (size_t)rows * pitch, hipMemcpyHostToDevice, c->upload_stream));
     s.back_filled = true;
     return RFX_OK;
 }
 
 // ---- streamed AOV frames (include/rfx.h): the planes of rfx_pack_gbuffer / rfx_pack_velocity / the depth and direct uploads, staged once on the
 // upload stream and packed by one fused kernel (k0_import.hip k0_aov_pack) into the back buffers rfx_stage_flip publishes
-static int export_fail(rfx_ctx *c, int code, const char *fn, const char *what);  // ("fn: what" into the context's error text; defined with the export)
 static const rfx_plane *aov_planes(const rfx_aov_frame *f) { return &f->diffuse; }  // eight rfx_plane in RFX_AOV_* order
 static const char *aov_plan(const rfx_ctx *c, const rfx_aov_frame *f, int row0, int rows, rfx_aov_plan *t) {
     static_assert(sizeof(rfx_aov_frame) == RFX_AOV_PLANES * sizeof(rfx_plane), "rfx_aov_frame is eight planes");
@@ -338,14 +353,14 @@ int rfx_stage_aov(rfx_ctx *c, const rfx_aov_frame *f, int row0, int rows) {
     if (!c || !f) return RFX_EINVAL;
     RFX_ENTER(c);
     rfx_aov_plan t;
-    if (const char *bad = aov_plan(c, f, row0, rows, &t)) return export_fail(c, RFX_EINVAL, "rfx_stage_aov", bad);
+    if (const char *bad = aov_plan(c, f, row0, rows, &t)) return fail_in(c, RFX_EINVAL, "rfx_stage_aov", bad);
     const int ids[4] = {RFX_TEX_DEPTH, RFX_TEX_GBUFFER, RFX_TEX_VELOCITY, RFX_TEX_DIRECT_LIGHT};
     const bool writes[4] = {true, t.write_gbuffer != 0, t.write_velocity != 0, t.write_direct != 0};
     int rc;
     for (int k = 0; k < 4; k++) {  // every check before anything is enqueued
         if (!writes[k]) continue;
         if ((rc = ensure(c, ids[k]))) return rc;
-        if (!c->slots[ids[k]].owned) return export_fail(c, RFX_ESTATE, "rfx_stage_aov", "a slot to be written is bound to an external buffer");
+        if (!c->slots[ids[k]].owned) return fail_in(c, RFX_ESTATE, "rfx_stage_aov", "a slot to be written is bound to an external buffer");
     }
     if ((rc = stage_streams(c))) return rc;
     for (int k = 0; k < 4; k++)
@@ -374,7 +389,7 @@ int rfx_stage_aov(rfx_ctx *c, const rfx_aov_frame *f, int row0, int rows) {
             if (p.type == RFX_PLANE_F16) A.half_mask |= 1u << i;
         }
         A.diffuse_ch = f->diffuse.channels; A.direct_ch = f->direct.channels;
-        const auto first = [&](int id) { const Slot &s = c->slots[id]; return (char *)s.back + (size_t)(g.row0 - s.row0) * s.width * s.texel; };
+        const auto first = [&](int id) { return slot_back_row(c->slots[id], g.row0); };
         A.depth = (float *)first(RFX_TEX_DEPTH);
         if (g.full && t.write_gbuffer) A.gbuffer = (uint4 *)first(RFX_TEX_GBUFFER);
         if (g.full && t.write_velocity) A.velocity = (uint4 *)first(RFX_TEX_VELOCITY);
@@ -489,6 +504,13 @@ static rfx_scaled_rows_plan ctx_scaled_rows(const rfx_ctx *c, int Hs) {
 static bool scaled_rows_fit(const rfx_ctx *c, int Ws, const rfx_scaled_rows_plan &t) {
     return (size_t)(t.j1 - t.j0) * Ws <= (size_t)c->slots[RFX_TEX_SSGI].rows * c->W;
 }
+// Is `rs` a resolutionScale this context can draw at, and the size of its target (SSGIPass.setSize :52-57)?  The caller words the error.
+static bool scaled_target(const rfx_ctx *c, float rs, int *Ws, int *Hs) {
+    const float fw = (float)c->W * rs, fh = (float)c->H * rs;
+    if (!(rs > 0.0f && rs <= 1.0f) || fw != floorf(fw) || fh != floorf(fh) || fw < 1.0f || fh < 1.0f) return false;
+    *Ws = (int)fw; *Hs = (int)fh;
+    return true;
+}
 static int need(rfx_ctx *c, const int *ids, int n) {
     for (int i = 0; i < n; i++) {
         int rc = ensure(c, ids[i]);
@@ -552,8 +574,7 @@ int rfx_pack_gbuffer(rfx_ctx *c, const rfx_aov_gbuffer *a, int row0, int rows) {
     float *stage = nullptr;
     if ((rc = stage_planes(c, host, ch, 6, (size_t)rows * c->W, &stage, dev))) return rc;
     Slot &s = c->slots[RFX_TEX_GBUFFER];
-    hipError_t e = rfx_launch_pack_gbuffer(c->W, rows, dev[0], dev[1], dev[2], dev[3], dev[4], dev[5],
-                                           (char *)s.ptr + (size_t)(row0 - s.row0) * s.width * s.texel, c->stream);
+    hipError_t e = rfx_launch_pack_gbuffer(c->W, rows, dev[0], dev[1], dev[2], dev[3], dev[4], dev[5], slot_row(s, row0), c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // the caller may free the planes as soon as we return
     hipFree(stage);
     if (e != hipSuccess) return fail(c, RFX_EDEVICE, "rfx_pack_gbuffer", e);
@@ -572,7 +593,7 @@ int rfx_pack_velocity(rfx_ctx *c, const rfx_aov_velocity *a, int row0, int rows)
     float *stage = nullptr;
     if ((rc = stage_planes(c, host, ch, 3, (size_t)rows * c->W, &stage, dev))) return rc;
     Slot &s = c->slots[RFX_TEX_VELOCITY];
-    hipError_t e = rfx_launch_pack_velocity(c->W, rows, dev[0], dev[1], dev[2], (char *)s.ptr + (size_t)(row0 - s.row0) * s.width * s.texel, c->stream);
+    hipError_t e = rfx_launch_pack_velocity(c->W, rows, dev[0], dev[1], dev[2], slot_row(s, row0), c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     hipFree(stage);
     if (e != hipSuccess) return fail(c, RFX_EDEVICE, "rfx_pack_velocity", e);
@@ -729,11 +750,10 @@ static int ssgi_validate(rfx_ctx *c, const rfx_ssgi_params *p) {
     if (!c->slots[RFX_TEX_DEPTH].uploaded || !c->slots[RFX_TEX_GBUFFER].uploaded || !c->slots[RFX_TEX_BLUE_NOISE].uploaded)
         return fail(c, RFX_ESTATE, "rfx_ssgi_march/trace/shade: depth / gbuffer / blue-noise not uploaded");
     const float rs = ssgi_resolution_scale(p);
-    if (rs != 1.0f) {  // SSGIPass.setSize :52-57
-        const float fw = (float)c->W * rs, fh = (float)c->H * rs;
-        if (!(rs > 0.0f && rs <= 1.0f) || fw != floorf(fw) || fh != floorf(fh) || fw < 1.0f || fh < 1.0f)
-            return fail(c, RFX_EINVAL, "rfx_ssgi_march/trace/shade: resolutionScale must be in (0, 1] with whole W*s and H*s");
-        if (!scaled_rows_fit(c, (int)fw, ctx_scaled_rows(c, (int)fh)))
+    if (rs != 1.0f) {
+        int Ws, Hs;
+        if (!scaled_target(c, rs, &Ws, &Hs)) return fail(c, RFX_EINVAL, "rfx_ssgi_march/trace/shade: resolutionScale must be in (0, 1] with whole W*s and H*s");
+        if (!scaled_rows_fit(c, Ws, ctx_scaled_rows(c, Hs)))
             return fail(c, RFX_EINVAL, "rfx_ssgi_march/trace/shade: the target rows of this tile at this resolutionScale do not fit the held band (more halo rows)");
     }
     return RFX_OK;
@@ -964,10 +984,9 @@ int rfx_ssgi_target_rows(rfx_ctx *c, float resolutionScale, int *row0, int *rows
     const float rs = resolutionScale == 0.0f ? 1.0f : resolutionScale;
     rfx_scaled_rows_plan t = {c->slots[RFX_TEX_SSGI].row0, c->slots[RFX_TEX_SSGI].row0 + c->slots[RFX_TEX_SSGI].rows};  // scale 1: the held band
     if (rs != 1.0f) {
-        const float fw = (float)c->W * rs, fh = (float)c->H * rs;
-        if (!(rs > 0.0f && rs <= 1.0f) || fw != floorf(fw) || fh != floorf(fh) || fw < 1.0f || fh < 1.0f)
-            return fail(c, RFX_EINVAL, "rfx_ssgi_target_rows: resolutionScale must be in (0, 1] with whole W*s and H*s");
-        t = ctx_scaled_rows(c, (int)fh);
+        int Ws, Hs;
+        if (!scaled_target(c, rs, &Ws, &Hs)) return fail(c, RFX_EINVAL, "rfx_ssgi_target_rows: resolutionScale must be in (0, 1] with whole W*s and H*s");
+        t = ctx_scaled_rows(c, Hs);
     }
     if (row0) *row0 = t.j0;
     if (rows) *rows = t.j1 - t.j0;
@@ -1162,14 +1181,9 @@ static int k6_validate(rfx_ctx *c, const rfx_motion_blur_params *p, bool draw) {
                                              "rfx_motion_blur_stage / rfx_motion_blur_gather");
         if (c->blur_armed != p->source) return fail(c, RFX_ESTATE, "rfx_motion_blur: the row-tiled draw is armed (rfx_motion_blur_stage / rfx_motion_blur_gather) for another source");
     }
-    // host-filled planes must have been uploaded (packed, staged or bound), as K2 / K3 require of theirs; the slots a draw writes
-    // (FINAL, TEMPORAL0, SSGI) must at least exist — a draw, an upload or a clear made them
-    const auto host_filled = [](int id) {
-        return id == RFX_TEX_VELOCITY || id == RFX_TEX_BLUE_NOISE || id == RFX_TEX_DIRECT_LIGHT || id == RFX_TEX_EFFECT_INPUT;
-    };
     const int ins[] = {RFX_TEX_VELOCITY, RFX_TEX_BLUE_NOISE, p->source, center};
     for (int id : ins)
-        if (host_filled(id) ? !c->slots[id].uploaded : !c->slots[id].ptr)
+        if (!slot_filled(c, id))  // (uploaded if the host fills it — the slots a draw writes, FINAL, TEMPORAL0, SSGI, must at least exist)
             return fail(c, RFX_ESTATE, "rfx_motion_blur: an input slot holds nothing yet (upload it or draw into it first)");
     return RFX_OK;
 }
@@ -1259,9 +1273,8 @@ int rfx_motion_blur_stage(rfx_ctx *c, const rfx_motion_blur_params *p) {
     if (!is_tiled(c)) return RFX_OK;  // the whole-frame draw reads the source itself
     if ((rc = ensure(c, RFX_TEX_BLUR_SOURCE))) return rc;
     const Slot &s = c->slots[p->source], &b = c->slots[RFX_TEX_BLUR_SOURCE];
-    const size_t pitch = (size_t)c->W * 16;  // every source slot is read as RGBA32F
-    HIPCHK(c, hipMemcpyAsync((char *)b.ptr + (size_t)c->tile_y0 * pitch, (const char *)s.ptr + (size_t)(c->tile_y0 - s.row0) * pitch, (size_t)c->tile_rows * pitch,
-                             hipMemcpyDeviceToDevice, c->stream));
+    const size_t pitch = (size_t)c->W * 16;  // every source slot is read as RGBA32F; RFX_TEX_BLUR_SOURCE is held whole, as RGBA32F
+    HIPCHK(c, hipMemcpyAsync(slot_row(b, c->tile_y0), slot_row(s, c->tile_y0), (size_t)c->tile_rows * pitch, hipMemcpyDeviceToDevice, c->stream));
     c->blur_armed = p->source;
     return RFX_OK;
 }
@@ -1283,11 +1296,6 @@ static const char *export_params_error(const rfx_export_params *p) {
     }
     return nullptr;
 }
-static int export_fail(rfx_ctx *c, int code, const char *fn, const char *what) {
-    char buf[384];
-    snprintf(buf, sizeof buf, "%s: %s", fn, what);
-    return fail(c, code, buf);
-}
 
 size_t rfx_export_bytes(const rfx_ctx *c, const rfx_export_params *p) {
     rfx_export_plan t;
@@ -1295,26 +1303,37 @@ size_t rfx_export_bytes(const rfx_ctx *c, const rfx_export_params *p) {
     return (size_t)t.bytes;
 }
 
+// a device buffer of at least `want` bytes in *buf (capacity *cap), replaced when it is too small: the caller knows it idle
+static int grow_idle(rfx_ctx *c, void **buf, size_t *cap, size_t want, const char *what) {
+    if (*cap >= want) return RFX_OK;
+    if (*buf) hipFree(*buf);
+    *buf = nullptr;
+    *cap = 0;
+    hipError_t e = hipMalloc(buf, want);
+    if (e != hipSuccess) return fail(c, RFX_ENOMEM, what, e);
+    *cap = want;
+    return RFX_OK;
+}
+
 // png_filter < 0: the plain export (K7's bytes cross PCIe); 0..4: rfx_stage_png — K7 as ever, then K8 on the download stream and its result buffer
 static int export_enqueue(rfx_ctx *c, const rfx_export_params *p, void *host, size_t bytes, int *ticket, const char *fn, int png_filter = -1) {
     if (!c || !p || !host) return RFX_EINVAL;
     RFX_ENTER(c);
-    if (const char *bad = export_params_error(p)) return export_fail(c, RFX_EINVAL, fn, bad);
+    if (const char *bad = export_params_error(p)) return fail_in(c, RFX_EINVAL, fn, bad);
     rfx_export_plan t;
-    if (!rfx_export_plan_for(c->tile_rows * c->W, p->format, p->channels, &t)) return export_fail(c, RFX_EINVAL, fn, "bad format or channel count");
+    if (!rfx_export_plan_for(c->tile_rows * c->W, p->format, p->channels, &t)) return fail_in(c, RFX_EINVAL, fn, "bad format or channel count");
     const bool png = png_filter >= 0;
     rfx_png_plan g = {};
     if (png) {
-        if (p->format != RFX_EXPORT_U8_SRGB) return export_fail(c, RFX_EINVAL, fn, "format must be RFX_EXPORT_U8_SRGB");
-        if (png_filter > 4) return export_fail(c, RFX_EINVAL, fn, "filter must be 0 (adaptive) or 1..4 (None, Sub, Up, Paeth)");
-        if (!rfx_png_plan_for(c->tile_rows, c->W, p->channels, &g)) return export_fail(c, RFX_EINVAL, fn, "bad channel count");
-        if (bytes != (size_t)g.bound) return export_fail(c, RFX_EINVAL, fn, "bytes != rfx_png_bound(ctx, params)");
-    } else if (bytes != (size_t)t.bytes) return export_fail(c, RFX_EINVAL, fn, "bytes != rfx_export_bytes(ctx, params)");
+        if (p->format != RFX_EXPORT_U8_SRGB) return fail_in(c, RFX_EINVAL, fn, "format must be RFX_EXPORT_U8_SRGB");
+        if (png_filter > 4) return fail_in(c, RFX_EINVAL, fn, "filter must be 0 (adaptive) or 1..4 (None, Sub, Up, Paeth)");
+        if (!rfx_png_plan_for(c->tile_rows, c->W, p->channels, &g)) return fail_in(c, RFX_EINVAL, fn, "bad channel count");
+        if (bytes != (size_t)g.bound) return fail_in(c, RFX_EINVAL, fn, "bytes != rfx_png_bound(ctx, params)");
+    } else if (bytes != (size_t)t.bytes) return fail_in(c, RFX_EINVAL, fn, "bytes != rfx_export_bytes(ctx, params)");
     const size_t stream_bytes = (size_t)t.bytes;  // K7's output
     // rfx_motion_blur's rule: a host-filled plane must have been uploaded (staged, bound); a slot a draw writes must at least exist
     const Slot &s = c->slots[p->source];
-    const bool host_filled = p->source == RFX_TEX_DIRECT_LIGHT || p->source == RFX_TEX_EFFECT_INPUT;
-    if (host_filled ? !s.uploaded : !s.ptr) return export_fail(c, RFX_ESTATE, fn, "the source slot holds nothing yet (upload it or draw into it first)");
+    if (!slot_filled(c, p->source)) return fail_in(c, RFX_ESTATE, fn, "the source slot holds nothing yet (upload it or draw into it first)");
     if (!c->download_stream) {
         hipError_t e = hipStreamCreateWithFlags(&c->download_stream, hipStreamNonBlocking);
         for (int b = 0; b < 2; b++) {
@@ -1332,24 +1351,13 @@ static int export_enqueue(rfx_ctx *c, const rfx_export_params *p, void *host, si
         // ... and the order on the device: this encode overwrites the buffer that copy read
         HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_export_copied[b], 0));
     }
-    if (c->export_cap[b] < stream_bytes) {  // (idle: its last copy has completed)
-        if (c->export_buf[b]) hipFree(c->export_buf[b]);
-        c->export_buf[b] = nullptr;
-        c->export_cap[b] = 0;
-        hipError_t e = hipMalloc(&c->export_buf[b], stream_bytes);
-        if (e != hipSuccess) return fail(c, RFX_ENOMEM, "rfx_stage_export: hipMalloc(staging buffer)", e);
-        c->export_cap[b] = stream_bytes;
-    }
-    if (png && c->png_cap[b] < (size_t)g.device_bytes) {  // (idle by the same event: K8 and its copy ran behind that buffer's last encode)
-        if (c->png_buf[b]) hipFree(c->png_buf[b]);
-        c->png_buf[b] = nullptr;
-        c->png_cap[b] = 0;
-        hipError_t e = hipMalloc(&c->png_buf[b], (size_t)g.device_bytes);
-        if (e != hipSuccess) return fail(c, RFX_ENOMEM, "rfx_stage_png: hipMalloc(PNG buffer)", e);
-        c->png_cap[b] = (size_t)g.device_bytes;
-    }
+    int rc;
+    // (idle: its last copy has completed)
+    if ((rc = grow_idle(c, &c->export_buf[b], &c->export_cap[b], stream_bytes, "rfx_stage_export: hipMalloc(staging buffer)"))) return rc;
+    // (idle by the same event: K8 and its copy ran behind that buffer's last encode)
+    if (png && (rc = grow_idle(c, &c->png_buf[b], &c->png_cap[b], (size_t)g.device_bytes, "rfx_stage_png: hipMalloc(PNG buffer)"))) return rc;
     K7Args A;
-    A.src = (const uint4 *)s.ptr + (size_t)(c->tile_y0 - s.row0) * c->W;
+    A.src = (const uint4 *)slot_row(s, c->tile_y0);
     A.dst = c->export_buf[b];
     A.groups = t.groups;
     A.tail_start = t.tail_start;
@@ -1415,12 +1423,12 @@ size_t rfx_png_bound(const rfx_ctx *c, const rfx_export_params *p) {
 
 int rfx_stage_png(rfx_ctx *c, const rfx_export_params *p, int filter, void *host, size_t bytes, int *ticket) {
     if (!ticket) return RFX_EINVAL;
-    if (filter < 0 || filter > 4) return c ? export_fail(c, RFX_EINVAL, "rfx_stage_png", "filter must be 0 (adaptive) or 1..4 (None, Sub, Up, Paeth)") : RFX_EINVAL;
+    if (filter < 0 || filter > 4) return c ? fail_in(c, RFX_EINVAL, "rfx_stage_png", "filter must be 0 (adaptive) or 1..4 (None, Sub, Up, Paeth)") : RFX_EINVAL;
     return export_enqueue(c, p, host, bytes, ticket, "rfx_stage_png", filter);
 }
 
 int rfx_png(rfx_ctx *c, const rfx_export_params *p, int filter, void *host, size_t bytes) {
-    if (filter < 0 || filter > 4) return c ? export_fail(c, RFX_EINVAL, "rfx_png", "filter must be 0 (adaptive) or 1..4 (None, Sub, Up, Paeth)") : RFX_EINVAL;
+    if (filter < 0 || filter > 4) return c ? fail_in(c, RFX_EINVAL, "rfx_png", "filter must be 0 (adaptive) or 1..4 (None, Sub, Up, Paeth)") : RFX_EINVAL;
     int ticket = 0;
     const int rc = export_enqueue(c, p, host, bytes, &ticket, "rfx_png", filter);
     return rc ? rc : rfx_export_wait(c, ticket);

@@ -1,10 +1,28 @@
-// rfx_kernels.h — launch-argument blocks and launcher prototypes of the four kernels.
+// rfx_kernels.h — launch-argument blocks and launcher prototypes of the kernels, K0 .. K8, each block with its launchers under it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "rfx_device.h"
 
 // Rows [y0, y1) of the frame are produced by a launch (the context's tile, plus whatever extra
 // rows the host asks for, e.g. K1's +-2 rows that K2's neighbourhood clamp reads).
+
+// K0 importer (k0_import.hip): device staging planes of `rows` rows -> packed texels
+hipError_t rfx_launch_pack_gbuffer(int W, int rows, const float *diffuse, const float *normal, const float *roughness, const float *metalness,
+                                   const float *emissive, const float *depth, void *out, hipStream_t);
+hipError_t rfx_launch_pack_velocity(int W, int rows, const float *velocity, const float *normal, const float *depth, void *out, hipStream_t);
+// K0 AOV pack (k0_import.hip): one segment of rfx_stage_aov (rfx_launch.h rfx_aov_plan_for) — the staged planes of its flat pixel run -> the
+// segment's first texel of every slot it writes.  Planes in rfx_aov_frame's order (RFX_AOV_*); a null output is not written.
+struct K0AovArgs {
+    const void *plane[8];      // 256-byte-aligned staging pieces; null: not read
+    unsigned int half_mask;    // bit i: plane i holds IEEE halves
+    int diffuse_ch, direct_ch; // 3 or 4
+    uint4 *gbuffer, *velocity, *direct;
+    float *depth;
+    int groups, tail_start, tail_pixels;  // lanes [0, groups) own four pixels each; lane `groups` the tail
+};
+hipError_t rfx_launch_k0_aov(const K0AovArgs &, int blocks, hipStream_t);
+// CubeToEquirectEnvPass (k0_import.hip): six S x S RGBA32F faces -> a W x H RGBA32F equirectangular image
+hipError_t rfx_launch_cube_to_equirect(float4 *chain, int size, int levels, float4 *out, int W, int H, const UvPlanes &uv, hipStream_t);
 
 struct K1Args {
     FrameDims dims;
@@ -39,7 +57,15 @@ struct K1Args {
     unsigned char *fg_tiles;     // k1_prepare also writes K3's foreground map: one byte per 64 x 8-texel tile, rows of fg_w = ceil(W / 64) bytes
     int fg_w;
 };
-
+int rfx_k1_base_cell();  // edge of k1_prepare's base cells in texels
+hipError_t rfx_launch_k1_prepare(const K1Args &, hipStream_t);
+hipError_t rfx_launch_k1(const K1Args &, int stage /* 0 fused, 1 trace, 2 shade */, hipStream_t);
+// mask[row] |= 1 << column block (32 blocks across the frame) for every history texel the shade stage of the traced rays of rows [y0, y1) will read (H words, zeroed)
+hipError_t rfx_launch_k1_hit_mask(const FrameDims &, int y0, int y1, TexView depth, TexViewW out, const float4 *hits, bool allow_missed, unsigned int *mask, hipStream_t);
+// ... after a trace at resolutionScale != 1: the fragments are the out_w x [j0, j1) target rows (vUv planes out_uv), their hand-over texels sit at
+// (y - j0) * out_w + x, their depth at the NEAREST frame texel of their vUv; rows and column blocks are named at full resolution, as k1_shade reads them
+hipError_t rfx_launch_k1_hit_mask_scaled(const FrameDims &, const UvPlanes &out_uv, int out_w, int j0, int j1, TexView depth, const float4 *hits, bool allow_missed,
+                                         unsigned int *mask, hipStream_t);
 // one level of the environment's mip chain from the one above (glGenerateMipmap on the oracle's GL: 2x2 bilinear centre)
 hipError_t rfx_launch_env_mip(const float4 *src, float4 *dst, int sw, int sh, int dw, int dh, bool to_half, bool rtz, hipStream_t);
 
@@ -58,6 +84,9 @@ struct K2Args {
     // [in_j0, in_j0 + in_rows) from the start of the slot, pitch in_w (rfx_launch.h rfx_scaled_rows); 0, in_h on a whole-frame context
     int in_j0, in_rows;
 };
+hipError_t rfx_launch_k2(const K2Args &, hipStream_t);
+// rows [y0, y1) of an RGBA32F plane -> the same rows of an RGBA16F (to_half) or RGBA32F plane
+hipError_t rfx_launch_copy_fb(const FrameDims &, int y0, int y1, TexView src, TexViewW dst, bool to_half, hipStream_t);
 
 struct K3Args {
     FrameDims dims;
@@ -74,6 +103,7 @@ struct K3Args {
     // describes `depth` and y0 is a multiple of 8; the launcher drops it unless every view is the whole frame.
     const unsigned char *fg_tiles;
 };
+hipError_t rfx_launch_k3(const K3Args &, hipStream_t);
 
 struct K4Args {
     FrameDims dims;
@@ -84,49 +114,7 @@ struct K4Args {
     float *rgb_out;  // RFX_TEX_COMPOSE_RGB (whole frame, 3 floats per texel) or null
     rfx_compose_params p;
 };
-
-// K0 importer (k0_import.hip): device staging planes of `rows` rows -> packed texels
-hipError_t rfx_launch_pack_gbuffer(int W, int rows, const float *diffuse, const float *normal, const float *roughness, const float *metalness,
-                                   const float *emissive, const float *depth, void *out, hipStream_t);
-hipError_t rfx_launch_pack_velocity(int W, int rows, const float *velocity, const float *normal, const float *depth, void *out, hipStream_t);
-// K0 AOV pack (k0_import.hip): one segment of rfx_stage_aov (rfx_launch.h rfx_aov_plan_for) — the staged planes of its flat pixel run -> the
-// segment's first texel of every slot it writes.  Planes in rfx_aov_frame's order (RFX_AOV_*); a null output is not written.
-struct K0AovArgs {
-    const void *plane[8];      // 256-byte-aligned staging pieces; null: not read
-    unsigned int half_mask;    // bit i: plane i holds IEEE halves
-    int diffuse_ch, direct_ch; // 3 or 4
-    uint4 *gbuffer, *velocity, *direct;
-    float *depth;
-    int groups, tail_start, tail_pixels;  // lanes [0, groups) own four pixels each; lane `groups` the tail
-};
-hipError_t rfx_launch_k0_aov(const K0AovArgs &, int blocks, hipStream_t);
-// CubeToEquirectEnvPass (k0_import.hip): six S x S RGBA32F faces -> a W x H RGBA32F equirectangular image
-hipError_t rfx_launch_cube_to_equirect(float4 *chain, int size, int levels, float4 *out, int W, int H, const UvPlanes &uv, hipStream_t);
-
-// K7 export (k0_import.hip): `pixels` RGBA32F texels from `src` -> the packed stream at `dst`, laid out by rfx_launch.h rfx_export_plan_for
-struct K7Args {
-    const uint4 *src;  // first exported texel
-    void *dst;         // staging buffer (at least 16-byte aligned)
-    int groups;        // lanes [0, groups) own four pixels each
-    int tail_start, tail_pixels;  // lane `groups` writes these with element-wide stores
-    float exposure;
-};
-// format / channels / tonemap select the specialisation (hipErrorInvalidValue for a combination the export does not have); `blocks` from the plan
-hipError_t rfx_launch_k7(const K7Args &, int blocks, int format, int channels, int tonemap, hipStream_t);
-
-// K8 PNG encode (k8_png.h, built into k0_import.hip): K7's staged U8 stream -> the result buffer of include/rfx.h "PNG fragments", laid out by
-// rfx_launch.h rfx_png_plan_for.  Three launches on `stream`: one wave per scanline into the scratch slots, the scan, the gather.
-struct K8Args {
-    const unsigned char *src;     // K7's stream: `rows` rows of `rowbytes` bytes, row 0 = bottom
-    unsigned char *result;        // 32-byte header, then the fragment
-    unsigned char *slots;         // rows * slot_stride bytes of scratch: one whole chunk per scanline
-    unsigned *meta;               // rows * 4: chunk bytes, the two Adler partial sums, 0
-    unsigned long long *offsets;  // rows: where each chunk starts in the fragment
-    unsigned long long fragment_cap;  // bound - 32
-    int rows, rowbytes, bpp, filter;
-    unsigned slot_stride;
-};
-hipError_t rfx_launch_k8(const K8Args &, hipStream_t);
+hipError_t rfx_launch_k4(const K4Args &, hipStream_t);
 
 struct K5Args {
     FrameDims dims;
@@ -135,7 +123,6 @@ struct K5Args {
     TexViewW out;
     rfx_final_params p;
 };
-
 hipError_t rfx_launch_k5(const K5Args &, hipStream_t);
 
 // K6 (k4_compose.hip): MotionBlurEffect.  The whole-frame launch addresses every plane by frame row; the row-tiled launch (tiled != 0) reads
@@ -166,17 +153,28 @@ hipError_t rfx_launch_k6(const K6Args &, hipStream_t);
 // mask[row] |= 1 << column block for every texel of `src` that rfx_launch_k6 with the same block loads for rows [y0, y1): the draw's streak
 // set-up and tap addressing without the loads (velocity is always read through its band view)
 hipError_t rfx_launch_k6_reach(const K6Args &, hipStream_t);
-int rfx_k1_base_cell();  // edge of k1_prepare's base cells in texels
-hipError_t rfx_launch_k1_prepare(const K1Args &, hipStream_t);
-hipError_t rfx_launch_k1(const K1Args &, int stage /* 0 fused, 1 trace, 2 shade */, hipStream_t);
-// mask[row] |= 1 << column block (32 blocks across the frame) for every history texel the shade stage of the traced rays of rows [y0, y1) will read (H words, zeroed)
-hipError_t rfx_launch_k1_hit_mask(const FrameDims &, int y0, int y1, TexView depth, TexViewW out, const float4 *hits, bool allow_missed, unsigned int *mask, hipStream_t);
-// ... after a trace at resolutionScale != 1: the fragments are the out_w x [j0, j1) target rows (vUv planes out_uv), their hand-over texels sit at
-// (y - j0) * out_w + x, their depth at the NEAREST frame texel of their vUv; rows and column blocks are named at full resolution, as k1_shade reads them
-hipError_t rfx_launch_k1_hit_mask_scaled(const FrameDims &, const UvPlanes &out_uv, int out_w, int j0, int j1, TexView depth, const float4 *hits, bool allow_missed,
-                                         unsigned int *mask, hipStream_t);
-hipError_t rfx_launch_k2(const K2Args &, hipStream_t);
-hipError_t rfx_launch_k3(const K3Args &, hipStream_t);
-hipError_t rfx_launch_k4(const K4Args &, hipStream_t);
-// rows [y0, y1) of an RGBA32F plane -> the same rows of an RGBA16F (to_half) or RGBA32F plane
-hipError_t rfx_launch_copy_fb(const FrameDims &, int y0, int y1, TexView src, TexViewW dst, bool to_half, hipStream_t);
+
+// K7 export (k0_import.hip): `pixels` RGBA32F texels from `src` -> the packed stream at `dst`, laid out by rfx_launch.h rfx_export_plan_for
+struct K7Args {
+    const uint4 *src;  // first exported texel
+    void *dst;         // staging buffer (at least 16-byte aligned)
+    int groups;        // lanes [0, groups) own four pixels each
+    int tail_start, tail_pixels;  // lane `groups` writes these with element-wide stores
+    float exposure;
+};
+// format / channels / tonemap select the specialisation (hipErrorInvalidValue for a combination the export does not have); `blocks` from the plan
+hipError_t rfx_launch_k7(const K7Args &, int blocks, int format, int channels, int tonemap, hipStream_t);
+
+// K8 PNG encode (k8_png.h, built into k0_import.hip): K7's staged U8 stream -> the result buffer of include/rfx.h "PNG fragments", laid out by
+// rfx_launch.h rfx_png_plan_for.  Three launches on `stream`: one wave per scanline into the scratch slots, the scan, the gather.
+struct K8Args {
+    const unsigned char *src;     // K7's stream: `rows` rows of `rowbytes` bytes, row 0 = bottom
+    unsigned char *result;        // 32-byte header, then the fragment
+    unsigned char *slots;         // rows * slot_stride bytes of scratch: one whole chunk per scanline
+    unsigned *meta;               // rows * 4: chunk bytes, the two Adler partial sums, 0
+    unsigned long long *offsets;  // rows: where each chunk starts in the fragment
+    unsigned long long fragment_cap;  // bound - 32
+    int rows, rowbytes, bpp, filter;
+    unsigned slot_stride;
+};
+hipError_t rfx_launch_k8(const K8Args &, hipStream_t);
