@@ -486,6 +486,42 @@ size_t rfx_png_bound(const rfx_ctx *, const rfx_export_params *);
 int rfx_stage_png(rfx_ctx *, const rfx_export_params *, int filter, void *host, size_t bytes, int *ticket);
 int rfx_png(rfx_ctx *, const rfx_export_params *, int filter, void *host, size_t bytes);
 
+/* ---- EXR fragments (K8's second pre-transform): the F16 export leaves the device as finished OpenEXR ZIPS chunks.  Additive to ABI 21: three
+ * more entry points, no new profile kind; a host checks for the symbol.  K7 runs exactly as for rfx_stage_export with RFX_EXPORT_F16 and 3 or 4
+ * channels, so the samples in the file are by construction the halfs rfx_export returns; K8 then encodes them on the DOWNLOAD stream, behind the
+ * "encoded" event, into the device buffer it uses for a PNG, and the device-to-host copy of the WHOLE bound follows (as for a PNG: copying only
+ * fragment_bytes would need a host wait mid-stream; header.raw_bytes - header.fragment_bytes is what it would save).
+ *
+ * THE FRAGMENT is the scanline chunks of the context's tile rows and nothing else.
+ *   Scanlines run top first: tile scanline s = 0 is frame row tile_y0 + tile_rows - 1; its EXR y is H - tile_y0 - tile_rows + s.
+ *   One scanline = one chunk:   int32 y | int32 size | data   (little-endian)
+ *   The scanline's RAW BLOCK, n = W * channels * 2 bytes: the channels in alphabetical order — A, B, G, R for 4 channels; B, G, R for 3 —
+ *     each as W little-endian halfs.
+ *   Its PREDICTED BYTES d: t = the even-indexed bytes of the raw block, then the odd-indexed ones; d[0] = t[0], d[i] = (t[i] - t[i-1] + 128) & 255
+ *     (OpenEXR's ZIP / ZIPS / RLE pre-transform).
+ *   data: form (a) when it is STRICTLY smaller than n bytes, else form (b); a reader tells them apart by size == n.
+ *     (a) a complete zlib stream: 78 01; one FINAL dynamic-Huffman block (header bits 1 0 1) of the n literals d and the end-of-block symbol —
+ *         no length / distance codes; HLIT declares 257 codes, HDIST one distance code of length 0 — padded to a byte; the Adler-32 of d,
+ *         big-endian.  The code lengths follow THE CODE-LENGTH RULE and the block header the header-token rule of "PNG fragments" above, word for
+ *         word: the data is a pure function of the halfs (tests/exr_device_ref.py restates it and the device's result equals it byte for byte).
+ *         Size: 2 + ceil(block bits / 8) + 4.
+ *     (b) the raw block itself, n bytes, unpredicted.
+ *   There is no state across scanlines: the fragments of any row tiling, concatenated top tile first, are the whole frame's fragment.
+ * THE RESULT BUFFER (`host`, rfx_exr_bound bytes): a 32-byte little-endian header, the fragment from offset 32, unspecified bytes after it.
+ *       uint64 fragment_bytes | uint32 chunks | uint32 first_y | uint64 raw_bytes | uint32 raw_form_chunks | 4 bytes of zero
+ *   chunks = tile_rows; first_y = the y of the first chunk; raw_bytes = tile_rows * n; raw_form_chunks = the chunks in form (b).
+ * THE HOST'S WRAP: magic and version; the attributes of a scanline file — channels (HALF, alphabetical), compression 2 (ZIPS), dataWindow,
+ *   displayWindow, lineOrder 0 (increasing y), pixelAspectRatio, screenWindowCenter, screenWindowWidth; the offset table, built by walking the
+ *   chunks' size fields; the fragments, TOP TILE FIRST.
+ * rfx_exr_bound = 32 + tile_rows * (8 + n): every chunk in form (b).  0 on bad params or a format other than RFX_EXPORT_F16.
+ * Tickets come from rfx_stage_export's sequence and rfx_export_wait retires all three kinds; the back pressure and the two-buffer rule apply to
+ * the mixed sequence.  rfx_exr = rfx_stage_exr + rfx_export_wait.  The encode is timed under RFX_PROF_K8.
+ * RFX_EINVAL: what rfx_stage_export refuses, a format other than RFX_EXPORT_F16, bytes != rfx_exr_bound.
+ * RFX_ESTATE: rfx_stage_export's rule. */
+size_t rfx_exr_bound(const rfx_ctx *, const rfx_export_params *);
+int rfx_stage_exr(rfx_ctx *, const rfx_export_params *, void *host, size_t bytes, int *ticket);
+int rfx_exr(rfx_ctx *, const rfx_export_params *, void *host, size_t bytes);
+
 int rfx_sync(rfx_ctx *);
 
 /* ---- streaming dumps: host buffers that cross PCIe every frame (an offline run over a dumped sequence).  rfx_upload is synchronous
@@ -621,7 +657,8 @@ enum { RFX_PROF_K1_PREPASS = 0, RFX_PROF_K1_MARCH, RFX_PROF_K2, RFX_PROF_K3_PASS
 /* Kinds added from here on do not grow RFX_PROF_COUNT: rfx_profile_read has no size argument and keeps filling exactly RFX_PROF_COUNT entries, so
  * a caller built against an earlier header is never overrun.  rfx_profile_read_n fills min(entries, RFX_PROF_COUNT_ALL) entries of each array
  * (the first RFX_PROF_COUNT are rfx_profile_read's) and is how the kinds below are read. */
-enum { RFX_PROF_K8 = RFX_PROF_COUNT, /* the PNG encode of rfx_png / rfx_stage_png: its three launches on the download stream */
+enum { RFX_PROF_K8 = RFX_PROF_COUNT, /* the PNG encode of rfx_png / rfx_stage_png: its three launches on the download stream; the EXR encode of
+                                       * rfx_exr / rfx_stage_exr (its four launches) is timed under this kind too */
        RFX_PROF_COUNT_ALL };
 int rfx_profile(rfx_ctx *, int enable);
 int rfx_profile_read(rfx_ctx *, float *ms_sum, int *launches);

@@ -1315,8 +1315,9 @@ static int grow_idle(rfx_ctx *c, void **buf, size_t *cap, size_t want, const cha
     return RFX_OK;
 }
 
-// png_filter < 0: the plain export (K7's bytes cross PCIe); 0..4: rfx_stage_png — K7 as ever, then K8 on the download stream and its result buffer
-static int export_enqueue(rfx_ctx *c, const rfx_export_params *p, void *host, size_t bytes, int *ticket, const char *fn, int png_filter = -1) {
+// png_filter < 0: the plain export (K7's bytes cross PCIe); 0..4: rfx_stage_png — K7 as ever, then K8 on the download stream and its result buffer.
+// exr: rfx_stage_exr — the same with K8's EXR pre-transform behind K7's F16 stream.
+static int export_enqueue(rfx_ctx *c, const rfx_export_params *p, void *host, size_t bytes, int *ticket, const char *fn, int png_filter = -1, bool exr = false) {
     if (!c || !p || !host) return RFX_EINVAL;
     RFX_ENTER(c);
     if (const char *bad = export_params_error(p)) return fail_in(c, RFX_EINVAL, fn, bad);
@@ -1324,11 +1325,16 @@ static int export_enqueue(rfx_ctx *c, const rfx_export_params *p, void *host, si
     if (!rfx_export_plan_for(c->tile_rows * c->W, p->format, p->channels, &t)) return fail_in(c, RFX_EINVAL, fn, "bad format or channel count");
     const bool png = png_filter >= 0;
     rfx_png_plan g = {};
+    rfx_exr_plan x = {};
     if (png) {
         if (p->format != RFX_EXPORT_U8_SRGB) return fail_in(c, RFX_EINVAL, fn, "format must be RFX_EXPORT_U8_SRGB");
         if (png_filter > 4) return fail_in(c, RFX_EINVAL, fn, "filter must be 0 (adaptive) or 1..4 (None, Sub, Up, Paeth)");
         if (!rfx_png_plan_for(c->tile_rows, c->W, p->channels, &g)) return fail_in(c, RFX_EINVAL, fn, "bad channel count");
         if (bytes != (size_t)g.bound) return fail_in(c, RFX_EINVAL, fn, "bytes != rfx_png_bound(ctx, params)");
+    } else if (exr) {
+        if (p->format != RFX_EXPORT_F16) return fail_in(c, RFX_EINVAL, fn, "format must be RFX_EXPORT_F16");
+        if (!rfx_exr_plan_for(c->tile_rows, c->W, p->channels, &x)) return fail_in(c, RFX_EINVAL, fn, "bad channel count");
+        if (bytes != (size_t)x.bound) return fail_in(c, RFX_EINVAL, fn, "bytes != rfx_exr_bound(ctx, params)");
     } else if (bytes != (size_t)t.bytes) return fail_in(c, RFX_EINVAL, fn, "bytes != rfx_export_bytes(ctx, params)");
     const size_t stream_bytes = (size_t)t.bytes;  // K7's output
     // rfx_motion_blur's rule: a host-filled plane must have been uploaded (staged, bound); a slot a draw writes must at least exist
@@ -1356,6 +1362,7 @@ static int export_enqueue(rfx_ctx *c, const rfx_export_params *p, void *host, si
     if ((rc = grow_idle(c, &c->export_buf[b], &c->export_cap[b], stream_bytes, "rfx_stage_export: hipMalloc(staging buffer)"))) return rc;
     // (idle by the same event: K8 and its copy ran behind that buffer's last encode)
     if (png && (rc = grow_idle(c, &c->png_buf[b], &c->png_cap[b], (size_t)g.device_bytes, "rfx_stage_png: hipMalloc(PNG buffer)"))) return rc;
+    if (exr && (rc = grow_idle(c, &c->png_buf[b], &c->png_cap[b], (size_t)x.device_bytes, "rfx_stage_exr: hipMalloc(EXR buffer)"))) return rc;
     K7Args A;
     A.src = (const uint4 *)slot_row(s, c->tile_y0);
     A.dst = c->export_buf[b];
@@ -1384,8 +1391,24 @@ static int export_enqueue(rfx_ctx *c, const rfx_export_params *p, void *host, si
         ProfScope prof(c, RFX_PROF_K8, c->download_stream);
         HIPCHK(c, rfx_launch_k8(E, c->download_stream));
         from = base;
+    } else if (exr) {
+        unsigned char *base = (unsigned char *)c->png_buf[b];
+        K8ExrArgs E;
+        E.src = (const unsigned short *)c->export_buf[b];
+        E.result = base;
+        E.slots = base + x.slots_at;
+        E.planes = base + x.planes_at;
+        E.meta = (unsigned *)(base + x.meta_at);
+        E.offsets = (unsigned long long *)(base + x.offsets_at);
+        E.fragment_cap = x.bound - 32ull;
+        E.rows = x.rows; E.width = x.width; E.channels = x.channels;
+        E.first_y = c->H - c->tile_y0 - c->tile_rows;
+        E.slot_stride = x.slot_stride; E.plane_stride = x.plane_stride;
+        ProfScope prof(c, RFX_PROF_K8, c->download_stream);
+        HIPCHK(c, rfx_launch_k8_exr(E, c->download_stream));
+        from = base;
     }
-    // (the whole bound crosses for a PNG: copying only fragment_bytes would need the host to wait for the header first — rfx.h)
+    // (the whole bound crosses for a PNG or an EXR fragment: copying only fragment_bytes would need the host to wait for the header first — rfx.h)
     HIPCHK(c, hipMemcpyAsync(host, from, bytes, hipMemcpyDeviceToHost, c->download_stream));
     HIPCHK(c, hipEventRecord(c->ev_export_copied[b], c->download_stream));
     c->exports = n + 1;
@@ -1431,6 +1454,24 @@ int rfx_png(rfx_ctx *c, const rfx_export_params *p, int filter, void *host, size
     if (filter < 0 || filter > 4) return c ? fail_in(c, RFX_EINVAL, "rfx_png", "filter must be 0 (adaptive) or 1..4 (None, Sub, Up, Paeth)") : RFX_EINVAL;
     int ticket = 0;
     const int rc = export_enqueue(c, p, host, bytes, &ticket, "rfx_png", filter);
+    return rc ? rc : rfx_export_wait(c, ticket);
+}
+
+// ---- K8: ... and as a finished EXR fragment, ZIPS chunks (include/rfx.h "EXR fragments"; the kernels are in k8_exr.h)
+size_t rfx_exr_bound(const rfx_ctx *c, const rfx_export_params *p) {
+    rfx_exr_plan x;
+    if (!c || !p || export_params_error(p) || p->format != RFX_EXPORT_F16 || !rfx_exr_plan_for(c->tile_rows, c->W, p->channels, &x)) return 0;
+    return (size_t)x.bound;
+}
+
+int rfx_stage_exr(rfx_ctx *c, const rfx_export_params *p, void *host, size_t bytes, int *ticket) {
+    if (!ticket) return RFX_EINVAL;
+    return export_enqueue(c, p, host, bytes, ticket, "rfx_stage_exr", -1, true);
+}
+
+int rfx_exr(rfx_ctx *c, const rfx_export_params *p, void *host, size_t bytes) {
+    int ticket = 0;
+    const int rc = export_enqueue(c, p, host, bytes, &ticket, "rfx_exr", -1, true);
     return rc ? rc : rfx_export_wait(c, ticket);
 }
 

@@ -88,7 +88,8 @@ struct rfx_ctx {
     size_t export_cap[2] = {0, 0};
     hipEvent_t ev_export_encoded[2] = {nullptr, nullptr}, ev_export_copied[2] = {nullptr, nullptr};
     unsigned int exports = 0;  // tickets issued so far (ticket t = export t - 1)
-    // rfx_stage_png: K8's device buffers (result + scratch, rfx_launch.h rfx_png_plan), one per staging buffer; same owner, same growth rule
+    // rfx_stage_png / rfx_stage_exr: K8's device buffers (result + scratch, rfx_launch.h rfx_png_plan / rfx_exr_plan), one per staging buffer;
+    // same owner, same growth rule
     void *png_buf[2] = {nullptr, nullptr};
     size_t png_cap[2] = {0, 0};
     // the peer-load history gather (rfx_peer.hip): this rank's flag block (fine-grained), the device table of every rank's plane and flag block

@@ -178,3 +178,19 @@ struct K8Args {
     unsigned slot_stride;
 };
 hipError_t rfx_launch_k8(const K8Args &, hipStream_t);
+
+// K8 EXR encode (k8_exr.h, built into k0_import.hip): K7's staged F16 stream -> the result buffer of include/rfx.h "EXR fragments", laid out by
+// rfx_launch.h rfx_exr_plan_for.  Four launches on `stream`: the byte planes, one wave per scanline into the scratch slots, the scan, the gather.
+struct K8ExrArgs {
+    const unsigned short *src;    // K7's stream: `rows` rows of `width` pixels of `channels` halfs, row 0 = bottom
+    unsigned char *result;        // 32-byte header, then the fragment
+    unsigned char *slots;         // rows * slot_stride bytes of scratch: one whole chunk per scanline
+    unsigned char *planes;        // rows * plane_stride bytes of scratch: each scanline's low bytes, then its high bytes
+    unsigned *meta;               // rows * 4: chunk bytes, 1 for a raw chunk, 0, 0
+    unsigned long long *offsets;  // rows: where each chunk starts in the fragment
+    unsigned long long fragment_cap;  // bound - 32
+    int rows, width, channels;
+    int first_y;                  // the EXR y of the tile's top scanline
+    unsigned slot_stride, plane_stride;
+};
+hipError_t rfx_launch_k8_exr(const K8ExrArgs &, hipStream_t);

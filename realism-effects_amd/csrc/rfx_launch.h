@@ -178,6 +178,34 @@ inline bool rfx_png_plan_for(int rows, int W, int channels, rfx_png_plan *out) {
     return true;
 }
 
+// ---------------------------------------------------------------- K8: the EXR fragment's buffers
+// rfx_exr_bound and the layout of the device buffer behind one staged EXR fragment: the result (header + fragment, `bound` bytes), one scratch
+// slot per scanline (a whole chunk in its raw form, rounded up to dwords, plus one dword: the bit window leaves as whole dwords), one byte
+// plane per scanline (n bytes rounded up to dwords: the coder reads it dword-wise), the per-scanline sizes, the chunk offsets.  A pure function
+// of its arguments.
+struct rfx_exr_plan {
+    int rows, width, channels, line_bytes;  // line_bytes = n = W * channels * 2
+    unsigned slot_stride, plane_stride;
+    unsigned long long bound, slots_at, planes_at, meta_at, offsets_at, device_bytes;
+};
+inline bool rfx_exr_plan_for(int rows, int W, int channels, rfx_exr_plan *out) {
+    if (rows <= 0 || rows > 65535 || W <= 0 || (channels != 3 && channels != 4)) return false;
+    rfx_exr_plan t;
+    t.rows = rows; t.width = W; t.channels = channels;
+    t.line_bytes = 2 * W * channels;
+    const unsigned long long chunk = 8ull + (unsigned long long)t.line_bytes;
+    t.bound = 32ull + (unsigned long long)rows * chunk;
+    t.slot_stride = (unsigned)((chunk + 3ull) & ~3ull) + 4u;
+    t.plane_stride = ((unsigned)t.line_bytes + 3u) & ~3u;
+    t.slots_at = (t.bound + 255ull) & ~255ull;
+    t.planes_at = t.slots_at + (((unsigned long long)rows * t.slot_stride + 255ull) & ~255ull);
+    t.meta_at = t.planes_at + (((unsigned long long)rows * t.plane_stride + 255ull) & ~255ull);
+    t.offsets_at = t.meta_at + (((unsigned long long)rows * 16ull + 255ull) & ~255ull);
+    t.device_bytes = t.offsets_at + (unsigned long long)rows * 8ull;
+    *out = t;
+    return true;
+}
+
 // ---------------------------------------------------------------- K0 AOV staging: rfx_stage_aov's rows, staging area and launches
 // The planes of an AOV frame (include/rfx.h rfx_aov_frame, in the struct's order) cover the band [row0, row0 + rows) of the frame.  DEPTH is held
 // whole, GBUFFER / VELOCITY / DIRECT_LIGHT hold the rows [held_row0, held_row0 + held_rows), so the band falls into at most three SEGMENTS of

@@ -209,6 +209,29 @@ class Renderer {
 		for (const t of this._exports.keys()) if (t <= ticket - 2) this._exports.delete(t)
 		return ticket
 	}
+	// EXR fragments (rfx.h "EXR fragments"): the F16 export encoded on the device as the ZIPS chunks of the tile rows.  params as for exportFrame
+	// (format is F16; channels 4 by default).  io.exrFromFragments wraps the result.
+	exrParams(params) {
+		return this.exportParams(Object.assign({ channels: 4 }, params, { format: EXPORT.F16 }))
+	}
+	exrBound(params) {
+		return addon.exrBound(this._h, this.exrParams(params || {}))
+	}
+	// -> the result buffer (Uint8Array of exrBound bytes: 32-byte header, fragment, slack); blocks (rfx_exr)
+	exr(params, out) {
+		const p = this.exrParams(params)
+		if (!out) out = new Uint8Array(Math.max(1, addon.exrBound(this._h, p)))
+		addon.exrFrame(this._h, p, out)
+		return out
+	}
+	// stageExport's contract with an EXR fragment as the payload; the ticket is one of the same sequence and exportWait retires it (rfx_stage_exr)
+	stageExr(params, out) {
+		const ticket = addon.stageExr(this._h, this.exrParams(params), out)
+		if (!this._exports) this._exports = new Map()
+		this._exports.set(ticket, out)
+		for (const t of this._exports.keys()) if (t <= ticket - 2) this._exports.delete(t)
+		return ticket
+	}
 	exportWait(ticket) {
 		addon.exportWait(this._h, ticket)
 		if (this._exports) this._exports.delete(ticket)

@@ -16,7 +16,9 @@ const FRAME_FORMATS = { png: [EXPORT.U8_SRGB, 3], exr: [EXPORT.F16, 4], pfm: [EX
 class FrameExporter {
 	// options: { format: "png" | "exr" | "pfm", tonemap: "aces" | "linear", exposure, hostAlloc, write,
 	//            encode: "host" (default) | "device" — png only: the frame leaves the device as a PNG fragment (rfx_stage_png, K8) and the host
-	//            only wraps and writes it; filter: the fragment's filter, "adaptive" by default }
+	//            only wraps and writes it; filter: the fragment's filter, "adaptive" by default;
+	//            compression: "none" (default) | "zips" — exr only: the frame leaves the device as finished ZIPS chunks (rfx_stage_exr, rfx.h "EXR
+	//            fragments") and the host only wraps and writes them }
 	constructor(renderer, dir, options) {
 		options = options || {}
 		this.renderer = renderer
@@ -31,9 +33,13 @@ class FrameExporter {
 		if (this.encode !== "host" && this.encode !== "device") throw new RangeError("framesEncode: \"host\" or \"device\"")
 		if (this.encode === "device" && this.format !== "png") throw new RangeError("framesEncode \"device\" is for framesFormat \"png\" only")
 		this.filter = options.filter === undefined ? "adaptive" : options.filter
-		const n = this.encode === "device" ? renderer.pngBound(this.params) : renderer.width * renderer.tileRows * f[1]
+		this.compression = options.compression === undefined ? "none" : options.compression
+		if (this.compression !== "none" && this.compression !== "zips") throw new RangeError("framesCompression: \"none\" or \"zips\"")
+		if (this.compression === "zips" && this.format !== "exr") throw new RangeError("framesCompression \"zips\" is for framesFormat \"exr\" only")
+		const zips = this.compression === "zips"
+		const n = this.encode === "device" ? renderer.pngBound(this.params) : zips ? renderer.exrBound(this.params) : renderer.width * renderer.tileRows * f[1]
 		const alloc = options.hostAlloc || Renderer.hostAlloc
-		this.buffers = [0, 1].map(() => alloc(EXPORT_ARRAY[f[0]], n))
+		this.buffers = [0, 1].map(() => alloc(zips ? Uint8Array : EXPORT_ARRAY[f[0]], n))
 		this.write = options.write || ((index, data) => this.writeFrame(index, data))
 		this.count = 0
 		this.pending = null // { ticket, index, buffer }
@@ -42,6 +48,7 @@ class FrameExporter {
 		const file = path.join(this.dir, "frame_" + String(index).padStart(5, "0") + "." + this.format)
 		const w = this.renderer.width, h = this.renderer.tileRows
 		if (this.encode === "device") fs.writeFileSync(file, io.pngFromFragments(w, h, 3, [data]))
+		else if (this.compression === "zips") fs.writeFileSync(file, io.exrFromFragments(w, h, 4, [data]))
 		else if (this.format === "png") io.writePNG(file, data, w, h, 3)
 		else if (this.format === "exr") io.writeEXR(file, data, w, h, true)
 		else io.writePFM(file, data, w, h, 3)
@@ -50,6 +57,7 @@ class FrameExporter {
 		const index = this.count++
 		const buffer = this.buffers[index & 1]
 		const ticket = this.encode === "device" ? this.renderer.stagePng(Object.assign({ source }, this.params), this.filter, buffer)
+			: this.compression === "zips" ? this.renderer.stageExr(Object.assign({ source }, this.params), buffer)
 			: this.renderer.stageExport(Object.assign({ source }, this.params), buffer)
 		this.retire()
 		this.pending = { ticket, index, buffer }

@@ -140,6 +140,49 @@ function writeEXR(file, rgba, width, height, half) {
 	fs.writeFileSync(file, Buffer.concat([header, table, body]))
 }
 
+// The host's wrap of include/rfx.h "EXR fragments": `fragments` are the result buffers of Renderer.exr / stageExr (32-byte header, then the ZIPS
+// chunks of a tile's rows), TOP TILE FIRST -> the file's bytes (a Buffer): the scanline header of writeEXR with HALF channels and compression 2,
+// the offset table built by walking the chunks' size fields, the fragments.  Byte for byte rfx_amd/imageio.py exr_from_fragments.
+function exrFromFragments(width, height, channels, fragments) {
+	if (channels !== 3 && channels !== 4) throw new RangeError("EXR: 3 or 4 channels")
+	const names = channels === 4 ? ["A", "B", "G", "R"] : ["B", "G", "R"]
+	const attr = (name, type, payload) => Buffer.concat([Buffer.from(name + "\0" + type + "\0", "ascii"), (() => { const b = Buffer.alloc(4); b.writeInt32LE(payload.length, 0); return b })(), payload])
+	const chlist = Buffer.concat(names.map(n => { const b = Buffer.alloc(n.length + 1 + 16); b.write(n, 0, "ascii"); b.writeInt32LE(1, n.length + 1); b.writeInt32LE(1, n.length + 9); b.writeInt32LE(1, n.length + 13); return b }).concat([Buffer.from([0])]))
+	const box = Buffer.alloc(16)
+	box.writeInt32LE(width - 1, 8)
+	box.writeInt32LE(height - 1, 12)
+	const f32 = v => { const b = Buffer.alloc(4); b.writeFloatLE(v, 0); return b }
+	const header = Buffer.concat([Buffer.from([0x76, 0x2f, 0x31, 0x01, 2, 0, 0, 0]), attr("channels", "chlist", chlist), attr("compression", "compression", Buffer.from([2])),
+		attr("dataWindow", "box2i", box), attr("displayWindow", "box2i", box), attr("lineOrder", "lineOrder", Buffer.from([0])), attr("pixelAspectRatio", "float", f32(1)),
+		attr("screenWindowCenter", "v2f", Buffer.concat([f32(0), f32(0)])), attr("screenWindowWidth", "float", f32(1)), Buffer.from([0])])
+	const n = 2 * width * channels
+	const table = Buffer.alloc(8 * height), bodies = []
+	let pos = header.length + table.length, y = 0
+	for (const f of fragments) {
+		const b = Buffer.from(f.buffer, f.byteOffset, f.byteLength)
+		const nbytes = Number(b.readBigUInt64LE(0)), chunks = b.readUInt32LE(8), firstY = b.readUInt32LE(12), raw = Number(b.readBigUInt64LE(16))
+		if (32 + nbytes > b.length) throw new RangeError("EXR fragment: header says " + nbytes + " bytes, buffer holds " + (b.length - 32))
+		if (firstY !== y || raw !== chunks * n || y + chunks > height) throw new RangeError("EXR fragments: a tile of " + chunks + " scanlines from y = " + firstY + " (" + raw + " raw bytes) where y = " + y + " of a " + width + " x " + height + " x " + channels + " image is due")
+		const body = b.subarray(32, 32 + nbytes)
+		let at = 0
+		for (let k = 0; k < chunks; k++) {
+			if (at + 8 > nbytes) throw new RangeError("EXR fragment: chunk " + k + " of the tile at y = " + y + " is damaged")
+			const cy = body.readInt32LE(at), size = body.readInt32LE(at + 4)
+			if (cy !== y + k || size < 0 || size > n || at + 8 + size > nbytes) throw new RangeError("EXR fragment: chunk " + k + " of the tile at y = " + y + " is damaged")
+			const off = pos + at
+			table.writeUInt32LE(off >>> 0, 8 * (y + k))
+			table.writeUInt32LE(Math.floor(off / 4294967296), 8 * (y + k) + 4)
+			at += 8 + size
+		}
+		if (at !== nbytes) throw new RangeError("EXR fragment: " + (nbytes - at) + " bytes behind the last chunk")
+		bodies.push(body)
+		pos += nbytes
+		y += chunks
+	}
+	if (y !== height) throw new RangeError("EXR fragments: " + y + " scanlines, the image has " + height)
+	return Buffer.concat([header, table].concat(bodies))
+}
+
 // channels 3: `rgba` is already the file's body, tightly packed RGB float32 (the device's RFX_EXPORT_F32 x 3 stream), written as it is
 function writePFM(file, rgba, width, height, channels) {
 	let body
@@ -151,4 +194,4 @@ function writePFM(file, rgba, width, height, channels) {
 	fs.writeFileSync(file, Buffer.concat([Buffer.from("PF\n" + width + " " + height + "\n-1.0\n", "ascii"), body]))
 }
 
-module.exports = { writePNG, pngFromFragments, writeEXR, writePFM, tonemap }
+module.exports = { writePNG, pngFromFragments, writeEXR, exrFromFragments, writePFM, tonemap }

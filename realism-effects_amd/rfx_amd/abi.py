@@ -25,6 +25,7 @@ EXPORT_FORMATS = {"f32": EXPORT_F32, "f16": EXPORT_F16, "u8_srgb": EXPORT_U8_SRG
 EXPORT_DTYPE = {EXPORT_F32: np.float32, EXPORT_F16: np.float16, EXPORT_U8_SRGB: np.uint8}
 PNG_FILTERS = {"adaptive": 0, "none": 1, "sub": 2, "up": 3, "paeth": 4}  # rfx_stage_png's `filter`
 PNG_HEADER_BYTES = 32  # rfx_stage_png's result buffer: the fragment starts here
+EXR_HEADER_BYTES = 32  # rfx_stage_exr's result buffer: the fragment starts here
 EXPORT_TONEMAP = {"linear": 0, "aces": 1}  # rfx_export_params.tonemap: imageio.tonemap's operators
 RFX_UV_IDEAL, RFX_UV_REFERENCE_GL = 0, 1  # rfx_set_uv_model
 RFX_OK, RFX_EINVAL, RFX_ENOMEM, RFX_EDEVICE, RFX_ESTATE, RFX_EUNSUPPORTED = 0, -1, -2, -3, -4, -5
@@ -139,6 +140,7 @@ EXPORTS = [
     "rfx_export_bytes", "rfx_export", "rfx_stage_export", "rfx_export_wait",
     "rfx_png_bound", "rfx_stage_png", "rfx_png", "rfx_profile_read_n",
     "rfx_aov_stage_bytes", "rfx_stage_aov",
+    "rfx_exr_bound", "rfx_stage_exr", "rfx_exr",
 ]
 
 _lib = None
@@ -245,6 +247,10 @@ def load_library(path: str | None = None) -> C.CDLL:
     lib.rfx_png_bound.restype = C.c_size_t
     lib.rfx_stage_png.argtypes = [vp, C.POINTER(ExportParams), i, vp, C.c_size_t, C.POINTER(i)]
     lib.rfx_png.argtypes = [vp, C.POINTER(ExportParams), i, vp, C.c_size_t]
+    lib.rfx_exr_bound.argtypes = [vp, C.POINTER(ExportParams)]
+    lib.rfx_exr_bound.restype = C.c_size_t
+    lib.rfx_stage_exr.argtypes = [vp, C.POINTER(ExportParams), vp, C.c_size_t, C.POINTER(i)]
+    lib.rfx_exr.argtypes = [vp, C.POINTER(ExportParams), vp, C.c_size_t]
     lib.rfx_aov_stage_bytes.argtypes = [vp, C.POINTER(AovFrame), i, i]
     lib.rfx_aov_stage_bytes.restype = C.c_size_t
     lib.rfx_stage_aov.argtypes = [vp, C.POINTER(AovFrame), i, i]

@@ -257,6 +257,42 @@ class Context:
             del keep[old]
         return int(t.value)
 
+    # -- EXR fragments (rfx.h "EXR fragments"): the F16 export, encoded on the device as the ZIPS chunks of the tile rows
+    def exr_bound(self, channels: int = 4) -> int:
+        """rfx_exr_bound: the bytes of a result buffer (32-byte header + the fragment at its largest)"""
+        return int(self.lib.rfx_exr_bound(self._h, C.byref(self.export_params(abi.TEX_FINAL, "f16", channels))))
+
+    def _exr_out(self, p: abi.ExportParams, out, what):
+        n = int(self.lib.rfx_exr_bound(self._h, C.byref(p)))
+        if out is None:
+            return np.empty(max(n, 1), np.uint8), n  # (bad params: any non-empty buffer will do, the library names the fault)
+        if not isinstance(out, np.ndarray) or not out.flags["C_CONTIGUOUS"] or not out.flags["WRITEABLE"]:
+            raise TypeError("%s: out must be a writeable C-contiguous ndarray" % what)
+        if n and (out.dtype != np.uint8 or out.nbytes != n):
+            raise ValueError("%s: out must hold %d bytes of uint8, got %d of %s" % (what, n, out.nbytes, out.dtype))
+        return out, n
+
+    def exr(self, source: int, channels: int = 4, out=None) -> np.ndarray:
+        """rfx_exr: the tile rows of `source` as an EXR fragment -> the result buffer (exr_bound() bytes of uint8: header, fragment, slack);
+        imageio.exr_from_fragments wraps one or more of them into a file.  Blocks until the bytes are there."""
+        p = self.export_params(source, "f16", channels)
+        out, n = self._exr_out(p, out, "exr")
+        self._chk(self.lib.rfx_exr(self._h, C.byref(p), out.ctypes.data_as(C.c_void_p), n), "rfx_exr")
+        return out
+
+    def stage_exr(self, source: int, channels: int = 4, *, out: np.ndarray) -> int:
+        """rfx_stage_exr: stage_export's contract with an EXR fragment as the payload; the ticket is one of the same sequence and
+        export_wait(ticket) retires it."""
+        p = self.export_params(source, "f16", channels)
+        out, n = self._exr_out(p, out, "stage_exr")
+        t = C.c_int(0)
+        self._chk(self.lib.rfx_stage_exr(self._h, C.byref(p), out.ctypes.data_as(C.c_void_p), n, C.byref(t)), "rfx_stage_exr")
+        keep = self.__dict__.setdefault("_export_keepalive", {})
+        keep[t.value] = out
+        for old in [k for k in keep if k <= t.value - 2]:
+            del keep[old]
+        return int(t.value)
+
     def clear(self, tex: int):
         self._chk(self.lib.rfx_clear(self._h, tex), "rfx_clear")
 

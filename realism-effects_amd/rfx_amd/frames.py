@@ -4,7 +4,10 @@
 
 submit(source) is called once per frame AFTER the frame's draws are enqueued: it stages this frame's export into one of two pinned buffers,
 then waits for the PREVIOUS frame's ticket — which has had this frame's draws to hide behind — and hands its bytes to `write`.  At most two
-exports are in flight; finish() waits for the last one."""
+exports are in flight; finish() waits for the last one.
+
+compression="zips" (exr only; default "none"): the frame leaves the device as finished ZIPS chunks (Context.stage_exr, include/rfx.h "EXR
+fragments") and the host only wraps them; "none" is the uncompressed file written from the staged halfs."""
 from __future__ import annotations
 
 import os
@@ -18,14 +21,18 @@ FRAME_FORMATS = {"png": ("u8_srgb", 3), "exr": ("f16", 4), "pfm": ("f32", 3)}
 
 class FrameExporter:
     def __init__(self, ctx, directory: str, format: str = "png", tonemap: str = "aces", exposure: float = 1.0, write=None, encode: str = "host",
-                 filter="adaptive"):
+                 filter="adaptive", compression: str = "none"):
         if format not in FRAME_FORMATS:
             raise ValueError('format: "png", "exr" or "pfm"')
         if encode not in ("host", "device"):
             raise ValueError('encode: "host" or "device"')
         if encode == "device" and format != "png":
             raise ValueError('encode "device" is for format "png" only')
-        self.encode, self.filter = encode, filter
+        if compression not in ("none", "zips"):
+            raise ValueError('compression: "none" or "zips"')
+        if compression == "zips" and format != "exr":
+            raise ValueError('compression "zips" is for format "exr" only')
+        self.encode, self.filter, self.compression = encode, filter, compression
         self.ctx, self.dir, self.format = ctx, directory, format
         self.kind, self.channels = FRAME_FORMATS[format]
         u8 = self.kind == "u8_srgb"
@@ -33,6 +40,8 @@ class FrameExporter:
         dtype = abi.EXPORT_DTYPE[abi.EXPORT_FORMATS[self.kind]]
         if encode == "device":  # the payload is a PNG fragment (Context.stage_png): the host wraps it and writes
             self.buffers = [ctx.host_alloc((ctx.png_bound(self.channels),), np.uint8) for _ in range(2)]
+        elif compression == "zips":  # the payload is an EXR fragment (Context.stage_exr)
+            self.buffers = [ctx.host_alloc((ctx.exr_bound(self.channels),), np.uint8) for _ in range(2)]
         else:
             self.buffers = [ctx.host_alloc((ctx.tile_rows, ctx.W, self.channels), dtype) for _ in range(2)]
         self.write = write or self.write_frame
@@ -43,6 +52,9 @@ class FrameExporter:
         if self.encode == "device":
             with open(path, "wb") as f:
                 f.write(imageio.png_from_fragments(self.ctx.W, self.ctx.tile_rows, self.channels, [data]))
+        elif self.compression == "zips":
+            with open(path, "wb") as f:
+                f.write(imageio.exr_from_fragments(self.ctx.W, self.ctx.tile_rows, self.channels, [data]))
         elif self.format == "png":
             imageio.write_png(path, data)
         elif self.format == "exr":
@@ -55,6 +67,8 @@ class FrameExporter:
         buf = self.buffers[index & 1]
         if self.encode == "device":
             ticket = self.ctx.stage_png(source, self.channels, self.tonemap, self.exposure, self.filter, out=buf)
+        elif self.compression == "zips":
+            ticket = self.ctx.stage_exr(source, self.channels, out=buf)
         else:
             ticket = self.ctx.stage_export(source, self.kind, self.channels, self.tonemap, self.exposure, out=buf)
         self._retire()

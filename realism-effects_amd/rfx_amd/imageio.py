@@ -5,6 +5,7 @@ offline run leaves on disk (HDR and tone-mapped images).  Pure Python + numpy + 
                     by three's RGBELoader) -> scene.environment for rfx_set_environment
   read_exr/write_exr  OpenEXR, scanline, compression NONE / RLE / ZIPS / ZIP / PIZ / PXR24, HALF / FLOAT / UINT channels, arbitrary layer.channel names —
                     the usual container of renderer AOVs; `exr_to_dump_planes` maps its layers onto the dump's attribute planes
+  exr_from_fragments  the file around the ZIPS chunks the device encodes (include/rfx.h "EXR fragments")
   read_pfm/write_pfm  Portable Float Map (the simplest HDR interchange format)
   write_png         8-bit RGB(A) PNG
   tonemap           linear radiance -> display: ACES filmic (the reference example's renderer.toneMapping, example/main.js) or plain
@@ -742,6 +743,49 @@ def write_exr(path: str, channels: dict, compression: str = "zip", half: bool = 
         f.write(struct.pack("<%dQ" % len(offs), *offs))
         for b in blocks:
             f.write(b)
+
+
+def exr_from_fragments(W: int, H: int, channels: int, fragments) -> bytes:
+    """The host's wrap of include/rfx.h "EXR fragments": `fragments` are the result buffers of Context.exr / stage_exr (32-byte header, then the
+    ZIPS chunks of a tile's rows), TOP TILE FIRST -> the file's bytes: write_exr's scanline header with HALF channels, the offset table built
+    by walking the chunks' size fields, the fragments."""
+    if channels not in (3, 4):
+        raise ValueError("EXR: 3 or 4 channels")
+    names = sorted("RGBA"[:channels])
+    chlist = b"".join(n.encode() + b"\0" + struct.pack("<iBBBBii", _PT_HALF, 0, 0, 0, 0, 1, 1) for n in names) + b"\0"
+    box = struct.pack("<iiii", 0, 0, W - 1, H - 1)
+    header = (b"\x76\x2f\x31\x01" + struct.pack("<i", 2) +
+              _exr_attr(b"channels", b"chlist", chlist) + _exr_attr(b"compression", b"compression", bytes([_COMP_ZIPS])) +
+              _exr_attr(b"dataWindow", b"box2i", box) + _exr_attr(b"displayWindow", b"box2i", box) +
+              _exr_attr(b"lineOrder", b"lineOrder", b"\0") + _exr_attr(b"pixelAspectRatio", b"float", struct.pack("<f", 1.0)) +
+              _exr_attr(b"screenWindowCenter", b"v2f", struct.pack("<ff", 0.0, 0.0)) + _exr_attr(b"screenWindowWidth", b"float", struct.pack("<f", 1.0)) +
+              b"\0")
+    n = 2 * W * channels
+    bodies, offs, pos, y = [], [], len(header) + 8 * H, 0
+    for f in fragments:
+        f = memoryview(np.ascontiguousarray(f).view(np.uint8).reshape(-1)) if isinstance(f, np.ndarray) else memoryview(f)
+        nbytes, chunks, first_y, raw, _, _ = struct.unpack("<QIIQII", f[:32])
+        if 32 + nbytes > len(f):
+            raise ValueError("EXR fragment: header says %d bytes, buffer holds %d" % (nbytes, len(f) - 32))
+        if first_y != y or raw != chunks * n:
+            raise ValueError("EXR fragments: a tile of %d scanlines from y = %d (%d raw bytes) where y = %d of a %d x %d x %d image is due" %
+                             (chunks, first_y, raw, y, W, H, channels))
+        body = bytes(f[32:32 + nbytes])
+        at = 0
+        for k in range(chunks):
+            cy, size = struct.unpack("<ii", body[at:at + 8])
+            if cy != y + k or size < 0 or size > n or at + 8 + size > nbytes:
+                raise ValueError("EXR fragment: chunk %d of the tile at y = %d is damaged" % (k, y))
+            offs.append(pos + at)
+            at += 8 + size
+        if at != nbytes:
+            raise ValueError("EXR fragment: %d bytes behind the last chunk" % (nbytes - at))
+        bodies.append(body)
+        pos += nbytes
+        y += chunks
+    if y != H:
+        raise ValueError("EXR fragments: %d scanlines, the image has %d" % (y, H))
+    return header + struct.pack("<%dQ" % H, *offs) + b"".join(bodies)
 
 
 def _exr_parse_header(d: bytes, pos: int):

@@ -14,6 +14,17 @@ warmed first, then three alternating rounds of the three modes, each a steady st
 read and write; the fragment's size per frame is recorded with K8's.
 
     python tools/export_rate.py [--out profiles/export/rates.json] [--seconds 1.0]
+
+--modes exr measures the HDR output instead, by the same protocol (T0 and the three modes below in alternating rounds), and ADDS its results to
+--out under the key "exr" (the entries above stay):
+
+    E1  stage_export F16 x 4, waited one frame late, written by the host's imageio.write_exr(compression="none", half=True) to /dev/null:
+        FrameExporter("exr")
+    E2  E1 with write_exr(compression="zips"): the host's own ZIPS writer (numpy + zlib level 4, one thread), a few frames
+    E3  stage_exr (K8 behind the EXR predictor: the frame leaves the device as ZIPS chunks), waited one frame late, wrapped by
+        imageio.exr_from_fragments and written to /dev/null: FrameExporter("exr", compression="zips")
+
+and the EXR encode alone (rfx_profile, kind K8) next to the PNG encode measured in the same process.
 """
 import argparse
 import copy
@@ -37,8 +48,9 @@ from rfx_amd.scene import synthetic_frame_parallel  # noqa: E402
 W, H = 3840, 2160
 HBM_PEAK = 8e12  # bytes / s
 MODES = ("T0", "T1", "T2", "T2h", "T3")
-WARM = {"T2h": (1, 2)}   # frames of the two warming loops (default 5 and 20)
-MIN_FRAMES = {"T2h": 3}  # ... and the fewest of a measured loop (default 20)
+EXR_MODES = ("T0", "E1", "E2", "E3")
+WARM = {"T2h": (1, 2), "E1": (1, 3), "E2": (1, 2)}   # frames of the two warming loops (default 5 and 20)
+MIN_FRAMES = {"T2h": 3, "E1": 5, "E2": 3}            # ... and the fewest of a measured loop (default 20)
 
 
 class Run:
@@ -62,6 +74,11 @@ class Run:
         self.u8 = [ctx.host_alloc((H, W, 3), np.uint8) for _ in range(2)]
         self.png = [ctx.host_alloc((ctx.png_bound(3),), np.uint8) for _ in range(2)]
         self.fragment_bytes = []
+        self.f16, self.exr, self.exr_file_bytes = None, None, []
+
+    def alloc_exr(self):
+        self.f16 = [self.ctx.host_alloc((H, W, 4), np.float16) for _ in range(2)]
+        self.exr = [self.ctx.host_alloc((self.ctx.exr_bound(4),), np.uint8) for _ in range(2)]
 
     def write(self, mode, buf):
         """what the host does with a waited frame"""
@@ -70,6 +87,13 @@ class Run:
         elif mode == "T3":
             data = imageio.png_from_fragments(W, H, 3, [buf])
             self.fragment_bytes.append(len(data))
+            with open(os.devnull, "wb") as f:
+                f.write(data)
+        elif mode in ("E1", "E2"):
+            imageio.write_exr(os.devnull, {n: buf[..., k] for k, n in enumerate("RGBA")}, compression="none" if mode == "E1" else "zips", half=True)
+        elif mode == "E3":
+            data = imageio.exr_from_fragments(W, H, 4, [buf])
+            self.exr_file_bytes.append(len(data))
             with open(os.devnull, "wb") as f:
                 f.write(data)
 
@@ -98,8 +122,14 @@ class Run:
             self.frame(cur)
             if mode == "T1":
                 ctx._chk(ctx.lib.rfx_download(ctx._h, abi.TEX_FINAL, self.final.ctypes.data_as(C.c_void_p), 0, H), "rfx_download")
-            elif mode in ("T2", "T2h", "T3"):
-                if mode == "T3":
+            elif mode in ("T2", "T2h", "T3", "E1", "E2", "E3"):
+                if mode == "E3":
+                    buf = self.exr[i & 1]
+                    t = ctx.stage_exr(abi.TEX_FINAL, 4, out=buf)
+                elif mode in ("E1", "E2"):
+                    buf = self.f16[i & 1]
+                    t = ctx.stage_export(abi.TEX_FINAL, "f16", 4, out=buf)
+                elif mode == "T3":
                     buf = self.png[i & 1]
                     t = ctx.stage_png(abi.TEX_FINAL, 3, "aces", 1.0, out=buf)
                 else:
@@ -118,16 +148,98 @@ class Run:
         return time.perf_counter() - t0
 
 
+def main_exr(run, a):
+    """--modes exr: T0 / E1 / E2 / E3 and the EXR encode alone, merged into the file under the key "exr" """
+    import struct
+    import tempfile
+    run.alloc_exr()
+    ctx = run.ctx
+    result = dict(width=W, height=H, seed=a.seed, seconds=a.seconds, rounds={}, frames={})
+    for streamed in (False, True):
+        key = "streamed" if streamed else "resident"
+        n = {}
+        for mode in EXR_MODES:
+            w0, w1 = WARM.get(mode, (5, 20))
+            run.loop(mode, streamed, w0)
+            per = run.loop(mode, streamed, w1) / w1
+            n[mode] = max(MIN_FRAMES.get(mode, 20), int(math.ceil(a.seconds / per)))
+        rounds = []
+        for r in range(3):
+            row = {}
+            for mode in EXR_MODES:
+                row[mode] = round(run.loop(mode, streamed, n[mode]) / n[mode] * 1e3, 4)
+            row["E3_minus_T0"] = round(row["E3"] - row["T0"], 4)
+            row["E3_minus_E1"] = round(row["E3"] - row["E1"], 4)
+            row["E3_below_E2"] = row["E3"] < row["E2"]
+            rounds.append(row)
+            print(key, json.dumps(row), flush=True)
+        result["rounds"][key] = rounds
+        result["frames"][key] = n
+    result["E3_below_E2_every_round"] = all(r["E3_below_E2"] for rs in result["rounds"].values() for r in rs)
+    # the EXR encode alone (its four launches on the download stream), inside a loop of staged fragments; then the PNG encode the same way
+    for _ in range(5):
+        ctx.export_wait(ctx.stage_exr(abi.TEX_FINAL, 4, out=run.exr[0]))
+    ctx.sync()
+    ctx.profile(True)
+    for i in range(20):
+        ctx.export_wait(ctx.stage_exr(abi.TEX_FINAL, 4, out=run.exr[i & 1]))
+    prof = ctx.profile_read()
+    ctx.profile(False)
+    ms, launches = prof["k8_png"]
+    k7ms, k7n = prof["k7_export"]
+    fragment, chunks, _, raw, raw_chunks, _ = struct.unpack("<QIIQII", run.exr[1][:32].tobytes())
+    result["k8_exr_f16x4"] = dict(ms=round(ms / launches, 5), launches=launches, bytes_read=raw, bytes_written=fragment, fragment_of_raw=round(fragment / raw, 4),
+                                  raw_form_chunks=raw_chunks, chunks=chunks, bound=int(ctx.exr_bound(4)), mb_per_ms=round(raw / 1e6 / (ms / launches), 2),
+                                  pcie_bytes_a_fragment_only_copy_would_save=int(ctx.exr_bound(4)) - 32 - fragment)
+    result["k7_f16x4"] = dict(ms=round(k7ms / k7n, 5), launches=k7n)
+    print(json.dumps(result["k8_exr_f16x4"]), flush=True)
+    for _ in range(5):
+        ctx.export_wait(ctx.stage_png(abi.TEX_FINAL, 3, "aces", 1.0, out=run.png[0]))
+    ctx.sync()
+    ctx.profile(True)
+    for i in range(20):
+        ctx.export_wait(ctx.stage_png(abi.TEX_FINAL, 3, "aces", 1.0, out=run.png[i & 1]))
+    ms, launches = ctx.profile_read()["k8_png"]
+    ctx.profile(False)
+    result["k8_png_u8x3_same_process"] = dict(ms=round(ms / launches, 5), launches=launches, bytes_read=W * H * 3, mb_per_ms=round(W * H * 3 / 1e6 / (ms / launches), 2))
+    print(json.dumps(result["k8_png_u8x3_same_process"]), flush=True)
+    # file bytes over raw: the frames E3 wrote, and one frame through both writers (outside every clock)
+    halfs = ctx.export(abi.TEX_FINAL, "f16", 4)
+    with tempfile.TemporaryDirectory() as d:
+        path = os.path.join(d, "host_zips.exr")
+        imageio.write_exr(path, {n: halfs[..., k] for k, n in enumerate("RGBA")}, compression="zips", half=True)
+        host_bytes = os.path.getsize(path)
+    device_bytes = len(imageio.exr_from_fragments(W, H, 4, [ctx.exr(abi.TEX_FINAL, 4)]))
+    raw_frame = W * H * 8
+    fb = run.exr_file_bytes
+    result["file_bytes"] = dict(raw=raw_frame, E3_min=min(fb), E3_max=max(fb), E3_frames=len(fb), E3_min_of_raw=round(min(fb) / raw_frame, 4),
+                                E3_max_of_raw=round(max(fb) / raw_frame, 4), same_frame_device=device_bytes, same_frame_host_zips_level4=host_bytes)
+    print(json.dumps(result["file_bytes"]), flush=True)
+    ctx.close()
+    merged = {}
+    if os.path.exists(a.out):
+        with open(a.out) as f:
+            merged = json.load(f)
+    merged["exr"] = result
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(merged, f, indent=1)
+        f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "export", "rates.json"))
     ap.add_argument("--seconds", type=float, default=1.0, help="steady state per measurement, at least")
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--size", default="3840x2160", help="frame size (the committed numbers are 4K; a small size checks the script itself)")
+    ap.add_argument("--modes", default="png", choices=("png", "exr"), help='"exr": T0 / E1 / E2 / E3, added to --out under "exr"')
     a = ap.parse_args()
     global W, H
     W, H = (int(v) for v in a.size.split("x"))
     run = Run(a.seed)
+    if a.modes == "exr":
+        return main_exr(run, a)
     result = dict(width=W, height=H, seed=a.seed, seconds=a.seconds, rounds={}, frames={})
     for streamed in (False, True):
         key = "streamed" if streamed else "resident"
