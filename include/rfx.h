@@ -574,6 +574,55 @@ typedef struct rfx_aov_frame {
 size_t rfx_aov_stage_bytes(const rfx_ctx *, const rfx_aov_frame *, int row0, int rows);
 int rfx_stage_aov(rfx_ctx *, const rfx_aov_frame *, int row0, int rows);
 
+/* ---- streamed EXR frames (additive to ABI 21: a host checks for the symbol): rfx_stage_aov for an AOV frame that is still a compressed OpenEXR
+ * file.  The scanline chunks cross PCIe as they sit in the file, on the upload stream; K9 (csrc/k9_exr_import.hip) inflates them — one wave per
+ * chunk, any RFC 1950 stream: stored, fixed and dynamic blocks, the Adler-32 checked —, undoes the predictor and the byte split, and scatters the
+ * mapped channels into the typed staging planes rfx_stage_aov copies into; the same fused pack kernel then writes the back buffers.  The texels
+ * are by construction the ones rfx_stage_aov writes for the planes a host decode of the file gives.  The host parses the header and the offset
+ * table (a few KiB) and does no per-pixel work.
+ * THE DESCRIPTOR.  `data` / `bytes`: the file (pinned memory makes the copies asynchronous).  Per part: its compression (OpenEXR's numbers: NONE 0,
+ * ZIPS 2, ZIP 3) and its channels IN FILE ORDER, each with its pixel type (OpenEXR's: HALF 1, FLOAT 2) and the AOV plane (RFX_EXR_PLANE_*: the
+ * index of the plane in rfx_aov_frame) and component it feeds, or plane RFX_EXR_SKIP: the channel is decoded with its chunk and dropped.  Per
+ * chunk: its part, the file offset of the PACKED DATA (behind the chunk's y and size fields), the packed size, the first scanline y (0 = top) and
+ * its rows.  Every part's data window is the frame (width x height of the context); a ZIP chunk has 16 rows but the last, the others one.
+ * A chunk whose packed size equals rows x the part's bytes per scanline is the raw block (OpenEXR's rule) and is copied, as is every NONE chunk.
+ * THE PLANES.  A plane exists when a channel maps to it; its components must be 0 .. n-1, each once, with n what rfx_stage_aov accepts (a
+ * diffuse or direct plane without component 3 has three channels: alpha 1).  A plane whose channels are all HALF is staged as RFX_PLANE_F16, else
+ * as RFX_PLANE_F32 with its halves widened.  The written-slot rules, the band rules, the host-pointer lifetime (`data`; the descriptor itself is
+ * consumed by the call) and the back pressure are rfx_stage_aov's, word for word, for those planes.
+ * THE BAND.  Only chunks with a scanline inside the band [row0, row0 + rows) (frame rows, 0 = bottom: scanline y is frame row height - 1 - y) are
+ * copied and decoded, each with one copy of exactly its packed bytes; a ZIP chunk that straddles the band's edge is decoded whole and only its
+ * rows inside the band are scattered.  Every scanline of the band must be covered by a chunk of every part that feeds a plane.
+ * rfx_exr_aov_stage_bytes returns exactly the bytes the call copies host -> device: the packed bytes of those chunks (0 for a frame the call
+ * would refuse).
+ * STATUS.  A chunk that does not decode (any byte string is safe to send: reads are bounded by the packed size, writes by the raw size) makes
+ * its rows read as not covered — depth 1, every other staged sample of it 0 — and is counted.  rfx_exr_aov_status blocks until the decode of the
+ * most recent rfx_stage_exr_aov call has executed and reports the number of bad chunks, the first bad chunk's index in the descriptor's table
+ * (-1: none) and its error code (csrc/k9_inflate.h K9_E_*; 0: none).  Any pointer may be NULL.  RFX_ESTATE before the first call.
+ * Packed bytes, inflate scratch and status live in staging areas the context owns: allocated on first use, grown only when a later call needs
+ * more (the one wait of this path), freed by rfx_destroy; nothing is allocated, freed or synchronised per call otherwise.
+ * RFX_EINVAL: a UINT channel or another pixel type; a compression other than the three; a chunk outside the file bytes; a chunk whose part, y or
+ * rows are inconsistent with the header (rows: 16 for ZIP but the last chunk, else 1; y a multiple of that; a packed size of 0 or of 2^30 or more,
+ * or different from the raw size in a NONE part); two chunks of a part on one scanline; a band scanline no chunk of a mapped part covers; a component mapped
+ * twice or missing; and what rfx_stage_aov refuses for the resulting planes (no depth, a partial G-buffer set, velocity without normal, a band
+ * outside DEPTH's rows).  RFX_ESTATE, RFX_ENOMEM: rfx_stage_aov's. */
+enum { RFX_EXR_NONE = 0, RFX_EXR_ZIPS = 2, RFX_EXR_ZIP = 3 };   /* rfx_exr_part.compression */
+enum { RFX_EXR_HALF = 1, RFX_EXR_FLOAT = 2 };                    /* rfx_exr_channel.pixel_type */
+enum { RFX_EXR_SKIP = -1, RFX_EXR_PLANE_DIFFUSE = 0, RFX_EXR_PLANE_NORMAL, RFX_EXR_PLANE_ROUGHNESS, RFX_EXR_PLANE_METALNESS, RFX_EXR_PLANE_EMISSIVE,
+       RFX_EXR_PLANE_VELOCITY, RFX_EXR_PLANE_DEPTH, RFX_EXR_PLANE_DIRECT };
+typedef struct rfx_exr_channel { int pixel_type; int plane; int component; } rfx_exr_channel;
+typedef struct rfx_exr_part { int compression; int channels; const rfx_exr_channel *channel; } rfx_exr_part;
+typedef struct rfx_exr_chunk { int part; int y; int rows; int reserved; unsigned long long offset; unsigned long long packed_bytes; } rfx_exr_chunk;
+typedef struct rfx_exr_frame {
+    const void *data; unsigned long long bytes;
+    int parts; int chunks;
+    const rfx_exr_part *part;
+    const rfx_exr_chunk *chunk;
+} rfx_exr_frame;
+size_t rfx_exr_aov_stage_bytes(const rfx_ctx *, const rfx_exr_frame *, int row0, int rows);
+int rfx_stage_exr_aov(rfx_ctx *, const rfx_exr_frame *, int row0, int rows);
+int rfx_exr_aov_status(rfx_ctx *, int *bad_chunks, int *first_bad, int *code);
+
 /* ---- row-tiled runs: the exchanges, one process per GPU, RCCL over xGMI.  RCCL is bound at run time (a
  * single-GPU host needs none; a process that already maps an RCCL — e.g. torch's — shares it).
  * Tiles: rank r of n owns rfx_split_rows(height, n, r) — boundaries on even rows, the last tile takes the remainder.  The exchanges run on a second stream of the context: each call orders itself AFTER all draws

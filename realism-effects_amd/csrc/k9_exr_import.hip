@@ -1,0 +1,228 @@
+// K9 — EXR import: the scanline chunks of an OpenEXR AOV file, as they sit in the file, -> the typed staging planes of rfx_stage_aov, on the device
+// (include/rfx.h "streamed EXR frames").  The inverse of K8's EXR fragment (k8_exr.h) for any deflate stream a writer may produce.
+//   k9_inflate     one wave per chunk.  The decoder is k9_inflate.h's, statement for statement the one the CPU tests run under the sanitizers;
+//                  here its state (bit buffer, positions, symbols) is wave-uniform — every lane computes the same values — and the IO below spreads
+//                  the memory work over the lanes: the input is read 256 bytes at a time, one dword per lane, and handed out by lane index; a literal
+//                  is stored by the lane its position names, a match or a stored run by all lanes, 64 bytes per step.  The chunk's scratch slot in
+//                  device memory is the output and the LZ77 window.  Decode tables: 3.5 KiB of LDS per wave (k9_inflate.h K9Tables), so LDS is not
+//                  what limits residency: the kernel's 112 VGPRs are, at 4 waves per SIMD, 16 per CU.  The parallelism is the number of chunks.  A chunk whose packed size is its raw size is copied.
+//   k9_exr_planes  one block per chunk: t[i] = t[i-1] + d[i] - 128 is a byte prefix sum (4 KiB tiles, 16 bytes per thread, a block scan of the
+//                  thread sums), in place; the even/odd byte split is undone while the samples are read; every mapped channel's row goes to its
+//                  plane, row 0 = bottom (EXR scanlines run top-down), halves widened where the plane is F32.
+//   k9_exr_finish  the rows of a chunk that did not decode: depth 1 (not covered), everything else 0 (written by k9_exr_planes); the status words.
+// All integer work: nothing here depends on contraction.
+#include "rfx_device.h"
+#include "rfx_kernels.h"
+#include "rfx_launch.h"
+
+#define K9_FN RFX_DEV
+#define K9_NO_HOST_IO
+#include "k9_inflate.h"
+
+namespace {
+
+// what one lane stored becomes visible to the other lanes of its wave (global memory and LDS), and the wave is back in step
+#if defined(__HIP_DEVICE_COMPILE__)
+#define K9_WAVE_FENCE() do { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); RFX_WAVE_JOIN(); } while (0)
+#else
+#define K9_WAVE_FENCE() RFX_WAVE_JOIN()
+#endif
+
+struct K9WaveIO {
+    const unsigned char *in;
+    size_t in_len, nwords;  // nwords = ceil(in_len / 4)
+    unsigned char *out;
+    K9Tables *t;
+    unsigned int *red;      // 128 words of LDS: the Adler sums of the lanes
+    int lane;
+    size_t win_base;        // the 64 input words [win_base, win_base + 64) sit one per lane in `win`
+    unsigned int win;
+    size_t synced;          // out[0, synced) is visible to every lane
+
+    RFX_DEV unsigned int word(size_t i) {
+        if (i >= nwords) return 0u;
+        const size_t base = i & ~(size_t)63;
+        if (base != win_base) {
+            const size_t k = base + (size_t)lane;
+            unsigned int w = 0u;
+            if (4 * k + 4 <= in_len) w = ((const unsigned int *)in)[k];  // (the packed bytes start 256-byte aligned)
+            else
+                for (int j = 0; j < 4; j++)
+                    if (4 * k + (size_t)j < in_len) w |= (unsigned int)in[4 * k + (size_t)j] << (8 * j);
+            win = w;
+            win_base = base;
+        }
+        return (unsigned int)__shfl((int)win, (int)(i & 63));
+    }
+    RFX_DEV void put(size_t pos, unsigned int byte) {
+        if (lane == (int)(pos & 63)) out[pos] = (unsigned char)byte;
+    }
+    RFX_DEV void copy(size_t pos, unsigned int dist, unsigned int len) {
+        const unsigned int span = dist < len ? dist : len;  // the source bytes: [pos - dist, pos - dist + span)
+        if (pos - dist + span > synced) {
+            K9_WAVE_FENCE();
+            synced = pos;
+        }
+        const unsigned char *src = out + (pos - dist);
+        for (unsigned int k = (unsigned int)lane; k < len; k += 64u) out[pos + k] = src[dist >= len ? k : k % dist];
+    }
+    RFX_DEV void copy_in(size_t pos, size_t src, unsigned int len) {
+        for (unsigned int k = (unsigned int)lane; k < len; k += 64u) out[pos + k] = in[src + k];
+    }
+    // 256 bytes per step, one dword per lane: a piece of m bytes ending e bytes before the end adds (sum, sum of (m - j) byte_j + e * sum) to (a, b).
+    // The sums stay below 2^64 for n < 2^30 (rfx_stage_exr_aov refuses a larger chunk) and are reduced once.
+    RFX_DEV unsigned int adler(size_t n) {
+        K9_WAVE_FENCE();
+        unsigned long long a = 0ull, b = 0ull;
+        for (size_t at = 4 * (size_t)lane; at < n; at += 256) {
+            const unsigned int m = n - at < 4 ? (unsigned int)(n - at) : 4u;
+            unsigned int by[4] = {0u, 0u, 0u, 0u};
+            if (m == 4u) {
+                const unsigned int w = *(const unsigned int *)(out + at);  // (the slot starts 256-byte aligned)
+                by[0] = w & 255u; by[1] = (w >> 8) & 255u; by[2] = (w >> 16) & 255u; by[3] = w >> 24;
+            } else
+                for (unsigned int j = 0; j < m; j++) by[j] = out[at + j];
+            const unsigned int s = by[0] + by[1] + by[2] + by[3];
+            unsigned int wsum = 0u;
+            for (unsigned int j = 0; j < m; j++) wsum += (m - j) * by[j];
+            a += s;
+            b += wsum + (unsigned long long)s * (unsigned long long)(n - at - m);
+        }
+        red[lane] = (unsigned int)(a % 65521ull);
+        red[64 + lane] = (unsigned int)(b % 65521ull);
+        K9_WAVE_FENCE();
+        unsigned long long ta = 1ull, tb = (unsigned long long)(n % 65521);
+        for (int l = 0; l < 64; l++) { ta += red[l]; tb += red[64 + l]; }
+        K9_WAVE_FENCE();  // (red is free again)
+        return ((unsigned int)(tb % 65521ull) << 16) | (unsigned int)(ta % 65521ull);
+    }
+    RFX_DEV K9Tables &tables() { return *t; }
+    RFX_DEV void sync() { K9_WAVE_FENCE(); }
+};
+
+RFX_DEV bool k9_raw_form(const K9Chunk &ck, const K9Part &pt) { return pt.stored || ck.packed == ck.raw; }
+
+__global__ __launch_bounds__(64) void k9_inflate(K9Args A) {
+    __shared__ K9Tables tables;
+    __shared__ unsigned int red[128];
+    const K9Chunk ck = A.chunks[blockIdx.x];
+    const K9Part pt = A.parts[ck.part];
+    const int lane = (int)threadIdx.x;
+    const unsigned char *in = A.packed + ck.src;
+    unsigned char *out = A.scratch + ck.dst;
+    int code = K9_OK;
+    if (k9_raw_form(ck, pt)) {  // (packed == raw: checked by the host for a NONE part)
+        const unsigned int words = ck.raw / 4u;
+        for (unsigned int k = (unsigned int)lane; k < words; k += 64u) ((unsigned int *)out)[k] = ((const unsigned int *)in)[k];
+        for (unsigned int k = words * 4u + (unsigned int)lane; k < ck.raw; k += 64u) out[k] = in[k];
+    } else {
+        K9WaveIO io;
+        io.in = in; io.in_len = ck.packed; io.nwords = ((size_t)ck.packed + 3) / 4; io.out = out; io.t = &tables; io.red = red; io.lane = lane;
+        io.win_base = ~(size_t)0; io.win = 0u; io.synced = 0;
+        code = k9_inflate_zlib(io, (size_t)ck.packed, (size_t)ck.raw);
+    }
+    if (lane == 0) A.err[blockIdx.x] = code;
+}
+
+constexpr int K9_PLANES_BLOCK = 256, K9_SCAN_BYTES = 16;
+// frame row fy of `plane`: the segment that stages it, or -1
+RFX_DEV int k9_segment(const K9Args &A, int plane, int fy) {
+    for (int s = 0; s < A.nseg; s++)
+        if (fy >= A.seg_row0[s] && fy < A.seg_row0[s] + A.seg_rows[s] && A.seg_plane[s][plane]) return s;
+    return -1;
+}
+__global__ __launch_bounds__(K9_PLANES_BLOCK) void k9_exr_planes(K9Args A) {
+    __shared__ unsigned int scan[K9_PLANES_BLOCK];
+    const K9Chunk ck = A.chunks[blockIdx.x];
+    const K9Part pt = A.parts[ck.part];
+    unsigned char *buf = A.scratch + ck.dst;
+    const int tid = (int)threadIdx.x;
+    const int err = A.err[blockIdx.x];
+    const bool raw_form = k9_raw_form(ck, pt);
+    const unsigned int n = ck.raw;
+    if (!raw_form && !err) {
+        unsigned int carry = 0u;  // the sum of every d[j] - 128 before the tile, mod 256
+        for (unsigned int tile = 0; tile < n; tile += K9_PLANES_BLOCK * K9_SCAN_BYTES) {
+            const unsigned int at = tile + (unsigned int)tid * K9_SCAN_BYTES;
+            const unsigned int m = at >= n ? 0u : (n - at < K9_SCAN_BYTES ? n - at : (unsigned int)K9_SCAN_BYTES);
+            unsigned char d[K9_SCAN_BYTES];
+            if (m == K9_SCAN_BYTES) {
+                const uint4 w = *(const uint4 *)(buf + at);  // (the slot starts 256-byte aligned)
+                const unsigned int ws[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+                for (int k = 0; k < K9_SCAN_BYTES; k++) d[k] = (unsigned char)(ws[k >> 2] >> (8 * (k & 3)));
+            } else
+                for (unsigned int k = 0; k < m; k++) d[k] = buf[at + k];
+            unsigned int run = 0u;
+            for (unsigned int k = 0; k < m; k++) {
+                run = (run + d[k] + 128u) & 255u;  // (+128 = -128 mod 256)
+                d[k] = (unsigned char)run;
+            }
+            scan[tid] = run;
+            __syncthreads();
+            for (int off = 1; off < K9_PLANES_BLOCK; off <<= 1) {
+                const unsigned int v = tid >= off ? scan[tid - off] : 0u;
+                __syncthreads();
+                scan[tid] += v;
+                __syncthreads();
+            }
+            const unsigned int before = (carry + scan[tid] - run) & 255u;  // every byte before this thread's run
+            carry = (carry + scan[K9_PLANES_BLOCK - 1]) & 255u;
+            for (unsigned int k = 0; k < m; k++) buf[at + k] = (unsigned char)(before + d[k] + 128u);  // t[i] = 128 + the sum of d[j] - 128, j <= i
+            __syncthreads();
+        }
+    }
+    __syncthreads();
+    const unsigned int half_n = (n + 1u) / 2u;  // the even-indexed bytes of the raw block come first
+    const auto raw_byte = [&](unsigned int p) -> unsigned int { return raw_form ? buf[p] : ((p & 1u) ? buf[half_n + (p >> 1)] : buf[p >> 1]); };
+    const unsigned int per_row = (unsigned int)pt.nchan * (unsigned int)A.W, total = (unsigned int)ck.rows * per_row;
+    for (unsigned int i = (unsigned int)tid; i < total; i += K9_PLANES_BLOCK) {
+        const unsigned int r = i / per_row, rem = i - r * per_row, c = rem / (unsigned int)A.W, x = rem - c * (unsigned int)A.W;
+        const K9Chan ch = A.chans[pt.chan0 + (int)c];
+        if (ch.plane < 0) continue;
+        const int fy = A.H - 1 - (ck.y + (int)r);
+        const int s = k9_segment(A, ch.plane, fy);
+        if (s < 0) continue;
+        const size_t dst = ((size_t)(fy - A.seg_row0[s]) * A.W + x) * A.plane_ch[ch.plane] + ch.comp;
+        unsigned int bits;
+        if (err) {
+            bits = 0u;
+        } else {
+            const unsigned int p = r * pt.row_bytes + ch.row_off + x * (ch.half ? 2u : 4u);
+            bits = raw_byte(p) | (raw_byte(p + 1u) << 8);
+            if (!ch.half) bits |= (raw_byte(p + 2u) << 16) | (raw_byte(p + 3u) << 24);
+        }
+        if (A.plane_half[ch.plane]) ((unsigned short *)A.seg_plane[s][ch.plane])[dst] = (unsigned short)bits;  // (every channel of the plane is HALF)
+        else ((float *)A.seg_plane[s][ch.plane])[dst] = ch.half ? rfx_h2f((unsigned short)bits) : __uint_as_float(bits);
+    }
+}
+
+__global__ __launch_bounds__(256) void k9_exr_finish(K9Args A) {
+    const int err = A.err[blockIdx.x];
+    if (!err) return;
+    const K9Chunk ck = A.chunks[blockIdx.x];
+    if (threadIdx.x == 0) {
+        atomicAdd((unsigned int *)A.status, 1u);
+        atomicMax(A.status + 1, 0x7fffffff - ((ck.index << 8) | err));
+    }
+    const unsigned int total = (unsigned int)ck.rows * (unsigned int)A.W;
+    for (unsigned int i = threadIdx.x; i < total; i += 256u) {
+        const unsigned int r = i / (unsigned int)A.W, x = i - r * (unsigned int)A.W;
+        const int fy = A.H - 1 - (ck.y + (int)r);
+        const int s = k9_segment(A, RFX_AOV_DEPTH, fy);
+        if (s < 0) continue;
+        const size_t dst = (size_t)(fy - A.seg_row0[s]) * A.W + x;
+        if (A.plane_half[RFX_AOV_DEPTH]) ((unsigned short *)A.seg_plane[s][RFX_AOV_DEPTH])[dst] = (unsigned short)0x3c00u;
+        else ((float *)A.seg_plane[s][RFX_AOV_DEPTH])[dst] = 1.0f;
+    }
+}
+
+}  // namespace
+
+hipError_t rfx_launch_k9(const K9Args &A, hipStream_t stream) {
+    if (A.nchunks <= 0 || !A.chunks || !A.parts || !A.chans || !A.packed || !A.scratch || !A.err || !A.status) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k9_inflate, dim3(A.nchunks), dim3(64), 0, stream, A);
+    hipLaunchKernelGGL(k9_exr_planes, dim3(A.nchunks), dim3(K9_PLANES_BLOCK), 0, stream, A);
+    hipLaunchKernelGGL(k9_exr_finish, dim3(A.nchunks), dim3(256), 0, stream, A);
+    return hipGetLastError();
+}

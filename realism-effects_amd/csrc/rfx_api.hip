@@ -127,6 +127,11 @@ void rfx_destroy(rfx_ctx *c) {
         if (c->slots[i].back) hipFree(c->slots[i].back);
     }
     if (c->aov_stage) hipFree(c->aov_stage);
+    if (c->exr_stage) hipFree(c->exr_stage);
+    for (void *p : c->exr_tables_host)
+        if (p) hipHostFree(p);
+    if (c->exr_status_host) hipHostFree(c->exr_status_host);
+    if (c->ev_exr_status) hipEventDestroy(c->ev_exr_status);
     for (hipEvent_t e : c->ev_batch)
         if (e) hipEventDestroy(e);
     if (c->ev_staged) hipEventDestroy(c->ev_staged);
@@ -343,6 +348,17 @@ static const char *aov_plan(const rfx_ctx *c, const rfx_aov_frame *f, int row0, 
     return rfx_aov_plan_for(c->W, c->H, g.row0, g.rows, type, channels, row0, rows, t);
 }
 
+// one segment's pack launch on the upload stream: A holds the segment's staged planes, their half mask and the rgb(a) channel counts
+static hipError_t aov_pack_segment(rfx_ctx *c, const rfx_aov_plan &t, const rfx_aov_segment &g, K0AovArgs A) {
+    const auto first = [&](int id) { return slot_back_row(c->slots[id], g.row0); };
+    A.depth = (float *)first(RFX_TEX_DEPTH);
+    if (g.full && t.write_gbuffer) A.gbuffer = (uint4 *)first(RFX_TEX_GBUFFER);
+    if (g.full && t.write_velocity) A.velocity = (uint4 *)first(RFX_TEX_VELOCITY);
+    if (g.full && t.write_direct) A.direct = (uint4 *)first(RFX_TEX_DIRECT_LIGHT);
+    A.groups = g.groups; A.tail_start = g.tail_start; A.tail_pixels = g.tail_pixels;
+    return rfx_launch_k0_aov(A, g.blocks, c->upload_stream);
+}
+
 size_t rfx_aov_stage_bytes(const rfx_ctx *c, const rfx_aov_frame *f, int row0, int rows) {
     rfx_aov_plan t;
     if (!c || !f || aov_plan(c, f, row0, rows, &t)) return 0;
@@ -389,16 +405,211 @@ int rfx_stage_aov(rfx_ctx *c, const rfx_aov_frame *f, int row0, int rows) {
             if (p.type == RFX_PLANE_F16) A.half_mask |= 1u << i;
         }
         A.diffuse_ch = f->diffuse.channels; A.direct_ch = f->direct.channels;
-        const auto first = [&](int id) { return slot_back_row(c->slots[id], g.row0); };
-        A.depth = (float *)first(RFX_TEX_DEPTH);
-        if (g.full && t.write_gbuffer) A.gbuffer = (uint4 *)first(RFX_TEX_GBUFFER);
-        if (g.full && t.write_velocity) A.velocity = (uint4 *)first(RFX_TEX_VELOCITY);
-        if (g.full && t.write_direct) A.direct = (uint4 *)first(RFX_TEX_DIRECT_LIGHT);
-        A.groups = g.groups; A.tail_start = g.tail_start; A.tail_pixels = g.tail_pixels;
-        HIPCHK(c, rfx_launch_k0_aov(A, g.blocks, c->upload_stream));
+        HIPCHK(c, aov_pack_segment(c, t, g, A));
     }
     for (int k = 0; k < 4; k++)
         if (writes[k]) c->slots[ids[k]].back_filled = true;
+    return RFX_OK;
+}
+
+// ---- streamed EXR frames (include/rfx.h): the file's chunks cross PCIe packed; K9 (k9_exr_import.hip) turns them into the staged planes of the
+// plan above, and the same pack launches follow
+struct ExrPlan {
+    rfx_aov_plan aov;
+    int type[RFX_AOV_PLANES], channels[RFX_AOV_PLANES];
+    std::vector<K9Part> parts;
+    std::vector<K9Chan> chans;
+    std::vector<K9Chunk> chunks;  // the ones the band needs, in the descriptor's order
+    std::vector<unsigned long long> file_offset;  // of each of them
+    unsigned long long copy_bytes = 0, packed_bytes = 0, scratch_bytes = 0;  // host -> device; the two device areas (256-byte-aligned pieces)
+};
+static unsigned long long align256(unsigned long long n) { return (n + 255ull) & ~255ull; }
+// the call's checks and layout, a pure function of the descriptor and the context's geometry.  0, or the RFX_EINVAL case in words.
+static const char *exr_plan(const rfx_ctx *c, const rfx_exr_frame *f, int row0, int rows, ExrPlan *p) {
+    static const int want_max[RFX_AOV_PLANES] = {4, 3, 1, 1, 3, 2, 1, 4};
+    if (!f->data || !f->bytes || f->parts <= 0 || f->chunks <= 0 || !f->part || !f->chunk) return "an empty descriptor";
+    if (f->chunks >= (1 << 23) || f->parts > 4096) return "more than 2^23 chunks or 4096 parts";
+    const int W = c->W, H = c->H;
+    unsigned int comp_mask[RFX_AOV_PLANES] = {0}, any_float[RFX_AOV_PLANES] = {0};
+    std::vector<char> mapped((size_t)f->parts, 0);
+    for (int k = 0; k < f->parts; k++) {
+        const rfx_exr_part &q = f->part[k];
+        if (q.compression != RFX_EXR_NONE && q.compression != RFX_EXR_ZIPS && q.compression != RFX_EXR_ZIP) return "a part's compression is none of NONE, ZIPS, ZIP";
+        if (q.channels <= 0 || q.channels > 1024 || !q.channel) return "a part's channel list";
+        K9Part part = {(int)p->chans.size(), q.channels, 0u, q.compression == RFX_EXR_NONE};
+        for (int i = 0; i < q.channels; i++) {
+            const rfx_exr_channel &ch = q.channel[i];
+            if (ch.pixel_type != RFX_EXR_HALF && ch.pixel_type != RFX_EXR_FLOAT) return "a channel's pixel type must be HALF or FLOAT (UINT channels are not streamed)";
+            if (ch.plane < RFX_EXR_SKIP || ch.plane >= RFX_AOV_PLANES) return "a channel's plane";
+            const bool half = ch.pixel_type == RFX_EXR_HALF;
+            if (ch.plane >= 0) {
+                if (ch.component < 0 || ch.component >= want_max[ch.plane]) return "a channel's component";
+                if (comp_mask[ch.plane] & (1u << ch.component)) return "two channels feed one component of a plane";
+                comp_mask[ch.plane] |= 1u << ch.component;
+                any_float[ch.plane] |= half ? 0u : 1u;
+                mapped[k] = 1;
+            }
+            p->chans.push_back({half ? 1 : 0, ch.plane, ch.plane >= 0 ? ch.component : 0, part.row_bytes});
+            part.row_bytes += (unsigned int)W * (half ? 2u : 4u);  // (W <= 32768, at most 1024 channels: < 2^27)
+        }
+        p->parts.push_back(part);
+    }
+    for (int i = 0; i < RFX_AOV_PLANES; i++) {
+        int n = 0;
+        while (comp_mask[i] >> n & 1u) n++;
+        if (comp_mask[i] != (1u << n) - 1u) return "a plane's components must be 0 .. n-1, each fed by one channel";
+        p->channels[i] = n;
+        p->type[i] = any_float[i] ? RFX_PLANE_F32 : RFX_PLANE_F16;
+    }
+    const Slot &g = c->slots[RFX_TEX_GBUFFER];
+    if (const char *bad = rfx_aov_plan_for(W, H, g.row0, g.rows, p->type, p->channels, row0, rows, &p->aov)) return bad;
+    const int y_lo = H - row0 - rows, y_hi = H - row0;  // the band's scanlines, top first
+    std::vector<char> covered((size_t)f->parts * (size_t)rows, 0);
+    for (int k = 0; k < f->chunks; k++) {
+        const rfx_exr_chunk &q = f->chunk[k];
+        if (q.part < 0 || q.part >= f->parts) return "a chunk's part";
+        const K9Part &part = p->parts[q.part];
+        const int per = f->part[q.part].compression == RFX_EXR_ZIP ? 16 : 1;
+        if (q.y < 0 || q.y >= H || q.y % per || q.rows != (H - q.y < per ? H - q.y : per)) return "a chunk's scanline or row count does not fit its part's header";
+        const unsigned long long raw = (unsigned long long)q.rows * part.row_bytes;
+        if (raw >= (1ull << 30)) return "a chunk of 2^30 raw bytes or more";
+        if (q.packed_bytes == 0 || q.packed_bytes >= (1ull << 30) || (part.stored && q.packed_bytes != raw)) return "a chunk's packed size does not fit its rows";
+        if (q.offset > f->bytes || q.packed_bytes > f->bytes - q.offset) return "a chunk lies outside the file bytes";
+        if (!mapped[q.part] || q.y >= y_hi || q.y + q.rows <= y_lo) continue;
+        for (int y = q.y > y_lo ? q.y : y_lo; y < q.y + q.rows && y < y_hi; y++) {
+            char &seen = covered[(size_t)q.part * (size_t)rows + (size_t)(y - y_lo)];
+            if (seen) return "two chunks of a part hold one scanline";
+            seen = 1;
+        }
+        p->chunks.push_back({p->packed_bytes, p->scratch_bytes, (unsigned int)q.packed_bytes, (unsigned int)raw, q.part, q.y, q.rows, k});
+        p->file_offset.push_back(q.offset);
+        p->copy_bytes += q.packed_bytes;
+        p->packed_bytes += align256(q.packed_bytes);
+        p->scratch_bytes += align256(raw);
+    }
+    for (int k = 0; k < f->parts; k++)
+        for (int y = 0; mapped[k] && y < rows; y++)
+            if (!covered[(size_t)k * (size_t)rows + (size_t)y]) return "a scanline of the band has no chunk in a part that feeds a plane";
+    return nullptr;
+}
+
+size_t rfx_exr_aov_stage_bytes(const rfx_ctx *c, const rfx_exr_frame *f, int row0, int rows) {
+    ExrPlan p;
+    if (!c || !f || exr_plan(c, f, row0, rows, &p)) return 0;
+    return (size_t)p.copy_bytes;
+}
+
+// a device area of the context grows: the one wait of the staged paths (an earlier call's kernels may still be using the area that goes)
+static int grow_stage_area(rfx_ctx *c, void **area, size_t *cap, size_t need, const char *what) {
+    if (*cap >= need) return RFX_OK;
+    if (*area) { HIPCHK(c, hipStreamSynchronize(c->upload_stream)); hipFree(*area); }
+    *area = nullptr;
+    *cap = 0;
+    hipError_t e = hipMalloc(area, need);
+    if (e != hipSuccess) return fail(c, RFX_ENOMEM, what, e);
+    *cap = need;
+    return RFX_OK;
+}
+
+int rfx_stage_exr_aov(rfx_ctx *c, const rfx_exr_frame *f, int row0, int rows) {
+    if (!c || !f) return RFX_EINVAL;
+    RFX_ENTER(c);
+    ExrPlan p;
+    if (const char *bad = exr_plan(c, f, row0, rows, &p)) return fail_in(c, RFX_EINVAL, "rfx_stage_exr_aov", bad);
+    const rfx_aov_plan &t = p.aov;
+    const int ids[4] = {RFX_TEX_DEPTH, RFX_TEX_GBUFFER, RFX_TEX_VELOCITY, RFX_TEX_DIRECT_LIGHT};
+    const bool writes[4] = {true, t.write_gbuffer != 0, t.write_velocity != 0, t.write_direct != 0};
+    int rc;
+    for (int k = 0; k < 4; k++) {  // every check before anything is enqueued
+        if (!writes[k]) continue;
+        if ((rc = ensure(c, ids[k]))) return rc;
+        if (!c->slots[ids[k]].owned) return fail_in(c, RFX_ESTATE, "rfx_stage_exr_aov", "a slot to be written is bound to an external buffer");
+    }
+    if ((rc = stage_streams(c))) return rc;
+    for (int k = 0; k < 4; k++)
+        if (writes[k] && (rc = stage_back(c, c->slots[ids[k]]))) return rc;
+    // the device area: parts | channels | chunks | error words | status | packed bytes | inflate scratch, every piece 256-byte aligned
+    const size_t n = p.chunks.size();
+    const size_t parts_b = align256(p.parts.size() * sizeof(K9Part)), chans_b = align256(p.chans.size() * sizeof(K9Chan)), chunks_b = align256(n * sizeof(K9Chunk));
+    const size_t tables_b = parts_b + chans_b + chunks_b, err_b = align256(n * sizeof(int)), status_b = 256;
+    const size_t need = tables_b + err_b + status_b + (size_t)p.packed_bytes + (size_t)p.scratch_bytes;
+    if ((rc = grow_stage_area(c, &c->aov_stage, &c->aov_stage_cap, (size_t)t.stage_bytes, "rfx_stage_exr_aov: hipMalloc(staging area)"))) return rc;
+    if ((rc = grow_stage_area(c, &c->exr_stage, &c->exr_stage_cap, need, "rfx_stage_exr_aov: hipMalloc(chunk area)"))) return rc;
+    if (!c->ev_exr_status) {
+        hipError_t e = hipEventCreateWithFlags(&c->ev_exr_status, hipEventDisableTiming);
+        if (e != hipSuccess) return fail(c, RFX_EDEVICE, "rfx_stage_exr_aov: the status event", e);
+    }
+    if (!c->exr_status_host) {
+        hipError_t e = hipHostMalloc((void **)&c->exr_status_host, 2 * sizeof(int), hipHostMallocDefault);
+        if (e != hipSuccess) { c->exr_status_host = nullptr; return fail(c, RFX_ENOMEM, "rfx_stage_exr_aov: the status block", e); }
+    }
+    // the tables, written into this batch's pinned block behind what an earlier call of the batch put there
+    const int hb = (int)(c->flips & 1u);
+    if (c->exr_tables_batch[hb] != c->flips) { c->exr_tables_batch[hb] = c->flips; c->exr_tables_used[hb] = 0; }
+    if (c->exr_tables_used[hb] + tables_b > c->exr_tables_cap[hb]) {
+        if (c->exr_tables_host[hb]) { HIPCHK(c, hipStreamSynchronize(c->upload_stream)); hipHostFree(c->exr_tables_host[hb]); }  // (grown: as the device areas)
+        c->exr_tables_host[hb] = nullptr;
+        c->exr_tables_cap[hb] = c->exr_tables_used[hb] = 0;
+        hipError_t e = hipHostMalloc(&c->exr_tables_host[hb], 2 * tables_b, hipHostMallocDefault);
+        if (e != hipSuccess) return fail(c, RFX_ENOMEM, "rfx_stage_exr_aov: hipHostMalloc(tables)", e);
+        c->exr_tables_cap[hb] = 2 * tables_b;
+    }
+    char *tables = (char *)c->exr_tables_host[hb] + c->exr_tables_used[hb];
+    c->exr_tables_used[hb] += tables_b;
+    memset(tables, 0, tables_b);
+    memcpy(tables, p.parts.data(), p.parts.size() * sizeof(K9Part));
+    memcpy(tables + parts_b, p.chans.data(), p.chans.size() * sizeof(K9Chan));
+    memcpy(tables + parts_b + chans_b, p.chunks.data(), n * sizeof(K9Chunk));
+    char *dev = (char *)c->exr_stage;
+    // rfx_stage_upload's order: the back buffers were the front buffers until the last flip
+    HIPCHK(c, hipStreamWaitEvent(c->upload_stream, c->ev_frame_done, 0));
+    HIPCHK(c, hipMemcpyAsync(dev, tables, tables_b, hipMemcpyHostToDevice, c->upload_stream));
+    HIPCHK(c, hipMemsetAsync(dev + tables_b + err_b, 0, status_b, c->upload_stream));
+    char *packed = dev + tables_b + err_b + status_b;
+    for (size_t k = 0; k < n; k++)  // exactly the packed bytes of every chunk the band needs
+        HIPCHK(c, hipMemcpyAsync(packed + p.chunks[k].src, (const char *)f->data + p.file_offset[k], p.chunks[k].packed, hipMemcpyHostToDevice, c->upload_stream));
+    K9Args A = {};
+    A.parts = (const K9Part *)dev; A.chans = (const K9Chan *)(dev + parts_b); A.chunks = (const K9Chunk *)(dev + parts_b + chans_b);
+    A.nchunks = (int)n;
+    A.err = (int *)(dev + tables_b); A.status = (int *)(dev + tables_b + err_b);
+    A.packed = (const unsigned char *)packed; A.scratch = (unsigned char *)packed + p.packed_bytes;
+    A.W = c->W; A.H = c->H;
+    A.nseg = t.nseg;
+    unsigned int half_mask = 0;
+    for (int i = 0; i < RFX_AOV_PLANES; i++) {
+        A.plane_ch[i] = p.channels[i];
+        A.plane_half[i] = p.channels[i] && p.type[i] == RFX_PLANE_F16;
+        if (A.plane_half[i]) half_mask |= 1u << i;
+    }
+    for (int k = 0; k < t.nseg; k++) {
+        A.seg_row0[k] = t.seg[k].row0; A.seg_rows[k] = t.seg[k].rows;
+        for (int i = 0; i < RFX_AOV_PLANES; i++) A.seg_plane[k][i] = t.seg[k].offset[i] == ~0ull ? nullptr : (char *)c->aov_stage + t.seg[k].offset[i];
+    }
+    HIPCHK(c, rfx_launch_k9(A, c->upload_stream));
+    HIPCHK(c, hipMemcpyAsync(c->exr_status_host, A.status, 2 * sizeof(int), hipMemcpyDeviceToHost, c->upload_stream));
+    HIPCHK(c, hipEventRecord(c->ev_exr_status, c->upload_stream));
+    c->exr_staged = true;
+    for (int k = 0; k < t.nseg; k++) {
+        K0AovArgs P = {};
+        for (int i = 0; i < RFX_AOV_PLANES; i++) P.plane[i] = A.seg_plane[k][i];
+        P.half_mask = half_mask;
+        P.diffuse_ch = p.channels[RFX_AOV_DIFFUSE]; P.direct_ch = p.channels[RFX_AOV_DIRECT];
+        HIPCHK(c, aov_pack_segment(c, t, t.seg[k], P));
+    }
+    for (int k = 0; k < 4; k++)
+        if (writes[k]) c->slots[ids[k]].back_filled = true;
+    return RFX_OK;
+}
+
+int rfx_exr_aov_status(rfx_ctx *c, int *bad_chunks, int *first_bad, int *code) {
+    if (!c) return RFX_EINVAL;
+    RFX_ENTER(c);
+    if (!c->exr_staged) return fail(c, RFX_ESTATE, "rfx_exr_aov_status: no EXR frame has been staged");
+    HIPCHK(c, hipEventSynchronize(c->ev_exr_status));
+    const int bad = c->exr_status_host[0], key = c->exr_status_host[1] ? 0x7fffffff - c->exr_status_host[1] : -1;
+    if (bad_chunks) *bad_chunks = bad;
+    if (first_bad) *first_bad = key < 0 ? -1 : key >> 8;
+    if (code) *code = key < 0 ? 0 : key & 255;
     return RFX_OK;
 }
 

@@ -81,6 +81,17 @@ struct rfx_ctx {
     // texture slot nor checkpoint state
     void *aov_stage = nullptr;
     size_t aov_stage_cap = 0;
+    // rfx_stage_exr_aov: the device area of a call's tables, packed chunks and inflate scratch (the same owner and growth rule); two pinned host
+    // blocks the tables are written into before they are copied (batch n uses block n & 1: rfx_stage_flip's back pressure says the copies of batch
+    // n - 2 have executed; calls of one batch append); the pinned status words and the event behind their copy
+    void *exr_stage = nullptr;
+    size_t exr_stage_cap = 0;
+    void *exr_tables_host[2] = {nullptr, nullptr};
+    size_t exr_tables_cap[2] = {0, 0}, exr_tables_used[2] = {0, 0};
+    unsigned int exr_tables_batch[2] = {0, 0};
+    int *exr_status_host = nullptr;
+    hipEvent_t ev_exr_status = nullptr;
+    bool exr_staged = false;
     // streamed export (rfx_stage_export): a fourth stream for the device-to-host copies, two device staging buffers the encodes alternate
     // between (export n uses buffer n & 1), and per buffer the event behind its last encode (draw stream) and its last copy (download stream)
     hipStream_t download_stream = nullptr;

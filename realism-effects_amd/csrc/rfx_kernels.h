@@ -194,3 +194,32 @@ struct K8ExrArgs {
     unsigned slot_stride, plane_stride;
 };
 hipError_t rfx_launch_k8_exr(const K8ExrArgs &, hipStream_t);
+
+// K9 EXR import (k9_exr_import.hip): the packed scanline chunks of an OpenEXR file -> the typed AOV staging planes k0_aov_pack reads (include/rfx.h
+// "streamed EXR frames").  Three launches on `stream`: k9_inflate (one wave per chunk: zlib stream or raw block -> the chunk's scratch slot),
+// k9_exr_planes (one block per chunk: predictor and byte split undone, the mapped channels scattered, rows flipped), k9_exr_finish (the rows of a
+// bad chunk read as not covered; the status words).  The tables are device copies of the call's descriptor, built by rfx_stage_exr_aov.
+struct K9Chunk {
+    unsigned long long src, dst;  // 256-byte-aligned offsets of the packed bytes / of the scratch slot (raw bytes, which is the LZ77 window too)
+    unsigned int packed, raw;     // packed == raw: the raw block itself
+    int part, y, rows;            // y: the EXR scanline (0 = top) of the chunk's first row
+    int index;                    // in the descriptor's chunk table (what the status reports)
+};
+struct K9Chan { int half, plane, comp; unsigned int row_off; };  // plane < 0: dropped; row_off: bytes from the scanline's start to the channel's W samples
+struct K9Part { int chan0, nchan; unsigned int row_bytes; int stored; };  // stored: compression NONE
+struct K9Args {
+    const K9Chunk *chunks;
+    const K9Part *parts;
+    const K9Chan *chans;
+    int nchunks;
+    const unsigned char *packed;
+    unsigned char *scratch;
+    int *err;                  // per chunk: k9_inflate.h's K9_E_* (0: decoded)
+    int *status;               // [0] bad chunks, [1] 0x7fffffff - ((index << 8) | code) of the first bad chunk (0: none), zeroed before the launches
+    int W, H;
+    int nseg;                  // rfx_aov_plan's segments: frame rows [seg_row0, seg_row0 + seg_rows) and where each plane's rows of them are staged
+    int seg_row0[3], seg_rows[3];
+    void *seg_plane[3][8];     // null: the segment does not read the plane
+    int plane_ch[8], plane_half[8];
+};
+hipError_t rfx_launch_k9(const K9Args &, hipStream_t);

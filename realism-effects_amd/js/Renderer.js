@@ -133,6 +133,19 @@ class Renderer {
 	aovStageBytes(planes, row0, rows) {
 		return addon.aovStageBytes(this._h, planes, row0 === undefined ? 0 : row0, rows === undefined ? this.height - (row0 || 0) : rows)
 	}
+	// streamed EXR frames (rfx.h): stageAov for a frame that is still an OpenEXR file — `bytes` the file (a Uint8Array / Buffer; over hostAlloc
+	// memory the copies are asynchronous), `layout` = imageio.exrAovLayout(bytes): the chunks of the band cross PCIe packed and are decoded on
+	// the device.  exrAovStatus() waits for that decode -> [bad chunks, index of the first bad chunk or -1, its error code or 0]
+	stageExrAov(bytes, layout, row0, rows) {
+		addon.stageExrAov(this._h, bytes, layout.parts, layout.chunks, row0 === undefined ? 0 : row0, rows === undefined ? this.height - (row0 || 0) : rows)
+		;(this._stagedExrNow = this._stagedExrNow || []).push(bytes) // kept alive until the copies of this batch have executed (stageFlip)
+	}
+	exrAovStageBytes(bytes, layout, row0, rows) {
+		return addon.exrAovStageBytes(this._h, bytes, layout.parts, layout.chunks, row0 === undefined ? 0 : row0, rows === undefined ? this.height - (row0 || 0) : rows)
+	}
+	exrAovStatus() {
+		return addon.exrAovStatus(this._h)
+	}
 	// a frame with packed planes, or — no `gbuffer` — with `aov` attribute planes
 	stageFrame(frame) {
 		if (!frame.gbuffer) {
@@ -151,6 +164,9 @@ class Renderer {
 	}
 	stageFlip() {
 		addon.stageFlip(this._h)
+		// rfx_stage_flip returns when the copies published by the PREVIOUS flip have executed: keep this batch's file bytes and the one before's
+		this._stagedExrKeep = [this._stagedExrKeep ? this._stagedExrKeep[1] : [], this._stagedExrNow || []]
+		this._stagedExrNow = []
 	}
 
 	// streamed frame export (rfx.h "streamed frame export"): the tile rows of `source`, encoded on the device.  params: { source, format: EXPORT.*

@@ -194,4 +194,118 @@ function writePFM(file, rgba, width, height, channels) {
 	fs.writeFileSync(file, Buffer.concat([Buffer.from("PF\n" + width + " " + height + "\n-1.0\n", "ascii"), body]))
 }
 
-module.exports = { writePNG, pngFromFragments, writeEXR, exrFromFragments, writePFM, tonemap }
+// ---- AOV EXR -> the descriptor of the device decode (rfx.h "streamed EXR frames"; the twin of rfx_amd/imageio.py exr_aov_layout)
+// layer.channel names an AOV EXR is expected to carry, in rfx_aov_frame's plane order (pass `names` to override a layer's channels)
+const AOV_LAYOUT = {
+	diffuse: ["diffuse.R", "diffuse.G", "diffuse.B", "diffuse.A"],
+	normal: ["normal.X", "normal.Y", "normal.Z"],
+	roughness: ["roughness.Y"],
+	metalness: ["metalness.Y"],
+	emissive: ["emissive.R", "emissive.G", "emissive.B"],
+	velocity: ["velocity.X", "velocity.Y"],
+	depth: ["depth.Z"],
+	direct: ["direct.R", "direct.G", "direct.B", "direct.A"]
+}
+class ExrNotStreamable extends Error {}
+// Parse the header(s) and offset table(s) of a scanline AOV EXR held in `buffer` (a Buffer / Uint8Array: the whole file).  Returns
+// { width, height, fileBytes, parts: Int32Array, chunks: Uint8Array, chunkCount, planes: { name: [channels, "half" | "float"] } } — `parts` and
+// `chunks` in the layout Renderer.stageExrAov hands to the addon: parts = [n, then per part: compression, channels, then per channel: pixel type,
+// plane or -1, component]; chunks = 32-byte records { int32 part, y, rows, 0; uint64 offset of the packed data, packed bytes }.
+// Throws ExrNotStreamable for what stays on the host: tiled or deep files, RLE / PIZ / PXR24 parts, UINT channels, a dataWindow that is not the
+// displayWindow.
+function exrAovLayout(buffer, names) {
+	const b = Buffer.from(buffer.buffer, buffer.byteOffset, buffer.byteLength)
+	if (b.length < 8 || b.readUInt32LE(0) !== 0x01312f76) throw new Error("not an OpenEXR file")
+	const version = b.readInt32LE(4)
+	if (version & 0x800) throw new ExrNotStreamable("deep data")
+	if (version & 0x200) throw new ExrNotStreamable("a tiled file")
+	const multipart = !!(version & 0x1000)
+	const cstr = pos => {
+		const e = b.indexOf(0, pos)
+		if (e < 0) throw new Error("damaged EXR header")
+		return [b.toString("latin1", pos, e), e + 1]
+	}
+	const headers = []
+	let pos = 8
+	for (;;) {
+		const attrs = {}
+		while (b[pos] !== 0) {
+			let name, type
+			;[name, pos] = cstr(pos)
+			;[type, pos] = cstr(pos)
+			const n = b.readInt32LE(pos)
+			attrs[name] = b.subarray(pos + 4, pos + 4 + n)
+			pos += 4 + n
+		}
+		pos++
+		headers.push(attrs)
+		if (!multipart || b[pos] === 0) break
+	}
+	if (multipart) pos++
+	const layout = Object.assign({}, AOV_LAYOUT, names || {})
+	const feeds = {}
+	Object.keys(AOV_LAYOUT).forEach((key, pi) => layout[key].forEach((cn, j) => (feeds[cn] = [pi, j])))
+	const partWords = [headers.length], records = [], seen = {}
+	let W = -1, H = -1
+	headers.forEach((attrs, k) => {
+		const type = attrs.type ? attrs.type.toString("latin1").replace(/\0+$/, "") : "scanlineimage"
+		if (type !== "scanlineimage") throw new ExrNotStreamable("a part of type " + type)
+		const comp = attrs.compression[0]
+		if (comp !== 0 && comp !== 2 && comp !== 3) {
+			if (comp === 1 || comp === 4 || comp === 5) throw new ExrNotStreamable("compression " + { 1: "RLE", 4: "PIZ", 5: "PXR24" }[comp])
+			throw new Error("compression " + comp + " not supported")
+		}
+		if (Buffer.compare(attrs.dataWindow, attrs.displayWindow) !== 0) throw new ExrNotStreamable("the dataWindow is not the displayWindow")
+		const dw = attrs.dataWindow, y0 = dw.readInt32LE(4)
+		const w = dw.readInt32LE(8) - dw.readInt32LE(0) + 1, h = dw.readInt32LE(12) - y0 + 1
+		if (W >= 0 && (w !== W || h !== H)) throw new Error("parts of different sizes")
+		W = w
+		H = h
+		const pname = attrs.name ? attrs.name.toString("latin1").replace(/\0+$/, "") : ""
+		const cl = attrs.channels, chans = []
+		for (let p = 0; cl[p] !== 0; ) {
+			const e = cl.indexOf(0, p), nm = cl.toString("latin1", p, e), pt = cl.readInt32LE(e + 1)
+			if (cl.readInt32LE(e + 9) !== 1 || cl.readInt32LE(e + 13) !== 1) throw new Error("subsampled channels are not supported")
+			if (pt === 0) throw new ExrNotStreamable("UINT channel " + nm)
+			const full = nm.includes(".") || !pname ? nm : pname + "." + nm
+			const f = feeds[full] || [-1, 0]
+			if (f[0] >= 0) {
+				if (full in seen) throw new Error("channel " + full + " appears in two parts")
+				seen[full] = pt
+			}
+			chans.push(pt, f[0], f[1])
+			p = e + 17
+		}
+		partWords.push(comp, chans.length / 3, ...chans)
+		const per = comp === 3 ? 16 : 1
+		const n = attrs.chunkCount ? attrs.chunkCount.readInt32LE(0) : Math.ceil(H / per)
+		const hdr = multipart ? 12 : 8
+		for (let i = 0; i < n; i++) {
+			const o = Number(b.readBigUInt64LE(pos + 8 * i))
+			if (o + hdr > b.length) throw new Error("a chunk offset outside the file")
+			if (multipart && b.readInt32LE(o) !== k) throw new Error("a chunk of part " + k + " carries another part number")
+			const y = b.readInt32LE(o + hdr - 8) - y0
+			records.push([k, y, Math.min(per, H - y), o + hdr, b.readInt32LE(o + hdr - 4)])
+		}
+		pos += 8 * n
+	})
+	const planes = {}
+	for (const key of Object.keys(AOV_LAYOUT)) {
+		const have = layout[key].filter(c => c in seen), missing = layout[key].filter(c => !(c in seen))
+		if (!have.length) continue
+		if (missing.length && !((key === "diffuse" || key === "direct") && missing.length === 1 && missing[0] === layout[key][3]))
+			throw new Error("channel(s) " + missing.join(", ") + " of AOV " + key + " missing")
+		planes[key] = [have.length, have.every(c => seen[c] === 1) ? "half" : "float"]
+	}
+	const chunks = Buffer.alloc(32 * records.length)
+	records.forEach(([part, y, rows, offset, packed], i) => {
+		chunks.writeInt32LE(part, 32 * i)
+		chunks.writeInt32LE(y, 32 * i + 4)
+		chunks.writeInt32LE(rows, 32 * i + 8)
+		chunks.writeBigUInt64LE(BigInt(offset), 32 * i + 16)
+		chunks.writeBigUInt64LE(BigInt(packed), 32 * i + 24)
+	})
+	return { width: W, height: H, fileBytes: b.length, parts: Int32Array.from(partWords), chunks: new Uint8Array(chunks.buffer, chunks.byteOffset, chunks.length), chunkCount: records.length, planes }
+}
+
+module.exports = { writePNG, pngFromFragments, writeEXR, exrFromFragments, writePFM, tonemap, exrAovLayout, ExrNotStreamable, AOV_LAYOUT }

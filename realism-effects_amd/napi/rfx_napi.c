@@ -14,6 +14,7 @@
 #include <node_api.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 #include "../../include/rfx.h"
 
@@ -295,6 +296,86 @@ static napi_value aov_call(napi_env env, napi_callback_info info, int stage) {
 }
 static napi_value n_stage_aov(napi_env env, napi_callback_info info) { return aov_call(env, info, 1); }
 static napi_value n_aov_stage_bytes(napi_env env, napi_callback_info info) { return aov_call(env, info, 0); }
+/* An EXR frame descriptor (rfx.h "streamed EXR frames") from what imageio.exrAovLayout returns: `bytes` the file (a Uint8Array / Buffer, ideally over
+ * hostAlloc() memory), `parts` an Int32Array [parts, then per part: compression, channels, then per channel: pixel type, plane, component],
+ * `chunks` a Uint8Array of rfx_exr_chunk records.  The descriptor is consumed by the call: its tables are copies in one block, *hold, which the
+ * caller frees.  Returns 0 after throwing. */
+static int read_exr_frame(napi_env env, napi_value bytes, napi_value parts, napi_value chunks, rfx_exr_frame *f, void **hold) {
+    napi_typedarray_type tb, tp, tc;
+    size_t nb, np, nc;
+    void *pb, *pp, *pc;
+    *hold = NULL;
+    if (napi_get_typedarray_info(env, bytes, &tb, &nb, &pb, NULL, NULL) != napi_ok || tb != napi_uint8_array ||
+        napi_get_typedarray_info(env, parts, &tp, &np, &pp, NULL, NULL) != napi_ok || tp != napi_int32_array ||
+        napi_get_typedarray_info(env, chunks, &tc, &nc, &pc, NULL, NULL) != napi_ok || tc != napi_uint8_array) {
+        napi_throw_type_error(env, NULL, "EXR frame: (Uint8Array file bytes, Int32Array parts, Uint8Array chunk records) expected");
+        return 0;
+    }
+    const int32_t *w = (const int32_t *)pp;
+    size_t nparts = np ? (size_t)w[0] : 0, at = 1, nchan = 0;
+    int ok = np >= 1 && w[0] > 0 && nc % sizeof(rfx_exr_chunk) == 0 && nc > 0;
+    for (size_t k = 0; ok && k < nparts; k++) {  /* walk the list once: it must end where the array ends */
+        if (at + 2 > np || w[at + 1] <= 0 || at + 2 + 3 * (size_t)w[at + 1] > np) { ok = 0; break; }
+        nchan += (size_t)w[at + 1];
+        at += 2 + 3 * (size_t)w[at + 1];
+    }
+    if (!ok || at != np) { napi_throw_range_error(env, NULL, "EXR frame: the part list or the chunk records are malformed"); return 0; }
+    const size_t parts_b = nparts * sizeof(rfx_exr_part), chans_b = nchan * sizeof(rfx_exr_channel);
+    char *block = (char *)malloc(nc + parts_b + chans_b);  /* chunk records first: they hold 64-bit fields */
+    if (!block) { napi_throw_error(env, NULL, "EXR frame: out of memory"); return 0; }
+    memcpy(block, pc, nc);
+    rfx_exr_part *P = (rfx_exr_part *)(block + nc);
+    rfx_exr_channel *C = (rfx_exr_channel *)(block + nc + parts_b);
+    at = 1;
+    for (size_t k = 0; k < nparts; k++) {
+        P[k].compression = w[at]; P[k].channels = w[at + 1]; P[k].channel = C;
+        for (int32_t i = 0; i < w[at + 1]; i++, C++) { C->pixel_type = w[at + 2 + 3 * i]; C->plane = w[at + 3 + 3 * i]; C->component = w[at + 4 + 3 * i]; }
+        at += 2 + 3 * (size_t)w[at + 1];
+    }
+    f->data = pb; f->bytes = nb; f->parts = (int)nparts; f->chunks = (int)(nc / sizeof(rfx_exr_chunk));
+    f->part = P; f->chunk = (const rfx_exr_chunk *)block;
+    *hold = block;
+    return 1;
+}
+/* stageExrAov(ctx, bytes, parts, chunks, row0, rows): rfx_stage_exr_aov; `bytes` must stay alive and unchanged like stageUpload's planes.
+ * exrAovStageBytes(...) -> the bytes that call copies (0: it would be refused).  exrAovStatus(ctx) -> [bad chunks, first bad chunk, code] */
+static napi_value exr_aov_call(napi_env env, napi_callback_info info, int stage) {
+    napi_value a[6], out = NULL;
+    int32_t row0, rows;
+    rfx_exr_frame f;
+    void *hold;
+    if (!get_args(env, info, 6, a)) return NULL;
+    rfx_ctx *c = get_ctx(env, a[0]);
+    if (!c || !get_int(env, a[4], &row0) || !get_int(env, a[5], &rows)) return NULL;
+    if (!read_exr_frame(env, a[1], a[2], a[3], &f, &hold)) return NULL;
+    if (!stage) {
+        const size_t n = rfx_exr_aov_stage_bytes(c, &f, row0, rows);
+        free(hold);
+        NAPI_CALL(env, napi_create_double(env, (double)n, &out));
+        return out;
+    }
+    int rc = rfx_stage_exr_aov(c, &f, row0, rows);
+    free(hold);
+    if (rc) return throw_rfx(env, c, "rfx_stage_exr_aov", rc);
+    return NULL;
+}
+static napi_value n_stage_exr_aov(napi_env env, napi_callback_info info) { return exr_aov_call(env, info, 1); }
+static napi_value n_exr_aov_stage_bytes(napi_env env, napi_callback_info info) { return exr_aov_call(env, info, 0); }
+static napi_value n_exr_aov_status(napi_env env, napi_callback_info info) {
+    napi_value a[1], out, v;
+    int s[3] = {0, -1, 0};
+    if (!get_args(env, info, 1, a)) return NULL;
+    rfx_ctx *c = get_ctx(env, a[0]);
+    if (!c) return NULL;
+    int rc = rfx_exr_aov_status(c, &s[0], &s[1], &s[2]);
+    if (rc) return throw_rfx(env, c, "rfx_exr_aov_status", rc);
+    NAPI_CALL(env, napi_create_array_with_length(env, 3, &out));
+    for (uint32_t i = 0; i < 3; i++) {
+        NAPI_CALL(env, napi_create_int32(env, s[i], &v));
+        NAPI_CALL(env, napi_set_element(env, out, i, v));
+    }
+    return out;
+}
 static napi_value n_upload(napi_env env, napi_callback_info info) { return xfer(env, info, 1); }
 static napi_value n_download(napi_env env, napi_callback_info info) { return xfer(env, info, 0); }
 
@@ -1101,6 +1182,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"motionBlurStage", n_motion_blur_stage}, {"motionBlurReachMask", n_motion_blur_reach_mask}, {"motionBlurGather", n_motion_blur_gather},
         {"sync", n_sync}, {"setRowWindow", n_set_row_window}, {"setUvModel", n_set_uv_model}, {"cubeToEquirect", n_cube_to_equirect}, {"haloViolations", n_halo_violations}, {"timeBegin", n_time_begin}, {"timeEnd", n_time_end}, {"profile", n_profile}, {"profileRead", n_profile_read},
         {"stageUpload", n_stage_upload}, {"stageFlip", n_stage_flip}, {"hostAlloc", n_host_alloc}, {"stageAov", n_stage_aov}, {"aovStageBytes", n_aov_stage_bytes},
+        {"stageExrAov", n_stage_exr_aov}, {"exrAovStageBytes", n_exr_aov_stage_bytes}, {"exrAovStatus", n_exr_aov_status},
         {"exportBytes", n_export_bytes}, {"exportFrame", n_export_frame}, {"stageExport", n_stage_export}, {"exportWait", n_export_wait}, {"constants", n_constants},
         {"pngBound", n_png_bound}, {"pngFrame", n_png_frame}, {"stagePng", n_stage_png},
         {"exrBound", n_exr_bound}, {"exrFrame", n_exr_frame}, {"stageExr", n_stage_exr},

@@ -116,6 +116,31 @@ class AovFrame(C.Structure):
     _fields_ = [(name, Plane) for name in AOV_PLANES]
 
 
+# rfx.h "streamed EXR frames": the descriptor of rfx_stage_exr_aov (OpenEXR's own numbers for compression and pixel type)
+EXR_NONE, EXR_ZIPS, EXR_ZIP = 0, 2, 3
+EXR_HALF, EXR_FLOAT = 1, 2
+EXR_SKIP = -1
+
+
+class ExrChannel(C.Structure):
+    _fields_ = [("pixel_type", C.c_int32), ("plane", C.c_int32), ("component", C.c_int32)]
+
+
+class ExrPart(C.Structure):
+    _fields_ = [("compression", C.c_int32), ("channels", C.c_int32), ("channel", C.POINTER(ExrChannel))]
+
+
+class ExrChunk(C.Structure):
+    _fields_ = [("part", C.c_int32), ("y", C.c_int32), ("rows", C.c_int32), ("reserved", C.c_int32), ("offset", C.c_uint64), ("packed_bytes", C.c_uint64)]
+
+
+EXR_CHUNK_DTYPE = np.dtype([("part", "<i4"), ("y", "<i4"), ("rows", "<i4"), ("reserved", "<i4"), ("offset", "<u8"), ("packed_bytes", "<u8")])  # ExrChunk as a numpy record
+
+
+class ExrFrame(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("bytes", C.c_uint64), ("parts", C.c_int32), ("chunks", C.c_int32), ("part", C.POINTER(ExrPart)), ("chunk", C.POINTER(ExrChunk))]
+
+
 class FinalParams(C.Structure):
     _fields_ = [("camera", Camera), ("isDebug", C.c_int32), ("inputSource", C.c_int32), ("fogMode", C.c_int32), ("fogColor", C.c_float * 3), ("fogNear", C.c_float),
                 ("fogFar", C.c_float), ("fogDensity", C.c_float)]
@@ -141,6 +166,7 @@ EXPORTS = [
     "rfx_png_bound", "rfx_stage_png", "rfx_png", "rfx_profile_read_n",
     "rfx_aov_stage_bytes", "rfx_stage_aov",
     "rfx_exr_bound", "rfx_stage_exr", "rfx_exr",
+    "rfx_exr_aov_stage_bytes", "rfx_stage_exr_aov", "rfx_exr_aov_status",
 ]
 
 _lib = None
@@ -254,6 +280,10 @@ def load_library(path: str | None = None) -> C.CDLL:
     lib.rfx_aov_stage_bytes.argtypes = [vp, C.POINTER(AovFrame), i, i]
     lib.rfx_aov_stage_bytes.restype = C.c_size_t
     lib.rfx_stage_aov.argtypes = [vp, C.POINTER(AovFrame), i, i]
+    lib.rfx_exr_aov_stage_bytes.argtypes = [vp, C.POINTER(ExrFrame), i, i]
+    lib.rfx_exr_aov_stage_bytes.restype = C.c_size_t
+    lib.rfx_stage_exr_aov.argtypes = [vp, C.POINTER(ExrFrame), i, i]
+    lib.rfx_exr_aov_status.argtypes = [vp, C.POINTER(i), C.POINTER(i), C.POINTER(i)]
     if lib.rfx_abi_version() != RFX_ABI_VERSION:
         raise ImportError("librfx_hip.so ABI version %d != %d" % (lib.rfx_abi_version(), RFX_ABI_VERSION))
     if path is None:

@@ -164,6 +164,65 @@ class Context:
         self.__dict__.setdefault("_staged_now", []).extend(keep)  # kept alive until the copies of this batch have executed
         self._chk(self.lib.rfx_stage_aov(self._h, C.byref(f), row0, rows), "rfx_stage_aov")
 
+    # -- streamed EXR frames (rfx.h "streamed EXR frames"): the file's chunks cross PCIe packed and are decoded on the device
+    def _exr_frame(self, buf, layout):
+        """-> (abi.ExrFrame, the objects it points into).  `buf`: the file's bytes (bytes, or a uint8 array — host_alloc() makes the copies
+        asynchronous); `layout`: imageio.exr_aov_layout of the same bytes."""
+        if (layout.width, layout.height) != (self.W, self.H):
+            raise ValueError("EXR frame of %d x %d on a context of %d x %d" % (layout.width, layout.height, self.W, self.H))
+        a = np.frombuffer(buf, np.uint8) if not isinstance(buf, np.ndarray) else buf
+        if not a.flags["C_CONTIGUOUS"] or a.nbytes < layout.file_bytes:
+            raise ValueError("EXR frame: a contiguous buffer of the file's %d bytes" % layout.file_bytes)
+        # (built per call from what the layout holds now: the part list is a few words, the chunk records are handed over as they are)
+        chans = [(abi.ExrChannel * len(ch))(*[abi.ExrChannel(pt, pl, comp) for pt, pl, comp in ch]) for _, ch in layout.parts]
+        parts = (abi.ExrPart * len(layout.parts))(*[abi.ExrPart(comp, len(ch), arr) for (comp, ch), arr in zip(layout.parts, chans)])
+        chunks = np.ascontiguousarray(layout.chunks, abi.EXR_CHUNK_DTYPE)
+        c = (chans, parts, chunks)
+        f = abi.ExrFrame(a.ctypes.data, layout.file_bytes, len(parts), len(chunks), parts, chunks.ctypes.data_as(C.POINTER(abi.ExrChunk)))
+        return f, (a, c)
+
+    def _band(self, row0, rows):
+        row0 = 0 if row0 is None else int(row0)
+        return row0, (self.H - row0 if rows is None else int(rows))
+
+    def exr_aov_stage_bytes(self, buf, layout, row0: int | None = None, rows: int | None = None) -> int:
+        """rfx_exr_aov_stage_bytes: the bytes stage_exr_aov(buf, layout, row0, rows) copies host -> device (0: the library would refuse the frame)"""
+        f, _ = self._exr_frame(buf, layout)
+        return int(self.lib.rfx_exr_aov_stage_bytes(self._h, C.byref(f), *self._band(row0, rows)))
+
+    def stage_exr_aov(self, buf, layout, row0: int | None = None, rows: int | None = None):
+        """rfx_stage_exr_aov: stage_aov for a frame that is still an OpenEXR file — the chunks of rows [row0, row0+rows) of the FRAME (default:
+        all of it) are copied as they sit in `buf` and inflated, unpredicted and scattered on the device; published by stage_flip()."""
+        f, keep = self._exr_frame(buf, layout)
+        self.__dict__.setdefault("_staged_now", []).append(keep[0])  # kept alive until the copies of this batch have executed
+        self._chk(self.lib.rfx_stage_exr_aov(self._h, C.byref(f), *self._band(row0, rows)), "rfx_stage_exr_aov")
+
+    def exr_aov_status(self):
+        """rfx_exr_aov_status -> (bad chunks, index of the first bad chunk in layout.chunks or -1, its k9_inflate.h error code or 0); waits for
+        the decode of the most recent stage_exr_aov"""
+        bad, first, code = C.c_int(), C.c_int(), C.c_int()
+        self._chk(self.lib.rfx_exr_aov_status(self._h, C.byref(bad), C.byref(first), C.byref(code)), "rfx_exr_aov_status")
+        return bad.value, first.value, code.value
+
+    def stage_exr_frame(self, path: str, decode: str = "host", names: dict | None = None):
+        """Stage a whole AOV EXR file.  decode="host" (the default): imageio.exr_to_typed_planes + stage_aov.  decode="device": the file's bytes
+        + stage_exr_aov; a file the device decode does not take (imageio.ExrNotStreamable: tiled, RLE / PIZ / PXR24, ...) goes the host's way.
+        -> the way taken, "host" or "device"."""
+        from . import imageio
+        if decode not in ("host", "device"):
+            raise ValueError("decode: \"host\" or \"device\"")
+        if decode == "device":
+            with open(path, "rb") as f:
+                data = f.read()
+            try:
+                self.stage_exr_aov(data, imageio.exr_aov_layout(data, names))
+                return "device"
+            except imageio.ExrNotStreamable:
+                pass
+        t = imageio.exr_to_typed_planes(path, names)
+        self.stage_aov(dict(t["aov"], depth=t["depth"], direct=t["direct"]))
+        return "host"
+
     def stage_flip(self):
         self._chk(self.lib.rfx_stage_flip(self._h), "rfx_stage_flip")
         # rfx_stage_flip returns when the copies published by the PREVIOUS flip have executed: keep this batch's planes and the one before

@@ -83,3 +83,38 @@ class FrameExporter:
 
     def finish(self):
         self._retire()
+
+
+class ExrSequence:
+    """Per-frame input of an offline run through the device EXR decode (include/rfx.h "streamed EXR frames"): the AOV EXR files of a directory, or
+    a list of paths, read with readinto() into two alternating pinned buffers and staged with Context.stage_exr_aov.
+
+        seq = ExrSequence(ctx, directory);  seq.stage(0); ctx.stage_flip()
+        for i in range(len(seq)):  seq.stage(i + 1) if i + 1 < len(seq) else None;  <draws of frame i>;  ctx.stage_flip()
+
+    Buffer k & 1 is refilled for frame k when the flip after frame k - 1's has returned: rfx_stage_flip's back pressure says the copies out of
+    it have executed.  A file the device decode does not take (imageio.ExrNotStreamable) is read on the host (Context.stage_exr_frame)."""
+    def __init__(self, ctx, source, names: dict | None = None):
+        self.ctx, self.names = ctx, names
+        self.paths = sorted(os.path.join(source, f) for f in os.listdir(source) if f.lower().endswith(".exr")) if isinstance(source, str) else list(source)
+        self.buffers = [None, None]
+
+    def __len__(self):
+        return len(self.paths)
+
+    def stage(self, index: int) -> str:
+        """stage frame `index` (published by the next stage_flip) -> "device" or "host": the way it went"""
+        path = self.paths[index]
+        size = os.path.getsize(path)
+        buf = self.buffers[index & 1]
+        if buf is None or buf.size < size:  # grown with some room: frames of a sequence differ by a few per cent
+            buf = self.buffers[index & 1] = self.ctx.host_alloc((size + size // 8,), np.uint8)
+        with open(path, "rb", buffering=0) as f:
+            got = f.readinto(memoryview(buf)[:size])
+        if got != size:
+            raise IOError("%s: read %d of %d bytes" % (path, got, size))
+        try:
+            self.ctx.stage_exr_aov(buf, imageio.exr_aov_layout(buf[:size], self.names))
+            return "device"
+        except imageio.ExrNotStreamable:
+            return self.ctx.stage_exr_frame(path, "host", self.names)

@@ -16,10 +16,13 @@ that store the top row first are flipped on the way in and out.
 """
 from __future__ import annotations
 
+import os
 import struct
 import zlib
 
 import numpy as np
+
+from .abi import EXR_CHUNK_DTYPE  # rfx_exr_chunk as a numpy record: the one definition
 
 
 # ------------------------------------------------------------------------------------------------ Radiance .hdr (RGBE)
@@ -922,13 +925,14 @@ def exr_channel_types(path: str) -> dict:
 
 
 def write_exr_multipart(path: str, parts: dict, compression: str = "zip", half: bool = False):
-    """parts: part name -> {channel: (H, W) array}: one scanline part per entry (how several renderers lay out AOVs)."""
+    """parts: part name -> {channel: (H, W) array}: one scanline part per entry (how several renderers lay out AOVs).  half: True / False for
+    every part, or the names of the parts to store as binary16 (the rest float32)."""
     comp = {"none": _COMP_NONE, "rle": _COMP_RLE, "zips": _COMP_ZIPS, "zip": _COMP_ZIP, "piz": _COMP_PIZ, "pxr24": _COMP_PXR24}[compression]
-    pt = _PT_HALF if half else _PT_FLOAT
-    dt = _PT_DTYPE[pt]
     per_block = {_COMP_NONE: 1, _COMP_RLE: 1, _COMP_ZIPS: 1, _COMP_ZIP: 16, _COMP_PIZ: 32, _COMP_PXR24: 16}[comp]
     headers, chunk_lists = b"", []
     for k, (pname, channels) in enumerate(parts.items()):
+        pt = _PT_HALF if (half is True or (half and not isinstance(half, bool) and pname in half)) else _PT_FLOAT
+        dt = _PT_DTYPE[pt]
         names = sorted(channels)
         planes = [np.ascontiguousarray(np.asarray(channels[n])[::-1].astype(dt)) for n in names]
         H, W = planes[0].shape
@@ -1024,3 +1028,116 @@ def exr_to_typed_planes(path: str, names: dict | None = None) -> dict:
             flat[key] = np.ascontiguousarray(flat[key].astype(np.float16))
     depth, direct = flat.pop("depth"), flat.pop("direct")
     return {"aov": flat, "depth": depth, "direct": direct}
+
+
+# ------------------------------------------------------------------------------------------------ AOV EXR -> the descriptor of the device decode
+class ExrNotStreamable(ValueError):
+    """exr_aov_layout: the file is one the device decode (rfx.h "streamed EXR frames") does not take — read it on the host (exr_to_typed_planes)"""
+
+
+class ExrAovLayout:
+    """What Context.stage_exr_aov needs besides the file's bytes (rfx.h rfx_exr_frame): per part its compression and, per channel in file order,
+    (pixel type, plane index in AOV_LAYOUT's order or -1, component); the chunk table as records (part, y, rows, reserved, offset of the packed
+    data, packed bytes); and what follows from them: `planes` = {name: (channels, "half" | "float")} as the device will stage them."""
+    def __init__(self, width, height, file_bytes, parts, chunks, planes):
+        self.width, self.height, self.file_bytes, self.parts, self.chunks, self.planes = width, height, file_bytes, parts, chunks, planes
+
+    def band_chunks(self, row0=None, rows=None):
+        """the records of the chunks a band [row0, row0 + rows) of frame rows (0 = bottom) needs: a scanline inside it, a part that feeds a plane"""
+        row0 = 0 if row0 is None else row0
+        rows = self.height - row0 if rows is None else rows
+        y_lo, y_hi = self.height - row0 - rows, self.height - row0
+        mapped = np.array([any(pl >= 0 for _, pl, _ in chans) for _, chans in self.parts])
+        c = self.chunks
+        return c[mapped[c["part"]] & (c["y"] < y_hi) & (c["y"] + c["rows"] > y_lo)]
+
+
+def exr_aov_layout(path_or_bytes, names: dict | None = None) -> ExrAovLayout:
+    """Parse the header(s) and the offset table(s) of an AOV EXR — a path, or the file's bytes (bytes, a memoryview, a uint8 array: a pinned
+    buffer the file was read into) — for the device decode.  Channel names map to planes as exr_to_typed_planes maps them (AOV_LAYOUT, `names`):
+    a plane none of whose channels is in the file is absent, a diffuse / direct plane without its fourth channel has three (alpha 1), a plane
+    whose channels are all HALF is staged as halves.  Channels no plane names are dropped on the device.
+    ExrNotStreamable: tiled or deep files, RLE / PIZ / PXR24 parts, UINT channels, a dataWindow that is not the displayWindow."""
+    if isinstance(path_or_bytes, (str, os.PathLike)):
+        with open(path_or_bytes, "rb") as f:
+            data = f.read()
+        what = str(path_or_bytes)
+    else:
+        data, what = path_or_bytes, "<bytes>"
+    u8 = np.frombuffer(data, np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data).view(np.uint8).reshape(-1)
+    if u8.size < 8 or bytes(u8[:4]) != b"\x76\x2f\x31\x01":
+        raise ValueError("%s: not an OpenEXR file" % what)
+    version = struct.unpack("<i", bytes(u8[4:8]))[0]
+    if version & 0x800:
+        raise ExrNotStreamable("%s: deep data" % what)
+    if version & 0x200:
+        raise ExrNotStreamable("%s: a tiled file" % what)
+    multipart = bool(version & 0x1000)
+    head_len = 1 << 16
+    while True:  # the headers sit in the first few KiB: parse a prefix, longer if it ends inside them
+        d = bytes(u8[:head_len])
+        try:
+            headers, pos = [], 8
+            while True:
+                attrs, pos = _exr_parse_header(d, pos)
+                headers.append(attrs)
+                if not multipart or d[pos] == 0:
+                    break
+            break
+        except (IndexError, ValueError, struct.error):
+            if head_len >= u8.size:
+                raise ValueError("%s: damaged header" % what)
+            head_len *= 4
+    table_pos = pos + (1 if multipart else 0)
+    layout = dict(AOV_LAYOUT)
+    layout.update(names or {})
+    feeds = {cn: (pi, j) for pi, key in enumerate(AOV_LAYOUT) for j, cn in enumerate(layout[key])}
+    parts, tables, W, H, seen = [], [], None, None, {}
+    for k, attrs in enumerate(headers):
+        typ = attrs.get(b"type", (b"", b"scanlineimage"))[1].rstrip(b"\0")
+        if typ != b"scanlineimage":
+            raise ExrNotStreamable("%s: a part of type %s" % (what, typ.decode()))
+        lay = _exr_part_layout(what, attrs, False)
+        if lay["comp"] not in (_COMP_NONE, _COMP_ZIPS, _COMP_ZIP):
+            raise ExrNotStreamable("%s: compression %s" % (what, {_COMP_RLE: "RLE", _COMP_PIZ: "PIZ", _COMP_PXR24: "PXR24"}[lay["comp"]]))
+        if attrs[b"dataWindow"][1] != attrs[b"displayWindow"][1]:
+            raise ExrNotStreamable("%s: the dataWindow is not the displayWindow" % what)
+        if W is not None and (lay["W"], lay["H"]) != (W, H):
+            raise ValueError("%s: parts of different sizes" % what)
+        W, H = lay["W"], lay["H"]
+        pname = attrs[b"name"][1].rstrip(b"\0").decode() if b"name" in attrs else ""
+        chans = []
+        for nm, pt in lay["chans"]:
+            if pt == _PT_UINT:
+                raise ExrNotStreamable("%s: UINT channel %s" % (what, nm))
+            full = nm if ("." in nm or not pname) else pname + "." + nm
+            pl, comp = feeds.get(full, (-1, 0))
+            if pl >= 0:
+                if full in seen:
+                    raise ValueError("%s: channel %s appears in two parts" % (what, full))
+                seen[full] = pt
+            chans.append((pt, pl, comp))
+        parts.append((lay["comp"], chans))
+        n = lay["chunks"]
+        offs = np.frombuffer(u8, "<u8", n, table_pos).astype(np.int64)
+        table_pos += 8 * n
+        hdr = 12 if multipart else 8
+        if n and (offs.min() < 0 or offs.max() + hdr > u8.size):
+            raise ValueError("%s: a chunk offset outside the file" % what)
+        words = u8[offs[:, None] + np.arange(hdr)[None, :]].copy().view("<i4").reshape(n, hdr // 4)
+        if multipart and np.any(words[:, 0] != k):
+            raise ValueError("%s: a chunk of part %d carries another part number" % (what, k))
+        rec = np.zeros(n, EXR_CHUNK_DTYPE)
+        rec["part"], rec["y"], rec["offset"], rec["packed_bytes"] = k, words[:, -2] - lay["y0"], offs + hdr, words[:, -1].astype(np.int64)
+        rec["rows"] = np.minimum(lay["per_block"], H - rec["y"])
+        tables.append(rec)
+    planes = {}
+    for pi, key in enumerate(AOV_LAYOUT):
+        have = [seen[c] for c in layout[key] if c in seen]
+        if not have:
+            continue
+        missing = [c for c in layout[key] if c not in seen]
+        if missing and not (key in ("diffuse", "direct") and missing == [layout[key][3]]):
+            raise KeyError("%s: channel(s) %s of AOV %r missing" % (what, missing, key))
+        planes[key] = (len(have), "half" if all(pt == _PT_HALF for pt in have) else "float")
+    return ExrAovLayout(W, H, int(u8.size), parts, np.concatenate(tables), planes)

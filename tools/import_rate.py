@@ -10,14 +10,24 @@
 on the seeded dump whose AOV planes are rounded to half wherever A2 sends halves (all four modes see the same values), in ONE process: every
 mode is warmed first, then three alternating rounds, each mode a steady state of at least --seconds with a device synchronise inside the clock.
 
-    python tools/import_rate.py [--out profiles/import/rates.json] [--seconds 1.0]
+--modes E0,E1: the same typed frame as an OpenEXR file — multi-part, one part per plane, half / float as A2 types them, written once per
+compression (ZIPS, ZIP) —
+
+    E0  file -> imageio.exr_to_typed_planes (the host inflates, unpredicts, de-interleaves) -> stage_aov
+    E1  file -> readinto a pinned buffer -> imageio.exr_aov_layout (header and offset table) -> stage_exr_aov (the device decodes: K9)
+
+measured the same way, per compression, with A2 in the same rounds; the result is merged into --out under "exr".
+
+    python tools/import_rate.py [--modes P0,A0,A1,A2 | E0,E1] [--out profiles/import/rates.json] [--seconds 1.0]
     rocprofv3 --kernel-trace --stats -d DIR -- python tools/import_rate.py --kernel-only      (the pack kernel's own time: a run of its own)
+    rocprofv3 --kernel-trace --stats -d DIR -- python tools/import_rate.py --kernel-only --modes E1      (... and the K9 kernels')
 """
 import argparse
 import json
 import math
 import os
 import sys
+import tempfile
 import time
 import types
 
@@ -26,12 +36,14 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "realism-effects_amd"))
 
-from rfx_amd import abi, effect  # noqa: E402
+from rfx_amd import abi, effect, imageio  # noqa: E402
 from rfx_amd.context import Context  # noqa: E402
 from rfx_amd.scene import AnalyticScene, _pool_worker_init  # noqa: E402
 
 W, H = 3840, 2160
 MODES = ("P0", "A0", "A1", "A2")
+EXR_MODES = ("E0", "E1")
+EXR_COMPRESSIONS = ("zips", "zip")
 BYTES_PER_PIXEL = dict(P0=52, A0=96, A1=76, A2=44)
 HALF = ("diffuse", "normal", "roughness", "metalness", "emissive", "direct")
 AOV = ("diffuse", "normal", "roughness", "metalness", "emissive", "velocity")
@@ -63,10 +75,19 @@ def render(seed, index, workers=16):
 
 
 class Run:
-    def __init__(self, seed):
+    def __init__(self, seed, modes=MODES, exr_dir=None, files_only=False):
         self.ctx = ctx = Context(W, H)  # raises without a device
         self.scene = types.SimpleNamespace(frame=None)
         self.frames = {m: [] for m in MODES}
+        exr = [m for m in modes if m in EXR_MODES]
+        self.exr_bytes = {}
+        files = {(i, comp): os.path.join(exr_dir, "frame%d_%s.exr" % (i, comp)) for i in range(2) for comp in EXR_COMPRESSIONS} if exr else {}
+        if files_only:  # a kernel trace of E1 over files an earlier run left in --exr-dir: nothing is rendered, nothing is drawn
+            for (i, comp), path in sorted(files.items()):
+                self.exr_bytes.setdefault(comp, []).append(os.path.getsize(path))
+                self.frames.setdefault("E1:" + comp, []).append(types.SimpleNamespace(path=path, exr="E1"))
+            self.file_buffers = [ctx.host_alloc((max(max(v) for v in self.exr_bytes.values()),), np.uint8) for _ in range(2)]
+            return
 
         def pin(a):  # a pinned copy: what makes the staged copies asynchronous
             p = ctx.host_alloc(a.shape, a.dtype)
@@ -85,6 +106,16 @@ class Run:
             self.frames["A0"].append(ns(False, wide["depth"], wide["direct"], gbuffer=None, velocity=None, aov={k: wide[k] for k in AOV}))
             self.frames["A1"].append(ns("resident", pin(wide["depth"]), pin(wide["direct"]), gbuffer=None, velocity=None, aov={k: pin(wide[k]) for k in AOV}))
             self.frames["A2"].append(ns("resident", pin(typed["depth"]), pin(typed["direct"]), gbuffer=None, velocity=None, aov={k: pin(typed[k]) for k in AOV}))
+            for comp in EXR_COMPRESSIONS if exr else ():  # the typed frame as a file: one part per plane, halves where A2 sends halves
+                path = files[(i, comp)]
+                parts = {k: {cn.split(".")[1]: (typed[k][..., j] if typed[k].ndim == 3 else typed[k]) for j, cn in enumerate(imageio.AOV_LAYOUT[k])} for k in imageio.AOV_LAYOUT}
+                imageio.write_exr_multipart(path, parts, comp, half=set(HALF))
+                self.exr_bytes.setdefault(comp, []).append(os.path.getsize(path))
+                for m in EXR_MODES:
+                    self.frames.setdefault(m + ":" + comp, []).append(ns("resident", None, None, gbuffer=None, velocity=None, aov=None, path=path, exr=m))
+            print("frame %d ready" % i, file=sys.stderr, flush=True)
+        if exr:  # E1's two pinned file buffers
+            self.file_buffers = [ctx.host_alloc((max(max(v) for v in self.exr_bytes.values()),), np.uint8) for _ in range(2)]
         self.cam = types.SimpleNamespace(**vars(self.frames["P0"][0].camera))
         self.fx = effect.SSGIEffect(None, self.scene, self.cam, dict(width=W, height=H, steps=20, refineSteps=5), seeds=dict(ssgi=11, denoise=22), half_store_rtz=True)
         for m in ("A1", "A2"):
@@ -97,30 +128,44 @@ class Run:
             setattr(self.cam, k, v)
         self.fx.update(self.ctx, None)
 
+    def stage(self, f, k):
+        """stage frame f, the k-th staged of its loop"""
+        ctx = self.ctx
+        if getattr(f, "exr", None) == "E0":
+            t = imageio.exr_to_typed_planes(f.path)
+            ctx.stage_aov(dict(t["aov"], depth=t["depth"], direct=t["direct"]))
+        elif getattr(f, "exr", None) == "E1":
+            buf, size = self.file_buffers[k & 1], os.path.getsize(f.path)
+            with open(f.path, "rb", buffering=0) as fh:
+                assert fh.readinto(memoryview(buf)[:size]) == size
+            ctx.stage_exr_aov(buf, imageio.exr_aov_layout(buf[:size]))
+        else:
+            ctx.stage_frame(f)
+
     def loop(self, mode, n):
         """n frames; wall seconds, the device synchronised inside the clock"""
         ctx, fr = self.ctx, self.frames[mode]
         staged = mode != "A0"
         if staged:
-            ctx.stage_frame(fr[0])
+            self.stage(fr[0], 0)
             ctx.stage_flip()
         ctx.sync()
         t0 = time.perf_counter()
         for i in range(n):
             if staged:
-                ctx.stage_frame(fr[(i + 1) & 1])  # frame i + 1 crosses while frame i draws
+                self.stage(fr[(i + 1) & 1], i + 1)  # frame i + 1 crosses while frame i draws
             self.draw(fr[i & 1])
             if staged:
                 ctx.stage_flip()
         ctx.sync()
         return time.perf_counter() - t0
 
-    def kernel_only(self, n=20):
-        """stage_aov + flip alone, for a kernel trace: A1's frame, then A2's"""
+    def kernel_only(self, n=20, modes=("A1", "A2")):
+        """stage + flip alone, for a kernel trace: A1's frame, then A2's (or, --modes E1: the ZIPS file, then the ZIP file)"""
         ctx = self.ctx
-        for mode in ("A1", "A2"):
+        for mode in modes:
             for i in range(n):
-                ctx.stage_frame(self.frames[mode][i & 1])
+                self.stage(self.frames[mode][i & 1], i)
                 ctx.stage_flip()
             ctx.sync()
 
@@ -132,9 +177,14 @@ def main():
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--size", default="3840x2160", help="frame size (the committed numbers are 4K; a small size checks the script itself)")
     ap.add_argument("--kernel-only", action="store_true", help="only stage and flip AOV frames (under rocprofv3 --kernel-trace --stats)")
+    ap.add_argument("--modes", default=",".join(MODES), help="P0,A0,A1,A2 (the default) or E0,E1 (the EXR file modes, measured beside A2)")
+    ap.add_argument("--exr-dir", default=None, help="where the E modes write their files (default: a temporary directory)")
     a = ap.parse_args()
     global W, H
     W, H = (int(v) for v in a.size.split("x"))
+    modes = tuple(a.modes.split(","))
+    if any(m in EXR_MODES for m in modes):
+        return main_exr(a, modes)
     run = Run(a.seed)
     if a.kernel_only:
         run.kernel_only()
@@ -165,6 +215,57 @@ def main():
         f.write("\n")
     if not result["required_A1_and_A2_below_A0_every_round"]:
         sys.exit("import_rate: stage_aov is not faster than the synchronous importer in every round: the staging does not overlap")
+
+
+def main_exr(a, modes):
+    """E0 / E1 beside A2, per compression; merged into --out under "exr" """
+    assert set(modes) <= set(EXR_MODES), "the EXR modes are measured on their own (with A2 beside them)"
+    tmp = None if a.exr_dir else tempfile.TemporaryDirectory()
+    have = a.exr_dir and all(os.path.exists(os.path.join(a.exr_dir, "frame%d_%s.exr" % (i, c))) for i in range(2) for c in EXR_COMPRESSIONS)
+    run = Run(a.seed, modes, a.exr_dir or tmp.name, files_only=bool(a.kernel_only and have))
+    if a.kernel_only:
+        run.kernel_only(n=10, modes=["E1:" + c for c in EXR_COMPRESSIONS])
+        run.ctx.close()
+        return
+    out = dict(width=W, height=H, seed=a.seed, seconds=a.seconds, compressions={})
+    ok = True
+    for comp in EXR_COMPRESSIONS:
+        names = ["A2"] + [m + ":" + comp for m in modes]
+        n = {}
+        for mode in names:  # warm every mode, and size its loop from the warm rate (E0 takes seconds per frame: two frames are a loop)
+            run.loop(mode, 2)
+            per = run.loop(mode, 2) / 2
+            n[mode] = max(2 if per > 0.25 else 20, int(math.ceil(a.seconds / per)))
+        size = run.exr_bytes[comp][0]
+        row0 = dict(file_bytes=run.exr_bytes[comp], file_bytes_per_pixel=round(size / (W * H), 3), ratio_to_typed_planes=round(size / (BYTES_PER_PIXEL["A2"] * W * H), 4),
+                    staged_bytes=run.ctx.exr_aov_stage_bytes(*run_file(run, comp)), frames=n, rounds=[])
+        for r in range(3):
+            row = {mode.split(":")[0]: round(run.loop(mode, n[mode]) / n[mode] * 1e3, 4) for mode in names}
+            if "E0" in row and "E1" in row:
+                row["E1_below_E0"] = row["E1"] < row["E0"]
+                ok = ok and row["E1_below_E0"]
+            if "E1" in row:
+                row["E1_over_A2"] = round(row["E1"] / row["A2"], 4)
+            row0["rounds"].append(row)
+            print(comp, json.dumps(row), flush=True)
+        assert run.ctx.exr_aov_status()[0] == 0
+        out["compressions"][comp] = row0
+    out["required_E1_below_E0_every_round"] = ok
+    run.ctx.close()
+    result = json.load(open(a.out)) if os.path.exists(a.out) else {}
+    result["exr"] = out
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+    if not ok:
+        sys.exit("import_rate: the device decode is not faster than the host decode in every round")
+
+
+def run_file(run, comp):
+    """(the bytes of frame 0's file of this compression, its layout)"""
+    data = open(run.frames["E1:" + comp][0].path, "rb").read()
+    return data, imageio.exr_aov_layout(data)
 
 
 if __name__ == "__main__":
