@@ -623,6 +623,37 @@ size_t rfx_exr_aov_stage_bytes(const rfx_ctx *, const rfx_exr_frame *, int row0,
 int rfx_stage_exr_aov(rfx_ctx *, const rfx_exr_frame *, int row0, int rows);
 int rfx_exr_aov_status(rfx_ctx *, int *bad_chunks, int *first_bad, int *code);
 
+/* ---- EXR blocks (additive to ABI 21: a host checks for the symbol): the streamed EXR frames above for the file forms other writers choose — tiled
+ * parts, RLE and PXR24 compression, a data window that is not the display window.  rfx_stage_exr_aov keeps its descriptor, checks and results; it
+ * and rfx_stage_exr_blocks run one plan and the same kernels.
+ * THE DESCRIPTOR.  rfx_exr_part and rfx_exr_channel as above.  A BLOCK is a rectangle of the frame: `x`, `y` its top-left texel (scanline 0 = top),
+ * `cols` x `rows` texels, stored as OpenEXR stores a chunk — per row, every channel's `cols` samples, in file order —; `offset` / `packed_bytes`:
+ * the PACKED DATA in the file bytes.  It serves a scanline chunk (x = 0, cols = width) and a tile alike: the library does not know which it is.
+ * The frame (width x height of the context) is the parts' common data window.
+ * COMPRESSIONS.  A part's compression is one of the five: NONE 0, RLE 1, ZIPS 2, ZIP 3, PXR24 5 (OpenEXR's numbers).
+ * GEOMETRY.  A block lies inside the frame, cols >= 1, rows >= 1.  There is no per-compression row rule: the decoders need none.
+ * SIZES.  The raw size rows x cols x bytes per texel is below 2^30; the packed size is 1 .. 2^30 - 1 and inside the file bytes; in a NONE part it
+ * equals the raw size.  A block whose packed size equals its raw size is the raw block, whatever the compression (OpenEXR's rule) — for PXR24
+ * with FLOAT channels that is whole 32-bit floats, while its zlib stream holds 3 bytes per FLOAT sample: the inflate must give exactly
+ * rows x cols x (2 per HALF channel + 3 per FLOAT channel) bytes, not the raw size.
+ * COVERAGE.  Within the band every texel of every part that feeds a plane lies in exactly one block of that part: two blocks on one texel, and a
+ * texel without a block, are both refused (checked on the host by sorting the x-intervals of the band's rows).
+ * THE BAND.  A block with a row inside the band is copied (one copy of exactly its packed bytes) and decoded whole; only its rows inside the band
+ * are scattered.  rfx_exr_blocks_stage_bytes is the sum of the packed bytes of exactly those blocks (0 for a frame the call would refuse).
+ * THE PLANES (components 0 .. n-1, F16 iff every channel is HALF, the missing alpha), the written-slot and band rules, the host-pointer lifetime
+ * and the back pressure, the staging areas' ownership and growth: rfx_stage_exr_aov's, word for word.
+ * STATUS.  Any byte string is safe to send: reads are bounded by the packed size, writes by the raw size.  A block that does not decode makes its
+ * rectangle read as not covered (depth 1, every other staged sample of it 0) and is counted; rfx_exr_aov_status reports, for the most recent call
+ * of either entry point, the bad blocks, the first one's index in the block table and its code (csrc/k9_inflate.h, csrc/k9_rle.h K9_E_*).
+ * RFX_EINVAL: what the rules above exclude, and rfx_stage_exr_aov's cases for parts, channels, planes and the band.  No new profile kind. */
+enum { RFX_EXR_RLE = 1, RFX_EXR_PXR24 = 5 };   /* beside NONE 0, ZIPS 2, ZIP 3: OpenEXR's own numbers */
+typedef struct rfx_exr_block { int part; int x; int y; int cols; int rows; int reserved;
+                               unsigned long long offset; unsigned long long packed_bytes; } rfx_exr_block;
+typedef struct rfx_exr_block_frame { const void *data; unsigned long long bytes; int parts; int blocks;
+                                     const rfx_exr_part *part; const rfx_exr_block *block; } rfx_exr_block_frame;
+size_t rfx_exr_blocks_stage_bytes(const rfx_ctx *, const rfx_exr_block_frame *, int row0, int rows);
+int    rfx_stage_exr_blocks(rfx_ctx *, const rfx_exr_block_frame *, int row0, int rows);
+
 /* ---- row-tiled runs: the exchanges, one process per GPU, RCCL over xGMI.  RCCL is bound at run time (a
  * single-GPU host needs none; a process that already maps an RCCL — e.g. torch's — shares it).
  * Tiles: rank r of n owns rfx_split_rows(height, n, r) — boundaries on even rows, the last tile takes the remainder.  The exchanges run on a second stream of the context: each call orders itself AFTER all draws

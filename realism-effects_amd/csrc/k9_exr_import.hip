@@ -1,15 +1,23 @@
-// K9 — EXR import: the scanline chunks of an OpenEXR AOV file, as they sit in the file, -> the typed staging planes of rfx_stage_aov, on the device
-// (include/rfx.h "streamed EXR frames").  The inverse of K8's EXR fragment (k8_exr.h) for any deflate stream a writer may produce.
+// K9 — EXR import: the chunks of an OpenEXR AOV file — scanline chunks or tiles —, as they sit in the file, -> the typed staging planes of
+// rfx_stage_aov, on the device (include/rfx.h "streamed EXR frames", "EXR blocks").  The inverse of K8's EXR fragment (k8_exr.h) for any deflate stream a writer may produce.
 //   k9_inflate     one wave per chunk.  The decoder is k9_inflate.h's, statement for statement the one the CPU tests run under the sanitizers;
 //                  here its state (bit buffer, positions, symbols) is wave-uniform — every lane computes the same values — and the IO below spreads
 //                  the memory work over the lanes: the input is read 256 bytes at a time, one dword per lane, and handed out by lane index; a literal
 //                  is stored by the lane its position names, a match or a stored run by all lanes, 64 bytes per step.  The chunk's scratch slot in
 //                  device memory is the output and the LZ77 window.  Decode tables: 3.5 KiB of LDS per wave (k9_inflate.h K9Tables), so LDS is not
 //                  what limits residency: the kernel's 112 VGPRs are, at 4 waves per SIMD, 16 per CU.  The parallelism is the number of chunks.  A chunk whose packed size is its raw size is copied.
+//                  ZIP, ZIPS and PXR24 streams alike (a PXR24 stream must inflate to 3 bytes per FLOAT sample: K9Chunk.expect); it returns at once
+//                  for an RLE stream.
+//   k9_rle         one wave per chunk, which returns at once for every chunk that is not an RLE stream: k9_rle.h's expander on the same IO — the
+//                  walk over the count bytes is wave-uniform, a run or a literal (up to 128 bytes) is stored by all lanes.  What it leaves in the
+//                  scratch slot is what the inflate leaves for ZIP: the predicted, split bytes.
 //   k9_exr_planes  one block per chunk: t[i] = t[i-1] + d[i] - 128 is a byte prefix sum (4 KiB tiles, 16 bytes per thread, a block scan of the
 //                  thread sums), in place; the even/odd byte split is undone while the samples are read; every mapped channel's row goes to its
-//                  plane, row 0 = bottom (EXR scanlines run top-down), halves widened where the plane is F32.
-//   k9_exr_finish  the rows of a chunk that did not decode: depth 1 (not covered), everything else 0 (written by k9_exr_planes); the status words.
+//                  plane at (x + i, y + r) — a chunk is a rectangle of the frame, a scanline chunk one with x = 0, cols = W —, row 0 = bottom (EXR
+//                  scanlines run top-down), halves widened where the plane is F32.  A PXR24 stream instead: one segmented scan per (row, channel)
+//                  of the k-byte differences (k9_pxr24.h), the segments dealt to the block's four waves, 64 samples per step with a carry,
+//                  written straight into the planes.
+//   k9_exr_finish  the rectangle of a chunk that did not decode: depth 1 (not covered), everything else 0 (written by k9_exr_planes); the status words.
 // All integer work: nothing here depends on contraction.
 #include "rfx_device.h"
 #include "rfx_kernels.h"
@@ -18,6 +26,8 @@
 #define K9_FN RFX_DEV
 #define K9_NO_HOST_IO
 #include "k9_inflate.h"
+#include "k9_rle.h"
+#include "k9_pxr24.h"
 
 namespace {
 
@@ -69,6 +79,9 @@ struct K9WaveIO {
     RFX_DEV void copy_in(size_t pos, size_t src, unsigned int len) {
         for (unsigned int k = (unsigned int)lane; k < len; k += 64u) out[pos + k] = in[src + k];
     }
+    RFX_DEV void fill(size_t pos, unsigned int byte, unsigned int len) {
+        for (unsigned int k = (unsigned int)lane; k < len; k += 64u) out[pos + k] = (unsigned char)byte;
+    }
     // 256 bytes per step, one dword per lane: a piece of m bytes ending e bytes before the end adds (sum, sum of (m - j) byte_j + e * sum) to (a, b).
     // The sums stay below 2^64 for n < 2^30 (rfx_stage_exr_aov refuses a larger chunk) and are reduced once.
     RFX_DEV unsigned int adler(size_t n) {
@@ -100,13 +113,15 @@ struct K9WaveIO {
     RFX_DEV void sync() { K9_WAVE_FENCE(); }
 };
 
-RFX_DEV bool k9_raw_form(const K9Chunk &ck, const K9Part &pt) { return pt.stored || ck.packed == ck.raw; }
+RFX_DEV bool k9_raw_form(const K9Chunk &ck, const K9Part &pt) { return pt.compression == RFX_EXR_NONE || ck.packed == ck.raw; }
+RFX_DEV bool k9_rle_form(const K9Chunk &ck, const K9Part &pt) { return pt.compression == RFX_EXR_RLE && ck.packed != ck.raw; }
 
 __global__ __launch_bounds__(64) void k9_inflate(K9Args A) {
     __shared__ K9Tables tables;
     __shared__ unsigned int red[128];
     const K9Chunk ck = A.chunks[blockIdx.x];
     const K9Part pt = A.parts[ck.part];
+    if (k9_rle_form(ck, pt)) return;  // k9_rle's
     const int lane = (int)threadIdx.x;
     const unsigned char *in = A.packed + ck.src;
     unsigned char *out = A.scratch + ck.dst;
@@ -119,9 +134,20 @@ __global__ __launch_bounds__(64) void k9_inflate(K9Args A) {
         K9WaveIO io;
         io.in = in; io.in_len = ck.packed; io.nwords = ((size_t)ck.packed + 3) / 4; io.out = out; io.t = &tables; io.red = red; io.lane = lane;
         io.win_base = ~(size_t)0; io.win = 0u; io.synced = 0;
-        code = k9_inflate_zlib(io, (size_t)ck.packed, (size_t)ck.raw);
+        code = k9_inflate_zlib(io, (size_t)ck.packed, (size_t)ck.expect);  // (expect <= raw, the slot's size)
     }
     if (lane == 0) A.err[blockIdx.x] = code;
+}
+
+__global__ __launch_bounds__(64) void k9_rle(K9Args A) {
+    const K9Chunk ck = A.chunks[blockIdx.x];
+    const K9Part pt = A.parts[ck.part];
+    if (!k9_rle_form(ck, pt)) return;  // k9_inflate's
+    K9WaveIO io;
+    io.in = A.packed + ck.src; io.in_len = ck.packed; io.nwords = ((size_t)ck.packed + 3) / 4; io.out = A.scratch + ck.dst; io.t = nullptr; io.red = nullptr;
+    io.lane = (int)threadIdx.x; io.win_base = ~(size_t)0; io.win = 0u; io.synced = 0;
+    const int code = k9_rle_expand(io, (size_t)ck.packed, (size_t)ck.raw);
+    if (threadIdx.x == 0) A.err[blockIdx.x] = code;
 }
 
 constexpr int K9_PLANES_BLOCK = 256, K9_SCAN_BYTES = 16;
@@ -140,6 +166,37 @@ __global__ __launch_bounds__(K9_PLANES_BLOCK) void k9_exr_planes(K9Args A) {
     const int err = A.err[blockIdx.x];
     const bool raw_form = k9_raw_form(ck, pt);
     const unsigned int n = ck.raw;
+    const unsigned int cols = (unsigned int)ck.cols;
+    if (pt.compression == RFX_EXR_PXR24 && !raw_form && !err) {
+        // buf: per row and channel the k byte planes of the differences.  One (row, channel) segment per wave and turn; everything that decides
+        // whether a segment is walked is wave-uniform, so the shuffles below see all 64 lanes.
+        const int wave = tid >> 6, lane = tid & 63, nsegs = ck.rows * pt.nchan;
+        for (int sg = wave; sg < nsegs; sg += K9_PLANES_BLOCK / 64) {
+            const int r = sg / pt.nchan;
+            const K9Chan ch = A.chans[pt.chan0 + (sg - r * pt.nchan)];
+            if (ch.plane < 0) continue;
+            const int fy = A.H - 1 - (ck.y + r);
+            const int s = k9_segment(A, ch.plane, fy);
+            if (s < 0) continue;
+            const unsigned char *seg = buf + (size_t)r * cols * pt.pxr_bytes + (size_t)cols * ch.pxr_off;
+            const unsigned int k = k9_pxr24_planes(ch.half);
+            const size_t row = ((size_t)(fy - A.seg_row0[s]) * A.W + (size_t)ck.x) * A.plane_ch[ch.plane] + ch.comp;
+            unsigned int carry = 0u;
+            for (unsigned int base = 0; base < cols; base += 64u) {
+                const unsigned int i = base + (unsigned int)lane;
+                unsigned int sum = k9_pxr24_diff(seg, cols, k, i);
+                for (int off = 1; off < 64; off <<= 1) sum = k9_pxr24_scan_step(lane, off, sum, (unsigned int)__shfl((int)sum, lane - off));
+                sum += carry;
+                carry = (unsigned int)__shfl((int)sum, 63);
+                if (i >= cols) continue;
+                const unsigned int bits = k9_pxr24_bits(sum, ch.half);
+                const size_t dst = row + (size_t)i * A.plane_ch[ch.plane];
+                if (A.plane_half[ch.plane]) ((unsigned short *)A.seg_plane[s][ch.plane])[dst] = (unsigned short)bits;
+                else ((float *)A.seg_plane[s][ch.plane])[dst] = ch.half ? rfx_h2f((unsigned short)bits) : __uint_as_float(bits);
+            }
+        }
+        return;
+    }
     if (!raw_form && !err) {
         unsigned int carry = 0u;  // the sum of every d[j] - 128 before the tile, mod 256
         for (unsigned int tile = 0; tile < n; tile += K9_PLANES_BLOCK * K9_SCAN_BYTES) {
@@ -175,20 +232,20 @@ __global__ __launch_bounds__(K9_PLANES_BLOCK) void k9_exr_planes(K9Args A) {
     __syncthreads();
     const unsigned int half_n = (n + 1u) / 2u;  // the even-indexed bytes of the raw block come first
     const auto raw_byte = [&](unsigned int p) -> unsigned int { return raw_form ? buf[p] : ((p & 1u) ? buf[half_n + (p >> 1)] : buf[p >> 1]); };
-    const unsigned int per_row = (unsigned int)pt.nchan * (unsigned int)A.W, total = (unsigned int)ck.rows * per_row;
+    const unsigned int per_row = (unsigned int)pt.nchan * cols, total = (unsigned int)ck.rows * per_row, row_bytes = cols * pt.texel_bytes;
     for (unsigned int i = (unsigned int)tid; i < total; i += K9_PLANES_BLOCK) {
-        const unsigned int r = i / per_row, rem = i - r * per_row, c = rem / (unsigned int)A.W, x = rem - c * (unsigned int)A.W;
+        const unsigned int r = i / per_row, rem = i - r * per_row, c = rem / cols, x = rem - c * cols;
         const K9Chan ch = A.chans[pt.chan0 + (int)c];
         if (ch.plane < 0) continue;
         const int fy = A.H - 1 - (ck.y + (int)r);
         const int s = k9_segment(A, ch.plane, fy);
         if (s < 0) continue;
-        const size_t dst = ((size_t)(fy - A.seg_row0[s]) * A.W + x) * A.plane_ch[ch.plane] + ch.comp;
+        const size_t dst = ((size_t)(fy - A.seg_row0[s]) * A.W + (size_t)ck.x + x) * A.plane_ch[ch.plane] + ch.comp;
         unsigned int bits;
         if (err) {
             bits = 0u;
         } else {
-            const unsigned int p = r * pt.row_bytes + ch.row_off + x * (ch.half ? 2u : 4u);
+            const unsigned int p = r * row_bytes + cols * ch.off + x * (ch.half ? 2u : 4u);
             bits = raw_byte(p) | (raw_byte(p + 1u) << 8);
             if (!ch.half) bits |= (raw_byte(p + 2u) << 16) | (raw_byte(p + 3u) << 24);
         }
@@ -205,13 +262,13 @@ __global__ __launch_bounds__(256) void k9_exr_finish(K9Args A) {
         atomicAdd((unsigned int *)A.status, 1u);
         atomicMax(A.status + 1, 0x7fffffff - ((ck.index << 8) | err));
     }
-    const unsigned int total = (unsigned int)ck.rows * (unsigned int)A.W;
+    const unsigned int cols = (unsigned int)ck.cols, total = (unsigned int)ck.rows * cols;
     for (unsigned int i = threadIdx.x; i < total; i += 256u) {
-        const unsigned int r = i / (unsigned int)A.W, x = i - r * (unsigned int)A.W;
+        const unsigned int r = i / cols, x = i - r * cols;
         const int fy = A.H - 1 - (ck.y + (int)r);
         const int s = k9_segment(A, RFX_AOV_DEPTH, fy);
         if (s < 0) continue;
-        const size_t dst = (size_t)(fy - A.seg_row0[s]) * A.W + x;
+        const size_t dst = (size_t)(fy - A.seg_row0[s]) * A.W + (size_t)ck.x + x;
         if (A.plane_half[RFX_AOV_DEPTH]) ((unsigned short *)A.seg_plane[s][RFX_AOV_DEPTH])[dst] = (unsigned short)0x3c00u;
         else ((float *)A.seg_plane[s][RFX_AOV_DEPTH])[dst] = 1.0f;
     }
@@ -222,6 +279,7 @@ __global__ __launch_bounds__(256) void k9_exr_finish(K9Args A) {
 hipError_t rfx_launch_k9(const K9Args &A, hipStream_t stream) {
     if (A.nchunks <= 0 || !A.chunks || !A.parts || !A.chans || !A.packed || !A.scratch || !A.err || !A.status) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k9_inflate, dim3(A.nchunks), dim3(64), 0, stream, A);
+    if (A.rle_chunks > 0) hipLaunchKernelGGL(k9_rle, dim3(A.nchunks), dim3(64), 0, stream, A);  // (a frame without an RLE stream: nothing to do)
     hipLaunchKernelGGL(k9_exr_planes, dim3(A.nchunks), dim3(K9_PLANES_BLOCK), 0, stream, A);
     hipLaunchKernelGGL(k9_exr_finish, dim3(A.nchunks), dim3(256), 0, stream, A);
     return hipGetLastError();

@@ -195,26 +195,33 @@ struct K8ExrArgs {
 };
 hipError_t rfx_launch_k8_exr(const K8ExrArgs &, hipStream_t);
 
-// K9 EXR import (k9_exr_import.hip): the packed scanline chunks of an OpenEXR file -> the typed AOV staging planes k0_aov_pack reads (include/rfx.h
-// "streamed EXR frames").  Three launches on `stream`: k9_inflate (one wave per chunk: zlib stream or raw block -> the chunk's scratch slot),
-// k9_exr_planes (one block per chunk: predictor and byte split undone, the mapped channels scattered, rows flipped), k9_exr_finish (the rows of a
-// bad chunk read as not covered; the status words).  The tables are device copies of the call's descriptor, built by rfx_stage_exr_aov.
+// K9 EXR import (k9_exr_import.hip): the packed blocks of an OpenEXR file — scanline chunks or tiles, a rectangle of the frame each — -> the typed
+// AOV staging planes k0_aov_pack reads (include/rfx.h "streamed EXR frames", "EXR blocks").  Four launches on `stream`: k9_inflate (one wave per
+// block: zlib stream or raw block -> the block's scratch slot), k9_rle (one wave per block: the RLE parts' blocks), k9_exr_planes (one block of
+// threads per file block: predictor and byte split, or PXR24's differences, undone, the mapped channels scattered, rows flipped), k9_exr_finish
+// (the rectangle of a bad block reads as not covered; the status words).  The tables are device copies of the call's descriptor, built by
+// rfx_api.hip's exr_blocks_plan for both entry points.
 struct K9Chunk {
     unsigned long long src, dst;  // 256-byte-aligned offsets of the packed bytes / of the scratch slot (raw bytes, which is the LZ77 window too)
     unsigned int packed, raw;     // packed == raw: the raw block itself
-    int part, y, rows;            // y: the EXR scanline (0 = top) of the chunk's first row
-    int index;                    // in the descriptor's chunk table (what the status reports)
+    unsigned int expect;          // what the decoder must produce: raw, but for PXR24 3 bytes per FLOAT sample
+    int part, x, y, cols, rows;   // the block's top-left texel (EXR scanline 0 = top) and size; a scanline chunk: x = 0, cols = W
+    int index;                    // in the descriptor's chunk / block table (what the status reports)
+    int pad;
 };
-struct K9Chan { int half, plane, comp; unsigned int row_off; };  // plane < 0: dropped; row_off: bytes from the scanline's start to the channel's W samples
-struct K9Part { int chan0, nchan; unsigned int row_bytes; int stored; };  // stored: compression NONE
+// plane < 0: dropped; off / pxr_off: bytes per texel of the part's channels before this one, raw and as PXR24 stores them — the channel's samples
+// of a block's row start cols x that many bytes behind the row's start
+struct K9Chan { int half, plane, comp; unsigned int off, pxr_off; };
+struct K9Part { int chan0, nchan; unsigned int texel_bytes, pxr_bytes; int compression; };  // OpenEXR's number (rfx.h RFX_EXR_*)
 struct K9Args {
     const K9Chunk *chunks;
     const K9Part *parts;
     const K9Chan *chans;
     int nchunks;
+    int rle_chunks;            // how many of them are RLE streams (0: k9_rle is not launched)
     const unsigned char *packed;
     unsigned char *scratch;
-    int *err;                  // per chunk: k9_inflate.h's K9_E_* (0: decoded)
+    int *err;                  // per chunk: k9_inflate.h's / k9_rle.h's K9_E_* (0: decoded)
     int *status;               // [0] bad chunks, [1] 0x7fffffff - ((index << 8) | code) of the first bad chunk (0: none), zeroed before the launches
     int W, H;
     int nseg;                  // rfx_aov_plan's segments: frame rows [seg_row0, seg_row0 + seg_rows) and where each plane's rows of them are staged

@@ -146,6 +146,15 @@ class Renderer {
 	exrAovStatus() {
 		return addon.exrAovStatus(this._h)
 	}
+	// EXR blocks (rfx.h): the same for tiled parts, RLE and PXR24, a moved data window — `layout` = imageio.exrAovLayout(bytes, names, { forms:
+	// "blocks" }), whose `blocks` are rectangles of the frame (a scanline chunk or a tile each).  exrAovStatus() reports on either call.
+	stageExrBlocks(bytes, layout, row0, rows) {
+		addon.stageExrBlocks(this._h, bytes, layout.parts, layout.blocks, row0 === undefined ? 0 : row0, rows === undefined ? this.height - (row0 || 0) : rows)
+		;(this._stagedExrNow = this._stagedExrNow || []).push(bytes) // kept alive until the copies of this batch have executed (stageFlip)
+	}
+	exrBlocksStageBytes(bytes, layout, row0, rows) {
+		return addon.exrBlocksStageBytes(this._h, bytes, layout.parts, layout.blocks, row0 === undefined ? 0 : row0, rows === undefined ? this.height - (row0 || 0) : rows)
+	}
 	// a frame with packed planes, or — no `gbuffer` — with `aov` attribute planes
 	stageFrame(frame) {
 		if (!frame.gbuffer) {

@@ -213,12 +213,19 @@ class ExrNotStreamable extends Error {}
 // plane or -1, component]; chunks = 32-byte records { int32 part, y, rows, 0; uint64 offset of the packed data, packed bytes }.
 // Throws ExrNotStreamable for what stays on the host: tiled or deep files, RLE / PIZ / PXR24 parts, UINT channels, a dataWindow that is not the
 // displayWindow.
-function exrAovLayout(buffer, names) {
+// options.forms = "blocks" (rfx.h "EXR blocks", Renderer.stageExrBlocks): `blocks` in place of `chunks` — 40-byte records { int32 part, x, y, cols,
+// rows, 0; uint64 offset of the packed data, packed bytes }, a scanline chunk or a tile each — and `blockCount`; scanline and tiled parts (level 0
+// of a mip-mapped one), NONE / RLE / ZIPS / ZIP / PXR24, any data window every part shares (the frame is the data window).  ExrNotStreamable then:
+// PIZ, deep data, UINT channels, parts of different data windows.
+function exrAovLayout(buffer, names, options) {
+	const forms = (options && options.forms) || "scanline"
+	if (forms !== "scanline" && forms !== "blocks") throw new Error('forms: "scanline" or "blocks"')
+	const asBlocks = forms === "blocks"
 	const b = Buffer.from(buffer.buffer, buffer.byteOffset, buffer.byteLength)
 	if (b.length < 8 || b.readUInt32LE(0) !== 0x01312f76) throw new Error("not an OpenEXR file")
 	const version = b.readInt32LE(4)
 	if (version & 0x800) throw new ExrNotStreamable("deep data")
-	if (version & 0x200) throw new ExrNotStreamable("a tiled file")
+	if (version & 0x200 && !asBlocks) throw new ExrNotStreamable("a tiled file")
 	const multipart = !!(version & 0x1000)
 	const cstr = pos => {
 		const e = b.indexOf(0, pos)
@@ -246,16 +253,19 @@ function exrAovLayout(buffer, names) {
 	const feeds = {}
 	Object.keys(AOV_LAYOUT).forEach((key, pi) => layout[key].forEach((cn, j) => (feeds[cn] = [pi, j])))
 	const partWords = [headers.length], records = [], seen = {}
-	let W = -1, H = -1
+	let W = -1, H = -1, window = null
 	headers.forEach((attrs, k) => {
-		const type = attrs.type ? attrs.type.toString("latin1").replace(/\0+$/, "") : "scanlineimage"
-		if (type !== "scanlineimage") throw new ExrNotStreamable("a part of type " + type)
+		const type = attrs.type ? attrs.type.toString("latin1").replace(/\0+$/, "") : version & 0x200 ? "tiledimage" : "scanlineimage"
+		if (type !== "scanlineimage" && !(asBlocks && type === "tiledimage")) throw new ExrNotStreamable("a part of type " + type)
+		const tiled = type === "tiledimage"
 		const comp = attrs.compression[0]
-		if (comp !== 0 && comp !== 2 && comp !== 3) {
+		if (comp !== 0 && comp !== 2 && comp !== 3 && !(asBlocks && (comp === 1 || comp === 5))) {
 			if (comp === 1 || comp === 4 || comp === 5) throw new ExrNotStreamable("compression " + { 1: "RLE", 4: "PIZ", 5: "PXR24" }[comp])
 			throw new Error("compression " + comp + " not supported")
 		}
-		if (Buffer.compare(attrs.dataWindow, attrs.displayWindow) !== 0) throw new ExrNotStreamable("the dataWindow is not the displayWindow")
+		if (!asBlocks && Buffer.compare(attrs.dataWindow, attrs.displayWindow) !== 0) throw new ExrNotStreamable("the dataWindow is not the displayWindow")
+		if (asBlocks && window && Buffer.compare(attrs.dataWindow, window) !== 0) throw new ExrNotStreamable("parts of different data windows")
+		window = attrs.dataWindow
 		const dw = attrs.dataWindow, y0 = dw.readInt32LE(4)
 		const w = dw.readInt32LE(8) - dw.readInt32LE(0) + 1, h = dw.readInt32LE(12) - y0 + 1
 		if (W >= 0 && (w !== W || h !== H)) throw new Error("parts of different sizes")
@@ -277,15 +287,38 @@ function exrAovLayout(buffer, names) {
 			p = e + 17
 		}
 		partWords.push(comp, chans.length / 3, ...chans)
-		const per = comp === 3 ? 16 : 1
-		const n = attrs.chunkCount ? attrs.chunkCount.readInt32LE(0) : Math.ceil(H / per)
-		const hdr = multipart ? 12 : 8
-		for (let i = 0; i < n; i++) {
+		const per = comp === 3 || comp === 5 ? 16 : 1
+		let level0 = Math.ceil(H / per), n = level0, tw = 0, th = 0, ntx = 0, nty = 0
+		if (tiled) {
+			tw = attrs.tiles.readUInt32LE(0)
+			th = attrs.tiles.readUInt32LE(4)
+			const mode = attrs.tiles[8]
+			if ((mode & 15) === 2) throw new Error("rip-mapped tiles are not supported")
+			ntx = Math.ceil(W / tw)
+			nty = Math.ceil(H / th)
+			level0 = n = ntx * nty // level 0 comes first in the offset table (the only level, or the mip chain's base)
+			if (mode & 15) for (let lw = W, lh = H; !(lw === 1 && lh === 1); n += Math.ceil(lw / tw) * Math.ceil(lh / th)) {
+				lw = Math.max(1, (lw + (mode >> 4)) >> 1)
+				lh = Math.max(1, (lh + (mode >> 4)) >> 1)
+			}
+		}
+		if (attrs.chunkCount) n = attrs.chunkCount.readInt32LE(0)
+		if (!tiled) level0 = n
+		const hdr = (multipart ? 4 : 0) + (tiled ? 20 : 8)
+		for (let i = 0; i < level0; i++) {
 			const o = Number(b.readBigUInt64LE(pos + 8 * i))
 			if (o + hdr > b.length) throw new Error("a chunk offset outside the file")
 			if (multipart && b.readInt32LE(o) !== k) throw new Error("a chunk of part " + k + " carries another part number")
-			const y = b.readInt32LE(o + hdr - 8) - y0
-			records.push([k, y, Math.min(per, H - y), o + hdr, b.readInt32LE(o + hdr - 4)])
+			const packed = b.readInt32LE(o + hdr - 4)
+			if (tiled) {
+				const tx = b.readInt32LE(o + hdr - 20), ty = b.readInt32LE(o + hdr - 16)
+				if (b.readInt32LE(o + hdr - 12) || b.readInt32LE(o + hdr - 8) || tx < 0 || tx >= ntx || ty < 0 || ty >= nty)
+					throw new Error("an unexpected tile among the first " + level0 + " of part " + k + " (level 0 comes first)")
+				records.push([k, tx * tw, ty * th, Math.min(tw, W - tx * tw), Math.min(th, H - ty * th), o + hdr, packed])
+			} else {
+				const y = b.readInt32LE(o + hdr - 8) - y0 // relative to the data window, like a tile's coordinates
+				records.push([k, 0, y, W, Math.min(per, H - y), o + hdr, packed])
+			}
 		}
 		pos += 8 * n
 	})
@@ -297,8 +330,17 @@ function exrAovLayout(buffer, names) {
 			throw new Error("channel(s) " + missing.join(", ") + " of AOV " + key + " missing")
 		planes[key] = [have.length, have.every(c => seen[c] === 1) ? "half" : "float"]
 	}
+	if (asBlocks) {
+		const blocks = Buffer.alloc(40 * records.length)
+		records.forEach((r, i) => {
+			for (let j = 0; j < 5; j++) blocks.writeInt32LE(r[j], 40 * i + 4 * j)
+			blocks.writeBigUInt64LE(BigInt(r[5]), 40 * i + 24)
+			blocks.writeBigUInt64LE(BigInt(r[6]), 40 * i + 32)
+		})
+		return { width: W, height: H, fileBytes: b.length, parts: Int32Array.from(partWords), blocks: new Uint8Array(blocks.buffer, blocks.byteOffset, blocks.length), blockCount: records.length, planes }
+	}
 	const chunks = Buffer.alloc(32 * records.length)
-	records.forEach(([part, y, rows, offset, packed], i) => {
+	records.forEach(([part, , y, , rows, offset, packed], i) => {
 		chunks.writeInt32LE(part, 32 * i)
 		chunks.writeInt32LE(y, 32 * i + 4)
 		chunks.writeInt32LE(rows, 32 * i + 8)

@@ -300,7 +300,7 @@ static napi_value n_aov_stage_bytes(napi_env env, napi_callback_info info) { ret
  * hostAlloc() memory), `parts` an Int32Array [parts, then per part: compression, channels, then per channel: pixel type, plane, component],
  * `chunks` a Uint8Array of rfx_exr_chunk records.  The descriptor is consumed by the call: its tables are copies in one block, *hold, which the
  * caller frees.  Returns 0 after throwing. */
-static int read_exr_frame(napi_env env, napi_value bytes, napi_value parts, napi_value chunks, rfx_exr_frame *f, void **hold) {
+static int read_exr_frame(napi_env env, napi_value bytes, napi_value parts, napi_value chunks, size_t record, rfx_exr_frame *f, void **hold) {
     napi_typedarray_type tb, tp, tc;
     size_t nb, np, nc;
     void *pb, *pp, *pc;
@@ -313,7 +313,7 @@ static int read_exr_frame(napi_env env, napi_value bytes, napi_value parts, napi
     }
     const int32_t *w = (const int32_t *)pp;
     size_t nparts = np ? (size_t)w[0] : 0, at = 1, nchan = 0;
-    int ok = np >= 1 && w[0] > 0 && nc % sizeof(rfx_exr_chunk) == 0 && nc > 0;
+    int ok = np >= 1 && w[0] > 0 && nc % record == 0 && nc > 0;
     for (size_t k = 0; ok && k < nparts; k++) {  /* walk the list once: it must end where the array ends */
         if (at + 2 > np || w[at + 1] <= 0 || at + 2 + 3 * (size_t)w[at + 1] > np) { ok = 0; break; }
         nchan += (size_t)w[at + 1];
@@ -332,7 +332,7 @@ static int read_exr_frame(napi_env env, napi_value bytes, napi_value parts, napi
         for (int32_t i = 0; i < w[at + 1]; i++, C++) { C->pixel_type = w[at + 2 + 3 * i]; C->plane = w[at + 3 + 3 * i]; C->component = w[at + 4 + 3 * i]; }
         at += 2 + 3 * (size_t)w[at + 1];
     }
-    f->data = pb; f->bytes = nb; f->parts = (int)nparts; f->chunks = (int)(nc / sizeof(rfx_exr_chunk));
+    f->data = pb; f->bytes = nb; f->parts = (int)nparts; f->chunks = (int)(nc / record);
     f->part = P; f->chunk = (const rfx_exr_chunk *)block;
     *hold = block;
     return 1;
@@ -347,7 +347,7 @@ static napi_value exr_aov_call(napi_env env, napi_callback_info info, int stage)
     if (!get_args(env, info, 6, a)) return NULL;
     rfx_ctx *c = get_ctx(env, a[0]);
     if (!c || !get_int(env, a[4], &row0) || !get_int(env, a[5], &rows)) return NULL;
-    if (!read_exr_frame(env, a[1], a[2], a[3], &f, &hold)) return NULL;
+    if (!read_exr_frame(env, a[1], a[2], a[3], sizeof(rfx_exr_chunk), &f, &hold)) return NULL;
     if (!stage) {
         const size_t n = rfx_exr_aov_stage_bytes(c, &f, row0, rows);
         free(hold);
@@ -361,6 +361,31 @@ static napi_value exr_aov_call(napi_env env, napi_callback_info info, int stage)
 }
 static napi_value n_stage_exr_aov(napi_env env, napi_callback_info info) { return exr_aov_call(env, info, 1); }
 static napi_value n_exr_aov_stage_bytes(napi_env env, napi_callback_info info) { return exr_aov_call(env, info, 0); }
+/* stageExrBlocks / exrBlocksStageBytes(ctx, bytes, parts, blocks, row0, rows): rfx_stage_exr_blocks / rfx_exr_blocks_stage_bytes (rfx.h "EXR
+ * blocks") — the same arguments, `blocks` a Uint8Array of rfx_exr_block records (imageio.exrAovLayout(..., { forms: "blocks" })) */
+static napi_value exr_blocks_call(napi_env env, napi_callback_info info, int stage) {
+    napi_value a[6], out = NULL;
+    int32_t row0, rows;
+    rfx_exr_frame f;
+    void *hold;
+    if (!get_args(env, info, 6, a)) return NULL;
+    rfx_ctx *c = get_ctx(env, a[0]);
+    if (!c || !get_int(env, a[4], &row0) || !get_int(env, a[5], &rows)) return NULL;
+    if (!read_exr_frame(env, a[1], a[2], a[3], sizeof(rfx_exr_block), &f, &hold)) return NULL;
+    const rfx_exr_block_frame b = {f.data, f.bytes, f.parts, f.chunks, f.part, (const rfx_exr_block *)hold};  /* (the records lead the block) */
+    if (!stage) {
+        const size_t n = rfx_exr_blocks_stage_bytes(c, &b, row0, rows);
+        free(hold);
+        NAPI_CALL(env, napi_create_double(env, (double)n, &out));
+        return out;
+    }
+    int rc = rfx_stage_exr_blocks(c, &b, row0, rows);
+    free(hold);
+    if (rc) return throw_rfx(env, c, "rfx_stage_exr_blocks", rc);
+    return NULL;
+}
+static napi_value n_stage_exr_blocks(napi_env env, napi_callback_info info) { return exr_blocks_call(env, info, 1); }
+static napi_value n_exr_blocks_stage_bytes(napi_env env, napi_callback_info info) { return exr_blocks_call(env, info, 0); }
 static napi_value n_exr_aov_status(napi_env env, napi_callback_info info) {
     napi_value a[1], out, v;
     int s[3] = {0, -1, 0};
@@ -1183,6 +1208,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"sync", n_sync}, {"setRowWindow", n_set_row_window}, {"setUvModel", n_set_uv_model}, {"cubeToEquirect", n_cube_to_equirect}, {"haloViolations", n_halo_violations}, {"timeBegin", n_time_begin}, {"timeEnd", n_time_end}, {"profile", n_profile}, {"profileRead", n_profile_read},
         {"stageUpload", n_stage_upload}, {"stageFlip", n_stage_flip}, {"hostAlloc", n_host_alloc}, {"stageAov", n_stage_aov}, {"aovStageBytes", n_aov_stage_bytes},
         {"stageExrAov", n_stage_exr_aov}, {"exrAovStageBytes", n_exr_aov_stage_bytes}, {"exrAovStatus", n_exr_aov_status},
+        {"stageExrBlocks", n_stage_exr_blocks}, {"exrBlocksStageBytes", n_exr_blocks_stage_bytes},
         {"exportBytes", n_export_bytes}, {"exportFrame", n_export_frame}, {"stageExport", n_stage_export}, {"exportWait", n_export_wait}, {"constants", n_constants},
         {"pngBound", n_png_bound}, {"pngFrame", n_png_frame}, {"stagePng", n_stage_png},
         {"exrBound", n_exr_bound}, {"exrFrame", n_exr_frame}, {"stageExr", n_stage_exr},

@@ -141,6 +141,23 @@ class ExrFrame(C.Structure):
     _fields_ = [("data", C.c_void_p), ("bytes", C.c_uint64), ("parts", C.c_int32), ("chunks", C.c_int32), ("part", C.POINTER(ExrPart)), ("chunk", C.POINTER(ExrChunk))]
 
 
+# rfx.h "EXR blocks": the descriptor of rfx_stage_exr_blocks — a block is a rectangle of the frame, a scanline chunk or a tile
+EXR_RLE, EXR_PXR24 = 1, 5
+
+
+class ExrBlock(C.Structure):
+    _fields_ = [("part", C.c_int32), ("x", C.c_int32), ("y", C.c_int32), ("cols", C.c_int32), ("rows", C.c_int32), ("reserved", C.c_int32), ("offset", C.c_uint64),
+                ("packed_bytes", C.c_uint64)]
+
+
+EXR_BLOCK_DTYPE = np.dtype([("part", "<i4"), ("x", "<i4"), ("y", "<i4"), ("cols", "<i4"), ("rows", "<i4"), ("reserved", "<i4"), ("offset", "<u8"),
+                            ("packed_bytes", "<u8")])  # ExrBlock as a numpy record
+
+
+class ExrBlockFrame(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("bytes", C.c_uint64), ("parts", C.c_int32), ("blocks", C.c_int32), ("part", C.POINTER(ExrPart)), ("block", C.POINTER(ExrBlock))]
+
+
 class FinalParams(C.Structure):
     _fields_ = [("camera", Camera), ("isDebug", C.c_int32), ("inputSource", C.c_int32), ("fogMode", C.c_int32), ("fogColor", C.c_float * 3), ("fogNear", C.c_float),
                 ("fogFar", C.c_float), ("fogDensity", C.c_float)]
@@ -167,6 +184,7 @@ EXPORTS = [
     "rfx_aov_stage_bytes", "rfx_stage_aov",
     "rfx_exr_bound", "rfx_stage_exr", "rfx_exr",
     "rfx_exr_aov_stage_bytes", "rfx_stage_exr_aov", "rfx_exr_aov_status",
+    "rfx_exr_blocks_stage_bytes", "rfx_stage_exr_blocks",
 ]
 
 _lib = None
@@ -284,6 +302,9 @@ def load_library(path: str | None = None) -> C.CDLL:
     lib.rfx_exr_aov_stage_bytes.restype = C.c_size_t
     lib.rfx_stage_exr_aov.argtypes = [vp, C.POINTER(ExrFrame), i, i]
     lib.rfx_exr_aov_status.argtypes = [vp, C.POINTER(i), C.POINTER(i), C.POINTER(i)]
+    lib.rfx_exr_blocks_stage_bytes.argtypes = [vp, C.POINTER(ExrBlockFrame), i, i]
+    lib.rfx_exr_blocks_stage_bytes.restype = C.c_size_t
+    lib.rfx_stage_exr_blocks.argtypes = [vp, C.POINTER(ExrBlockFrame), i, i]
     if lib.rfx_abi_version() != RFX_ABI_VERSION:
         raise ImportError("librfx_hip.so ABI version %d != %d" % (lib.rfx_abi_version(), RFX_ABI_VERSION))
     if path is None:

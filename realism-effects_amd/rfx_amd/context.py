@@ -204,9 +204,50 @@ class Context:
         self._chk(self.lib.rfx_exr_aov_status(self._h, C.byref(bad), C.byref(first), C.byref(code)), "rfx_exr_aov_status")
         return bad.value, first.value, code.value
 
+    # -- EXR blocks (rfx.h "EXR blocks"): the same for tiled parts, RLE and PXR24, a moved data window
+    def _exr_block_frame(self, buf, layout):
+        """-> (abi.ExrBlockFrame, the objects it points into); `layout`: imageio.exr_aov_layout(..., forms="blocks") of the same bytes"""
+        if (layout.width, layout.height) != (self.W, self.H):
+            raise ValueError("EXR frame of %d x %d on a context of %d x %d" % (layout.width, layout.height, self.W, self.H))
+        a = np.frombuffer(buf, np.uint8) if not isinstance(buf, np.ndarray) else buf
+        if not a.flags["C_CONTIGUOUS"] or a.nbytes < layout.file_bytes:
+            raise ValueError("EXR frame: a contiguous buffer of the file's %d bytes" % layout.file_bytes)
+        chans = [(abi.ExrChannel * len(ch))(*[abi.ExrChannel(pt, pl, comp) for pt, pl, comp in ch]) for _, ch in layout.parts]
+        parts = (abi.ExrPart * len(layout.parts))(*[abi.ExrPart(comp, len(ch), arr) for (comp, ch), arr in zip(layout.parts, chans)])
+        blocks = np.ascontiguousarray(layout.blocks, abi.EXR_BLOCK_DTYPE)
+        f = abi.ExrBlockFrame(a.ctypes.data, layout.file_bytes, len(parts), len(blocks), parts, blocks.ctypes.data_as(C.POINTER(abi.ExrBlock)))
+        return f, (a, (chans, parts, blocks))
+
+    @property
+    def has_exr_blocks(self) -> bool:
+        """the library exports rfx_stage_exr_blocks (additive to ABI 21)"""
+        return hasattr(self.lib, "rfx_stage_exr_blocks")
+
+    def exr_blocks_stage_bytes(self, buf, layout, row0: int | None = None, rows: int | None = None) -> int:
+        """rfx_exr_blocks_stage_bytes: the bytes stage_exr_blocks(buf, layout, row0, rows) copies host -> device (0: the library would refuse the frame)"""
+        f, _ = self._exr_block_frame(buf, layout)
+        return int(self.lib.rfx_exr_blocks_stage_bytes(self._h, C.byref(f), *self._band(row0, rows)))
+
+    def stage_exr_blocks(self, buf, layout, row0: int | None = None, rows: int | None = None):
+        """rfx_stage_exr_blocks: stage_exr_aov for a layout of blocks — scanline chunks and tiles, NONE / RLE / ZIPS / ZIP / PXR24; exr_aov_status()
+        reports on the most recent call of either"""
+        f, keep = self._exr_block_frame(buf, layout)
+        self.__dict__.setdefault("_staged_now", []).append(keep[0])  # kept alive until the copies of this batch have executed
+        self._chk(self.lib.rfx_stage_exr_blocks(self._h, C.byref(f), *self._band(row0, rows)), "rfx_stage_exr_blocks")
+
+    def stage_exr_device(self, buf, names: dict | None = None):
+        """One whole AOV EXR file held in `buf` through the device decode: the blocks form where the library has it, else the scanline form.
+        imageio.ExrNotStreamable: the file is one neither takes."""
+        from . import imageio
+        if self.has_exr_blocks:
+            self.stage_exr_blocks(buf, imageio.exr_aov_layout(buf, names, forms="blocks"))
+        else:
+            self.stage_exr_aov(buf, imageio.exr_aov_layout(buf, names))
+
     def stage_exr_frame(self, path: str, decode: str = "host", names: dict | None = None):
         """Stage a whole AOV EXR file.  decode="host" (the default): imageio.exr_to_typed_planes + stage_aov.  decode="device": the file's bytes
-        + stage_exr_aov; a file the device decode does not take (imageio.ExrNotStreamable: tiled, RLE / PIZ / PXR24, ...) goes the host's way.
+        + stage_exr_blocks (stage_exr_aov on a library without it); a file the device decode does not take (imageio.ExrNotStreamable: PIZ, deep
+        data, UINT channels, ...) goes the host's way.
         -> the way taken, "host" or "device"."""
         from . import imageio
         if decode not in ("host", "device"):
@@ -215,7 +256,7 @@ class Context:
             with open(path, "rb") as f:
                 data = f.read()
             try:
-                self.stage_exr_aov(data, imageio.exr_aov_layout(data, names))
+                self.stage_exr_device(data, names)
                 return "device"
             except imageio.ExrNotStreamable:
                 pass

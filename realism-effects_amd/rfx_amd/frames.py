@@ -87,7 +87,8 @@ class FrameExporter:
 
 class ExrSequence:
     """Per-frame input of an offline run through the device EXR decode (include/rfx.h "streamed EXR frames"): the AOV EXR files of a directory, or
-    a list of paths, read with readinto() into two alternating pinned buffers and staged with Context.stage_exr_aov.
+    a list of paths, read with readinto() into two alternating pinned buffers and staged with Context.stage_exr_device (the EXR blocks where the
+    library has them: scanline and tiled parts, NONE / RLE / ZIPS / ZIP / PXR24).
 
         seq = ExrSequence(ctx, directory);  seq.stage(0); ctx.stage_flip()
         for i in range(len(seq)):  seq.stage(i + 1) if i + 1 < len(seq) else None;  <draws of frame i>;  ctx.stage_flip()
@@ -114,7 +115,7 @@ class ExrSequence:
         if got != size:
             raise IOError("%s: read %d of %d bytes" % (path, got, size))
         try:
-            self.ctx.stage_exr_aov(buf, imageio.exr_aov_layout(buf[:size], self.names))
+            self.ctx.stage_exr_device(buf[:size], self.names)  # (the blocks form where the library has it: tiled, RLE and PXR24 files too)
             return "device"
         except imageio.ExrNotStreamable:
             return self.ctx.stage_exr_frame(path, "host", self.names)

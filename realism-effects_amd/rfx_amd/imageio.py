@@ -22,7 +22,7 @@ import zlib
 
 import numpy as np
 
-from .abi import EXR_CHUNK_DTYPE  # rfx_exr_chunk as a numpy record: the one definition
+from .abi import EXR_BLOCK_DTYPE, EXR_CHUNK_DTYPE  # rfx_exr_block / rfx_exr_chunk as numpy records: the one definition
 
 
 # ------------------------------------------------------------------------------------------------ Radiance .hdr (RGBE)
@@ -924,9 +924,10 @@ def exr_channel_types(path: str) -> dict:
     return out
 
 
-def write_exr_multipart(path: str, parts: dict, compression: str = "zip", half: bool = False):
-    """parts: part name -> {channel: (H, W) array}: one scanline part per entry (how several renderers lay out AOVs).  half: True / False for
-    every part, or the names of the parts to store as binary16 (the rest float32)."""
+def write_exr_multipart(path: str, parts: dict, compression: str = "zip", half: bool = False, tiles=None):
+    """parts: part name -> {channel: (H, W) array}: one part per entry (how several renderers lay out AOVs).  half: True / False for
+    every part, or the names of the parts to store as binary16 (the rest float32).  tiles: None — scanline parts —, (tile_w, tile_h) — every
+    part a single-level tiled one, as write_exr's —, or {part name: (tile_w, tile_h)}: those parts tiled, the rest scanline."""
     comp = {"none": _COMP_NONE, "rle": _COMP_RLE, "zips": _COMP_ZIPS, "zip": _COMP_ZIP, "piz": _COMP_PIZ, "pxr24": _COMP_PXR24}[compression]
     per_block = {_COMP_NONE: 1, _COMP_RLE: 1, _COMP_ZIPS: 1, _COMP_ZIP: 16, _COMP_PIZ: 32, _COMP_PXR24: 16}[comp]
     headers, chunk_lists = b"", []
@@ -937,8 +938,16 @@ def write_exr_multipart(path: str, parts: dict, compression: str = "zip", half: 
         planes = [np.ascontiguousarray(np.asarray(channels[n])[::-1].astype(dt)) for n in names]
         H, W = planes[0].shape
         chans = [(n, pt) for n in names]
+        tile = tiles.get(pname) if isinstance(tiles, dict) else tiles
         chunks = []
-        for y0 in range(0, H, per_block):
+        if tile:
+            tw, th = tile
+            for ty in range((H + th - 1) // th):
+                for tx in range((W + tw - 1) // tw):
+                    y0, y1, x0, x1 = ty * th, min(H, ty * th + th), tx * tw, min(W, tx * tw + tw)
+                    raw = _exr_pack_block(b"".join(tp[y, x0:x1].tobytes() for y in range(y0, y1) for tp in planes), comp, chans, x1 - x0, y1 - y0)
+                    chunks.append(struct.pack("<iiiiii", k, tx, ty, 0, 0, len(raw)) + raw)
+        for y0 in range(0, 0 if tile else H, per_block):
             y1 = min(H, y0 + per_block)
             raw = _exr_pack_block(b"".join(tp[y].tobytes() for y in range(y0, y1) for tp in planes), comp, chans, W, y1 - y0)
             chunks.append(struct.pack("<iii", k, y0, len(raw)) + raw)
@@ -950,7 +959,9 @@ def write_exr_multipart(path: str, parts: dict, compression: str = "zip", half: 
                     _exr_attr(b"displayWindow", b"box2i", box) + _exr_attr(b"lineOrder", b"lineOrder", b"\0") +
                     _exr_attr(b"name", b"string", pname.encode()) + _exr_attr(b"pixelAspectRatio", b"float", struct.pack("<f", 1.0)) +
                     _exr_attr(b"screenWindowCenter", b"v2f", struct.pack("<ff", 0.0, 0.0)) +
-                    _exr_attr(b"screenWindowWidth", b"float", struct.pack("<f", 1.0)) + _exr_attr(b"type", b"string", b"scanlineimage") + b"\0")
+                    _exr_attr(b"screenWindowWidth", b"float", struct.pack("<f", 1.0)) +
+                    (_exr_attr(b"tiles", b"tiledesc", struct.pack("<IIB", tile[0], tile[1], 0)) if tile else b"") +
+                    _exr_attr(b"type", b"string", b"tiledimage" if tile else b"scanlineimage") + b"\0")
     head = b"\x76\x2f\x31\x01" + struct.pack("<i", 2 | 0x1000) + headers + b"\0"
     pos = len(head) + 8 * sum(len(c) for c in chunk_lists)
     table = b""
@@ -1039,25 +1050,41 @@ class ExrAovLayout:
     """What Context.stage_exr_aov needs besides the file's bytes (rfx.h rfx_exr_frame): per part its compression and, per channel in file order,
     (pixel type, plane index in AOV_LAYOUT's order or -1, component); the chunk table as records (part, y, rows, reserved, offset of the packed
     data, packed bytes); and what follows from them: `planes` = {name: (channels, "half" | "float")} as the device will stage them."""
-    def __init__(self, width, height, file_bytes, parts, chunks, planes):
+    def __init__(self, width, height, file_bytes, parts, chunks, planes, blocks=None):
         self.width, self.height, self.file_bytes, self.parts, self.chunks, self.planes = width, height, file_bytes, parts, chunks, planes
+        # forms="blocks" (rfx.h rfx_exr_block_frame, Context.stage_exr_blocks): records (part, x, y, cols, rows, reserved, offset, packed bytes) of
+        # abi.EXR_BLOCK_DTYPE — a scanline chunk or a tile each — in place of `chunks`
+        self.blocks = blocks
 
-    def band_chunks(self, row0=None, rows=None):
-        """the records of the chunks a band [row0, row0 + rows) of frame rows (0 = bottom) needs: a scanline inside it, a part that feeds a plane"""
+    def _band(self, c, row0, rows):
         row0 = 0 if row0 is None else row0
         rows = self.height - row0 if rows is None else rows
         y_lo, y_hi = self.height - row0 - rows, self.height - row0
         mapped = np.array([any(pl >= 0 for _, pl, _ in chans) for _, chans in self.parts])
-        c = self.chunks
         return c[mapped[c["part"]] & (c["y"] < y_hi) & (c["y"] + c["rows"] > y_lo)]
 
+    def band_chunks(self, row0=None, rows=None):
+        """the records of the chunks a band [row0, row0 + rows) of frame rows (0 = bottom) needs: a scanline inside it, a part that feeds a plane"""
+        return self._band(self.chunks, row0, rows)
 
-def exr_aov_layout(path_or_bytes, names: dict | None = None) -> ExrAovLayout:
+    def band_blocks(self, row0=None, rows=None):
+        """band_chunks for a layout of blocks: the blocks with a row inside the band, of the parts that feed a plane"""
+        return self._band(self.blocks, row0, rows)
+
+
+def exr_aov_layout(path_or_bytes, names: dict | None = None, forms: str = "scanline") -> ExrAovLayout:
     """Parse the header(s) and the offset table(s) of an AOV EXR — a path, or the file's bytes (bytes, a memoryview, a uint8 array: a pinned
     buffer the file was read into) — for the device decode.  Channel names map to planes as exr_to_typed_planes maps them (AOV_LAYOUT, `names`):
     a plane none of whose channels is in the file is absent, a diffuse / direct plane without its fourth channel has three (alpha 1), a plane
     whose channels are all HALF is staged as halves.  Channels no plane names are dropped on the device.
-    ExrNotStreamable: tiled or deep files, RLE / PIZ / PXR24 parts, UINT channels, a dataWindow that is not the displayWindow."""
+    forms="scanline" (the default), for Context.stage_exr_aov: `chunks`.  ExrNotStreamable: tiled or deep files, RLE / PIZ / PXR24 parts, UINT
+    channels, a dataWindow that is not the displayWindow.
+    forms="blocks", for Context.stage_exr_blocks: `blocks`, a rectangle of the frame each — scanline and tiled parts (level 0 of a mip-mapped
+    one), NONE / RLE / ZIPS / ZIP / PXR24, any data window every part shares: the frame is the data window, as for read_exr.
+    ExrNotStreamable: PIZ, deep data, UINT channels, parts of different data windows."""
+    if forms not in ("scanline", "blocks"):
+        raise ValueError('forms: "scanline" or "blocks"')
+    as_blocks = forms == "blocks"
     if isinstance(path_or_bytes, (str, os.PathLike)):
         with open(path_or_bytes, "rb") as f:
             data = f.read()
@@ -1070,7 +1097,7 @@ def exr_aov_layout(path_or_bytes, names: dict | None = None) -> ExrAovLayout:
     version = struct.unpack("<i", bytes(u8[4:8]))[0]
     if version & 0x800:
         raise ExrNotStreamable("%s: deep data" % what)
-    if version & 0x200:
+    if version & 0x200 and not as_blocks:
         raise ExrNotStreamable("%s: a tiled file" % what)
     multipart = bool(version & 0x1000)
     head_len = 1 << 16
@@ -1092,16 +1119,20 @@ def exr_aov_layout(path_or_bytes, names: dict | None = None) -> ExrAovLayout:
     layout = dict(AOV_LAYOUT)
     layout.update(names or {})
     feeds = {cn: (pi, j) for pi, key in enumerate(AOV_LAYOUT) for j, cn in enumerate(layout[key])}
-    parts, tables, W, H, seen = [], [], None, None, {}
+    parts, tables, W, H, seen, window = [], [], None, None, {}, None
     for k, attrs in enumerate(headers):
-        typ = attrs.get(b"type", (b"", b"scanlineimage"))[1].rstrip(b"\0")
-        if typ != b"scanlineimage":
+        typ = attrs.get(b"type", (b"", b"tiledimage" if version & 0x200 else b"scanlineimage"))[1].rstrip(b"\0")
+        if typ != b"scanlineimage" and not (as_blocks and typ == b"tiledimage"):
             raise ExrNotStreamable("%s: a part of type %s" % (what, typ.decode()))
-        lay = _exr_part_layout(what, attrs, False)
-        if lay["comp"] not in (_COMP_NONE, _COMP_ZIPS, _COMP_ZIP):
+        tiled = typ == b"tiledimage"
+        lay = _exr_part_layout(what, attrs, tiled)
+        if lay["comp"] not in ((_COMP_NONE, _COMP_RLE, _COMP_ZIPS, _COMP_ZIP, _COMP_PXR24) if as_blocks else (_COMP_NONE, _COMP_ZIPS, _COMP_ZIP)):
             raise ExrNotStreamable("%s: compression %s" % (what, {_COMP_RLE: "RLE", _COMP_PIZ: "PIZ", _COMP_PXR24: "PXR24"}[lay["comp"]]))
-        if attrs[b"dataWindow"][1] != attrs[b"displayWindow"][1]:
+        if not as_blocks and attrs[b"dataWindow"][1] != attrs[b"displayWindow"][1]:
             raise ExrNotStreamable("%s: the dataWindow is not the displayWindow" % what)
+        if as_blocks and window is not None and attrs[b"dataWindow"][1] != window:
+            raise ExrNotStreamable("%s: parts of different data windows" % what)
+        window = attrs[b"dataWindow"][1]
         if W is not None and (lay["W"], lay["H"]) != (W, H):
             raise ValueError("%s: parts of different sizes" % what)
         W, H = lay["W"], lay["H"]
@@ -1118,18 +1149,32 @@ def exr_aov_layout(path_or_bytes, names: dict | None = None) -> ExrAovLayout:
                 seen[full] = pt
             chans.append((pt, pl, comp))
         parts.append((lay["comp"], chans))
-        n = lay["chunks"]
+        n = lay["level0_chunks"]  # (level 0 comes first in a mip-mapped part's table; a scanline part has nothing else)
         offs = np.frombuffer(u8, "<u8", n, table_pos).astype(np.int64)
-        table_pos += 8 * n
-        hdr = 12 if multipart else 8
+        table_pos += 8 * lay["chunks"]
+        hdr = (4 if multipart else 0) + (20 if tiled else 8)
         if n and (offs.min() < 0 or offs.max() + hdr > u8.size):
             raise ValueError("%s: a chunk offset outside the file" % what)
         words = u8[offs[:, None] + np.arange(hdr)[None, :]].copy().view("<i4").reshape(n, hdr // 4)
         if multipart and np.any(words[:, 0] != k):
             raise ValueError("%s: a chunk of part %d carries another part number" % (what, k))
-        rec = np.zeros(n, EXR_CHUNK_DTYPE)
-        rec["part"], rec["y"], rec["offset"], rec["packed_bytes"] = k, words[:, -2] - lay["y0"], offs + hdr, words[:, -1].astype(np.int64)
-        rec["rows"] = np.minimum(lay["per_block"], H - rec["y"])
+        if not as_blocks:
+            rec = np.zeros(n, EXR_CHUNK_DTYPE)
+            rec["part"], rec["y"], rec["offset"], rec["packed_bytes"] = k, words[:, -2] - lay["y0"], offs + hdr, words[:, -1].astype(np.int64)
+            rec["rows"] = np.minimum(lay["per_block"], H - rec["y"])
+            tables.append(rec)
+            continue
+        rec = np.zeros(n, EXR_BLOCK_DTYPE)
+        rec["part"], rec["offset"], rec["packed_bytes"] = k, offs + hdr, words[:, -1].astype(np.int64)
+        if tiled:
+            tx, ty, lx, ly = (words[:, -5 + j] for j in range(4))
+            if np.any(lx != 0) or np.any(ly != 0) or np.any(tx < 0) or np.any(tx >= lay["ntx"]) or np.any(ty < 0) or np.any(ty >= lay["nty"]):
+                raise ValueError("%s: an unexpected tile among the first %d of part %d (level 0 comes first)" % (what, n, k))
+            rec["x"], rec["y"] = tx * lay["tw"], ty * lay["th"]
+            rec["cols"], rec["rows"] = np.minimum(lay["tw"], W - rec["x"]), np.minimum(lay["th"], H - rec["y"])
+        else:
+            rec["y"] = words[:, -2] - lay["y0"]  # relative to the data window, like a tile's coordinates
+            rec["cols"], rec["rows"] = W, np.minimum(lay["per_block"], H - rec["y"])
         tables.append(rec)
     planes = {}
     for pi, key in enumerate(AOV_LAYOUT):
@@ -1140,4 +1185,6 @@ def exr_aov_layout(path_or_bytes, names: dict | None = None) -> ExrAovLayout:
         if missing and not (key in ("diffuse", "direct") and missing == [layout[key][3]]):
             raise KeyError("%s: channel(s) %s of AOV %r missing" % (what, missing, key))
         planes[key] = (len(have), "half" if all(pt == _PT_HALF for pt in have) else "float")
-    return ExrAovLayout(W, H, int(u8.size), parts, np.concatenate(tables), planes)
+    table = np.concatenate(tables)
+    return ExrAovLayout(W, H, int(u8.size), parts, None if as_blocks else table, planes, table if as_blocks else None)
+

@@ -18,6 +18,12 @@ compression (ZIPS, ZIP) —
 
 measured the same way, per compression, with A2 in the same rounds; the result is merged into --out under "exr".
 
+--forms tiled_zip,pxr24,rle (with --modes E0,E1): the file forms of rfx.h "EXR blocks" — the same typed frame as ZIP tiles of 64 x 64, as PXR24
+scanline chunks (depth and velocity, the FLOAT planes, keep 24 bits in that file; E0 and E1 read the same file) and as RLE scanline chunks — where
+E1 is readinto + imageio.exr_aov_layout(forms="blocks") + stage_exr_blocks; "zip" is measured in the same run through the same call, so that every
+new figure has E1's ZIP figure beside it.  The result is merged into --out under "exr_blocks".  The RLE file is written by a vectorised coder
+of this tool (imageio's is a byte loop), and its E0 — imageio's byte loop again — is timed over --e0-frames frames only.
+
     python tools/import_rate.py [--modes P0,A0,A1,A2 | E0,E1] [--out profiles/import/rates.json] [--seconds 1.0]
     rocprofv3 --kernel-trace --stats -d DIR -- python tools/import_rate.py --kernel-only      (the pack kernel's own time: a run of its own)
     rocprofv3 --kernel-trace --stats -d DIR -- python tools/import_rate.py --kernel-only --modes E1      (... and the K9 kernels')
@@ -44,6 +50,41 @@ W, H = 3840, 2160
 MODES = ("P0", "A0", "A1", "A2")
 EXR_MODES = ("E0", "E1")
 EXR_COMPRESSIONS = ("zips", "zip")
+# --forms: name -> (compression, tiles); the two above are the forms rfx_stage_exr_aov takes, the others go through rfx_stage_exr_blocks
+EXR_FORMS = {"zips": ("zips", None), "zip": ("zip", None), "tiled_zip": ("zip", (64, 64)), "pxr24": ("pxr24", None), "rle": ("rle", None)}
+BLOCK_FORMS = ("tiled_zip", "pxr24", "rle")
+
+
+def rle_compress_fast(buf: bytes) -> bytes:
+    """imageio._rle_compress's code (runs of 3 .. 128, literals up to 127) with the run search in numpy: a valid stream of the same format, not
+    necessarily the same bytes"""
+    a = np.frombuffer(buf, np.uint8)
+    n = a.size
+    if n == 0:
+        return b""
+    starts = np.flatnonzero(np.concatenate(([True], a[1:] != a[:-1])))
+    lens = np.diff(np.concatenate((starts, [n])))
+    out, lit0 = bytearray(), 0  # lit0: where the pending literal stretch starts
+
+    def flush(end):
+        nonlocal lit0
+        while lit0 < end:
+            m = min(127, end - lit0)
+            out.append(256 - m)
+            out.extend(buf[lit0:lit0 + m])
+            lit0 += m
+    for s0, ln in zip(starts[lens >= 3].tolist(), lens[lens >= 3].tolist()):
+        flush(s0)
+        v = buf[s0]
+        while ln >= 3:
+            m = min(128, ln)
+            out.append(m - 1)
+            out.append(v)
+            ln -= m
+            s0 += m
+        lit0 = s0  # (a rest of one or two bytes joins the next literal)
+    flush(n)
+    return bytes(out)
 BYTES_PER_PIXEL = dict(P0=52, A0=96, A1=76, A2=44)
 HALF = ("diffuse", "normal", "roughness", "metalness", "emissive", "direct")
 AOV = ("diffuse", "normal", "roughness", "metalness", "emissive", "velocity")
@@ -75,13 +116,14 @@ def render(seed, index, workers=16):
 
 
 class Run:
-    def __init__(self, seed, modes=MODES, exr_dir=None, files_only=False):
+    def __init__(self, seed, modes=MODES, exr_dir=None, files_only=False, forms=EXR_COMPRESSIONS):
         self.ctx = ctx = Context(W, H)  # raises without a device
         self.scene = types.SimpleNamespace(frame=None)
         self.frames = {m: [] for m in MODES}
         exr = [m for m in modes if m in EXR_MODES]
         self.exr_bytes = {}
-        files = {(i, comp): os.path.join(exr_dir, "frame%d_%s.exr" % (i, comp)) for i in range(2) for comp in EXR_COMPRESSIONS} if exr else {}
+        self.forms = forms
+        files = {(i, comp): os.path.join(exr_dir, "frame%d_%s.exr" % (i, comp)) for i in range(2) for comp in forms} if exr else {}
         if files_only:  # a kernel trace of E1 over files an earlier run left in --exr-dir: nothing is rendered, nothing is drawn
             for (i, comp), path in sorted(files.items()):
                 self.exr_bytes.setdefault(comp, []).append(os.path.getsize(path))
@@ -106,10 +148,16 @@ class Run:
             self.frames["A0"].append(ns(False, wide["depth"], wide["direct"], gbuffer=None, velocity=None, aov={k: wide[k] for k in AOV}))
             self.frames["A1"].append(ns("resident", pin(wide["depth"]), pin(wide["direct"]), gbuffer=None, velocity=None, aov={k: pin(wide[k]) for k in AOV}))
             self.frames["A2"].append(ns("resident", pin(typed["depth"]), pin(typed["direct"]), gbuffer=None, velocity=None, aov={k: pin(typed[k]) for k in AOV}))
-            for comp in EXR_COMPRESSIONS if exr else ():  # the typed frame as a file: one part per plane, halves where A2 sends halves
+            for comp in forms if exr else ():  # the typed frame as a file: one part per plane, halves where A2 sends halves
                 path = files[(i, comp)]
                 parts = {k: {cn.split(".")[1]: (typed[k][..., j] if typed[k].ndim == 3 else typed[k]) for j, cn in enumerate(imageio.AOV_LAYOUT[k])} for k in imageio.AOV_LAYOUT}
-                imageio.write_exr_multipart(path, parts, comp, half=set(HALF))
+                slow = imageio._rle_compress
+                if comp == "rle":
+                    imageio._rle_compress = rle_compress_fast
+                try:
+                    imageio.write_exr_multipart(path, parts, EXR_FORMS[comp][0], half=set(HALF), tiles=EXR_FORMS[comp][1])
+                finally:
+                    imageio._rle_compress = slow
                 self.exr_bytes.setdefault(comp, []).append(os.path.getsize(path))
                 for m in EXR_MODES:
                     self.frames.setdefault(m + ":" + comp, []).append(ns("resident", None, None, gbuffer=None, velocity=None, aov=None, path=path, exr=m))
@@ -138,7 +186,10 @@ class Run:
             buf, size = self.file_buffers[k & 1], os.path.getsize(f.path)
             with open(f.path, "rb", buffering=0) as fh:
                 assert fh.readinto(memoryview(buf)[:size]) == size
-            ctx.stage_exr_aov(buf, imageio.exr_aov_layout(buf[:size]))
+            if self.forms == EXR_COMPRESSIONS:
+                ctx.stage_exr_aov(buf, imageio.exr_aov_layout(buf[:size]))
+            else:
+                ctx.stage_exr_blocks(buf, imageio.exr_aov_layout(buf[:size], forms="blocks"))
         else:
             ctx.stage_frame(f)
 
@@ -179,12 +230,14 @@ def main():
     ap.add_argument("--kernel-only", action="store_true", help="only stage and flip AOV frames (under rocprofv3 --kernel-trace --stats)")
     ap.add_argument("--modes", default=",".join(MODES), help="P0,A0,A1,A2 (the default) or E0,E1 (the EXR file modes, measured beside A2)")
     ap.add_argument("--exr-dir", default=None, help="where the E modes write their files (default: a temporary directory)")
+    ap.add_argument("--forms", default=None, help="with --modes E0,E1: tiled_zip,pxr24,rle (any of them) — the EXR blocks forms, measured beside E1's zip")
+    ap.add_argument("--e0-frames", type=int, default=2, help="--forms rle: the frames of one E0 loop (the host's RLE decode is a byte loop)")
     a = ap.parse_args()
     global W, H
     W, H = (int(v) for v in a.size.split("x"))
     modes = tuple(a.modes.split(","))
     if any(m in EXR_MODES for m in modes):
-        return main_exr(a, modes)
+        return main_exr_blocks(a, modes) if a.forms else main_exr(a, modes)
     run = Run(a.seed)
     if a.kernel_only:
         run.kernel_only()
@@ -260,6 +313,55 @@ def main_exr(a, modes):
         f.write("\n")
     if not ok:
         sys.exit("import_rate: the device decode is not faster than the host decode in every round")
+
+
+def main_exr_blocks(a, modes):
+    """E0 / E1 per --forms form, E1 of the ZIP scanline file beside them (all through stage_exr_blocks); merged into --out under "exr_blocks" """
+    assert set(modes) <= set(EXR_MODES)
+    forms = tuple(a.forms.split(","))
+    assert forms and set(forms) <= set(BLOCK_FORMS), "--forms: any of " + ",".join(BLOCK_FORMS)
+    tmp = None if a.exr_dir else tempfile.TemporaryDirectory()
+    run = Run(a.seed, modes, a.exr_dir or tmp.name, forms=("zip",) + forms)
+    out = dict(width=W, height=H, seed=a.seed, seconds=a.seconds, tiles=list(EXR_FORMS["tiled_zip"][1]), forms={})
+    for form in ("zip",) + forms:
+        names = [m + ":" + form for m in modes if not (form == "zip" and m == "E0")]
+        n = {}
+        for mode in names:
+            if mode == "E0:rle":
+                n[mode] = a.e0_frames
+                continue
+            run.loop(mode, 2)
+            per = run.loop(mode, 2) / 2
+            n[mode] = max(2 if per > 0.25 else 20, int(math.ceil(a.seconds / per)))
+        size = run.exr_bytes[form][0]
+        data = open(run.frames["E1:" + form][0].path, "rb").read()
+        lay = imageio.exr_aov_layout(data, forms="blocks")
+        row0 = dict(file_bytes=run.exr_bytes[form], file_bytes_per_pixel=round(size / (W * H), 3), blocks=len(lay.blocks),
+                    raw_blocks=int((lay.blocks["packed_bytes"] == block_raw_sizes(lay)).sum()), staged_bytes=run.ctx.exr_blocks_stage_bytes(data, lay), frames=n, rounds=[])
+        for r in range(1 if form == "rle" else 3):
+            row = {mode.split(":")[0]: round(run.loop(mode, n[mode]) / n[mode] * 1e3, 4) for mode in names}
+            if "E0" in row and "E1" in row:
+                row["E0_over_E1"] = round(row["E0"] / row["E1"], 2)
+            row0["rounds"].append(row)
+            print(form, json.dumps(row), flush=True)
+        assert run.ctx.exr_aov_status()[0] == 0
+        out["forms"][form] = row0
+    zip_e1 = min(r["E1"] for r in out["forms"]["zip"]["rounds"])
+    for form in forms:
+        out["forms"][form]["E1_over_E1_zip"] = round(min(r["E1"] for r in out["forms"][form]["rounds"]) / zip_e1, 4)
+    run.ctx.close()
+    result = json.load(open(a.out)) if os.path.exists(a.out) else {}
+    result["exr_blocks"] = out
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+
+
+def block_raw_sizes(lay):
+    texel = np.array([sum(2 if pt == 1 else 4 for pt, _, _ in chans) for _, chans in lay.parts])
+    b = lay.blocks
+    return b["rows"].astype(np.int64) * b["cols"] * texel[b["part"]]
 
 
 def run_file(run, comp):
