@@ -654,6 +654,21 @@ typedef struct rfx_exr_block_frame { const void *data; unsigned long long bytes;
 size_t rfx_exr_blocks_stage_bytes(const rfx_ctx *, const rfx_exr_block_frame *, int row0, int rows);
 int    rfx_stage_exr_blocks(rfx_ctx *, const rfx_exr_block_frame *, int row0, int rows);
 
+/* ---- EXR blocks with PIZ (additive to ABI 21: a host checks for the symbol): rfx_stage_exr_blocks for a file whose parts may also be PIZ-compressed
+ * (4: the OpenEXR library's default).  The descriptor, the rules, the band arithmetic, the back pressure, the staging ownership and the results are
+ * rfx_stage_exr_blocks', word for word, and both run one plan and the same kernels; the one difference: a part's compression may also be 4, in any
+ * mix with the other five.  rfx_stage_exr_blocks and rfx_stage_exr_aov keep refusing it (RFX_EINVAL): a host opts in by calling these.
+ * A PIZ BLOCK.  OpenEXR's scanline block of a PIZ part holds min(32, the rows left) rows, and a tile is a block, as now: there is still no row rule,
+ * the library does not know which it is.  THE LIMIT: the wavelet of a block is decoded in cells of 64 x 64 words, each through all its levels on its
+ * own, which holds while the largest power of two <= min(cols, rows) is at most 64: a block of a PIZ part whose cols AND rows are both 128 or more
+ * is refused (RFX_EINVAL).  Scanline blocks of any width and tiles of up to 127 texels on their shorter side are taken.  The packed size equal to the raw size is the raw block, as for every compression.
+ * THE DEVICE AREA grows by K9_PIZ_TABLE_BYTES (csrc/k9_piz.h: 257 KiB — the reverse lookup table, the sorted symbols) per PIZ block of the band that
+ * is not stored raw (csrc/rfx_launch.h rfx_exr_piz_tables_for), under the growth rule of the staging areas.
+ * STATUS.  rfx_exr_aov_status reports a bad PIZ block with csrc/k9_piz.h's K9_E_PIZ_* (15 .. 23); its rectangle reads as not covered. */
+enum { RFX_EXR_PIZ = 4 };
+size_t rfx_exr_blocks_piz_stage_bytes(const rfx_ctx *, const rfx_exr_block_frame *, int row0, int rows);
+int    rfx_stage_exr_blocks_piz(rfx_ctx *, const rfx_exr_block_frame *, int row0, int rows);
+
 /* ---- row-tiled runs: the exchanges, one process per GPU, RCCL over xGMI.  RCCL is bound at run time (a
  * single-GPU host needs none; a process that already maps an RCCL — e.g. torch's — shares it).
  * Tiles: rank r of n owns rfx_split_rows(height, n, r) — boundaries on even rows, the last tile takes the remainder.  The exchanges run on a second stream of the context: each call orders itself AFTER all draws

@@ -17,6 +17,11 @@
 //                  scanlines run top-down), halves widened where the plane is F32.  A PXR24 stream instead: one segmented scan per (row, channel)
 //                  of the k-byte differences (k9_pxr24.h), the segments dealt to the block's four waves, 64 samples per step with a carry,
 //                  written straight into the planes.
+//   k9_piz_huf     one wave per PIZ chunk (launched when the band has one; every other chunk returns at once, as PIZ chunks do from k9_inflate): the
+//                  reverse lookup table from the bitmap, the canonical Huffman tables and the decode of k9_piz.h on the same wave-wide input IO:
+//                  the chunk's words, channel-planar, into its scratch slot.
+//   k9_piz_planes  eight workgroups per PIZ chunk: the 2-D wavelet in cells of 64 x 64 words in LDS, the lookup, and k9_exr_planes' scatter — PIZ has
+//                  no predictor and no byte split, so k9_exr_planes returns at once for a PIZ chunk that decoded.
 //   k9_exr_finish  the rectangle of a chunk that did not decode: depth 1 (not covered), everything else 0 (written by k9_exr_planes); the status words.
 // All integer work: nothing here depends on contraction.
 #include "rfx_device.h"
@@ -28,6 +33,7 @@
 #include "k9_inflate.h"
 #include "k9_rle.h"
 #include "k9_pxr24.h"
+#include "k9_piz.h"
 
 namespace {
 
@@ -115,13 +121,47 @@ struct K9WaveIO {
 
 RFX_DEV bool k9_raw_form(const K9Chunk &ck, const K9Part &pt) { return pt.compression == RFX_EXR_NONE || ck.packed == ck.raw; }
 RFX_DEV bool k9_rle_form(const K9Chunk &ck, const K9Part &pt) { return pt.compression == RFX_EXR_RLE && ck.packed != ck.raw; }
+RFX_DEV bool k9_piz_form(const K9Chunk &ck, const K9Part &pt) { return pt.compression == RFX_EXR_PIZ && ck.packed != ck.raw; }
+
+// k9_piz.h's IO on the wave: the tables in LDS, the sorted symbols in the block's table scratch; the words leave in groups of 64 — lane l holds
+// the word of position (pstart & ~63) + l until its group is full or a run follows —, a run is stored by all lanes.
+struct K9PizWaveIO : K9WaveIO {
+    K9PizHuf *h;
+    unsigned short *symbols, *out16;
+    unsigned int pend;
+    size_t pstart;  // out16[0, pstart) is stored; the words of [pstart, n) wait in `pend`, all in one group of 64
+    RFX_DEV bool leader() const { return lane == 0; }
+    RFX_DEV unsigned int bcast(unsigned int v) { return (unsigned int)__shfl((int)v, 0); }
+    RFX_DEV K9PizHuf &huf() { return *h; }
+    RFX_DEV void fast_fill(unsigned int lo, unsigned int n, unsigned int e) {
+        for (unsigned int k = (unsigned int)lane; k < n; k += 64u) h->fast[lo + k] = e;
+    }
+    RFX_DEV void sym_put(unsigned int i, unsigned int v) {
+        if (lane == 0) symbols[i] = (unsigned short)v;
+    }
+    RFX_DEV unsigned int sym(unsigned int i) const { return symbols[i]; }
+    RFX_DEV void flush(size_t n) {
+        const size_t pos = (pstart & ~(size_t)63) + (size_t)lane;
+        if (pos >= pstart && pos < n) out16[pos] = (unsigned short)pend;
+        pstart = n;
+    }
+    RFX_DEV void put16(size_t n, unsigned int v) {
+        if (lane == (int)(n & 63)) pend = v;
+        if ((n & 63) == 63) flush(n + 1);
+    }
+    RFX_DEV void fill16(size_t n, unsigned int v, unsigned int len) {
+        flush(n);
+        for (unsigned int k = (unsigned int)lane; k < len; k += 64u) out16[n + k] = (unsigned short)v;
+        pstart = n + len;
+    }
+};
 
 __global__ __launch_bounds__(64) void k9_inflate(K9Args A) {
     __shared__ K9Tables tables;
     __shared__ unsigned int red[128];
     const K9Chunk ck = A.chunks[blockIdx.x];
     const K9Part pt = A.parts[ck.part];
-    if (k9_rle_form(ck, pt)) return;  // k9_rle's
+    if (k9_rle_form(ck, pt) || k9_piz_form(ck, pt)) return;  // k9_rle's, k9_piz_huf's
     const int lane = (int)threadIdx.x;
     const unsigned char *in = A.packed + ck.src;
     unsigned char *out = A.scratch + ck.dst;
@@ -150,13 +190,94 @@ __global__ __launch_bounds__(64) void k9_rle(K9Args A) {
     if (threadIdx.x == 0) A.err[blockIdx.x] = code;
 }
 
-constexpr int K9_PLANES_BLOCK = 256, K9_SCAN_BYTES = 16;
 // frame row fy of `plane`: the segment that stages it, or -1
 RFX_DEV int k9_segment(const K9Args &A, int plane, int fy) {
     for (int s = 0; s < A.nseg; s++)
         if (fy >= A.seg_row0[s] && fy < A.seg_row0[s] + A.seg_rows[s] && A.seg_plane[s][plane]) return s;
     return -1;
 }
+
+// One wave per PIZ block: the reverse lookup table from the bitmap (a lane counts the bits of its 1024 values, the counts before it are where it
+// writes), then k9_piz.h's Huffman decode: the block's words, channel-planar, into its scratch slot.  17 824 bytes of LDS per wave: 9 waves per CU.
+__global__ __launch_bounds__(64) void k9_piz_huf(K9Args A) {
+    __shared__ K9PizHuf huf;
+    __shared__ unsigned int bits[64];
+    const K9Chunk ck = A.chunks[blockIdx.x];
+    const K9Part pt = A.parts[ck.part];
+    if (!k9_piz_form(ck, pt)) return;
+    const int lane = (int)threadIdx.x;
+    unsigned char *tab = A.piz_tables + (size_t)ck.piz * K9_PIZ_TABLE_BYTES;
+    K9PizWaveIO io;
+    io.in = A.packed + ck.src; io.in_len = ck.packed; io.nwords = ((size_t)ck.packed + 3) / 4; io.out = A.scratch + ck.dst; io.t = nullptr; io.red = nullptr;
+    io.lane = lane; io.win_base = ~(size_t)0; io.win = 0u; io.synced = 0;
+    io.h = &huf; io.symbols = (unsigned short *)(tab + K9_PIZ_REV_BYTES); io.out16 = (unsigned short *)io.out; io.pend = 0u; io.pstart = 0;
+    K9PizHead hd;
+    int code = k9_piz_head(io, (size_t)ck.packed, &hd);
+    if (!code) {
+        const unsigned char *bm = io.in + 4;  // (k9_piz_head: bytes [4, 4 + bm_max - bm_min] lie inside the block)
+        bits[lane] = k9_piz_rev_count(bm, hd.bm_min, hd.bm_max, lane);
+        K9_WAVE_FENCE();
+        unsigned int base = 0u, total = 0u;
+        for (int l = 0; l < 64; l++) {
+            if (l < lane) base += bits[l];
+            total += bits[l];
+        }
+        k9_piz_rev_write(bm, hd.bm_min, hd.bm_max, lane, base, total, (unsigned short *)tab);
+        if (lane == 0) *(int *)(tab + K9_PIZ_REV_BYTES + K9_PIZ_SYM_BYTES) = (int)total - 1;  // mx
+        code = k9_piz_huf_decode(io, hd.huf_at, hd.huf_len, (size_t)ck.raw / 2);
+    }
+    if (lane == 0) A.err[blockIdx.x] = code;
+}
+
+// The parallel part of a PIZ block: one workgroup per (channel, cell) in turn — K9_PIZ_SLICES workgroups share a block's cells —: the cell of each of
+// the channel's word planes (HALF: one; FLOAT: two, interleaved in x, the low word first) into LDS, the wavelet levels from the coarsest to the
+// finest (k9_piz.h k9_piz_cell_level, one thread per square), the reverse lookup, and the samples to the staging planes as k9_exr_planes scatters.
+constexpr int K9_PIZ_SLICES = 8, K9_PIZ_BLOCK = 256;
+static_assert(K9_PIZ_CELL == RFX_EXR_PIZ_CELL, "the plan's cell is the kernel's");
+__global__ __launch_bounds__(K9_PIZ_BLOCK) void k9_piz_planes(K9Args A) {
+    __shared__ unsigned short cell[2][K9_PIZ_CELL * K9_PIZ_CELL];
+    const K9Chunk ck = A.chunks[blockIdx.x];
+    const K9Part pt = A.parts[ck.part];
+    if (!k9_piz_form(ck, pt) || A.err[blockIdx.x]) return;  // (a bad block: k9_exr_planes writes its zeros)
+    const int tid = (int)threadIdx.x;
+    const unsigned short *words = (const unsigned short *)(A.scratch + ck.dst);
+    const unsigned char *tab = A.piz_tables + (size_t)ck.piz * K9_PIZ_TABLE_BYTES;
+    const unsigned short *rev = (const unsigned short *)tab;
+    const bool w14 = *(const int *)(tab + K9_PIZ_REV_BYTES + K9_PIZ_SYM_BYTES) < (1 << 14);
+    const int cols = ck.cols, rows = ck.rows, cx = (cols + K9_PIZ_CELL - 1) / K9_PIZ_CELL, cy = (rows + K9_PIZ_CELL - 1) / K9_PIZ_CELL;
+    const int top = k9_piz_top_level(cols, rows), items = pt.nchan * cx * cy;
+    for (int it = (int)blockIdx.y; it < items; it += (int)gridDim.y) {  // (every condition on the way to a barrier is uniform over the workgroup)
+        const int c = it / (cx * cy), rem = it - c * cx * cy, y0 = (rem / cx) * K9_PIZ_CELL, x0 = (rem % cx) * K9_PIZ_CELL;
+        const K9Chan ch = A.chans[pt.chan0 + c];
+        if (ch.plane < 0) continue;
+        const int size = ch.half ? 1 : 2;
+        const int w = cols - x0 < K9_PIZ_CELL ? cols - x0 : K9_PIZ_CELL, h = rows - y0 < K9_PIZ_CELL ? rows - y0 : K9_PIZ_CELL;
+        const unsigned short *plane = words + (size_t)rows * (size_t)cols * (ch.off / 2u);  // (channel-planar: ch.off / 2 words per texel before it)
+        __syncthreads();  // the cell of the previous turn has been read
+        for (int i = tid; i < h * w * size; i += K9_PIZ_BLOCK) {
+            const int ly = i / (w * size), k = i - ly * (w * size);
+            cell[k % size][ly * K9_PIZ_CELL + k / size] = plane[(size_t)(y0 + ly) * (size_t)(cols * size) + (size_t)(x0 * size + k)];
+        }
+        __syncthreads();
+        for (int p = top; p >= 1; p >>= 1) {
+            for (int j = 0; j < size; j++) k9_piz_cell_level(cell[j], x0, y0, cols, rows, p, w14, tid, K9_PIZ_BLOCK);
+            __syncthreads();
+        }
+        for (int i = tid; i < h * w; i += K9_PIZ_BLOCK) {
+            const int ly = i / w, lx = i - ly * w;
+            const int fy = A.H - 1 - (ck.y + y0 + ly);
+            const int s = k9_segment(A, ch.plane, fy);
+            if (s < 0) continue;
+            unsigned int bits = rev[cell[0][ly * K9_PIZ_CELL + lx]];
+            if (size == 2) bits |= (unsigned int)rev[cell[1][ly * K9_PIZ_CELL + lx]] << 16;
+            const size_t dst = ((size_t)(fy - A.seg_row0[s]) * A.W + (size_t)(ck.x + x0 + lx)) * A.plane_ch[ch.plane] + ch.comp;
+            if (A.plane_half[ch.plane]) ((unsigned short *)A.seg_plane[s][ch.plane])[dst] = (unsigned short)bits;
+            else ((float *)A.seg_plane[s][ch.plane])[dst] = ch.half ? rfx_h2f((unsigned short)bits) : __uint_as_float(bits);
+        }
+    }
+}
+
+constexpr int K9_PLANES_BLOCK = 256, K9_SCAN_BYTES = 16;
 __global__ __launch_bounds__(K9_PLANES_BLOCK) void k9_exr_planes(K9Args A) {
     __shared__ unsigned int scan[K9_PLANES_BLOCK];
     const K9Chunk ck = A.chunks[blockIdx.x];
@@ -165,6 +286,7 @@ __global__ __launch_bounds__(K9_PLANES_BLOCK) void k9_exr_planes(K9Args A) {
     const int tid = (int)threadIdx.x;
     const int err = A.err[blockIdx.x];
     const bool raw_form = k9_raw_form(ck, pt);
+    if (k9_piz_form(ck, pt) && !err) return;  // k9_piz_planes' (PIZ has no predictor and no byte split; a bad block's zeros are written below)
     const unsigned int n = ck.raw;
     const unsigned int cols = (unsigned int)ck.cols;
     if (pt.compression == RFX_EXR_PXR24 && !raw_form && !err) {
@@ -280,6 +402,11 @@ hipError_t rfx_launch_k9(const K9Args &A, hipStream_t stream) {
     if (A.nchunks <= 0 || !A.chunks || !A.parts || !A.chans || !A.packed || !A.scratch || !A.err || !A.status) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k9_inflate, dim3(A.nchunks), dim3(64), 0, stream, A);
     if (A.rle_chunks > 0) hipLaunchKernelGGL(k9_rle, dim3(A.nchunks), dim3(64), 0, stream, A);  // (a frame without an RLE stream: nothing to do)
+    if (A.piz_chunks > 0) {
+        if (!A.piz_tables) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k9_piz_huf, dim3(A.nchunks), dim3(64), 0, stream, A);
+        hipLaunchKernelGGL(k9_piz_planes, dim3(A.nchunks, K9_PIZ_SLICES), dim3(K9_PIZ_BLOCK), 0, stream, A);
+    }
     hipLaunchKernelGGL(k9_exr_planes, dim3(A.nchunks), dim3(K9_PLANES_BLOCK), 0, stream, A);
     hipLaunchKernelGGL(k9_exr_finish, dim3(A.nchunks), dim3(256), 0, stream, A);
     return hipGetLastError();

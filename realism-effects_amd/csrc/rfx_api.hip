@@ -427,7 +427,7 @@ struct ExrPlan {
     std::vector<K9Chunk> chunks;  // the ones the band needs, in the descriptor's order
     std::vector<unsigned long long> file_offset;  // of each of them
     unsigned long long copy_bytes = 0, packed_bytes = 0, scratch_bytes = 0;  // host -> device; the two device areas (256-byte-aligned pieces)
-    int rle_chunks = 0;
+    int rle_chunks = 0, piz_chunks = 0;
 };
 static unsigned long long align256(unsigned long long n) { return (n + 255ull) & ~255ull; }
 
@@ -522,8 +522,9 @@ static const char *exr_cover_part(const ExrSpan *first, const ExrSpan *last, int
 
 // The blocks: geometry, sizes, the band's blocks and their coverage.  A pure function of the descriptor and the context's geometry, after
 // exr_parts_plan.  0, or the RFX_EINVAL case in words.
+// accept_piz: a PIZ part's blocks are taken (its geometry rules: include/rfx.h "EXR blocks with PIZ"); the parts' plan has refused one otherwise.
 static const char *exr_blocks_plan(const rfx_ctx *c, unsigned long long file_bytes, const rfx_exr_block *block, int nblocks, int row0, int rows, const char *overlap,
-                                   const char *hole, ExrPlan *p) {
+                                   const char *hole, ExrPlan *p, bool accept_piz = false) {
     const int W = c->W, H = c->H, nparts = (int)p->parts.size();
     const int y_lo = H - row0 - rows, y_hi = H - row0;  // the band's scanlines, top first
     std::vector<ExrSpan> spans;
@@ -536,10 +537,17 @@ static const char *exr_blocks_plan(const rfx_ctx *c, unsigned long long file_byt
         if (raw >= (1ull << 30)) return "a block of 2^30 raw bytes or more";
         if (q.packed_bytes == 0 || q.packed_bytes >= (1ull << 30) || (part.compression == RFX_EXR_NONE && q.packed_bytes != raw)) return "a block's packed size does not fit its texels";
         if (q.offset > file_bytes || q.packed_bytes > file_bytes - q.offset) return "a block lies outside the file bytes";
+        int piz = 0;
+        if (part.compression == RFX_EXR_PIZ) {
+            if (!accept_piz) return "a PIZ part";
+            if (q.cols >= 2 * RFX_EXR_PIZ_CELL && q.rows >= 2 * RFX_EXR_PIZ_CELL) return "a PIZ block of 128 x 128 texels or more";
+            piz = q.packed_bytes != raw;
+        }
         if (!p->mapped[q.part] || q.y >= y_hi || q.y + q.rows <= y_lo) continue;
         const unsigned long long expect = part.compression == RFX_EXR_PXR24 && q.packed_bytes != raw ? texels * part.pxr_bytes : raw;
         if (part.compression == RFX_EXR_RLE && q.packed_bytes != raw) p->rle_chunks++;
-        p->chunks.push_back({p->packed_bytes, p->scratch_bytes, (unsigned int)q.packed_bytes, (unsigned int)raw, (unsigned int)expect, q.part, q.x, q.y, q.cols, q.rows, k, 0});
+        p->chunks.push_back({p->packed_bytes, p->scratch_bytes, (unsigned int)q.packed_bytes, (unsigned int)raw, (unsigned int)expect, q.part, q.x, q.y, q.cols, q.rows, k, piz ? p->piz_chunks : 0});
+        p->piz_chunks += piz;
         p->file_offset.push_back(q.offset);
         p->copy_bytes += q.packed_bytes;
         p->packed_bytes += align256(q.packed_bytes);
@@ -584,13 +592,16 @@ static const char *exr_plan(const rfx_ctx *c, const rfx_exr_frame *f, int row0, 
                            "a scanline of the band has no chunk in a part that feeds a plane", p);
 }
 
-static const char *exr_block_frame_plan(const rfx_ctx *c, const rfx_exr_block_frame *f, int row0, int rows, ExrPlan *p) {
+static const char *exr_block_frame_plan(const rfx_ctx *c, const rfx_exr_block_frame *f, int row0, int rows, ExrPlan *p, bool accept_piz = false) {
     if (!f->data || !f->bytes || f->parts <= 0 || f->blocks <= 0 || !f->part || !f->block) return "an empty descriptor";
     if (f->blocks >= (1 << 23) || f->parts > 4096) return "more than 2^23 blocks or 4096 parts";
     const unsigned int five = 1u << RFX_EXR_NONE | 1u << RFX_EXR_RLE | 1u << RFX_EXR_ZIPS | 1u << RFX_EXR_ZIP | 1u << RFX_EXR_PXR24;
-    if (const char *bad = exr_parts_plan(c, f->part, f->parts, five, "a part's compression is none of NONE, RLE, ZIPS, ZIP, PXR24", row0, rows, p)) return bad;
+    if (const char *bad = exr_parts_plan(c, f->part, f->parts, accept_piz ? five | 1u << RFX_EXR_PIZ : five,
+                                         accept_piz ? "a part's compression is none of NONE, RLE, ZIPS, ZIP, PIZ, PXR24" : "a part's compression is none of NONE, RLE, ZIPS, ZIP, PXR24",
+                                         row0, rows, p))
+        return bad;
     return exr_blocks_plan(c, f->bytes, f->block, f->blocks, row0, rows, "two blocks of a part hold one texel of the band",
-                           "a texel of the band has no block in a part that feeds a plane", p);
+                           "a texel of the band has no block in a part that feeds a plane", p, accept_piz);
 }
 
 size_t rfx_exr_aov_stage_bytes(const rfx_ctx *c, const rfx_exr_frame *f, int row0, int rows) {
@@ -602,6 +613,12 @@ size_t rfx_exr_aov_stage_bytes(const rfx_ctx *c, const rfx_exr_frame *f, int row
 size_t rfx_exr_blocks_stage_bytes(const rfx_ctx *c, const rfx_exr_block_frame *f, int row0, int rows) {
     ExrPlan p;
     if (!c || !f || exr_block_frame_plan(c, f, row0, rows, &p)) return 0;
+    return (size_t)p.copy_bytes;
+}
+
+size_t rfx_exr_blocks_piz_stage_bytes(const rfx_ctx *c, const rfx_exr_block_frame *f, int row0, int rows) {
+    ExrPlan p;
+    if (!c || !f || exr_block_frame_plan(c, f, row0, rows, &p, true)) return 0;
     return (size_t)p.copy_bytes;
 }
 
@@ -631,11 +648,13 @@ static int stage_exr_plan(rfx_ctx *c, const ExrPlan &p, const void *data, const 
     if ((rc = stage_streams(c))) return rc;
     for (int k = 0; k < 4; k++)
         if (writes[k] && (rc = stage_back(c, c->slots[ids[k]]))) return rc;
-    // the device area: parts | channels | chunks | error words | status | packed bytes | inflate scratch, every piece 256-byte aligned
+    // the device area: parts | channels | chunks | error words | status | packed bytes | inflate scratch | PIZ tables, every piece 256-byte aligned
+    rfx_exr_piz_tables piz;
+    if (!rfx_exr_piz_tables_for(p.piz_chunks, &piz)) return fail_in(c, RFX_EINVAL, fn, "too many PIZ blocks");
     const size_t n = p.chunks.size();
     const size_t parts_b = align256(p.parts.size() * sizeof(K9Part)), chans_b = align256(p.chans.size() * sizeof(K9Chan)), chunks_b = align256(n * sizeof(K9Chunk));
     const size_t tables_b = parts_b + chans_b + chunks_b, err_b = align256(n * sizeof(int)), status_b = 256;
-    const size_t need = tables_b + err_b + status_b + (size_t)p.packed_bytes + (size_t)p.scratch_bytes;
+    const size_t need = tables_b + err_b + status_b + (size_t)p.packed_bytes + (size_t)p.scratch_bytes + (size_t)piz.bytes;
     if ((rc = grow_stage_area(c, &c->aov_stage, &c->aov_stage_cap, (size_t)t.stage_bytes, (std::string(fn) + ": hipMalloc(staging area)").c_str()))) return rc;
     if ((rc = grow_stage_area(c, &c->exr_stage, &c->exr_stage_cap, need, (std::string(fn) + ": hipMalloc(chunk area)").c_str()))) return rc;
     if (!c->ev_exr_status) {
@@ -676,6 +695,7 @@ static int stage_exr_plan(rfx_ctx *c, const ExrPlan &p, const void *data, const 
     A.nchunks = (int)n; A.rle_chunks = p.rle_chunks;
     A.err = (int *)(dev + tables_b); A.status = (int *)(dev + tables_b + err_b);
     A.packed = (const unsigned char *)packed; A.scratch = (unsigned char *)packed + p.packed_bytes;
+    A.piz_chunks = p.piz_chunks; A.piz_tables = p.piz_chunks ? A.scratch + p.scratch_bytes : nullptr;
     A.W = c->W; A.H = c->H;
     A.nseg = t.nseg;
     unsigned int half_mask = 0;
@@ -718,6 +738,14 @@ int rfx_stage_exr_blocks(rfx_ctx *c, const rfx_exr_block_frame *f, int row0, int
     ExrPlan p;
     if (const char *bad = exr_block_frame_plan(c, f, row0, rows, &p)) return fail_in(c, RFX_EINVAL, "rfx_stage_exr_blocks", bad);
     return stage_exr_plan(c, p, f->data, "rfx_stage_exr_blocks");
+}
+
+int rfx_stage_exr_blocks_piz(rfx_ctx *c, const rfx_exr_block_frame *f, int row0, int rows) {
+    if (!c || !f) return RFX_EINVAL;
+    RFX_ENTER(c);
+    ExrPlan p;
+    if (const char *bad = exr_block_frame_plan(c, f, row0, rows, &p, true)) return fail_in(c, RFX_EINVAL, "rfx_stage_exr_blocks_piz", bad);
+    return stage_exr_plan(c, p, f->data, "rfx_stage_exr_blocks_piz");
 }
 
 int rfx_exr_aov_status(rfx_ctx *c, int *bad_chunks, int *first_bad, int *code) {
@@ -1237,6 +1265,7 @@ int rfx_internal_export_plan(int pixels, int format, int channels, struct rfx_ex
 int rfx_internal_aov_plan(int W, int H, int held_row0, int held_rows, const int *type, const int *channels, int row0, int rows, struct rfx_aov_plan *out) {
     return rfx_aov_plan_for(W, H, held_row0, held_rows, type, channels, row0, rows, out) ? RFX_EINVAL : RFX_OK;
 }
+int rfx_internal_exr_piz_tables(int piz_blocks, struct rfx_exr_piz_tables *out) { return out && rfx_exr_piz_tables_for(piz_blocks, out) ? 0 : -1; }
 int rfx_internal_k3_tile(int W, int H, float radius, int inputIsTemporal, int textureCount, struct rfx_k3_tile_plan *out) {
     *out = rfx_k3_tile((float)W, (float)H, radius, inputIsTemporal != 0, textureCount);
     return RFX_OK;

@@ -138,6 +138,7 @@ extern "C" int rfx_internal_scaled_rows(int W, int H, int Hs, int uv_model, int 
 extern "C" int rfx_internal_export_plan(int pixels, int format, int channels, struct rfx_export_plan *out);
 // (held_row0, held_rows: the rows GBUFFER / VELOCITY / DIRECT_LIGHT hold; type, channels: eight entries in rfx_aov_frame's order, channels 0 = not given)
 extern "C" int rfx_internal_aov_plan(int W, int H, int held_row0, int held_rows, const int *type, const int *channels, int row0, int rows, struct rfx_aov_plan *out);
+extern "C" int rfx_internal_exr_piz_tables(int piz_blocks, struct rfx_exr_piz_tables *out);
 extern "C" int rfx_internal_k3_tile(int W, int H, float radius, int inputIsTemporal, int textureCount, struct rfx_k3_tile_plan *out);
 
 extern thread_local std::string g_create_err;

@@ -199,7 +199,9 @@ hipError_t rfx_launch_k8_exr(const K8ExrArgs &, hipStream_t);
 // AOV staging planes k0_aov_pack reads (include/rfx.h "streamed EXR frames", "EXR blocks").  Four launches on `stream`: k9_inflate (one wave per
 // block: zlib stream or raw block -> the block's scratch slot), k9_rle (one wave per block: the RLE parts' blocks), k9_exr_planes (one block of
 // threads per file block: predictor and byte split, or PXR24's differences, undone, the mapped channels scattered, rows flipped), k9_exr_finish
-// (the rectangle of a bad block reads as not covered; the status words).  The tables are device copies of the call's descriptor, built by
+// (the rectangle of a bad block reads as not covered; the status words); with PIZ streams in the band two more in front of the planes: k9_piz_huf
+// (one wave per block: reverse lookup table, Huffman tables and decode, csrc/k9_piz.h) and k9_piz_planes (the wavelet in cells, the lookup, the
+// scatter).  The tables are device copies of the call's descriptor, built by
 // rfx_api.hip's exr_blocks_plan for both entry points.
 struct K9Chunk {
     unsigned long long src, dst;  // 256-byte-aligned offsets of the packed bytes / of the scratch slot (raw bytes, which is the LZ77 window too)
@@ -207,7 +209,7 @@ struct K9Chunk {
     unsigned int expect;          // what the decoder must produce: raw, but for PXR24 3 bytes per FLOAT sample
     int part, x, y, cols, rows;   // the block's top-left texel (EXR scanline 0 = top) and size; a scanline chunk: x = 0, cols = W
     int index;                    // in the descriptor's chunk / block table (what the status reports)
-    int pad;
+    int piz;                      // a PIZ stream: its slot in K9Args.piz_tables
 };
 // plane < 0: dropped; off / pxr_off: bytes per texel of the part's channels before this one, raw and as PXR24 stores them — the channel's samples
 // of a block's row start cols x that many bytes behind the row's start
@@ -219,6 +221,8 @@ struct K9Args {
     const K9Chan *chans;
     int nchunks;
     int rle_chunks;            // how many of them are RLE streams (0: k9_rle is not launched)
+    int piz_chunks;            // ... PIZ streams (0: k9_piz_huf and k9_piz_planes are not launched)
+    unsigned char *piz_tables; // piz_chunks slots of k9_piz.h's K9_PIZ_TABLE_BYTES: reverse lookup table, sorted symbols, mx
     const unsigned char *packed;
     unsigned char *scratch;
     int *err;                  // per chunk: k9_inflate.h's / k9_rle.h's K9_E_* (0: decoded)

@@ -1,7 +1,7 @@
 // rfx_launch.h — what a launch decides on the host before it launches: K1's table layout, a scaled tile's target rows, K3's tile geometry, the
 // "whole frame" test, the step from a run-time option to a template argument, and what is remembered per kernel and device.  Host code
 // (rfx_device.h comes in for UvPlanes and the two vUv expressions the kernels and the row plan share).  The plans are pure functions of their
-// arguments (no HIP call, no context): rfx_api.hip exports them as rfx_internal_k1_table / rfx_internal_k3_tile / rfx_internal_scaled_rows / rfx_internal_export_plan / rfx_internal_aov_plan and
+// arguments (no HIP call, no context): rfx_api.hip exports them as rfx_internal_k1_table / rfx_internal_k3_tile / rfx_internal_scaled_rows / rfx_internal_export_plan / rfx_internal_aov_plan / rfx_internal_exr_piz_tables and
 // the CPU tests call them as built (tests/test_k1_table_layout.py, tests/test_k3_tile_geometry.py, tests/test_resolution_scale_rows_cpu.py).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -202,6 +202,23 @@ inline bool rfx_exr_plan_for(int rows, int W, int channels, rfx_exr_plan *out) {
     t.meta_at = t.planes_at + (((unsigned long long)rows * t.plane_stride + 255ull) & ~255ull);
     t.offsets_at = t.meta_at + (((unsigned long long)rows * 16ull + 255ull) & ~255ull);
     t.device_bytes = t.offsets_at + (unsigned long long)rows * 8ull;
+    *out = t;
+    return true;
+}
+
+// K9's PIZ table scratch (k9_piz.h): one slot per PIZ stream of a call — blocks in flight are the blocks of the call, every one its own wave —, each
+// the reverse lookup table (65536 x 2 bytes), the sorted symbol list (65537 x 2 bytes, rounded up to 256) and the info words (256).  A pure
+// function of its argument, exported as rfx_internal_exr_piz_tables.
+constexpr int RFX_EXR_PIZ_CELL = 64;  // the side of a wavelet cell: a block with both sides >= 2 cells is refused (include/rfx.h)
+struct rfx_exr_piz_tables { unsigned long long rev_bytes, symbol_bytes, info_bytes, slot_bytes, bytes; };
+inline bool rfx_exr_piz_tables_for(int piz_blocks, rfx_exr_piz_tables *out) {
+    if (piz_blocks < 0 || piz_blocks >= (1 << 23)) return false;
+    rfx_exr_piz_tables t;
+    t.rev_bytes = 65536ull * 2ull;
+    t.symbol_bytes = (65537ull * 2ull + 255ull) & ~255ull;
+    t.info_bytes = 256ull;
+    t.slot_bytes = t.rev_bytes + t.symbol_bytes + t.info_bytes;
+    t.bytes = t.slot_bytes * (unsigned long long)piz_blocks;
     *out = t;
     return true;
 }

@@ -148,12 +148,23 @@ class Renderer {
 	}
 	// EXR blocks (rfx.h): the same for tiled parts, RLE and PXR24, a moved data window — `layout` = imageio.exrAovLayout(bytes, names, { forms:
 	// "blocks" }), whose `blocks` are rectangles of the frame (a scanline chunk or a tile each).  exrAovStatus() reports on either call.
+	// A layout with a PIZ part (exrAovLayout(..., { forms: "blocks", piz: true }); rfx.h "EXR blocks with PIZ") goes through rfx_stage_exr_blocks_piz.
+	static _layoutHasPiz(layout) {
+		const w = layout.parts
+		for (let k = 0, at = 1; k < w[0]; k++) {
+			if (w[at] === 4) return true
+			at += 2 + 3 * w[at + 1] // compression, channels, three words per channel
+		}
+		return false
+	}
 	stageExrBlocks(bytes, layout, row0, rows) {
-		addon.stageExrBlocks(this._h, bytes, layout.parts, layout.blocks, row0 === undefined ? 0 : row0, rows === undefined ? this.height - (row0 || 0) : rows)
+		const stage = Renderer._layoutHasPiz(layout) ? addon.stageExrBlocksPiz : addon.stageExrBlocks
+		stage(this._h, bytes, layout.parts, layout.blocks, row0 === undefined ? 0 : row0, rows === undefined ? this.height - (row0 || 0) : rows)
 		;(this._stagedExrNow = this._stagedExrNow || []).push(bytes) // kept alive until the copies of this batch have executed (stageFlip)
 	}
 	exrBlocksStageBytes(bytes, layout, row0, rows) {
-		return addon.exrBlocksStageBytes(this._h, bytes, layout.parts, layout.blocks, row0 === undefined ? 0 : row0, rows === undefined ? this.height - (row0 || 0) : rows)
+		const count = Renderer._layoutHasPiz(layout) ? addon.exrBlocksPizStageBytes : addon.exrBlocksStageBytes
+		return count(this._h, bytes, layout.parts, layout.blocks, row0 === undefined ? 0 : row0, rows === undefined ? this.height - (row0 || 0) : rows)
 	}
 	// a frame with packed planes, or — no `gbuffer` — with `aov` attribute planes
 	stageFrame(frame) {

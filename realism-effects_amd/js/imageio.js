@@ -217,10 +217,14 @@ class ExrNotStreamable extends Error {}
 // rows, 0; uint64 offset of the packed data, packed bytes }, a scanline chunk or a tile each — and `blockCount`; scanline and tiled parts (level 0
 // of a mip-mapped one), NONE / RLE / ZIPS / ZIP / PXR24, any data window every part shares (the frame is the data window).  ExrNotStreamable then:
 // PIZ, deep data, UINT channels, parts of different data windows.
+// options.piz = true (with forms "blocks"; rfx.h "EXR blocks with PIZ"): PIZ parts too — compression 4, a scanline block of 32 rows —, which
+// Renderer.stageExrBlocks sends through rfx_stage_exr_blocks_piz; tiles of 128 x 128 texels or more stay ExrNotStreamable.  The default refuses PIZ.
 function exrAovLayout(buffer, names, options) {
 	const forms = (options && options.forms) || "scanline"
 	if (forms !== "scanline" && forms !== "blocks") throw new Error('forms: "scanline" or "blocks"')
 	const asBlocks = forms === "blocks"
+	const piz = !!(options && options.piz)
+	if (piz && !asBlocks) throw new Error('piz: true needs forms: "blocks"')
 	const b = Buffer.from(buffer.buffer, buffer.byteOffset, buffer.byteLength)
 	if (b.length < 8 || b.readUInt32LE(0) !== 0x01312f76) throw new Error("not an OpenEXR file")
 	const version = b.readInt32LE(4)
@@ -259,7 +263,7 @@ function exrAovLayout(buffer, names, options) {
 		if (type !== "scanlineimage" && !(asBlocks && type === "tiledimage")) throw new ExrNotStreamable("a part of type " + type)
 		const tiled = type === "tiledimage"
 		const comp = attrs.compression[0]
-		if (comp !== 0 && comp !== 2 && comp !== 3 && !(asBlocks && (comp === 1 || comp === 5))) {
+		if (comp !== 0 && comp !== 2 && comp !== 3 && !(asBlocks && (comp === 1 || comp === 5)) && !(piz && comp === 4)) {
 			if (comp === 1 || comp === 4 || comp === 5) throw new ExrNotStreamable("compression " + { 1: "RLE", 4: "PIZ", 5: "PXR24" }[comp])
 			throw new Error("compression " + comp + " not supported")
 		}
@@ -287,7 +291,7 @@ function exrAovLayout(buffer, names, options) {
 			p = e + 17
 		}
 		partWords.push(comp, chans.length / 3, ...chans)
-		const per = comp === 3 || comp === 5 ? 16 : 1
+		const per = comp === 3 || comp === 5 ? 16 : comp === 4 ? 32 : 1
 		let level0 = Math.ceil(H / per), n = level0, tw = 0, th = 0, ntx = 0, nty = 0
 		if (tiled) {
 			tw = attrs.tiles.readUInt32LE(0)
@@ -314,6 +318,7 @@ function exrAovLayout(buffer, names, options) {
 				const tx = b.readInt32LE(o + hdr - 20), ty = b.readInt32LE(o + hdr - 16)
 				if (b.readInt32LE(o + hdr - 12) || b.readInt32LE(o + hdr - 8) || tx < 0 || tx >= ntx || ty < 0 || ty >= nty)
 					throw new Error("an unexpected tile among the first " + level0 + " of part " + k + " (level 0 comes first)")
+				if (comp === 4 && Math.min(tw, W - tx * tw) >= 128 && Math.min(th, H - ty * th) >= 128) throw new ExrNotStreamable("PIZ tiles of 128 x 128 texels or more")
 				records.push([k, tx * tw, ty * th, Math.min(tw, W - tx * tw), Math.min(th, H - ty * th), o + hdr, packed])
 			} else {
 				const y = b.readInt32LE(o + hdr - 8) - y0 // relative to the data window, like a tile's coordinates

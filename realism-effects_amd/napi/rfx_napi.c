@@ -363,7 +363,7 @@ static napi_value n_stage_exr_aov(napi_env env, napi_callback_info info) { retur
 static napi_value n_exr_aov_stage_bytes(napi_env env, napi_callback_info info) { return exr_aov_call(env, info, 0); }
 /* stageExrBlocks / exrBlocksStageBytes(ctx, bytes, parts, blocks, row0, rows): rfx_stage_exr_blocks / rfx_exr_blocks_stage_bytes (rfx.h "EXR
  * blocks") — the same arguments, `blocks` a Uint8Array of rfx_exr_block records (imageio.exrAovLayout(..., { forms: "blocks" })) */
-static napi_value exr_blocks_call(napi_env env, napi_callback_info info, int stage) {
+static napi_value exr_blocks_call(napi_env env, napi_callback_info info, int stage, int piz) {
     napi_value a[6], out = NULL;
     int32_t row0, rows;
     rfx_exr_frame f;
@@ -374,18 +374,22 @@ static napi_value exr_blocks_call(napi_env env, napi_callback_info info, int sta
     if (!read_exr_frame(env, a[1], a[2], a[3], sizeof(rfx_exr_block), &f, &hold)) return NULL;
     const rfx_exr_block_frame b = {f.data, f.bytes, f.parts, f.chunks, f.part, (const rfx_exr_block *)hold};  /* (the records lead the block) */
     if (!stage) {
-        const size_t n = rfx_exr_blocks_stage_bytes(c, &b, row0, rows);
+        const size_t n = piz ? rfx_exr_blocks_piz_stage_bytes(c, &b, row0, rows) : rfx_exr_blocks_stage_bytes(c, &b, row0, rows);
         free(hold);
         NAPI_CALL(env, napi_create_double(env, (double)n, &out));
         return out;
     }
-    int rc = rfx_stage_exr_blocks(c, &b, row0, rows);
+    int rc = piz ? rfx_stage_exr_blocks_piz(c, &b, row0, rows) : rfx_stage_exr_blocks(c, &b, row0, rows);
     free(hold);
-    if (rc) return throw_rfx(env, c, "rfx_stage_exr_blocks", rc);
+    if (rc) return throw_rfx(env, c, piz ? "rfx_stage_exr_blocks_piz" : "rfx_stage_exr_blocks", rc);
     return NULL;
 }
-static napi_value n_stage_exr_blocks(napi_env env, napi_callback_info info) { return exr_blocks_call(env, info, 1); }
-static napi_value n_exr_blocks_stage_bytes(napi_env env, napi_callback_info info) { return exr_blocks_call(env, info, 0); }
+static napi_value n_stage_exr_blocks(napi_env env, napi_callback_info info) { return exr_blocks_call(env, info, 1, 0); }
+static napi_value n_exr_blocks_stage_bytes(napi_env env, napi_callback_info info) { return exr_blocks_call(env, info, 0, 0); }
+/* stageExrBlocksPiz / exrBlocksPizStageBytes: the same through rfx_stage_exr_blocks_piz / rfx_exr_blocks_piz_stage_bytes (rfx.h "EXR blocks with
+ * PIZ": a part's compression may also be 4) */
+static napi_value n_stage_exr_blocks_piz(napi_env env, napi_callback_info info) { return exr_blocks_call(env, info, 1, 1); }
+static napi_value n_exr_blocks_piz_stage_bytes(napi_env env, napi_callback_info info) { return exr_blocks_call(env, info, 0, 1); }
 static napi_value n_exr_aov_status(napi_env env, napi_callback_info info) {
     napi_value a[1], out, v;
     int s[3] = {0, -1, 0};
@@ -1209,6 +1213,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"stageUpload", n_stage_upload}, {"stageFlip", n_stage_flip}, {"hostAlloc", n_host_alloc}, {"stageAov", n_stage_aov}, {"aovStageBytes", n_aov_stage_bytes},
         {"stageExrAov", n_stage_exr_aov}, {"exrAovStageBytes", n_exr_aov_stage_bytes}, {"exrAovStatus", n_exr_aov_status},
         {"stageExrBlocks", n_stage_exr_blocks}, {"exrBlocksStageBytes", n_exr_blocks_stage_bytes},
+        {"stageExrBlocksPiz", n_stage_exr_blocks_piz}, {"exrBlocksPizStageBytes", n_exr_blocks_piz_stage_bytes},
         {"exportBytes", n_export_bytes}, {"exportFrame", n_export_frame}, {"stageExport", n_stage_export}, {"exportWait", n_export_wait}, {"constants", n_constants},
         {"pngBound", n_png_bound}, {"pngFrame", n_png_frame}, {"stagePng", n_stage_png},
         {"exrBound", n_exr_bound}, {"exrFrame", n_exr_frame}, {"stageExr", n_stage_exr},

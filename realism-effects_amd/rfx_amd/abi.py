@@ -143,6 +143,7 @@ class ExrFrame(C.Structure):
 
 # rfx.h "EXR blocks": the descriptor of rfx_stage_exr_blocks — a block is a rectangle of the frame, a scanline chunk or a tile
 EXR_RLE, EXR_PXR24 = 1, 5
+EXR_PIZ = 4  # rfx.h "EXR blocks with PIZ": taken by rfx_stage_exr_blocks_piz alone
 
 
 class ExrBlock(C.Structure):
@@ -185,6 +186,7 @@ EXPORTS = [
     "rfx_exr_bound", "rfx_stage_exr", "rfx_exr",
     "rfx_exr_aov_stage_bytes", "rfx_stage_exr_aov", "rfx_exr_aov_status",
     "rfx_exr_blocks_stage_bytes", "rfx_stage_exr_blocks",
+    "rfx_exr_blocks_piz_stage_bytes", "rfx_stage_exr_blocks_piz",
 ]
 
 _lib = None
@@ -305,6 +307,10 @@ def load_library(path: str | None = None) -> C.CDLL:
     lib.rfx_exr_blocks_stage_bytes.argtypes = [vp, C.POINTER(ExrBlockFrame), i, i]
     lib.rfx_exr_blocks_stage_bytes.restype = C.c_size_t
     lib.rfx_stage_exr_blocks.argtypes = [vp, C.POINTER(ExrBlockFrame), i, i]
+    if hasattr(lib, "rfx_stage_exr_blocks_piz"):  # (additive to ABI 21: Context.has_exr_piz)
+        lib.rfx_exr_blocks_piz_stage_bytes.argtypes = [vp, C.POINTER(ExrBlockFrame), i, i]
+        lib.rfx_exr_blocks_piz_stage_bytes.restype = C.c_size_t
+        lib.rfx_stage_exr_blocks_piz.argtypes = [vp, C.POINTER(ExrBlockFrame), i, i]
     if lib.rfx_abi_version() != RFX_ABI_VERSION:
         raise ImportError("librfx_hip.so ABI version %d != %d" % (lib.rfx_abi_version(), RFX_ABI_VERSION))
     if path is None:

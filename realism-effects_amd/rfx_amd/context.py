@@ -223,31 +223,47 @@ class Context:
         """the library exports rfx_stage_exr_blocks (additive to ABI 21)"""
         return hasattr(self.lib, "rfx_stage_exr_blocks")
 
+    @property
+    def has_exr_piz(self) -> bool:
+        """the library exports rfx_stage_exr_blocks_piz (additive to ABI 21): PIZ parts in a layout of blocks"""
+        return hasattr(self.lib, "rfx_stage_exr_blocks_piz")
+
+    @staticmethod
+    def _layout_has_piz(layout) -> bool:
+        return any(comp == abi.EXR_PIZ for comp, _ in layout.parts)
+
     def exr_blocks_stage_bytes(self, buf, layout, row0: int | None = None, rows: int | None = None) -> int:
-        """rfx_exr_blocks_stage_bytes: the bytes stage_exr_blocks(buf, layout, row0, rows) copies host -> device (0: the library would refuse the frame)"""
+        """rfx_exr_blocks_stage_bytes (rfx_exr_blocks_piz_stage_bytes for a layout with a PIZ part): the bytes stage_exr_blocks(buf, layout, row0,
+        rows) copies host -> device (0: the library would refuse the frame)"""
         f, _ = self._exr_block_frame(buf, layout)
-        return int(self.lib.rfx_exr_blocks_stage_bytes(self._h, C.byref(f), *self._band(row0, rows)))
+        fn = self.lib.rfx_exr_blocks_piz_stage_bytes if self._layout_has_piz(layout) and self.has_exr_piz else self.lib.rfx_exr_blocks_stage_bytes
+        return int(fn(self._h, C.byref(f), *self._band(row0, rows)))
 
     def stage_exr_blocks(self, buf, layout, row0: int | None = None, rows: int | None = None):
         """rfx_stage_exr_blocks: stage_exr_aov for a layout of blocks — scanline chunks and tiles, NONE / RLE / ZIPS / ZIP / PXR24; exr_aov_status()
-        reports on the most recent call of either"""
+        reports on the most recent call of either.  A layout with a PIZ part (imageio.exr_aov_layout(..., forms="blocks", piz=True)) goes through
+        rfx_stage_exr_blocks_piz where the library has it (has_exr_piz)."""
         f, keep = self._exr_block_frame(buf, layout)
         self.__dict__.setdefault("_staged_now", []).append(keep[0])  # kept alive until the copies of this batch have executed
-        self._chk(self.lib.rfx_stage_exr_blocks(self._h, C.byref(f), *self._band(row0, rows)), "rfx_stage_exr_blocks")
+        if self._layout_has_piz(layout) and self.has_exr_piz:
+            self._chk(self.lib.rfx_stage_exr_blocks_piz(self._h, C.byref(f), *self._band(row0, rows)), "rfx_stage_exr_blocks_piz")
+        else:
+            self._chk(self.lib.rfx_stage_exr_blocks(self._h, C.byref(f), *self._band(row0, rows)), "rfx_stage_exr_blocks")
 
-    def stage_exr_device(self, buf, names: dict | None = None):
+    def stage_exr_device(self, buf, names: dict | None = None, piz: bool = False):
         """One whole AOV EXR file held in `buf` through the device decode: the blocks form where the library has it, else the scanline form.
-        imageio.ExrNotStreamable: the file is one neither takes."""
+        piz=True: PIZ parts too, where the library has rfx_stage_exr_blocks_piz.  imageio.ExrNotStreamable: the file is one neither takes."""
         from . import imageio
         if self.has_exr_blocks:
-            self.stage_exr_blocks(buf, imageio.exr_aov_layout(buf, names, forms="blocks"))
+            self.stage_exr_blocks(buf, imageio.exr_aov_layout(buf, names, forms="blocks", piz=piz and self.has_exr_piz))
         else:
             self.stage_exr_aov(buf, imageio.exr_aov_layout(buf, names))
 
-    def stage_exr_frame(self, path: str, decode: str = "host", names: dict | None = None):
+    def stage_exr_frame(self, path: str, decode: str = "host", names: dict | None = None, piz: bool = False):
         """Stage a whole AOV EXR file.  decode="host" (the default): imageio.exr_to_typed_planes + stage_aov.  decode="device": the file's bytes
         + stage_exr_blocks (stage_exr_aov on a library without it); a file the device decode does not take (imageio.ExrNotStreamable: PIZ, deep
-        data, UINT channels, ...) goes the host's way.
+        data, UINT channels, ...) goes the host's way.  piz=True (with decode="device"): a PIZ file is decoded on the device too where the library
+        has the entry points (has_exr_piz); the default keeps it on the host.
         -> the way taken, "host" or "device"."""
         from . import imageio
         if decode not in ("host", "device"):
@@ -256,7 +272,7 @@ class Context:
             with open(path, "rb") as f:
                 data = f.read()
             try:
-                self.stage_exr_device(data, names)
+                self.stage_exr_device(data, names, piz)
                 return "device"
             except imageio.ExrNotStreamable:
                 pass

@@ -94,9 +94,10 @@ class ExrSequence:
         for i in range(len(seq)):  seq.stage(i + 1) if i + 1 < len(seq) else None;  <draws of frame i>;  ctx.stage_flip()
 
     Buffer k & 1 is refilled for frame k when the flip after frame k - 1's has returned: rfx_stage_flip's back pressure says the copies out of
-    it have executed.  A file the device decode does not take (imageio.ExrNotStreamable) is read on the host (Context.stage_exr_frame)."""
-    def __init__(self, ctx, source, names: dict | None = None):
-        self.ctx, self.names = ctx, names
+    it have executed.  A file the device decode does not take (imageio.ExrNotStreamable) is read on the host (Context.stage_exr_frame): a PIZ
+    file too, unless piz=True and the library has the PIZ entry points (Context.has_exr_piz)."""
+    def __init__(self, ctx, source, names: dict | None = None, piz: bool = False):
+        self.ctx, self.names, self.piz = ctx, names, piz
         self.paths = sorted(os.path.join(source, f) for f in os.listdir(source) if f.lower().endswith(".exr")) if isinstance(source, str) else list(source)
         self.buffers = [None, None]
 
@@ -115,7 +116,7 @@ class ExrSequence:
         if got != size:
             raise IOError("%s: read %d of %d bytes" % (path, got, size))
         try:
-            self.ctx.stage_exr_device(buf[:size], self.names)  # (the blocks form where the library has it: tiled, RLE and PXR24 files too)
+            self.ctx.stage_exr_device(buf[:size], self.names, self.piz)  # (the blocks form where the library has it: tiled, RLE and PXR24 files too)
             return "device"
         except imageio.ExrNotStreamable:
             return self.ctx.stage_exr_frame(path, "host", self.names)

@@ -1072,7 +1072,7 @@ class ExrAovLayout:
         return self._band(self.blocks, row0, rows)
 
 
-def exr_aov_layout(path_or_bytes, names: dict | None = None, forms: str = "scanline") -> ExrAovLayout:
+def exr_aov_layout(path_or_bytes, names: dict | None = None, forms: str = "scanline", piz: bool = False) -> ExrAovLayout:
     """Parse the header(s) and the offset table(s) of an AOV EXR — a path, or the file's bytes (bytes, a memoryview, a uint8 array: a pinned
     buffer the file was read into) — for the device decode.  Channel names map to planes as exr_to_typed_planes maps them (AOV_LAYOUT, `names`):
     a plane none of whose channels is in the file is absent, a diffuse / direct plane without its fourth channel has three (alpha 1), a plane
@@ -1081,10 +1081,14 @@ def exr_aov_layout(path_or_bytes, names: dict | None = None, forms: str = "scanl
     channels, a dataWindow that is not the displayWindow.
     forms="blocks", for Context.stage_exr_blocks: `blocks`, a rectangle of the frame each — scanline and tiled parts (level 0 of a mip-mapped
     one), NONE / RLE / ZIPS / ZIP / PXR24, any data window every part shares: the frame is the data window, as for read_exr.
-    ExrNotStreamable: PIZ, deep data, UINT channels, parts of different data windows."""
+    ExrNotStreamable: PIZ, deep data, UINT channels, parts of different data windows.
+    forms="blocks", piz=True: PIZ parts too (compression 4; a scanline block of 32 rows), for a library with rfx_stage_exr_blocks_piz
+    (Context.has_exr_piz); the default refuses them as before."""
     if forms not in ("scanline", "blocks"):
         raise ValueError('forms: "scanline" or "blocks"')
     as_blocks = forms == "blocks"
+    if piz and not as_blocks:
+        raise ValueError('piz=True needs forms="blocks"')
     if isinstance(path_or_bytes, (str, os.PathLike)):
         with open(path_or_bytes, "rb") as f:
             data = f.read()
@@ -1126,7 +1130,7 @@ def exr_aov_layout(path_or_bytes, names: dict | None = None, forms: str = "scanl
             raise ExrNotStreamable("%s: a part of type %s" % (what, typ.decode()))
         tiled = typ == b"tiledimage"
         lay = _exr_part_layout(what, attrs, tiled)
-        if lay["comp"] not in ((_COMP_NONE, _COMP_RLE, _COMP_ZIPS, _COMP_ZIP, _COMP_PXR24) if as_blocks else (_COMP_NONE, _COMP_ZIPS, _COMP_ZIP)):
+        if lay["comp"] not in ((_COMP_NONE, _COMP_RLE, _COMP_ZIPS, _COMP_ZIP, _COMP_PXR24) + ((_COMP_PIZ,) if piz else ()) if as_blocks else (_COMP_NONE, _COMP_ZIPS, _COMP_ZIP)):
             raise ExrNotStreamable("%s: compression %s" % (what, {_COMP_RLE: "RLE", _COMP_PIZ: "PIZ", _COMP_PXR24: "PXR24"}[lay["comp"]]))
         if not as_blocks and attrs[b"dataWindow"][1] != attrs[b"displayWindow"][1]:
             raise ExrNotStreamable("%s: the dataWindow is not the displayWindow" % what)
@@ -1175,6 +1179,8 @@ def exr_aov_layout(path_or_bytes, names: dict | None = None, forms: str = "scanl
         else:
             rec["y"] = words[:, -2] - lay["y0"]  # relative to the data window, like a tile's coordinates
             rec["cols"], rec["rows"] = W, np.minimum(lay["per_block"], H - rec["y"])
+        if lay["comp"] == _COMP_PIZ and np.any((rec["cols"] >= 128) & (rec["rows"] >= 128)):
+            raise ExrNotStreamable("%s: PIZ tiles of 128 x 128 texels or more" % what)  # (rfx.h "EXR blocks with PIZ": the limit)
         tables.append(rec)
     planes = {}
     for pi, key in enumerate(AOV_LAYOUT):

@@ -24,6 +24,14 @@ E1 is readinto + imageio.exr_aov_layout(forms="blocks") + stage_exr_blocks; "zip
 new figure has E1's ZIP figure beside it.  The result is merged into --out under "exr_blocks".  The RLE file is written by a vectorised coder
 of this tool (imageio's is a byte loop), and its E0 — imageio's byte loop again — is timed over --e0-frames frames only.
 
+--forms piz,tiled_piz (with --modes E0,E1): the typed frame as PIZ scanline blocks of 32 rows and as PIZ tiles of 64 x 64, decoded on the device on
+request (rfx.h "EXR blocks with PIZ"): E1 is readinto + imageio.exr_aov_layout(forms="blocks", piz=True) + stage_exr_blocks.  imageio's PIZ
+writer and reader are Python loops of a few microseconds per 16-bit word, so frame 0's file is written once (and kept: with --exr-dir a later run
+reuses it) and serves both staging slots, and E0 — the host decode, where such a file goes by default — is not looped: the host's
+imageio._exr_unpack_block is timed over the blocks of the file's first block row (32 scanlines, or one row of tiles) and scaled by height / those
+rows ("E0_band_scaled"; the de-interleave and stage_aov behind it, milliseconds, are not in it).  Merged into --out under "exr_piz".  With them: K9_PIZ_FAST_BITS, the waves per CU
+the decode's LDS leaves, and the table scratch bytes of the frame.
+
     python tools/import_rate.py [--modes P0,A0,A1,A2 | E0,E1] [--out profiles/import/rates.json] [--seconds 1.0]
     rocprofv3 --kernel-trace --stats -d DIR -- python tools/import_rate.py --kernel-only      (the pack kernel's own time: a run of its own)
     rocprofv3 --kernel-trace --stats -d DIR -- python tools/import_rate.py --kernel-only --modes E1      (... and the K9 kernels')
@@ -51,8 +59,12 @@ MODES = ("P0", "A0", "A1", "A2")
 EXR_MODES = ("E0", "E1")
 EXR_COMPRESSIONS = ("zips", "zip")
 # --forms: name -> (compression, tiles); the two above are the forms rfx_stage_exr_aov takes, the others go through rfx_stage_exr_blocks
-EXR_FORMS = {"zips": ("zips", None), "zip": ("zip", None), "tiled_zip": ("zip", (64, 64)), "pxr24": ("pxr24", None), "rle": ("rle", None)}
-BLOCK_FORMS = ("tiled_zip", "pxr24", "rle")
+EXR_FORMS = {"zips": ("zips", None), "zip": ("zip", None), "tiled_zip": ("zip", (64, 64)), "pxr24": ("pxr24", None), "rle": ("rle", None),
+             "piz": ("piz", None), "tiled_piz": ("piz", (64, 64))}
+BLOCK_FORMS = ("tiled_zip", "pxr24", "rle", "piz", "tiled_piz")
+PIZ_FORMS = ("piz", "tiled_piz")
+# csrc/k9_piz.h: the primary table's bits, the LDS of one decoding wave (K9PizHuf + the 64 counts of the bitmap scan), a block's table scratch
+PIZ_FAST_BITS, PIZ_WAVE_LDS, PIZ_TABLE_BYTES, CU_LDS = 12, 17824, 131072 + 131328 + 256, 160 * 1024
 
 
 def rle_compress_fast(buf: bytes) -> bytes:
@@ -123,7 +135,7 @@ class Run:
         exr = [m for m in modes if m in EXR_MODES]
         self.exr_bytes = {}
         self.forms = forms
-        files = {(i, comp): os.path.join(exr_dir, "frame%d_%s.exr" % (i, comp)) for i in range(2) for comp in forms} if exr else {}
+        files = {(i, comp): os.path.join(exr_dir, "frame%d_%s.exr" % (0 if comp in PIZ_FORMS else i, comp)) for i in range(2) for comp in forms} if exr else {}
         if files_only:  # a kernel trace of E1 over files an earlier run left in --exr-dir: nothing is rendered, nothing is drawn
             for (i, comp), path in sorted(files.items()):
                 self.exr_bytes.setdefault(comp, []).append(os.path.getsize(path))
@@ -155,7 +167,9 @@ class Run:
                 if comp == "rle":
                     imageio._rle_compress = rle_compress_fast
                 try:
-                    imageio.write_exr_multipart(path, parts, EXR_FORMS[comp][0], half=set(HALF), tiles=EXR_FORMS[comp][1])
+                    if not (comp in PIZ_FORMS and os.path.exists(path)):  # (a PIZ file: minutes to write; frame 0's, once)
+                        imageio.write_exr_multipart(path, parts, EXR_FORMS[comp][0], half=set(HALF), tiles=EXR_FORMS[comp][1])
+                        print("wrote %s" % os.path.basename(path), file=sys.stderr, flush=True)
                 finally:
                     imageio._rle_compress = slow
                 self.exr_bytes.setdefault(comp, []).append(os.path.getsize(path))
@@ -189,7 +203,7 @@ class Run:
             if self.forms == EXR_COMPRESSIONS:
                 ctx.stage_exr_aov(buf, imageio.exr_aov_layout(buf[:size]))
             else:
-                ctx.stage_exr_blocks(buf, imageio.exr_aov_layout(buf[:size], forms="blocks"))
+                ctx.stage_exr_blocks(buf, imageio.exr_aov_layout(buf[:size], forms="blocks", piz=ctx.has_exr_piz))
         else:
             ctx.stage_frame(f)
 
@@ -230,7 +244,7 @@ def main():
     ap.add_argument("--kernel-only", action="store_true", help="only stage and flip AOV frames (under rocprofv3 --kernel-trace --stats)")
     ap.add_argument("--modes", default=",".join(MODES), help="P0,A0,A1,A2 (the default) or E0,E1 (the EXR file modes, measured beside A2)")
     ap.add_argument("--exr-dir", default=None, help="where the E modes write their files (default: a temporary directory)")
-    ap.add_argument("--forms", default=None, help="with --modes E0,E1: tiled_zip,pxr24,rle (any of them) — the EXR blocks forms, measured beside E1's zip")
+    ap.add_argument("--forms", default=None, help="with --modes E0,E1: tiled_zip,pxr24,rle,piz,tiled_piz (any of them) — the EXR blocks forms, measured beside E1's zip")
     ap.add_argument("--e0-frames", type=int, default=2, help="--forms rle: the frames of one E0 loop (the host's RLE decode is a byte loop)")
     a = ap.parse_args()
     global W, H
@@ -316,7 +330,8 @@ def main_exr(a, modes):
 
 
 def main_exr_blocks(a, modes):
-    """E0 / E1 per --forms form, E1 of the ZIP scanline file beside them (all through stage_exr_blocks); merged into --out under "exr_blocks" """
+    """E0 / E1 per --forms form, E1 of the ZIP scanline file beside them (all through stage_exr_blocks); merged into --out under "exr_blocks", or
+    under "exr_piz" when a PIZ form is among them"""
     assert set(modes) <= set(EXR_MODES)
     forms = tuple(a.forms.split(","))
     assert forms and set(forms) <= set(BLOCK_FORMS), "--forms: any of " + ",".join(BLOCK_FORMS)
@@ -324,7 +339,7 @@ def main_exr_blocks(a, modes):
     run = Run(a.seed, modes, a.exr_dir or tmp.name, forms=("zip",) + forms)
     out = dict(width=W, height=H, seed=a.seed, seconds=a.seconds, tiles=list(EXR_FORMS["tiled_zip"][1]), forms={})
     for form in ("zip",) + forms:
-        names = [m + ":" + form for m in modes if not (form == "zip" and m == "E0")]
+        names = [m + ":" + form for m in modes if not (m == "E0" and (form == "zip" or form in PIZ_FORMS))]
         n = {}
         for mode in names:
             if mode == "E0:rle":
@@ -335,13 +350,19 @@ def main_exr_blocks(a, modes):
             n[mode] = max(2 if per > 0.25 else 20, int(math.ceil(a.seconds / per)))
         size = run.exr_bytes[form][0]
         data = open(run.frames["E1:" + form][0].path, "rb").read()
-        lay = imageio.exr_aov_layout(data, forms="blocks")
+        lay = imageio.exr_aov_layout(data, forms="blocks", piz=form in PIZ_FORMS)
         row0 = dict(file_bytes=run.exr_bytes[form], file_bytes_per_pixel=round(size / (W * H), 3), blocks=len(lay.blocks),
                     raw_blocks=int((lay.blocks["packed_bytes"] == block_raw_sizes(lay)).sum()), staged_bytes=run.ctx.exr_blocks_stage_bytes(data, lay), frames=n, rounds=[])
+        if form in PIZ_FORMS:
+            row0.update(piz_host_band(data, lay))
+            row0.update(fast_bits=PIZ_FAST_BITS, wave_lds_bytes=PIZ_WAVE_LDS, waves_per_cu=CU_LDS // PIZ_WAVE_LDS,
+                        table_scratch_bytes=(len(lay.blocks) - row0["raw_blocks"]) * PIZ_TABLE_BYTES)
         for r in range(1 if form == "rle" else 3):
             row = {mode.split(":")[0]: round(run.loop(mode, n[mode]) / n[mode] * 1e3, 4) for mode in names}
             if "E0" in row and "E1" in row:
                 row["E0_over_E1"] = round(row["E0"] / row["E1"], 2)
+            if "E0_band_scaled" in row0 and "E1" in row:
+                row["E0_band_scaled_over_E1"] = round(row0["E0_band_scaled"] / row["E1"], 2)
             row0["rounds"].append(row)
             print(form, json.dumps(row), flush=True)
         assert run.ctx.exr_aov_status()[0] == 0
@@ -351,11 +372,25 @@ def main_exr_blocks(a, modes):
         out["forms"][form]["E1_over_E1_zip"] = round(min(r["E1"] for r in out["forms"][form]["rounds"]) / zip_e1, 4)
     run.ctx.close()
     result = json.load(open(a.out)) if os.path.exists(a.out) else {}
-    result["exr_blocks"] = out
+    result["exr_piz" if set(forms) & set(PIZ_FORMS) else "exr_blocks"] = out  # (a PIZ run is a run of its own: it does not replace the 4K figures)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(result, f, indent=1)
         f.write("\n")
+
+
+def piz_host_band(data, lay):
+    """the host's PIZ decode of the file's first block row — the blocks with y = 0 of every part —, in ms, and that scaled to the frame's rows"""
+    first = [b for b in lay.blocks if int(b["y"]) == 0]
+    rows = int(first[0]["rows"])
+    assert all(int(b["rows"]) == rows for b in first)
+    t0 = time.perf_counter()
+    for b in first:
+        chans = [(None, pt) for pt, _, _ in lay.parts[int(b["part"])][1]]
+        raw = int(b["rows"]) * int(b["cols"]) * sum(2 if pt == 1 else 4 for _, pt in chans)
+        imageio._exr_unpack_block(data[int(b["offset"]):int(b["offset"] + b["packed_bytes"])], imageio._COMP_PIZ, chans, int(b["cols"]), int(b["rows"]), raw)
+    ms = (time.perf_counter() - t0) * 1e3
+    return dict(E0_band_rows=rows, E0_band_blocks=len(first), E0_band_ms=round(ms, 1), E0_band_scaled=round(ms * H / rows, 1))
 
 
 def block_raw_sizes(lay):
