@@ -473,7 +473,7 @@ int rfx_export_wait(rfx_ctx *, int ticket);
  *     (A decoder accepts any valid header; this one is fixed so that the fragment is a pure function of the pixels — tests/png_device_ref.py
  *     restates it and the device's fragment equals it byte for byte.)
  * THE RESULT BUFFER (`host`, rfx_png_bound bytes): a 32-byte little-endian header, the fragment from offset 32, unspecified bytes after it.
- *       uint64 fragment_bytes | uint32 adler_a | uint32 adler_b | uint64 raw_bytes | 8 bytes of zero
+ *       uint64 fragment_bytes | uint32 adler_a | uint32 adler_b | uint64 raw_bytes | 8 bytes of zero ("Match form" below counts its chunks in the first four)
  *   adler_a / adler_b: the stand-alone Adler-32 (initial value 1) of the tile's filtered bytes, low and high half; raw_bytes = tile_rows * n.
  * THE HOST'S WRAP: signature; IHDR; IDAT(78 01); the fragments, TOP TILE FIRST; IDAT(03 00 | Adler-32 big-endian) — the final empty block and
  *   the tiles' Adlers combined in that order as A = (A1 + A2 - 1) mod 65521, B = (B1 + B2 + len2 * (A1 - 1)) mod 65521; IEND.
@@ -508,7 +508,7 @@ int rfx_png(rfx_ctx *, const rfx_export_params *, int filter, void *host, size_t
  *     (b) the raw block itself, n bytes, unpredicted.
  *   There is no state across scanlines: the fragments of any row tiling, concatenated top tile first, are the whole frame's fragment.
  * THE RESULT BUFFER (`host`, rfx_exr_bound bytes): a 32-byte little-endian header, the fragment from offset 32, unspecified bytes after it.
- *       uint64 fragment_bytes | uint32 chunks | uint32 first_y | uint64 raw_bytes | uint32 raw_form_chunks | 4 bytes of zero
+ *       uint64 fragment_bytes | uint32 chunks | uint32 first_y | uint64 raw_bytes | uint32 raw_form_chunks | 4 bytes of zero ("Match form" below counts its chunks there)
  *   chunks = tile_rows; first_y = the y of the first chunk; raw_bytes = tile_rows * n; raw_form_chunks = the chunks in form (b).
  * THE HOST'S WRAP: magic and version; the attributes of a scanline file — channels (HALF, alphabetical), compression 2 (ZIPS), dataWindow,
  *   displayWindow, lineOrder 0 (increasing y), pixelAspectRatio, screenWindowCenter, screenWindowWidth; the offset table, built by walking the
@@ -521,6 +521,39 @@ int rfx_png(rfx_ctx *, const rfx_export_params *, int filter, void *host, size_t
 size_t rfx_exr_bound(const rfx_ctx *, const rfx_export_params *);
 int rfx_stage_exr(rfx_ctx *, const rfx_export_params *, void *host, size_t bytes, int *ticket);
 int rfx_exr(rfx_ctx *, const rfx_export_params *, void *host, size_t bytes);
+
+/* ---- Match form (K8 with run-length matches): both fragment kinds gain a third chunk form with LZ77 matches of distance 1.  Additive to ABI
+ * 21: four more entry points, no new profile kind; a host checks for the symbol.  Opt-in per call: `flags` = 0 is rfx_stage_png / rfx_png /
+ * rfx_stage_exr / rfx_exr byte for byte, RFX_ENCODE_MATCHES adds form (c) below; any other bit is RFX_EINVAL.  Everything else — K7, the
+ * tickets, the back pressure, the two staging buffers, rfx_export_wait, RFX_PROF_K8, the bounds, the host's wrap — is the export's, over the
+ * mixed sequence of all export kinds.  rfx_export_params keeps its layout.
+ *
+ *   THE BYTE SEQUENCE d[0, n) of a chunk is what the chunk codes without matches: the PNG scanline's filtered bytes, type byte first; the EXR
+ *     scanline's predicted bytes.
+ *   THE TOKEN RULE.  Position j >= 1 is REPEATING when d[j] == d[j - 1].  A maximal interval [s, e) of repeating positions is cut from s into
+ *     pieces of 258 positions.  A piece of 3 or more positions is ONE MATCH: length = the piece, distance 1.  A last piece of 1 or 2 positions
+ *     is literals, and so is every position that is not repeating.  A match never reaches before d[0]: no state crosses chunks, the fragments
+ *     of any row tiling still concatenate to the whole frame's, and a PNG scanline still never looks at the previous scanline's bytes.
+ *   FORM (c): one dynamic-Huffman block of those tokens and the end-of-block symbol.  The literal / length code covers 286 symbols, limit 15,
+ *     the end-of-block symbol counted once, built by THE CODE-LENGTH RULE of "PNG fragments" from the tokens' frequencies (a match counts for
+ *     its length symbol).  HLIT declares the codes up to the highest used symbol, at least 257.  HDIST declares one distance code, code 0, of
+ *     length 1.  A match costs its length symbol, deflate's extra bits for the length, and the one distance bit 0 (distance code 0 has no extra
+ *     bits).  The code-length sequence — the HLIT lengths, then that 1 — is tokenised by the header-token rule and coded by the code-length
+ *     code rule of "PNG fragments", word for word.
+ *     PNG: the block is non-final and followed by the empty stored block, exactly as form (a).  Size: ceil((block bits + 3) / 8) + 4.
+ *     EXR: the block is FINAL inside 78 01 ... Adler-32 of d, exactly as form (a).  Size: 2 + ceil(block bits / 8) + 4.
+ *   FORM CHOICE.  A chunk takes form (c) only when it contains at least one match AND (c) is STRICTLY smaller than what the chunk gets without
+ *     matches — PNG: the smaller of (a) and (b); EXR: (a) when that is smaller than n, else n.  So no chunk is larger with matches than
+ *     without, and a chunk without a match is byte-identical.  (tests/match_device_ref.py restates the form; the device's result equals it
+ *     byte for byte.)
+ *   THE RESULT BUFFER: uint32 match_form_chunks, the chunks in form (c), stands in bytes that are zero otherwise — PNG: the first four of the
+ *     header's trailing 8 bytes (offset 24); EXR: the trailing 4 bytes (offset 28).  Zero with flags = 0.
+ * RFX_EINVAL: a bit in `flags` other than RFX_ENCODE_MATCHES; what the call without _ex refuses. */
+#define RFX_ENCODE_MATCHES 1u
+int rfx_stage_png_ex(rfx_ctx *, const rfx_export_params *, int filter, unsigned flags, void *host, size_t bytes, int *ticket);
+int rfx_png_ex(rfx_ctx *, const rfx_export_params *, int filter, unsigned flags, void *host, size_t bytes);
+int rfx_stage_exr_ex(rfx_ctx *, const rfx_export_params *, unsigned flags, void *host, size_t bytes, int *ticket);
+int rfx_exr_ex(rfx_ctx *, const rfx_export_params *, unsigned flags, void *host, size_t bytes);
 
 int rfx_sync(rfx_ctx *);
 

@@ -482,6 +482,7 @@ __global__ __launch_bounds__(RFX_K7_BLOCK) void k7_export(K7Args A) {
 
 #include "k8_png.h"  // K8: the PNG fragment of K7's U8 stream
 #include "k8_exr.h"  // ... and the EXR fragment of its F16 stream: the same coder behind another pre-transform
+#include "k8_match.h"  // ... and both with run-length matches, as second scanline kernels
 
 template <int FMT, int CH, int TM>
 static void k7_launch(const K7Args &A, int blocks, hipStream_t stream) {

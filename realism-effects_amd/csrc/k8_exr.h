@@ -7,7 +7,7 @@
 //   k8_exr_rows    one wave per scanline: the predicted bytes d (each t byte's difference to its predecessor + 128), histogram, the Adler-32's
 //                  partial sums, code lengths, block header, bit packing into the scanline's slot — a whole chunk: y, size, data — or, when the
 //                  zlib stream would not be smaller than the raw block, the raw block
-//   k8_exr_scan    one wave: exclusive scan of the chunk sizes, the count of raw chunks, the 32-byte result header
+//   k8_exr_scan    one wave: exclusive scan of the chunk sizes, the counts of raw and of match-form chunks, the 32-byte result header
 //   k8_png_gather  slot -> its place in the contiguous fragment (k8_png.h)
 //
 // The zlib stream goes through the bit window whole: its two header bytes are the window's first 16 bits, the Adler-32 its last 32.
@@ -195,7 +195,7 @@ __global__ __launch_bounds__(64) void k8_exr_rows(K8ExrArgs A) {
 __global__ __launch_bounds__(64) void k8_exr_scan(K8ExrArgs A) {
     const int lane = (int)threadIdx.x;
     unsigned long long running = 0;
-    int raw = 0;
+    int raw = 0, matched = 0;
     for (int base = 0; base < A.rows; base += 64) {
         const int s = base + lane;
         int len = 0;
@@ -203,6 +203,7 @@ __global__ __launch_bounds__(64) void k8_exr_scan(K8ExrArgs A) {
             const unsigned *m = A.meta + 4 * (size_t)s;
             len = (int)m[0];
             raw += (int)m[1];
+            matched += (int)m[2];  // chunks in the match form (k8_match.h); none from k8_exr_rows
         }
         int total;
         const int off = k8_wave_scan(len, lane, total);
@@ -210,6 +211,7 @@ __global__ __launch_bounds__(64) void k8_exr_scan(K8ExrArgs A) {
         running += (unsigned long long)total;
     }
     raw = k8_wave_sum(raw);
+    matched = k8_wave_sum(matched);
     if (lane == 0) {
         const unsigned long long N = (unsigned long long)A.rows * (unsigned long long)(2 * A.width * A.channels);
         unsigned *h = (unsigned *)A.result;
@@ -217,16 +219,19 @@ __global__ __launch_bounds__(64) void k8_exr_scan(K8ExrArgs A) {
         h[2] = (unsigned)A.rows;
         h[3] = (unsigned)A.first_y;
         h[4] = (unsigned)N; h[5] = (unsigned)(N >> 32);
-        h[6] = (unsigned)raw; h[7] = 0;
+        h[6] = (unsigned)raw; h[7] = (unsigned)matched;
     }
 }
 
 }  // namespace
 
-hipError_t rfx_launch_k8_exr(const K8ExrArgs &A, hipStream_t stream) {
+hipError_t rfx_launch_k8_exr(const K8ExrArgs &A, hipStream_t stream, bool matches) {
     if (A.rows <= 0 || A.rows > 65535 || A.width <= 0 || (A.channels != 3 && A.channels != 4)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k8_exr_planes, dim3((A.width + 255) / 256, A.rows), dim3(256), 0, stream, A);
-    hipLaunchKernelGGL(k8_exr_rows, dim3(A.rows), dim3(64), 0, stream, A);
+    if (matches) {
+        const hipError_t e = rfx_launch_k8_exr_rows_m(A, stream);  // k8_match.h
+        if (e != hipSuccess) return e;
+    } else hipLaunchKernelGGL(k8_exr_rows, dim3(A.rows), dim3(64), 0, stream, A);
     hipLaunchKernelGGL(k8_exr_scan, dim3(1), dim3(64), 0, stream, A);
     K8Args G = {};  // the gather reads the chunk sizes, the offsets and the slots only
     G.result = A.result; G.slots = A.slots; G.meta = A.meta; G.offsets = A.offsets;

@@ -3,7 +3,8 @@
 //
 //   k8_png_rows    one wave (a workgroup of 64 lanes) per scanline: filter choice, histogram, code lengths, block header, bit packing into
 //                  the scanline's slot of a scratch buffer (a whole chunk: length, "IDAT", payload, CRC-32), Adler partial sums
-//   k8_png_scan    one wave: exclusive scan of the chunk sizes, the tile's Adler-32 from the partial sums, the 32-byte result header
+//   k8_png_scan    one wave: exclusive scan of the chunk sizes, the tile's Adler-32 from the partial sums, the count of match-form chunks,
+//                  the 32-byte result header
 //   k8_png_gather  one workgroup per chunk: slot -> its place in the contiguous fragment
 //
 // The row is never staged in LDS (a 32768 x 4 row is 131 073 bytes): it is read three times — costs, histogram, codes — from L2, where K7
@@ -442,12 +443,14 @@ __global__ __launch_bounds__(64) void k8_png_scan(K8Args A) {
     const int lane = (int)threadIdx.x;
     const unsigned long long n = (unsigned long long)A.rowbytes + 1ull;
     unsigned long long running = 0, a = 0, b = 0;
+    int matched = 0;  // chunks in the match form (k8_match.h); none from k8_png_rows
     for (int base = 0; base < A.rows; base += 64) {
         const int s = base + lane;
         int len = 0;
         if (s < A.rows) {
             const unsigned *m = A.meta + 4 * (size_t)s;
             len = (int)m[0];
+            matched += (int)m[3];
             a += m[1];
             b += m[2] + ((unsigned long long)(A.rows - 1 - s) * n) % K8_ADLER * m[1];
         }
@@ -458,13 +461,14 @@ __global__ __launch_bounds__(64) void k8_png_scan(K8Args A) {
     }
     const unsigned long long N = (unsigned long long)A.rows * n;
     const unsigned sa = (unsigned)k8_wave_sum((int)(a % K8_ADLER)), sb = (unsigned)k8_wave_sum((int)(b % K8_ADLER));
+    matched = k8_wave_sum(matched);
     if (lane == 0) {
         unsigned *h = (unsigned *)A.result;
         h[0] = (unsigned)running; h[1] = (unsigned)(running >> 32);
         h[2] = (1u + sa) % K8_ADLER;
         h[3] = (unsigned)((N + sb) % K8_ADLER);
         h[4] = (unsigned)N; h[5] = (unsigned)(N >> 32);
-        h[6] = 0; h[7] = 0;
+        h[6] = (unsigned)matched; h[7] = 0;
     }
 }
 
@@ -480,9 +484,12 @@ __global__ __launch_bounds__(256) void k8_png_gather(K8Args A) {
 
 }  // namespace
 
-hipError_t rfx_launch_k8(const K8Args &A, hipStream_t stream) {
+hipError_t rfx_launch_k8(const K8Args &A, hipStream_t stream, bool matches) {
     if (A.rows <= 0 || A.rowbytes <= 0 || (A.bpp != 3 && A.bpp != 4) || A.filter < 0 || A.filter > 4) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k8_png_rows, dim3(A.rows), dim3(64), 0, stream, A);
+    if (matches) {
+        const hipError_t e = rfx_launch_k8_rows_m(A, stream);  // k8_match.h
+        if (e != hipSuccess) return e;
+    } else hipLaunchKernelGGL(k8_png_rows, dim3(A.rows), dim3(64), 0, stream, A);
     hipLaunchKernelGGL(k8_png_scan, dim3(1), dim3(64), 0, stream, A);
     hipLaunchKernelGGL(k8_png_gather, dim3(A.rows), dim3(256), 0, stream, A);
     return hipGetLastError();

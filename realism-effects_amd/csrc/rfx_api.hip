@@ -1676,13 +1676,14 @@ static int grow_idle(rfx_ctx *c, void **buf, size_t *cap, size_t want, const cha
 
 // png_filter < 0: the plain export (K7's bytes cross PCIe); 0..4: rfx_stage_png — K7 as ever, then K8 on the download stream and its result buffer.
 // exr: rfx_stage_exr — the same with K8's EXR pre-transform behind K7's F16 stream.
-static int export_enqueue(rfx_ctx *c, const rfx_export_params *p, void *host, size_t bytes, int *ticket, const char *fn, int png_filter = -1, bool exr = false) {
+static int export_enqueue(rfx_ctx *c, const rfx_export_params *p, void *host, size_t bytes, int *ticket, const char *fn, int png_filter = -1, bool exr = false, unsigned flags = 0) {
     if (!c || !p || !host) return RFX_EINVAL;
     RFX_ENTER(c);
     if (const char *bad = export_params_error(p)) return fail_in(c, RFX_EINVAL, fn, bad);
     rfx_export_plan t;
     if (!rfx_export_plan_for(c->tile_rows * c->W, p->format, p->channels, &t)) return fail_in(c, RFX_EINVAL, fn, "bad format or channel count");
     const bool png = png_filter >= 0;
+    if (flags & ~RFX_ENCODE_MATCHES) return fail_in(c, RFX_EINVAL, fn, "flags holds a bit other than RFX_ENCODE_MATCHES");
     rfx_png_plan g = {};
     rfx_exr_plan x = {};
     if (png) {
@@ -1748,7 +1749,7 @@ static int export_enqueue(rfx_ctx *c, const rfx_export_params *p, void *host, si
         E.rows = g.rows; E.rowbytes = g.rowbytes; E.bpp = p->channels; E.filter = png_filter;
         E.slot_stride = g.slot_stride;
         ProfScope prof(c, RFX_PROF_K8, c->download_stream);
-        HIPCHK(c, rfx_launch_k8(E, c->download_stream));
+        HIPCHK(c, rfx_launch_k8(E, c->download_stream, (flags & RFX_ENCODE_MATCHES) != 0));
         from = base;
     } else if (exr) {
         unsigned char *base = (unsigned char *)c->png_buf[b];
@@ -1764,7 +1765,7 @@ static int export_enqueue(rfx_ctx *c, const rfx_export_params *p, void *host, si
         E.first_y = c->H - c->tile_y0 - c->tile_rows;
         E.slot_stride = x.slot_stride; E.plane_stride = x.plane_stride;
         ProfScope prof(c, RFX_PROF_K8, c->download_stream);
-        HIPCHK(c, rfx_launch_k8_exr(E, c->download_stream));
+        HIPCHK(c, rfx_launch_k8_exr(E, c->download_stream, (flags & RFX_ENCODE_MATCHES) != 0));
         from = base;
     }
     // (the whole bound crosses for a PNG or an EXR fragment: copying only fragment_bytes would need the host to wait for the header first — rfx.h)
@@ -1831,6 +1832,31 @@ int rfx_stage_exr(rfx_ctx *c, const rfx_export_params *p, void *host, size_t byt
 int rfx_exr(rfx_ctx *c, const rfx_export_params *p, void *host, size_t bytes) {
     int ticket = 0;
     const int rc = export_enqueue(c, p, host, bytes, &ticket, "rfx_exr", -1, true);
+    return rc ? rc : rfx_export_wait(c, ticket);
+}
+
+// ---- K8 with run-length matches (include/rfx.h "Match form"; the kernels are in k8_match.h): flags = 0 is the call without _ex
+int rfx_stage_png_ex(rfx_ctx *c, const rfx_export_params *p, int filter, unsigned flags, void *host, size_t bytes, int *ticket) {
+    if (!ticket) return RFX_EINVAL;
+    if (filter < 0 || filter > 4) return c ? fail_in(c, RFX_EINVAL, "rfx_stage_png_ex", "filter must be 0 (adaptive) or 1..4 (None, Sub, Up, Paeth)") : RFX_EINVAL;
+    return export_enqueue(c, p, host, bytes, ticket, "rfx_stage_png_ex", filter, false, flags);
+}
+
+int rfx_png_ex(rfx_ctx *c, const rfx_export_params *p, int filter, unsigned flags, void *host, size_t bytes) {
+    if (filter < 0 || filter > 4) return c ? fail_in(c, RFX_EINVAL, "rfx_png_ex", "filter must be 0 (adaptive) or 1..4 (None, Sub, Up, Paeth)") : RFX_EINVAL;
+    int ticket = 0;
+    const int rc = export_enqueue(c, p, host, bytes, &ticket, "rfx_png_ex", filter, false, flags);
+    return rc ? rc : rfx_export_wait(c, ticket);
+}
+
+int rfx_stage_exr_ex(rfx_ctx *c, const rfx_export_params *p, unsigned flags, void *host, size_t bytes, int *ticket) {
+    if (!ticket) return RFX_EINVAL;
+    return export_enqueue(c, p, host, bytes, ticket, "rfx_stage_exr_ex", -1, true, flags);
+}
+
+int rfx_exr_ex(rfx_ctx *c, const rfx_export_params *p, unsigned flags, void *host, size_t bytes) {
+    int ticket = 0;
+    const int rc = export_enqueue(c, p, host, bytes, &ticket, "rfx_exr_ex", -1, true, flags);
     return rc ? rc : rfx_export_wait(c, ticket);
 }
 

@@ -171,13 +171,15 @@ struct K8Args {
     const unsigned char *src;     // K7's stream: `rows` rows of `rowbytes` bytes, row 0 = bottom
     unsigned char *result;        // 32-byte header, then the fragment
     unsigned char *slots;         // rows * slot_stride bytes of scratch: one whole chunk per scanline
-    unsigned *meta;               // rows * 4: chunk bytes, the two Adler partial sums, 0
+    unsigned *meta;               // rows * 4: chunk bytes, the two Adler partial sums, 1 for a chunk in the match form
     unsigned long long *offsets;  // rows: where each chunk starts in the fragment
     unsigned long long fragment_cap;  // bound - 32
     int rows, rowbytes, bpp, filter;
     unsigned slot_stride;
 };
-hipError_t rfx_launch_k8(const K8Args &, hipStream_t);
+// matches: the scanline kernel is k8_png_rows_m (k8_match.h: the match form where it is smaller) instead of k8_png_rows (literals only)
+hipError_t rfx_launch_k8(const K8Args &, hipStream_t, bool matches = false);
+hipError_t rfx_launch_k8_rows_m(const K8Args &, hipStream_t);  // the scanline kernel alone, with matches: rfx_launch_k8 calls it
 
 // K8 EXR encode (k8_exr.h, built into k0_import.hip): K7's staged F16 stream -> the result buffer of include/rfx.h "EXR fragments", laid out by
 // rfx_launch.h rfx_exr_plan_for.  Four launches on `stream`: the byte planes, one wave per scanline into the scratch slots, the scan, the gather.
@@ -186,14 +188,16 @@ struct K8ExrArgs {
     unsigned char *result;        // 32-byte header, then the fragment
     unsigned char *slots;         // rows * slot_stride bytes of scratch: one whole chunk per scanline
     unsigned char *planes;        // rows * plane_stride bytes of scratch: each scanline's low bytes, then its high bytes
-    unsigned *meta;               // rows * 4: chunk bytes, 1 for a raw chunk, 0, 0
+    unsigned *meta;               // rows * 4: chunk bytes, 1 for a raw chunk, 1 for a chunk in the match form, 0
     unsigned long long *offsets;  // rows: where each chunk starts in the fragment
     unsigned long long fragment_cap;  // bound - 32
     int rows, width, channels;
     int first_y;                  // the EXR y of the tile's top scanline
     unsigned slot_stride, plane_stride;
 };
-hipError_t rfx_launch_k8_exr(const K8ExrArgs &, hipStream_t);
+// matches: the scanline kernel is k8_exr_rows_m (k8_match.h) instead of k8_exr_rows
+hipError_t rfx_launch_k8_exr(const K8ExrArgs &, hipStream_t, bool matches = false);
+hipError_t rfx_launch_k8_exr_rows_m(const K8ExrArgs &, hipStream_t);  // the scanline kernel alone, with matches: rfx_launch_k8_exr calls it
 
 // K9 EXR import (k9_exr_import.hip): the packed blocks of an OpenEXR file — scanline chunks or tiles, a rectangle of the frame each — -> the typed
 // AOV staging planes k0_aov_pack reads (include/rfx.h "streamed EXR frames", "EXR blocks").  Four launches on `stream`: k9_inflate (one wave per

@@ -66,6 +66,8 @@ const PROF_KINDS = ["k1_prepass", "k1_ssgi_march", "k2_temporal_reproject", "k3_
 const PROF_KINDS_ALL = PROF_KINDS.concat(["k8_png"])
 // rfx_stage_png's `filter` (include/rfx.h "PNG fragments")
 const PNG_FILTERS = { adaptive: 0, none: 1, sub: 2, up: 3, paeth: 4 }
+// RFX_ENCODE_MATCHES (include/rfx.h "Match form"): the flags bit of rfx_png_ex / rfx_stage_png_ex / rfx_exr_ex / rfx_stage_exr_ex
+const ENCODE_MATCHES = 1
 
 // 128x128 RGBA8 blue-noise table: decoded once from the reference's PNG asset, already flipY'd
 // (tools/make_blue_noise_table.py; src/utils/BlueNoiseUtils.js:9-15)
@@ -231,15 +233,19 @@ class Renderer {
 		return addon.pngBound(this._h, this.pngParams(params || {}))
 	}
 	// -> the result buffer (Uint8Array of pngBound bytes: 32-byte header, fragment, slack); blocks (rfx_png)
-	png(params, filter, out) {
+	// options: { matches: true } encodes with run-length matches (rfx.h "Match form": rfx_png_ex with RFX_ENCODE_MATCHES); the same for
+	// stagePng, exr and stageExr
+	png(params, filter, out, options) {
 		const p = this.pngParams(params)
 		if (!out) out = new Uint8Array(Math.max(1, addon.pngBound(this._h, p)))
-		addon.pngFrame(this._h, p, this.pngFilter(filter), out)
+		if (options && options.matches) addon.pngFrameEx(this._h, p, this.pngFilter(filter), ENCODE_MATCHES, out)
+		else addon.pngFrame(this._h, p, this.pngFilter(filter), out)
 		return out
 	}
 	// stageExport's contract with a PNG fragment as the payload; the ticket is one of the same sequence and exportWait retires it (rfx_stage_png)
-	stagePng(params, filter, out) {
-		const ticket = addon.stagePng(this._h, this.pngParams(params), this.pngFilter(filter), out)
+	stagePng(params, filter, out, options) {
+		const ticket = options && options.matches ? addon.stagePngEx(this._h, this.pngParams(params), this.pngFilter(filter), ENCODE_MATCHES, out)
+			: addon.stagePng(this._h, this.pngParams(params), this.pngFilter(filter), out)
 		if (!this._exports) this._exports = new Map()
 		this._exports.set(ticket, out)
 		for (const t of this._exports.keys()) if (t <= ticket - 2) this._exports.delete(t)
@@ -254,15 +260,16 @@ class Renderer {
 		return addon.exrBound(this._h, this.exrParams(params || {}))
 	}
 	// -> the result buffer (Uint8Array of exrBound bytes: 32-byte header, fragment, slack); blocks (rfx_exr)
-	exr(params, out) {
+	exr(params, out, options) {
 		const p = this.exrParams(params)
 		if (!out) out = new Uint8Array(Math.max(1, addon.exrBound(this._h, p)))
-		addon.exrFrame(this._h, p, out)
+		if (options && options.matches) addon.exrFrameEx(this._h, p, ENCODE_MATCHES, out)
+		else addon.exrFrame(this._h, p, out)
 		return out
 	}
 	// stageExport's contract with an EXR fragment as the payload; the ticket is one of the same sequence and exportWait retires it (rfx_stage_exr)
-	stageExr(params, out) {
-		const ticket = addon.stageExr(this._h, this.exrParams(params), out)
+	stageExr(params, out, options) {
+		const ticket = options && options.matches ? addon.stageExrEx(this._h, this.exrParams(params), ENCODE_MATCHES, out) : addon.stageExr(this._h, this.exrParams(params), out)
 		if (!this._exports) this._exports = new Map()
 		this._exports.set(ticket, out)
 		for (const t of this._exports.keys()) if (t <= ticket - 2) this._exports.delete(t)
@@ -398,4 +405,4 @@ class Renderer {
 	}
 }
 
-module.exports = { Renderer, TEX, FORMAT, EXPORT, EXPORT_ARRAY, PROF_KINDS, PROF_KINDS_ALL, PNG_FILTERS, loadBlueNoiseTable, abiVersion: addon.abiVersion, constants: addon.constants }
+module.exports = { Renderer, TEX, FORMAT, EXPORT, EXPORT_ARRAY, PROF_KINDS, PROF_KINDS_ALL, PNG_FILTERS, ENCODE_MATCHES, loadBlueNoiseTable, abiVersion: addon.abiVersion, constants: addon.constants }

@@ -18,7 +18,9 @@ class FrameExporter {
 	//            encode: "host" (default) | "device" — png only: the frame leaves the device as a PNG fragment (rfx_stage_png, K8) and the host
 	//            only wraps and writes it; filter: the fragment's filter, "adaptive" by default;
 	//            compression: "none" (default) | "zips" — exr only: the frame leaves the device as finished ZIPS chunks (rfx_stage_exr, rfx.h "EXR
-	//            fragments") and the host only wraps and writes them }
+	//            fragments") and the host only wraps and writes them;
+	//            matches: false (default) | true — with encode "device" or compression "zips" only: the device encode with run-length matches
+	//            (rfx.h "Match form") }
 	constructor(renderer, dir, options) {
 		options = options || {}
 		this.renderer = renderer
@@ -37,6 +39,8 @@ class FrameExporter {
 		if (this.compression !== "none" && this.compression !== "zips") throw new RangeError("framesCompression: \"none\" or \"zips\"")
 		if (this.compression === "zips" && this.format !== "exr") throw new RangeError("framesCompression \"zips\" is for framesFormat \"exr\" only")
 		const zips = this.compression === "zips"
+		this.matches = !!options.matches
+		if (this.matches && this.encode !== "device" && !zips) throw new RangeError("framesMatches is for framesEncode \"device\" or framesCompression \"zips\" only")
 		const n = this.encode === "device" ? renderer.pngBound(this.params) : zips ? renderer.exrBound(this.params) : renderer.width * renderer.tileRows * f[1]
 		const alloc = options.hostAlloc || Renderer.hostAlloc
 		this.buffers = [0, 1].map(() => alloc(zips ? Uint8Array : EXPORT_ARRAY[f[0]], n))
@@ -56,8 +60,8 @@ class FrameExporter {
 	submit(source) {
 		const index = this.count++
 		const buffer = this.buffers[index & 1]
-		const ticket = this.encode === "device" ? this.renderer.stagePng(Object.assign({ source }, this.params), this.filter, buffer)
-			: this.compression === "zips" ? this.renderer.stageExr(Object.assign({ source }, this.params), buffer)
+		const ticket = this.encode === "device" ? this.renderer.stagePng(Object.assign({ source }, this.params), this.filter, buffer, { matches: this.matches })
+			: this.compression === "zips" ? this.renderer.stageExr(Object.assign({ source }, this.params), buffer, { matches: this.matches })
 			: this.renderer.stageExport(Object.assign({ source }, this.params), buffer)
 		this.retire()
 		this.pending = { ticket, index, buffer }

@@ -28,7 +28,8 @@
 // with --ranks it throws, like the other image writers.  --framesEncode '"device"' (png only; default '"host"'): the frame leaves the device as a
 // finished PNG data stream (rfx_stage_png, K8: per-scanline adaptive filter + literal-only dynamic Huffman blocks) and the host only wraps it.
 // --framesCompression '"zips"' (exr only; default '"none"'): the frame leaves the device as finished OpenEXR ZIPS chunks (rfx_stage_exr, K8 behind
-// the EXR byte predictor) and the host only wraps them; the samples are the uncompressed file's.
+// the EXR byte predictor) and the host only wraps them; the samples are the uncompressed file's.  --framesMatches true (with either of the two;
+// default false): the device encode with run-length matches (rfx.h "Match form"): smaller files where pixels repeat exactly.
 // --saveState DIR [--saveEvery N]: write a checkpoint of the temporal state (js/state.js) into DIR after every N-th frame and after the last;
 // --loadState DIR: restore one first — the dump directories given are then the REMAINING frames, and the outputs are byte-identical to an
 // uninterrupted run.  Both work with --ranks (every rank writes its rows of the whole-frame planes; any rank count loads them), --traa,
@@ -107,16 +108,17 @@ const stream = !!opt.stream
 delete opt.stream
 const images = { png: opt.png, exr: opt.exr, pfm: opt.pfm, tonemap: opt.tonemap, exposure: opt.exposure }
 for (const k of Object.keys(images)) delete opt[k]
-const framesOut = opt.framesOut === undefined ? null : { dir: String(opt.framesOut), format: opt.framesFormat || "png", encode: opt.framesEncode || "host", compression: opt.framesCompression || "none" }
+const framesOut = opt.framesOut === undefined ? null : { dir: String(opt.framesOut), format: opt.framesFormat || "png", encode: opt.framesEncode || "host", compression: opt.framesCompression || "none", matches: !!opt.framesMatches }
 delete opt.framesOut
 delete opt.framesFormat
 delete opt.framesEncode
 delete opt.framesCompression
+delete opt.framesMatches
 let frames = null
 function openFrames() {
 	if (!framesOut) return
 	fs.mkdirSync(framesOut.dir, { recursive: true })
-	frames = new rfx.FrameExporter(renderer, framesOut.dir, { format: framesOut.format, tonemap: images.tonemap, exposure: images.exposure, encode: framesOut.encode, compression: framesOut.compression })
+	frames = new rfx.FrameExporter(renderer, framesOut.dir, { format: framesOut.format, tonemap: images.tonemap, exposure: images.exposure, encode: framesOut.encode, compression: framesOut.compression, matches: framesOut.matches })
 }
 const checkpoint = { save: opt.saveState, every: opt.saveEvery, load: opt.loadState }
 delete opt.saveState

@@ -1035,32 +1035,42 @@ static napi_value n_png_bound(napi_env env, napi_callback_info info) {
 }
 /* pngFrame(ctx, params, filter, Uint8Array): rfx_png (blocks) / stagePng(ctx, params, filter, Uint8Array) -> ticket: rfx_stage_png — the result
  * buffer of include/rfx.h "PNG fragments"; the array must stay alive until exportWait(ctx, ticket) has returned.  The library checks the byte count. */
-static napi_value png_into(napi_env env, napi_callback_info info, int staged) {
-    napi_value a[4], ab, out;
+/* pngFrameEx(ctx, params, filter, flags, Uint8Array) / stagePngEx(...) -> ticket: rfx_png_ex / rfx_stage_png_ex (rfx.h "Match form": flags =
+ * RFX_ENCODE_MATCHES or 0) */
+static napi_value png_into(napi_env env, napi_callback_info info, int staged, int ex) {
+    napi_value a[5], ab, out;
     napi_typedarray_type type;
     size_t len = 0, off = 0;
     void *data = NULL;
-    int32_t filter = 0;
-    if (!get_args(env, info, 4, a)) return NULL;
+    int32_t filter = 0, flags = 0;
+    if (!get_args(env, info, ex ? 5 : 4, a)) return NULL;
     rfx_ctx *c = get_ctx(env, a[0]);
-    if (!c || !get_int(env, a[2], &filter)) return NULL;
+    if (!c || !get_int(env, a[2], &filter) || (ex && !get_int(env, a[3], &flags))) return NULL;
     rfx_export_params p;
     export_params(env, a[1], &p);
+    napi_value arr = a[ex ? 4 : 3];
     bool is_ta = false;
-    napi_is_typedarray(env, a[3], &is_ta);
-    if (!is_ta || napi_get_typedarray_info(env, a[3], &type, &len, &data, &ab, &off) != napi_ok || !data || type != napi_uint8_array) {
+    napi_is_typedarray(env, arr, &is_ta);
+    if (!is_ta || napi_get_typedarray_info(env, arr, &type, &len, &data, &ab, &off) != napi_ok || !data || type != napi_uint8_array) {
         napi_throw_type_error(env, NULL, staged ? "stagePng: Uint8Array expected" : "pngFrame: Uint8Array expected");
         return NULL;
     }
-    int ticket = 0;
-    int rc = staged ? rfx_stage_png(c, &p, filter, data, len, &ticket) : rfx_png(c, &p, filter, data, len);
-    if (rc) return throw_rfx(env, c, staged ? "rfx_stage_png" : "rfx_png", rc);
+    int ticket = 0, rc;
+    if (ex) {
+        rc = staged ? rfx_stage_png_ex(c, &p, filter, (unsigned)flags, data, len, &ticket) : rfx_png_ex(c, &p, filter, (unsigned)flags, data, len);
+        if (rc) return throw_rfx(env, c, staged ? "rfx_stage_png_ex" : "rfx_png_ex", rc);
+    } else {
+        rc = staged ? rfx_stage_png(c, &p, filter, data, len, &ticket) : rfx_png(c, &p, filter, data, len);
+        if (rc) return throw_rfx(env, c, staged ? "rfx_stage_png" : "rfx_png", rc);
+    }
     if (!staged) return NULL;
     NAPI_CALL(env, napi_create_int32(env, ticket, &out));
     return out;
 }
-static napi_value n_png_frame(napi_env env, napi_callback_info info) { return png_into(env, info, 0); }
-static napi_value n_stage_png(napi_env env, napi_callback_info info) { return png_into(env, info, 1); }
+static napi_value n_png_frame(napi_env env, napi_callback_info info) { return png_into(env, info, 0, 0); }
+static napi_value n_stage_png(napi_env env, napi_callback_info info) { return png_into(env, info, 1, 0); }
+static napi_value n_png_frame_ex(napi_env env, napi_callback_info info) { return png_into(env, info, 0, 1); }
+static napi_value n_stage_png_ex(napi_env env, napi_callback_info info) { return png_into(env, info, 1, 1); }
 /* exrBound(ctx, params) -> rfx_exr_bound (0: bad params or a format other than F16) */
 static napi_value n_exr_bound(napi_env env, napi_callback_info info) {
     napi_value a[2], out;
@@ -1074,31 +1084,41 @@ static napi_value n_exr_bound(napi_env env, napi_callback_info info) {
 }
 /* exrFrame(ctx, params, Uint8Array): rfx_exr (blocks) / stageExr(ctx, params, Uint8Array) -> ticket: rfx_stage_exr — the result buffer of
  * include/rfx.h "EXR fragments"; the array must stay alive until exportWait(ctx, ticket) has returned.  The library checks the byte count. */
-static napi_value exr_into(napi_env env, napi_callback_info info, int staged) {
-    napi_value a[3], ab, out;
+/* exrFrameEx(ctx, params, flags, Uint8Array) / stageExrEx(...) -> ticket: rfx_exr_ex / rfx_stage_exr_ex (rfx.h "Match form") */
+static napi_value exr_into(napi_env env, napi_callback_info info, int staged, int ex) {
+    napi_value a[4], ab, out;
     napi_typedarray_type type;
     size_t len = 0, off = 0;
     void *data = NULL;
-    if (!get_args(env, info, 3, a)) return NULL;
+    int32_t flags = 0;
+    if (!get_args(env, info, ex ? 4 : 3, a)) return NULL;
     rfx_ctx *c = get_ctx(env, a[0]);
-    if (!c) return NULL;
+    if (!c || (ex && !get_int(env, a[2], &flags))) return NULL;
     rfx_export_params p;
     export_params(env, a[1], &p);
+    napi_value arr = a[ex ? 3 : 2];
     bool is_ta = false;
-    napi_is_typedarray(env, a[2], &is_ta);
-    if (!is_ta || napi_get_typedarray_info(env, a[2], &type, &len, &data, &ab, &off) != napi_ok || !data || type != napi_uint8_array) {
+    napi_is_typedarray(env, arr, &is_ta);
+    if (!is_ta || napi_get_typedarray_info(env, arr, &type, &len, &data, &ab, &off) != napi_ok || !data || type != napi_uint8_array) {
         napi_throw_type_error(env, NULL, staged ? "stageExr: Uint8Array expected" : "exrFrame: Uint8Array expected");
         return NULL;
     }
-    int ticket = 0;
-    int rc = staged ? rfx_stage_exr(c, &p, data, len, &ticket) : rfx_exr(c, &p, data, len);
-    if (rc) return throw_rfx(env, c, staged ? "rfx_stage_exr" : "rfx_exr", rc);
+    int ticket = 0, rc;
+    if (ex) {
+        rc = staged ? rfx_stage_exr_ex(c, &p, (unsigned)flags, data, len, &ticket) : rfx_exr_ex(c, &p, (unsigned)flags, data, len);
+        if (rc) return throw_rfx(env, c, staged ? "rfx_stage_exr_ex" : "rfx_exr_ex", rc);
+    } else {
+        rc = staged ? rfx_stage_exr(c, &p, data, len, &ticket) : rfx_exr(c, &p, data, len);
+        if (rc) return throw_rfx(env, c, staged ? "rfx_stage_exr" : "rfx_exr", rc);
+    }
     if (!staged) return NULL;
     NAPI_CALL(env, napi_create_int32(env, ticket, &out));
     return out;
 }
-static napi_value n_exr_frame(napi_env env, napi_callback_info info) { return exr_into(env, info, 0); }
-static napi_value n_stage_exr(napi_env env, napi_callback_info info) { return exr_into(env, info, 1); }
+static napi_value n_exr_frame(napi_env env, napi_callback_info info) { return exr_into(env, info, 0, 0); }
+static napi_value n_stage_exr(napi_env env, napi_callback_info info) { return exr_into(env, info, 1, 0); }
+static napi_value n_exr_frame_ex(napi_env env, napi_callback_info info) { return exr_into(env, info, 0, 1); }
+static napi_value n_stage_exr_ex(napi_env env, napi_callback_info info) { return exr_into(env, info, 1, 1); }
 /* exportWait(ctx, ticket): rfx_export_wait */
 static napi_value n_export_wait(napi_env env, napi_callback_info info) {
     napi_value a[2];
@@ -1217,6 +1237,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"exportBytes", n_export_bytes}, {"exportFrame", n_export_frame}, {"stageExport", n_stage_export}, {"exportWait", n_export_wait}, {"constants", n_constants},
         {"pngBound", n_png_bound}, {"pngFrame", n_png_frame}, {"stagePng", n_stage_png},
         {"exrBound", n_exr_bound}, {"exrFrame", n_exr_frame}, {"stageExr", n_stage_exr},
+        {"pngFrameEx", n_png_frame_ex}, {"stagePngEx", n_stage_png_ex}, {"exrFrameEx", n_exr_frame_ex}, {"stageExrEx", n_stage_exr_ex},
         {"splitRows", n_split_rows}, {"commUniqueId", n_comm_unique_id}, {"commInit", n_comm_init}, {"haloExchange", n_halo_exchange},
         {"allgatherHistory", n_allgather_history}, {"gatherHistoryRows", n_gather_history_rows}, {"commWait", n_comm_wait}, {"commDestroy", n_comm_destroy},
         {"peerExport", n_peer_export}, {"peerOpen", n_peer_open}, {"peerGatherHistory", n_peer_gather_history}, {"peerClose", n_peer_close}, {"ssgiHitMask", n_ssgi_hit_mask},

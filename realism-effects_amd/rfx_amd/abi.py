@@ -143,6 +143,7 @@ class ExrFrame(C.Structure):
 
 # rfx.h "EXR blocks": the descriptor of rfx_stage_exr_blocks — a block is a rectangle of the frame, a scanline chunk or a tile
 EXR_RLE, EXR_PXR24 = 1, 5
+ENCODE_MATCHES = 1  # rfx.h "Match form": the flags bit of rfx_stage_png_ex / rfx_png_ex / rfx_stage_exr_ex / rfx_exr_ex
 EXR_PIZ = 4  # rfx.h "EXR blocks with PIZ": taken by rfx_stage_exr_blocks_piz alone
 
 
@@ -187,6 +188,7 @@ EXPORTS = [
     "rfx_exr_aov_stage_bytes", "rfx_stage_exr_aov", "rfx_exr_aov_status",
     "rfx_exr_blocks_stage_bytes", "rfx_stage_exr_blocks",
     "rfx_exr_blocks_piz_stage_bytes", "rfx_stage_exr_blocks_piz",
+    "rfx_stage_png_ex", "rfx_png_ex", "rfx_stage_exr_ex", "rfx_exr_ex",
 ]
 
 _lib = None
@@ -311,6 +313,11 @@ def load_library(path: str | None = None) -> C.CDLL:
         lib.rfx_exr_blocks_piz_stage_bytes.argtypes = [vp, C.POINTER(ExrBlockFrame), i, i]
         lib.rfx_exr_blocks_piz_stage_bytes.restype = C.c_size_t
         lib.rfx_stage_exr_blocks_piz.argtypes = [vp, C.POINTER(ExrBlockFrame), i, i]
+    if hasattr(lib, "rfx_stage_png_ex"):  # (additive to ABI 21: Context.has_export_matches)
+        lib.rfx_stage_png_ex.argtypes = [vp, C.POINTER(ExportParams), i, C.c_uint, vp, C.c_size_t, C.POINTER(i)]
+        lib.rfx_png_ex.argtypes = [vp, C.POINTER(ExportParams), i, C.c_uint, vp, C.c_size_t]
+        lib.rfx_stage_exr_ex.argtypes = [vp, C.POINTER(ExportParams), C.c_uint, vp, C.c_size_t, C.POINTER(i)]
+        lib.rfx_exr_ex.argtypes = [vp, C.POINTER(ExportParams), C.c_uint, vp, C.c_size_t]
     if lib.rfx_abi_version() != RFX_ABI_VERSION:
         raise ImportError("librfx_hip.so ABI version %d != %d" % (lib.rfx_abi_version(), RFX_ABI_VERSION))
     if path is None:

@@ -335,6 +335,16 @@ class Context:
         self._chk(self.lib.rfx_export_wait(self._h, int(ticket)), "rfx_export_wait")
         self.__dict__.get("_export_keepalive", {}).pop(int(ticket), None)
 
+    # -- rfx.h "Match form": the device encode with run-length matches, per call (matches=True on png / stage_png / exr / stage_exr)
+    @property
+    def has_export_matches(self) -> bool:
+        """the library exports rfx_stage_png_ex and its three companions (additive to ABI 21)"""
+        return hasattr(self.lib, "rfx_stage_png_ex")
+
+    def _need_matches(self, what):
+        if not self.has_export_matches:
+            raise RuntimeError("%s(matches=True): this librfx_hip.so has no rfx_stage_png_ex (Context.has_export_matches)" % what)
+
     # -- PNG fragments (rfx.h "PNG fragments"): the same export, encoded on the device as the IDAT chunks of the tile rows
     def png_bound(self, channels: int = 3) -> int:
         """rfx_png_bound: the bytes of a result buffer (32-byte header + the fragment at its largest)"""
@@ -350,23 +360,32 @@ class Context:
             raise ValueError("%s: out must hold %d bytes of uint8, got %d of %s" % (what, n, out.nbytes, out.dtype))
         return out, n
 
-    def png(self, source: int, channels: int = 3, tonemap="linear", exposure: float = 1.0, filter=0, out=None) -> np.ndarray:
+    def png(self, source: int, channels: int = 3, tonemap="linear", exposure: float = 1.0, filter=0, out=None, matches: bool = False) -> np.ndarray:
         """rfx_png: the tile rows of `source` as a PNG fragment -> the result buffer (png_bound() bytes of uint8: header, fragment, slack);
         imageio.png_from_fragments wraps one or more of them into a file.  `filter`: "adaptive" / "none" / "sub" / "up" / "paeth" or 0..4.
-        Blocks until the bytes are there."""
+        matches=True: rfx_png_ex with RFX_ENCODE_MATCHES (rfx.h "Match form").  Blocks until the bytes are there."""
         p = self.export_params(source, "u8_srgb", channels, tonemap, exposure)
         out, n = self._png_out(p, out, "png")
+        if matches:
+            self._need_matches("png")
+            self._chk(self.lib.rfx_png_ex(self._h, C.byref(p), int(abi.PNG_FILTERS.get(filter, filter)), abi.ENCODE_MATCHES, out.ctypes.data_as(C.c_void_p), n),
+                      "rfx_png_ex")
+            return out
         self._chk(self.lib.rfx_png(self._h, C.byref(p), int(abi.PNG_FILTERS.get(filter, filter)), out.ctypes.data_as(C.c_void_p), n), "rfx_png")
         return out
 
-    def stage_png(self, source: int, channels: int = 3, tonemap="linear", exposure: float = 1.0, filter=0, *, out: np.ndarray) -> int:
+    def stage_png(self, source: int, channels: int = 3, tonemap="linear", exposure: float = 1.0, filter=0, *, out: np.ndarray, matches: bool = False) -> int:
         """rfx_stage_png: stage_export's contract with a PNG fragment as the payload; the ticket is one of the same sequence and
-        export_wait(ticket) retires it."""
+        export_wait(ticket) retires it.  matches=True: rfx_stage_png_ex with RFX_ENCODE_MATCHES."""
         p = self.export_params(source, "u8_srgb", channels, tonemap, exposure)
         out, n = self._png_out(p, out, "stage_png")
         t = C.c_int(0)
-        self._chk(self.lib.rfx_stage_png(self._h, C.byref(p), int(abi.PNG_FILTERS.get(filter, filter)), out.ctypes.data_as(C.c_void_p), n, C.byref(t)),
-                  "rfx_stage_png")
+        f = int(abi.PNG_FILTERS.get(filter, filter))
+        if matches:
+            self._need_matches("stage_png")
+            self._chk(self.lib.rfx_stage_png_ex(self._h, C.byref(p), f, abi.ENCODE_MATCHES, out.ctypes.data_as(C.c_void_p), n, C.byref(t)), "rfx_stage_png_ex")
+        else:
+            self._chk(self.lib.rfx_stage_png(self._h, C.byref(p), f, out.ctypes.data_as(C.c_void_p), n, C.byref(t)), "rfx_stage_png")
         keep = self.__dict__.setdefault("_export_keepalive", {})
         keep[t.value] = out
         for old in [k for k in keep if k <= t.value - 2]:
@@ -388,21 +407,30 @@ class Context:
             raise ValueError("%s: out must hold %d bytes of uint8, got %d of %s" % (what, n, out.nbytes, out.dtype))
         return out, n
 
-    def exr(self, source: int, channels: int = 4, out=None) -> np.ndarray:
+    def exr(self, source: int, channels: int = 4, out=None, matches: bool = False) -> np.ndarray:
         """rfx_exr: the tile rows of `source` as an EXR fragment -> the result buffer (exr_bound() bytes of uint8: header, fragment, slack);
-        imageio.exr_from_fragments wraps one or more of them into a file.  Blocks until the bytes are there."""
+        imageio.exr_from_fragments wraps one or more of them into a file.  matches=True: rfx_exr_ex with RFX_ENCODE_MATCHES (rfx.h "Match form").
+        Blocks until the bytes are there."""
         p = self.export_params(source, "f16", channels)
         out, n = self._exr_out(p, out, "exr")
+        if matches:
+            self._need_matches("exr")
+            self._chk(self.lib.rfx_exr_ex(self._h, C.byref(p), abi.ENCODE_MATCHES, out.ctypes.data_as(C.c_void_p), n), "rfx_exr_ex")
+            return out
         self._chk(self.lib.rfx_exr(self._h, C.byref(p), out.ctypes.data_as(C.c_void_p), n), "rfx_exr")
         return out
 
-    def stage_exr(self, source: int, channels: int = 4, *, out: np.ndarray) -> int:
+    def stage_exr(self, source: int, channels: int = 4, *, out: np.ndarray, matches: bool = False) -> int:
         """rfx_stage_exr: stage_export's contract with an EXR fragment as the payload; the ticket is one of the same sequence and
-        export_wait(ticket) retires it."""
+        export_wait(ticket) retires it.  matches=True: rfx_stage_exr_ex with RFX_ENCODE_MATCHES."""
         p = self.export_params(source, "f16", channels)
         out, n = self._exr_out(p, out, "stage_exr")
         t = C.c_int(0)
-        self._chk(self.lib.rfx_stage_exr(self._h, C.byref(p), out.ctypes.data_as(C.c_void_p), n, C.byref(t)), "rfx_stage_exr")
+        if matches:
+            self._need_matches("stage_exr")
+            self._chk(self.lib.rfx_stage_exr_ex(self._h, C.byref(p), abi.ENCODE_MATCHES, out.ctypes.data_as(C.c_void_p), n, C.byref(t)), "rfx_stage_exr_ex")
+        else:
+            self._chk(self.lib.rfx_stage_exr(self._h, C.byref(p), out.ctypes.data_as(C.c_void_p), n, C.byref(t)), "rfx_stage_exr")
         keep = self.__dict__.setdefault("_export_keepalive", {})
         keep[t.value] = out
         for old in [k for k in keep if k <= t.value - 2]:

@@ -7,7 +7,10 @@ then waits for the PREVIOUS frame's ticket — which has had this frame's draws 
 exports are in flight; finish() waits for the last one.
 
 compression="zips" (exr only; default "none"): the frame leaves the device as finished ZIPS chunks (Context.stage_exr, include/rfx.h "EXR
-fragments") and the host only wraps them; "none" is the uncompressed file written from the staged halfs."""
+fragments") and the host only wraps them; "none" is the uncompressed file written from the staged halfs.
+
+matches=True (with encode="device" or compression="zips" only): the device encode with run-length matches (include/rfx.h "Match form"); the
+files are smaller where pixels repeat exactly and wrap the same way."""
 from __future__ import annotations
 
 import os
@@ -21,7 +24,7 @@ FRAME_FORMATS = {"png": ("u8_srgb", 3), "exr": ("f16", 4), "pfm": ("f32", 3)}
 
 class FrameExporter:
     def __init__(self, ctx, directory: str, format: str = "png", tonemap: str = "aces", exposure: float = 1.0, write=None, encode: str = "host",
-                 filter="adaptive", compression: str = "none"):
+                 filter="adaptive", compression: str = "none", matches: bool = False):
         if format not in FRAME_FORMATS:
             raise ValueError('format: "png", "exr" or "pfm"')
         if encode not in ("host", "device"):
@@ -32,7 +35,11 @@ class FrameExporter:
             raise ValueError('compression: "none" or "zips"')
         if compression == "zips" and format != "exr":
             raise ValueError('compression "zips" is for format "exr" only')
-        self.encode, self.filter, self.compression = encode, filter, compression
+        if matches and encode != "device" and compression != "zips":
+            raise ValueError('matches is for encode "device" or compression "zips" only')
+        if matches and not ctx.has_export_matches:
+            raise ValueError("matches: this librfx_hip.so has no rfx_stage_png_ex (Context.has_export_matches)")
+        self.encode, self.filter, self.compression, self.matches = encode, filter, compression, bool(matches)
         self.ctx, self.dir, self.format = ctx, directory, format
         self.kind, self.channels = FRAME_FORMATS[format]
         u8 = self.kind == "u8_srgb"
@@ -66,13 +73,16 @@ class FrameExporter:
         index, self.count = self.count, self.count + 1
         buf = self.buffers[index & 1]
         if self.encode == "device":
-            ticket = self.ctx.stage_png(source, self.channels, self.tonemap, self.exposure, self.filter, out=buf)
+            ticket = self.ctx.stage_png(source, self.channels, self.tonemap, self.exposure, self.filter, out=buf, **self._matches_kw())
         elif self.compression == "zips":
-            ticket = self.ctx.stage_exr(source, self.channels, out=buf)
+            ticket = self.ctx.stage_exr(source, self.channels, out=buf, **self._matches_kw())
         else:
             ticket = self.ctx.stage_export(source, self.kind, self.channels, self.tonemap, self.exposure, out=buf)
         self._retire()
         self.pending = (ticket, index, buf)
+
+    def _matches_kw(self):
+        return {"matches": True} if self.matches else {}  # (off: the call as it was, for a ctx that predates the keyword)
 
     def _retire(self):
         if self.pending is None:

@@ -1,0 +1,148 @@
+"""GPU (-m gpu; also under --hostsim): K8's PNG fragment with run-length matches (rfx_png_ex / rfx_stage_png_ex with RFX_ENCODE_MATCHES; the
+kernel: csrc/k8_match.h k8_png_rows_m).  For every case of tests/match_cases.py the result buffer, header included, must be byte-identical to the
+restatement's (tests/match_device_ref.py) of the bytes ctx.export returns; flags = 0 through the _ex calls must be the old calls' bytes."""
+import ctypes as C
+import struct
+
+import numpy as np
+import pytest
+
+import match_cases as K
+import match_device_ref as M
+import png_device_ref as R
+from rfx_amd import abi
+from rfx_amd.context import Context
+from test_gpu_exr_device import plane_of
+from test_gpu_png import SRC, decode, plant
+
+pytestmark = pytest.mark.gpu
+
+
+def encode(ctx, ch, filt, flags):
+    """rfx_png_ex, called for itself: no look at whether the library has it"""
+    p = ctx.export_params(SRC, "u8_srgb", ch)
+    out = np.zeros(ctx.png_bound(ch), np.uint8)
+    rc = ctx.lib.rfx_png_ex(ctx._h, C.byref(p), filt, flags, out.ctypes.data_as(C.c_void_p), out.nbytes)
+    assert rc == abi.RFX_OK, ctx.lib.rfx_last_error(ctx._h).decode()
+    return out
+
+
+def check(ctx, img, filt):
+    """the planted img: matches on against the restatement, flags = 0 and Context.png(matches=True) against their twins -> the result buffer"""
+    H, W, ch = img.shape
+    assert np.array_equal(ctx.export(SRC, "u8_srgb", ch), img)
+    got = encode(ctx, ch, filt, abi.ENCODE_MATCHES)
+    want = M.result_prefix_png(img, filt)
+    n = struct.unpack("<Q", got[:8].tobytes())[0]
+    assert 32 + n <= got.nbytes == R.bound(W, H, ch)
+    assert got[:32].tobytes() == want[:32], (M.png_header_of(got), M.png_header_of(want))
+    assert got[:32 + n].tobytes() == want
+    off = encode(ctx, ch, filt, 0)
+    old = ctx.png(SRC, ch, filter=filt)
+    n0 = struct.unpack("<Q", old[:8].tobytes())[0]
+    assert off[:32 + n0].tobytes() == old[:32 + n0].tobytes() == R.result_prefix(img, filt) and M.png_header_of(off)[4:] == (0, 0)
+    assert n <= n0
+    assert ctx.png(SRC, ch, filter=filt, matches=True)[:32 + n].tobytes() == want
+    return got
+
+
+@pytest.mark.parametrize("name", sorted(K.PNG_CASES))
+def test_result_buffer_equals_the_restatement(name, tmp_path):
+    img, filt = K.png_case(name)
+    H, W, ch = img.shape
+    ctx = Context(W, H)
+    ctx.upload(SRC, plant(img))
+    got = check(ctx, img, filt)
+    ctx.close()
+    assert np.array_equal(decode(tmp_path, W, H, ch, [got]), img)
+
+
+def test_three_row_tiles_stitch(tmp_path):
+    W, H, halo = 97, 55, 2
+    img, filt = K.png_case("half_flat_97x55")
+    a = plant(img)
+    results = []
+    for rank in (2, 1, 0):  # top tile first
+        y0, n = Context.split_rows(H, 3, rank)
+        t = Context(W, H, tile_y0=y0, tile_rows=n, halo_rows=halo)
+        r0, rn = t.held_rows(SRC)
+        t.upload(SRC, a[r0:r0 + rn])
+        results.append(check(t, img[y0:y0 + n], filt).copy())
+        t.close()
+    assert sum(M.png_header_of(r)[4] for r in results) > 0
+    assert np.array_equal(decode(tmp_path, W, H, 3, results), img)
+
+
+def test_staged_in_the_mixed_ticket_sequence():
+    """six frames: stage_export, stage_png and stage_exr with and without matches share the tickets, the two staging buffers and the back pressure"""
+    W, H = 97, 55
+    ctx = Context(W, H)
+    plan = [("png", 3, True), ("u8", 4, None), ("png", 4, False), ("exr", 4, True), ("png", 4, True), ("exr", 3, False)]
+    outs, tickets, wants = [], [], []
+    for i, (kind, ch, matches) in enumerate(plan):
+        if kind == "exr":
+            halfs = K.half_flat_halfs(W, H, ch, seed=60 + i)
+            ctx.upload(SRC, plane_of(halfs))  # (widening is exact: the F16 export is `halfs`)
+            out = ctx.host_alloc((ctx.exr_bound(ch),), np.uint8)
+            t = ctx.stage_exr(SRC, ch, out=out, matches=matches)
+            wants.append(M.result_prefix_exr(halfs, 0, matches))
+        else:
+            img = K.half_flat_bytes(W, H, ch, seed=60 + i)
+            ctx.upload(SRC, plant(img))
+            if kind == "png":
+                out = ctx.host_alloc((ctx.png_bound(ch),), np.uint8)
+                t = ctx.stage_png(SRC, ch, filter=0, out=out, matches=matches)
+                wants.append(M.result_prefix_png(img, 0, matches))
+            else:
+                out = ctx.host_alloc((H, W, ch), np.uint8)
+                t = ctx.stage_export(SRC, "u8_srgb", ch, out=out)
+                wants.append(img.tobytes())
+        outs.append(out)
+        tickets.append(t)
+        assert t == tickets[0] + i
+        if i:
+            ctx.export_wait(tickets[i - 1])  # one frame late
+    ctx.export_wait(tickets[-1])
+    for i, want in enumerate(wants):
+        assert outs[i].reshape(-1)[:len(want)].tobytes() == want, i
+    ctx.close()
+
+
+def test_refusals():
+    W, H = 16, 8
+    ctx = Context(W, H)
+    ctx.upload(SRC, np.zeros((H, W, 4), np.float32))
+    p = ctx.export_params(SRC, "u8_srgb", 3)
+    bound = ctx.png_bound(3)
+    buf = np.zeros(bound, np.uint8)
+    ptr = buf.ctypes.data_as(C.c_void_p)
+    t = C.c_int(0)
+    for flags in (2, 3, 0x80000000):
+        assert ctx.lib.rfx_png_ex(ctx._h, C.byref(p), 0, flags, ptr, bound) == abi.RFX_EINVAL
+        msg = ctx.lib.rfx_last_error(ctx._h).decode()
+        assert msg.startswith("rfx_png_ex:") and "flags" in msg, msg
+        assert ctx.lib.rfx_stage_png_ex(ctx._h, C.byref(p), 0, flags, ptr, bound, C.byref(t)) == abi.RFX_EINVAL
+        assert ctx.lib.rfx_last_error(ctx._h).decode().startswith("rfx_stage_png_ex:")
+    assert ctx.lib.rfx_png_ex(ctx._h, C.byref(p), 5, 1, ptr, bound) == abi.RFX_EINVAL and "filter" in ctx.lib.rfx_last_error(ctx._h).decode()
+    assert ctx.lib.rfx_png_ex(ctx._h, C.byref(p), 0, 1, ptr, bound - 1) == abi.RFX_EINVAL and "rfx_png_bound" in ctx.lib.rfx_last_error(ctx._h).decode()
+    assert ctx.lib.rfx_stage_png_ex(ctx._h, C.byref(p), 0, 1, ptr, bound, None) == abi.RFX_EINVAL
+    f16 = ctx.export_params(SRC, "f16", 3)
+    assert ctx.lib.rfx_png_ex(ctx._h, C.byref(f16), 0, 1, ptr, bound) == abi.RFX_EINVAL
+    assert ctx.lib.rfx_png_ex(ctx._h, C.byref(p), 0, 1, ptr, bound) == abi.RFX_OK
+    assert ctx.has_export_matches
+    ctx.close()
+
+
+def test_the_match_encode_is_profiled():
+    W, H = 97, 55
+    img, filt = K.png_case("half_flat_97x55")
+    ctx = Context(W, H)
+    ctx.upload(SRC, plant(img))
+    ctx.profile(True)
+    ctx.png(SRC, 3, matches=True)
+    ctx.png(SRC, 3)
+    ctx.profile(False)
+    prof = ctx.profile_read()
+    assert list(prof) == ["k7_export", "k8_png"]
+    assert prof["k8_png"][1] == 2 and prof["k8_png"][0] >= 0.0 and prof["k7_export"][1] == 2
+    ctx.close()

@@ -25,6 +25,16 @@ read and write; the fragment's size per frame is recorded with K8's.
         imageio.exr_from_fragments and written to /dev/null: FrameExporter("exr", compression="zips")
 
 and the EXR encode alone (rfx_profile, kind K8) next to the PNG encode measured in the same process.
+
+--modes matches measures the device encode with run-length matches (rfx.h "Match form") against the one without, by the same protocol (T0, T3,
+E3 and the two modes below in alternating rounds), and ADDS its results to --out under the key "matches":
+
+    T3m  T3 with stage_png(matches=True)
+    E3m  E3 with stage_exr(matches=True)
+
+and the encode alone (rfx_profile, kind K8) for PNG and EXR with matches off and on, three alternating rounds of 20 launches each, so that the
+spread from round to round stands next to the difference; the fragment bytes of the same frame off and on, and that frame through the host's
+ZIPS writer.
 """
 import argparse
 import copy
@@ -49,6 +59,7 @@ W, H = 3840, 2160
 HBM_PEAK = 8e12  # bytes / s
 MODES = ("T0", "T1", "T2", "T2h", "T3")
 EXR_MODES = ("T0", "E1", "E2", "E3")
+MATCH_MODES = ("T0", "T3", "T3m", "E3", "E3m")
 WARM = {"T2h": (1, 2), "E1": (1, 3), "E2": (1, 2)}   # frames of the two warming loops (default 5 and 20)
 MIN_FRAMES = {"T2h": 3, "E1": 5, "E2": 3}            # ... and the fewest of a measured loop (default 20)
 
@@ -75,6 +86,7 @@ class Run:
         self.png = [ctx.host_alloc((ctx.png_bound(3),), np.uint8) for _ in range(2)]
         self.fragment_bytes = []
         self.f16, self.exr, self.exr_file_bytes = None, None, []
+        self.match_file_bytes = {}
 
     def alloc_exr(self):
         self.f16 = [self.ctx.host_alloc((H, W, 4), np.float16) for _ in range(2)]
@@ -84,16 +96,16 @@ class Run:
         """what the host does with a waited frame"""
         if mode == "T2h":
             imageio.write_png(os.devnull, buf)
-        elif mode == "T3":
+        elif mode in ("T3", "T3m"):
             data = imageio.png_from_fragments(W, H, 3, [buf])
-            self.fragment_bytes.append(len(data))
+            (self.fragment_bytes if mode == "T3" else self.match_file_bytes.setdefault(mode, [])).append(len(data))
             with open(os.devnull, "wb") as f:
                 f.write(data)
         elif mode in ("E1", "E2"):
             imageio.write_exr(os.devnull, {n: buf[..., k] for k, n in enumerate("RGBA")}, compression="none" if mode == "E1" else "zips", half=True)
-        elif mode == "E3":
+        elif mode in ("E3", "E3m"):
             data = imageio.exr_from_fragments(W, H, 4, [buf])
-            self.exr_file_bytes.append(len(data))
+            (self.exr_file_bytes if mode == "E3" else self.match_file_bytes.setdefault(mode, [])).append(len(data))
             with open(os.devnull, "wb") as f:
                 f.write(data)
 
@@ -122,16 +134,16 @@ class Run:
             self.frame(cur)
             if mode == "T1":
                 ctx._chk(ctx.lib.rfx_download(ctx._h, abi.TEX_FINAL, self.final.ctypes.data_as(C.c_void_p), 0, H), "rfx_download")
-            elif mode in ("T2", "T2h", "T3", "E1", "E2", "E3"):
-                if mode == "E3":
+            elif mode in ("T2", "T2h", "T3", "T3m", "E1", "E2", "E3", "E3m"):
+                if mode in ("E3", "E3m"):
                     buf = self.exr[i & 1]
-                    t = ctx.stage_exr(abi.TEX_FINAL, 4, out=buf)
+                    t = ctx.stage_exr(abi.TEX_FINAL, 4, out=buf, matches=mode == "E3m")
                 elif mode in ("E1", "E2"):
                     buf = self.f16[i & 1]
                     t = ctx.stage_export(abi.TEX_FINAL, "f16", 4, out=buf)
-                elif mode == "T3":
+                elif mode in ("T3", "T3m"):
                     buf = self.png[i & 1]
-                    t = ctx.stage_png(abi.TEX_FINAL, 3, "aces", 1.0, out=buf)
+                    t = ctx.stage_png(abi.TEX_FINAL, 3, "aces", 1.0, out=buf, matches=mode == "T3m")
                 else:
                     buf = self.u8[i & 1]
                     t = ctx.stage_export(abi.TEX_FINAL, "u8_srgb", 3, "aces", 1.0, out=buf)
@@ -227,19 +239,102 @@ def main_exr(run, a):
         f.write("\n")
 
 
+def main_matches(run, a):
+    """--modes matches: T0 / T3 / T3m / E3 / E3m and the two encodes alone with matches off and on, merged into the file under the key "matches" """
+    import struct
+    import tempfile
+    run.alloc_exr()
+    ctx = run.ctx
+    result = dict(width=W, height=H, seed=a.seed, seconds=a.seconds, rounds={}, frames={})
+    for streamed in (False, True):
+        key = "streamed" if streamed else "resident"
+        n = {}
+        for mode in MATCH_MODES:
+            run.loop(mode, streamed, 5)
+            per = run.loop(mode, streamed, 20) / 20
+            n[mode] = max(20, int(math.ceil(a.seconds / per)))
+        rounds = []
+        for r in range(3):
+            row = {}
+            for mode in MATCH_MODES:
+                row[mode] = round(run.loop(mode, streamed, n[mode]) / n[mode] * 1e3, 4)
+            row["T3m_minus_T3"] = round(row["T3m"] - row["T3"], 4)
+            row["E3m_minus_E3"] = round(row["E3m"] - row["E3"], 4)
+            rounds.append(row)
+            print(key, json.dumps(row), flush=True)
+        result["rounds"][key] = rounds
+        result["frames"][key] = n
+    # the encodes alone, inside loops of staged fragments of ONE frame: off and on alternate, three rounds, so the spread is on record
+    def stage(kind, matches, buf):
+        if kind == "png":
+            return ctx.stage_png(abi.TEX_FINAL, 3, "aces", 1.0, out=buf, matches=matches)
+        return ctx.stage_exr(abi.TEX_FINAL, 4, out=buf, matches=matches)
+
+    alone = {}
+    for kind, bufs in (("png", run.png), ("exr", run.exr)):
+        for matches in (False, True):
+            for _ in range(5):
+                ctx.export_wait(stage(kind, matches, bufs[0]))
+    for r in range(3):
+        for kind, bufs in (("png", run.png), ("exr", run.exr)):
+            for matches in (False, True):
+                ctx.sync()
+                ctx.profile(True)
+                for i in range(20):
+                    ctx.export_wait(stage(kind, matches, bufs[i & 1]))
+                ms, launches = ctx.profile_read()["k8_png"]
+                ctx.profile(False)
+                alone.setdefault("%s_%s" % (kind, "on" if matches else "off"), []).append(round(ms / launches, 5))
+    for k, v in alone.items():
+        result["k8_" + k] = dict(ms_rounds=v, ms=round(sorted(v)[1], 5), spread=round(max(v) - min(v), 5), launches_per_round=20)
+    print(json.dumps({k: v for k, v in result.items() if k.startswith("k8_")}), flush=True)
+    # the fragments of that frame, off and on; the same frame through the host's ZIPS writer (outside every clock)
+    sizes = {}
+    for matches in (False, True):
+        head = struct.unpack("<QIIQII", ctx.png(abi.TEX_FINAL, 3, "aces", 1.0, matches=matches)[:32].tobytes())
+        sizes["png_on" if matches else "png_off"] = dict(fragment=head[0], raw=head[3], fragment_of_raw=round(head[0] / head[3], 4), match_form_chunks=head[4], chunks=H)
+        head = struct.unpack("<QIIQII", ctx.exr(abi.TEX_FINAL, 4, matches=matches)[:32].tobytes())
+        sizes["exr_on" if matches else "exr_off"] = dict(fragment=head[0], raw=head[3], fragment_of_raw=round(head[0] / head[3], 4), raw_form_chunks=head[4],
+                                                         match_form_chunks=head[5], chunks=head[1])
+    halfs = ctx.export(abi.TEX_FINAL, "f16", 4)
+    with tempfile.TemporaryDirectory() as d:
+        path = os.path.join(d, "host_zips.exr")
+        imageio.write_exr(path, {n: halfs[..., k] for k, n in enumerate("RGBA")}, compression="zips", half=True)
+        sizes["exr_same_frame_host_zips_level4_file"] = os.path.getsize(path)
+    result["same_frame"] = sizes
+    result["file_bytes_per_frame"] = {m: dict(min=min(v), max=max(v), frames=len(v)) for m, v in run.match_file_bytes.items()}
+    result["file_bytes_per_frame"]["T3"] = dict(min=min(run.fragment_bytes), max=max(run.fragment_bytes), frames=len(run.fragment_bytes))
+    result["file_bytes_per_frame"]["E3"] = dict(min=min(run.exr_file_bytes), max=max(run.exr_file_bytes), frames=len(run.exr_file_bytes))
+    print(json.dumps(result["same_frame"]), flush=True)
+    print(json.dumps(result["file_bytes_per_frame"]), flush=True)
+    ctx.close()
+    merged = {}
+    if os.path.exists(a.out):
+        with open(a.out) as f:
+            merged = json.load(f)
+    merged["matches"] = result
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(merged, f, indent=1)
+        f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "export", "rates.json"))
     ap.add_argument("--seconds", type=float, default=1.0, help="steady state per measurement, at least")
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--size", default="3840x2160", help="frame size (the committed numbers are 4K; a small size checks the script itself)")
-    ap.add_argument("--modes", default="png", choices=("png", "exr"), help='"exr": T0 / E1 / E2 / E3, added to --out under "exr"')
+    ap.add_argument("--modes", default="png", choices=("png", "exr", "matches"),
+                    help='"exr": T0 / E1 / E2 / E3, added to --out under "exr"; "matches": T0 / T3 / T3m / E3 / E3m, added under "matches"')
     a = ap.parse_args()
     global W, H
     W, H = (int(v) for v in a.size.split("x"))
     run = Run(a.seed)
     if a.modes == "exr":
         return main_exr(run, a)
+    if a.modes == "matches":
+        return main_matches(run, a)
     result = dict(width=W, height=H, seed=a.seed, seconds=a.seconds, rounds={}, frames={})
     for streamed in (False, True):
         key = "streamed" if streamed else "resident"
