@@ -12,6 +12,8 @@ import pytest
 
 from rfx_amd import imageio
 
+from piz_cases import GAPS, SKEW, Bits, huffman_block, table_bits
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "realism-effects_amd", "csrc")
 K9_OK = 0
@@ -134,83 +136,7 @@ def test_blocks_of_the_writer_equal_the_host_decode(driver, tmp_path):
         assert code == K9_OK and (got == imageio._huf_uncompress(s, n)).all(), name
 
 
-# ---------------------------------------------------------------- hand-made Huffman blocks
-class Bits:
-    """the test's own bit writer: MSB first"""
-
-    def __init__(self):
-        self.bits = []
-
-    def put(self, n, v):
-        assert 0 <= v < (1 << n)
-        self.bits += [(v >> (n - 1 - k)) & 1 for k in range(n)]
-        return self
-
-    def bytes(self):
-        b = self.bits + [0] * (-len(self.bits) % 8)
-        return bytes(int("".join(map(str, b[i:i + 8])), 2) for i in range(0, len(b), 8))
-
-
-def canonical(lengths):
-    """{symbol: length} -> {symbol: code}: ascending within a length, longer codes first"""
-    count = [0] * 60
-    for ln in lengths.values():
-        count[ln] += 1
-    start, c = [0] * 60, 0
-    for ln in range(58, 0, -1):
-        start[ln] = c
-        c = (c + count[ln]) >> 1
-    codes, nxt = {}, list(start)
-    for s in sorted(lengths):
-        codes[s] = nxt[lengths[s]]
-        nxt[lengths[s]] += 1
-    full = np.zeros(imageio._HUF_ENCSIZE, np.int64)
-    for s, ln in lengths.items():
-        full[s] = ln
-    theirs = imageio._huf_canonical(full)
-    assert all(int(theirs[s]) == codes[s] for s in lengths)
-    return codes
-
-
-def table_bits(lengths, im, iM):
-    """the packed length table of symbols im .. iM, zero runs collapsed as the format allows"""
-    t, i = Bits(), im
-    while i <= iM:
-        if i in lengths:
-            t.put(6, lengths[i])
-            i += 1
-            continue
-        run = 1
-        while i + run <= iM and (i + run) not in lengths and run < 261:
-            run += 1
-        if run >= 6:
-            t.put(6, 63).put(8, run - 6)
-        elif run >= 2:
-            t.put(6, 59 + run - 2)
-        else:
-            t.put(6, 0)
-        i += run
-    return t
-
-
-def huffman_block(lengths, im, iM, stream, table=None, nbits=None, tlen=None):
-    """stream: [symbol | ("run", count)] -> the Huffman block"""
-    codes = canonical(lengths)
-    d = Bits()
-    for s in stream:
-        if isinstance(s, tuple):
-            d.put(lengths[iM], codes[iM]).put(8, s[1])
-        else:
-            d.put(lengths[s], codes[s])
-    t = (table or table_bits(lengths, im, iM)).bytes()
-    return struct.pack("<IIIII", im, iM, len(t) if tlen is None else tlen, len(d.bits) if nbits is None else nbits, 0) + t + d.bytes()
-
-
-SKEW = {s: s + 1 for s in range(58)}  # lengths 1 .. 58, and the run escape 58 bits too: a complete set
-SKEW[58] = 58
-GAPS = {0: 2, 4: 2, 105: 2, 300: 2}  # 3, 100 and 194 symbols without a code between them: the short and the long zero run
-
-
+# ---------------------------------------------------------------- hand-made Huffman blocks (the bit writer and the blocks: tests/piz_cases.py)
 def test_handmade_huffman_blocks(driver, tmp_path):
     tb = table_bits(GAPS, 0, 300).bits
     assert len(tb) == 6 * 4 + 6 + 2 * 14  # (one short escape, two long ones)
