@@ -516,7 +516,7 @@ RFX_DEV void k1_ssgi_march_body(const K1Args &A, const FrameDims &d, const k1_ce
 
     // vUv of the (possibly smaller, resolutionScale) render target; the full-resolution inputs are fetched NEAREST at vUv.  y is a row of that
     // target: a row tile draws its rows [j0, j1) (rfx_launch.h rfx_scaled_rows) into the start of its slot, and the host hands `out.ptr` and `hits`
-    // over rebased by j0 rows (k1_args in rfx_api.hip), so that row y sits at y * out_w here whatever the tile
+    // over rebased by j0 rows (k1_args in rfx_draw.hip), so that row y sits at y * out_w here whatever the tile
     const bool scaled = A.out_w != d.W || A.out_h != d.H;
     const float u = rfx_frag_u(A.out_uv, x, y), v = rfx_frag_v(A.out_uv, y);
     const int sx = scaled ? rfx_nearest_idx(u, d.fW, d.W) : x, sy = scaled ? rfx_nearest_idx(v, d.fH, d.H) : y;

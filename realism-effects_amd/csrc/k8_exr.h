@@ -1,5 +1,5 @@
 // k8_exr.h — K8's second pre-transform: the EXR fragment of include/rfx.h "EXR fragments" (ZIPS chunks, one per scanline), encoded on the device
-// from K7's staged F16 stream.  Included by k0_import.hip behind k8_png.h, whose coder it shares unchanged: k8_build_code, the header tokens,
+// from K7's staged F16 stream.  Included by k7_export.hip behind k8_png.h, whose coder it shares unchanged: k8_build_code, the header tokens,
 // the bit window, the wave helpers, k8_png_gather.  All of it is integer arithmetic: the fragment is a pure function of the staged halfs.
 //
 //   k8_exr_planes  one lane per pixel: K7's pixel-interleaved halfs -> the scanline's `t` bytes (every channel's low bytes in alphabetical

@@ -1,4 +1,4 @@
-// k8_match.h — K8 with run-length matches: form (c) of include/rfx.h "Match form", for both fragment kinds.  Included by k0_import.hip behind
+// k8_match.h — K8 with run-length matches: form (c) of include/rfx.h "Match form", for both fragment kinds.  Included by k7_export.hip behind
 // k8_exr.h.  The literal-only kernels k8_png_rows / k8_exr_rows are not touched: these are second kernels the launchers select when the call
 // asked for matches, and they share k8_build_code, the bit window, the wave helpers, the filter stage, the scans and the gather.
 //

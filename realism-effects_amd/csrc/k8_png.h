@@ -1,5 +1,5 @@
 // k8_png.h — K8: the PNG fragment of include/rfx.h "PNG fragments", encoded on the device from K7's staged U8 stream.  Included by
-// k0_import.hip (one translation unit with K7).  All of it is integer arithmetic: the fragment is a pure function of the input bytes.
+// k7_export.hip (one translation unit with K7).  All of it is integer arithmetic: the fragment is a pure function of the input bytes.
 //
 //   k8_png_rows    one wave (a workgroup of 64 lanes) per scanline: filter choice, histogram, code lengths, block header, bit packing into
 //                  the scanline's slot of a scratch buffer (a whole chunk: length, "IDAT", payload, CRC-32), Adler partial sums

@@ -1,5 +1,5 @@
-// rfx_ctx.h — the context object behind the opaque rfx_ctx handle, shared by rfx_api.hip (slots, draws) and rfx_comm.hip
-// (RCCL exchanges of a row-tiled run).  Private to librfx_hip.so.
+// rfx_ctx.h — the context object behind the opaque rfx_ctx handle, shared by the host files of the C ABI (through rfx_host.h: slots, uploads,
+// draws, export) and by rfx_comm.hip / rfx_peer.hip (the exchanges of a row-tiled run).  Private to librfx_hip.so.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -127,12 +127,12 @@ int rfx_ensure_streams(rfx_ctx *c);
 int rfx_comm_begin(rfx_ctx *c);
 int rfx_comm_end(rfx_ctx *c);
 void rfx_peer_release(rfx_ctx *c);  // rfx_peer.hip: called by rfx_destroy (before rfx_comm_release: it drains the exchange stream)
-// rfx_api.hip, for rfx_comm.hip / rfx_peer.hip: enqueue on the draw stream the reduction of the traced rays' row masks into the first H words
+// rfx_draw.hip, for rfx_comm.hip / rfx_peer.hip: enqueue on the draw stream the reduction of the traced rays' row masks into the first H words
 // of c->hit_mask_dev (allocated here for `ranks` gathered copies)
 extern "C" int rfx_internal_hit_mask_enqueue(rfx_ctx *c, int ranks);  // (internal: not part of include/rfx.h)
-// ... and of the texels a row-tiled rfx_motion_blur with these (validated) params will load, in the same words
+// ... and (rfx_blur.hip) of the texels a row-tiled rfx_motion_blur with these (validated) params will load, in the same words
 extern "C" int rfx_internal_blur_reach_enqueue(rfx_ctx *c, const rfx_motion_blur_params *p, int ranks);
-// ... and, for the CPU tests: the launch plans of rfx_launch.h as the library computes them (K1's table layout, K3's tile geometry)
+// ... and (rfx_draw.hip), for the CPU tests: the launch plans of rfx_launch.h as the library computes them (K1's table layout, K3's tile geometry)
 extern "C" int rfx_internal_k1_table(int W, int H, struct rfx_k1_table_plan *out);
 extern "C" int rfx_internal_scaled_rows(int W, int H, int Hs, int uv_model, int y0, int y1, int apron, int *j0, int *j1);
 extern "C" int rfx_internal_export_plan(int pixels, int format, int channels, struct rfx_export_plan *out);

@@ -21,7 +21,7 @@ struct K0AovArgs {
     int groups, tail_start, tail_pixels;  // lanes [0, groups) own four pixels each; lane `groups` the tail
 };
 hipError_t rfx_launch_k0_aov(const K0AovArgs &, int blocks, hipStream_t);
-// CubeToEquirectEnvPass (k0_import.hip): six S x S RGBA32F faces -> a W x H RGBA32F equirectangular image
+// CubeToEquirectEnvPass (k0_cube.hip): six S x S RGBA32F faces -> a W x H RGBA32F equirectangular image
 hipError_t rfx_launch_cube_to_equirect(float4 *chain, int size, int levels, float4 *out, int W, int H, const UvPlanes &uv, hipStream_t);
 
 struct K1Args {
@@ -125,7 +125,7 @@ struct K5Args {
 };
 hipError_t rfx_launch_k5(const K5Args &, hipStream_t);
 
-// K6 (k4_compose.hip): MotionBlurEffect.  The whole-frame launch addresses every plane by frame row; the row-tiled launch (tiled != 0) reads
+// K6 (k6_motion_blur.hip): MotionBlurEffect.  The whole-frame launch addresses every plane by frame row; the row-tiled launch (tiled != 0) reads
 // velocity and an explicit centre, and writes the output, through their held bands (the *_row0 / *_rows pairs at the end of the block) while
 // `src` is RFX_TEX_BLUR_SOURCE, held whole.
 struct K6Args {
@@ -154,7 +154,7 @@ hipError_t rfx_launch_k6(const K6Args &, hipStream_t);
 // set-up and tap addressing without the loads (velocity is always read through its band view)
 hipError_t rfx_launch_k6_reach(const K6Args &, hipStream_t);
 
-// K7 export (k0_import.hip): `pixels` RGBA32F texels from `src` -> the packed stream at `dst`, laid out by rfx_launch.h rfx_export_plan_for
+// K7 export (k7_export.hip): `pixels` RGBA32F texels from `src` -> the packed stream at `dst`, laid out by rfx_launch.h rfx_export_plan_for
 struct K7Args {
     const uint4 *src;  // first exported texel
     void *dst;         // staging buffer (at least 16-byte aligned)
@@ -165,7 +165,7 @@ struct K7Args {
 // format / channels / tonemap select the specialisation (hipErrorInvalidValue for a combination the export does not have); `blocks` from the plan
 hipError_t rfx_launch_k7(const K7Args &, int blocks, int format, int channels, int tonemap, hipStream_t);
 
-// K8 PNG encode (k8_png.h, built into k0_import.hip): K7's staged U8 stream -> the result buffer of include/rfx.h "PNG fragments", laid out by
+// K8 PNG encode (k8_png.h, built into k7_export.hip): K7's staged U8 stream -> the result buffer of include/rfx.h "PNG fragments", laid out by
 // rfx_launch.h rfx_png_plan_for.  Three launches on `stream`: one wave per scanline into the scratch slots, the scan, the gather.
 struct K8Args {
     const unsigned char *src;     // K7's stream: `rows` rows of `rowbytes` bytes, row 0 = bottom
@@ -181,7 +181,7 @@ struct K8Args {
 hipError_t rfx_launch_k8(const K8Args &, hipStream_t, bool matches = false);
 hipError_t rfx_launch_k8_rows_m(const K8Args &, hipStream_t);  // the scanline kernel alone, with matches: rfx_launch_k8 calls it
 
-// K8 EXR encode (k8_exr.h, built into k0_import.hip): K7's staged F16 stream -> the result buffer of include/rfx.h "EXR fragments", laid out by
+// K8 EXR encode (k8_exr.h, built into k7_export.hip): K7's staged F16 stream -> the result buffer of include/rfx.h "EXR fragments", laid out by
 // rfx_launch.h rfx_exr_plan_for.  Four launches on `stream`: the byte planes, one wave per scanline into the scratch slots, the scan, the gather.
 struct K8ExrArgs {
     const unsigned short *src;    // K7's stream: `rows` rows of `width` pixels of `channels` halfs, row 0 = bottom
@@ -206,7 +206,7 @@ hipError_t rfx_launch_k8_exr_rows_m(const K8ExrArgs &, hipStream_t);  // the sca
 // (the rectangle of a bad block reads as not covered; the status words); with PIZ streams in the band two more in front of the planes: k9_piz_huf
 // (one wave per block: reverse lookup table, Huffman tables and decode, csrc/k9_piz.h) and k9_piz_planes (the wavelet in cells, the lookup, the
 // scatter).  The tables are device copies of the call's descriptor, built by
-// rfx_api.hip's exr_blocks_plan for both entry points.
+// rfx_exr_import.hip's exr_blocks_plan for every entry point.
 struct K9Chunk {
     unsigned long long src, dst;  // 256-byte-aligned offsets of the packed bytes / of the scratch slot (raw bytes, which is the LZ77 window too)
     unsigned int packed, raw;     // packed == raw: the raw block itself

@@ -1,7 +1,7 @@
 // rfx_launch.h — what a launch decides on the host before it launches: K1's table layout, a scaled tile's target rows, K3's tile geometry, the
 // "whole frame" test, the step from a run-time option to a template argument, and what is remembered per kernel and device.  Host code
 // (rfx_device.h comes in for UvPlanes and the two vUv expressions the kernels and the row plan share).  The plans are pure functions of their
-// arguments (no HIP call, no context): rfx_api.hip exports them as rfx_internal_k1_table / rfx_internal_k3_tile / rfx_internal_scaled_rows / rfx_internal_export_plan / rfx_internal_aov_plan / rfx_internal_exr_piz_tables and
+// arguments (no HIP call, no context): rfx_draw.hip exports them as rfx_internal_k1_table / rfx_internal_k3_tile / rfx_internal_scaled_rows / rfx_internal_export_plan / rfx_internal_aov_plan / rfx_internal_exr_piz_tables and
 // the CPU tests call them as built (tests/test_k1_table_layout.py, tests/test_k3_tile_geometry.py, tests/test_resolution_scale_rows_cpu.py).
 #pragma once
 #include <hip/hip_runtime.h>

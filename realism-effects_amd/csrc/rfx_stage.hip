@@ -1,0 +1,167 @@
+// rfx_stage.hip — the C ABI's streamed uploads (include/rfx.h "streaming dumps", "streamed AOV frames"): the next frame's planes cross PCIe on their
+// own stream into back buffers while the current frame is drawn; rfx_stage_flip publishes them.  The staging helpers rfx_exr_import.hip shares are
+// declared in rfx_host.h.
+#include "rfx_host.h"
+
+static bool is_dump_input(int id) { return id == RFX_TEX_DEPTH || id == RFX_TEX_GBUFFER || id == RFX_TEX_VELOCITY || id == RFX_TEX_DIRECT_LIGHT; }
+
+// the upload stream and the events that order it against the draws, created by the first staged call
+static int stage_streams(rfx_ctx *c) {
+    if (c->upload_stream) return RFX_OK;
+    hipError_t e = hipStreamCreateWithFlags(&c->upload_stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_staged, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_frame_done, hipEventDisableTiming);
+    for (hipEvent_t &b : c->ev_batch)
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&b, hipEventDisableTiming);
+    if (e != hipSuccess) return fail(c, RFX_EDEVICE, "rfx_stage_upload: stream/event creation", e);
+    // nothing of an earlier frame can still be reading a back buffer: there is none yet
+    HIPCHK(c, hipEventRecord(c->ev_frame_done, c->stream));
+    return RFX_OK;
+}
+// ... and a slot's back buffer
+static int stage_back(rfx_ctx *c, Slot &s) {
+    if (s.back) return RFX_OK;
+    hipError_t e = hipMalloc(&s.back, (size_t)s.rows * s.width * s.texel);
+    if (e != hipSuccess) return fail(c, RFX_ENOMEM, "hipMalloc(back buffer)", e);
+    return RFX_OK;
+}
+
+// the slots a plan writes: depth always, the packed ones where their planes are given
+static const int plan_ids[4] = {RFX_TEX_DEPTH, RFX_TEX_GBUFFER, RFX_TEX_VELOCITY, RFX_TEX_DIRECT_LIGHT};
+static bool plan_writes(const rfx_aov_plan &t, int k) { return k == 0 || (k == 1 ? t.write_gbuffer : k == 2 ? t.write_velocity : t.write_direct) != 0; }
+
+int stage_plan_begin(rfx_ctx *c, const rfx_aov_plan &t, const char *fn) {
+    int rc;
+    for (int k = 0; k < 4; k++) {  // every check before anything is enqueued
+        if (!plan_writes(t, k)) continue;
+        if ((rc = ensure(c, plan_ids[k]))) return rc;
+        if (!c->slots[plan_ids[k]].owned) return fail_in(c, RFX_ESTATE, fn, "a slot to be written is bound to an external buffer");
+    }
+    if ((rc = stage_streams(c))) return rc;
+    for (int k = 0; k < 4; k++)
+        if (plan_writes(t, k) && (rc = stage_back(c, c->slots[plan_ids[k]]))) return rc;
+    return RFX_OK;
+}
+void stage_plan_end(rfx_ctx *c, const rfx_aov_plan &t) {
+    for (int k = 0; k < 4; k++)
+        if (plan_writes(t, k)) c->slots[plan_ids[k]].back_filled = true;
+}
+
+int grow_stage_area(rfx_ctx *c, void **area, size_t *cap, size_t need, const char *what) {
+    if (*cap >= need) return RFX_OK;
+    if (*area) HIPCHK(c, hipStreamSynchronize(c->upload_stream));
+    return grow_idle(c, area, cap, need, what);
+}
+
+hipError_t aov_pack_segment(rfx_ctx *c, const rfx_aov_plan &t, const rfx_aov_segment &g, K0AovArgs A) {
+    const auto first = [&](int id) { return slot_back_row(c->slots[id], g.row0); };
+    A.depth = (float *)first(RFX_TEX_DEPTH);
+    if (g.full && t.write_gbuffer) A.gbuffer = (uint4 *)first(RFX_TEX_GBUFFER);
+    if (g.full && t.write_velocity) A.velocity = (uint4 *)first(RFX_TEX_VELOCITY);
+    if (g.full && t.write_direct) A.direct = (uint4 *)first(RFX_TEX_DIRECT_LIGHT);
+    A.groups = g.groups; A.tail_start = g.tail_start; A.tail_pixels = g.tail_pixels;
+    return rfx_launch_k0_aov(A, g.blocks, c->upload_stream);
+}
+
+// ---- streamed AOV frames (include/rfx.h): the planes of rfx_pack_gbuffer / rfx_pack_velocity / the depth and direct uploads, staged once on the
+// upload stream and packed by one fused kernel (k0_import.hip k0_aov_pack) into the back buffers rfx_stage_flip publishes
+static const rfx_plane *aov_planes(const rfx_aov_frame *f) { return &f->diffuse; }  // eight rfx_plane in RFX_AOV_* order
+static const char *aov_plan(const rfx_ctx *c, const rfx_aov_frame *f, int row0, int rows, rfx_aov_plan *t) {
+    static_assert(sizeof(rfx_aov_frame) == RFX_AOV_PLANES * sizeof(rfx_plane), "rfx_aov_frame is eight planes");
+    int type[RFX_AOV_PLANES], channels[RFX_AOV_PLANES];
+    for (int i = 0; i < RFX_AOV_PLANES; i++) {
+        const rfx_plane &p = aov_planes(f)[i];
+        type[i] = p.type;
+        channels[i] = p.data ? p.channels : 0;
+        if (p.data && p.channels <= 0) return "a plane's channel count";
+    }
+    const Slot &g = c->slots[RFX_TEX_GBUFFER];  // (VELOCITY and DIRECT_LIGHT hold the same rows)
+    return rfx_aov_plan_for(c->W, c->H, g.row0, g.rows, type, channels, row0, rows, t);
+}
+
+extern "C" {
+
+int rfx_stage_upload(rfx_ctx *c, rfx_tex id, const void *host, int row0, int rows) {
+    if (!c || !host) return RFX_EINVAL;
+    if (!is_dump_input(id)) return fail(c, RFX_EINVAL, "rfx_stage_upload: only the dump's input planes (depth, gbuffer, velocity, direct light) are double-buffered");
+    int rc = band_check(c, id, row0, rows);
+    if (rc) return rc;
+    if ((rc = ensure(c, id))) return rc;
+    RFX_ENTER(c);
+    Slot &s = c->slots[id];
+    if (!s.owned) return fail(c, RFX_ESTATE, "rfx_stage_upload: the slot is bound to an external buffer");
+    const size_t pitch = (size_t)s.width * s.texel;
+    if ((rc = stage_streams(c))) return rc;
+    if ((rc = stage_back(c, s))) return rc;
+    // the buffer being filled was the FRONT buffer until the last flip: the draws that read it were enqueued before that flip
+    HIPCHK(c, hipStreamWaitEvent(c->upload_stream, c->ev_frame_done, 0));
+    HIPCHK(c, hipMemcpyAsync(slot_back_row(s, row0), host, (size_t)rows * pitch, hipMemcpyHostToDevice, c->upload_stream));
+    s.back_filled = true;
+    return RFX_OK;
+}
+
+size_t rfx_aov_stage_bytes(const rfx_ctx *c, const rfx_aov_frame *f, int row0, int rows) {
+    rfx_aov_plan t;
+    if (!c || !f || aov_plan(c, f, row0, rows, &t)) return 0;
+    return (size_t)t.copy_bytes;
+}
+
+int rfx_stage_aov(rfx_ctx *c, const rfx_aov_frame *f, int row0, int rows) {
+    if (!c || !f) return RFX_EINVAL;
+    RFX_ENTER(c);
+    rfx_aov_plan t;
+    if (const char *bad = aov_plan(c, f, row0, rows, &t)) return fail_in(c, RFX_EINVAL, "rfx_stage_aov", bad);
+    int rc = stage_plan_begin(c, t, "rfx_stage_aov");
+    if (rc) return rc;
+    if ((rc = grow_stage_area(c, &c->aov_stage, &c->aov_stage_cap, (size_t)t.stage_bytes, "rfx_stage_aov: hipMalloc(staging area)"))) return rc;
+    // rfx_stage_upload's order: the back buffers were the front buffers until the last flip
+    HIPCHK(c, hipStreamWaitEvent(c->upload_stream, c->ev_frame_done, 0));
+    for (int k = 0; k < t.nseg; k++) {
+        const rfx_aov_segment &g = t.seg[k];
+        K0AovArgs A = {};
+        for (int i = 0; i < RFX_AOV_PLANES; i++) {
+            if (g.offset[i] == ~0ull) continue;
+            const rfx_plane &p = aov_planes(f)[i];
+            const size_t texel = (size_t)p.channels * t.elem_bytes[i];
+            void *dev = (char *)c->aov_stage + g.offset[i];
+            HIPCHK(c, hipMemcpyAsync(dev, (const char *)p.data + (size_t)(g.row0 - row0) * c->W * texel, (size_t)g.pixels * texel, hipMemcpyHostToDevice, c->upload_stream));
+            A.plane[i] = dev;
+            if (p.type == RFX_PLANE_F16) A.half_mask |= 1u << i;
+        }
+        A.diffuse_ch = f->diffuse.channels; A.direct_ch = f->direct.channels;
+        HIPCHK(c, aov_pack_segment(c, t, g, A));
+    }
+    stage_plan_end(c, t);
+    return RFX_OK;
+}
+
+int rfx_stage_flip(rfx_ctx *c) {
+    if (!c) return RFX_EINVAL;
+    if (!c->upload_stream) return fail(c, RFX_ESTATE, "rfx_stage_flip: nothing staged");
+    RFX_ENTER(c);
+    // draws enqueued from now on wait for the staged copies; copies staged from now on wait for the draws enqueued so far
+    HIPCHK(c, hipEventRecord(c->ev_staged, c->upload_stream));
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_staged, 0));
+    HIPCHK(c, hipEventRecord(c->ev_frame_done, c->stream));
+    // Host-side back pressure.  Neither rfx_stage_upload nor the flip waits for the GPU, and a staged copy executes only once the
+    // draws of two frames earlier have finished — a host running ahead (two alternating sets of pinned planes) could refill a set
+    // before the copy that reads it has run.  So this flip returns only when the copies published by the PREVIOUS flip have
+    // executed: the planes staged before that flip are free to be rewritten, and the host is never more than two frames ahead.
+    const unsigned int k = c->flips++;
+    HIPCHK(c, hipEventRecord(c->ev_batch[k & 1], c->upload_stream));
+    if (k >= 1) HIPCHK(c, hipEventSynchronize(c->ev_batch[(k - 1) & 1]));
+    for (int id = 0; id < RFX_TEX_COUNT; id++) {
+        Slot &s = c->slots[id];
+        if (!s.back_filled) continue;
+        if (id == RFX_TEX_DEPTH) {  // the depth pre-pass of the next K1 waits for this copy on its own stream
+            HIPCHK(c, hipEventRecord(c->ev_depth, c->upload_stream));
+            depth_new_writer(c, DEPTH_PENDING);  // another plane is the depth slot now
+        }
+        void *t = s.ptr; s.ptr = s.back; s.back = t;
+        s.back_filled = false;
+        s.uploaded = true;
+    }
+    return RFX_OK;
+}
+
+}  // extern "C"

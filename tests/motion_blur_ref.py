@@ -1,5 +1,5 @@
 """A numpy restatement of K6, MotionBlurEffect's mainImage (src/motion-blur/shader/motion_blur.frag:11-45, blueNoise from
-src/utils/shader/blue_noise.glsl:37-45), in the operation order and roundings of the kernel (realism-effects_amd/csrc/k4_compose.hip
+src/utils/shader/blue_noise.glsl:37-45), in the operation order and roundings of the kernel (realism-effects_amd/csrc/k6_motion_blur.hip
 k6_motion_blur): fp32 throughout, the sampler's lerps as single-rounding fmas, every other product and sum (`mix` included) rounded on
 its own.
 
@@ -34,7 +34,7 @@ def fma(a, b, c):
 
 
 def blue_noise_shift(index: int):
-    """blue_noise.glsl:9-34 (rfx_api.hip blue_noise_shift): the frame's toroidal shift of the 128 x 128 table; index 0 = unshifted."""
+    """blue_noise.glsl:9-34 (rfx_host.h blue_noise_shift): the frame's toroidal shift of the 128 x 128 table; index 0 = unshifted."""
     if index == 0:
         return 0, 0
     m = 0xFFFFFFFF

@@ -1,4 +1,4 @@
-"""-m gpu: CubeToEquirectEnvPass on the device (rfx_cube_to_equirect, csrc/k0_import.hip) — scene.environment given as a CubeTexture
+"""-m gpu: CubeToEquirectEnvPass on the device (rfx_cube_to_equirect, csrc/k0_cube.hip) — scene.environment given as a CubeTexture
 (SSGIEffect.js:316-321, src/ssgi/pass/CubeToEquirectEnvPass.js:21-42).  Written after the round's GPU budget was spent: this file sorts
 last so that its first run on hardware cannot hide any other test's result."""
 import types
