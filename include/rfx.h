@@ -348,6 +348,29 @@ int rfx_download_environment(rfx_ctx *, int level, float *rgba, int *levels);
  * reduced by the GL's bilinear blit, an even one by the 2x2 average it degenerates to), with the implicit level of detail of `textureCube`
  * (the pass minifies near the face edges: levels 0-2 take part). */
 int rfx_cube_to_equirect(rfx_ctx *, const float *faces_rgba, int size, int generateMipmaps, float *equirect_rgba, int width, int height);
+/* ---- the environment kept on the device (additive to ABI 21: a host checks for the symbols; the version number stands).  For an
+ * environment that changes during a sequence — a CubeCamera probe, an animated sky — the three calls above cost two uploads, a read-back,
+ * the table build on the host and four waits per change.  The two calls below are STREAM-ORDERED on the context's stream instead: a draw
+ * queued before them reads the old environment, one queued after them the new one.  They do not synchronise the stream, and they neither
+ * allocate nor free device memory when the sizes are those of the previous call (the context owns the chain, the cube's chain, the staging,
+ * the tables and K10's scratch, and grows them on demand).  They mix freely with the blocking calls above, which behave as before.
+ *
+ * rfx_set_environment_cube = rfx_cube_to_equirect followed by rfx_set_environment(equirect, width, height, 0, 0) with the equirectangular
+ * map never leaving the device: every level is byte-identical to the two-call form.  The rules are those two calls': size 1..8192, width
+ * and height powers of two <= 16384 (RFX_EINVAL).  Its one wait is on an event behind the copy of `faces_rgba`, which the caller may reuse
+ * on return.  Like rfx_set_environment it invalidates the importance tables: importanceSampling is refused until a build (or
+ * rfx_set_environment_importance) has run.
+ *
+ * rfx_build_environment_importance runs K10 (csrc/k10_env_tables.hip) on level 0 of the held environment — whichever call set it — and sets
+ * the two tables and the two sums: bit for bit what rfx_amd/envmap.py build_importance (js/envmap.js buildImportance) computes from the same
+ * texels for every finite input.  `flipY`: the texture's flipY, i.e. the worker's lossy "un-flip" of the reversed rows is reproduced.
+ * RFX_ESTATE when no environment is set.
+ *
+ * rfx_download_environment_importance reads the tables back for inspection (any pointer may be NULL; synchronises): marginal (height floats),
+ * conditional (width x height), totalSumValue and its two parts.  RFX_ESTATE when no tables are set. */
+int rfx_set_environment_cube(rfx_ctx *, const float *faces_rgba, int size, int generateMipmaps, int width, int height);
+int rfx_build_environment_importance(rfx_ctx *, int flipY);
+int rfx_download_environment_importance(rfx_ctx *, float *marginal, float *conditional, double *totalSumValue, float *whole, float *decimal);
 
 /* ---- the four draws (+ the framebuffer copy and the effect's own fragment) */
 int rfx_ssgi_march(rfx_ctx *, const rfx_ssgi_params *);

@@ -600,7 +600,7 @@ RFX_DEV void k1_ssgi_march_body(const K1Args &A, const FrameDims &d, const k1_ce
         const int qx = x & ~1, qy = y & ~1;
         const float lod = k1_implicit_lod(A, k1_cdf_uv(A, d, qx, qy), k1_cdf_uv(A, d, qx + 1, qy), k1_cdf_uv(A, d, qx, qy + 1));
         const float3 col = k1_env_trilinear(A, uv.x, uv.y, lod);
-        const float totalSum = A.totalSumWhole + A.totalSumDecimal;
+        const float totalSum = A.env_sums ? A.env_sums[0] + A.env_sums[1] : A.totalSumWhole + A.totalSumDecimal;  // (device-built tables: K10's sums)
         ems.pdf = ((float)A.env_w * (float)A.env_h) * (rfx_lum(col) / totalSum);
         envMisDir = rfx_normalize(rfx_vec_mul_mat(C, derived, 0.0f));  // (vec4(dir, 0.) * cameraMatrixWorld).xyz :199
         float prob = rfx_dot(envMisDir, viewNormal);

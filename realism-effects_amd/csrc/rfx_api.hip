@@ -117,6 +117,9 @@ void rfx_destroy(rfx_ctx *c) {
     if (c->env) hipFree(c->env);
     if (c->env_marginal) hipFree(c->env_marginal);
     if (c->env_conditional) hipFree(c->env_conditional);
+    for (void *p : {c->env_stage, c->env_cube, c->env_k10})
+        if (p) hipFree(p);
+    if (c->ev_env_copied) hipEventDestroy(c->ev_env_copied);
     prof_recycle(c);
     for (hipEvent_t e : c->prof_free) hipEventDestroy(e);
     if (c->ev0) hipEventDestroy(c->ev0);

@@ -62,6 +62,17 @@ struct rfx_ctx {
     float env_sum_whole = 1.0f, env_sum_decimal = 0.0f;
     int env_w = 0, env_h = 0, env_levels = 0;
     unsigned int env_off[16] = {0};
+    // The context owns the chain and the tables with their capacities in bytes (env_cap; env_tab_cap: marginal, conditional), so that the
+    // stream-ordered updates (rfx_set_environment_cube, rfx_build_environment_importance) re-use them when the sizes repeat; the blocking entry
+    // points free and allocate exactly, as they always did.  env_tables_set: the tables describe the held environment (importanceSampling is
+    // refused otherwise); env_sums_on_device: K10 built them, K1 reads the two sums from env_k10 and not from env_sum_whole / env_sum_decimal.
+    size_t env_cap = 0, env_tab_cap[2] = {0, 0};
+    bool env_tables_set = false, env_sums_on_device = false;
+    // ... and the areas of the device path, grown on demand like aov_stage: the equirect staging the cube pass draws into and the mip kernel reads,
+    // the cube's own chain, K10's scratch (rfx_kernels.h rfx_env_tables_scratch_bytes); the event behind the copy of the caller's faces
+    void *env_stage = nullptr, *env_cube = nullptr, *env_k10 = nullptr;
+    size_t env_stage_cap = 0, env_cube_cap = 0, env_k10_cap = 0;
+    hipEvent_t ev_env_copied = nullptr;
     Slot slots[RFX_TEX_COUNT];
     // row-tiled runs (rfx_comm.hip): the RCCL communicator of the tile ring, a second stream the exchanges run on, and the two
     // events that order it against the draw stream

@@ -39,7 +39,7 @@ static float ssgi_resolution_scale(const rfx_ssgi_params *p) { return p->resolut
 static int ssgi_validate(rfx_ctx *c, const rfx_ssgi_params *p) {
     if (!c || !p) return RFX_EINVAL;
     if (p->mode != 0 && p->mode != 1) return fail(c, RFX_EINVAL, "rfx_ssgi_march/trace/shade: mode must be 0 (MODE_SSGI) or 1 (MODE_SSR)");
-    if (p->importanceSampling && (!p->useEnvMap || !c->env_marginal))
+    if (p->importanceSampling && (!p->useEnvMap || !c->env_tables_set))
         return fail(c, RFX_ESTATE, "rfx_ssgi_march/trace/shade: importanceSampling needs useEnvMap and rfx_set_environment_importance");
     if (p->useEnvMap && !c->env) return fail(c, RFX_ESTATE, "rfx_ssgi_march/trace/shade: useEnvMap without rfx_set_environment");
     if (p->steps < 1 || p->refineSteps < 0) return fail(c, RFX_EINVAL, "rfx_ssgi_march/trace/shade: steps/refineSteps");
@@ -138,6 +138,7 @@ static bool k1_args(rfx_ctx *c, const rfx_ssgi_params *p, int stage, const rfx_k
     A.env_w = c->env_w; A.env_h = c->env_h; A.env_levels = c->env_levels;
     A.env_marginal = c->env_marginal; A.env_conditional = c->env_conditional;
     A.totalSumWhole = c->env_sum_whole; A.totalSumDecimal = c->env_sum_decimal;
+    A.env_sums = c->env_sums_on_device ? rfx_env_tables_sums(c->env_k10) : nullptr;
     memcpy(A.env_off, c->env_off, sizeof A.env_off);
     {   // getMaxMipLevel (src/ssgi/utils/Utils.js:30-34): floor(log2(max(w, h))) + 1
         int m = c->env_w > c->env_h ? c->env_w : c->env_h, lg = 0;

@@ -56,6 +56,7 @@ struct K1Args {
     int n_cu;                    // compute units of the device (sizes the persistent grid)
     unsigned char *fg_tiles;     // k1_prepare also writes K3's foreground map: one byte per 64 x 8-texel tile, rows of fg_w = ceil(W / 64) bytes
     int fg_w;
+    const float *env_sums;       // tables built on the device (K10): totalSumWhole, totalSumDecimal are read here (device memory); null: the two fields above
 };
 int rfx_k1_base_cell();  // edge of k1_prepare's base cells in texels
 hipError_t rfx_launch_k1_prepare(const K1Args &, hipStream_t);
@@ -68,6 +69,11 @@ hipError_t rfx_launch_k1_hit_mask_scaled(const FrameDims &, const UvPlanes &out_
                                          unsigned int *mask, hipStream_t);
 // one level of the environment's mip chain from the one above (glGenerateMipmap on the oracle's GL: 2x2 bilinear centre)
 hipError_t rfx_launch_env_mip(const float4 *src, float4 *dst, int sw, int sh, int dw, int dh, bool to_half, bool rtz, hipStream_t);
+// K10 (k10_env_tables.hip): the importance tables of a W x H environment (powers of two) from its level 0 — marginal (H floats), conditional (W x H),
+// and in `scratch` (rfx_env_tables_scratch_bytes) a K10Sums first: the double total, then the two floats K1 reads (rfx_env_tables_sums)
+hipError_t rfx_launch_env_tables(const float4 *env, int W, int H, int flipY, float *marginal, float *conditional, void *scratch, hipStream_t);
+static inline size_t rfx_env_tables_scratch_bytes(int H) { return 24 + (size_t)H * sizeof(double); }  // K10Sums, the marginal's last sum, the row sums
+static inline const float *rfx_env_tables_sums(const void *scratch) { return (const float *)((const char *)scratch + 8); }
 
 struct K2Args {
     FrameDims dims;

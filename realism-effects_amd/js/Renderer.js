@@ -307,6 +307,7 @@ class Renderer {
 	// scene.environment: Float32Array(H*W*4) equirect map (row 0 = bottom) or null — rfx_set_environment
 	setEnvironment(data, width, height, halfFloatType, halfStoreRTZ) {
 		addon.setEnvironment(this._h, data || null, width || 0, height || 0, halfFloatType ? 1 : 0, halfStoreRTZ ? 1 : 0)
+		this._envSize = data ? [width | 0, height | 0] : null // (downloadEnvironmentImportance)
 	}
 
 	// EquirectHdrInfoUniform's tables for importanceSampling (js/envmap.js buildImportance) — rfx_set_environment_importance
@@ -329,6 +330,28 @@ class Renderer {
 		const out = new Float32Array(width * height * 4)
 		addon.cubeToEquirect(this._h, faces, size | 0, generateMipmaps ? 1 : 0, out, width | 0, height | 0)
 		return out
+	}
+	// ---- the environment kept on the device (include/rfx.h): stream-ordered, no read-back, no host build of the tables
+	get hasEnvDevice() {
+		return typeof addon.buildEnvironmentImportance === "function"
+	}
+	// cubeToEquirect + setEnvironment(equirect, width, height, false, false) with the map never leaving the device (rfx_set_environment_cube);
+	// `faces` may be reused on return.  Invalidates the importance tables
+	setEnvironmentCube(faces, size, width, height, generateMipmaps) {
+		addon.setEnvironmentCube(this._h, faces, size | 0, generateMipmaps ? 1 : 0, width | 0, height | 0)
+		this._envSize = [width | 0, height | 0]
+	}
+	// the tables and sums of js/envmap.js buildImportance, built from level 0 of the held environment (K10), bit for bit
+	buildEnvironmentImportance(flipY) {
+		addon.buildEnvironmentImportance(this._h, flipY ? 1 : 0)
+	}
+	// { marginalWeights, conditionalWeights, totalSumValue, whole, decimal } as the context holds them (synchronises); width, height: the
+	// environment's, remembered from setEnvironment / setEnvironmentCube when not given
+	downloadEnvironmentImportance(width, height) {
+		const [w, h] = width ? [width | 0, height | 0] : this._envSize || [0, 0]
+		if (!w || !h) throw new Error("downloadEnvironmentImportance: no environment set")
+		const marginalWeights = new Float32Array(h), conditionalWeights = new Float32Array(w * h)
+		return Object.assign({ marginalWeights, conditionalWeights }, addon.downloadEnvironmentImportance(this._h, marginalWeights, conditionalWeights, w, h))
 	}
 	// which vUv the following draws' fragments see (rfx_set_uv_model): "ideal" = (i + 0.5) / n, "reference_gl" = what the reference GL's
 	// rasteriser interpolates for three's full-screen triangle, bit for bit

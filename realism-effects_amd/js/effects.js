@@ -676,7 +676,8 @@ const LinearMipmapLinearFilter = 1008
 // faces: Float32Array(6 * size * size * 4) linear values (+X -X +Y -Y +Z -Z, row j = t as uploaded), size, and the two sampler fields the
 // lookup depends on: minFilter (default LinearMipmapLinearFilter, three's Texture default) and generateMipmaps (default true) }.
 class CubeToEquirectEnvPass {
-	generateEquirectEnvMap(renderer, cubeMap, width = null, height = null, maxWidth = 4096) {
+	// onDevice: the draw's target stays on the device and becomes the environment there (renderer.setEnvironmentCube); no `data` then
+	generateEquirectEnvMap(renderer, cubeMap, width = null, height = null, maxWidth = 4096, onDevice = false) {
 		if (width === null && height === null) {
 			// :62-69
 			const w = cubeMap.size
@@ -699,6 +700,10 @@ class CubeToEquirectEnvPass {
 			throw new Error("CubeToEquirectEnvPass: cube minFilter " + minFilter + " — LinearFilter and LinearMipmapLinearFilter are built")
 		}
 		// render + readRenderTargetPixels :76-85, then the DataTexture of :87-97 (FloatType, ClampToEdge, EquirectangularReflectionMapping)
+		if (onDevice) {
+			renderer.setEnvironmentCube(cubeMap.faces, cubeMap.size, width, height, mips)
+			return { data: null, width, height, type: FloatType, isCubeTexture: false }
+		}
 		const data = renderer.cubeToEquirect(cubeMap.faces, cubeMap.size, width, height, mips)
 		return { data, width, height, type: FloatType, isCubeTexture: false }
 	}
@@ -737,6 +742,10 @@ class SSGIEffect {
 			}
 		}
 		seeds = seeds || {}
+		// envOnDevice (an addition, off by default): keepEnvMapUpdated keeps a changed scene.environment on the device where the renderer can
+		// (Renderer.hasEnvDevice) — a cube becomes the environment without a read-back, the importance tables are built by K10: the same bits
+		this._envOnDevice = !!options.envOnDevice
+		delete options.envOnDevice
 		this._options = options
 		this._halfStoreRTZ = halfStoreRTZ
 		this.ssgiPass = new SSGIPass(this, options, seeds.ssgi)
@@ -900,15 +909,20 @@ class SSGIEffect {
 		if (env) {
 			if (this._envUuid !== env) {
 				let map = env
+				const onDevice = this._envOnDevice && !!renderer.hasEnvDevice
 				if (map.isCubeTexture) {
 					// :316-321 convert it to an equirectangular texture so the pass can sample it and use MIS
 					if (!this.cubeToEquirectEnvPass) this.cubeToEquirectEnvPass = new CubeToEquirectEnvPass()
-					map = this.cubeToEquirectEnvPass.generateEquirectEnvMap(renderer, map)
+					map = this.cubeToEquirectEnvPass.generateEquirectEnvMap(renderer, map, null, null, 4096, onDevice)
 				}
 				const half = map.type === undefined || map.type === null || map.type === HalfFloatType
-				renderer.setEnvironment(map.data, map.width, map.height, half, this._halfStoreRTZ === undefined || this._halfStoreRTZ)
+				// (no data: the cube pass has set the environment on the device)
+				if (map.data) renderer.setEnvironment(map.data, map.width, map.height, half, this._halfStoreRTZ === undefined || this._halfStoreRTZ)
 				u.importanceSampling = 0
-				if (this._options.importanceSampling) {
+				if (this._options.importanceSampling && onDevice) {
+					renderer.buildEnvironmentImportance(!!map.flipY) // the same tables, built from the held level 0 (K10)
+					u.importanceSampling = 1
+				} else if (this._options.importanceSampling) {
 					// :348-351 EquirectHdrInfoUniform.updateFrom, then the define.  The worker sees the half-float texels (fromHalfFloat); `data` is
 					// in GL row order (row 0 = bottom): with texture.flipY the reference's array is the other way up and the worker "un-flips" it
 					let texels = half ? toHalfPrecision(map.data) : map.data

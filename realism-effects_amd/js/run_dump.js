@@ -30,6 +30,8 @@
 // --framesCompression '"zips"' (exr only; default '"none"'): the frame leaves the device as finished OpenEXR ZIPS chunks (rfx_stage_exr, K8 behind
 // the EXR byte predictor) and the host only wraps them; the samples are the uncompressed file's.  --framesMatches true (with either of the two;
 // default false): the device encode with run-length matches (rfx.h "Match form"): smaller files where pixels repeat exactly.
+// --env / --envCube (below, where they are read): scene.environment; --envCube with %d in the name: a cube per frame; --envOnDevice true: every
+// change of the environment stays on the device (SSGIEffect's envOnDevice: rfx_set_environment_cube, rfx_build_environment_importance), same bytes.
 // --saveState DIR [--saveEvery N]: write a checkpoint of the temporal state (js/state.js) into DIR after every N-th frame and after the last;
 // --loadState DIR: restore one first — the dump directories given are then the REMAINING frames, and the outputs are byte-identical to an
 // uninterrupted run.  Both work with --ranks (every rank writes its rows of the whole-frame planes; any rank count loads them), --traa,
@@ -146,21 +148,41 @@ delete opt.ssgiSeed
 delete opt.denoiseSeed
 const first = rfx.readDump(dumps[0])
 const scene = { frame: first }
-// --env <file.bin> --envWidth W --envHeight H: a raw Float32 RGBA equirect map (row 0 = bottom) as scene.environment (needs --importanceSampling false)
+// --env <file.bin> --envWidth W --envHeight H [--envFlipY true]: a raw Float32 RGBA equirect map (row 0 = bottom) as scene.environment, a
+// HalfFloatType texture; --envFlipY: its flipY is set (the importance tables are then built from the worker's "un-flipped" rows)
 if (opt.env) {
 	const b = fs.readFileSync(opt.env)
 	scene.environment = { data: new Float32Array(b.buffer, b.byteOffset, b.length / 4), width: opt.envWidth, height: opt.envHeight }
+	if (opt.envFlipY) scene.environment.flipY = true
 	delete opt.env
 	delete opt.envWidth
 	delete opt.envHeight
 }
+delete opt.envFlipY
 // --envCube <file.bin> --envCubeSize S [--envCubeMipmaps false]: scene.environment as a CubeTexture — six S x S Float32 RGBA faces (+X -X +Y -Y
 // +Z -Z, row j = t as uploaded), converted once through CubeToEquirectEnvPass (three's default sampler state unless --envCubeMipmaps false:
-// LinearFilter, no chain)
+// LinearFilter, no chain).  A name with %d names the file of frame index %d (0-based): every frame that has one gets a NEW scene.environment
+// object, a frame without one keeps the environment it found — an environment that changes during the sequence (a re-rendered probe, an animated
+// sky).  --envOnDevice true (SSGIEffect's envOnDevice): every change stays on the device (rfx_set_environment_cube, rfx_build_environment_importance)
+let frameEnvironment = () => {}
 if (opt.envCube) {
-	const b = fs.readFileSync(opt.envCube)
-	scene.environment = { isCubeTexture: true, faces: new Float32Array(b.buffer, b.byteOffset, b.length / 4), size: opt.envCubeSize }
-	if (opt.envCubeMipmaps === false) Object.assign(scene.environment, { minFilter: rfx.LinearFilter, generateMipmaps: false })
+	const cubeName = String(opt.envCube), cubeSize = opt.envCubeSize, cubeMipmaps = opt.envCubeMipmaps
+	const loadCube = file => {
+		const b = fs.readFileSync(file)
+		const cube = { isCubeTexture: true, faces: new Float32Array(b.buffer, b.byteOffset, b.length / 4), size: cubeSize }
+		if (cubeMipmaps === false) Object.assign(cube, { minFilter: rfx.LinearFilter, generateMipmaps: false })
+		return cube
+	}
+	if (cubeName.includes("%d")) {
+		let held = null
+		frameEnvironment = i => {
+			const file = cubeName.replace("%d", String(i))
+			if (file !== held && fs.existsSync(file)) {
+				scene.environment = loadCube(file)
+				held = file
+			}
+		}
+	} else scene.environment = loadCube(cubeName)
 	delete opt.envCube
 	delete opt.envCubeSize
 	delete opt.envCubeMipmaps
@@ -295,6 +317,7 @@ if (stream && !tiled) {
 		if (next) renderer.stageFrame(next) // frame i+1 starts crossing PCIe ...
 		scene.frame = cur
 		Object.assign(camera, cur.camera)
+		frameEnvironment(i)
 		effect.update(renderer, null) // ... while frame i is drawn
 		blurFrame()
 		exportFrame() // (before the flip: the effect's fragment reads this frame's planes)
@@ -307,6 +330,7 @@ if (stream && !tiled) {
 		const f = d === dumps[0] ? first : rfx.readDump(d)
 		scene.frame = f
 		Object.assign(camera, f.camera)
+		frameEnvironment(i)
 		effect.update(renderer, null)
 		blurFrame()
 		exportFrame()

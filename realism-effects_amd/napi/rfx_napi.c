@@ -550,6 +550,86 @@ static napi_value n_set_environment_importance(napi_env env, napi_callback_info 
     return NULL;
 }
 
+/* ---- the environment kept on the device (include/rfx.h): stream-ordered, no read-back
+ * setEnvironmentCube(ctx, Float32Array faces[6 * size * size * 4], size, generateMipmaps, width, height): rfx_set_environment_cube */
+static napi_value n_set_environment_cube(napi_env env, napi_callback_info info) {
+    napi_value a[6];
+    if (!get_args(env, info, 6, a)) return NULL;
+    rfx_ctx *c = get_ctx(env, a[0]);
+    if (!c) return NULL;
+    int32_t size, mips, w, h;
+    if (!get_int(env, a[2], &size) || !get_int(env, a[3], &mips) || !get_int(env, a[4], &w) || !get_int(env, a[5], &h)) return NULL;
+    napi_typedarray_type tt;
+    size_t len;
+    void *ptr;
+    if (napi_get_typedarray_info(env, a[1], &tt, &len, &ptr, NULL, NULL) != napi_ok || tt != napi_float32_array) {
+        napi_throw_type_error(env, NULL, "setEnvironmentCube: Float32Array faces expected");
+        return NULL;
+    }
+    if (size < 1 || (size_t)6 * (size_t)size * (size_t)size * 4 != len) {
+        napi_throw_range_error(env, NULL, "setEnvironmentCube: faces length != 6 * size * size * 4");
+        return NULL;
+    }
+    int rc = rfx_set_environment_cube(c, (const float *)ptr, size, mips, w, h);
+    if (rc) return throw_rfx(env, c, "rfx_set_environment_cube", rc);
+    return NULL;
+}
+/* buildEnvironmentImportance(ctx, flipY): rfx_build_environment_importance (K10) */
+static napi_value n_build_environment_importance(napi_env env, napi_callback_info info) {
+    napi_value a[2];
+    if (!get_args(env, info, 2, a)) return NULL;
+    rfx_ctx *c = get_ctx(env, a[0]);
+    int32_t flip = 0;
+    if (!c || !get_int(env, a[1], &flip)) return NULL;
+    int rc = rfx_build_environment_importance(c, flip);
+    if (rc) return throw_rfx(env, c, "rfx_build_environment_importance", rc);
+    return NULL;
+}
+/* downloadEnvironmentImportance(ctx, Float32Array marginal[height], Float32Array conditional[width * height]) -> {totalSumValue, whole, decimal}
+ * (the caller sizes the arrays for the environment it set: the library copies height and width * height floats) */
+static napi_value n_download_environment_importance(napi_env env, napi_callback_info info) {
+    napi_value a[5], out, v;
+    if (!get_args(env, info, 5, a)) return NULL;
+    rfx_ctx *c = get_ctx(env, a[0]);
+    int32_t w, h;
+    if (!c || !get_int(env, a[3], &w) || !get_int(env, a[4], &h)) return NULL;
+    float *tab[2];
+    for (int k = 0; k < 2; k++) {
+        napi_typedarray_type tt;
+        size_t len;
+        void *ptr;
+        if (napi_get_typedarray_info(env, a[1 + k], &tt, &len, &ptr, NULL, NULL) != napi_ok || tt != napi_float32_array) {
+            napi_throw_type_error(env, NULL, "downloadEnvironmentImportance: Float32Array expected");
+            return NULL;
+        }
+        if (w < 1 || h < 1 || len != (k ? (size_t)w * (size_t)h : (size_t)h)) {
+            napi_throw_range_error(env, NULL, "downloadEnvironmentImportance: marginal must hold height floats and conditional width * height");
+            return NULL;
+        }
+        tab[k] = (float *)ptr;
+    }
+    int levels = 0;
+    int rc = rfx_download_environment(c, 0, NULL, &levels);  /* the size the caller states must be the held environment's: 1 + log2(max edge) levels */
+    int want = 1;
+    for (int m = w > h ? w : h; m > 1; m >>= 1) want++;
+    if (!rc && levels != want) {
+        napi_throw_range_error(env, NULL, "downloadEnvironmentImportance: width / height are not the held environment's");
+        return NULL;
+    }
+    double total = 0;
+    float whole = 0, dec = 0;
+    if (!rc) rc = rfx_download_environment_importance(c, tab[0], tab[1], &total, &whole, &dec);
+    if (rc) return throw_rfx(env, c, "rfx_download_environment_importance", rc);
+    NAPI_CALL(env, napi_create_object(env, &out));
+    NAPI_CALL(env, napi_create_double(env, total, &v));
+    NAPI_CALL(env, napi_set_named_property(env, out, "totalSumValue", v));
+    NAPI_CALL(env, napi_create_double(env, whole, &v));
+    NAPI_CALL(env, napi_set_named_property(env, out, "whole", v));
+    NAPI_CALL(env, napi_create_double(env, dec, &v));
+    NAPI_CALL(env, napi_set_named_property(env, out, "decimal", v));
+    return out;
+}
+
 /* ssgiMarch / ssgiTrace / ssgiShade(ctx, {camera, steps, refineSteps, mode, useDirectLight, missedRays, importanceSampling,
  *                 rayDistance, thickness, envBlur, blueNoiseIndex, historySource, resolutionScale, useEnvMap}) */
 static napi_value ssgi_stage(napi_env env, napi_callback_info info, int stage) {
@@ -1229,7 +1309,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"abiVersion", n_abi_version}, {"create", n_create}, {"heldRows", n_held_rows}, {"ssgiTargetRows", n_ssgi_target_rows}, {"upload", n_upload}, {"download", n_download},
         {"clear", n_clear}, {"setEnvironment", n_set_environment}, {"setEnvironmentImportance", n_set_environment_importance}, {"packGBuffer", n_pack_gbuffer}, {"packVelocity", n_pack_velocity}, {"ssgiMarch", n_ssgi}, {"ssgiTrace", n_ssgi_trace}, {"ssgiShade", n_ssgi_shade}, {"temporalReproject", n_temporal}, {"copyFramebuffer", n_copy_framebuffer}, {"poissonDenoise", n_denoise}, {"compose", n_compose}, {"finalCompose", n_final}, {"motionBlur", n_motion_blur},
         {"motionBlurStage", n_motion_blur_stage}, {"motionBlurReachMask", n_motion_blur_reach_mask}, {"motionBlurGather", n_motion_blur_gather},
-        {"sync", n_sync}, {"setRowWindow", n_set_row_window}, {"setUvModel", n_set_uv_model}, {"cubeToEquirect", n_cube_to_equirect}, {"haloViolations", n_halo_violations}, {"timeBegin", n_time_begin}, {"timeEnd", n_time_end}, {"profile", n_profile}, {"profileRead", n_profile_read},
+        {"sync", n_sync}, {"setRowWindow", n_set_row_window}, {"setUvModel", n_set_uv_model}, {"cubeToEquirect", n_cube_to_equirect}, {"setEnvironmentCube", n_set_environment_cube}, {"buildEnvironmentImportance", n_build_environment_importance}, {"downloadEnvironmentImportance", n_download_environment_importance}, {"haloViolations", n_halo_violations}, {"timeBegin", n_time_begin}, {"timeEnd", n_time_end}, {"profile", n_profile}, {"profileRead", n_profile_read},
         {"stageUpload", n_stage_upload}, {"stageFlip", n_stage_flip}, {"hostAlloc", n_host_alloc}, {"stageAov", n_stage_aov}, {"aovStageBytes", n_aov_stage_bytes},
         {"stageExrAov", n_stage_exr_aov}, {"exrAovStageBytes", n_exr_aov_stage_bytes}, {"exrAovStatus", n_exr_aov_status},
         {"stageExrBlocks", n_stage_exr_blocks}, {"exrBlocksStageBytes", n_exr_blocks_stage_bytes},

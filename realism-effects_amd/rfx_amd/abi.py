@@ -189,6 +189,7 @@ EXPORTS = [
     "rfx_exr_blocks_stage_bytes", "rfx_stage_exr_blocks",
     "rfx_exr_blocks_piz_stage_bytes", "rfx_stage_exr_blocks_piz",
     "rfx_stage_png_ex", "rfx_png_ex", "rfx_stage_exr_ex", "rfx_exr_ex",
+    "rfx_set_environment_cube", "rfx_build_environment_importance", "rfx_download_environment_importance",
 ]
 
 _lib = None
@@ -318,6 +319,10 @@ def load_library(path: str | None = None) -> C.CDLL:
         lib.rfx_png_ex.argtypes = [vp, C.POINTER(ExportParams), i, C.c_uint, vp, C.c_size_t]
         lib.rfx_stage_exr_ex.argtypes = [vp, C.POINTER(ExportParams), C.c_uint, vp, C.c_size_t, C.POINTER(i)]
         lib.rfx_exr_ex.argtypes = [vp, C.POINTER(ExportParams), C.c_uint, vp, C.c_size_t]
+    if hasattr(lib, "rfx_build_environment_importance"):  # (additive to ABI 21: Context.has_env_device)
+        lib.rfx_set_environment_cube.argtypes = [vp, vp, i, i, i, i]
+        lib.rfx_build_environment_importance.argtypes = [vp, i]
+        lib.rfx_download_environment_importance.argtypes = [vp, vp, vp, C.POINTER(C.c_double), C.POINTER(f), C.POINTER(f)]
     if lib.rfx_abi_version() != RFX_ABI_VERSION:
         raise ImportError("librfx_hip.so ABI version %d != %d" % (lib.rfx_abi_version(), RFX_ABI_VERSION))
     if path is None:

@@ -492,12 +492,14 @@ class Context:
         """scene.environment: an (H, W, 4) float32 equirectangular map (row 0 = bottom), or None to remove it."""
         if rgba is None:
             self._chk(self.lib.rfx_set_environment(self._h, None, 0, 0, 0, 0), "rfx_set_environment")
+            self._env_size = None
             return
         a = np.ascontiguousarray(rgba, np.float32)
         if a.ndim != 3 or a.shape[2] != 4:
             raise ValueError("environment map must be (H, W, 4)")
         self._chk(self.lib.rfx_set_environment(self._h, a.ctypes.data_as(C.c_void_p), a.shape[1], a.shape[0], 1 if half_float_type else 0,
                                                1 if half_store_rtz else 0), "rfx_set_environment")
+        self._env_size = (a.shape[1], a.shape[0])  # (download_environment_importance)
 
     def set_environment_importance(self, marginal, conditional, total_sum: float):
         """The tables of EquirectHdrInfoUniform.updateFrom (rfx_amd.envmap.build_importance) for importanceSampling; totalSumValue is split the
@@ -526,6 +528,44 @@ class Context:
         self._chk(self.lib.rfx_cube_to_equirect(self._h, faces.ctypes.data_as(C.c_void_p), faces.shape[1], 1 if generate_mipmaps else 0,
                                                 out.ctypes.data_as(C.c_void_p), int(width), int(height)), "rfx_cube_to_equirect")
         return out
+
+    @property
+    def has_env_device(self) -> bool:
+        """the library keeps environment updates on the device (rfx_set_environment_cube / rfx_build_environment_importance: additive to ABI 21)"""
+        return hasattr(self.lib, "rfx_build_environment_importance")
+
+    def _need_env_device(self, what):
+        if not self.has_env_device:
+            raise RuntimeError("%s: this librfx_hip.so has no rfx_build_environment_importance (Context.has_env_device)" % what)
+
+    def set_environment_cube(self, faces, width: int, height: int, generate_mipmaps: bool = False):
+        """cube_to_equirect + set_environment(..., half_float_type=False, half_store_rtz=False) with the equirectangular map never leaving the
+        device (rfx_set_environment_cube): stream-ordered, `faces` may be reused on return.  Invalidates the importance tables."""
+        self._need_env_device("set_environment_cube")
+        faces = np.ascontiguousarray(faces, np.float32)
+        if faces.ndim != 4 or faces.shape[0] != 6 or faces.shape[1] != faces.shape[2] or faces.shape[3] != 4:
+            raise ValueError("set_environment_cube: faces must be (6, S, S, 4) float32")
+        self._chk(self.lib.rfx_set_environment_cube(self._h, faces.ctypes.data_as(C.c_void_p), faces.shape[1], 1 if generate_mipmaps else 0,
+                                                    int(width), int(height)), "rfx_set_environment_cube")
+        self._env_size = (int(width), int(height))
+
+    def build_environment_importance(self, flip_y: bool = False):
+        """The tables and sums of rfx_amd.envmap.build_importance, built on the device from level 0 of the held environment (K10), bit for bit;
+        `flip_y`: the texture's flipY (what the hosts pass build_importance as `texels[::-1], True`).  Stream-ordered."""
+        self._need_env_device("build_environment_importance")
+        self._chk(self.lib.rfx_build_environment_importance(self._h, 1 if flip_y else 0), "rfx_build_environment_importance")
+
+    def download_environment_importance(self):
+        """(marginalWeights float32[H], conditionalWeights float32[H, W], totalSumValue, whole, decimal) as the context holds them.  Synchronises."""
+        self._need_env_device("download_environment_importance")
+        size = self.__dict__.get("_env_size")
+        if size is None:
+            raise RfxError("download_environment_importance: no environment set")
+        m, c = np.empty(int(size[1]), np.float32), np.empty((int(size[1]), int(size[0])), np.float32)
+        total, whole, dec = C.c_double(), C.c_float(), C.c_float()
+        self._chk(self.lib.rfx_download_environment_importance(self._h, m.ctypes.data_as(C.c_void_p), c.ctypes.data_as(C.c_void_p), C.byref(total),
+                                                               C.byref(whole), C.byref(dec)), "rfx_download_environment_importance")
+        return m, c, total.value, np.float32(whole.value), np.float32(dec.value)
 
     def environment_levels(self) -> int:
         n = C.c_int()

@@ -624,7 +624,9 @@ class CubeToEquirectEnvPass:
     `isCubeTexture`, `faces` ((6, S, S, 4) float32 linear values, +X -X +Y -Y +Z -Z, row j = t as uploaded), and the two sampler fields
     the lookup depends on: `minFilter` (default LinearMipmapLinearFilter, three's Texture default) and `generateMipmaps` (default True)."""
 
-    def generateEquirectEnvMap(self, renderer, cubeMap, width=None, height=None, maxWidth=4096):
+    def generateEquirectEnvMap(self, renderer, cubeMap, width=None, height=None, maxWidth=4096, on_device=False):
+        """on_device: the draw's target stays on the device and becomes the environment there (renderer.set_environment_cube); the DataTexture
+        returned then carries no `data`."""
         get = (lambda k, d=None: cubeMap.get(k, d)) if isinstance(cubeMap, dict) else (lambda k, d=None: getattr(cubeMap, k, d))
         faces = np.ascontiguousarray(get("faces"), np.float32)
         if width is None and height is None:  # :62-69
@@ -642,6 +644,9 @@ class CubeToEquirectEnvPass:
             mips = False
         else:
             raise NotImplementedError("CubeToEquirectEnvPass: cube minFilter %r — LinearFilter and LinearMipmapLinearFilter are built" % (min_filter,))
+        if on_device:
+            renderer.set_environment_cube(faces, width, height, generate_mipmaps=mips)
+            return dict(data=None, type=FloatType, generateMipmaps=False, isCubeTexture=False)
         data = renderer.cube_to_equirect(faces, width, height, generate_mipmaps=mips)  # render + readRenderTargetPixels :76-85
         # :87-97 DataTexture(pixelBuffer, width, height, RGBAFormat, FloatType), ClampToEdge, EquirectangularReflectionMapping
         return dict(data=data, type=FloatType, generateMipmaps=False, isCubeTexture=False)
@@ -655,9 +660,12 @@ class SSGIEffect:
 
     DefaultOptions = defaultSSGIOptions
 
-    def __init__(self, composer, scene, camera, options=None, seeds=None, half_store_rtz=True):
+    def __init__(self, composer, scene, camera, options=None, seeds=None, half_store_rtz=True, env_on_device=False):
         options = dict(defaultSSGIOptions, **(options or {}))
         self._scene, self._camera, self.composer = scene, camera, composer
+        # keepEnvMapUpdated keeps a changed scene.environment on the device where the renderer can (Context.has_env_device): a cube becomes the
+        # environment without a read-back, the importance tables are built by K10 — the same bits as the host path, no host wait
+        self._env_on_device = bool(env_on_device)
         self.isUsingRenderPass = True
         if options["mode"] == "ssr":  # :70-73
             options["reprojectSpecular"] = True
@@ -802,16 +810,22 @@ class SSGIEffect:
         if env is not None:
             if self.__dict__.get("_env_uuid") is not env:
                 get = (lambda k, d=None: env.get(k, d)) if isinstance(env, dict) else (lambda k, d=None: getattr(env, k, d))
+                on_device = self._env_on_device and bool(getattr(renderer, "has_env_device", False))
                 if get("isCubeTexture"):  # :316-321 convert it to an equirectangular texture so the pass can sample it and use MIS
                     if self.__dict__.get("cubeToEquirectEnvPass") is None:
                         object.__setattr__(self, "cubeToEquirectEnvPass", CubeToEquirectEnvPass())
-                    converted = self.cubeToEquirectEnvPass.generateEquirectEnvMap(renderer, env)
+                    converted = self.cubeToEquirectEnvPass.generateEquirectEnvMap(renderer, env, on_device=on_device)
                     get = lambda k, d=None: converted.get(k, d)  # noqa: E731
                 t = get("type", HalfFloatType)
-                data = np.ascontiguousarray(get("data"), np.float32)
-                renderer.set_environment(data, half_float_type=(t == HalfFloatType), half_store_rtz=self._half_store_rtz)
+                data = None
+                if get("data") is not None:  # (None: the cube pass has set the environment on the device)
+                    data = np.ascontiguousarray(get("data"), np.float32)
+                    renderer.set_environment(data, half_float_type=(t == HalfFloatType), half_store_rtz=self._half_store_rtz)
                 u.importanceSampling = 0
-                if self._options["importanceSampling"]:  # :348-351 EquirectHdrInfoUniform.updateFrom, then the define
+                if self._options["importanceSampling"] and on_device:  # the same tables, built from the held level 0 (K10)
+                    renderer.build_environment_importance(bool(get("flipY", False)))
+                    u.importanceSampling = 1
+                elif self._options["importanceSampling"]:  # :348-351 EquirectHdrInfoUniform.updateFrom, then the define
                     from .envmap import build_importance
                     texels = data.astype(np.float16).astype(np.float32) if t == HalfFloatType else data  # the worker's fromHalfFloat view
                     # `data` is in GL row order (row 0 = bottom, as sampled).  With texture.flipY the reference's DataTexture array is the

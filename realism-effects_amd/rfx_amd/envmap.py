@@ -9,8 +9,19 @@ import numpy as np
 
 
 def _closest_index(cdf: np.ndarray, targets: np.ndarray) -> np.ndarray:
-    """binarySearchFindClosestIndexOf (:130-146): first index whose value is not below the target, capped at the last element."""
-    return np.minimum(np.searchsorted(cdf.astype(np.float64), targets, side="left"), len(cdf) - 1)
+    """binarySearchFindClosestIndexOf (:130-146): first index whose value is not below the target, capped at the last element — on a
+    monotone CDF.  A negative texel makes the CDF fall somewhere, and the worker's answer is then whatever its probe sequence (lower = 0,
+    upper = n - 1, mid = (lower + upper) >> 1) ends on, not a lower bound: that sequence is run as it stands (js/envmap.js lowerBound,
+    csrc/k10_env_tables.h k10_closest do the same)."""
+    c = cdf.astype(np.float64)
+    if not (c[1:] < c[:-1]).any():
+        return np.minimum(np.searchsorted(c, targets, side="left"), len(c) - 1)
+    lo, hi = np.zeros(len(targets), np.int64), np.full(len(targets), len(c) - 1, np.int64)
+    while (lo < hi).any():
+        mid = (lo + hi) >> 1
+        live, below = lo < hi, c[mid] < targets
+        lo, hi = np.where(live & below, mid + 1, lo), np.where(live & ~below, mid, hi)
+    return lo
 
 
 def build_importance(data: np.ndarray, flip_y: bool = False):
