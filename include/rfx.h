@@ -597,8 +597,8 @@ int rfx_stage_flip(rfx_ctx *);
 
 /* ---- streamed AOV frames (additive to ABI 21: a host checks for the symbol): the importer's planes staged like a packed dump.
  * rfx_stage_aov is rfx_stage_upload for an engine's UNPACKED attribute planes: every needed plane crosses PCIe once, on the upload stream,
- * into a staging area the context owns (allocated on first use, grown when a later call needs more, freed by rfx_destroy; at most 76 bytes
- * per band pixel), and one fused pack kernel behind the copies writes the BACK buffers of the dump's input slots, which rfx_stage_flip
+ * into a staging area the context owns (allocated on first use, grown when a later call needs more, freed by rfx_destroy; at most 84 bytes
+ * per band pixel: 76 without a position plane, "AOV conventions" below), and one fused pack kernel behind the copies writes the BACK buffers of the dump's input slots, which rfx_stage_flip
  * publishes as ever.  Nothing is allocated, freed or synchronised per call.  Host-pointer lifetime and back pressure are rfx_stage_upload's:
  * a plane must stay valid and unchanged until the flip AFTER the one that publishes it has returned; pinned planes (rfx_host_alloc) make
  * the copies asynchronous, a pageable plane is accepted and simply does not overlap.
@@ -629,6 +629,60 @@ typedef struct rfx_aov_frame {
 } rfx_aov_frame;
 size_t rfx_aov_stage_bytes(const rfx_ctx *, const rfx_aov_frame *, int row0, int rows);
 int rfx_stage_aov(rfx_ctx *, const rfx_aov_frame *, int row0, int rows);
+
+/* ---- AOV conventions (additive to ABI 21: a host checks for the symbol): the planes as engines write them.
+ * rfx_aov_frame's attributes are the reference's raster passes': depth = gl_FragCoord.z with 1.0 = not covered, velocity = the uv-space
+ * pos1 - pos0 of VelocityDepthNormalMaterial.js:76-80, normal in world space.  A renderer writes a world position pass or a camera-space
+ * depth, motion in pixels with its own sign and y direction (or none: a static scene under a moving camera), often camera-space normals.
+ * rfx_set_aov_conventions says which of these the NEXT rfx_stage_aov / rfx_stage_exr_aov / rfx_stage_exr_blocks / rfx_stage_exr_blocks_piz
+ * calls stage; the pack kernel converts per pixel, in fp32, on the staged planes.  The setting is context state, read at each of those calls
+ * (set it per frame: the matrices change); NULL, or a struct whose three kinds are all 0, is the default: every call gives the bytes it gives
+ * without the setting.  It is not checkpoint state; rfx_pack_gbuffer, rfx_pack_velocity and rfx_stage_upload never read it.
+ *   depth_kind     FRAGCOORD: as above.  VIEW_Z: the 1-channel depth plane holds the positive distance along the camera axis, viewZ = -value.
+ *                  POSITION: the depth plane has 3 channels, world x, y, z (an EXR descriptor maps P.X / P.Y / P.Z to components 0..2 of
+ *                  RFX_EXR_PLANE_DEPTH).
+ *   velocity_kind  UV: as above.  SCALED: the 2-channel plane times velocity_scale, e.g. (1/W, -1/H) for pixels, y down; a negated pair for the
+ *                  other time direction.  CAMERAS: no velocity plane (one given: RFX_EINVAL); VELOCITY is written iff normal is given, the
+ *                  motion is the point's own position through velocityMatrix and prevVelocityMatrix.
+ *   normal_space   WORLD: as above.  VIEW: camera-space normals, turned by cameraMatrixWorld.
+ * Matrices are float32, column-major (M[c][r] = m[4 c + r]), named as the reference names its uniforms: velocityMatrix / prevVelocityMatrix =
+ * projectionMatrix x matrixWorldInverse of this and of the previous frame (VelocityDepthNormalMaterial.js:42-43 for an identity model matrix;
+ * a host forms the product in float64 in three's multiplyMatrices element order, then rounds).  near_, far_, perspective: the camera's, read
+ * where a FRAGCOORD depth is turned back into view Z (CAMERAS).  has_background_position: a texel whose position equals background_position
+ * component-wise (==) is not covered (Blender writes 0, 0, 0 there).
+ * ARITHMETIC.  IEEE binary32, uncontracted, in this order (tests/aov_convention_ref.py restates it):
+ *   mul(M, p)_i = ((M[0][i] x + M[1][i] y) + M[2][i] z) + M[3][i]
+ *   POSITION  new = mul(velocityMatrix, p); fragCoordZ = ((0.5f new.z) / new.w) + 0.5f (line 81's shape).  Covered iff x, y, z are finite, the
+ *             texel is not the background position, new.w > 0 and 0 <= fragCoordZ < 1; else depth 1.0.
+ *   VIEW_Z    cz = P[2][2] viewZ + P[3][2], cw = P[2][3] viewZ + P[3][3], the same quotient; P[0][2], P[0][3], P[1][2], P[1][3] must be 0
+ *             (RFX_EINVAL).  Covered iff the value is finite and > 0 and 0 <= fragCoordZ < 1.
+ *   CAMERAS   pos0 = (prev.xy / prev.w) 0.5f + 0.5f with prev = mul(prevVelocityMatrix, p), pos1 likewise from new, vel = pos1 - pos0 (lines
+ *             76-79).  p is the position plane's texel under POSITION; else it is rebuilt from the texel's uv ((x + 0.5f) / W, (y + 0.5f) / H)
+ *             and its view Z — perspectiveDepthToViewZ / orthographicDepthToViewZ of the depth under FRAGCOORD, -value under VIEW_Z — by
+ *             getViewPosition (ssgi_utils.frag:17-24: clipW = P[2][3] viewZ + P[3][3]; v = Pinv x (((uv, viewZ) - 0.5f) 2.0f clipW, clipW) with
+ *             all four terms of each row summed left to right; v.z = viewZ) and p = mul(cameraMatrixWorld, v).
+ *   VIEW      n_i = (C[0][i] nx + C[1][i] ny) + C[2][i] nz, C = cameraMatrixWorld, then the oct encoder as ever.
+ *   A texel that is not covered has the clear colour in GBUFFER and VELOCITY, as under the default.  Non-finite results of vel are "a
+ *   non-finite value"; payload bits and subnormal intermediates are not specified.
+ * ROWS AND BYTES.  rfx_aov_stage_bytes and its three EXR twins count the 3-channel plane; the staging area is at most 84 bytes per band pixel.
+ * A bad EXR chunk or block still reads as not covered under every depth kind: a non-finite position or view Z is staged there, not 1.
+ * RFX_EINVAL from rfx_set_aov_conventions: an unknown kind; a non-finite velocity_scale under SCALED; the four projection entries under VIEW_Z;
+ * near_ >= far_ or a non-finite one where they are read (FRAGCOORD with CAMERAS).  From the staging calls: a depth plane that has not the
+ * kind's channel count, a velocity plane under CAMERAS. */
+enum { RFX_AOV_DEPTH_FRAGCOORD = 0, RFX_AOV_DEPTH_VIEW_Z = 1, RFX_AOV_DEPTH_POSITION = 2 };
+enum { RFX_AOV_VELOCITY_UV = 0, RFX_AOV_VELOCITY_SCALED = 1, RFX_AOV_VELOCITY_CAMERAS = 2 };
+enum { RFX_AOV_NORMAL_WORLD = 0, RFX_AOV_NORMAL_VIEW = 1 };
+typedef struct rfx_aov_conventions {
+    int32_t depth_kind, velocity_kind, normal_space;
+    int32_t perspective;
+    float velocity_scale[2];
+    float near_, far_;
+    float velocityMatrix[16], prevVelocityMatrix[16];
+    float projectionMatrix[16], projectionMatrixInverse[16], cameraMatrixWorld[16];
+    int32_t has_background_position;
+    float background_position[3];
+} rfx_aov_conventions;
+int rfx_set_aov_conventions(rfx_ctx *, const rfx_aov_conventions *);   /* NULL: back to the default */
 
 /* ---- streamed EXR frames (additive to ABI 21: a host checks for the symbol): rfx_stage_aov for an AOV frame that is still a compressed OpenEXR
  * file.  The scanline chunks cross PCIe as they sit in the file, on the upload stream; K9 (csrc/k9_exr_import.hip) inflates them — one wave per

@@ -80,7 +80,7 @@ __global__ __launch_bounds__(256) void k0_pack_velocity(K0Velocity A) {
 }
 
 // ---------------------------------------------------------------- K0 AOV pack: the two packers above, fused, for rfx_stage_aov (include/rfx.h "streamed AOV frames")
-// One pass over the flat pixel run of a segment (rfx_launch.h rfx_aov_plan_for): 44 .. 76 B in per pixel, 52 B out.  Lane t owns the four
+// One pass over the flat pixel run of a segment (rfx_launch.h rfx_aov_plan_for): 44 .. 76 B in per pixel (84 with a float position plane), 52 B out.  Lane t owns the four
 // consecutive pixels [4 t, 4 t + 4), as K7's does: a float plane of C channels is C 16-byte loads, a half plane C 8-byte loads (C / 2 16-byte
 // loads for an even C), and every slot leaves as 16-byte stores — four G-buffer, four velocity and four direct-light texels and the four depth
 // values.  Normal and depth are read once for both packed texels.  The pixels mod 4 left over go to the lane after the last group, element by
@@ -142,14 +142,114 @@ RFX_DEV uint4 k0_aov_velocity_texel(float depth, float vx, float vy, uint32_t no
     if (depth == 1.0f) return make_uint4(0u, 0u, 0u, 0x3f800000u);
     return make_uint4(__float_as_uint(vx), __float_as_uint(vy), normal, __float_as_uint(depth));
 }
+// ---- conventions in use (include/rfx.h "AOV conventions"): the planes as an engine writes them -> the depth and velocity the packers above take.
+// Everything here is decided by wave-uniform branches on K0AovConv; the arithmetic is the header's, operation for operation (this file is built
+// uncontracted), restated by tests/aov_convention_ref.py.
+RFX_DEV bool k0_finite(float a) { return (__float_as_uint(a) & 0x7f800000u) != 0x7f800000u; }
+RFX_DEV void k0_conv_mul(const float *M, float x, float y, float z, float *r) {  // mul(M, p)
+#pragma unroll
+    for (int i = 0; i < 4; i++) r[i] = ((M[i] * x + M[4 + i] * y) + M[8 + i] * z) + M[12 + i];
+}
+RFX_DEV float k0_conv_frag_z(float cz, float cw) { return ((0.5f * cz) / cw) + 0.5f; }  // VelocityDepthNormalMaterial.js:81
+// One texel.  dp: the depth plane's widened texel (three values under POSITION, else one); (x, y): its frame coordinates, read only where the
+// world point is rebuilt from uv and view Z; vel: in, the velocity plane's texel (UV, SCALED); out, the uv-space velocity.  -> gl_FragCoord.z,
+// 1.0 where the texel is not covered.
+RFX_DEV float k0_conv_pixel(const K0AovConv &v, const float *dp, int x, int y, bool want_velocity, float *vel) {
+    float depth = dp[0], viewZ = 0.0f;
+    if (v.depth_kind == RFX_AOV_DEPTH_POSITION) {
+        float n[4];
+        k0_conv_mul(v.VM, dp[0], dp[1], dp[2], n);
+        const float fz = k0_conv_frag_z(n[2], n[3]);
+        const bool background = v.has_background && dp[0] == v.background[0] && dp[1] == v.background[1] && dp[2] == v.background[2];
+        const bool covered = k0_finite(dp[0]) && k0_finite(dp[1]) && k0_finite(dp[2]) && !background && n[3] > 0.0f && fz >= 0.0f && fz < 1.0f;
+        depth = covered ? fz : 1.0f;
+    } else if (v.depth_kind == RFX_AOV_DEPTH_VIEW_Z) {
+        viewZ = -dp[0];
+        const float fz = k0_conv_frag_z(v.P[10] * viewZ + v.P[14], v.P[11] * viewZ + v.P[15]);
+        const bool covered = k0_finite(dp[0]) && dp[0] > 0.0f && fz >= 0.0f && fz < 1.0f;
+        depth = covered ? fz : 1.0f;
+    }
+    if (!want_velocity) return depth;
+    if (v.velocity_kind == RFX_AOV_VELOCITY_SCALED) {
+        vel[0] = vel[0] * v.scale[0];
+        vel[1] = vel[1] * v.scale[1];
+    } else if (v.velocity_kind == RFX_AOV_VELOCITY_CAMERAS) {
+        float w[4] = {dp[0], dp[1], dp[2], 1.0f};
+        if (v.depth_kind != RFX_AOV_DEPTH_POSITION) {
+            if (v.depth_kind == RFX_AOV_DEPTH_FRAGCOORD) viewZ = rfx_depth_to_view_z(dp[0], v.near_, v.far_, v.perspective != 0);
+            const float u = ((float)x + 0.5f) / (float)v.W, uv_v = ((float)y + 0.5f) / (float)v.H;
+            // getViewPosition ssgi_utils.frag:17-24, as K1 evaluates it
+            const float clipW = v.P[11] * viewZ + v.P[15];
+            const float4 pp = rfx_mat_mul(v.Pi, ((u - 0.5f) * 2.0f) * clipW, ((uv_v - 0.5f) * 2.0f) * clipW, ((viewZ - 0.5f) * 2.0f) * clipW, 1.0f * clipW);
+            k0_conv_mul(v.C, pp.x, pp.y, viewZ, w);
+        }
+        float n[4], p[4];
+        k0_conv_mul(v.VM, w[0], w[1], w[2], n);
+        k0_conv_mul(v.PVM, w[0], w[1], w[2], p);
+        // VelocityDepthNormalMaterial.js:76-79
+        const float pos0x = (p[0] / p[3]) * 0.5f + 0.5f, pos0y = (p[1] / p[3]) * 0.5f + 0.5f;
+        const float pos1x = (n[0] / n[3]) * 0.5f + 0.5f, pos1y = (n[1] / n[3]) * 0.5f + 0.5f;
+        vel[0] = pos1x - pos0x;
+        vel[1] = pos1y - pos0y;
+    }
+    return depth;
+}
+RFX_DEV float3 k0_conv_normal(const K0AovConv &v, float3 n) {  // camera space -> world space
+    if (v.normal_space != RFX_AOV_NORMAL_VIEW) return n;
+    const float *C = v.C;
+    return make_float3((C[0] * n.x + C[4] * n.y) + C[8] * n.z, (C[1] * n.x + C[5] * n.y) + C[9] * n.z, (C[2] * n.x + C[6] * n.y) + C[10] * n.z);
+}
+// the frame coordinates of the segment's pixel i: one integer divide per lane, the lane's other pixels step with a row wrap
+RFX_DEV bool k0_conv_needs_xy(const K0AovConv &v, bool want_velocity) {
+    return want_velocity && v.velocity_kind == RFX_AOV_VELOCITY_CAMERAS && v.depth_kind != RFX_AOV_DEPTH_POSITION;
+}
+RFX_DEV void k0_conv_xy(const K0AovConv &v, int i, int &x, int &y) {
+    const int r = i / v.W;
+    x = i - r * v.W;
+    y = v.row0 + r;
+}
+RFX_DEV void k0_conv_step(const K0AovConv &v, int &x, int &y) {
+    if (++x == v.W) { x = 0; y++; }
+}
+// lane g's four pixels: depth plane (and velocity plane, where the kind has one) -> d[4], vel[8]
 template <int SET>
-__global__ __launch_bounds__(RFX_K0_AOV_BLOCK) void k0_aov_pack(K0AovArgs A) {
+RFX_DEV void k0_conv_group(const K0AovConvArgs &A, size_t g, float *d, float *vel) {
+    const K0AovConv &v = A.v;
+    const bool want = A.velocity != nullptr, hd = k0_aov_half<SET>(A, RFX_AOV_DEPTH);
+    float dp[12];
+    if (v.depth_kind == RFX_AOV_DEPTH_POSITION) {
+        k0_aov_load4<3>(A.plane[RFX_AOV_DEPTH], hd, g, dp);
+    } else {
+        float z[4];
+        k0_aov_load4<1>(A.plane[RFX_AOV_DEPTH], hd, g, z);
+#pragma unroll
+        for (int k = 0; k < 4; k++) { dp[3 * k] = z[k]; dp[3 * k + 1] = 0.0f; dp[3 * k + 2] = 0.0f; }
+    }
+#pragma unroll
+    for (int k = 0; k < 8; k++) vel[k] = 0.0f;
+    if (want && v.velocity_kind != RFX_AOV_VELOCITY_CAMERAS) k0_aov_load4<2>(A.plane[RFX_AOV_VELOCITY], k0_aov_half<SET>(A, RFX_AOV_VELOCITY), g, vel);
+    int x = 0, y = 0;
+    if (k0_conv_needs_xy(v, want)) k0_conv_xy(v, 4 * (int)g, x, y);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        d[k] = k0_conv_pixel(v, dp + 3 * k, x, y, want, vel + 2 * k);
+        k0_conv_step(v, x, y);
+    }
+}
+template <bool CONV>
+struct K0AovBlock { typedef K0AovArgs type; };
+template <>
+struct K0AovBlock<true> { typedef K0AovConvArgs type; };
+// CONV false: the default, on K0AovArgs alone — its source path is the one this kernel had before the conventions
+template <int SET, bool CONV>
+__global__ __launch_bounds__(RFX_K0_AOV_BLOCK) void k0_aov_pack(typename K0AovBlock<CONV>::type A) {
     const int t = blockIdx.x * RFX_K0_AOV_BLOCK + threadIdx.x;
     const bool packs = A.gbuffer || A.velocity;
     if (t < A.groups) {
         const size_t g = (size_t)t;
-        float d[4];
-        k0_aov_load4<1>(A.plane[RFX_AOV_DEPTH], k0_aov_half<SET>(A, RFX_AOV_DEPTH), g, d);
+        float d[4], cv[8];
+        if constexpr (CONV) k0_conv_group<SET>(A, g, d, cv);
+        else k0_aov_load4<1>(A.plane[RFX_AOV_DEPTH], k0_aov_half<SET>(A, RFX_AOV_DEPTH), g, d);
         float *od = A.depth + g * 4;  // (dword-aligned only when the segment's first texel is not a multiple of four: four dwords, one store where the target allows)
         od[0] = d[0]; od[1] = d[1]; od[2] = d[2]; od[3] = d[3];
         uint32_t nrm[4] = {0u, 0u, 0u, 0u};
@@ -157,7 +257,10 @@ __global__ __launch_bounds__(RFX_K0_AOV_BLOCK) void k0_aov_pack(K0AovArgs A) {
             float n[12];
             k0_aov_load4<3>(A.plane[RFX_AOV_NORMAL], k0_aov_half<SET>(A, RFX_AOV_NORMAL), g, n);
 #pragma unroll
-            for (int k = 0; k < 4; k++) nrm[k] = k0_pack_normal(make_float3(n[3 * k], n[3 * k + 1], n[3 * k + 2]));
+            for (int k = 0; k < 4; k++) {
+                if constexpr (CONV) nrm[k] = k0_pack_normal(k0_conv_normal(A.v, make_float3(n[3 * k], n[3 * k + 1], n[3 * k + 2])));
+                else nrm[k] = k0_pack_normal(make_float3(n[3 * k], n[3 * k + 1], n[3 * k + 2]));
+            }
         }
         if (A.gbuffer) {
             float c[16], r[4], m[4], e[12];
@@ -171,7 +274,10 @@ __global__ __launch_bounds__(RFX_K0_AOV_BLOCK) void k0_aov_pack(K0AovArgs A) {
         }
         if (A.velocity) {
             float v[8];
-            k0_aov_load4<2>(A.plane[RFX_AOV_VELOCITY], k0_aov_half<SET>(A, RFX_AOV_VELOCITY), g, v);
+            if constexpr (CONV) {
+#pragma unroll
+                for (int k = 0; k < 8; k++) v[k] = cv[k];
+            } else k0_aov_load4<2>(A.plane[RFX_AOV_VELOCITY], k0_aov_half<SET>(A, RFX_AOV_VELOCITY), g, v);
             uint4 *o = A.velocity + g * 4;
 #pragma unroll
             for (int k = 0; k < 4; k++) o[k] = k0_aov_velocity_texel(d[k], v[2 * k], v[2 * k + 1], nrm[k]);
@@ -184,15 +290,35 @@ __global__ __launch_bounds__(RFX_K0_AOV_BLOCK) void k0_aov_pack(K0AovArgs A) {
             for (int k = 0; k < 4; k++) o[k] = make_uint4(__float_as_uint(q[4 * k]), __float_as_uint(q[4 * k + 1]), __float_as_uint(q[4 * k + 2]), __float_as_uint(q[4 * k + 3]));
         }
     } else if (t == A.groups) {
+        int cx = 0, cy = 0;
+        if constexpr (CONV) {
+            if (k0_conv_needs_xy(A.v, A.velocity != nullptr)) k0_conv_xy(A.v, A.tail_start, cx, cy);
+        }
         for (int k = 0; k < A.tail_pixels; k++) {
             const size_t px = (size_t)A.tail_start + k;
-            const float d = k0_aov_elem(A.plane[RFX_AOV_DEPTH], k0_aov_half<SET>(A, RFX_AOV_DEPTH), px);
+            float d, cv[2] = {0.0f, 0.0f};
+            if constexpr (CONV) {
+                const bool hd = k0_aov_half<SET>(A, RFX_AOV_DEPTH), want = A.velocity != nullptr;
+                const void *pd = A.plane[RFX_AOV_DEPTH];
+                float dp[3] = {0.0f, 0.0f, 0.0f};
+                if (A.v.depth_kind == RFX_AOV_DEPTH_POSITION) { dp[0] = k0_aov_elem(pd, hd, 3 * px); dp[1] = k0_aov_elem(pd, hd, 3 * px + 1); dp[2] = k0_aov_elem(pd, hd, 3 * px + 2); }
+                else dp[0] = k0_aov_elem(pd, hd, px);
+                if (want && A.v.velocity_kind != RFX_AOV_VELOCITY_CAMERAS) {
+                    const bool h = k0_aov_half<SET>(A, RFX_AOV_VELOCITY);
+                    cv[0] = k0_aov_elem(A.plane[RFX_AOV_VELOCITY], h, 2 * px);
+                    cv[1] = k0_aov_elem(A.plane[RFX_AOV_VELOCITY], h, 2 * px + 1);
+                }
+                d = k0_conv_pixel(A.v, dp, cx, cy, want, cv);
+                k0_conv_step(A.v, cx, cy);
+            } else d = k0_aov_elem(A.plane[RFX_AOV_DEPTH], k0_aov_half<SET>(A, RFX_AOV_DEPTH), px);
             A.depth[px] = d;
             uint32_t nrm = 0u;
             if (packs) {
                 const bool h = k0_aov_half<SET>(A, RFX_AOV_NORMAL);
                 const void *p = A.plane[RFX_AOV_NORMAL];
-                nrm = k0_pack_normal(make_float3(k0_aov_elem(p, h, 3 * px), k0_aov_elem(p, h, 3 * px + 1), k0_aov_elem(p, h, 3 * px + 2)));
+                const float3 n = make_float3(k0_aov_elem(p, h, 3 * px), k0_aov_elem(p, h, 3 * px + 1), k0_aov_elem(p, h, 3 * px + 2));
+                if constexpr (CONV) nrm = k0_pack_normal(k0_conv_normal(A.v, n));
+                else nrm = k0_pack_normal(n);
             }
             if (A.gbuffer) {
                 const bool hc = k0_aov_half<SET>(A, RFX_AOV_DIFFUSE), he = k0_aov_half<SET>(A, RFX_AOV_EMISSIVE);
@@ -204,9 +330,13 @@ __global__ __launch_bounds__(RFX_K0_AOV_BLOCK) void k0_aov_pack(K0AovArgs A) {
                                                      k0_aov_elem(A.plane[RFX_AOV_METALNESS], k0_aov_half<SET>(A, RFX_AOV_METALNESS), px), e);
             }
             if (A.velocity) {
-                const bool h = k0_aov_half<SET>(A, RFX_AOV_VELOCITY);
-                const void *p = A.plane[RFX_AOV_VELOCITY];
-                A.velocity[px] = k0_aov_velocity_texel(d, k0_aov_elem(p, h, 2 * px), k0_aov_elem(p, h, 2 * px + 1), nrm);
+                if constexpr (CONV) {
+                    A.velocity[px] = k0_aov_velocity_texel(d, cv[0], cv[1], nrm);
+                } else {
+                    const bool h = k0_aov_half<SET>(A, RFX_AOV_VELOCITY);
+                    const void *p = A.plane[RFX_AOV_VELOCITY];
+                    A.velocity[px] = k0_aov_velocity_texel(d, k0_aov_elem(p, h, 2 * px), k0_aov_elem(p, h, 2 * px + 1), nrm);
+                }
             }
             if (A.direct) {
                 const bool h = k0_aov_half<SET>(A, RFX_AOV_DIRECT);
@@ -228,15 +358,28 @@ hipError_t rfx_launch_pack_gbuffer(int W, int rows, const float *diffuse, const 
     hipLaunchKernelGGL(k0_pack_gbuffer, grid, block, 0, stream, A);
     return hipGetLastError();
 }
-// the three specialisations: no half plane, the typed set (every plane the segment reads but velocity and depth), any other mix
-hipError_t rfx_launch_k0_aov(const K0AovArgs &A, int blocks, hipStream_t stream) {
+// the three specialisations: no half plane, the typed set (every plane the segment reads but velocity and depth), any other mix; each of them
+// once more with conventions in use
+template <bool CONV, class Block>
+static void k0_aov_launch(int set, const Block &B, int blocks, hipStream_t stream) {
+    if (set == 0) hipLaunchKernelGGL((k0_aov_pack<0, CONV>), dim3(blocks), dim3(RFX_K0_AOV_BLOCK), 0, stream, B);
+    else if (set == 1) hipLaunchKernelGGL((k0_aov_pack<1, CONV>), dim3(blocks), dim3(RFX_K0_AOV_BLOCK), 0, stream, B);
+    else hipLaunchKernelGGL((k0_aov_pack<2, CONV>), dim3(blocks), dim3(RFX_K0_AOV_BLOCK), 0, stream, B);
+}
+hipError_t rfx_launch_k0_aov(const K0AovArgs &A, int blocks, hipStream_t stream, const K0AovConv *conv) {
     if (!A.plane[RFX_AOV_DEPTH] || !A.depth || blocks <= 0) return hipErrorInvalidValue;
     unsigned int given = 0;
     for (int i = 0; i < RFX_AOV_PLANES; i++) given |= A.plane[i] ? 1u << i : 0u;
     const unsigned int halves = A.half_mask & given, typed = given & ~((1u << RFX_AOV_VELOCITY) | (1u << RFX_AOV_DEPTH));
-    if (halves == 0u) hipLaunchKernelGGL(k0_aov_pack<0>, dim3(blocks), dim3(RFX_K0_AOV_BLOCK), 0, stream, A);
-    else if (halves == typed) hipLaunchKernelGGL(k0_aov_pack<1>, dim3(blocks), dim3(RFX_K0_AOV_BLOCK), 0, stream, A);
-    else hipLaunchKernelGGL(k0_aov_pack<2>, dim3(blocks), dim3(RFX_K0_AOV_BLOCK), 0, stream, A);
+    const int set = halves == 0u ? 0 : halves == typed ? 1 : 2;
+    if (conv) {
+        if (conv->W <= 0 || conv->H <= 0) return hipErrorInvalidValue;
+        if (A.velocity && conv->velocity_kind != RFX_AOV_VELOCITY_CAMERAS && !A.plane[RFX_AOV_VELOCITY]) return hipErrorInvalidValue;
+        K0AovConvArgs B;
+        static_cast<K0AovArgs &>(B) = A;
+        B.v = *conv;
+        k0_aov_launch<true>(set, B, blocks, stream);
+    } else k0_aov_launch<false>(set, A, blocks, stream);
     return hipGetLastError();
 }
 hipError_t rfx_launch_pack_velocity(int W, int rows, const float *velocity, const float *normal, const float *depth, void *out, hipStream_t stream) {

@@ -391,8 +391,11 @@ __global__ __launch_bounds__(256) void k9_exr_finish(K9Args A) {
         const int s = k9_segment(A, RFX_AOV_DEPTH, fy);
         if (s < 0) continue;
         const size_t dst = (size_t)(fy - A.seg_row0[s]) * A.W + (size_t)ck.x + x;
-        if (A.plane_half[RFX_AOV_DEPTH]) ((unsigned short *)A.seg_plane[s][RFX_AOV_DEPTH])[dst] = (unsigned short)0x3c00u;
-        else ((float *)A.seg_plane[s][RFX_AOV_DEPTH])[dst] = 1.0f;
+        const int dc = A.plane_ch[RFX_AOV_DEPTH];
+        for (int ch = 0; ch < dc; ch++) {
+            if (A.plane_half[RFX_AOV_DEPTH]) ((unsigned short *)A.seg_plane[s][RFX_AOV_DEPTH])[dst * dc + ch] = (unsigned short)(A.depth_bad_nan ? 0x7e00u : 0x3c00u);
+            else ((unsigned int *)A.seg_plane[s][RFX_AOV_DEPTH])[dst * dc + ch] = A.depth_bad_nan ? 0x7fc00000u : 0x3f800000u;
+        }
     }
 }
 

@@ -92,6 +92,10 @@ struct rfx_ctx {
     // texture slot nor checkpoint state
     void *aov_stage = nullptr;
     size_t aov_stage_cap = 0;
+    // rfx_set_aov_conventions (include/rfx.h "AOV conventions"): what the next staging call reads; aov_conv_on false: the default, whatever
+    // aov_conv holds.  Context state, not checkpoint state
+    bool aov_conv_on = false;
+    rfx_aov_conventions aov_conv = {};
     // rfx_stage_exr_aov: the device area of a call's tables, packed chunks and inflate scratch (the same owner and growth rule); two pinned host
     // blocks the tables are written into before they are copied (batch n uses block n & 1: rfx_stage_flip's back pressure says the copies of batch
     // n - 2 have executed; calls of one batch append); the pinned status words and the event behind their copy
@@ -149,6 +153,9 @@ extern "C" int rfx_internal_scaled_rows(int W, int H, int Hs, int uv_model, int 
 extern "C" int rfx_internal_export_plan(int pixels, int format, int channels, struct rfx_export_plan *out);
 // (held_row0, held_rows: the rows GBUFFER / VELOCITY / DIRECT_LIGHT hold; type, channels: eight entries in rfx_aov_frame's order, channels 0 = not given)
 extern "C" int rfx_internal_aov_plan(int W, int H, int held_row0, int held_rows, const int *type, const int *channels, int row0, int rows, struct rfx_aov_plan *out);
+// ... with the kinds of include/rfx.h "AOV conventions" (rfx_launch.h rfx_aov_plan_conv_for)
+extern "C" int rfx_internal_aov_plan_conv(int W, int H, int held_row0, int held_rows, const int *type, const int *channels, int row0, int rows, int depth_kind,
+                                          int velocity_kind, struct rfx_aov_plan *out);
 extern "C" int rfx_internal_exr_piz_tables(int piz_blocks, struct rfx_exr_piz_tables *out);
 extern "C" int rfx_internal_k3_tile(int W, int H, float radius, int inputIsTemporal, int textureCount, struct rfx_k3_tile_plan *out);
 

@@ -20,14 +20,15 @@ struct ExrPlan {
     int rle_chunks = 0, piz_chunks = 0;
 };
 // all the planner reads of a context: the frame, and the rows RFX_TEX_GBUFFER holds (VELOCITY and DIRECT_LIGHT hold the same)
-struct ExrGeom { int W, H, held_row0, held_rows; };
-static ExrGeom exr_geom(const rfx_ctx *c) { return {c->W, c->H, c->slots[RFX_TEX_GBUFFER].row0, c->slots[RFX_TEX_GBUFFER].rows}; }
+// ... and the kinds of its AOV conventions (include/rfx.h): a position plane has three components, CAMERAS no velocity plane
+struct ExrGeom { int W, H, held_row0, held_rows, depth_kind, velocity_kind; };
+static ExrGeom exr_geom(const rfx_ctx *c) { return {c->W, c->H, c->slots[RFX_TEX_GBUFFER].row0, c->slots[RFX_TEX_GBUFFER].rows, aov_depth_kind(c), aov_velocity_kind(c)}; }
 static unsigned long long align256(unsigned long long n) { return (n + 255ull) & ~255ull; }
 
 // The parts, their channels and the planes they make.  allowed: bit k set = compression k is taken.  0, or the RFX_EINVAL case in words.
 static const char *exr_parts_plan(const ExrGeom &g, const rfx_exr_part *part, int nparts, unsigned int allowed, const char *bad_compression, int row0, int rows,
                                   ExrPlan *p) {
-    static const int want_max[RFX_AOV_PLANES] = {4, 3, 1, 1, 3, 2, 1, 4};
+    const int want_max[RFX_AOV_PLANES] = {4, 3, 1, 1, 3, 2, g.depth_kind == RFX_AOV_DEPTH_POSITION ? 3 : 1, 4};
     unsigned int comp_mask[RFX_AOV_PLANES] = {0}, any_float[RFX_AOV_PLANES] = {0};
     p->mapped.assign((size_t)nparts, 0);
     for (int k = 0; k < nparts; k++) {
@@ -60,7 +61,7 @@ static const char *exr_parts_plan(const ExrGeom &g, const rfx_exr_part *part, in
         p->channels[i] = n;
         p->type[i] = any_float[i] ? RFX_PLANE_F32 : RFX_PLANE_F16;
     }
-    return rfx_aov_plan_for(g.W, g.H, g.held_row0, g.held_rows, p->type, p->channels, row0, rows, &p->aov);
+    return rfx_aov_plan_conv_for(g.W, g.H, g.held_row0, g.held_rows, p->type, p->channels, row0, rows, g.depth_kind, g.velocity_kind, &p->aov);
 }
 
 // Coverage of the band's scanlines [y_lo, y_hi) by the blocks of ONE mapped part (first .. last: the rows of each clipped to the band, sorted by
@@ -250,6 +251,7 @@ static int stage_exr_plan(rfx_ctx *c, const ExrPlan &p, const void *data, const 
     A.packed = (const unsigned char *)packed; A.scratch = (unsigned char *)packed + p.packed_bytes;
     A.piz_chunks = p.piz_chunks; A.piz_tables = p.piz_chunks ? A.scratch + p.scratch_bytes : nullptr;
     A.W = c->W; A.H = c->H;
+    A.depth_bad_nan = aov_depth_kind(c) != RFX_AOV_DEPTH_FRAGCOORD;  // a bad block reads as not covered: a non-finite view z or position, not depth 1
     A.nseg = t.nseg;
     unsigned int half_mask = 0;
     for (int i = 0; i < RFX_AOV_PLANES; i++) {

@@ -192,3 +192,6 @@ RFX_HIDDEN void stage_plan_end(rfx_ctx *c, const rfx_aov_plan &t);
 RFX_HIDDEN int grow_stage_area(rfx_ctx *c, void **area, size_t *cap, size_t need, const char *what);
 // one segment's pack launch on the upload stream: A holds the segment's staged planes, their half mask and the rgb(a) channel counts
 RFX_HIDDEN hipError_t aov_pack_segment(rfx_ctx *c, const rfx_aov_plan &t, const rfx_aov_segment &g, K0AovArgs A);
+// the kinds the next staging call plans with (include/rfx.h "AOV conventions"; the default where nothing is set)
+RFX_HIDDEN int aov_depth_kind(const rfx_ctx *c);
+RFX_HIDDEN int aov_velocity_kind(const rfx_ctx *c);

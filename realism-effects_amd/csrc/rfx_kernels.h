@@ -20,7 +20,20 @@ struct K0AovArgs {
     float *depth;
     int groups, tail_start, tail_pixels;  // lanes [0, groups) own four pixels each; lane `groups` the tail
 };
-hipError_t rfx_launch_k0_aov(const K0AovArgs &, int blocks, hipStream_t);
+// ... with conventions in use (include/rfx.h "AOV conventions"): the setting as the kernel reads it, wave-uniform in the argument block behind
+// K0AovArgs.  (W, H, row0): the frame and the segment's first frame row, for the texels' uv.
+struct K0AovConv {
+    int depth_kind, velocity_kind, normal_space, perspective;
+    int W, H, row0;
+    int has_background;
+    float background[3];
+    float scale[2];
+    float near_, far_;
+    float VM[16], PVM[16], P[16], Pi[16], C[16];  // velocityMatrix, prevVelocityMatrix, projectionMatrix, its inverse, cameraMatrixWorld
+};
+struct K0AovConvArgs : K0AovArgs { K0AovConv v; };
+// conv null: the default kernels, on K0AovArgs alone
+hipError_t rfx_launch_k0_aov(const K0AovArgs &, int blocks, hipStream_t, const K0AovConv *conv = nullptr);
 // CubeToEquirectEnvPass (k0_cube.hip): six S x S RGBA32F faces -> a W x H RGBA32F equirectangular image
 hipError_t rfx_launch_cube_to_equirect(float4 *chain, int size, int levels, float4 *out, int W, int H, const UvPlanes &uv, hipStream_t);
 
@@ -242,5 +255,6 @@ struct K9Args {
     int seg_row0[3], seg_rows[3];
     void *seg_plane[3][8];     // null: the segment does not read the plane
     int plane_ch[8], plane_half[8];
+    int depth_bad_nan;         // the depth plane of a bad block's rectangle: 0 -> 1.0; else NaN in every channel (AOV conventions: view z, position)
 };
 hipError_t rfx_launch_k9(const K9Args &, hipStream_t);

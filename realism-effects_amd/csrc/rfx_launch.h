@@ -248,22 +248,30 @@ struct rfx_aov_plan {
     unsigned long long copy_bytes, stage_bytes;                  // host -> device bytes (rfx_aov_stage_bytes); the staging area
 };
 // type / channels: per plane, channels 0 = the plane is not given.  0, or the RFX_EINVAL case in words.
-inline const char *rfx_aov_plan_for(int W, int H, int held_row0, int held_rows, const int *type, const int *channels, int row0, int rows, rfx_aov_plan *out) {
-    static const int want[RFX_AOV_PLANES] = {4, 3, 1, 1, 3, 2, 1, 4};
+// depth_kind, velocity_kind: include/rfx.h "AOV conventions" — under POSITION the depth plane has three channels; under CAMERAS there is no
+// velocity plane and VELOCITY is written iff normal is given.  (0, 0): rfx_aov_plan_for.
+inline const char *rfx_aov_plan_conv_for(int W, int H, int held_row0, int held_rows, const int *type, const int *channels, int row0, int rows, int depth_kind,
+                                         int velocity_kind, rfx_aov_plan *out) {
+    const bool position = depth_kind == RFX_AOV_DEPTH_POSITION, cameras = velocity_kind == RFX_AOV_VELOCITY_CAMERAS;
+    const int want[RFX_AOV_PLANES] = {4, 3, 1, 1, 3, 2, position ? 3 : 1, 4};
+    if (depth_kind < 0 || depth_kind > RFX_AOV_DEPTH_POSITION || velocity_kind < 0 || velocity_kind > RFX_AOV_VELOCITY_CAMERAS) return "an unknown depth or velocity kind";
     if (W <= 0 || H <= 0 || held_rows < 0) return "bad geometry";
     rfx_aov_plan t = {};
     for (int i = 0; i < RFX_AOV_PLANES; i++) {
         if (!channels[i]) continue;
         if (type[i] != RFX_PLANE_F32 && type[i] != RFX_PLANE_F16) return "a plane's type must be RFX_PLANE_F32 or RFX_PLANE_F16";
         const bool rgb_or_rgba = i == RFX_AOV_DIFFUSE || i == RFX_AOV_DIRECT;
-        if (channels[i] != want[i] && !(rgb_or_rgba && channels[i] == 3)) return "a plane's channel count (diffuse, direct: 3 or 4; normal, emissive: 3; velocity: 2; the others: 1)";
+        if (channels[i] != want[i] && !(rgb_or_rgba && channels[i] == 3))
+            return i == RFX_AOV_DEPTH && (position || channels[i] == 3) ? "the depth plane holds a world position (3 channels) under RFX_AOV_DEPTH_POSITION and under it alone"
+                                                                         : "a plane's channel count (diffuse, direct: 3 or 4; normal, emissive: 3; velocity: 2; the others: 1)";
         t.elem_bytes[i] = type[i] == RFX_PLANE_F16 ? 2 : 4;
     }
     if (!channels[RFX_AOV_DEPTH]) return "the depth plane is required";
     const bool normal = channels[RFX_AOV_NORMAL] != 0;
     const int g = (channels[RFX_AOV_DIFFUSE] != 0) + (channels[RFX_AOV_ROUGHNESS] != 0) + (channels[RFX_AOV_METALNESS] != 0) + (channels[RFX_AOV_EMISSIVE] != 0);
     t.write_gbuffer = g == 4 && normal;
-    t.write_velocity = channels[RFX_AOV_VELOCITY] != 0;
+    if (cameras && channels[RFX_AOV_VELOCITY]) return "a velocity plane under RFX_AOV_VELOCITY_CAMERAS";
+    t.write_velocity = cameras ? normal : channels[RFX_AOV_VELOCITY] != 0;
     t.write_direct = channels[RFX_AOV_DIRECT] != 0;
     if (t.write_velocity && !normal) return "a velocity plane needs the normal plane";
     if (!t.write_gbuffer && (g != 0 || (normal && !t.write_velocity)))
@@ -295,6 +303,9 @@ inline const char *rfx_aov_plan_for(int W, int H, int held_row0, int held_rows, 
     }
     *out = t;
     return nullptr;
+}
+inline const char *rfx_aov_plan_for(int W, int H, int held_row0, int held_rows, const int *type, const int *channels, int row0, int rows, rfx_aov_plan *out) {
+    return rfx_aov_plan_conv_for(W, H, held_row0, held_rows, type, channels, row0, rows, RFX_AOV_DEPTH_FRAGCOORD, RFX_AOV_VELOCITY_UV, out);
 }
 
 // ---------------------------------------------------------------- shared by the launchers

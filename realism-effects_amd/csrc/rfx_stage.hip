@@ -60,8 +60,22 @@ hipError_t aov_pack_segment(rfx_ctx *c, const rfx_aov_plan &t, const rfx_aov_seg
     if (g.full && t.write_velocity) A.velocity = (uint4 *)first(RFX_TEX_VELOCITY);
     if (g.full && t.write_direct) A.direct = (uint4 *)first(RFX_TEX_DIRECT_LIGHT);
     A.groups = g.groups; A.tail_start = g.tail_start; A.tail_pixels = g.tail_pixels;
-    return rfx_launch_k0_aov(A, g.blocks, c->upload_stream);
+    if (!c->aov_conv_on) return rfx_launch_k0_aov(A, g.blocks, c->upload_stream);
+    // conventions in use: the setting as it stands at this call, with the segment's place in the frame
+    const rfx_aov_conventions &q = c->aov_conv;
+    K0AovConv v = {};
+    v.depth_kind = q.depth_kind; v.velocity_kind = q.velocity_kind; v.normal_space = q.normal_space; v.perspective = q.perspective;
+    v.W = c->W; v.H = c->H; v.row0 = g.row0;
+    v.has_background = q.has_background_position != 0;
+    for (int i = 0; i < 3; i++) v.background[i] = q.background_position[i];
+    v.scale[0] = q.velocity_scale[0]; v.scale[1] = q.velocity_scale[1];
+    v.near_ = q.near_; v.far_ = q.far_;
+    memcpy(v.VM, q.velocityMatrix, sizeof v.VM); memcpy(v.PVM, q.prevVelocityMatrix, sizeof v.PVM);
+    memcpy(v.P, q.projectionMatrix, sizeof v.P); memcpy(v.Pi, q.projectionMatrixInverse, sizeof v.Pi); memcpy(v.C, q.cameraMatrixWorld, sizeof v.C);
+    return rfx_launch_k0_aov(A, g.blocks, c->upload_stream, &v);
 }
+int aov_depth_kind(const rfx_ctx *c) { return c->aov_conv_on ? c->aov_conv.depth_kind : RFX_AOV_DEPTH_FRAGCOORD; }
+int aov_velocity_kind(const rfx_ctx *c) { return c->aov_conv_on ? c->aov_conv.velocity_kind : RFX_AOV_VELOCITY_UV; }
 
 // ---- streamed AOV frames (include/rfx.h): the planes of rfx_pack_gbuffer / rfx_pack_velocity / the depth and direct uploads, staged once on the
 // upload stream and packed by one fused kernel (k0_import.hip k0_aov_pack) into the back buffers rfx_stage_flip publishes
@@ -76,7 +90,7 @@ static const char *aov_plan(const rfx_ctx *c, const rfx_aov_frame *f, int row0, 
         if (p.data && p.channels <= 0) return "a plane's channel count";
     }
     const Slot &g = c->slots[RFX_TEX_GBUFFER];  // (VELOCITY and DIRECT_LIGHT hold the same rows)
-    return rfx_aov_plan_for(c->W, c->H, g.row0, g.rows, type, channels, row0, rows, t);
+    return rfx_aov_plan_conv_for(c->W, c->H, g.row0, g.rows, type, channels, row0, rows, aov_depth_kind(c), aov_velocity_kind(c), t);
 }
 
 extern "C" {
@@ -132,6 +146,29 @@ int rfx_stage_aov(rfx_ctx *c, const rfx_aov_frame *f, int row0, int rows) {
         HIPCHK(c, aov_pack_segment(c, t, g, A));
     }
     stage_plan_end(c, t);
+    return RFX_OK;
+}
+
+int rfx_set_aov_conventions(rfx_ctx *c, const rfx_aov_conventions *q) {
+    if (!c) return RFX_EINVAL;
+    RFX_ENTER(c);
+    const char *fn = "rfx_set_aov_conventions";
+    if (!q) { c->aov_conv_on = false; return RFX_OK; }
+    if (q->depth_kind < 0 || q->depth_kind > RFX_AOV_DEPTH_POSITION) return fail_in(c, RFX_EINVAL, fn, "an unknown depth_kind");
+    if (q->velocity_kind < 0 || q->velocity_kind > RFX_AOV_VELOCITY_CAMERAS) return fail_in(c, RFX_EINVAL, fn, "an unknown velocity_kind");
+    if (q->normal_space < 0 || q->normal_space > RFX_AOV_NORMAL_VIEW) return fail_in(c, RFX_EINVAL, fn, "an unknown normal_space");
+    if (q->velocity_kind == RFX_AOV_VELOCITY_SCALED && !(isfinite(q->velocity_scale[0]) && isfinite(q->velocity_scale[1])))
+        return fail_in(c, RFX_EINVAL, fn, "a non-finite velocity_scale");
+    if (q->depth_kind == RFX_AOV_DEPTH_VIEW_Z) {
+        const float *P = q->projectionMatrix;  // P[c][r] = P[4 c + r]
+        if (!(P[2] == 0.0f && P[3] == 0.0f && P[6] == 0.0f && P[7] == 0.0f))
+            return fail_in(c, RFX_EINVAL, fn, "RFX_AOV_DEPTH_VIEW_Z needs projectionMatrix[0][2], [0][3], [1][2] and [1][3] to be 0: clip z and w must depend on view z alone");
+    }
+    if (q->depth_kind == RFX_AOV_DEPTH_FRAGCOORD && q->velocity_kind == RFX_AOV_VELOCITY_CAMERAS && !(isfinite(q->near_) && isfinite(q->far_) && q->near_ < q->far_))
+        return fail_in(c, RFX_EINVAL, fn, "near_ >= far_ (or a non-finite one) where the depth is turned back into view z");
+    c->aov_conv = *q;
+    // (all three kinds 0 is the default: the default kernels run and nothing else of the struct is read)
+    c->aov_conv_on = q->depth_kind != 0 || q->velocity_kind != 0 || q->normal_space != 0;
     return RFX_OK;
 }
 

@@ -132,6 +132,65 @@ class Renderer {
 		addon.stageAov(this._h, planes, row0 === undefined ? 0 : row0, rows === undefined ? this.height - (row0 || 0) : rows)
 		this._stagedAov = planes // keep the planes alive while they are in flight
 	}
+	// AOV conventions (rfx.h): what the next stageAov / stageExrAov / stageExrBlocks calls take their depth, velocity and normal planes for —
+	// { depth_kind: "fragcoord" | "view_z" | "position", velocity_kind: "uv" | "scaled" | "cameras", normal_space: "world" | "view", perspective,
+	// velocity_scale: [sx, sy], near, far, velocityMatrix, prevVelocityMatrix, projectionMatrix, projectionMatrixInverse, cameraMatrixWorld (16
+	// column-major floats each), background_position: [x, y, z] | null }: the record rfx_amd.conventions.AovConventions.to_json writes.
+	// null / undefined: the default.  Set per frame: the matrices change.  Under "position" / "view_z" the depth plane holds that.
+	get hasAovConventions() {
+		return typeof addon.setAovConventions === "function"
+	}
+	static velocityMatrix(projectionMatrix, matrixWorldInverse) {
+		// three's Matrix4.multiplyMatrices on the float32 elements, every sum in float64 left to right, rounded once: what the reference uploads
+		// for an identity model matrix (the Python host forms the same 16 floats: conventions.multiply_matrices)
+		const a = projectionMatrix, b = matrixWorldInverse, out = new Float32Array(16)
+		for (let j = 0; j < 4; j++) {
+			for (let i = 0; i < 4; i++) {
+				let s = a[i] * b[4 * j]
+				s = s + a[4 + i] * b[4 * j + 1]
+				s = s + a[8 + i] * b[4 * j + 2]
+				s = s + a[12 + i] * b[4 * j + 3]
+				out[4 * j + i] = s
+			}
+		}
+		return out
+	}
+	// a record without matrices (a dump directory's, a command line's) completed from the frame's cameras
+	static conventionsFor(record, camera, prevCamera) {
+		const prev = prevCamera || camera
+		return Object.assign({
+			perspective: camera.isPerspectiveCamera !== false, near: camera.near, far: camera.far,
+			velocityMatrix: Renderer.velocityMatrix(Float32Array.from(camera.projectionMatrix), Float32Array.from(camera.matrixWorldInverse)),
+			prevVelocityMatrix: Renderer.velocityMatrix(Float32Array.from(prev.projectionMatrix), Float32Array.from(prev.matrixWorldInverse)),
+			projectionMatrix: camera.projectionMatrix, projectionMatrixInverse: camera.projectionMatrixInverse, cameraMatrixWorld: camera.matrixWorld
+		}, record)
+	}
+	setAovConventions(conv) {
+		if (!this.hasAovConventions) throw new Error("this addon has no setAovConventions")
+		this._conventionsSet = !(conv === null || conv === undefined)
+		if (conv === null || conv === undefined) return addon.setAovConventions(this._h, null, null)
+		const pick = (table, v, what) => {
+			if (!(v in table)) throw new RangeError("AOV conventions: " + what + " " + Object.keys(table).join(" | "))
+			return table[v]
+		}
+		const bg = conv.background_position
+		const kinds = Int32Array.of(
+			pick({ fragcoord: 0, view_z: 1, position: 2 }, conv.depth_kind === undefined ? "fragcoord" : conv.depth_kind, "depth_kind"),
+			pick({ uv: 0, scaled: 1, cameras: 2 }, conv.velocity_kind === undefined ? "uv" : conv.velocity_kind, "velocity_kind"),
+			pick({ world: 0, view: 1 }, conv.normal_space === undefined ? "world" : conv.normal_space, "normal_space"),
+			conv.perspective === false ? 0 : 1, bg ? 1 : 0)
+		const f = new Float32Array(87)
+		const scale = conv.velocity_scale || [1, 1]
+		f[0] = scale[0]; f[1] = scale[1]; f[2] = conv.near || 0; f[3] = conv.far || 0
+		const names = ["velocityMatrix", "prevVelocityMatrix", "projectionMatrix", "projectionMatrixInverse", "cameraMatrixWorld"]
+		names.forEach((n, k) => {
+			const m = conv[n] || [1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1]
+			if (m.length !== 16) throw new RangeError("AOV conventions: " + n + " has 16 elements")
+			f.set(m, 4 + 16 * k)
+		})
+		if (bg) f.set(bg, 84)
+		addon.setAovConventions(this._h, kinds, f)
+	}
 	aovStageBytes(planes, row0, rows) {
 		return addon.aovStageBytes(this._h, planes, row0 === undefined ? 0 : row0, rows === undefined ? this.height - (row0 || 0) : rows)
 	}
@@ -171,6 +230,9 @@ class Renderer {
 	// a frame with packed planes, or — no `gbuffer` — with `aov` attribute planes
 	stageFrame(frame) {
 		if (!frame.gbuffer) {
+			// an engine-form frame (dump.js): its conventions are set for this call; a reference-form frame after one resets them
+			if (frame.aovConventions) this.setAovConventions(Renderer.conventionsFor(frame.aovConventions, frame.camera, frame.prevCamera))
+			else if (this._conventionsSet) this.setAovConventions(null)
 			this.stageAov(Object.assign({ depth: frame.depth, direct: frame.direct }, frame.aov))
 			this._staged = frame
 			return

@@ -9,6 +9,11 @@
 // A plane whose values are halves may be stored as IEEE binary16 — aov_<name>.f16.bin / direct.f16.bin instead of the .bin — and is read as a
 // Uint16Array of half bits: the typed frame Renderer.stageAov sends at two bytes per element (widenHalf gives the Float32Array the
 // synchronous loaders take).  diffuse and direct may have three channels (alpha 1): the count follows from the file size.
+// An ENGINE-FORM dump (include/rfx.h "AOV conventions") carries the planes as a renderer writes them: aov_position(.f16).bin (world x, y, z:
+// W*H*3) or aov_view_z(.f16).bin (positive camera-axis distance: W*H) in place of depth.bin, aov_normal in camera space, aov_velocity in the
+// engine's units or absent (velocity_kind "cameras"), and frame.json's "aovConventions": the record rfx_amd.conventions.AovConventions.to_json
+// writes (kinds, velocity_scale, background_position; the matrices when present, else derived from the frame's cameras).  frame.depth is then
+// that plane, frame.aovConventions the record; such a frame is staged (Renderer.stageFrame: --stream true), the device converts.
 const fs = require("fs")
 const path = require("path")
 
@@ -82,12 +87,20 @@ function readDump(dir) {
 		height: meta.height,
 		camera: meta.camera,
 		prevCamera: meta.prevCamera,
-		depth: plane(path.join(dir, "depth.bin"), Float32Array),
+		depth: null,
+		aovConventions: meta.aovConventions || null,
 		direct: typedPlane(dir, "direct", n, [3, 4]),
 		gbuffer: null,
 		velocity: null,
 		aov: null
 	}
+	const has = stem => fs.existsSync(path.join(dir, stem + ".bin")) || fs.existsSync(path.join(dir, stem + ".f16.bin"))
+	let depthChannels = 1
+	if (has("aov_position")) {
+		frame.depth = typedPlane(dir, "aov_position", n, [3])
+		depthChannels = 3
+	} else if (has("aov_view_z")) frame.depth = typedPlane(dir, "aov_view_z", n, [1])
+	else frame.depth = plane(path.join(dir, "depth.bin"), Float32Array)
 	if (fs.existsSync(path.join(dir, "gbuffer.bin"))) {
 		frame.gbuffer = plane(path.join(dir, "gbuffer.bin"), Uint32Array)
 		frame.velocity = plane(path.join(dir, "velocity.bin"), Uint32Array)
@@ -95,10 +108,11 @@ function readDump(dir) {
 	} else {
 		frame.aov = {}
 		for (const kc of [["diffuse", 4], ["normal", 3], ["roughness", 1], ["metalness", 1], ["emissive", 3], ["velocity", 2]]) {
+			if (kc[0] === "velocity" && !has("aov_velocity")) continue // (velocity_kind "cameras": no motion plane)
 			frame.aov[kc[0]] = typedPlane(dir, "aov_" + kc[0], n, kc[0] === "diffuse" ? [3, 4] : [kc[1]])
 		}
 	}
-	if (frame.depth.length !== n) throw new Error("dump " + dir + ": plane sizes do not match frame.json")
+	if (frame.depth.length !== depthChannels * n) throw new Error("dump " + dir + ": plane sizes do not match frame.json")
 	return frame
 }
 

@@ -219,6 +219,7 @@ class ExrNotStreamable extends Error {}
 // PIZ, deep data, UINT channels, parts of different data windows.
 // options.piz = true (with forms "blocks"; rfx.h "EXR blocks with PIZ"): PIZ parts too — compression 4, a scanline block of 32 rows —, which
 // Renderer.stageExrBlocks sends through rfx_stage_exr_blocks_piz; tiles of 128 x 128 texels or more stay ExrNotStreamable.  The default refuses PIZ.
+const ENGINE_DEPTH_LAYOUT = { position: ["position.X", "position.Y", "position.Z"], view_z: ["depth.Z"] }
 function exrAovLayout(buffer, names, options) {
 	const forms = (options && options.forms) || "scanline"
 	if (forms !== "scanline" && forms !== "blocks") throw new Error('forms: "scanline" or "blocks"')
@@ -253,7 +254,17 @@ function exrAovLayout(buffer, names, options) {
 		if (!multipart || b[pos] === 0) break
 	}
 	if (multipart) pos++
-	const layout = Object.assign({}, AOV_LAYOUT, names || {})
+	// names may carry ONE of `position` / `view_z` (rfx.h "AOV conventions": an array of channel names, or null for the default ones): the
+	// depth plane is then fed by those channels — components 0..2 of a world position, or the view Z
+	const given = Object.assign({}, names || {})
+	const engine = Object.keys(ENGINE_DEPTH_LAYOUT).filter(k => k in given)
+	if (engine.length > 1 || (engine.length && "depth" in given)) throw new RangeError("names: depth, position and view_z are one plane")
+	for (const k of engine) {
+		given.depth = given[k] && given[k].length ? Array.from(given[k]) : ENGINE_DEPTH_LAYOUT[k]
+		if (given.depth.length !== ENGINE_DEPTH_LAYOUT[k].length) throw new RangeError("names: " + k + " has " + ENGINE_DEPTH_LAYOUT[k].length + " channels")
+		delete given[k]
+	}
+	const layout = Object.assign({}, AOV_LAYOUT, given)
 	const feeds = {}
 	Object.keys(AOV_LAYOUT).forEach((key, pi) => layout[key].forEach((cn, j) => (feeds[cn] = [pi, j])))
 	const partWords = [headers.length], records = [], seen = {}
@@ -355,4 +366,4 @@ function exrAovLayout(buffer, names, options) {
 	return { width: W, height: H, fileBytes: b.length, parts: Int32Array.from(partWords), chunks: new Uint8Array(chunks.buffer, chunks.byteOffset, chunks.length), chunkCount: records.length, planes }
 }
 
-module.exports = { writePNG, pngFromFragments, writeEXR, exrFromFragments, writePFM, tonemap, exrAovLayout, ExrNotStreamable, AOV_LAYOUT }
+module.exports = { writePNG, pngFromFragments, writeEXR, exrFromFragments, writePFM, tonemap, exrAovLayout, ExrNotStreamable, AOV_LAYOUT, ENGINE_DEPTH_LAYOUT }

@@ -146,7 +146,18 @@ function writeMotionBlur(mb) {
 const seeds = { ssgi: opt.ssgiSeed === undefined ? 11 : opt.ssgiSeed, denoise: opt.denoiseSeed === undefined ? 22 : opt.denoiseSeed }
 delete opt.ssgiSeed
 delete opt.denoiseSeed
-const first = rfx.readDump(dumps[0])
+// --aovConventions '{"depth_kind": "view_z", "velocity_kind": "scaled", "velocity_scale": [sx, sy], ...}': the unpacked dumps are in an engine's
+// conventions (rfx.h "AOV conventions"; the record of rfx_amd.conventions.AovConventions.to_json, matrices optional: they come from each frame's
+// cameras) — for directories whose frame.json does not say so itself.  Engine-form frames are converted on the device: --stream true.
+const aovConventions = opt.aovConventions || null
+delete opt.aovConventions
+const readDump = d => {
+	const f = rfx.readDump(d)
+	if (aovConventions && !f.gbuffer) f.aovConventions = aovConventions
+	return f
+}
+const first = readDump(dumps[0])
+if (first.aovConventions && !(stream && !tiled)) throw new Error("engine-form AOV planes (aovConventions) are converted by the staged import: add --stream true")
 const scene = { frame: first }
 // --env <file.bin> --envWidth W --envHeight H [--envFlipY true]: a raw Float32 RGBA equirect map (row 0 = bottom) as scene.environment, a
 // HalfFloatType texture; --envFlipY: its flipY is set (the importance tables are then built from the worker's "un-flipped" rows)
@@ -193,7 +204,7 @@ if (tiled) {
 	// halo: the K3 tap footprint, the largest vertical motion of the sequence and K1's source rows at --resolutionScale (rfx_amd/tiling.py required_halo)
 	let vmax = 0
 	for (const d of dumps) {
-		const f = d === dumps[0] ? first : rfx.readDump(d)
+		const f = d === dumps[0] ? first : readDump(d)
 		if (!f.velocity) throw new Error("--ranks needs packed velocity.bin dumps")
 		const v = new Float32Array(f.velocity.buffer, f.velocity.byteOffset, f.velocity.length)
 		for (let i = 1; i < v.length; i += 4) if (Math.abs(v[i]) > vmax) vmax = Math.abs(v[i])
@@ -244,7 +255,7 @@ if (opt.traa) {
 	if (framesOut && !mb && framesOut.format === "exr") throw new Error("--framesOut with --traa alone: png or pfm (TRAA's alpha of 1 is written by the host's traa_compose)")
 	openFrames()
 	dumps.forEach((d, i) => {
-		const f = d === dumps[0] ? first : rfx.readDump(d)
+		const f = d === dumps[0] ? first : readDump(d)
 		scene.frame = f
 		Object.assign(camera, f.camera)
 		traa.update(renderer, { texture: { type: half ? rfx.HalfFloatType : rfx.FloatType }, width: f.width, height: f.height, data: rfx.floatPlane(f.direct, f.width * f.height, 4) })
@@ -304,7 +315,7 @@ if (stream && !tiled) {
 		dst.set(src)
 	}
 	const load = (d, set) => { // disk -> pinned planes (a reader thread's job in a long run)
-		const f = d === dumps[0] ? first : rfx.readDump(d)
+		const f = d === dumps[0] ? first : readDump(d)
 		for (const k of top) fill(set[k], f[k], d + " " + k)
 		if (set.aov) for (const k of Object.keys(set.aov)) fill(set.aov[k], f.aov && f.aov[k], d + " aov " + k)
 		return Object.assign({}, f, set, { static: "resident" })
@@ -327,7 +338,7 @@ if (stream && !tiled) {
 	}
 } else
 	dumps.forEach((d, i) => {
-		const f = d === dumps[0] ? first : rfx.readDump(d)
+		const f = d === dumps[0] ? first : readDump(d)
 		scene.frame = f
 		Object.assign(camera, f.camera)
 		frameEnvironment(i)

@@ -294,6 +294,43 @@ static napi_value aov_call(napi_env env, napi_callback_info info, int stage) {
     if (rc) return throw_rfx(env, c, "rfx_stage_aov", rc);
     return NULL;
 }
+/* setAovConventions(ctx, kinds, floats): rfx_set_aov_conventions (rfx.h "AOV conventions").  kinds: an Int32Array [depth_kind, velocity_kind,
+ * normal_space, perspective, has_background_position]; floats: a Float32Array of 87 in the struct's order — velocity_scale[2], near_, far_, the
+ * five matrices, background_position[3].  kinds null / undefined: back to the default. */
+static napi_value n_set_aov_conventions(napi_env env, napi_callback_info info) {
+    napi_value a[3];
+    if (!get_args(env, info, 3, a)) return NULL;
+    rfx_ctx *c = get_ctx(env, a[0]);
+    if (!c) return NULL;
+    napi_valuetype vt = napi_undefined;
+    napi_typeof(env, a[1], &vt);
+    if (vt == napi_null || vt == napi_undefined) {
+        int rc = rfx_set_aov_conventions(c, NULL);
+        if (rc) return throw_rfx(env, c, "rfx_set_aov_conventions", rc);
+        return NULL;
+    }
+    napi_typedarray_type tk, tf;
+    size_t nk, nf;
+    void *pk, *pf;
+    if (napi_get_typedarray_info(env, a[1], &tk, &nk, &pk, NULL, NULL) != napi_ok || tk != napi_int32_array || nk != 5 ||
+        napi_get_typedarray_info(env, a[2], &tf, &nf, &pf, NULL, NULL) != napi_ok || tf != napi_float32_array || nf != 87) {
+        napi_throw_type_error(env, NULL, "setAovConventions: an Int32Array of 5 and a Float32Array of 87 expected");
+        return NULL;
+    }
+    const int32_t *k = (const int32_t *)pk;
+    const float *f = (const float *)pf;
+    rfx_aov_conventions q;
+    memset(&q, 0, sizeof q);
+    q.depth_kind = k[0]; q.velocity_kind = k[1]; q.normal_space = k[2]; q.perspective = k[3]; q.has_background_position = k[4];
+    q.velocity_scale[0] = f[0]; q.velocity_scale[1] = f[1];
+    q.near_ = f[2]; q.far_ = f[3];
+    memcpy(q.velocityMatrix, f + 4, 64); memcpy(q.prevVelocityMatrix, f + 20, 64); memcpy(q.projectionMatrix, f + 36, 64);
+    memcpy(q.projectionMatrixInverse, f + 52, 64); memcpy(q.cameraMatrixWorld, f + 68, 64);
+    memcpy(q.background_position, f + 84, 12);
+    int rc = rfx_set_aov_conventions(c, &q);
+    if (rc) return throw_rfx(env, c, "rfx_set_aov_conventions", rc);
+    return NULL;
+}
 static napi_value n_stage_aov(napi_env env, napi_callback_info info) { return aov_call(env, info, 1); }
 static napi_value n_aov_stage_bytes(napi_env env, napi_callback_info info) { return aov_call(env, info, 0); }
 /* An EXR frame descriptor (rfx.h "streamed EXR frames") from what imageio.exrAovLayout returns: `bytes` the file (a Uint8Array / Buffer, ideally over
@@ -1310,7 +1347,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"clear", n_clear}, {"setEnvironment", n_set_environment}, {"setEnvironmentImportance", n_set_environment_importance}, {"packGBuffer", n_pack_gbuffer}, {"packVelocity", n_pack_velocity}, {"ssgiMarch", n_ssgi}, {"ssgiTrace", n_ssgi_trace}, {"ssgiShade", n_ssgi_shade}, {"temporalReproject", n_temporal}, {"copyFramebuffer", n_copy_framebuffer}, {"poissonDenoise", n_denoise}, {"compose", n_compose}, {"finalCompose", n_final}, {"motionBlur", n_motion_blur},
         {"motionBlurStage", n_motion_blur_stage}, {"motionBlurReachMask", n_motion_blur_reach_mask}, {"motionBlurGather", n_motion_blur_gather},
         {"sync", n_sync}, {"setRowWindow", n_set_row_window}, {"setUvModel", n_set_uv_model}, {"cubeToEquirect", n_cube_to_equirect}, {"setEnvironmentCube", n_set_environment_cube}, {"buildEnvironmentImportance", n_build_environment_importance}, {"downloadEnvironmentImportance", n_download_environment_importance}, {"haloViolations", n_halo_violations}, {"timeBegin", n_time_begin}, {"timeEnd", n_time_end}, {"profile", n_profile}, {"profileRead", n_profile_read},
-        {"stageUpload", n_stage_upload}, {"stageFlip", n_stage_flip}, {"hostAlloc", n_host_alloc}, {"stageAov", n_stage_aov}, {"aovStageBytes", n_aov_stage_bytes},
+        {"stageUpload", n_stage_upload}, {"stageFlip", n_stage_flip}, {"hostAlloc", n_host_alloc}, {"stageAov", n_stage_aov}, {"setAovConventions", n_set_aov_conventions},{"aovStageBytes", n_aov_stage_bytes},
         {"stageExrAov", n_stage_exr_aov}, {"exrAovStageBytes", n_exr_aov_stage_bytes}, {"exrAovStatus", n_exr_aov_status},
         {"stageExrBlocks", n_stage_exr_blocks}, {"exrBlocksStageBytes", n_exr_blocks_stage_bytes},
         {"stageExrBlocksPiz", n_stage_exr_blocks_piz}, {"exrBlocksPizStageBytes", n_exr_blocks_piz_stage_bytes},

@@ -116,6 +116,20 @@ class AovFrame(C.Structure):
     _fields_ = [(name, Plane) for name in AOV_PLANES]
 
 
+# rfx.h "AOV conventions": the planes as engines write them (rfx_set_aov_conventions, additive to ABI 21)
+AOV_DEPTH_FRAGCOORD, AOV_DEPTH_VIEW_Z, AOV_DEPTH_POSITION = 0, 1, 2
+AOV_VELOCITY_UV, AOV_VELOCITY_SCALED, AOV_VELOCITY_CAMERAS = 0, 1, 2
+AOV_NORMAL_WORLD, AOV_NORMAL_VIEW = 0, 1
+
+
+class AovConventions(C.Structure):
+    _fields_ = [("depth_kind", C.c_int32), ("velocity_kind", C.c_int32), ("normal_space", C.c_int32), ("perspective", C.c_int32),
+                ("velocity_scale", C.c_float * 2), ("near_", C.c_float), ("far_", C.c_float),
+                ("velocityMatrix", C.c_float * 16), ("prevVelocityMatrix", C.c_float * 16),
+                ("projectionMatrix", C.c_float * 16), ("projectionMatrixInverse", C.c_float * 16), ("cameraMatrixWorld", C.c_float * 16),
+                ("has_background_position", C.c_int32), ("background_position", C.c_float * 3)]
+
+
 # rfx.h "streamed EXR frames": the descriptor of rfx_stage_exr_aov (OpenEXR's own numbers for compression and pixel type)
 EXR_NONE, EXR_ZIPS, EXR_ZIP = 0, 2, 3
 EXR_HALF, EXR_FLOAT = 1, 2
@@ -190,6 +204,7 @@ EXPORTS = [
     "rfx_exr_blocks_piz_stage_bytes", "rfx_stage_exr_blocks_piz",
     "rfx_stage_png_ex", "rfx_png_ex", "rfx_stage_exr_ex", "rfx_exr_ex",
     "rfx_set_environment_cube", "rfx_build_environment_importance", "rfx_download_environment_importance",
+    "rfx_set_aov_conventions",
 ]
 
 _lib = None
@@ -323,6 +338,8 @@ def load_library(path: str | None = None) -> C.CDLL:
         lib.rfx_set_environment_cube.argtypes = [vp, vp, i, i, i, i]
         lib.rfx_build_environment_importance.argtypes = [vp, i]
         lib.rfx_download_environment_importance.argtypes = [vp, vp, vp, C.POINTER(C.c_double), C.POINTER(f), C.POINTER(f)]
+    if hasattr(lib, "rfx_set_aov_conventions"):  # (additive to ABI 21: Context.has_aov_conventions)
+        lib.rfx_set_aov_conventions.argtypes = [vp, C.POINTER(AovConventions)]
     if lib.rfx_abi_version() != RFX_ABI_VERSION:
         raise ImportError("librfx_hip.so ABI version %d != %d" % (lib.rfx_abi_version(), RFX_ABI_VERSION))
     if path is None:

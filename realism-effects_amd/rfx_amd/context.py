@@ -116,6 +116,12 @@ class Context:
     def stage_frame(self, frame):
         """Stage a whole dumped frame: its packed planes, or — a frame with `aov` instead of `gbuffer` — its attribute planes (stage_aov)."""
         if getattr(frame, "gbuffer", None) is None:
+            conv = getattr(frame, "conventions", None)  # an engine-form frame (dump.read_dump): its conventions hold for this call
+            if conv is not None:
+                self.set_aov_conventions(conv)
+                self.__dict__["_frame_conventions"] = True
+            elif self.__dict__.pop("_frame_conventions", False):
+                self.set_aov_conventions(None)
             planes = dict(frame.aov)
             planes["depth"] = frame.depth
             if getattr(frame, "direct", None) is not None:
@@ -133,6 +139,11 @@ class Context:
         dtype (float32 / float16), the channel count from the size."""
         row0 = 0 if row0 is None else int(row0)
         rows = self.H - row0 if rows is None else int(rows)
+        alias = [k for k in ("depth", "position", "view_z") if planes.get(k) is not None]
+        if len(alias) > 1:
+            raise ValueError("AOV frame: %s are one plane (the depth plane under the conventions set)" % " and ".join(alias))
+        if alias and alias[0] != "depth":  # set_aov_conventions says which of the three the library takes the depth plane for
+            planes = {("depth" if k == alias[0] else k): v for k, v in planes.items() if k not in ("depth", "position", "view_z") or k == alias[0]}
         unknown = set(planes) - set(abi.AOV_PLANES)
         if unknown:
             raise ValueError("AOV frame: unknown planes %s" % sorted(unknown))
@@ -151,6 +162,20 @@ class Context:
             setattr(f, name, abi.Plane(a.ctypes.data, abi.PLANE_TYPES[a.dtype], a.size // texels))
         return f, row0, rows, keep
 
+    # -- AOV conventions (rfx.h "AOV conventions"): the planes as engines write them, converted by the pack kernel
+    @property
+    def has_aov_conventions(self) -> bool:
+        """the library exports rfx_set_aov_conventions (additive to ABI 21)"""
+        return hasattr(self.lib, "rfx_set_aov_conventions")
+
+    def set_aov_conventions(self, conv=None):
+        """rfx_set_aov_conventions: what the next stage_aov / stage_exr_aov / stage_exr_blocks calls take their depth, velocity and normal planes
+        for (conventions.AovConventions, or an abi.AovConventions); None: the default.  Set per frame: the matrices change."""
+        if not self.has_aov_conventions:
+            raise RfxError("this librfx_hip.so has no rfx_set_aov_conventions")
+        c = conv.to_abi() if hasattr(conv, "to_abi") else conv
+        self._chk(self.lib.rfx_set_aov_conventions(self._h, None if c is None else C.byref(c)), "rfx_set_aov_conventions")
+
     def aov_stage_bytes(self, planes: dict, row0: int | None = None, rows: int | None = None) -> int:
         """rfx_aov_stage_bytes: the bytes stage_aov(planes, row0, rows) copies host -> device (0: the library would refuse the frame)"""
         f, row0, rows, _ = self._aov_frame(planes, row0, rows)
@@ -159,7 +184,8 @@ class Context:
     def stage_aov(self, planes: dict, row0: int | None = None, rows: int | None = None):
         """rfx_stage_aov: the attribute planes of rows [row0, row0+rows) of the FRAME (default: all of it) -> the back buffers of DEPTH and of
         the slots the planes name (GBUFFER: diffuse, normal, roughness, metalness, emissive; VELOCITY: velocity, normal; DIRECT_LIGHT: direct);
-        published by stage_flip().  host_alloc() planes make the copies asynchronous."""
+        published by stage_flip().  host_alloc() planes make the copies asynchronous.  With set_aov_conventions the depth plane may be given
+        as `position` (3 channels, depth_kind "position") or `view_z` (depth_kind "view_z") instead of `depth`."""
         f, row0, rows, keep = self._aov_frame(planes, row0, rows)
         self.__dict__.setdefault("_staged_now", []).extend(keep)  # kept alive until the copies of this batch have executed
         self._chk(self.lib.rfx_stage_aov(self._h, C.byref(f), row0, rows), "rfx_stage_aov")
@@ -250,24 +276,30 @@ class Context:
         else:
             self._chk(self.lib.rfx_stage_exr_blocks(self._h, C.byref(f), *self._band(row0, rows)), "rfx_stage_exr_blocks")
 
-    def stage_exr_device(self, buf, names: dict | None = None, piz: bool = False):
+    def stage_exr_device(self, buf, names: dict | None = None, piz: bool = False, conventions=None):
         """One whole AOV EXR file held in `buf` through the device decode: the blocks form where the library has it, else the scanline form.
-        piz=True: PIZ parts too, where the library has rfx_stage_exr_blocks_piz.  imageio.ExrNotStreamable: the file is one neither takes."""
+        piz=True: PIZ parts too, where the library has rfx_stage_exr_blocks_piz.  imageio.ExrNotStreamable: the file is one neither takes.
+        conventions: this frame's conventions.AovConventions, set before the call (the context keeps them until the next set)."""
         from . import imageio
+        if conventions is not None:
+            self.set_aov_conventions(conventions)
         if self.has_exr_blocks:
             self.stage_exr_blocks(buf, imageio.exr_aov_layout(buf, names, forms="blocks", piz=piz and self.has_exr_piz))
         else:
             self.stage_exr_aov(buf, imageio.exr_aov_layout(buf, names))
 
-    def stage_exr_frame(self, path: str, decode: str = "host", names: dict | None = None, piz: bool = False):
+    def stage_exr_frame(self, path: str, decode: str = "host", names: dict | None = None, piz: bool = False, conventions=None):
         """Stage a whole AOV EXR file.  decode="host" (the default): imageio.exr_to_typed_planes + stage_aov.  decode="device": the file's bytes
         + stage_exr_blocks (stage_exr_aov on a library without it); a file the device decode does not take (imageio.ExrNotStreamable: PIZ, deep
         data, UINT channels, ...) goes the host's way.  piz=True (with decode="device"): a PIZ file is decoded on the device too where the library
         has the entry points (has_exr_piz); the default keeps it on the host.
+        conventions: this frame's conventions.AovConventions (names= then maps `position` / `view_z`), set before the planes are staged.
         -> the way taken, "host" or "device"."""
         from . import imageio
         if decode not in ("host", "device"):
             raise ValueError("decode: \"host\" or \"device\"")
+        if conventions is not None:
+            self.set_aov_conventions(conventions)
         if decode == "device":
             with open(path, "rb") as f:
                 data = f.read()

@@ -51,9 +51,19 @@ def _plane_file(dirname, stem, half=None):
     return os.path.join(dirname, stem + ".bin"), np.float32
 
 
-def write_dump(dirname: str, frame, packed: bool = True, half=()) -> None:
-    """`half` (unpacked dumps): the names among the AOV planes and "direct" to store as binary16 (the values are rounded if they are no halves)"""
+_ENGINE_DEPTH = {"position": ("aov_position", 3), "view_z": ("aov_view_z", 1)}  # depth_kind -> (file stem, channels) of the plane that stands for depth.bin
+
+
+def write_dump(dirname: str, frame, packed: bool = True, half=(), conventions=None) -> None:
+    """`half` (unpacked dumps): the names among the AOV planes and "direct" to store as binary16 (the values are rounded if they are no halves).
+    `conventions` (unpacked dumps; conventions.AovConventions): an ENGINE-FORM dump (rfx.h "AOV conventions") — frame.depth is the depth plane
+    in the setting's kind and is written as aov_position(.f16).bin / aov_view_z(.f16).bin ("depth" in `half` stores it as halves), frame.aov
+    holds the planes as the engine writes them (no "velocity" under velocity_kind "cameras"), frame.json carries the record."""
     os.makedirs(dirname, exist_ok=True)
+    if conventions is not None and packed:
+        raise ValueError("write_dump: conventions belong to an unpacked dump (packed=False)")
+    if conventions is not None:
+        return _write_engine_dump(dirname, frame, set(half), conventions)
     if packed and half:
         raise ValueError("write_dump: half planes belong to an unpacked dump (packed=False)")
     unknown = set(half) - {k for k, _ in _AOV} - {"direct"}
@@ -75,7 +85,26 @@ def write_dump(dirname: str, frame, packed: bool = True, half=()) -> None:
     np.ascontiguousarray(frame.direct, dt).tofile(path)
 
 
+def _write_engine_dump(dirname, frame, half, conventions):
+    meta = dict(width=int(frame.width), height=int(frame.height), camera=_cam_to_json(frame.camera),
+                prevCamera=_cam_to_json(getattr(frame, "prev_camera", frame.camera)), aovConventions=json.loads(conventions.to_json()))
+    with open(os.path.join(dirname, "frame.json"), "w") as f:
+        json.dump(meta, f)
+    stem = _ENGINE_DEPTH.get(conventions.depth_kind, ("depth", 1))[0]
+    path, dt = _plane_file(dirname, stem, "depth" in half and stem != "depth")
+    np.ascontiguousarray(frame.depth, dt).tofile(path)
+    for k, _ in _AOV:
+        if k == "velocity" and frame.aov.get(k) is None:
+            continue
+        path, dt = _plane_file(dirname, "aov_" + k, k in half)
+        np.ascontiguousarray(frame.aov[k], dt).tofile(path)
+    path, dt = _plane_file(dirname, "direct", "direct" in half)
+    np.ascontiguousarray(frame.direct, dt).tofile(path)
+
+
 def read_dump(dirname: str):
+    """-> a frame namespace.  An engine-form directory (write_dump(..., conventions=)): frame.conventions is its AovConventions, frame.depth the
+    position / view Z plane, and Context.stage_frame sets the one before it stages the other; else frame.conventions is None."""
     with open(os.path.join(dirname, "frame.json")) as f:
         meta = json.load(f)
     W, H = meta["width"], meta["height"]
@@ -89,13 +118,24 @@ def read_dump(dirname: str):
             raise ValueError("%s: %d elements do not make %s channel(s) of a %d x %d frame" % (path, a.size, " or ".join(map(str, channels)), W, H))
         return a.reshape((H, W, ch) if max(channels) > 1 else (H, W))
 
+    has = lambda stem: any(os.path.exists(os.path.join(dirname, stem + e)) for e in (".bin", ".f16.bin"))  # noqa: E731
+    engine = [v for v in _ENGINE_DEPTH.values() if has(v[0])]
+    depth = typed(engine[0][0], (engine[0][1],)) if engine else rd("depth.bin", np.float32, (H, W))
+    conv = None
+    if meta.get("aovConventions"):
+        from .conventions import MATRICES, AovConventions
+        rec = dict(meta["aovConventions"])
+        cams = AovConventions.from_cameras(_cam_from_json(meta["camera"]), _cam_from_json(meta["prevCamera"]))
+        for k in MATRICES + ("near", "far", "perspective"):  # (a record without the cameras' part: from the frame's own cameras)
+            rec.setdefault(k, getattr(cams, k))
+        conv = AovConventions.from_json(rec)
     fr = types.SimpleNamespace(width=W, height=H, camera=_cam_from_json(meta["camera"]), prev_camera=_cam_from_json(meta["prevCamera"]),
-                               depth=rd("depth.bin", np.float32, (H, W)), direct=typed("direct", (3, 4)), gbuffer=None, velocity=None,
-                               aov=None)
+                               depth=depth, direct=typed("direct", (3, 4)), gbuffer=None, velocity=None,
+                               aov=None, conventions=conv)
     if os.path.exists(os.path.join(dirname, "gbuffer.bin")):
         fr.gbuffer, fr.velocity = rd("gbuffer.bin", np.uint32, (H, W, 4)), rd("velocity.bin", np.uint32, (H, W, 4))
     else:
-        fr.aov = {k: typed("aov_" + k, (3, 4) if k == "diffuse" else (ch,)) for k, ch in _AOV}
+        fr.aov = {k: typed("aov_" + k, (3, 4) if k == "diffuse" else (ch,)) for k, ch in _AOV if not (k == "velocity" and not has("aov_velocity"))}
     return fr
 
 
@@ -123,7 +163,7 @@ def read_exr_dump(path: str, names: dict | None = None, typed: bool = False):
     planes = (imageio.exr_to_typed_planes if typed else imageio.exr_to_dump_planes)(path, names)
     with open(path + ".json") as f:
         meta = json.load(f)
-    H, W = planes["depth"].shape
+    H, W = planes["depth"].shape[:2]  # (a world position plane — names={"position": ...} — has three channels)
     if (W, H) != (meta["width"], meta["height"]):
         raise ValueError("%s: image is %dx%d, side-car says %dx%d" % (path, W, H, meta["width"], meta["height"]))
     return types.SimpleNamespace(width=W, height=H, camera=_cam_from_json(meta["camera"]), prev_camera=_cam_from_json(meta["prevCamera"]),

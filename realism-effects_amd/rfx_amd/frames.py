@@ -106,8 +106,10 @@ class ExrSequence:
     Buffer k & 1 is refilled for frame k when the flip after frame k - 1's has returned: rfx_stage_flip's back pressure says the copies out of
     it have executed.  A file the device decode does not take (imageio.ExrNotStreamable) is read on the host (Context.stage_exr_frame): a PIZ
     file too, unless piz=True and the library has the PIZ entry points (Context.has_exr_piz)."""
-    def __init__(self, ctx, source, names: dict | None = None, piz: bool = False):
-        self.ctx, self.names, self.piz = ctx, names, piz
+    def __init__(self, ctx, source, names: dict | None = None, piz: bool = False, conventions=None):
+        """conventions: the files are in an engine's conventions (rfx.h "AOV conventions") — one conventions.AovConventions for every frame, a
+        list of them (one per frame: the cameras move), or a callable index -> AovConventions; set on the context before each frame is staged."""
+        self.ctx, self.names, self.piz, self.conventions = ctx, names, piz, conventions
         self.paths = sorted(os.path.join(source, f) for f in os.listdir(source) if f.lower().endswith(".exr")) if isinstance(source, str) else list(source)
         self.buffers = [None, None]
 
@@ -125,6 +127,10 @@ class ExrSequence:
             got = f.readinto(memoryview(buf)[:size])
         if got != size:
             raise IOError("%s: read %d of %d bytes" % (path, got, size))
+        conv = self.conventions
+        if conv is not None:
+            conv = conv(index) if callable(conv) else conv[index] if isinstance(conv, (list, tuple)) else conv
+            self.ctx.set_aov_conventions(conv)
         try:
             self.ctx.stage_exr_device(buf[:size], self.names, self.piz)  # (the blocks form where the library has it: tiled, RLE and PXR24 files too)
             return "device"

@@ -991,15 +991,111 @@ AOV_LAYOUT = {
 }
 
 
+# ... and the two forms an engine writes the depth plane in (rfx.h "AOV conventions"): names= may carry ONE of these keys — a tuple of channel
+# names, or None for the default ones — and the "depth" plane then holds the world position (H, W, 3) or the view Z (H, W).  The conventions
+# set on the context (Context.set_aov_conventions) say which; aov_to_reference_conventions converts on the host.
+ENGINE_DEPTH_LAYOUT = {"position": ("position.X", "position.Y", "position.Z"), "view_z": ("depth.Z",)}
+
+
+def _aov_layout(names: dict | None) -> dict:
+    """AOV_LAYOUT with `names` applied: {plane: channel names}, the depth plane's taken from a `position` / `view_z` entry where there is one"""
+    layout, names = dict(AOV_LAYOUT), dict(names or {})
+    engine = [k for k in ENGINE_DEPTH_LAYOUT if k in names]
+    if len(engine) > 1 or (engine and "depth" in names):
+        raise ValueError("names: depth, position and view_z are one plane")
+    for k in engine:
+        cn = names.pop(k)
+        layout["depth"] = tuple(cn) if cn else ENGINE_DEPTH_LAYOUT[k]
+        if len(layout["depth"]) != len(ENGINE_DEPTH_LAYOUT[k]):
+            raise ValueError("names: %s has %d channels" % (k, len(ENGINE_DEPTH_LAYOUT[k])))
+    layout.update(names)
+    return layout
+
+
+def aov_to_reference_conventions(planes: dict, conv, row0: int = 0, frame_height: int | None = None) -> dict:
+    """The host's form of the pack kernel's conversion (rfx.h "AOV conventions", the same float32 operations in the same order): engine-form
+    planes -> the reference-form `depth`, `velocity` and `normal` Context.stage_aov / pack_gbuffer / pack_velocity / dump.write_dump take.
+    planes: name -> array of the band's rows (row `row0` of a frame of `frame_height` rows first); the depth plane under `depth`, `position`
+    or `view_z`.  conv: conventions.AovConventions.  Every other plane is handed through.  A texel that is not covered gets depth 1; its
+    velocity is whatever the arithmetic gives (the packers write the clear colour there)."""
+    f32 = np.float32
+    out = {k: v for k, v in planes.items() if k not in ("position", "view_z")}
+    given = [k for k in ("depth", "position", "view_z") if planes.get(k) is not None]
+    if len(given) != 1:
+        raise ValueError("aov_to_reference_conventions: exactly one of depth, position, view_z")
+    d = np.asarray(planes[given[0]]).astype(f32)
+    M = {k: getattr(conv, k).astype(f32) for k in ("velocityMatrix", "prevVelocityMatrix", "projectionMatrix", "projectionMatrixInverse", "cameraMatrixWorld")}
+
+    def mul(m, x, y, z):
+        return [((m[i] * x + m[4 + i] * y) + m[8 + i] * z) + m[12 + i] for i in range(4)]
+
+    def frag_z(cz, cw):
+        return ((f32(0.5) * cz) / cw) + f32(0.5)
+
+    with np.errstate(all="ignore"):
+        world, view_z = None, None
+        if conv.depth_kind == "position":
+            if d.ndim != 3 or d.shape[-1] != 3:
+                raise ValueError("aov_to_reference_conventions: a position plane is (rows, W, 3)")
+            x, y, z = d[..., 0], d[..., 1], d[..., 2]
+            new = mul(M["velocityMatrix"], x, y, z)
+            fz = frag_z(new[2], new[3])
+            covered = np.isfinite(x) & np.isfinite(y) & np.isfinite(z) & (new[3] > 0) & (fz >= 0) & (fz < 1)
+            if conv.background_position is not None:
+                b = [f32(v) for v in conv.background_position]
+                covered &= ~((x == b[0]) & (y == b[1]) & (z == b[2]))
+            depth = np.where(covered, fz, f32(1.0)).astype(f32)
+            world = (x, y, z)
+        elif conv.depth_kind == "view_z":
+            P = M["projectionMatrix"]
+            view_z = -d
+            fz = frag_z(P[10] * view_z + P[14], P[11] * view_z + P[15])
+            covered = np.isfinite(d) & (d > 0) & (fz >= 0) & (fz < 1)
+            depth = np.where(covered, fz, f32(1.0)).astype(f32)
+        else:
+            depth = d
+        out["depth"] = depth
+        rows, W = depth.shape
+        if conv.velocity_kind == "scaled" and planes.get("velocity") is not None:
+            v = np.asarray(planes["velocity"]).astype(f32)
+            out["velocity"] = np.stack([v[..., 0] * f32(conv.velocity_scale[0]), v[..., 1] * f32(conv.velocity_scale[1])], -1).astype(f32)
+        elif conv.velocity_kind == "cameras":
+            if planes.get("velocity") is not None:
+                raise ValueError("aov_to_reference_conventions: a velocity plane under velocity_kind \"cameras\"")
+            if world is None:
+                H = rows if frame_height is None else int(frame_height)
+                if view_z is None:
+                    n_, f_ = f32(conv.near), f32(conv.far)
+                    view_z = (n_ * f_) / ((f_ - n_) * d - f_) if conv.perspective else d * (n_ - f_) - n_
+                u = ((np.arange(W, dtype=f32) + f32(0.5)) / f32(W))[None, :]
+                vv = ((np.arange(row0, row0 + rows, dtype=f32) + f32(0.5)) / f32(H))[:, None]
+                P, Pi = M["projectionMatrix"], M["projectionMatrixInverse"]
+                clip_w = P[11] * view_z + P[15]
+                cx, cy, cz, cw = ((u - f32(0.5)) * f32(2.0)) * clip_w, ((vv - f32(0.5)) * f32(2.0)) * clip_w, ((view_z - f32(0.5)) * f32(2.0)) * clip_w, f32(1.0) * clip_w
+                px = ((Pi[0] * cx + Pi[4] * cy) + Pi[8] * cz) + Pi[12] * cw
+                py = ((Pi[1] * cx + Pi[5] * cy) + Pi[9] * cz) + Pi[13] * cw
+                world = tuple(mul(M["cameraMatrixWorld"], px, py, view_z)[:3])
+            new, prev = mul(M["velocityMatrix"], *world), mul(M["prevVelocityMatrix"], *world)
+            pos0 = [(prev[i] / prev[3]) * f32(0.5) + f32(0.5) for i in range(2)]
+            pos1 = [(new[i] / new[3]) * f32(0.5) + f32(0.5) for i in range(2)]
+            out["velocity"] = np.stack([pos1[0] - pos0[0], pos1[1] - pos0[1]], -1).astype(f32)
+        if conv.normal_space == "view" and planes.get("normal") is not None:
+            n = np.asarray(planes["normal"]).astype(f32)
+            C = M["cameraMatrixWorld"]
+            out["normal"] = np.stack([(C[i] * n[..., 0] + C[4 + i] * n[..., 1]) + C[8 + i] * n[..., 2] for i in range(3)], -1).astype(f32)
+    return out
+
+
 def exr_to_dump_planes(path: str, names: dict | None = None) -> dict:
     """One multi-layer AOV EXR -> the dump's unpacked attribute planes: {"aov": {diffuse, normal, roughness, metalness, emissive,
     velocity}, "depth": (H, W), "direct": (H, W, 4)} ready for Context.pack_gbuffer / pack_velocity (the device packs them into the
     reference's texel formats) or rfx_amd.dump.write_dump."""
     ch = read_exr(path)
-    layout = dict(AOV_LAYOUT)
-    layout.update(names or {})
+    layout = _aov_layout(names)
     planes = {}
     for key, cn in layout.items():
+        if not cn:  # names={key: ()}: the file has no such layer (no velocity layer under velocity_kind "cameras")
+            continue
         missing = [c for c in cn if c not in ch]
         if missing:
             if key == "diffuse" and missing == [cn[3]]:  # no alpha layer: opaque
@@ -1031,8 +1127,7 @@ def exr_to_typed_planes(path: str, names: dict | None = None) -> dict:
     typed frame Context.stage_aov sends at two bytes per half element.  Widening any of its planes gives exr_to_dump_planes' plane, bit for bit."""
     planes = exr_to_dump_planes(path, names)
     types_ = exr_channel_types(path)
-    layout = dict(AOV_LAYOUT)
-    layout.update(names or {})
+    layout = _aov_layout(names)
     flat = dict(planes["aov"], depth=planes["depth"], direct=planes["direct"])
     for key, cn in layout.items():
         if all(types_.get(c, "half") == "half" for c in cn) and any(c in types_ for c in cn):
@@ -1120,8 +1215,7 @@ def exr_aov_layout(path_or_bytes, names: dict | None = None, forms: str = "scanl
                 raise ValueError("%s: damaged header" % what)
             head_len *= 4
     table_pos = pos + (1 if multipart else 0)
-    layout = dict(AOV_LAYOUT)
-    layout.update(names or {})
+    layout = _aov_layout(names)
     feeds = {cn: (pi, j) for pi, key in enumerate(AOV_LAYOUT) for j, cn in enumerate(layout[key])}
     parts, tables, W, H, seen, window = [], [], None, None, {}, None
     for k, attrs in enumerate(headers):

@@ -206,6 +206,7 @@ class Frame:
     prev_camera: Camera
     frame_index: int = 0
     aov: dict | None = None  # unpacked attribute planes (render(..., aov=True)): what an engine exports, input of the device importer
+    engine: dict | None = None  # the same texels in an engine's own conventions (render(..., engine=True)): position, view_z, motion, view_normal
 
 
 class AnalyticScene:
@@ -328,14 +329,19 @@ class AnalyticScene:
         return t_best, mat, nrm
 
     def render(self, width: int, height: int, frame_index: int = 0, row0: int = 0, rows: int | None = None,
-               frame_height: int | None = None, vfov_rows: int | None = None, aov: bool = False, ortho_half_height: float | None = None) -> Frame:
+               frame_height: int | None = None, vfov_rows: int | None = None, aov: bool = False, ortho_half_height: float | None = None,
+               engine: bool = False) -> Frame:
         """Dump frame `frame_index`.  (row0, rows, frame_height) select a horizontal band of a
         taller frame — used by the row-tiled multi-GPU path; default = the whole frame.
         `vfov_rows`: number of rows that span the nominal 40 deg vertical fov; a taller frame
         (weak scaling: N stacked 4K tiles) widens the vertical fov instead of squeezing the
         horizontal one.  `aov=True` also keeps the UNPACKED attribute planes an engine would export (frame.aov: diffuse RGBA,
         world normal, roughness, metalness, emissive, uv-space velocity) — the input of the device-side importer (rfx_pack_gbuffer /
-        rfx_pack_velocity), which must reproduce `gbuffer` / `velocity` from them."""
+        rfx_pack_velocity), which must reproduce `gbuffer` / `velocity` from them.  `engine=True` also keeps the same texels as a renderer
+        writes them (frame.engine; rfx.h "AOV conventions"): `position` float32 world x, y, z with (0, 0, 0) where nothing is covered, `view_z`
+        float32 positive distance along the camera axis with +inf there, `motion` float32 in pixels, y down (uv velocity times (W, -H)),
+        `view_normal` float32 camera-space normals — and, for the tests, the float64 `depth64` / `velocity64` they were rounded from and the
+        coverage `hit`.  Every other output is unchanged."""
         fh = frame_height or height
         rows = rows if rows is not None else height
         aspect = width / fh
@@ -362,6 +368,11 @@ class AnalyticScene:
             planes = dict(diffuse=np.zeros((rows, width, 4), np.float32), normal=np.zeros((rows, width, 3), np.float32),
                           roughness=np.zeros((rows, width), np.float32), metalness=np.zeros((rows, width), np.float32),
                           emissive=np.zeros((rows, width, 3), np.float32), velocity=np.zeros((rows, width, 2), np.float32))
+        eng = None
+        if engine:
+            eng = dict(position=np.zeros((rows, width, 3), np.float32), view_z=np.full((rows, width), np.inf, np.float32),
+                       motion=np.zeros((rows, width, 2), np.float32), view_normal=np.zeros((rows, width, 3), np.float32),
+                       depth64=np.ones((rows, width), np.float64), velocity64=np.zeros((rows, width, 2), np.float64), hit=np.zeros((rows, width), bool))
         xs = (np.arange(width) + 0.5) / width * 2 - 1
         chunk = max(1, (1 << 20) // width)
         o = C[:3, 3]
@@ -431,8 +442,21 @@ class AnalyticScene:
                 planes["metalness"][sl] = self.mat_metal[m].astype(np.float32).reshape(shp)
                 planes["emissive"][sl] = self.mat_emissive[m].astype(np.float32).reshape(shp + (3,))
                 planes["velocity"][sl] = velxy.reshape(shp + (2,))
+            if eng is not None:
+                shp = hm.shape
+                with np.errstate(invalid="ignore"):
+                    vz = -(wp4 @ V.T)[:, 2]
+                    v64 = pos1 - pos0
+                eng["position"][sl] = np.where(hm[..., None], wp.astype(np.float32).reshape(shp + (3,)), np.float32(0.0))
+                eng["view_z"][sl] = np.where(hm, vz.astype(np.float32).reshape(shp), np.float32(np.inf))
+                eng["motion"][sl] = np.where(hm[..., None], (v64 * np.array([width, -fh], np.float64)).astype(np.float32).reshape(shp + (2,)), np.float32(0.0))
+                eng["view_normal"][sl] = (nsafe @ V[:3, :3].T).astype(np.float32).reshape(shp + (3,))
+                eng["depth64"][sl] = np.where(hm, z.reshape(shp), 1.0)
+                eng["velocity64"][sl] = np.where(hm[..., None], v64.reshape(shp + (2,)), 0.0)
+                eng["hit"][sl] = hm
         fr = Frame(width, rows, depth, gb, vel, direct, cam, prev, frame_index)
         fr.aov = planes
+        fr.engine = eng
         return fr
 
 

@@ -32,9 +32,16 @@ imageio._exr_unpack_block is timed over the blocks of the file's first block row
 rows ("E0_band_scaled"; the de-interleave and stage_aov behind it, milliseconds, are not in it).  Merged into --out under "exr_piz".  With them: K9_PIZ_FAST_BITS, the waves per CU
 the decode's LDS leaves, and the table scratch bytes of the frame.
 
-    python tools/import_rate.py [--modes P0,A0,A1,A2 | E0,E1] [--out profiles/import/rates.json] [--seconds 1.0]
+--modes C2: the typed frame as an engine writes it (rfx.h "AOV conventions"): a float32 world position in place of depth and velocity, camera-space
+normals, no velocity plane — POSITION + CAMERAS + VIEW, set per frame — the same 44 B/px, through stage_aov, beside A2 in three alternating
+rounds; with --parent-lib PATH (a librfx_hip.so built from the parent commit, loaded into the same process on a context of its own) A2 on that
+library too, so that each round is an A/B/C triple.  Beside each: "stage_only", the wall time of stage + flip + sync without draws — the copies
+with the pack kernel behind them, where a kernel that leaves the copy's shadow shows.  Merged into --out under "conventions".
+
+    python tools/import_rate.py [--modes P0,A0,A1,A2 | E0,E1 | C2] [--out profiles/import/rates.json] [--seconds 1.0]
     rocprofv3 --kernel-trace --stats -d DIR -- python tools/import_rate.py --kernel-only      (the pack kernel's own time: a run of its own)
     rocprofv3 --kernel-trace --stats -d DIR -- python tools/import_rate.py --kernel-only --modes E1      (... and the K9 kernels')
+    rocprofv3 --kernel-trace --stats -d DIR -- python tools/import_rate.py --kernel-only --modes C2      (... default beside converting)
 """
 import argparse
 import json
@@ -245,11 +252,14 @@ def main():
     ap.add_argument("--modes", default=",".join(MODES), help="P0,A0,A1,A2 (the default) or E0,E1 (the EXR file modes, measured beside A2)")
     ap.add_argument("--exr-dir", default=None, help="where the E modes write their files (default: a temporary directory)")
     ap.add_argument("--forms", default=None, help="with --modes E0,E1: tiled_zip,pxr24,rle,piz,tiled_piz (any of them) — the EXR blocks forms, measured beside E1's zip")
+    ap.add_argument("--parent-lib", default=None, help="with --modes C2: a librfx_hip.so of the parent commit, measured beside this one in the same rounds")
     ap.add_argument("--e0-frames", type=int, default=2, help="--forms rle: the frames of one E0 loop (the host's RLE decode is a byte loop)")
     a = ap.parse_args()
     global W, H
     W, H = (int(v) for v in a.size.split("x"))
     modes = tuple(a.modes.split(","))
+    if "C2" in modes:
+        return main_conventions(a)
     if any(m in EXR_MODES for m in modes):
         return main_exr_blocks(a, modes) if a.forms else main_exr(a, modes)
     run = Run(a.seed)
@@ -282,6 +292,114 @@ def main():
         f.write("\n")
     if not result["required_A1_and_A2_below_A0_every_round"]:
         sys.exit("import_rate: stage_aov is not faster than the synchronous importer in every round: the staging does not overlap")
+
+
+def _engine_band(args):
+    seed, index, row0, rows = args
+    f = AnalyticScene(seed).render(W, rows, index, row0=row0, rows=rows, frame_height=H, aov=True, engine=True)
+    return f.engine["position"], f.engine["view_normal"], f.camera, f.prev_camera
+
+
+def main_conventions(a):
+    """A2 beside C2 (and A2 on --parent-lib); merged into --out under "conventions" """
+    import multiprocessing as mp
+    from rfx_amd.conventions import AovConventions
+    run = Run(a.seed)
+    ctx = run.ctx
+    assert ctx.has_aov_conventions
+    edges = [H * i // 16 for i in range(17)]
+    frames, convs = [], []
+    for i in range(2):
+        pool = mp.get_context("fork").Pool(16, initializer=_pool_worker_init)
+        try:
+            parts = pool.map(_engine_band, [(a.seed, i, edges[k], edges[k + 1] - edges[k]) for k in range(16)])
+            pool.close()
+            pool.join()
+        except BaseException:
+            pool.terminate()
+            raise
+        a2 = run.frames["A2"][i]
+        planes = {k: v for k, v in a2.aov.items() if k not in ("velocity", "normal")}
+        for k, j, dt in (("position", 0, np.float32), ("normal", 1, np.float16)):
+            src = np.concatenate([p[j] for p in parts], axis=0).astype(dt)
+            planes[k] = ctx.host_alloc(src.shape, dt)
+            planes[k][...] = src
+        planes["direct"] = a2.direct
+        frames.append(planes)
+        convs.append(AovConventions.from_cameras(parts[0][2], parts[0][3], depth_kind="position", velocity_kind="cameras", normal_space="view", background_position=(0.0, 0.0, 0.0)))
+    assert ctx.set_aov_conventions(convs[0]) is None and ctx.aov_stage_bytes(frames[0]) == BYTES_PER_PIXEL["A2"] * W * H
+    ctx.set_aov_conventions(None)
+    runs = {"A2": (ctx, run.fx, run.cam, run.scene)}
+    if a.parent_lib:
+        abi.set_library_path(a.parent_lib)
+        pctx = Context(W, H)
+        abi.set_library_path(None)
+        assert not pctx.has_aov_conventions, "--parent-lib already has rfx_set_aov_conventions: not the parent"
+        pscene = types.SimpleNamespace(frame=None)
+        pcam = types.SimpleNamespace(**vars(run.cam))
+        pfx = effect.SSGIEffect(None, pscene, pcam, dict(width=W, height=H, steps=20, refineSteps=5), seeds=dict(ssgi=11, denoise=22), half_store_rtz=True)
+        runs["A2_parent"] = (pctx, pfx, pcam, pscene)
+    runs["C2"] = runs["A2"]
+
+    def stage(c, mode, i):
+        if mode == "C2":
+            c.set_aov_conventions(convs[i & 1])
+            c.stage_aov(frames[i & 1])
+        else:
+            c.stage_frame(run.frames["A2"][i & 1])
+
+    def loop(mode, n, draw=True):
+        c, fx, cam, scene = runs[mode]
+        if mode != "A2_parent":
+            c.set_aov_conventions(None)
+        stage(c, mode, 0)
+        c.stage_flip()
+        c.sync()
+        t0 = time.perf_counter()
+        for i in range(n):
+            stage(c, mode, i + 1)
+            if draw:
+                f = run.frames["A2"][i & 1]
+                scene.frame = f
+                for k, v in vars(f.camera).items():
+                    setattr(cam, k, v)
+                fx.update(c, None)
+            c.stage_flip()
+        c.sync()
+        return time.perf_counter() - t0
+
+    order = [m for m in ("A2_parent", "A2", "C2") if m in runs]
+    if a.kernel_only:  # under rocprofv3 --kernel-trace --stats: the pack kernel's default and converting instantiations, stage + flip alone
+        for m in ("A2", "C2"):
+            loop(m, 20, draw=False)
+        ctx.close()
+        return
+    n = {}
+    for m in order:
+        loop(m, 5)
+        n[m] = max(20, int(math.ceil(a.seconds / (loop(m, 20) / 20))))
+    out = dict(width=W, height=H, seed=a.seed, seconds=a.seconds, bytes_per_frame=BYTES_PER_PIXEL["A2"] * W * H, kinds="position + cameras + view", frames=n, rounds=[], stage_only=[])
+    for r in range(3):  # (the order rotates: no mode is always the first or the last of its round)
+        row = {m: round(loop(m, n[m]) / n[m] * 1e3, 4) for m in order[r % len(order):] + order[:r % len(order)]}
+        row = {m: row[m] for m in order}
+        out["rounds"].append(row)
+        print(json.dumps(row), flush=True)
+    for r in range(3):
+        row = {m: round(loop(m, 40, draw=False) / 40 * 1e3, 4) for m in order}
+        out["stage_only"].append(row)
+        print("stage_only", json.dumps(row), flush=True)
+    base = "A2_parent" if "A2_parent" in runs else "A2"
+    vals = [r[base] for r in out["rounds"]]
+    out["baseline"], out["baseline_spread_ms"] = base, round(max(vals) - min(vals), 4)
+    out["C2_minus_baseline_ms"] = [round(r["C2"] - r[base], 4) for r in out["rounds"]]
+    for c, *_ in {id(v[0]): v for v in runs.values()}.values():
+        assert c.halo_violations() == 0
+        c.close()
+    result = json.load(open(a.out)) if os.path.exists(a.out) else {}
+    result["conventions"] = out
+    with open(a.out, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
 
 
 def main_exr(a, modes):
