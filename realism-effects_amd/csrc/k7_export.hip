@@ -1,4 +1,4 @@
-// K7 — export: the importer run in reverse (include/rfx.h rfx_export_params), and K8, the encoders of its stream (k8_png.h, k8_exr.h, k8_match.h).
+// K7 — export: the importer run in reverse (include/rfx.h rfx_export_params), and K8, the encoders of its stream (k8_coder.h, k8_png.h, k8_exr.h).
 // A pure stream: 16 B in per pixel, 3 to 16 B out.  Lane t owns the four consecutive pixels [4 t, 4 t + 4) of the flat run (rfx_launch.h
 // rfx_export_plan_for): four 16-byte loads, one run of whole dwords out (12 .. 64 bytes at t * group_bytes), never a byte or short store.  The
 // pixels mod 4 left over are written by the lane after the last group with element-wide stores.  Format, channel count and operator are template
@@ -97,9 +97,8 @@ __global__ __launch_bounds__(RFX_K7_BLOCK) void k7_export(K7Args A) {
 
 }  // namespace
 
-#include "k8_png.h"  // K8: the PNG fragment of K7's U8 stream
+#include "k8_png.h"  // K8: the PNG fragment of K7's U8 stream (the deflate coder: k8_coder.h)
 #include "k8_exr.h"  // ... and the EXR fragment of its F16 stream: the same coder behind another pre-transform
-#include "k8_match.h"  // ... and both with run-length matches, as second scanline kernels
 
 template <int FMT, int CH, int TM>
 static void k7_launch(const K7Args &A, int blocks, hipStream_t stream) {

@@ -195,7 +195,7 @@ int rfx_exr(rfx_ctx *c, const rfx_export_params *p, void *host, size_t bytes) {
     return rc ? rc : rfx_export_wait(c, ticket);
 }
 
-// ---- K8 with run-length matches (include/rfx.h "Match form"; the kernels are in k8_match.h): flags = 0 is the call without _ex
+// ---- K8 with run-length matches (include/rfx.h "Match form"; the scanline kernels' <true> instantiations, the token rule is in k8_coder.h): flags = 0 is the call without _ex
 int rfx_stage_png_ex(rfx_ctx *c, const rfx_export_params *p, int filter, unsigned flags, void *host, size_t bytes, int *ticket) {
     if (!ticket) return RFX_EINVAL;
     if (const int rc = png_filter_check(c, "rfx_stage_png_ex", filter)) return rc;

@@ -184,7 +184,7 @@ struct K7Args {
 // format / channels / tonemap select the specialisation (hipErrorInvalidValue for a combination the export does not have); `blocks` from the plan
 hipError_t rfx_launch_k7(const K7Args &, int blocks, int format, int channels, int tonemap, hipStream_t);
 
-// K8 PNG encode (k8_png.h, built into k7_export.hip): K7's staged U8 stream -> the result buffer of include/rfx.h "PNG fragments", laid out by
+// K8 PNG encode (k8_png.h over k8_coder.h, built into k7_export.hip): K7's staged U8 stream -> the result buffer of include/rfx.h "PNG fragments", laid out by
 // rfx_launch.h rfx_png_plan_for.  Three launches on `stream`: one wave per scanline into the scratch slots, the scan, the gather.
 struct K8Args {
     const unsigned char *src;     // K7's stream: `rows` rows of `rowbytes` bytes, row 0 = bottom
@@ -196,9 +196,8 @@ struct K8Args {
     int rows, rowbytes, bpp, filter;
     unsigned slot_stride;
 };
-// matches: the scanline kernel is k8_png_rows_m (k8_match.h: the match form where it is smaller) instead of k8_png_rows (literals only)
+// matches: the scanline kernel is k8_png_rows<true> (the match form where it is smaller) instead of k8_png_rows<false> (literals only)
 hipError_t rfx_launch_k8(const K8Args &, hipStream_t, bool matches = false);
-hipError_t rfx_launch_k8_rows_m(const K8Args &, hipStream_t);  // the scanline kernel alone, with matches: rfx_launch_k8 calls it
 
 // K8 EXR encode (k8_exr.h, built into k7_export.hip): K7's staged F16 stream -> the result buffer of include/rfx.h "EXR fragments", laid out by
 // rfx_launch.h rfx_exr_plan_for.  Four launches on `stream`: the byte planes, one wave per scanline into the scratch slots, the scan, the gather.
@@ -214,9 +213,8 @@ struct K8ExrArgs {
     int first_y;                  // the EXR y of the tile's top scanline
     unsigned slot_stride, plane_stride;
 };
-// matches: the scanline kernel is k8_exr_rows_m (k8_match.h) instead of k8_exr_rows
+// matches: the scanline kernel is k8_exr_rows<true> instead of k8_exr_rows<false>
 hipError_t rfx_launch_k8_exr(const K8ExrArgs &, hipStream_t, bool matches = false);
-hipError_t rfx_launch_k8_exr_rows_m(const K8ExrArgs &, hipStream_t);  // the scanline kernel alone, with matches: rfx_launch_k8_exr calls it
 
 // K9 EXR import (k9_exr_import.hip): the packed blocks of an OpenEXR file — scanline chunks or tiles, a rectangle of the frame each — -> the typed
 // AOV staging planes k0_aov_pack reads (include/rfx.h "streamed EXR frames", "EXR blocks").  Four launches on `stream`: k9_inflate (one wave per

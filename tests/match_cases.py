@@ -1,5 +1,5 @@
 """Shared by the match-form tests (tests/test_png_matches_cpu.py, test_exr_matches_cpu.py, test_gpu_png_matches.py, test_gpu_exr_matches.py and the
-Node twins): inputs that take K8's match kernels (csrc/k8_match.h, include/rfx.h "Match form") to the edges of the token rule, of the sweep's
+Node twins): inputs that take K8's scanline kernels with MATCHES (csrc/k8_coder.h, include/rfx.h "Match form") to the edges of the token rule, of the sweep's
 256-position steps, of the lane's bit accumulator, of the bit window and of the form choice, and a model of the sweep that says how close an
 input comes.  Pure NumPy on top of tests/match_device_ref.py.  A case is built from a planted byte sequence d:
 
@@ -28,7 +28,7 @@ Sweep = namedtuple("Sweep", "steps max_nb over64 matches")
 
 
 def sweep_model(d):
-    """The step arithmetic of the match kernels' emission for the sequence d in form (c): every step of 256 positions adds the bits of the
+    """The step arithmetic of the coder's emission (k8_emit) for the sequence d in form (c): every step of 256 positions adds the bits of the
     tokens that END in it behind the pos & 31 bits carried over (the header's bits count as a carry of 31: an upper bound).  -> Sweep(steps =
     the bits in the window per step with the carry counted, max_nb = the most bits one lane packs, over64 = lanes with more than 64, matches)"""
     pos, tok, sym, eb, _, lens = M.coded(d)

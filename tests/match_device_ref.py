@@ -1,4 +1,4 @@
-"""NumPy restatement of the match form (include/rfx.h "Match form", K8's second scanline kernels in csrc/k8_match.h): the token rule, form (c) of
+"""NumPy restatement of the match form (include/rfx.h "Match form", K8's scanline kernels with MATCHES over csrc/k8_coder.h): the token rule, form (c) of
 a PNG payload and of an EXR chunk's data, the form choice, and the two result buffers with match_form_chunks.  The code-length rule, the
 canonical codes, the header tokens and the bit packing are png_device_ref's, and the forms without matches are png_device_ref's and
 exr_device_ref's, all by import.  Shared by the match tests; the device's result buffer must equal result_prefix_png / result_prefix_exr byte

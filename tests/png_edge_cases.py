@@ -1,4 +1,4 @@
-"""Shared by tests/test_png_edges_cpu.py and tests/test_gpu_png_edges.py: inputs that take K8 (csrc/k8_png.h) to the edges of its bit window, its
+"""Shared by tests/test_png_edges_cpu.py and tests/test_gpu_png_edges.py: inputs that take K8 (csrc/k8_png.h over csrc/k8_coder.h) to the edges of its bit window, its
 frame shapes, its stored blocks, the choice between the two payload forms, the block header's tokens, the filter ties and the Adler sums, and
 a model of the kernel's bit window that says how close a scanline comes.  Pure NumPy on top of tests/png_device_ref.py; every generator is
 seeded and returns (img, filter) with img an (H, W, channels) uint8 array (row 0 = bottom) and filter rfx_stage_png's 0..4.  The CPU tests
@@ -10,7 +10,7 @@ import numpy as np
 
 import png_device_ref as R
 
-STEP_BYTES, LANES, LANE_BYTES = 256, 64, 4  # k8_png_rows' sweep: 64 lanes by 4 bytes per step
+STEP_BYTES, LANES, LANE_BYTES = 256, 64, 4  # k8_png_rows<false>'s sweep: 64 lanes by 4 bytes per step
 WINDOW_BITS = 31 + STEP_BYTES * R.MAXBITS  # what the LDS window is laid out for: 3871
 
 Header = namedtuple("Header", "lens cllens hclen tokens bits cl_depth")
@@ -34,8 +34,8 @@ def block_header(line):
 
 
 def window_model(line):
-    """The step arithmetic of k8_png_rows for a filtered scanline (type byte first) in the compressed form: the header and the type byte's code
-    go into the window and whole dwords leave (first_flush = the bits in the window then); every step of 256 bytes adds its lanes' codes behind
+    """The step arithmetic of k8_png_rows<false> (the literals' sweep of csrc/k8_coder.h, which starts behind the type byte) for a filtered
+    scanline (type byte first) in the compressed form: the header and the type byte's code go into the window and whole dwords leave (first_flush = the bits in the window then); every step of 256 bytes adds its lanes' codes behind
     the pos & 31 bits carried over.  -> Window(header_bits, first_flush, steps = the bits in the window per step with the carry counted,
     max_nb = the most bits one lane packs, spills = lanes whose (o & 31) + nb > 64 reach a third dword, tokens = the header's)"""
     line = np.asarray(line, np.uint8)

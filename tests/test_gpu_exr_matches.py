@@ -1,5 +1,5 @@
 """GPU (-m gpu; also under --hostsim): K8's EXR fragment with run-length matches (rfx_exr_ex / rfx_stage_exr_ex with RFX_ENCODE_MATCHES; the
-kernel: csrc/k8_match.h k8_exr_rows_m).  For every case of tests/match_cases.py the result buffer, header included, must be byte-identical to the
+kernel: csrc/k8_exr.h k8_exr_rows<true>).  For every case of tests/match_cases.py the result buffer, header included, must be byte-identical to the
 restatement's (tests/match_device_ref.py) of the halfs ctx.export returns; flags = 0 through the _ex calls must be the old calls' bytes."""
 import ctypes as C
 import struct

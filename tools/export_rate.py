@@ -35,6 +35,10 @@ E3 and the two modes below in alternating rounds), and ADDS its results to --out
 and the encode alone (rfx_profile, kind K8) for PNG and EXR with matches off and on, three alternating rounds of 20 launches each, so that the
 spread from round to round stands next to the difference; the fragment bytes of the same frame off and on, and that frame through the host's
 ZIPS writer.
+
+--modes matches --parent-lib PATH (a librfx_hip.so built from the parent commit) measures only those encodes alone, on that library and on
+this tree's in alternating fresh processes of one session (--processes of each), and ADDS them to --out under --key with, per encode, the
+parent's median and full range, the tree's median, and whether the tree's median is within the parent's median plus that range.
 """
 import argparse
 import copy
@@ -239,6 +243,68 @@ def main_exr(run, a):
         f.write("\n")
 
 
+def encodes_alone(run):
+    """the K8 encodes alone (rfx_profile) inside loops of staged fragments of ONE frame, PNG U8 x 3 and EXR F16 x 4 with matches off and on:
+    the four alternate, three rounds of 20 launches each, so the spread is on record.  {"png_off": [ms per launch of each round], ...}"""
+    ctx = run.ctx
+
+    def stage(kind, matches, buf):
+        if kind == "png":
+            return ctx.stage_png(abi.TEX_FINAL, 3, "aces", 1.0, out=buf, matches=matches)
+        return ctx.stage_exr(abi.TEX_FINAL, 4, out=buf, matches=matches)
+
+    alone = {}
+    for kind, bufs in (("png", run.png), ("exr", run.exr)):
+        for matches in (False, True):
+            for _ in range(5):
+                ctx.export_wait(stage(kind, matches, bufs[0]))
+    for r in range(3):
+        for kind, bufs in (("png", run.png), ("exr", run.exr)):
+            for matches in (False, True):
+                ctx.sync()
+                ctx.profile(True)
+                for i in range(20):
+                    ctx.export_wait(stage(kind, matches, bufs[i & 1]))
+                ms, launches = ctx.profile_read()["k8_png"]
+                ctx.profile(False)
+                alone.setdefault("%s_%s" % (kind, "on" if matches else "off"), []).append(round(ms / launches, 5))
+    return alone
+
+
+def main_parent_against_tree(a):
+    """--modes matches --parent-lib PATH: the encodes alone on the parent commit's library and on this tree's, in alternating fresh processes
+    (--processes of each, this one opens no device), merged into the file under --key.  within: the tree's median is at most the parent's
+    median plus the parent's own full range over all its rounds and processes."""
+    import statistics
+    import subprocess
+    runs = {"parent": [], "tree": []}
+    for p in range(a.processes):
+        for name in ("parent", "tree"):
+            cmd = [sys.executable, os.path.abspath(__file__), "--modes", "matches", "--encodes-only", "--size", a.size, "--seed", str(a.seed)]
+            if name == "parent":
+                cmd += ["--lib", a.parent_lib]
+            out = subprocess.run(cmd, check=True, stdout=subprocess.PIPE, text=True, timeout=600).stdout  # a failed or hung process ends the session
+            runs[name].append(json.loads(out.strip().splitlines()[-1]))
+            print(name, p, json.dumps(runs[name][-1]), flush=True)
+    result = dict(what="the K8 encodes alone, the parent commit's library and this tree's in alternating processes of one session, three rounds "
+                       "of 20 launches each, ms", width=W, height=H, seed=a.seed, parent=runs["parent"], tree=runs["tree"], summary={})
+    for k in runs["parent"][0]:
+        pv = [v for r in runs["parent"] for v in r[k]]
+        tv = [v for r in runs["tree"] for v in r[k]]
+        pm, tm, rng = statistics.median(pv), statistics.median(tv), max(pv) - min(pv)
+        result["summary"][k] = dict(parent_median=round(pm, 5), parent_range=round(rng, 5), tree_median=round(tm, 5), within=bool(tm <= pm + rng))
+    print(json.dumps(result["summary"]), flush=True)
+    merged = {}
+    if os.path.exists(a.out):
+        with open(a.out) as f:
+            merged = json.load(f)
+    merged[a.key] = result
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(merged, f, indent=1)
+        f.write("\n")
+
+
 def main_matches(run, a):
     """--modes matches: T0 / T3 / T3m / E3 / E3m and the two encodes alone with matches off and on, merged into the file under the key "matches" """
     import struct
@@ -264,28 +330,7 @@ def main_matches(run, a):
             print(key, json.dumps(row), flush=True)
         result["rounds"][key] = rounds
         result["frames"][key] = n
-    # the encodes alone, inside loops of staged fragments of ONE frame: off and on alternate, three rounds, so the spread is on record
-    def stage(kind, matches, buf):
-        if kind == "png":
-            return ctx.stage_png(abi.TEX_FINAL, 3, "aces", 1.0, out=buf, matches=matches)
-        return ctx.stage_exr(abi.TEX_FINAL, 4, out=buf, matches=matches)
-
-    alone = {}
-    for kind, bufs in (("png", run.png), ("exr", run.exr)):
-        for matches in (False, True):
-            for _ in range(5):
-                ctx.export_wait(stage(kind, matches, bufs[0]))
-    for r in range(3):
-        for kind, bufs in (("png", run.png), ("exr", run.exr)):
-            for matches in (False, True):
-                ctx.sync()
-                ctx.profile(True)
-                for i in range(20):
-                    ctx.export_wait(stage(kind, matches, bufs[i & 1]))
-                ms, launches = ctx.profile_read()["k8_png"]
-                ctx.profile(False)
-                alone.setdefault("%s_%s" % (kind, "on" if matches else "off"), []).append(round(ms / launches, 5))
-    for k, v in alone.items():
+    for k, v in encodes_alone(run).items():
         result["k8_" + k] = dict(ms_rounds=v, ms=round(sorted(v)[1], 5), spread=round(max(v) - min(v), 5), launches_per_round=20)
     print(json.dumps({k: v for k, v in result.items() if k.startswith("k8_")}), flush=True)
     # the fragments of that frame, off and on; the same frame through the host's ZIPS writer (outside every clock)
@@ -327,10 +372,25 @@ def main():
     ap.add_argument("--size", default="3840x2160", help="frame size (the committed numbers are 4K; a small size checks the script itself)")
     ap.add_argument("--modes", default="png", choices=("png", "exr", "matches"),
                     help='"exr": T0 / E1 / E2 / E3, added to --out under "exr"; "matches": T0 / T3 / T3m / E3 / E3m, added under "matches"')
+    ap.add_argument("--parent-lib", default=None, help="with --modes matches: a librfx_hip.so of the parent commit; only the encodes alone are measured, "
+                                                       "on it and on this tree's library in alternating processes, and added to --out under --key")
+    ap.add_argument("--processes", type=int, default=2, help="with --parent-lib: processes per library")
+    ap.add_argument("--key", default="parent_against_tree", help="with --parent-lib: the key in --out")
+    ap.add_argument("--encodes-only", action="store_true", help="with --modes matches: only the encodes alone, printed as one JSON line (what --parent-lib starts)")
+    ap.add_argument("--lib", default=None, help="with --encodes-only: the librfx_hip.so to load instead of this tree's")
     a = ap.parse_args()
     global W, H
     W, H = (int(v) for v in a.size.split("x"))
+    if a.modes == "matches" and a.parent_lib:
+        return main_parent_against_tree(a)
+    if a.lib:
+        abi.set_library_path(a.lib)
     run = Run(a.seed)
+    if a.modes == "matches" and a.encodes_only:
+        run.alloc_exr()
+        run.loop("T0", False, 5)  # a frame to encode
+        print(json.dumps(encodes_alone(run)), flush=True)
+        return run.ctx.close()
     if a.modes == "exr":
         return main_exr(run, a)
     if a.modes == "matches":
