@@ -68,6 +68,10 @@ const PROF_KINDS_ALL = PROF_KINDS.concat(["k8_png"])
 const PNG_FILTERS = { adaptive: 0, none: 1, sub: 2, up: 3, paeth: 4 }
 // RFX_ENCODE_MATCHES (include/rfx.h "Match form"): the flags bit of rfx_png_ex / rfx_stage_png_ex / rfx_exr_ex / rfx_stage_exr_ex
 const ENCODE_MATCHES = 1
+// the addon's functions per encode kind: [the byte count of a result buffer, the blocking call, the staged call]; the match forms: + "Ex"
+const ENCODE = { export: ["exportBytes", "exportFrame", "stageExport"], png: ["pngBound", "pngFrame", "stagePng"], exr: ["exrBound", "exrFrame", "stageExr"] }
+// ... and per form of an EXR frame's records (layout.chunks, layout.blocks, "piz": blocks with a PIZ part): [the byte count, the staging call]
+const EXR_FRAME = { chunks: ["exrAovStageBytes", "stageExrAov"], blocks: ["exrBlocksStageBytes", "stageExrBlocks"], piz: ["exrBlocksPizStageBytes", "stageExrBlocksPiz"] }
 
 // 128x128 RGBA8 blue-noise table: decoded once from the reference's PNG asset, already flipY'd
 // (tools/make_blue_noise_table.py; src/utils/BlueNoiseUtils.js:9-15)
@@ -102,10 +106,18 @@ class Renderer {
 
 	// rows [row0, row0+rows) in FRAME rows; `array` holds exactly those rows
 	upload(tex, array, row0, rows) {
+		addon.upload(this._h, tex, array, ...this._heldBand(tex, row0, rows))
+	}
+	// the band of an upload, a download or a pack call: by default the rows the slot holds
+	_heldBand(tex, row0, rows) {
 		const held = this.heldRows(tex)
-		if (row0 === undefined) row0 = held[0]
-		if (rows === undefined) rows = held[1]
-		addon.upload(this._h, tex, array, row0, rows)
+		return [row0 === undefined ? held[0] : row0, rows === undefined ? held[1] : rows]
+	}
+	// a FULL-FRAME plane -> [the rows of it the slot holds (a plane of just those rows: as it is), row0, rows]
+	_heldPart(tex, plane) {
+		const held = this.heldRows(tex)
+		const per = FORMAT[tex][1] * this.width
+		return [plane.length === held[1] * per ? plane : plane.subarray(held[0] * per, (held[0] + held[1]) * per), held[0], held[1]]
 	}
 
 	// a dumped FULL-FRAME plane: the slot takes the band it holds.  Every call uploads (the reference re-renders its raster passes every
@@ -113,10 +125,7 @@ class Renderer {
 	// because a buffer refilled in place is the same object with new texels
 	uploadPlane(tex, plane, isStatic) {
 		if (isStatic === "resident" || (isStatic && this._resident[tex] === plane)) return
-		const held = this.heldRows(tex)
-		const per = FORMAT[tex][1] * this.width
-		const band = plane.length === held[1] * per ? plane : plane.subarray(held[0] * per, (held[0] + held[1]) * per)
-		this.upload(tex, band, held[0], held[1])
+		this.upload(tex, ...this._heldPart(tex, plane))
 		this._resident[tex] = plane
 	}
 
@@ -125,11 +134,15 @@ class Renderer {
 	static hostAlloc(Ctor, length) {
 		return new Ctor(addon.hostAlloc(length * Ctor.BYTES_PER_ELEMENT))
 	}
+	// the band of a staging call: FRAME rows [row0, row0 + rows), by default from row0 (0) to the top of the frame
+	_band(row0, rows) {
+		return [row0 === undefined ? 0 : row0, rows === undefined ? this.height - (row0 || 0) : rows]
+	}
 	// streamed AOV frames (rfx.h): the attribute planes of FRAME rows [row0, row0 + rows) (default: the whole frame) — Float32Array, or Uint16Array
 	// of IEEE half bits — are staged once and packed on the upload stream into the back buffers of DEPTH and of the slots the planes name
 	// { diffuse, normal, roughness, metalness, emissive, velocity, depth, direct }; stageFlip() publishes them
 	stageAov(planes, row0, rows) {
-		addon.stageAov(this._h, planes, row0 === undefined ? 0 : row0, rows === undefined ? this.height - (row0 || 0) : rows)
+		addon.stageAov(this._h, planes, ...this._band(row0, rows))
 		this._stagedAov = planes // keep the planes alive while they are in flight
 	}
 	// AOV conventions (rfx.h): what the next stageAov / stageExrAov / stageExrBlocks calls take their depth, velocity and normal planes for —
@@ -192,17 +205,16 @@ class Renderer {
 		addon.setAovConventions(this._h, kinds, f)
 	}
 	aovStageBytes(planes, row0, rows) {
-		return addon.aovStageBytes(this._h, planes, row0 === undefined ? 0 : row0, rows === undefined ? this.height - (row0 || 0) : rows)
+		return addon.aovStageBytes(this._h, planes, ...this._band(row0, rows))
 	}
 	// streamed EXR frames (rfx.h): stageAov for a frame that is still an OpenEXR file — `bytes` the file (a Uint8Array / Buffer; over hostAlloc
 	// memory the copies are asynchronous), `layout` = imageio.exrAovLayout(bytes): the chunks of the band cross PCIe packed and are decoded on
 	// the device.  exrAovStatus() waits for that decode -> [bad chunks, index of the first bad chunk or -1, its error code or 0]
 	stageExrAov(bytes, layout, row0, rows) {
-		addon.stageExrAov(this._h, bytes, layout.parts, layout.chunks, row0 === undefined ? 0 : row0, rows === undefined ? this.height - (row0 || 0) : rows)
-		;(this._stagedExrNow = this._stagedExrNow || []).push(bytes) // kept alive until the copies of this batch have executed (stageFlip)
+		this._exrFrame(1, "chunks", bytes, layout, row0, rows)
 	}
 	exrAovStageBytes(bytes, layout, row0, rows) {
-		return addon.exrAovStageBytes(this._h, bytes, layout.parts, layout.chunks, row0 === undefined ? 0 : row0, rows === undefined ? this.height - (row0 || 0) : rows)
+		return this._exrFrame(0, "chunks", bytes, layout, row0, rows)
 	}
 	exrAovStatus() {
 		return addon.exrAovStatus(this._h)
@@ -219,32 +231,29 @@ class Renderer {
 		return false
 	}
 	stageExrBlocks(bytes, layout, row0, rows) {
-		const stage = Renderer._layoutHasPiz(layout) ? addon.stageExrBlocksPiz : addon.stageExrBlocks
-		stage(this._h, bytes, layout.parts, layout.blocks, row0 === undefined ? 0 : row0, rows === undefined ? this.height - (row0 || 0) : rows)
-		;(this._stagedExrNow = this._stagedExrNow || []).push(bytes) // kept alive until the copies of this batch have executed (stageFlip)
+		this._exrFrame(1, "blocks", bytes, layout, row0, rows)
 	}
 	exrBlocksStageBytes(bytes, layout, row0, rows) {
-		const count = Renderer._layoutHasPiz(layout) ? addon.exrBlocksPizStageBytes : addon.exrBlocksStageBytes
-		return count(this._h, bytes, layout.parts, layout.blocks, row0 === undefined ? 0 : row0, rows === undefined ? this.height - (row0 || 0) : rows)
+		return this._exrFrame(0, "blocks", bytes, layout, row0, rows)
+	}
+	// the four calls above: the addon function of EXR_FRAME for the records the layout holds (stage: 1 = the staging call, 0 = its byte count)
+	_exrFrame(stage, records, bytes, layout, row0, rows) {
+		const form = records === "blocks" && Renderer._layoutHasPiz(layout) ? "piz" : records
+		const result = addon[EXR_FRAME[form][stage]](this._h, bytes, layout.parts, layout[records], ...this._band(row0, rows))
+		if (stage) (this._stagedExrNow = this._stagedExrNow || []).push(bytes) // kept alive until the copies of this batch have executed (stageFlip)
+		return result
 	}
 	// a frame with packed planes, or — no `gbuffer` — with `aov` attribute planes
 	stageFrame(frame) {
+		this._staged = frame // keep the planes alive while they are in flight
 		if (!frame.gbuffer) {
 			// an engine-form frame (dump.js): its conventions are set for this call; a reference-form frame after one resets them
 			if (frame.aovConventions) this.setAovConventions(Renderer.conventionsFor(frame.aovConventions, frame.camera, frame.prevCamera))
 			else if (this._conventionsSet) this.setAovConventions(null)
-			this.stageAov(Object.assign({ depth: frame.depth, direct: frame.direct }, frame.aov))
-			this._staged = frame
-			return
+			return this.stageAov(Object.assign({ depth: frame.depth, direct: frame.direct }, frame.aov))
 		}
-		for (const pt of [[TEX.DEPTH, frame.depth], [TEX.GBUFFER, frame.gbuffer], [TEX.VELOCITY, frame.velocity], [TEX.DIRECT_LIGHT, frame.direct]]) {
-			const held = this.heldRows(pt[0])
-			const per = FORMAT[pt[0]][1] * this.width
-			const plane = pt[1]
-			const band = plane.length === held[1] * per ? plane : plane.subarray(held[0] * per, (held[0] + held[1]) * per)
-			addon.stageUpload(this._h, pt[0], band, held[0], held[1])
-		}
-		this._staged = frame // keep the planes alive while they are in flight
+		for (const [tex, plane] of [[TEX.DEPTH, frame.depth], [TEX.GBUFFER, frame.gbuffer], [TEX.VELOCITY, frame.velocity], [TEX.DIRECT_LIGHT, frame.direct]])
+			addon.stageUpload(this._h, tex, ...this._heldPart(tex, plane))
 	}
 	stageFlip() {
 		addon.stageFlip(this._h)
@@ -265,21 +274,32 @@ class Renderer {
 	exportBytes(params) {
 		return addon.exportBytes(this._h, this.exportParams(params))
 	}
+	// the copy of a staged encode writes `out` until its ticket retires (exportWait) or two later tickets exist
+	_keepUntilRetired(ticket, out) {
+		if (!this._exports) this._exports = new Map()
+		this._exports.set(ticket, out)
+		for (const t of this._exports.keys()) if (t <= ticket - 2) this._exports.delete(t)
+		return ticket
+	}
+	// one call of ENCODE[kind], blocking (-> out, allocated at the bound when not given) or staged (-> ticket).  Only png's calls take `filter`;
+	// options.matches selects the Ex form and passes its flags
+	_encode(kind, staged, p, filter, out, options) {
+		const [bound, call, stage] = ENCODE[kind], matches = options && options.matches, Ctor = (kind === "export" && EXPORT_ARRAY[p.format]) || Uint8Array
+		if (!out && !staged) out = new Ctor(Math.max(1, addon[bound](this._h, p) / Ctor.BYTES_PER_ELEMENT))
+		const args = [this._h, p]
+		if (kind === "png") args.push(this.pngFilter(filter))
+		if (matches) args.push(ENCODE_MATCHES)
+		const result = addon[(staged ? stage : call) + (matches ? "Ex" : "")](...args, out)
+		return staged ? this._keepUntilRetired(result, out) : out
+	}
 	// -> Float32Array / Uint16Array (half bits) / Uint8Array of tileRows * width * channels elements, row 0 = bottom; blocks (rfx_export)
 	exportFrame(params, out) {
-		const p = this.exportParams(params)
-		if (!out) out = new (EXPORT_ARRAY[p.format] || Uint8Array)(Math.max(1, addon.exportBytes(this._h, p) / (EXPORT_ARRAY[p.format] || Uint8Array).BYTES_PER_ELEMENT))
-		addon.exportFrame(this._h, p, out)
-		return out
+		return this._encode("export", false, this.exportParams(params), undefined, out)
 	}
 	// enqueue the encode and the copy into `out` (a Renderer.hostAlloc array for an asynchronous copy) -> ticket; `out` is complete once
 	// exportWait(ticket) has returned.  Returns only when the export two tickets earlier has completed: alternate two buffers (rfx_stage_export)
 	stageExport(params, out) {
-		const ticket = addon.stageExport(this._h, this.exportParams(params), out)
-		if (!this._exports) this._exports = new Map()
-		this._exports.set(ticket, out) // the copy writes `out` until its ticket retires
-		for (const t of this._exports.keys()) if (t <= ticket - 2) this._exports.delete(t)
-		return ticket
+		return this._encode("export", true, this.exportParams(params), undefined, out)
 	}
 	// PNG fragments (rfx.h "PNG fragments"): the U8_SRGB export encoded on the device as the IDAT chunks of the tile rows.  params as for
 	// exportFrame (format is U8_SRGB); filter: "adaptive" | "none" | "sub" | "up" | "paeth" or 0..4.  io.pngFromFragments wraps the result.
@@ -298,20 +318,11 @@ class Renderer {
 	// options: { matches: true } encodes with run-length matches (rfx.h "Match form": rfx_png_ex with RFX_ENCODE_MATCHES); the same for
 	// stagePng, exr and stageExr
 	png(params, filter, out, options) {
-		const p = this.pngParams(params)
-		if (!out) out = new Uint8Array(Math.max(1, addon.pngBound(this._h, p)))
-		if (options && options.matches) addon.pngFrameEx(this._h, p, this.pngFilter(filter), ENCODE_MATCHES, out)
-		else addon.pngFrame(this._h, p, this.pngFilter(filter), out)
-		return out
+		return this._encode("png", false, this.pngParams(params), filter, out, options)
 	}
 	// stageExport's contract with a PNG fragment as the payload; the ticket is one of the same sequence and exportWait retires it (rfx_stage_png)
 	stagePng(params, filter, out, options) {
-		const ticket = options && options.matches ? addon.stagePngEx(this._h, this.pngParams(params), this.pngFilter(filter), ENCODE_MATCHES, out)
-			: addon.stagePng(this._h, this.pngParams(params), this.pngFilter(filter), out)
-		if (!this._exports) this._exports = new Map()
-		this._exports.set(ticket, out)
-		for (const t of this._exports.keys()) if (t <= ticket - 2) this._exports.delete(t)
-		return ticket
+		return this._encode("png", true, this.pngParams(params), filter, out, options)
 	}
 	// EXR fragments (rfx.h "EXR fragments"): the F16 export encoded on the device as the ZIPS chunks of the tile rows.  params as for exportFrame
 	// (format is F16; channels 4 by default).  io.exrFromFragments wraps the result.
@@ -323,19 +334,11 @@ class Renderer {
 	}
 	// -> the result buffer (Uint8Array of exrBound bytes: 32-byte header, fragment, slack); blocks (rfx_exr)
 	exr(params, out, options) {
-		const p = this.exrParams(params)
-		if (!out) out = new Uint8Array(Math.max(1, addon.exrBound(this._h, p)))
-		if (options && options.matches) addon.exrFrameEx(this._h, p, ENCODE_MATCHES, out)
-		else addon.exrFrame(this._h, p, out)
-		return out
+		return this._encode("exr", false, this.exrParams(params), undefined, out, options)
 	}
 	// stageExport's contract with an EXR fragment as the payload; the ticket is one of the same sequence and exportWait retires it (rfx_stage_exr)
 	stageExr(params, out, options) {
-		const ticket = options && options.matches ? addon.stageExrEx(this._h, this.exrParams(params), ENCODE_MATCHES, out) : addon.stageExr(this._h, this.exrParams(params), out)
-		if (!this._exports) this._exports = new Map()
-		this._exports.set(ticket, out)
-		for (const t of this._exports.keys()) if (t <= ticket - 2) this._exports.delete(t)
-		return ticket
+		return this._encode("exr", true, this.exrParams(params), undefined, out, options)
 	}
 	exportWait(ticket) {
 		addon.exportWait(this._h, ticket)
@@ -343,12 +346,10 @@ class Renderer {
 	}
 
 	download(tex, row0, rows) {
-		const held = this.heldRows(tex)
-		if (row0 === undefined) row0 = held[0]
-		if (rows === undefined) rows = held[1]
+		const band = this._heldBand(tex, row0, rows)
 		const f = FORMAT[tex]
-		const out = new f[0](rows * (tex === TEX.BLUE_NOISE ? 128 : this.width) * f[1])
-		addon.download(this._h, tex, out, row0, rows)
+		const out = new f[0](band[1] * (tex === TEX.BLUE_NOISE ? 128 : this.width) * f[1])
+		addon.download(this._h, tex, out, ...band)
 		return out
 	}
 
@@ -358,12 +359,10 @@ class Renderer {
 
 	// importer: unpacked attribute planes (Float32Arrays over rows [row0, row0+rows)) -> the packed render targets (rfx_pack_gbuffer / _velocity)
 	packGBuffer(aov, row0, rows) {
-		const held = this.heldRows(TEX.GBUFFER)
-		addon.packGBuffer(this._h, aov, row0 === undefined ? held[0] : row0, rows === undefined ? held[1] : rows)
+		addon.packGBuffer(this._h, aov, ...this._heldBand(TEX.GBUFFER, row0, rows))
 	}
 	packVelocity(aov, row0, rows) {
-		const held = this.heldRows(TEX.VELOCITY)
-		addon.packVelocity(this._h, aov, row0 === undefined ? held[0] : row0, rows === undefined ? held[1] : rows)
+		addon.packVelocity(this._h, aov, ...this._heldBand(TEX.VELOCITY, row0, rows))
 	}
 
 	// scene.environment: Float32Array(H*W*4) equirect map (row 0 = bottom) or null — rfx_set_environment

@@ -12,6 +12,7 @@
  * reference, whose draws are asynchronous on the GL command queue.
  */
 #include <node_api.h>
+#include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -41,6 +42,12 @@ static int get_args(napi_env env, napi_callback_info info, size_t want, napi_val
         return 0;
     }
     return 1;
+}
+/* the `data` pointer the function was created with (init): what the callbacks that serve several exports select by */
+static void *call_data(napi_env env, napi_callback_info info) {
+    void *data = NULL;
+    napi_get_cb_info(env, info, NULL, NULL, NULL, &data);
+    return data;
 }
 
 static rfx_ctx *get_ctx(napi_env env, napi_value v) {
@@ -130,6 +137,188 @@ static int read_camera(napi_env env, napi_value obj, const char *name, rfx_camer
     return 1;
 }
 
+/* obj[name] = three numbers -> out[3]; missing: left as it is, an element that is no number: 0 */
+static void prop_float3(napi_env env, napi_value obj, const char *name, float *out) {
+    napi_value v;
+    bool has = false;
+    if (napi_has_named_property(env, obj, name, &has) != napi_ok || !has || napi_get_named_property(env, obj, name, &v) != napi_ok) return;
+    for (uint32_t k = 0; k < 3; k++) {
+        napi_value e;
+        double d = 0;
+        if (napi_get_element(env, v, k, &e) == napi_ok) napi_get_value_double(env, e, &d);
+        out[k] = (float)d;
+    }
+}
+
+/* ---- the parameter objects of the draws and of the export calls: plain JS objects whose property names are the fields' (the reference's uniform /
+ * define names), read by one reader from one table per struct of include/rfx.h: {field, kind, offset, default where the property is missing}.
+ * An int or a float takes a number or a boolean; INT2 (a define bool[2]) a scalar for both or an array, default 0; FLOAT3 an array, default 0;
+ * FLOAT2 and CAMERA are required.  -NAN (denoise): the quiet NaN with the sign bit set, what 0.0 / 0.0 evaluated at run time gives on the host.
+ * A table lists every field of its struct, in the struct's order: table_that_misses_a_field() below, checked when the addon loads. */
+typedef enum { F_INT, F_FLOAT, F_INT2, F_FLOAT2, F_FLOAT3, F_CAMERA } field_kind;
+static const size_t FIELD_BYTES[] = {sizeof(int32_t), sizeof(float), 2 * sizeof(int32_t), 2 * sizeof(float), 3 * sizeof(float), sizeof(rfx_camera)};
+typedef struct { const char *name; field_kind kind; size_t offset; double def; } field;
+#define FIELD(S, name, kind, def) {#name, kind, offsetof(S, name), def}
+
+#define S rfx_ssgi_params
+static const field ssgi_fields[] = {
+    FIELD(S, camera, F_CAMERA, 0), FIELD(S, steps, F_INT, 20), FIELD(S, refineSteps, F_INT, 5), FIELD(S, mode, F_INT, 0), FIELD(S, useDirectLight, F_INT, 0),
+    FIELD(S, missedRays, F_INT, 0), FIELD(S, importanceSampling, F_INT, 0), FIELD(S, useEnvMap, F_INT, 0), FIELD(S, rayDistance, F_FLOAT, 10),
+    FIELD(S, thickness, F_FLOAT, 10), FIELD(S, envBlur, F_FLOAT, 0.5), FIELD(S, blueNoiseIndex, F_INT, 0), FIELD(S, resolutionScale, F_FLOAT, 1),
+    FIELD(S, historySource, F_INT, 0),
+};
+#undef S
+#define S rfx_temporal_params
+static const field temporal_fields[] = {
+    FIELD(S, camera, F_CAMERA, 0), FIELD(S, prevCamera, F_CAMERA, 0), FIELD(S, textureCount, F_INT, 2), FIELD(S, inputType, F_INT, 0),
+    FIELD(S, reprojectSpecular, F_INT2, 0), FIELD(S, neighborhoodClamp, F_INT2, 0), FIELD(S, logTransform, F_INT, 0), FIELD(S, fullAccumulate, F_INT, 0),
+    FIELD(S, confidencePower, F_FLOAT, 0.75), FIELD(S, neighborhoodClampIntensity, F_FLOAT, 1), FIELD(S, maxBlend, F_FLOAT, 1), FIELD(S, keepData, F_FLOAT, 1),
+    FIELD(S, historySource, F_INT, 0), FIELD(S, targetHalf, F_INT, 0), FIELD(S, halfStoreRTZ, F_INT, 1), FIELD(S, inputWidth, F_INT, 0),
+    FIELD(S, inputHeight, F_INT, 0),
+};
+#undef S
+#define S rfx_denoise_params
+static const field denoise_fields[] = {
+    FIELD(S, radius, F_FLOAT, 3), FIELD(S, phi, F_FLOAT, 0.5), FIELD(S, lumaPhi, F_FLOAT, 5), FIELD(S, depthPhi, F_FLOAT, 2), FIELD(S, normalPhi, F_FLOAT, 3.25),
+    FIELD(S, roughnessPhi, F_FLOAT, -NAN), FIELD(S, specularPhi, F_FLOAT, -NAN), FIELD(S, textureCount, F_INT, 2),
+    FIELD(S, isTextureSpecular, F_INT2, 0), FIELD(S, blueNoiseIndex, F_INT, 0), FIELD(S, inputIsTemporal, F_INT, 1), FIELD(S, writeToB, F_INT, 0),
+    FIELD(S, halfStoreRTZ, F_INT, 0),
+};
+#undef S
+#define S rfx_compose_params
+static const field compose_fields[] = {
+    FIELD(S, camera, F_CAMERA, 0), FIELD(S, inputType, F_INT, 0), FIELD(S, giSource, F_INT, 0), FIELD(S, writeHistoryRGB, F_INT, 0),
+};
+#undef S
+#define S rfx_final_params
+static const field final_fields[] = {
+    FIELD(S, camera, F_CAMERA, 0), FIELD(S, isDebug, F_INT, 0), FIELD(S, inputSource, F_INT, 0), FIELD(S, fogMode, F_INT, 0), FIELD(S, fogColor, F_FLOAT3, 0),
+    FIELD(S, fogNear, F_FLOAT, 0), FIELD(S, fogFar, F_FLOAT, 0), FIELD(S, fogDensity, F_FLOAT, 0),
+};
+#undef S
+#define S rfx_motion_blur_params
+static const field motion_blur_fields[] = {
+    FIELD(S, source, F_INT, RFX_TEX_FINAL), FIELD(S, center, F_INT, -1), FIELD(S, centerAlphaOne, F_INT, 0), FIELD(S, samples, F_INT, 16),
+    FIELD(S, intensity, F_FLOAT, 1), FIELD(S, jitter, F_FLOAT, 1), FIELD(S, deltaTime, F_FLOAT, 0), FIELD(S, frame, F_INT, 0), FIELD(S, resolution, F_FLOAT2, 0),
+    FIELD(S, targetHalf, F_INT, 0), FIELD(S, halfStoreRTZ, F_INT, 1),
+};
+#undef S
+#define S rfx_export_params
+static const field export_fields[] = {
+    FIELD(S, source, F_INT, RFX_TEX_FINAL), FIELD(S, format, F_INT, RFX_EXPORT_U8_SRGB), FIELD(S, channels, F_INT, 3), FIELD(S, tonemap, F_INT, 0),
+    FIELD(S, exposure, F_FLOAT, 1),
+};
+#undef S
+
+typedef enum { P_SSGI, P_TEMPORAL, P_DENOISE, P_COMPOSE, P_FINAL, P_MOTION_BLUR, P_EXPORT, P_COUNT } params_kind;
+typedef union {
+    rfx_ssgi_params ssgi; rfx_temporal_params temporal; rfx_denoise_params denoise; rfx_compose_params compose; rfx_final_params final;
+    rfx_motion_blur_params motion_blur; rfx_export_params export_;
+} any_params;
+#define TABLE(name, fields, S) {name, fields, sizeof fields / sizeof fields[0], sizeof(S)}
+static const struct { const char *name; const field *fields; size_t count, size; } PARAMS[P_COUNT] = {  /* name: paramBytes' `kind` */
+    TABLE("ssgi", ssgi_fields, rfx_ssgi_params), TABLE("temporal", temporal_fields, rfx_temporal_params), TABLE("denoise", denoise_fields, rfx_denoise_params),
+    TABLE("compose", compose_fields, rfx_compose_params), TABLE("final", final_fields, rfx_final_params),
+    TABLE("motionBlur", motion_blur_fields, rfx_motion_blur_params), TABLE("export", export_fields, rfx_export_params),
+};
+
+/* NULL, or the name of a table whose fields do not tile its struct from offset 0 to sizeof: a field of rfx.h that a table forgets must stop the
+ * addon from loading instead of reading as 0 (the structs hold 4-byte members only: no padding) */
+static const char *table_that_misses_a_field(void) {
+    for (int k = 0; k < P_COUNT; k++) {
+        size_t at = 0;
+        for (size_t i = 0; i < PARAMS[k].count; at += FIELD_BYTES[PARAMS[k].fields[i++].kind])
+            if (PARAMS[k].fields[i].offset != at) return PARAMS[k].name;
+        if (at != PARAMS[k].size) return PARAMS[k].name;
+    }
+    return NULL;
+}
+
+/* obj -> the struct of `kind` at `out`, as the call passes it to the C ABI.  Returns 0 (a type error is pending, naming `who`) when a required field
+ * is missing or malformed. */
+static int read_params(napi_env env, napi_value obj, params_kind kind, const char *who, void *out) {
+    memset(out, 0, PARAMS[kind].size);
+    for (size_t i = 0; i < PARAMS[kind].count; i++) {
+        const field *f = &PARAMS[kind].fields[i];
+        void *at = (char *)out + f->offset;
+        switch (f->kind) {
+        case F_INT: *(int32_t *)at = (int32_t)prop_num(env, obj, f->name, f->def); break;
+        case F_FLOAT: *(float *)at = (float)prop_num(env, obj, f->name, f->def); break;
+        case F_INT2: prop_bool2(env, obj, f->name, (int32_t *)at); break;
+        case F_FLOAT3: prop_float3(env, obj, f->name, (float *)at); break;
+        case F_CAMERA: if (!read_camera(env, obj, f->name, (rfx_camera *)at)) return 0; break;
+        case F_FLOAT2:
+            if (!prop_floats(env, obj, f->name, (float *)at, 2)) {
+                char msg[96];
+                snprintf(msg, sizeof msg, "%s: %s must hold 2 numbers", who, f->name);
+                napi_throw_type_error(env, NULL, msg);
+                return 0;
+            }
+            break;
+        }
+    }
+    return 1;
+}
+static int kind_by_name(napi_env env, napi_value v) {
+    char name[16] = "";
+    size_t n = 0;
+    if (napi_get_value_string_utf8(env, v, name, sizeof name, &n) == napi_ok)
+        for (int k = 0; k < P_COUNT; k++) if (!strcmp(name, PARAMS[k].name)) return k;
+    return -1;
+}
+/* paramBytes(kind, object) -> Buffer: the struct of "ssgi" | "temporal" | "denoise" | "compose" | "final" | "motionBlur" | "export" exactly as the
+ * corresponding call passes it to the C ABI.  A test hook in the spirit of the library's rfx_internal_* plan exports: no context, no GPU; js/ does
+ * not use it. */
+static napi_value n_param_bytes(napi_env env, napi_callback_info info) {
+    napi_value a[2], buf;
+    any_params p;
+    void *copy = NULL;
+    if (!get_args(env, info, 2, a)) return NULL;
+    const int kind = kind_by_name(env, a[0]);
+    if (kind < 0) { napi_throw_range_error(env, NULL, "paramBytes: unknown kind"); return NULL; }
+    if (!read_params(env, a[1], (params_kind)kind, "paramBytes", &p)) return NULL;
+    NAPI_CALL(env, napi_create_buffer_copy(env, PARAMS[kind].size, &p, &copy, &buf));
+    return buf;
+}
+/* the draws and the calls like them — (ctx, params object): read the struct of `kind`, call, throw on rc.  One row of EXPORTS each (DRAW) */
+typedef struct { const char *js, *c_name; params_kind kind; int (*fn)(rfx_ctx *, const void *); } params_fn;
+#define PARAMS_FN(fn, T) static int p_##fn(rfx_ctx *c, const void *p) { return fn(c, (const T *)p); }
+PARAMS_FN(rfx_ssgi_march, rfx_ssgi_params) PARAMS_FN(rfx_ssgi_trace, rfx_ssgi_params) PARAMS_FN(rfx_ssgi_shade, rfx_ssgi_params)
+PARAMS_FN(rfx_temporal_reproject, rfx_temporal_params) PARAMS_FN(rfx_poisson_denoise, rfx_denoise_params) PARAMS_FN(rfx_compose, rfx_compose_params)
+PARAMS_FN(rfx_final_compose, rfx_final_params) PARAMS_FN(rfx_motion_blur, rfx_motion_blur_params) PARAMS_FN(rfx_motion_blur_stage, rfx_motion_blur_params)
+static napi_value params_call(napi_env env, napi_callback_info info) {
+    const params_fn *d = (const params_fn *)call_data(env, info);
+    napi_value a[2];
+    any_params p;
+    if (!get_args(env, info, 2, a)) return NULL;
+    rfx_ctx *c = get_ctx(env, a[0]);
+    if (!c || !read_params(env, a[1], d->kind, d->js, &p)) return NULL;
+    int rc = d->fn(c, &p);
+    if (rc) return throw_rfx(env, c, d->c_name, rc);
+    return NULL;
+}
+/* ... and the calls whose arguments are (ctx, n integers): get them, call, throw on rc.  One row of EXPORTS each (INTS) */
+typedef struct { const char *c_name; size_t n; int (*fn)(rfx_ctx *, const int32_t *v); } ints_fn;
+#define INTS_FN(fn, call) static int i_##fn(rfx_ctx *c, const int32_t *v) { (void)v; return call; }
+INTS_FN(rfx_stage_flip, rfx_stage_flip(c)) INTS_FN(rfx_clear, rfx_clear(c, (rfx_tex)v[0])) INTS_FN(rfx_copy_framebuffer, rfx_copy_framebuffer(c, (rfx_tex)v[0]))
+INTS_FN(rfx_build_environment_importance, rfx_build_environment_importance(c, v[0])) INTS_FN(rfx_set_row_window, rfx_set_row_window(c, v[0], v[1]))
+INTS_FN(rfx_set_uv_model, rfx_set_uv_model(c, v[0])) INTS_FN(rfx_export_wait, rfx_export_wait(c, v[0])) INTS_FN(rfx_sync, rfx_sync(c))
+INTS_FN(rfx_time_begin, rfx_time_begin(c)) INTS_FN(rfx_halo_exchange, rfx_halo_exchange(c, (rfx_tex)v[0], NULL, v[1], v[2]))
+INTS_FN(rfx_allgather_history, rfx_allgather_history(c, (rfx_tex)v[0], NULL)) INTS_FN(rfx_comm_wait, rfx_comm_wait(c)) INTS_FN(rfx_peer_close, rfx_peer_close(c))
+INTS_FN(rfx_comm_destroy, (rfx_comm_destroy(c), RFX_OK))  /* (its result was never reported) */
+static napi_value ints_call(napi_env env, napi_callback_info info) {
+    const ints_fn *d = (const ints_fn *)call_data(env, info);
+    napi_value a[4];
+    int32_t v[3] = {0, 0, 0};
+    if (!get_args(env, info, 1 + d->n, a)) return NULL;
+    rfx_ctx *c = get_ctx(env, a[0]);
+    if (!c) return NULL;
+    for (size_t i = 0; i < d->n; i++) if (!get_int(env, a[1 + i], &v[i])) return NULL;
+    int rc = d->fn(c, v);
+    if (rc) return throw_rfx(env, c, d->c_name, rc);
+    return NULL;
+}
+
 static void destroy_ctx(napi_env env, void *data, void *hint) { (void)env; (void)hint; rfx_destroy((rfx_ctx *)data); }
 
 /* create(device, width, height, tileY0, tileRows, haloRows) -> handle */
@@ -151,9 +340,17 @@ static napi_value n_abi_version(napi_env env, napi_callback_info info) {
     return out;
 }
 
+/* [a, b] */
+static napi_value int_pair(napi_env env, int a, int b) {
+    napi_value arr, e;
+    NAPI_CALL(env, napi_create_array_with_length(env, 2, &arr));
+    napi_create_int32(env, a, &e); napi_set_element(env, arr, 0, e);
+    napi_create_int32(env, b, &e); napi_set_element(env, arr, 1, e);
+    return arr;
+}
 /* heldRows(ctx, tex) -> [row0, rows] */
 static napi_value n_held_rows(napi_env env, napi_callback_info info) {
-    napi_value a[2], arr, e;
+    napi_value a[2];
     int32_t tex;
     if (!get_args(env, info, 2, a)) return NULL;
     rfx_ctx *c = get_ctx(env, a[0]);
@@ -161,15 +358,12 @@ static napi_value n_held_rows(napi_env env, napi_callback_info info) {
     int r0 = 0, n = 0;
     int rc = rfx_tex_held_rows(c, (rfx_tex)tex, &r0, &n);
     if (rc) return throw_rfx(env, c, "rfx_tex_held_rows", rc);
-    NAPI_CALL(env, napi_create_array_with_length(env, 2, &arr));
-    napi_create_int32(env, r0, &e); napi_set_element(env, arr, 0, e);
-    napi_create_int32(env, n, &e); napi_set_element(env, arr, 1, e);
-    return arr;
+    return int_pair(env, r0, n);
 }
 
 /* ssgiTargetRows(ctx, resolutionScale) -> [row0, rows]: rfx_ssgi_target_rows */
 static napi_value n_ssgi_target_rows(napi_env env, napi_callback_info info) {
-    napi_value a[2], arr, e;
+    napi_value a[2];
     double scale = 1.0;
     if (!get_args(env, info, 2, a)) return NULL;
     rfx_ctx *c = get_ctx(env, a[0]);
@@ -181,14 +375,15 @@ static napi_value n_ssgi_target_rows(napi_env env, napi_callback_info info) {
     int r0 = 0, n = 0;
     int rc = rfx_ssgi_target_rows(c, (float)scale, &r0, &n);
     if (rc) return throw_rfx(env, c, "rfx_ssgi_target_rows", rc);
-    NAPI_CALL(env, napi_create_array_with_length(env, 2, &arr));
-    napi_create_int32(env, r0, &e); napi_set_element(env, arr, 0, e);
-    napi_create_int32(env, n, &e); napi_set_element(env, arr, 1, e);
-    return arr;
+    return int_pair(env, r0, n);
 }
 
-/* upload(ctx, tex, typedArray, row0, rows) / download(ctx, tex, typedArray, row0, rows) */
-static napi_value xfer(napi_env env, napi_callback_info info, int up) {
+/* download (XFER[0]) / upload (XFER[1]) / stageUpload (XFER[2]) (ctx, tex, typedArray, row0, rows).  stageUpload: asynchronous copy into the slot's
+ * back buffer (rfx.h "streaming dumps"); the array — ideally a view of hostAlloc() memory — must stay alive and unchanged until the flip that
+ * publishes it has been synced */
+static const int XFER[3] = {0, 1, 2};
+static napi_value xfer(napi_env env, napi_callback_info info) {
+    const int up = *(const int *)call_data(env, info);
     napi_value a[5];
     int32_t tex, row0, rows;
     if (!get_args(env, info, 5, a)) return NULL;
@@ -212,18 +407,6 @@ static napi_value xfer(napi_env env, napi_callback_info info, int up) {
     int rc = up == 2 ? rfx_stage_upload(c, (rfx_tex)tex, data, row0, rows)
              : up ? rfx_upload(c, (rfx_tex)tex, data, row0, rows) : rfx_download(c, (rfx_tex)tex, data, row0, rows);
     if (rc) return throw_rfx(env, c, up == 2 ? "rfx_stage_upload" : up ? "rfx_upload" : "rfx_download", rc);
-    return NULL;
-}
-/* stageUpload(ctx, tex, typedArray, row0, rows): asynchronous copy into the slot's back buffer (rfx.h "streaming dumps"); the array —
- * ideally a view of hostAlloc() memory — must stay alive and unchanged until the flip that publishes it has been synced */
-static napi_value n_stage_upload(napi_env env, napi_callback_info info) { return xfer(env, info, 2); }
-static napi_value n_stage_flip(napi_env env, napi_callback_info info) {
-    napi_value a[1];
-    if (!get_args(env, info, 1, a)) return NULL;
-    rfx_ctx *c = get_ctx(env, a[0]);
-    if (!c) return NULL;
-    int rc = rfx_stage_flip(c);
-    if (rc) return throw_rfx(env, c, "rfx_stage_flip", rc);
     return NULL;
 }
 static void host_free_cb(napi_env env, void *data, void *hint) { (void)env; (void)hint; rfx_host_free(data); }
@@ -278,7 +461,9 @@ static int read_aov_frame(napi_env env, rfx_ctx *c, napi_value obj, int32_t rows
 }
 /* stageAov(ctx, planes, row0, rows): rfx_stage_aov (rfx.h "streamed AOV frames"); the arrays — ideally views of hostAlloc() memory — must stay
  * alive and unchanged like stageUpload's.  aovStageBytes(ctx, planes, row0, rows) -> the bytes that call copies (0: it would be refused) */
-static napi_value aov_call(napi_env env, napi_callback_info info, int stage) {
+static const int AOV_BYTES = 0, AOV_STAGE = 1;
+static napi_value aov_call(napi_env env, napi_callback_info info) {
+    const int stage = *(const int *)call_data(env, info);
     napi_value a[4], out;
     int32_t row0, rows;
     rfx_aov_frame f;
@@ -331,8 +516,6 @@ static napi_value n_set_aov_conventions(napi_env env, napi_callback_info info) {
     if (rc) return throw_rfx(env, c, "rfx_set_aov_conventions", rc);
     return NULL;
 }
-static napi_value n_stage_aov(napi_env env, napi_callback_info info) { return aov_call(env, info, 1); }
-static napi_value n_aov_stage_bytes(napi_env env, napi_callback_info info) { return aov_call(env, info, 0); }
 /* An EXR frame descriptor (rfx.h "streamed EXR frames") from what imageio.exrAovLayout returns: `bytes` the file (a Uint8Array / Buffer, ideally over
  * hostAlloc() memory), `parts` an Int32Array [parts, then per part: compression, channels, then per channel: pixel type, plane, component],
  * `chunks` a Uint8Array of rfx_exr_chunk records.  The descriptor is consumed by the call: its tables are copies in one block, *hold, which the
@@ -374,9 +557,26 @@ static int read_exr_frame(napi_env env, napi_value bytes, napi_value parts, napi
     *hold = block;
     return 1;
 }
-/* stageExrAov(ctx, bytes, parts, chunks, row0, rows): rfx_stage_exr_aov; `bytes` must stay alive and unchanged like stageUpload's planes.
- * exrAovStageBytes(...) -> the bytes that call copies (0: it would be refused).  exrAovStatus(ctx) -> [bad chunks, first bad chunk, code] */
-static napi_value exr_aov_call(napi_env env, napi_callback_info info, int stage) {
+/* The calls on an EXR frame, (ctx, bytes, parts, records, row0, rows): stageExrAov -> rfx_stage_exr_aov, `records` a Uint8Array of rfx_exr_chunk;
+ * stageExrBlocks -> rfx_stage_exr_blocks (rfx.h "EXR blocks"), `records` of rfx_exr_block (imageio.exrAovLayout(..., { forms: "blocks" }));
+ * stageExrBlocksPiz -> rfx_stage_exr_blocks_piz (rfx.h "EXR blocks with PIZ": a part's compression may also be 4).  `bytes` must stay alive and
+ * unchanged like stageUpload's planes.  exrAovStageBytes / exrBlocksStageBytes / exrBlocksPizStageBytes(...) -> the bytes that call copies (0: it
+ * would be refused).  The two descriptors differ in the record type alone: a form has either the chunk functions or the block ones. */
+typedef struct {
+    const char *c_name;
+    size_t record;
+    int (*stage_chunks)(rfx_ctx *, const rfx_exr_frame *, int, int);
+    size_t (*bytes_chunks)(const rfx_ctx *, const rfx_exr_frame *, int, int);
+    int (*stage_blocks)(rfx_ctx *, const rfx_exr_block_frame *, int, int);
+    size_t (*bytes_blocks)(const rfx_ctx *, const rfx_exr_block_frame *, int, int);
+} exr_form;
+static const exr_form EXR_CHUNKS = {"rfx_stage_exr_aov", sizeof(rfx_exr_chunk), rfx_stage_exr_aov, rfx_exr_aov_stage_bytes, NULL, NULL};
+static const exr_form EXR_BLOCKS = {"rfx_stage_exr_blocks", sizeof(rfx_exr_block), NULL, NULL, rfx_stage_exr_blocks, rfx_exr_blocks_stage_bytes};
+static const exr_form EXR_PIZ = {"rfx_stage_exr_blocks_piz", sizeof(rfx_exr_block), NULL, NULL, rfx_stage_exr_blocks_piz, rfx_exr_blocks_piz_stage_bytes};
+typedef struct { const exr_form *form; int stage; } exr_fn;
+static napi_value exr_frame_call(napi_env env, napi_callback_info info) {
+    const exr_fn *d = (const exr_fn *)call_data(env, info);
+    const exr_form *form = d->form;
     napi_value a[6], out = NULL;
     int32_t row0, rows;
     rfx_exr_frame f;
@@ -384,49 +584,20 @@ static napi_value exr_aov_call(napi_env env, napi_callback_info info, int stage)
     if (!get_args(env, info, 6, a)) return NULL;
     rfx_ctx *c = get_ctx(env, a[0]);
     if (!c || !get_int(env, a[4], &row0) || !get_int(env, a[5], &rows)) return NULL;
-    if (!read_exr_frame(env, a[1], a[2], a[3], sizeof(rfx_exr_chunk), &f, &hold)) return NULL;
-    if (!stage) {
-        const size_t n = rfx_exr_aov_stage_bytes(c, &f, row0, rows);
-        free(hold);
-        NAPI_CALL(env, napi_create_double(env, (double)n, &out));
-        return out;
-    }
-    int rc = rfx_stage_exr_aov(c, &f, row0, rows);
-    free(hold);
-    if (rc) return throw_rfx(env, c, "rfx_stage_exr_aov", rc);
-    return NULL;
-}
-static napi_value n_stage_exr_aov(napi_env env, napi_callback_info info) { return exr_aov_call(env, info, 1); }
-static napi_value n_exr_aov_stage_bytes(napi_env env, napi_callback_info info) { return exr_aov_call(env, info, 0); }
-/* stageExrBlocks / exrBlocksStageBytes(ctx, bytes, parts, blocks, row0, rows): rfx_stage_exr_blocks / rfx_exr_blocks_stage_bytes (rfx.h "EXR
- * blocks") — the same arguments, `blocks` a Uint8Array of rfx_exr_block records (imageio.exrAovLayout(..., { forms: "blocks" })) */
-static napi_value exr_blocks_call(napi_env env, napi_callback_info info, int stage, int piz) {
-    napi_value a[6], out = NULL;
-    int32_t row0, rows;
-    rfx_exr_frame f;
-    void *hold;
-    if (!get_args(env, info, 6, a)) return NULL;
-    rfx_ctx *c = get_ctx(env, a[0]);
-    if (!c || !get_int(env, a[4], &row0) || !get_int(env, a[5], &rows)) return NULL;
-    if (!read_exr_frame(env, a[1], a[2], a[3], sizeof(rfx_exr_block), &f, &hold)) return NULL;
+    if (!read_exr_frame(env, a[1], a[2], a[3], form->record, &f, &hold)) return NULL;
     const rfx_exr_block_frame b = {f.data, f.bytes, f.parts, f.chunks, f.part, (const rfx_exr_block *)hold};  /* (the records lead the block) */
-    if (!stage) {
-        const size_t n = piz ? rfx_exr_blocks_piz_stage_bytes(c, &b, row0, rows) : rfx_exr_blocks_stage_bytes(c, &b, row0, rows);
+    if (!d->stage) {
+        const size_t n = form->bytes_blocks ? form->bytes_blocks(c, &b, row0, rows) : form->bytes_chunks(c, &f, row0, rows);
         free(hold);
         NAPI_CALL(env, napi_create_double(env, (double)n, &out));
         return out;
     }
-    int rc = piz ? rfx_stage_exr_blocks_piz(c, &b, row0, rows) : rfx_stage_exr_blocks(c, &b, row0, rows);
+    int rc = form->stage_blocks ? form->stage_blocks(c, &b, row0, rows) : form->stage_chunks(c, &f, row0, rows);
     free(hold);
-    if (rc) return throw_rfx(env, c, piz ? "rfx_stage_exr_blocks_piz" : "rfx_stage_exr_blocks", rc);
+    if (rc) return throw_rfx(env, c, form->c_name, rc);
     return NULL;
 }
-static napi_value n_stage_exr_blocks(napi_env env, napi_callback_info info) { return exr_blocks_call(env, info, 1, 0); }
-static napi_value n_exr_blocks_stage_bytes(napi_env env, napi_callback_info info) { return exr_blocks_call(env, info, 0, 0); }
-/* stageExrBlocksPiz / exrBlocksPizStageBytes: the same through rfx_stage_exr_blocks_piz / rfx_exr_blocks_piz_stage_bytes (rfx.h "EXR blocks with
- * PIZ": a part's compression may also be 4) */
-static napi_value n_stage_exr_blocks_piz(napi_env env, napi_callback_info info) { return exr_blocks_call(env, info, 1, 1); }
-static napi_value n_exr_blocks_piz_stage_bytes(napi_env env, napi_callback_info info) { return exr_blocks_call(env, info, 0, 1); }
+/* exrAovStatus(ctx) -> [bad chunks, first bad chunk, code] */
 static napi_value n_exr_aov_status(napi_env env, napi_callback_info info) {
     napi_value a[1], out, v;
     int s[3] = {0, -1, 0};
@@ -441,19 +612,6 @@ static napi_value n_exr_aov_status(napi_env env, napi_callback_info info) {
         NAPI_CALL(env, napi_set_element(env, out, i, v));
     }
     return out;
-}
-static napi_value n_upload(napi_env env, napi_callback_info info) { return xfer(env, info, 1); }
-static napi_value n_download(napi_env env, napi_callback_info info) { return xfer(env, info, 0); }
-
-static napi_value n_clear(napi_env env, napi_callback_info info) {
-    napi_value a[2];
-    int32_t tex;
-    if (!get_args(env, info, 2, a)) return NULL;
-    rfx_ctx *c = get_ctx(env, a[0]);
-    if (!c || !get_int(env, a[1], &tex)) return NULL;
-    int rc = rfx_clear(c, (rfx_tex)tex);
-    if (rc) return throw_rfx(env, c, "rfx_clear", rc);
-    return NULL;
 }
 
 static const float *f32_prop(napi_env env, napi_value obj, const char *name, size_t want, int optional, int *ok) {
@@ -477,7 +635,9 @@ static const float *f32_prop(napi_env env, napi_value obj, const char *name, siz
 }
 
 /* packGBuffer(ctx, {diffuse, normal, roughness, metalness, emissive, depth?}, row0, rows) / packVelocity(ctx, {velocity, normal, depth}, row0, rows) */
-static napi_value n_pack(napi_env env, napi_callback_info info, int velocity) {
+static const int PACK_GBUFFER = 0, PACK_VELOCITY = 1;
+static napi_value n_pack(napi_env env, napi_callback_info info) {
+    const int velocity = *(const int *)call_data(env, info);
     napi_value a[4];
     int32_t row0, rows, W = 0;
     if (!get_args(env, info, 4, a)) return NULL;
@@ -499,8 +659,6 @@ static napi_value n_pack(napi_env env, napi_callback_info info, int velocity) {
     if (rc) return throw_rfx(env, c, velocity ? "rfx_pack_velocity" : "rfx_pack_gbuffer", rc);
     return NULL;
 }
-static napi_value n_pack_gbuffer(napi_env env, napi_callback_info info) { return n_pack(env, info, 0); }
-static napi_value n_pack_velocity(napi_env env, napi_callback_info info) { return n_pack(env, info, 1); }
 
 /* setEnvironment(ctx, Float32Array | null, width, height, halfFloatType, halfStoreRTZ) — scene.environment (rfx_set_environment) */
 static napi_value n_set_environment(napi_env env, napi_callback_info info) {
@@ -611,17 +769,6 @@ static napi_value n_set_environment_cube(napi_env env, napi_callback_info info) 
     if (rc) return throw_rfx(env, c, "rfx_set_environment_cube", rc);
     return NULL;
 }
-/* buildEnvironmentImportance(ctx, flipY): rfx_build_environment_importance (K10) */
-static napi_value n_build_environment_importance(napi_env env, napi_callback_info info) {
-    napi_value a[2];
-    if (!get_args(env, info, 2, a)) return NULL;
-    rfx_ctx *c = get_ctx(env, a[0]);
-    int32_t flip = 0;
-    if (!c || !get_int(env, a[1], &flip)) return NULL;
-    int rc = rfx_build_environment_importance(c, flip);
-    if (rc) return throw_rfx(env, c, "rfx_build_environment_importance", rc);
-    return NULL;
-}
 /* downloadEnvironmentImportance(ctx, Float32Array marginal[height], Float32Array conditional[width * height]) -> {totalSumValue, whole, decimal}
  * (the caller sizes the arrays for the environment it set: the library copies height and width * height floats) */
 static napi_value n_download_environment_importance(napi_env env, napi_callback_info info) {
@@ -665,93 +812,6 @@ static napi_value n_download_environment_importance(napi_env env, napi_callback_
     NAPI_CALL(env, napi_create_double(env, dec, &v));
     NAPI_CALL(env, napi_set_named_property(env, out, "decimal", v));
     return out;
-}
-
-/* ssgiMarch / ssgiTrace / ssgiShade(ctx, {camera, steps, refineSteps, mode, useDirectLight, missedRays, importanceSampling,
- *                 rayDistance, thickness, envBlur, blueNoiseIndex, historySource, resolutionScale, useEnvMap}) */
-static napi_value ssgi_stage(napi_env env, napi_callback_info info, int stage) {
-    napi_value a[2];
-    if (!get_args(env, info, 2, a)) return NULL;
-    rfx_ctx *c = get_ctx(env, a[0]);
-    if (!c) return NULL;
-    rfx_ssgi_params p;
-    memset(&p, 0, sizeof p);
-    if (!read_camera(env, a[1], "camera", &p.camera)) return NULL;
-    p.steps = (int32_t)prop_num(env, a[1], "steps", 20);
-    p.refineSteps = (int32_t)prop_num(env, a[1], "refineSteps", 5);
-    p.mode = (int32_t)prop_num(env, a[1], "mode", 0);
-    p.useDirectLight = (int32_t)prop_num(env, a[1], "useDirectLight", 0);
-    p.missedRays = (int32_t)prop_num(env, a[1], "missedRays", 0);
-    p.importanceSampling = (int32_t)prop_num(env, a[1], "importanceSampling", 0);
-    p.useEnvMap = (int32_t)prop_num(env, a[1], "useEnvMap", 0);
-    p.rayDistance = (float)prop_num(env, a[1], "rayDistance", 10);
-    p.thickness = (float)prop_num(env, a[1], "thickness", 10);
-    p.envBlur = (float)prop_num(env, a[1], "envBlur", 0.5);
-    p.blueNoiseIndex = (int32_t)prop_num(env, a[1], "blueNoiseIndex", 0);
-    p.historySource = (int32_t)prop_num(env, a[1], "historySource", 0);
-    p.resolutionScale = (float)prop_num(env, a[1], "resolutionScale", 1);
-    int rc = stage == 0 ? rfx_ssgi_march(c, &p) : (stage == 1 ? rfx_ssgi_trace(c, &p) : rfx_ssgi_shade(c, &p));
-    if (rc) return throw_rfx(env, c, stage == 0 ? "rfx_ssgi_march" : (stage == 1 ? "rfx_ssgi_trace" : "rfx_ssgi_shade"), rc);
-    return NULL;
-}
-static napi_value n_ssgi(napi_env env, napi_callback_info info) { return ssgi_stage(env, info, 0); }
-static napi_value n_ssgi_trace(napi_env env, napi_callback_info info) { return ssgi_stage(env, info, 1); }
-static napi_value n_ssgi_shade(napi_env env, napi_callback_info info) { return ssgi_stage(env, info, 2); }
-
-/* temporalReproject(ctx, {camera, prevCamera, textureCount, inputType, reprojectSpecular[2], neighborhoodClamp[2],
- *                         logTransform, fullAccumulate, confidencePower, neighborhoodClampIntensity, maxBlend, keepData,
- *                         historySource, targetHalf, halfStoreRTZ}) */
-static napi_value n_temporal(napi_env env, napi_callback_info info) {
-    napi_value a[2];
-    if (!get_args(env, info, 2, a)) return NULL;
-    rfx_ctx *c = get_ctx(env, a[0]);
-    if (!c) return NULL;
-    rfx_temporal_params p;
-    memset(&p, 0, sizeof p);
-    if (!read_camera(env, a[1], "camera", &p.camera) || !read_camera(env, a[1], "prevCamera", &p.prevCamera)) return NULL;
-    p.textureCount = (int32_t)prop_num(env, a[1], "textureCount", 2);
-    p.inputType = (int32_t)prop_num(env, a[1], "inputType", 0);
-    prop_bool2(env, a[1], "reprojectSpecular", p.reprojectSpecular);
-    prop_bool2(env, a[1], "neighborhoodClamp", p.neighborhoodClamp);
-    p.logTransform = (int32_t)prop_num(env, a[1], "logTransform", 0);
-    p.fullAccumulate = (int32_t)prop_num(env, a[1], "fullAccumulate", 0);
-    p.confidencePower = (float)prop_num(env, a[1], "confidencePower", 0.75);
-    p.neighborhoodClampIntensity = (float)prop_num(env, a[1], "neighborhoodClampIntensity", 1);
-    p.maxBlend = (float)prop_num(env, a[1], "maxBlend", 1);
-    p.keepData = (float)prop_num(env, a[1], "keepData", 1);
-    p.historySource = (int32_t)prop_num(env, a[1], "historySource", 0);
-    p.targetHalf = (int32_t)prop_num(env, a[1], "targetHalf", 0);
-    p.halfStoreRTZ = (int32_t)prop_num(env, a[1], "halfStoreRTZ", 1);
-    p.inputWidth = (int32_t)prop_num(env, a[1], "inputWidth", 0);
-    p.inputHeight = (int32_t)prop_num(env, a[1], "inputHeight", 0);
-    int rc = rfx_temporal_reproject(c, &p);
-    if (rc) return throw_rfx(env, c, "rfx_temporal_reproject", rc);
-    return NULL;
-}
-
-/* copyFramebuffer(ctx, dstTex) — renderer.copyFramebufferToTexture of TemporalReprojectPass.js:198-201 */
-/* setRowWindow(ctx, y0, y1): rfx_set_row_window (y1 <= y0 resets) */
-static napi_value n_set_row_window(napi_env env, napi_callback_info info) {
-    napi_value a[3];
-    int32_t y0, y1;
-    if (!get_args(env, info, 3, a)) return NULL;
-    rfx_ctx *c = get_ctx(env, a[0]);
-    if (!c || !get_int(env, a[1], &y0) || !get_int(env, a[2], &y1)) return NULL;
-    int rc = rfx_set_row_window(c, y0, y1);
-    if (rc) return throw_rfx(env, c, "rfx_set_row_window", rc);
-    return NULL;
-}
-
-/* setUvModel(ctx, model): rfx_set_uv_model (0 = RFX_UV_IDEAL, 1 = RFX_UV_REFERENCE_GL) */
-static napi_value n_set_uv_model(napi_env env, napi_callback_info info) {
-    napi_value a[2];
-    int32_t m;
-    if (!get_args(env, info, 2, a)) return NULL;
-    rfx_ctx *c = get_ctx(env, a[0]);
-    if (!c || !get_int(env, a[1], &m)) return NULL;
-    int rc = rfx_set_uv_model(c, m);
-    if (rc) return throw_rfx(env, c, "rfx_set_uv_model", rc);
-    return NULL;
 }
 
 /* ---- row-tiled runs (rfx.h "row-tiled runs"): one Node process per GPU */
@@ -800,28 +860,6 @@ static napi_value n_comm_init(napi_env env, napi_callback_info info) {
     }
     int rc = rfx_comm_init(c, data, rank, n);
     if (rc) return throw_rfx(env, c, "rfx_comm_init", rc);
-    return NULL;
-}
-/* haloExchange(ctx, tex, upRank, downRank) — -1 = no such neighbour */
-static napi_value n_halo_exchange(napi_env env, napi_callback_info info) {
-    napi_value a[4];
-    int32_t tex, up, down;
-    if (!get_args(env, info, 4, a)) return NULL;
-    rfx_ctx *c = get_ctx(env, a[0]);
-    if (!c || !get_int(env, a[1], &tex) || !get_int(env, a[2], &up) || !get_int(env, a[3], &down)) return NULL;
-    int rc = rfx_halo_exchange(c, (rfx_tex)tex, NULL, up, down);
-    if (rc) return throw_rfx(env, c, "rfx_halo_exchange", rc);
-    return NULL;
-}
-/* allgatherHistory(ctx, tex) */
-static napi_value n_allgather_history(napi_env env, napi_callback_info info) {
-    napi_value a[2];
-    int32_t tex;
-    if (!get_args(env, info, 2, a)) return NULL;
-    rfx_ctx *c = get_ctx(env, a[0]);
-    if (!c || !get_int(env, a[1], &tex)) return NULL;
-    int rc = rfx_allgather_history(c, (rfx_tex)tex, NULL);
-    if (rc) return throw_rfx(env, c, "rfx_allgather_history", rc);
     return NULL;
 }
 /* gatherHistoryRows(ctx, tex) -> bytes this rank receives (rfx_gather_history_rows: between ssgiTrace and ssgiShade) */
@@ -881,15 +919,6 @@ static napi_value n_peer_gather_history(napi_env env, napi_callback_info info) {
     napi_create_double(env, (double)got, &out);
     return out;
 }
-static napi_value n_peer_close(napi_env env, napi_callback_info info) {
-    napi_value a[1];
-    if (!get_args(env, info, 1, a)) return NULL;
-    rfx_ctx *c = get_ctx(env, a[0]);
-    if (!c) return NULL;
-    int rc = rfx_peer_close(c);
-    if (rc) return throw_rfx(env, c, "rfx_peer_close", rc);
-    return NULL;
-}
 /* ssgiHitMask(ctx, Uint32Array of frame-height entries): rfx_ssgi_hit_mask (after ssgiTrace; blocks until the trace has finished) */
 static napi_value n_ssgi_hit_mask(napi_env env, napi_callback_info info) {
     napi_value a[2], ab;
@@ -907,156 +936,7 @@ static napi_value n_ssgi_hit_mask(napi_env env, napi_callback_info info) {
     if (rc) return throw_rfx(env, c, "rfx_ssgi_hit_mask", rc);
     return NULL;
 }
-/* commWait(ctx) / commDestroy(ctx) */
-static napi_value n_comm_wait(napi_env env, napi_callback_info info) {
-    napi_value a[1];
-    if (!get_args(env, info, 1, a)) return NULL;
-    rfx_ctx *c = get_ctx(env, a[0]);
-    if (!c) return NULL;
-    int rc = rfx_comm_wait(c);
-    if (rc) return throw_rfx(env, c, "rfx_comm_wait", rc);
-    return NULL;
-}
-static napi_value n_comm_destroy(napi_env env, napi_callback_info info) {
-    napi_value a[1];
-    if (!get_args(env, info, 1, a)) return NULL;
-    rfx_ctx *c = get_ctx(env, a[0]);
-    if (!c) return NULL;
-    rfx_comm_destroy(c);
-    return NULL;
-}
 
-static napi_value n_copy_framebuffer(napi_env env, napi_callback_info info) {
-    napi_value a[2];
-    int32_t tex;
-    if (!get_args(env, info, 2, a)) return NULL;
-    rfx_ctx *c = get_ctx(env, a[0]);
-    if (!c || !get_int(env, a[1], &tex)) return NULL;
-    int rc = rfx_copy_framebuffer(c, (rfx_tex)tex);
-    if (rc) return throw_rfx(env, c, "rfx_copy_framebuffer", rc);
-    return NULL;
-}
-
-/* poissonDenoise(ctx, {radius, phi, lumaPhi, depthPhi, normalPhi, roughnessPhi, specularPhi, textureCount,
- *                      isTextureSpecular[2], blueNoiseIndex, inputIsTemporal, writeToB, halfStoreRTZ}) */
-static napi_value n_denoise(napi_env env, napi_callback_info info) {
-    napi_value a[2];
-    if (!get_args(env, info, 2, a)) return NULL;
-    rfx_ctx *c = get_ctx(env, a[0]);
-    if (!c) return NULL;
-    rfx_denoise_params p;
-    memset(&p, 0, sizeof p);
-    p.radius = (float)prop_num(env, a[1], "radius", 3);
-    p.phi = (float)prop_num(env, a[1], "phi", 0.5);
-    p.lumaPhi = (float)prop_num(env, a[1], "lumaPhi", 5);
-    p.depthPhi = (float)prop_num(env, a[1], "depthPhi", 2);
-    p.normalPhi = (float)prop_num(env, a[1], "normalPhi", 3.25);
-    p.roughnessPhi = (float)prop_num(env, a[1], "roughnessPhi", 0.0 / 0.0);
-    p.specularPhi = (float)prop_num(env, a[1], "specularPhi", 0.0 / 0.0);
-    p.textureCount = (int32_t)prop_num(env, a[1], "textureCount", 2);
-    prop_bool2(env, a[1], "isTextureSpecular", p.isTextureSpecular);
-    p.blueNoiseIndex = (int32_t)prop_num(env, a[1], "blueNoiseIndex", 0);
-    p.inputIsTemporal = (int32_t)prop_num(env, a[1], "inputIsTemporal", 1);
-    p.writeToB = (int32_t)prop_num(env, a[1], "writeToB", 0);
-    p.halfStoreRTZ = (int32_t)prop_num(env, a[1], "halfStoreRTZ", 0);
-    int rc = rfx_poisson_denoise(c, &p);
-    if (rc) return throw_rfx(env, c, "rfx_poisson_denoise", rc);
-    return NULL;
-}
-
-/* compose(ctx, {camera, inputType}) */
-static napi_value n_compose(napi_env env, napi_callback_info info) {
-    napi_value a[2];
-    if (!get_args(env, info, 2, a)) return NULL;
-    rfx_ctx *c = get_ctx(env, a[0]);
-    if (!c) return NULL;
-    rfx_compose_params p;
-    memset(&p, 0, sizeof p);
-    if (!read_camera(env, a[1], "camera", &p.camera)) return NULL;
-    p.inputType = (int32_t)prop_num(env, a[1], "inputType", 0);
-    p.giSource = (int32_t)prop_num(env, a[1], "giSource", 0);
-    p.writeHistoryRGB = (int32_t)prop_num(env, a[1], "writeHistoryRGB", 0);
-    int rc = rfx_compose(c, &p);
-    if (rc) return throw_rfx(env, c, "rfx_compose", rc);
-    return NULL;
-}
-
-/* finalCompose(ctx, {camera, isDebug, inputSource, fogMode, fogColor[3], fogNear, fogFar, fogDensity}) — SSGIEffect's own fragment */
-static napi_value n_final(napi_env env, napi_callback_info info) {
-    napi_value a[2];
-    if (!get_args(env, info, 2, a)) return NULL;
-    rfx_ctx *c = get_ctx(env, a[0]);
-    if (!c) return NULL;
-    rfx_final_params p;
-    memset(&p, 0, sizeof p);
-    if (!read_camera(env, a[1], "camera", &p.camera)) return NULL;
-    p.isDebug = (int32_t)prop_num(env, a[1], "isDebug", 0);
-    p.inputSource = (int32_t)prop_num(env, a[1], "inputSource", 0);
-    p.fogMode = (int32_t)prop_num(env, a[1], "fogMode", 0);
-    napi_value fc;
-    bool has = false;
-    if (napi_has_named_property(env, a[1], "fogColor", &has) == napi_ok && has && napi_get_named_property(env, a[1], "fogColor", &fc) == napi_ok) {
-        for (uint32_t k = 0; k < 3; k++) {
-            napi_value e;
-            double v = 0;
-            if (napi_get_element(env, fc, k, &e) == napi_ok) napi_get_value_double(env, e, &v);
-            p.fogColor[k] = (float)v;
-        }
-    }
-    p.fogNear = (float)prop_num(env, a[1], "fogNear", 0);
-    p.fogFar = (float)prop_num(env, a[1], "fogFar", 0);
-    p.fogDensity = (float)prop_num(env, a[1], "fogDensity", 0);
-    int rc = rfx_final_compose(c, &p);
-    if (rc) return throw_rfx(env, c, "rfx_final_compose", rc);
-    return NULL;
-}
-
-/* the uniforms object of the four motion-blur calls: {source, center, centerAlphaOne, samples, intensity, jitter, deltaTime, frame, resolution[2],
- * targetHalf, halfStoreRTZ} -> rfx_motion_blur_params.  Returns 0 (a type error is pending) when `resolution` is malformed. */
-static int motion_blur_params(napi_env env, napi_value o, const char *who, rfx_motion_blur_params *p) {
-    memset(p, 0, sizeof *p);
-    p->source = (int32_t)prop_num(env, o, "source", RFX_TEX_FINAL);
-    p->center = (int32_t)prop_num(env, o, "center", -1);
-    p->centerAlphaOne = (int32_t)prop_num(env, o, "centerAlphaOne", 0);
-    p->samples = (int32_t)prop_num(env, o, "samples", 16);
-    p->intensity = (float)prop_num(env, o, "intensity", 1);
-    p->jitter = (float)prop_num(env, o, "jitter", 1);
-    p->deltaTime = (float)prop_num(env, o, "deltaTime", 0);
-    p->frame = (int32_t)prop_num(env, o, "frame", 0);
-    if (!prop_floats(env, o, "resolution", p->resolution, 2)) {
-        char msg[96];
-        snprintf(msg, sizeof msg, "%s: resolution must hold 2 numbers", who);
-        napi_throw_type_error(env, NULL, msg);
-        return 0;
-    }
-    p->targetHalf = (int32_t)prop_num(env, o, "targetHalf", 0);
-    p->halfStoreRTZ = (int32_t)prop_num(env, o, "halfStoreRTZ", 1);
-    return 1;
-}
-/* motionBlur(ctx, uniforms) — MotionBlurEffect's fragment (K6, rfx_motion_blur) -> RFX_TEX_MOTION_BLUR */
-static napi_value n_motion_blur(napi_env env, napi_callback_info info) {
-    napi_value a[2];
-    if (!get_args(env, info, 2, a)) return NULL;
-    rfx_ctx *c = get_ctx(env, a[0]);
-    if (!c) return NULL;
-    rfx_motion_blur_params p;
-    if (!motion_blur_params(env, a[1], "motionBlur", &p)) return NULL;
-    int rc = rfx_motion_blur(c, &p);
-    if (rc) return throw_rfx(env, c, "rfx_motion_blur", rc);
-    return NULL;
-}
-/* motionBlurStage(ctx, uniforms): rfx_motion_blur_stage (a row tile's rows of the source into RFX_TEX_BLUR_SOURCE; arms the tiled draw) */
-static napi_value n_motion_blur_stage(napi_env env, napi_callback_info info) {
-    napi_value a[2];
-    if (!get_args(env, info, 2, a)) return NULL;
-    rfx_ctx *c = get_ctx(env, a[0]);
-    if (!c) return NULL;
-    rfx_motion_blur_params p;
-    if (!motion_blur_params(env, a[1], "motionBlurStage", &p)) return NULL;
-    int rc = rfx_motion_blur_stage(c, &p);
-    if (rc) return throw_rfx(env, c, "rfx_motion_blur_stage", rc);
-    return NULL;
-}
 /* motionBlurReachMask(ctx, uniforms, Uint32Array of frame-height entries): rfx_motion_blur_reach_mask (blocks) */
 static napi_value n_motion_blur_reach_mask(napi_env env, napi_callback_info info) {
     napi_value a[3], ab;
@@ -1067,7 +947,7 @@ static napi_value n_motion_blur_reach_mask(napi_env env, napi_callback_info info
     rfx_ctx *c = get_ctx(env, a[0]);
     if (!c) return NULL;
     rfx_motion_blur_params p;
-    if (!motion_blur_params(env, a[1], "motionBlurReachMask", &p)) return NULL;
+    if (!read_params(env, a[1], P_MOTION_BLUR, "motionBlurReachMask", &p)) return NULL;
     if (napi_get_typedarray_info(env, a[2], &type, &len, &data, &ab, &off) != napi_ok || type != napi_uint32_array) {
         napi_throw_type_error(env, NULL, "motionBlurReachMask: a Uint32Array with one entry per frame row");
         return NULL;
@@ -1084,168 +964,83 @@ static napi_value n_motion_blur_gather(napi_env env, napi_callback_info info) {
     rfx_ctx *c = get_ctx(env, a[0]);
     if (!c) return NULL;
     rfx_motion_blur_params p;
-    if (!motion_blur_params(env, a[1], "motionBlurGather", &p)) return NULL;
+    if (!read_params(env, a[1], P_MOTION_BLUR, "motionBlurGather", &p)) return NULL;
     int rc = rfx_motion_blur_gather(c, &p, NULL, &got);
     if (rc) return throw_rfx(env, c, "rfx_motion_blur_gather", rc);
     napi_create_double(env, (double)got, &out);
     return out;
 }
 
-/* the params object of the export calls: {source, format, channels, tonemap, exposure} -> rfx_export_params (include/rfx.h) */
-static void export_params(napi_env env, napi_value o, rfx_export_params *p) {
-    memset(p, 0, sizeof *p);
-    p->source = (int32_t)prop_num(env, o, "source", RFX_TEX_FINAL);
-    p->format = (int32_t)prop_num(env, o, "format", RFX_EXPORT_U8_SRGB);
-    p->channels = (int32_t)prop_num(env, o, "channels", 3);
-    p->tonemap = (int32_t)prop_num(env, o, "tonemap", 0);
-    p->exposure = (float)prop_num(env, o, "exposure", 1);
+/* ---- the export calls (rfx.h "streamed frame export", "PNG fragments", "EXR fragments", "Match form"): one descriptor per kind of payload.
+ * exportBytes / pngBound / exrBound(ctx, params) -> the bytes of a result buffer (0: bad params, or a format other than the kind's).
+ * exportFrame(ctx, params, typedArray): rfx_export (blocks) / stageExport(...) -> ticket: rfx_stage_export — the array, ideally a view of
+ * hostAlloc() memory, must stay alive until exportWait(ctx, ticket) has returned.  pngFrame / stagePng(ctx, params, filter, Uint8Array) and
+ * exrFrame / stageExr(ctx, params, Uint8Array): the same with the result buffer of "PNG fragments" / "EXR fragments".  pngFrameEx / stagePngEx(ctx,
+ * params, filter, flags, Uint8Array) and exrFrameEx / stageExrEx(ctx, params, flags, Uint8Array): the _ex entry points (flags = RFX_ENCODE_MATCHES
+ * or 0).  The library checks the byte count. */
+typedef struct {
+    int has_filter, want_u8;        /* a `filter` argument after params; the array must be a Uint8Array */
+    const char *js[2];              /* [staged]: the names in the type errors */
+    const char *c_name[4];          /* [staged + 2 * ex] */
+    size_t (*bound)(const rfx_ctx *, const rfx_export_params *);
+    int (*call)(rfx_ctx *, const rfx_export_params *, int filter, int ex, unsigned flags, void *data, size_t bytes, int *ticket);  /* ticket NULL: blocks */
+} encode_kind;
+static int export_fn(rfx_ctx *c, const rfx_export_params *p, int filter, int ex, unsigned flags, void *d, size_t n, int *t) {
+    (void)filter; (void)ex; (void)flags;
+    return t ? rfx_stage_export(c, p, d, n, t) : rfx_export(c, p, d, n);
 }
-/* exportBytes(ctx, params) -> rfx_export_bytes (0: bad params) */
-static napi_value n_export_bytes(napi_env env, napi_callback_info info) {
+static int png_fn(rfx_ctx *c, const rfx_export_params *p, int filter, int ex, unsigned flags, void *d, size_t n, int *t) {
+    if (ex) return t ? rfx_stage_png_ex(c, p, filter, flags, d, n, t) : rfx_png_ex(c, p, filter, flags, d, n);
+    return t ? rfx_stage_png(c, p, filter, d, n, t) : rfx_png(c, p, filter, d, n);
+}
+static int exr_fn_(rfx_ctx *c, const rfx_export_params *p, int filter, int ex, unsigned flags, void *d, size_t n, int *t) {
+    (void)filter;
+    if (ex) return t ? rfx_stage_exr_ex(c, p, flags, d, n, t) : rfx_exr_ex(c, p, flags, d, n);
+    return t ? rfx_stage_exr(c, p, d, n, t) : rfx_exr(c, p, d, n);
+}
+static const encode_kind ENC_EXPORT = {0, 0, {"exportFrame: TypedArray expected", "stageExport: TypedArray expected"},
+                                       {"rfx_export", "rfx_stage_export", NULL, NULL}, rfx_export_bytes, export_fn};
+static const encode_kind ENC_PNG = {1, 1, {"pngFrame: Uint8Array expected", "stagePng: Uint8Array expected"},
+                                    {"rfx_png", "rfx_stage_png", "rfx_png_ex", "rfx_stage_png_ex"}, rfx_png_bound, png_fn};
+static const encode_kind ENC_EXR = {0, 1, {"exrFrame: Uint8Array expected", "stageExr: Uint8Array expected"},
+                                    {"rfx_exr", "rfx_stage_exr", "rfx_exr_ex", "rfx_stage_exr_ex"}, rfx_exr_bound, exr_fn_};
+static napi_value bound_call(napi_env env, napi_callback_info info) {
+    const encode_kind *k = (const encode_kind *)call_data(env, info);
     napi_value a[2], out;
+    rfx_export_params p;
     if (!get_args(env, info, 2, a)) return NULL;
     rfx_ctx *c = get_ctx(env, a[0]);
-    if (!c) return NULL;
-    rfx_export_params p;
-    export_params(env, a[1], &p);
-    NAPI_CALL(env, napi_create_double(env, (double)rfx_export_bytes(c, &p), &out));
+    if (!c || !read_params(env, a[1], P_EXPORT, "", &p)) return NULL;
+    NAPI_CALL(env, napi_create_double(env, (double)k->bound(c, &p), &out));
     return out;
 }
-/* exportFrame(ctx, params, typedArray): rfx_export (blocks) / stageExport(ctx, params, typedArray) -> ticket: rfx_stage_export — the array,
- * ideally a view of hostAlloc() memory, must stay alive until exportWait(ctx, ticket) has returned.  The library checks the byte count. */
-static napi_value export_into(napi_env env, napi_callback_info info, int staged) {
-    napi_value a[3], ab, out;
+typedef struct { const encode_kind *kind; int staged, ex; } encode_fn;
+static napi_value encode_call(napi_env env, napi_callback_info info) {
+    const encode_fn *d = (const encode_fn *)call_data(env, info);
+    const encode_kind *k = d->kind;
+    napi_value a[5], ab, out;
     napi_typedarray_type type;
-    size_t len = 0, off = 0;
+    size_t len = 0, off = 0, at = 2;
     void *data = NULL;
-    if (!get_args(env, info, 3, a)) return NULL;
-    rfx_ctx *c = get_ctx(env, a[0]);
-    if (!c) return NULL;
+    int32_t filter = 0, flags = 0;
     rfx_export_params p;
-    export_params(env, a[1], &p);
+    if (!get_args(env, info, 3 + k->has_filter + d->ex, a)) return NULL;
+    rfx_ctx *c = get_ctx(env, a[0]);
+    if (!c || (k->has_filter && !get_int(env, a[at++], &filter)) || (d->ex && !get_int(env, a[at++], &flags))) return NULL;
+    if (!read_params(env, a[1], P_EXPORT, "", &p)) return NULL;
     bool is_ta = false;
-    napi_is_typedarray(env, a[2], &is_ta);
-    if (!is_ta || napi_get_typedarray_info(env, a[2], &type, &len, &data, &ab, &off) != napi_ok || !data) {
-        napi_throw_type_error(env, NULL, staged ? "stageExport: TypedArray expected" : "exportFrame: TypedArray expected");
+    napi_is_typedarray(env, a[at], &is_ta);
+    if (!is_ta || napi_get_typedarray_info(env, a[at], &type, &len, &data, &ab, &off) != napi_ok || !data || (k->want_u8 && type != napi_uint8_array)) {
+        napi_throw_type_error(env, NULL, k->js[d->staged]);
         return NULL;
     }
     static const size_t esz[] = {1, 1, 1, 2, 2, 4, 4, 4, 8, 8, 8};
     int ticket = 0;
-    int rc = staged ? rfx_stage_export(c, &p, data, len * esz[type], &ticket) : rfx_export(c, &p, data, len * esz[type]);
-    if (rc) return throw_rfx(env, c, staged ? "rfx_stage_export" : "rfx_export", rc);
-    if (!staged) return NULL;
+    int rc = k->call(c, &p, filter, d->ex, (unsigned)flags, data, len * esz[type], d->staged ? &ticket : NULL);
+    if (rc) return throw_rfx(env, c, k->c_name[d->staged + 2 * d->ex], rc);
+    if (!d->staged) return NULL;
     NAPI_CALL(env, napi_create_int32(env, ticket, &out));
     return out;
-}
-static napi_value n_export_frame(napi_env env, napi_callback_info info) { return export_into(env, info, 0); }
-static napi_value n_stage_export(napi_env env, napi_callback_info info) { return export_into(env, info, 1); }
-/* pngBound(ctx, params) -> rfx_png_bound (0: bad params or a format other than U8_SRGB) */
-static napi_value n_png_bound(napi_env env, napi_callback_info info) {
-    napi_value a[2], out;
-    if (!get_args(env, info, 2, a)) return NULL;
-    rfx_ctx *c = get_ctx(env, a[0]);
-    if (!c) return NULL;
-    rfx_export_params p;
-    export_params(env, a[1], &p);
-    NAPI_CALL(env, napi_create_double(env, (double)rfx_png_bound(c, &p), &out));
-    return out;
-}
-/* pngFrame(ctx, params, filter, Uint8Array): rfx_png (blocks) / stagePng(ctx, params, filter, Uint8Array) -> ticket: rfx_stage_png — the result
- * buffer of include/rfx.h "PNG fragments"; the array must stay alive until exportWait(ctx, ticket) has returned.  The library checks the byte count. */
-/* pngFrameEx(ctx, params, filter, flags, Uint8Array) / stagePngEx(...) -> ticket: rfx_png_ex / rfx_stage_png_ex (rfx.h "Match form": flags =
- * RFX_ENCODE_MATCHES or 0) */
-static napi_value png_into(napi_env env, napi_callback_info info, int staged, int ex) {
-    napi_value a[5], ab, out;
-    napi_typedarray_type type;
-    size_t len = 0, off = 0;
-    void *data = NULL;
-    int32_t filter = 0, flags = 0;
-    if (!get_args(env, info, ex ? 5 : 4, a)) return NULL;
-    rfx_ctx *c = get_ctx(env, a[0]);
-    if (!c || !get_int(env, a[2], &filter) || (ex && !get_int(env, a[3], &flags))) return NULL;
-    rfx_export_params p;
-    export_params(env, a[1], &p);
-    napi_value arr = a[ex ? 4 : 3];
-    bool is_ta = false;
-    napi_is_typedarray(env, arr, &is_ta);
-    if (!is_ta || napi_get_typedarray_info(env, arr, &type, &len, &data, &ab, &off) != napi_ok || !data || type != napi_uint8_array) {
-        napi_throw_type_error(env, NULL, staged ? "stagePng: Uint8Array expected" : "pngFrame: Uint8Array expected");
-        return NULL;
-    }
-    int ticket = 0, rc;
-    if (ex) {
-        rc = staged ? rfx_stage_png_ex(c, &p, filter, (unsigned)flags, data, len, &ticket) : rfx_png_ex(c, &p, filter, (unsigned)flags, data, len);
-        if (rc) return throw_rfx(env, c, staged ? "rfx_stage_png_ex" : "rfx_png_ex", rc);
-    } else {
-        rc = staged ? rfx_stage_png(c, &p, filter, data, len, &ticket) : rfx_png(c, &p, filter, data, len);
-        if (rc) return throw_rfx(env, c, staged ? "rfx_stage_png" : "rfx_png", rc);
-    }
-    if (!staged) return NULL;
-    NAPI_CALL(env, napi_create_int32(env, ticket, &out));
-    return out;
-}
-static napi_value n_png_frame(napi_env env, napi_callback_info info) { return png_into(env, info, 0, 0); }
-static napi_value n_stage_png(napi_env env, napi_callback_info info) { return png_into(env, info, 1, 0); }
-static napi_value n_png_frame_ex(napi_env env, napi_callback_info info) { return png_into(env, info, 0, 1); }
-static napi_value n_stage_png_ex(napi_env env, napi_callback_info info) { return png_into(env, info, 1, 1); }
-/* exrBound(ctx, params) -> rfx_exr_bound (0: bad params or a format other than F16) */
-static napi_value n_exr_bound(napi_env env, napi_callback_info info) {
-    napi_value a[2], out;
-    if (!get_args(env, info, 2, a)) return NULL;
-    rfx_ctx *c = get_ctx(env, a[0]);
-    if (!c) return NULL;
-    rfx_export_params p;
-    export_params(env, a[1], &p);
-    NAPI_CALL(env, napi_create_double(env, (double)rfx_exr_bound(c, &p), &out));
-    return out;
-}
-/* exrFrame(ctx, params, Uint8Array): rfx_exr (blocks) / stageExr(ctx, params, Uint8Array) -> ticket: rfx_stage_exr — the result buffer of
- * include/rfx.h "EXR fragments"; the array must stay alive until exportWait(ctx, ticket) has returned.  The library checks the byte count. */
-/* exrFrameEx(ctx, params, flags, Uint8Array) / stageExrEx(...) -> ticket: rfx_exr_ex / rfx_stage_exr_ex (rfx.h "Match form") */
-static napi_value exr_into(napi_env env, napi_callback_info info, int staged, int ex) {
-    napi_value a[4], ab, out;
-    napi_typedarray_type type;
-    size_t len = 0, off = 0;
-    void *data = NULL;
-    int32_t flags = 0;
-    if (!get_args(env, info, ex ? 4 : 3, a)) return NULL;
-    rfx_ctx *c = get_ctx(env, a[0]);
-    if (!c || (ex && !get_int(env, a[2], &flags))) return NULL;
-    rfx_export_params p;
-    export_params(env, a[1], &p);
-    napi_value arr = a[ex ? 3 : 2];
-    bool is_ta = false;
-    napi_is_typedarray(env, arr, &is_ta);
-    if (!is_ta || napi_get_typedarray_info(env, arr, &type, &len, &data, &ab, &off) != napi_ok || !data || type != napi_uint8_array) {
-        napi_throw_type_error(env, NULL, staged ? "stageExr: Uint8Array expected" : "exrFrame: Uint8Array expected");
-        return NULL;
-    }
-    int ticket = 0, rc;
-    if (ex) {
-        rc = staged ? rfx_stage_exr_ex(c, &p, (unsigned)flags, data, len, &ticket) : rfx_exr_ex(c, &p, (unsigned)flags, data, len);
-        if (rc) return throw_rfx(env, c, staged ? "rfx_stage_exr_ex" : "rfx_exr_ex", rc);
-    } else {
-        rc = staged ? rfx_stage_exr(c, &p, data, len, &ticket) : rfx_exr(c, &p, data, len);
-        if (rc) return throw_rfx(env, c, staged ? "rfx_stage_exr" : "rfx_exr", rc);
-    }
-    if (!staged) return NULL;
-    NAPI_CALL(env, napi_create_int32(env, ticket, &out));
-    return out;
-}
-static napi_value n_exr_frame(napi_env env, napi_callback_info info) { return exr_into(env, info, 0, 0); }
-static napi_value n_stage_exr(napi_env env, napi_callback_info info) { return exr_into(env, info, 1, 0); }
-static napi_value n_exr_frame_ex(napi_env env, napi_callback_info info) { return exr_into(env, info, 0, 1); }
-static napi_value n_stage_exr_ex(napi_env env, napi_callback_info info) { return exr_into(env, info, 1, 1); }
-/* exportWait(ctx, ticket): rfx_export_wait */
-static napi_value n_export_wait(napi_env env, napi_callback_info info) {
-    napi_value a[2];
-    int32_t ticket = 0;
-    if (!get_args(env, info, 2, a)) return NULL;
-    rfx_ctx *c = get_ctx(env, a[0]);
-    if (!c || !get_int(env, a[1], &ticket)) return NULL;
-    int rc = rfx_export_wait(c, ticket);
-    if (rc) return throw_rfx(env, c, "rfx_export_wait", rc);
-    return NULL;
 }
 /* constants() -> the header's values the JS side mirrors (js/Renderer.js EXPORT, PROF_KINDS): checked against each other by the tests */
 static napi_value n_constants(napi_env env, napi_callback_info info) {
@@ -1264,16 +1059,6 @@ static napi_value n_constants(napi_env env, napi_callback_info info) {
     return out;
 }
 
-static napi_value n_sync(napi_env env, napi_callback_info info) {
-    napi_value a[1];
-    if (!get_args(env, info, 1, a)) return NULL;
-    rfx_ctx *c = get_ctx(env, a[0]);
-    if (!c) return NULL;
-    int rc = rfx_sync(c);
-    if (rc) return throw_rfx(env, c, "rfx_sync", rc);
-    return NULL;
-}
-
 static napi_value n_halo_violations(napi_env env, napi_callback_info info) {
     napi_value a[1], out;
     if (!get_args(env, info, 1, a)) return NULL;
@@ -1283,16 +1068,7 @@ static napi_value n_halo_violations(napi_env env, napi_callback_info info) {
     return out;
 }
 
-/* timeBegin(ctx) / timeEnd(ctx) -> ms */
-static napi_value n_time_begin(napi_env env, napi_callback_info info) {
-    napi_value a[1];
-    if (!get_args(env, info, 1, a)) return NULL;
-    rfx_ctx *c = get_ctx(env, a[0]);
-    if (!c) return NULL;
-    int rc = rfx_time_begin(c);
-    if (rc) return throw_rfx(env, c, "rfx_time_begin", rc);
-    return NULL;
-}
+/* timeEnd(ctx) -> ms since timeBegin(ctx) */
 static napi_value n_time_end(napi_env env, napi_callback_info info) {
     napi_value a[1], out;
     if (!get_args(env, info, 1, a)) return NULL;
@@ -1305,7 +1081,8 @@ static napi_value n_time_end(napi_env env, napi_callback_info info) {
     return out;
 }
 
-/* profile(ctx, enable) / profileRead(ctx) -> { ms, launches }: arrays of RFX_PROF_COUNT_ALL entries (rfx_profile, rfx_profile_read_n) */
+/* profile(ctx, enable) / profileRead(ctx) -> { ms, launches }: arrays of RFX_PROF_COUNT_ALL entries (rfx_profile, rfx_profile_read_n).
+ * (profile is no INTS row: an `enable` that is no number throws here, where ints_call returns without a word) */
 static napi_value n_profile(napi_env env, napi_callback_info info) {
     napi_value a[2];
     if (!get_args(env, info, 2, a)) return NULL;
@@ -1341,28 +1118,60 @@ static napi_value n_profile_read(napi_env env, napi_callback_info info) {
     return out;
 }
 
+/* What the addon exports: the JS name, the callback, and for a callback that serves several names what this one selects (call_data).  DRAW,
+ * INTS, ENCODE and EXR rows are whole functions: (ctx, params object), (ctx, n integers), the export calls, the calls on an EXR frame. */
+#define DRAW(js, fn, kind) {js, params_call, &(const params_fn){js, #fn, kind, p_##fn}}
+#define INTS(js, fn, n) {js, ints_call, &(const ints_fn){#fn, n, i_##fn}}
+#define ENCODE(js, kind, staged, ex) {js, encode_call, &(const encode_fn){&kind, staged, ex}}
+#define EXR(js, form, stage) {js, exr_frame_call, &(const exr_fn){&form, stage}}
+static const struct { const char *name; napi_callback fn; const void *data; } EXPORTS[] = {
+    {"abiVersion", n_abi_version, NULL}, {"create", n_create, NULL}, {"constants", n_constants, NULL}, {"paramBytes", n_param_bytes, NULL},
+    {"heldRows", n_held_rows, NULL}, {"ssgiTargetRows", n_ssgi_target_rows, NULL},
+    {"download", xfer, &XFER[0]}, {"upload", xfer, &XFER[1]}, {"stageUpload", xfer, &XFER[2]}, {"hostAlloc", n_host_alloc, NULL},
+    INTS("stageFlip", rfx_stage_flip, 0), INTS("clear", rfx_clear, 1),
+    {"stageAov", aov_call, &AOV_STAGE}, {"aovStageBytes", aov_call, &AOV_BYTES}, {"setAovConventions", n_set_aov_conventions, NULL},
+    EXR("stageExrAov", EXR_CHUNKS, 1), EXR("exrAovStageBytes", EXR_CHUNKS, 0), EXR("stageExrBlocks", EXR_BLOCKS, 1), EXR("exrBlocksStageBytes", EXR_BLOCKS, 0),
+    EXR("stageExrBlocksPiz", EXR_PIZ, 1), EXR("exrBlocksPizStageBytes", EXR_PIZ, 0), {"exrAovStatus", n_exr_aov_status, NULL},
+    {"packGBuffer", n_pack, &PACK_GBUFFER}, {"packVelocity", n_pack, &PACK_VELOCITY},
+    {"setEnvironment", n_set_environment, NULL}, {"setEnvironmentImportance", n_set_environment_importance, NULL}, {"cubeToEquirect", n_cube_to_equirect, NULL},
+    {"setEnvironmentCube", n_set_environment_cube, NULL}, INTS("buildEnvironmentImportance", rfx_build_environment_importance, 1),
+    {"downloadEnvironmentImportance", n_download_environment_importance, NULL},
+    /* the draws: ssgiMarch in one launch, or as ssgiTrace + ssgiShade (only the second reads last frame's composed GI); copyFramebuffer(ctx, dstTex) is
+     * renderer.copyFramebufferToTexture of TemporalReprojectPass.js:198-201; finalCompose SSGIEffect's own fragment; motionBlur MotionBlurEffect's (K6) ->
+     * RFX_TEX_MOTION_BLUR; motionBlurStage a row tile's rows of the source into RFX_TEX_BLUR_SOURCE (arms the tiled draw) */
+    DRAW("ssgiMarch", rfx_ssgi_march, P_SSGI), DRAW("ssgiTrace", rfx_ssgi_trace, P_SSGI), DRAW("ssgiShade", rfx_ssgi_shade, P_SSGI),
+    DRAW("temporalReproject", rfx_temporal_reproject, P_TEMPORAL), INTS("copyFramebuffer", rfx_copy_framebuffer, 1),
+    DRAW("poissonDenoise", rfx_poisson_denoise, P_DENOISE), DRAW("compose", rfx_compose, P_COMPOSE), DRAW("finalCompose", rfx_final_compose, P_FINAL),
+    DRAW("motionBlur", rfx_motion_blur, P_MOTION_BLUR), DRAW("motionBlurStage", rfx_motion_blur_stage, P_MOTION_BLUR),
+    {"motionBlurReachMask", n_motion_blur_reach_mask, NULL}, {"motionBlurGather", n_motion_blur_gather, NULL},
+    /* setRowWindow(ctx, y0, y1): y1 <= y0 resets; setUvModel(ctx, model): 0 = RFX_UV_IDEAL, 1 = RFX_UV_REFERENCE_GL */
+    INTS("setRowWindow", rfx_set_row_window, 2), INTS("setUvModel", rfx_set_uv_model, 1), INTS("sync", rfx_sync, 0),
+    {"haloViolations", n_halo_violations, NULL}, INTS("timeBegin", rfx_time_begin, 0), {"timeEnd", n_time_end, NULL},
+    {"profile", n_profile, NULL}, {"profileRead", n_profile_read, NULL},
+    {"exportBytes", bound_call, &ENC_EXPORT}, ENCODE("exportFrame", ENC_EXPORT, 0, 0), ENCODE("stageExport", ENC_EXPORT, 1, 0), INTS("exportWait", rfx_export_wait, 1),
+    {"pngBound", bound_call, &ENC_PNG}, ENCODE("pngFrame", ENC_PNG, 0, 0), ENCODE("stagePng", ENC_PNG, 1, 0),
+    ENCODE("pngFrameEx", ENC_PNG, 0, 1), ENCODE("stagePngEx", ENC_PNG, 1, 1),
+    {"exrBound", bound_call, &ENC_EXR}, ENCODE("exrFrame", ENC_EXR, 0, 0), ENCODE("stageExr", ENC_EXR, 1, 0),
+    ENCODE("exrFrameEx", ENC_EXR, 0, 1), ENCODE("stageExrEx", ENC_EXR, 1, 1),
+    /* row-tiled runs: haloExchange(ctx, tex, upRank, downRank) — -1 = no such neighbour */
+    {"splitRows", n_split_rows, NULL}, {"commUniqueId", n_comm_unique_id, NULL}, {"commInit", n_comm_init, NULL}, INTS("haloExchange", rfx_halo_exchange, 3),
+    INTS("allgatherHistory", rfx_allgather_history, 1), {"gatherHistoryRows", n_gather_history_rows, NULL}, INTS("commWait", rfx_comm_wait, 0),
+    INTS("commDestroy", rfx_comm_destroy, 0), {"peerExport", n_peer_export, NULL}, {"peerOpen", n_peer_open, NULL},
+    {"peerGatherHistory", n_peer_gather_history, NULL}, INTS("peerClose", rfx_peer_close, 0), {"ssgiHitMask", n_ssgi_hit_mask, NULL},
+};
+
 static napi_value init(napi_env env, napi_value exports) {
-    static const struct { const char *name; napi_callback fn; } fns[] = {
-        {"abiVersion", n_abi_version}, {"create", n_create}, {"heldRows", n_held_rows}, {"ssgiTargetRows", n_ssgi_target_rows}, {"upload", n_upload}, {"download", n_download},
-        {"clear", n_clear}, {"setEnvironment", n_set_environment}, {"setEnvironmentImportance", n_set_environment_importance}, {"packGBuffer", n_pack_gbuffer}, {"packVelocity", n_pack_velocity}, {"ssgiMarch", n_ssgi}, {"ssgiTrace", n_ssgi_trace}, {"ssgiShade", n_ssgi_shade}, {"temporalReproject", n_temporal}, {"copyFramebuffer", n_copy_framebuffer}, {"poissonDenoise", n_denoise}, {"compose", n_compose}, {"finalCompose", n_final}, {"motionBlur", n_motion_blur},
-        {"motionBlurStage", n_motion_blur_stage}, {"motionBlurReachMask", n_motion_blur_reach_mask}, {"motionBlurGather", n_motion_blur_gather},
-        {"sync", n_sync}, {"setRowWindow", n_set_row_window}, {"setUvModel", n_set_uv_model}, {"cubeToEquirect", n_cube_to_equirect}, {"setEnvironmentCube", n_set_environment_cube}, {"buildEnvironmentImportance", n_build_environment_importance}, {"downloadEnvironmentImportance", n_download_environment_importance}, {"haloViolations", n_halo_violations}, {"timeBegin", n_time_begin}, {"timeEnd", n_time_end}, {"profile", n_profile}, {"profileRead", n_profile_read},
-        {"stageUpload", n_stage_upload}, {"stageFlip", n_stage_flip}, {"hostAlloc", n_host_alloc}, {"stageAov", n_stage_aov}, {"setAovConventions", n_set_aov_conventions},{"aovStageBytes", n_aov_stage_bytes},
-        {"stageExrAov", n_stage_exr_aov}, {"exrAovStageBytes", n_exr_aov_stage_bytes}, {"exrAovStatus", n_exr_aov_status},
-        {"stageExrBlocks", n_stage_exr_blocks}, {"exrBlocksStageBytes", n_exr_blocks_stage_bytes},
-        {"stageExrBlocksPiz", n_stage_exr_blocks_piz}, {"exrBlocksPizStageBytes", n_exr_blocks_piz_stage_bytes},
-        {"exportBytes", n_export_bytes}, {"exportFrame", n_export_frame}, {"stageExport", n_stage_export}, {"exportWait", n_export_wait}, {"constants", n_constants},
-        {"pngBound", n_png_bound}, {"pngFrame", n_png_frame}, {"stagePng", n_stage_png},
-        {"exrBound", n_exr_bound}, {"exrFrame", n_exr_frame}, {"stageExr", n_stage_exr},
-        {"pngFrameEx", n_png_frame_ex}, {"stagePngEx", n_stage_png_ex}, {"exrFrameEx", n_exr_frame_ex}, {"stageExrEx", n_stage_exr_ex},
-        {"splitRows", n_split_rows}, {"commUniqueId", n_comm_unique_id}, {"commInit", n_comm_init}, {"haloExchange", n_halo_exchange},
-        {"allgatherHistory", n_allgather_history}, {"gatherHistoryRows", n_gather_history_rows}, {"commWait", n_comm_wait}, {"commDestroy", n_comm_destroy},
-        {"peerExport", n_peer_export}, {"peerOpen", n_peer_open}, {"peerGatherHistory", n_peer_gather_history}, {"peerClose", n_peer_close}, {"ssgiHitMask", n_ssgi_hit_mask},
-    };
-    for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
+    const char *bad = table_that_misses_a_field();
+    if (bad) {
+        char msg[128];
+        snprintf(msg, sizeof msg, "rfx_napi: the field table of \"%s\" does not cover its struct in include/rfx.h", bad);
+        napi_throw_error(env, NULL, msg);
+        return NULL;
+    }
+    for (size_t i = 0; i < sizeof EXPORTS / sizeof EXPORTS[0]; i++) {
         napi_value f;
-        if (napi_create_function(env, fns[i].name, NAPI_AUTO_LENGTH, fns[i].fn, NULL, &f) != napi_ok) return NULL;
-        napi_set_named_property(env, exports, fns[i].name, f);
+        if (napi_create_function(env, EXPORTS[i].name, NAPI_AUTO_LENGTH, EXPORTS[i].fn, (void *)EXPORTS[i].data, &f) != napi_ok) return NULL;
+        napi_set_named_property(env, exports, EXPORTS[i].name, f);
     }
     return exports;
 }

@@ -110,7 +110,7 @@ class Context:
         a = array if array.flags["C_CONTIGUOUS"] else np.ascontiguousarray(array)
         if a.nbytes != rows * self.W * ch * np.dtype(dtype).itemsize:
             raise ValueError("texture %s: %d bytes do not cover %d rows" % (abi.TEX_NAMES[tex], a.nbytes, rows))
-        self.__dict__.setdefault("_staged_now", []).append(a)  # kept alive until the copies of this batch have executed
+        self._keep_until_flip(a)
         self._chk(self.lib.rfx_stage_upload(self._h, tex, a.ctypes.data_as(C.c_void_p), row0, rows), "rfx_stage_upload")
 
     def stage_frame(self, frame):
@@ -187,29 +187,40 @@ class Context:
         published by stage_flip().  host_alloc() planes make the copies asynchronous.  With set_aov_conventions the depth plane may be given
         as `position` (3 channels, depth_kind "position") or `view_z` (depth_kind "view_z") instead of `depth`."""
         f, row0, rows, keep = self._aov_frame(planes, row0, rows)
-        self.__dict__.setdefault("_staged_now", []).extend(keep)  # kept alive until the copies of this batch have executed
+        self._keep_until_flip(*keep)
         self._chk(self.lib.rfx_stage_aov(self._h, C.byref(f), row0, rows), "rfx_stage_aov")
 
     # -- streamed EXR frames (rfx.h "streamed EXR frames"): the file's chunks cross PCIe packed and are decoded on the device
-    def _exr_frame(self, buf, layout):
-        """-> (abi.ExrFrame, the objects it points into).  `buf`: the file's bytes (bytes, or a uint8 array — host_alloc() makes the copies
-        asynchronous); `layout`: imageio.exr_aov_layout of the same bytes."""
+    # -- EXR blocks (rfx.h "EXR blocks"): the same for tiled parts, RLE and PXR24, a moved data window
+    _EXR_FORMS = {"chunks": (abi.EXR_CHUNK_DTYPE, abi.ExrChunk, abi.ExrFrame), "blocks": (abi.EXR_BLOCK_DTYPE, abi.ExrBlock, abi.ExrBlockFrame)}
+
+    def _exr_frame(self, buf, layout, form="chunks"):
+        """-> (abi.ExrFrame — abi.ExrBlockFrame for form "blocks" —, the objects it points into).  `buf`: the file's bytes (bytes, or a uint8
+        array — host_alloc() makes the copies asynchronous); `layout`: imageio.exr_aov_layout of the same bytes, with forms="blocks" for "blocks"."""
         if (layout.width, layout.height) != (self.W, self.H):
             raise ValueError("EXR frame of %d x %d on a context of %d x %d" % (layout.width, layout.height, self.W, self.H))
         a = np.frombuffer(buf, np.uint8) if not isinstance(buf, np.ndarray) else buf
         if not a.flags["C_CONTIGUOUS"] or a.nbytes < layout.file_bytes:
             raise ValueError("EXR frame: a contiguous buffer of the file's %d bytes" % layout.file_bytes)
-        # (built per call from what the layout holds now: the part list is a few words, the chunk records are handed over as they are)
+        dtype, record, frame = self._EXR_FORMS[form]
+        # (built per call from what the layout holds now: the part list is a few words, the chunk / block records are handed over as they are)
         chans = [(abi.ExrChannel * len(ch))(*[abi.ExrChannel(pt, pl, comp) for pt, pl, comp in ch]) for _, ch in layout.parts]
         parts = (abi.ExrPart * len(layout.parts))(*[abi.ExrPart(comp, len(ch), arr) for (comp, ch), arr in zip(layout.parts, chans)])
-        chunks = np.ascontiguousarray(layout.chunks, abi.EXR_CHUNK_DTYPE)
-        c = (chans, parts, chunks)
-        f = abi.ExrFrame(a.ctypes.data, layout.file_bytes, len(parts), len(chunks), parts, chunks.ctypes.data_as(C.POINTER(abi.ExrChunk)))
-        return f, (a, c)
+        records = np.ascontiguousarray(getattr(layout, form), dtype)
+        f = frame(a.ctypes.data, layout.file_bytes, len(parts), len(records), parts, records.ctypes.data_as(C.POINTER(record)))
+        return f, (a, (chans, parts, records))
+
+    def _exr_block_frame(self, buf, layout):
+        """_exr_frame for a layout of blocks (imageio.exr_aov_layout(..., forms="blocks")): the name the descriptor of the blocks calls keeps"""
+        return self._exr_frame(buf, layout, "blocks")
 
     def _band(self, row0, rows):
         row0 = 0 if row0 is None else int(row0)
         return row0, (self.H - row0 if rows is None else int(rows))
+
+    def _keep_until_flip(self, *objects):
+        """what the staged copies of this batch read: alive until they have executed (stage_flip keeps this batch and the one before)"""
+        self.__dict__.setdefault("_staged_now", []).extend(objects)
 
     def exr_aov_stage_bytes(self, buf, layout, row0: int | None = None, rows: int | None = None) -> int:
         """rfx_exr_aov_stage_bytes: the bytes stage_exr_aov(buf, layout, row0, rows) copies host -> device (0: the library would refuse the frame)"""
@@ -220,7 +231,7 @@ class Context:
         """rfx_stage_exr_aov: stage_aov for a frame that is still an OpenEXR file — the chunks of rows [row0, row0+rows) of the FRAME (default:
         all of it) are copied as they sit in `buf` and inflated, unpredicted and scattered on the device; published by stage_flip()."""
         f, keep = self._exr_frame(buf, layout)
-        self.__dict__.setdefault("_staged_now", []).append(keep[0])  # kept alive until the copies of this batch have executed
+        self._keep_until_flip(keep[0])
         self._chk(self.lib.rfx_stage_exr_aov(self._h, C.byref(f), *self._band(row0, rows)), "rfx_stage_exr_aov")
 
     def exr_aov_status(self):
@@ -229,20 +240,6 @@ class Context:
         bad, first, code = C.c_int(), C.c_int(), C.c_int()
         self._chk(self.lib.rfx_exr_aov_status(self._h, C.byref(bad), C.byref(first), C.byref(code)), "rfx_exr_aov_status")
         return bad.value, first.value, code.value
-
-    # -- EXR blocks (rfx.h "EXR blocks"): the same for tiled parts, RLE and PXR24, a moved data window
-    def _exr_block_frame(self, buf, layout):
-        """-> (abi.ExrBlockFrame, the objects it points into); `layout`: imageio.exr_aov_layout(..., forms="blocks") of the same bytes"""
-        if (layout.width, layout.height) != (self.W, self.H):
-            raise ValueError("EXR frame of %d x %d on a context of %d x %d" % (layout.width, layout.height, self.W, self.H))
-        a = np.frombuffer(buf, np.uint8) if not isinstance(buf, np.ndarray) else buf
-        if not a.flags["C_CONTIGUOUS"] or a.nbytes < layout.file_bytes:
-            raise ValueError("EXR frame: a contiguous buffer of the file's %d bytes" % layout.file_bytes)
-        chans = [(abi.ExrChannel * len(ch))(*[abi.ExrChannel(pt, pl, comp) for pt, pl, comp in ch]) for _, ch in layout.parts]
-        parts = (abi.ExrPart * len(layout.parts))(*[abi.ExrPart(comp, len(ch), arr) for (comp, ch), arr in zip(layout.parts, chans)])
-        blocks = np.ascontiguousarray(layout.blocks, abi.EXR_BLOCK_DTYPE)
-        f = abi.ExrBlockFrame(a.ctypes.data, layout.file_bytes, len(parts), len(blocks), parts, blocks.ctypes.data_as(C.POINTER(abi.ExrBlock)))
-        return f, (a, (chans, parts, blocks))
 
     @property
     def has_exr_blocks(self) -> bool:
@@ -254,27 +251,25 @@ class Context:
         """the library exports rfx_stage_exr_blocks_piz (additive to ABI 21): PIZ parts in a layout of blocks"""
         return hasattr(self.lib, "rfx_stage_exr_blocks_piz")
 
-    @staticmethod
-    def _layout_has_piz(layout) -> bool:
-        return any(comp == abi.EXR_PIZ for comp, _ in layout.parts)
+    def _blocks_symbol(self, layout, plain: str, piz: str) -> str:
+        """`piz` for a layout with a PIZ part on a library that has the entry points, else `plain`"""
+        return piz if self.has_exr_piz and any(comp == abi.EXR_PIZ for comp, _ in layout.parts) else plain
 
     def exr_blocks_stage_bytes(self, buf, layout, row0: int | None = None, rows: int | None = None) -> int:
         """rfx_exr_blocks_stage_bytes (rfx_exr_blocks_piz_stage_bytes for a layout with a PIZ part): the bytes stage_exr_blocks(buf, layout, row0,
         rows) copies host -> device (0: the library would refuse the frame)"""
         f, _ = self._exr_block_frame(buf, layout)
-        fn = self.lib.rfx_exr_blocks_piz_stage_bytes if self._layout_has_piz(layout) and self.has_exr_piz else self.lib.rfx_exr_blocks_stage_bytes
-        return int(fn(self._h, C.byref(f), *self._band(row0, rows)))
+        name = self._blocks_symbol(layout, "rfx_exr_blocks_stage_bytes", "rfx_exr_blocks_piz_stage_bytes")
+        return int(getattr(self.lib, name)(self._h, C.byref(f), *self._band(row0, rows)))
 
     def stage_exr_blocks(self, buf, layout, row0: int | None = None, rows: int | None = None):
         """rfx_stage_exr_blocks: stage_exr_aov for a layout of blocks — scanline chunks and tiles, NONE / RLE / ZIPS / ZIP / PXR24; exr_aov_status()
         reports on the most recent call of either.  A layout with a PIZ part (imageio.exr_aov_layout(..., forms="blocks", piz=True)) goes through
         rfx_stage_exr_blocks_piz where the library has it (has_exr_piz)."""
         f, keep = self._exr_block_frame(buf, layout)
-        self.__dict__.setdefault("_staged_now", []).append(keep[0])  # kept alive until the copies of this batch have executed
-        if self._layout_has_piz(layout) and self.has_exr_piz:
-            self._chk(self.lib.rfx_stage_exr_blocks_piz(self._h, C.byref(f), *self._band(row0, rows)), "rfx_stage_exr_blocks_piz")
-        else:
-            self._chk(self.lib.rfx_stage_exr_blocks(self._h, C.byref(f), *self._band(row0, rows)), "rfx_stage_exr_blocks")
+        self._keep_until_flip(keep[0])
+        name = self._blocks_symbol(layout, "rfx_stage_exr_blocks", "rfx_stage_exr_blocks_piz")
+        self._chk(getattr(self.lib, name)(self._h, C.byref(f), *self._band(row0, rows)), name)
 
     def stage_exr_device(self, buf, names: dict | None = None, piz: bool = False, conventions=None):
         """One whole AOV EXR file held in `buf` through the device decode: the blocks form where the library has it, else the scanline form.
@@ -329,39 +324,64 @@ class Context:
     def export_bytes(self, p: abi.ExportParams) -> int:
         return int(self.lib.rfx_export_bytes(self._h, C.byref(p)))
 
-    def _export_out(self, p: abi.ExportParams, out, what):
-        n = self.export_bytes(p)
-        dtype = abi.EXPORT_DTYPE.get(p.format)
+    @staticmethod
+    def _out_buffer(what, out, n, dtype, shape):
+        """The result buffer of an encode call: a new array of `shape` and `dtype`, or the caller's `out` checked to be `n` bytes of `dtype`.
+        n == 0 (bad params): any non-empty buffer will do, the library names the fault."""
         if out is None:
-            # (bad params: any non-empty buffer will do, the library names the fault)
-            return np.empty((self.tile_rows, self.W, p.channels) if n else (1,), dtype or np.uint8), n
+            return np.empty(shape if n else (1,), dtype)
         if not isinstance(out, np.ndarray) or not out.flags["C_CONTIGUOUS"] or not out.flags["WRITEABLE"]:
             raise TypeError("%s: out must be a writeable C-contiguous ndarray" % what)
         if n and (out.dtype != dtype or out.nbytes != n):
             raise ValueError("%s: out must hold %d bytes of %s, got %d of %s" % (what, n, np.dtype(dtype), out.nbytes, out.dtype))
-        return out, n
+        return out
+
+    def _keep_until_retired(self, ticket: int, out):
+        """the copy of a staged export writes `out` until its ticket retires (export_wait), or two later tickets exist"""
+        keep = self.__dict__.setdefault("_export_keepalive", {})
+        keep[ticket] = out
+        for old in [k for k in keep if k <= ticket - 2]:
+            del keep[old]
+
+    _ENCODE_BOUND = {"export": "rfx_export_bytes", "png": "rfx_png_bound", "exr": "rfx_exr_bound"}
+
+    def _encode(self, kind: str, p: abi.ExportParams, out, staged: bool, filter=None, matches: bool = False):
+        """export / png / exr and their stage_ forms: rfx_[stage_]<kind>[_ex].  -> the result buffer, or the ticket of a staged call.
+        Only png's symbols take `filter`, only the _ex ones (matches=True: rfx.h "Match form") the flags."""
+        what = ("stage_" if staged else "") + kind
+        n = int(getattr(self.lib, self._ENCODE_BOUND[kind])(self._h, C.byref(p)))
+        if kind == "export":
+            out = self._out_buffer(what, out, n, abi.EXPORT_DTYPE.get(p.format, np.uint8), (self.tile_rows, self.W, p.channels))
+        else:
+            out = self._out_buffer(what, out, n, np.uint8, (n,))
+        if matches:
+            self._need_matches(what)
+        name = "rfx_" + what + ("_ex" if matches else "")
+        args, ticket = [self._h, C.byref(p)], C.c_int(0)
+        if kind == "png":
+            args.append(int(abi.PNG_FILTERS.get(filter, filter)))
+        if matches:
+            args.append(abi.ENCODE_MATCHES)
+        args += [out.ctypes.data_as(C.c_void_p), n]
+        if staged:
+            args.append(C.byref(ticket))
+        self._chk(getattr(self.lib, name)(*args), name)
+        if not staged:
+            return out
+        self._keep_until_retired(ticket.value, out)
+        return int(ticket.value)
 
     def export(self, source: int, format, channels: int = 3, tonemap="linear", exposure: float = 1.0, out=None) -> np.ndarray:
         """rfx_export: the context's tile rows of `source`, encoded on the device -> (rows, W, channels) uint8 / float16 / float32, row 0 =
         bottom (the order download() uses).  Blocks until the bytes are there."""
         p = self.export_params(source, format, channels, tonemap, exposure)
-        out, n = self._export_out(p, out, "export")
-        self._chk(self.lib.rfx_export(self._h, C.byref(p), out.ctypes.data_as(C.c_void_p), n), "rfx_export")
-        return out.reshape(self.tile_rows, self.W, p.channels)
+        return self._encode("export", p, out, False).reshape(self.tile_rows, self.W, p.channels)
 
     def stage_export(self, source: int, format, channels: int = 3, tonemap="linear", exposure: float = 1.0, *, out: np.ndarray) -> int:
         """rfx_stage_export: enqueue the encode (after every draw enqueued so far) and the copy into `out` — a host_alloc() array for an
         asynchronous copy — and return the ticket.  `out` is complete once export_wait(ticket) has returned; the call itself returns only when
         the export two tickets earlier has completed (alternate two buffers)."""
-        p = self.export_params(source, format, channels, tonemap, exposure)
-        out, n = self._export_out(p, out, "stage_export")
-        t = C.c_int(0)
-        self._chk(self.lib.rfx_stage_export(self._h, C.byref(p), out.ctypes.data_as(C.c_void_p), n, C.byref(t)), "rfx_stage_export")
-        keep = self.__dict__.setdefault("_export_keepalive", {})  # the copy writes `out` until its ticket retires
-        keep[t.value] = out
-        for old in [k for k in keep if k <= t.value - 2]:
-            del keep[old]
-        return int(t.value)
+        return self._encode("export", self.export_params(source, format, channels, tonemap, exposure), out, True)
 
     def export_wait(self, ticket: int):
         self._chk(self.lib.rfx_export_wait(self._h, int(ticket)), "rfx_export_wait")
@@ -382,92 +402,32 @@ class Context:
         """rfx_png_bound: the bytes of a result buffer (32-byte header + the fragment at its largest)"""
         return int(self.lib.rfx_png_bound(self._h, C.byref(self.export_params(abi.TEX_FINAL, "u8_srgb", channels))))
 
-    def _png_out(self, p: abi.ExportParams, out, what):
-        n = int(self.lib.rfx_png_bound(self._h, C.byref(p)))
-        if out is None:
-            return np.empty(max(n, 1), np.uint8), n  # (bad params: any non-empty buffer will do, the library names the fault)
-        if not isinstance(out, np.ndarray) or not out.flags["C_CONTIGUOUS"] or not out.flags["WRITEABLE"]:
-            raise TypeError("%s: out must be a writeable C-contiguous ndarray" % what)
-        if n and (out.dtype != np.uint8 or out.nbytes != n):
-            raise ValueError("%s: out must hold %d bytes of uint8, got %d of %s" % (what, n, out.nbytes, out.dtype))
-        return out, n
-
     def png(self, source: int, channels: int = 3, tonemap="linear", exposure: float = 1.0, filter=0, out=None, matches: bool = False) -> np.ndarray:
         """rfx_png: the tile rows of `source` as a PNG fragment -> the result buffer (png_bound() bytes of uint8: header, fragment, slack);
         imageio.png_from_fragments wraps one or more of them into a file.  `filter`: "adaptive" / "none" / "sub" / "up" / "paeth" or 0..4.
         matches=True: rfx_png_ex with RFX_ENCODE_MATCHES (rfx.h "Match form").  Blocks until the bytes are there."""
-        p = self.export_params(source, "u8_srgb", channels, tonemap, exposure)
-        out, n = self._png_out(p, out, "png")
-        if matches:
-            self._need_matches("png")
-            self._chk(self.lib.rfx_png_ex(self._h, C.byref(p), int(abi.PNG_FILTERS.get(filter, filter)), abi.ENCODE_MATCHES, out.ctypes.data_as(C.c_void_p), n),
-                      "rfx_png_ex")
-            return out
-        self._chk(self.lib.rfx_png(self._h, C.byref(p), int(abi.PNG_FILTERS.get(filter, filter)), out.ctypes.data_as(C.c_void_p), n), "rfx_png")
-        return out
+        return self._encode("png", self.export_params(source, "u8_srgb", channels, tonemap, exposure), out, False, filter, matches)
 
     def stage_png(self, source: int, channels: int = 3, tonemap="linear", exposure: float = 1.0, filter=0, *, out: np.ndarray, matches: bool = False) -> int:
         """rfx_stage_png: stage_export's contract with a PNG fragment as the payload; the ticket is one of the same sequence and
         export_wait(ticket) retires it.  matches=True: rfx_stage_png_ex with RFX_ENCODE_MATCHES."""
-        p = self.export_params(source, "u8_srgb", channels, tonemap, exposure)
-        out, n = self._png_out(p, out, "stage_png")
-        t = C.c_int(0)
-        f = int(abi.PNG_FILTERS.get(filter, filter))
-        if matches:
-            self._need_matches("stage_png")
-            self._chk(self.lib.rfx_stage_png_ex(self._h, C.byref(p), f, abi.ENCODE_MATCHES, out.ctypes.data_as(C.c_void_p), n, C.byref(t)), "rfx_stage_png_ex")
-        else:
-            self._chk(self.lib.rfx_stage_png(self._h, C.byref(p), f, out.ctypes.data_as(C.c_void_p), n, C.byref(t)), "rfx_stage_png")
-        keep = self.__dict__.setdefault("_export_keepalive", {})
-        keep[t.value] = out
-        for old in [k for k in keep if k <= t.value - 2]:
-            del keep[old]
-        return int(t.value)
+        return self._encode("png", self.export_params(source, "u8_srgb", channels, tonemap, exposure), out, True, filter, matches)
 
     # -- EXR fragments (rfx.h "EXR fragments"): the F16 export, encoded on the device as the ZIPS chunks of the tile rows
     def exr_bound(self, channels: int = 4) -> int:
         """rfx_exr_bound: the bytes of a result buffer (32-byte header + the fragment at its largest)"""
         return int(self.lib.rfx_exr_bound(self._h, C.byref(self.export_params(abi.TEX_FINAL, "f16", channels))))
 
-    def _exr_out(self, p: abi.ExportParams, out, what):
-        n = int(self.lib.rfx_exr_bound(self._h, C.byref(p)))
-        if out is None:
-            return np.empty(max(n, 1), np.uint8), n  # (bad params: any non-empty buffer will do, the library names the fault)
-        if not isinstance(out, np.ndarray) or not out.flags["C_CONTIGUOUS"] or not out.flags["WRITEABLE"]:
-            raise TypeError("%s: out must be a writeable C-contiguous ndarray" % what)
-        if n and (out.dtype != np.uint8 or out.nbytes != n):
-            raise ValueError("%s: out must hold %d bytes of uint8, got %d of %s" % (what, n, out.nbytes, out.dtype))
-        return out, n
-
     def exr(self, source: int, channels: int = 4, out=None, matches: bool = False) -> np.ndarray:
         """rfx_exr: the tile rows of `source` as an EXR fragment -> the result buffer (exr_bound() bytes of uint8: header, fragment, slack);
         imageio.exr_from_fragments wraps one or more of them into a file.  matches=True: rfx_exr_ex with RFX_ENCODE_MATCHES (rfx.h "Match form").
         Blocks until the bytes are there."""
-        p = self.export_params(source, "f16", channels)
-        out, n = self._exr_out(p, out, "exr")
-        if matches:
-            self._need_matches("exr")
-            self._chk(self.lib.rfx_exr_ex(self._h, C.byref(p), abi.ENCODE_MATCHES, out.ctypes.data_as(C.c_void_p), n), "rfx_exr_ex")
-            return out
-        self._chk(self.lib.rfx_exr(self._h, C.byref(p), out.ctypes.data_as(C.c_void_p), n), "rfx_exr")
-        return out
+        return self._encode("exr", self.export_params(source, "f16", channels), out, False, matches=matches)
 
     def stage_exr(self, source: int, channels: int = 4, *, out: np.ndarray, matches: bool = False) -> int:
         """rfx_stage_exr: stage_export's contract with an EXR fragment as the payload; the ticket is one of the same sequence and
         export_wait(ticket) retires it.  matches=True: rfx_stage_exr_ex with RFX_ENCODE_MATCHES."""
-        p = self.export_params(source, "f16", channels)
-        out, n = self._exr_out(p, out, "stage_exr")
-        t = C.c_int(0)
-        if matches:
-            self._need_matches("stage_exr")
-            self._chk(self.lib.rfx_stage_exr_ex(self._h, C.byref(p), abi.ENCODE_MATCHES, out.ctypes.data_as(C.c_void_p), n, C.byref(t)), "rfx_stage_exr_ex")
-        else:
-            self._chk(self.lib.rfx_stage_exr(self._h, C.byref(p), out.ctypes.data_as(C.c_void_p), n, C.byref(t)), "rfx_stage_exr")
-        keep = self.__dict__.setdefault("_export_keepalive", {})
-        keep[t.value] = out
-        for old in [k for k in keep if k <= t.value - 2]:
-            del keep[old]
-        return int(t.value)
+        return self._encode("exr", self.export_params(source, "f16", channels), out, True, matches=matches)
 
     def clear(self, tex: int):
         self._chk(self.lib.rfx_clear(self._h, tex), "rfx_clear")
