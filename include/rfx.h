@@ -684,6 +684,42 @@ typedef struct rfx_aov_conventions {
 } rfx_aov_conventions;
 int rfx_set_aov_conventions(rfx_ctx *, const rfx_aov_conventions *);   /* NULL: back to the default */
 
+/* ---- device planes (additive to ABI 21: a host checks for the symbol): rfx_stage_aov for planes that already live in device memory.
+ * A renderer on the same device (a HIP path tracer, a torch rasteriser) hands over the buffers it wrote, laid out as IT lays them out; the pack
+ * kernel reads them where they are.  Nothing crosses PCIe, the staging area is not touched, and the LIBRARY allocates, frees and
+ * host-synchronises nothing per call — the caller, though, has to make the planes complete first (ORDERING below: in this version that is a
+ * synchronise of the producer's stream in the caller's frame loop).  In everything but where the bytes
+ * come from the call IS rfx_stage_aov: the same slots under the same rules (DEPTH always; GBUFFER, VELOCITY, DIRECT_LIGHT where their planes are
+ * given), the same back buffers published by rfx_stage_flip, the same row rule (DEPTH takes the whole band, the other slots band ∩ the rows they
+ * hold), rfx_set_aov_conventions read the same way (POSITION: the depth plane has 3 channels; CAMERAS: no velocity plane), and it mixes within
+ * one batch with rfx_stage_upload, rfx_stage_aov and the EXR calls.  The texels are, bit for bit, those rfx_stage_aov writes for the same
+ * element values.
+ * A PLANE is addressed by strides, in ELEMENTS (float32 or IEEE half, by `type`), of any sign, 0 allowed (a broadcast): the element of frame
+ * column x, frame row y of the band and channel ch is data[x stride_x + (y - row0) stride_y + ch stride_c].  Row 0 is the frame's BOTTOM row and
+ * stride_y steps to the row above: an image kept top-down has a negative stride_y and `data` at its last image row.  stride_c is not read for a
+ * 1-channel plane.  data == NULL: the plane is not given.  Three layouts are read with vector loads, when `data` is aligned to four elements and
+ * stride_y (and stride_c, planar) are multiples of four: INTERLEAVED (stride_c 1, stride_x = channels; any row pitch), PLANAR (stride_x 1; any
+ * plane and row pitch); everything else — a mirrored or broadcast axis, a base or a pitch off that alignment — is read element by element.
+ * When every plane a segment of the band reads is tight (interleaved, stride_y = width x channels) and 16-byte aligned, that segment is
+ * packed by rfx_stage_aov's own kernel on the caller's pointers.
+ * ORDERING.  producer_stream must be NULL in this version (anything else: RFX_EUNSUPPORTED; the parameter is where a hipStream_t the call
+ * orders itself against will go): the planes are complete when the call is made — the producer's stream has been synchronised, or the upload
+ * stream was made to wait by the caller's own means — and stay unchanged until the flip after the one that publishes them has returned
+ * (rfx_stage_aov's rule).
+ * Planes that overlap the context's own buffers (rfx_tex_device_ptr, a back buffer) are undefined.  The library does not ask the runtime what
+ * kind of memory `data` is: an address the device cannot read faults there.
+ * RFX_EINVAL: everything rfx_stage_aov refuses; a `data` not aligned to its element size; a plane whose extent — the sum over the three axes of
+ * |stride| (count - 1), plus one, elements over the band — does not fit in 2^62 - 1 bytes.  RFX_ESTATE: a slot to be written is bound to an external
+ * buffer.  Every check runs before anything is enqueued: a refused call leaves the batch as it was. */
+typedef struct rfx_device_plane {
+    const void *data;     /* device address of element (x = 0, frame row row0, channel 0); NULL: plane not given */
+    int32_t type;         /* RFX_PLANE_F32 / RFX_PLANE_F16 */
+    int32_t channels;     /* as rfx_plane */
+    int64_t stride_x, stride_y, stride_c;  /* in ELEMENTS, any sign, 0 allowed (broadcast); stride_y steps to frame row + 1 (row 0 = bottom) */
+} rfx_device_plane;
+typedef struct rfx_aov_device_frame { rfx_device_plane diffuse, normal, roughness, metalness, emissive, velocity, depth, direct; } rfx_aov_device_frame;
+int rfx_stage_aov_device(rfx_ctx *, const rfx_aov_device_frame *, int row0, int rows, void *producer_stream);
+
 /* ---- streamed EXR frames (additive to ABI 21: a host checks for the symbol): rfx_stage_aov for an AOV frame that is still a compressed OpenEXR
  * file.  The scanline chunks cross PCIe as they sit in the file, on the upload stream; K9 (csrc/k9_exr_import.hip) inflates them — one wave per
  * chunk, any RFC 1950 stream: stored, fixed and dynamic blocks, the Adler-32 checked —, undoes the predictor and the byte split, and scatters the

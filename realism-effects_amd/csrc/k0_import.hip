@@ -349,6 +349,161 @@ __global__ __launch_bounds__(RFX_K0_AOV_BLOCK) void k0_aov_pack(typename K0AovBl
     }
 }
 
+// ---------------------------------------------------------------- K0 AOV pack over device planes, for rfx_stage_aov_device (include/rfx.h "device planes")
+// k0_aov_pack's work on planes that lie where their producer left them: the element of column x, segment row y, channel ch of a plane sits
+// sx x + sy y + sc ch elements from its base, strides of any sign or 0.  Rows have pitch, so the decomposition is two-dimensional: a workgroup is
+// RFX_K0_DEV_BX lanes along a row by RFX_K0_DEV_BY rows, lane l < groups_x of a row owns its pixels [4 l, 4 l + 4), lane groups_x the W mod 4
+// pixels from tail_x on, element by element; no group straddles rows and the frame's (x, y) are at hand for the conventions (no k0_conv_xy).
+// Each plane's layout class is uniform over the launch (rfx_launch.h rfx_aov_device_plan_for decides it, with the alignment it needs) and
+// branched on per wave, as SET 2 does with half_mask:
+//   INTERLEAVED  the lane's 4 C elements are one run: C 16-byte loads (halves: C 8-byte loads), lane to lane 16 C bytes on — k0_aov_load4's access;
+//   PLANAR       per channel the lane's four elements are one run: one 16-byte (8-byte) load, lane to lane 16 (8) bytes on — a wave reads
+//                1 KiB (512 B) of consecutive bytes per instruction;
+//   ELEMENT      one element per load.
+// The slots leave as in k0_aov_pack: four 16-byte stores per lane and slot, the four depth values.  The arithmetic is the same device functions
+// on the same widened values: the texels are k0_aov_pack's bit for bit.
+RFX_DEV float k0s_elem(const K0AovStridedPlane &p, bool half, long long i) {
+    return half ? rfx_h2f(((const unsigned short *)p.base)[i]) : ((const float *)p.base)[i];
+}
+// N pixels from column x0 of row y, pixel-major: v[C k + ch].  N 4: by the plane's layout; N 1 (the tail): the element form
+template <int C, int N>
+RFX_DEV void k0s_load(const K0AovStridedPlane &p, int layout, bool half, int x0, int y, float *v) {
+    const long long row = (long long)y * p.sy;
+    if (N == 4 && layout == RFX_AOV_LAYOUT_INTERLEAVED) {
+        const long long at = row + (long long)x0 * C;
+        if (!half) {
+            const uint4 *q = (const uint4 *)((const float *)p.base + at);
+#pragma unroll
+            for (int i = 0; i < C; i++) {
+                const uint4 w = q[i];
+                v[4 * i] = __uint_as_float(w.x); v[4 * i + 1] = __uint_as_float(w.y); v[4 * i + 2] = __uint_as_float(w.z); v[4 * i + 3] = __uint_as_float(w.w);
+            }
+        } else {
+            const uint2 *q = (const uint2 *)((const unsigned short *)p.base + at);
+#pragma unroll
+            for (int i = 0; i < C; i++) {
+                const uint2 w = q[i];
+                k0_aov_widen2(w.x, v + 4 * i); k0_aov_widen2(w.y, v + 4 * i + 2);
+            }
+        }
+    } else if (N == 4 && layout == RFX_AOV_LAYOUT_PLANAR) {
+#pragma unroll
+        for (int ch = 0; ch < C; ch++) {
+            const long long at = row + (long long)ch * p.sc + x0;
+            float f[4];
+            if (!half) {
+                const uint4 w = *(const uint4 *)((const float *)p.base + at);
+                f[0] = __uint_as_float(w.x); f[1] = __uint_as_float(w.y); f[2] = __uint_as_float(w.z); f[3] = __uint_as_float(w.w);
+            } else {
+                const uint2 w = *(const uint2 *)((const unsigned short *)p.base + at);
+                k0_aov_widen2(w.x, f); k0_aov_widen2(w.y, f + 2);
+            }
+#pragma unroll
+            for (int k = 0; k < 4; k++) v[C * k + ch] = f[k];
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < N; k++)
+#pragma unroll
+            for (int ch = 0; ch < C; ch++) v[C * k + ch] = k0s_elem(p, half, row + (long long)(x0 + k) * p.sx + (long long)ch * p.sc);
+    }
+}
+// ... of an rgb(a) plane: always four channels out, alpha 1 where the plane has three
+template <int N>
+RFX_DEV void k0s_load_rgba(const K0AovStridedPlane &p, int layout, bool half, int channels, int x0, int y, float *v) {
+    if (channels == 4) {
+        k0s_load<4, N>(p, layout, half, x0, y, v);
+    } else {
+        float c[3 * N];
+        k0s_load<3, N>(p, layout, half, x0, y, c);
+#pragma unroll
+        for (int k = 0; k < N; k++) { v[4 * k] = c[3 * k]; v[4 * k + 1] = c[3 * k + 1]; v[4 * k + 2] = c[3 * k + 2]; v[4 * k + 3] = 1.0f; }
+    }
+}
+// the N pixels from column x0 of segment row y
+template <bool CONV, int N, class Block>
+RFX_DEV void k0s_pixels(const Block &A, int x0, int y) {
+    const auto lay = [&](int i) { return (int)((A.layouts >> (2 * i)) & 3u); };
+    const auto half = [&](int i) { return ((A.half_mask >> i) & 1u) != 0u; };
+    const size_t first = (size_t)y * (size_t)A.W + (size_t)x0;
+    float d[N], cv[2 * N];
+    if constexpr (CONV) {
+        const K0AovConv &v = A.v;
+        const bool want = A.velocity != nullptr;
+        float dp[3 * N];
+        if (v.depth_kind == RFX_AOV_DEPTH_POSITION) {
+            k0s_load<3, N>(A.plane[RFX_AOV_DEPTH], lay(RFX_AOV_DEPTH), half(RFX_AOV_DEPTH), x0, y, dp);
+        } else {
+            float z[N];
+            k0s_load<1, N>(A.plane[RFX_AOV_DEPTH], lay(RFX_AOV_DEPTH), half(RFX_AOV_DEPTH), x0, y, z);
+#pragma unroll
+            for (int k = 0; k < N; k++) { dp[3 * k] = z[k]; dp[3 * k + 1] = 0.0f; dp[3 * k + 2] = 0.0f; }
+        }
+#pragma unroll
+        for (int k = 0; k < 2 * N; k++) cv[k] = 0.0f;
+        if (want && v.velocity_kind != RFX_AOV_VELOCITY_CAMERAS)
+            k0s_load<2, N>(A.plane[RFX_AOV_VELOCITY], lay(RFX_AOV_VELOCITY), half(RFX_AOV_VELOCITY), x0, y, cv);
+#pragma unroll
+        for (int k = 0; k < N; k++) d[k] = k0_conv_pixel(v, dp + 3 * k, x0 + k, v.row0 + y, want, cv + 2 * k);
+    } else k0s_load<1, N>(A.plane[RFX_AOV_DEPTH], lay(RFX_AOV_DEPTH), half(RFX_AOV_DEPTH), x0, y, d);
+    float *od = A.depth + first;
+#pragma unroll
+    for (int k = 0; k < N; k++) od[k] = d[k];
+    uint32_t nrm[N];
+#pragma unroll
+    for (int k = 0; k < N; k++) nrm[k] = 0u;
+    if (A.gbuffer || A.velocity) {
+        float n[3 * N];
+        k0s_load<3, N>(A.plane[RFX_AOV_NORMAL], lay(RFX_AOV_NORMAL), half(RFX_AOV_NORMAL), x0, y, n);
+#pragma unroll
+        for (int k = 0; k < N; k++) {
+            if constexpr (CONV) nrm[k] = k0_pack_normal(k0_conv_normal(A.v, make_float3(n[3 * k], n[3 * k + 1], n[3 * k + 2])));
+            else nrm[k] = k0_pack_normal(make_float3(n[3 * k], n[3 * k + 1], n[3 * k + 2]));
+        }
+    }
+    if (A.gbuffer) {
+        float c[4 * N], r[N], m[N], e[3 * N];
+        k0s_load_rgba<N>(A.plane[RFX_AOV_DIFFUSE], lay(RFX_AOV_DIFFUSE), half(RFX_AOV_DIFFUSE), A.diffuse_ch, x0, y, c);
+        k0s_load<1, N>(A.plane[RFX_AOV_ROUGHNESS], lay(RFX_AOV_ROUGHNESS), half(RFX_AOV_ROUGHNESS), x0, y, r);
+        k0s_load<1, N>(A.plane[RFX_AOV_METALNESS], lay(RFX_AOV_METALNESS), half(RFX_AOV_METALNESS), x0, y, m);
+        k0s_load<3, N>(A.plane[RFX_AOV_EMISSIVE], lay(RFX_AOV_EMISSIVE), half(RFX_AOV_EMISSIVE), x0, y, e);
+        uint4 *o = A.gbuffer + first;
+#pragma unroll
+        for (int k = 0; k < N; k++) o[k] = k0_aov_gbuffer_texel(d[k], c + 4 * k, nrm[k], r[k], m[k], e + 3 * k);
+    }
+    if (A.velocity) {
+        float v[2 * N];
+        if constexpr (CONV) {
+#pragma unroll
+            for (int k = 0; k < 2 * N; k++) v[k] = cv[k];
+        } else k0s_load<2, N>(A.plane[RFX_AOV_VELOCITY], lay(RFX_AOV_VELOCITY), half(RFX_AOV_VELOCITY), x0, y, v);
+        uint4 *o = A.velocity + first;
+#pragma unroll
+        for (int k = 0; k < N; k++) o[k] = k0_aov_velocity_texel(d[k], v[2 * k], v[2 * k + 1], nrm[k]);
+    }
+    if (A.direct) {
+        float q[4 * N];
+        k0s_load_rgba<N>(A.plane[RFX_AOV_DIRECT], lay(RFX_AOV_DIRECT), half(RFX_AOV_DIRECT), A.direct_ch, x0, y, q);
+        uint4 *o = A.direct + first;
+#pragma unroll
+        for (int k = 0; k < N; k++) o[k] = make_uint4(__float_as_uint(q[4 * k]), __float_as_uint(q[4 * k + 1]), __float_as_uint(q[4 * k + 2]), __float_as_uint(q[4 * k + 3]));
+    }
+}
+template <bool CONV>
+struct K0AovStridedBlock { typedef K0AovStridedArgs type; };
+template <>
+struct K0AovStridedBlock<true> { typedef K0AovStridedConvArgs type; };
+template <bool CONV>
+__global__ __launch_bounds__(RFX_K0_DEV_BX * RFX_K0_DEV_BY) void k0_aov_pack_strided(typename K0AovStridedBlock<CONV>::type A) {
+    const int lane = blockIdx.x * RFX_K0_DEV_BX + threadIdx.x, y = blockIdx.y * RFX_K0_DEV_BY + threadIdx.y;
+    if (lane >= A.lanes_x || y >= A.rows) return;
+    if (lane < A.groups_x) {
+        k0s_pixels<CONV, 4>(A, 4 * lane, y);
+    } else {
+        for (int k = 0; k < A.tail_pixels; k++) k0s_pixels<CONV, 1>(A, A.tail_x + k, y);
+    }
+}
+
 }  // namespace
 
 hipError_t rfx_launch_pack_gbuffer(int W, int rows, const float *diffuse, const float *normal, const float *roughness, const float *metalness,
@@ -380,6 +535,21 @@ hipError_t rfx_launch_k0_aov(const K0AovArgs &A, int blocks, hipStream_t stream,
         B.v = *conv;
         k0_aov_launch<true>(set, B, blocks, stream);
     } else k0_aov_launch<false>(set, A, blocks, stream);
+    return hipGetLastError();
+}
+hipError_t rfx_launch_k0_aov_strided(const K0AovStridedArgs &A, int grid_x, int grid_y, hipStream_t stream, const K0AovConv *conv) {
+    if (!A.plane[RFX_AOV_DEPTH].base || !A.depth || grid_x <= 0 || grid_y <= 0 || A.W <= 0 || A.rows <= 0) return hipErrorInvalidValue;
+    if (A.groups_x != A.W / 4 || A.tail_x != 4 * A.groups_x || A.tail_pixels != A.W - A.tail_x || A.lanes_x != A.groups_x + (A.tail_pixels ? 1 : 0))
+        return hipErrorInvalidValue;
+    const dim3 grid(grid_x, grid_y), block(RFX_K0_DEV_BX, RFX_K0_DEV_BY);
+    if (conv) {
+        if (conv->W <= 0 || conv->H <= 0) return hipErrorInvalidValue;
+        if (A.velocity && conv->velocity_kind != RFX_AOV_VELOCITY_CAMERAS && !A.plane[RFX_AOV_VELOCITY].base) return hipErrorInvalidValue;
+        K0AovStridedConvArgs B;
+        static_cast<K0AovStridedArgs &>(B) = A;
+        B.v = *conv;
+        hipLaunchKernelGGL((k0_aov_pack_strided<true>), grid, block, 0, stream, B);
+    } else hipLaunchKernelGGL((k0_aov_pack_strided<false>), grid, block, 0, stream, A);
     return hipGetLastError();
 }
 hipError_t rfx_launch_pack_velocity(int W, int rows, const float *velocity, const float *normal, const float *depth, void *out, hipStream_t stream) {

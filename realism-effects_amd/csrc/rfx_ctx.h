@@ -156,6 +156,10 @@ extern "C" int rfx_internal_aov_plan(int W, int H, int held_row0, int held_rows,
 // ... with the kinds of include/rfx.h "AOV conventions" (rfx_launch.h rfx_aov_plan_conv_for)
 extern "C" int rfx_internal_aov_plan_conv(int W, int H, int held_row0, int held_rows, const int *type, const int *channels, int row0, int rows, int depth_kind,
                                           int velocity_kind, struct rfx_aov_plan *out);
+// (addr, stride_*: eight entries each — rfx_launch.h rfx_aov_device_plan_for)
+extern "C" int rfx_internal_aov_device_plan(int W, int H, int held_row0, int held_rows, const int *type, const int *channels, const unsigned long long *addr,
+                                            const long long *stride_x, const long long *stride_y, const long long *stride_c, int row0, int rows, int depth_kind,
+                                            int velocity_kind, struct rfx_aov_device_plan *out);
 extern "C" int rfx_internal_exr_piz_tables(int piz_blocks, struct rfx_exr_piz_tables *out);
 extern "C" int rfx_internal_k3_tile(int W, int H, float radius, int inputIsTemporal, int textureCount, struct rfx_k3_tile_plan *out);
 

@@ -217,6 +217,12 @@ int rfx_internal_aov_plan_conv(int W, int H, int held_row0, int held_rows, const
                                struct rfx_aov_plan *out) {
     return rfx_aov_plan_conv_for(W, H, held_row0, held_rows, type, channels, row0, rows, depth_kind, velocity_kind, out) ? RFX_EINVAL : RFX_OK;
 }
+int rfx_internal_aov_device_plan(int W, int H, int held_row0, int held_rows, const int *type, const int *channels, const unsigned long long *addr,
+                                 const long long *stride_x, const long long *stride_y, const long long *stride_c, int row0, int rows, int depth_kind, int velocity_kind,
+                                 struct rfx_aov_device_plan *out) {
+    return rfx_aov_device_plan_for(W, H, held_row0, held_rows, type, channels, addr, stride_x, stride_y, stride_c, row0, rows, depth_kind, velocity_kind, out) ? RFX_EINVAL
+                                                                                                                                                                : RFX_OK;
+}
 int rfx_internal_exr_piz_tables(int piz_blocks, struct rfx_exr_piz_tables *out) { return out && rfx_exr_piz_tables_for(piz_blocks, out) ? 0 : -1; }
 int rfx_internal_k3_tile(int W, int H, float radius, int inputIsTemporal, int textureCount, struct rfx_k3_tile_plan *out) {
     *out = rfx_k3_tile((float)W, (float)H, radius, inputIsTemporal != 0, textureCount);

@@ -34,6 +34,23 @@ struct K0AovConv {
 struct K0AovConvArgs : K0AovArgs { K0AovConv v; };
 // conv null: the default kernels, on K0AovArgs alone
 hipError_t rfx_launch_k0_aov(const K0AovArgs &, int blocks, hipStream_t, const K0AovConv *conv = nullptr);
+// K0 AOV pack over device planes (k0_import.hip k0_aov_pack_strided): one segment of rfx_stage_aov_device that k0_aov_pack cannot serve
+// (rfx_launch.h rfx_aov_device_plan_for) — the producer's planes, addressed by element strides, -> the segment's first texel of every slot it
+// writes (row pitch W).  `base`: the element of column 0, the segment's first row, channel 0.
+struct K0AovStridedPlane { const void *base; long long sx, sy, sc; };
+struct K0AovStridedArgs {
+    K0AovStridedPlane plane[8];  // base null: not read
+    unsigned int half_mask;      // bit i: plane i holds IEEE halves
+    unsigned int layouts;        // bits [2 i, 2 i + 2): plane i's RFX_AOV_LAYOUT_*
+    int diffuse_ch, direct_ch;   // 3 or 4
+    uint4 *gbuffer, *velocity, *direct;
+    float *depth;
+    int W, rows;                 // the segment: `rows` rows of W texels
+    int groups_x, tail_x, tail_pixels, lanes_x;  // per row: lanes [0, groups_x) own four pixels each, lane groups_x the tail; lanes_x of them
+};
+struct K0AovStridedConvArgs : K0AovStridedArgs { K0AovConv v; };
+// grid_x x grid_y workgroups of RFX_K0_DEV_BX x RFX_K0_DEV_BY lanes; conv null: the default kernel, on K0AovStridedArgs alone
+hipError_t rfx_launch_k0_aov_strided(const K0AovStridedArgs &, int grid_x, int grid_y, hipStream_t, const K0AovConv *conv = nullptr);
 // CubeToEquirectEnvPass (k0_cube.hip): six S x S RGBA32F faces -> a W x H RGBA32F equirectangular image
 hipError_t rfx_launch_cube_to_equirect(float4 *chain, int size, int levels, float4 *out, int W, int H, const UvPlanes &uv, hipStream_t);
 

@@ -1,7 +1,7 @@
 // rfx_launch.h — what a launch decides on the host before it launches: K1's table layout, a scaled tile's target rows, K3's tile geometry, the
 // "whole frame" test, the step from a run-time option to a template argument, and what is remembered per kernel and device.  Host code
 // (rfx_device.h comes in for UvPlanes and the two vUv expressions the kernels and the row plan share).  The plans are pure functions of their
-// arguments (no HIP call, no context): rfx_draw.hip exports them as rfx_internal_k1_table / rfx_internal_k3_tile / rfx_internal_scaled_rows / rfx_internal_export_plan / rfx_internal_aov_plan / rfx_internal_exr_piz_tables and
+// arguments (no HIP call, no context): rfx_draw.hip exports them as rfx_internal_k1_table / rfx_internal_k3_tile / rfx_internal_scaled_rows / rfx_internal_export_plan / rfx_internal_aov_plan / rfx_internal_aov_device_plan / rfx_internal_exr_piz_tables and
 // the CPU tests call them as built (tests/test_k1_table_layout.py, tests/test_k3_tile_geometry.py, tests/test_resolution_scale_rows_cpu.py).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -306,6 +306,81 @@ inline const char *rfx_aov_plan_conv_for(int W, int H, int held_row0, int held_r
 }
 inline const char *rfx_aov_plan_for(int W, int H, int held_row0, int held_rows, const int *type, const int *channels, int row0, int rows, rfx_aov_plan *out) {
     return rfx_aov_plan_conv_for(W, H, held_row0, held_rows, type, channels, row0, rows, RFX_AOV_DEPTH_FRAGCOORD, RFX_AOV_VELOCITY_UV, out);
+}
+
+// ---------------------------------------------------------------- K0 device planes: rfx_stage_aov_device's layouts and launches
+// The planes of include/rfx.h rfx_aov_device_frame are read where the producer left them: the element of frame column x, band row r and channel
+// ch of plane i sits stride_x x + stride_y r + stride_c ch ELEMENTS from its `data`.  Rows, segments, written slots and every refusal of
+// rfx_stage_aov come from rfx_aov_plan_conv_for (`rows` below; its staging offsets only say which planes a segment reads).  On top of that:
+//   layout[i]    the plane's class, uniform over the call (the kernel branches on it per wave, k0_import.hip k0_aov_pack_strided):
+//                INTERLEAVED  stride_c == 1 and stride_x == channels — a lane's 4 C elements are contiguous;
+//                PLANAR       stride_x == 1 — per channel, a lane's four elements are contiguous;
+//                both only when `data` is aligned to four elements and stride_y (PLANAR: stride_c too) is a multiple of four, so that every
+//                lane's run starts on a 16-byte (halves: 8-byte) boundary in every row; ELEMENT otherwise.  A 1-channel plane has no stride_c.
+//   flat[k]      segment k is served by k0_aov_pack on the caller's pointers: every plane it reads is interleaved with stride_y == W x channels
+//                and starts, in the segment's first row, on a 16-byte boundary — the staging area's layout.
+//   seg_offset   elements from `data` to the segment's first row.
+//   the strided launch: a lane owns four consecutive pixels of ONE row — groups_x = W / 4 groups per row, the W mod 4 pixels from tail_x on go
+//   to lane groups_x of the row, element by element; workgroups of RFX_K0_DEV_BX x RFX_K0_DEV_BY lanes (along the row x rows), grid_x x grid_y[k].
+// Refused on top of rfx_aov_plan_conv_for's cases: an address that is not a multiple of the element size; a plane whose extent over the band,
+// (1 + sum over the axes of |stride| (count - 1)) elements, does not fit in 2^62 - 1 bytes (64-bit arithmetic that cannot overflow).
+// A pure function of its arguments, exported as rfx_internal_aov_device_plan (tests/test_stage_aov_device_cpu.py restates it).
+enum { RFX_AOV_LAYOUT_NONE = 0, RFX_AOV_LAYOUT_INTERLEAVED = 1, RFX_AOV_LAYOUT_PLANAR = 2, RFX_AOV_LAYOUT_ELEMENT = 3 };
+constexpr int RFX_K0_DEV_BX = 64, RFX_K0_DEV_BY = 4;
+struct rfx_aov_device_plan {
+    rfx_aov_plan rows;
+    int layout[RFX_AOV_PLANES];
+    int flat[3];
+    int groups_x, tail_x, tail_pixels, lanes_x;
+    int grid_x, grid_y[3];
+    long long seg_offset[3][RFX_AOV_PLANES];
+};
+// addr: the planes' `data` as integers (read for alignment only); stride_*: in elements.  0, or the RFX_EINVAL case in words.
+inline const char *rfx_aov_device_plan_for(int W, int H, int held_row0, int held_rows, const int *type, const int *channels, const unsigned long long *addr,
+                                           const long long *stride_x, const long long *stride_y, const long long *stride_c, int row0, int rows, int depth_kind,
+                                           int velocity_kind, rfx_aov_device_plan *out) {
+    rfx_aov_device_plan t = {};
+    if (const char *bad = rfx_aov_plan_conv_for(W, H, held_row0, held_rows, type, channels, row0, rows, depth_kind, velocity_kind, &t.rows)) return bad;
+    long long sc[RFX_AOV_PLANES];
+    for (int i = 0; i < RFX_AOV_PLANES; i++) {
+        if (!channels[i]) continue;
+        const unsigned long long e = (unsigned long long)t.rows.elem_bytes[i];
+        if (addr[i] % e) return "a plane's data is not aligned to its element size";
+        sc[i] = channels[i] > 1 ? stride_c[i] : 1;
+        // the extent in elements, kept below lim at every step
+        const unsigned long long lim = ((1ull << 62) - 1ull) / e;
+        const long long s[3] = {stride_x[i], stride_y[i], channels[i] > 1 ? stride_c[i] : 0};
+        const int n[3] = {W, rows, channels[i]};
+        unsigned long long total = 1;
+        for (int k = 0; k < 3; k++) {
+            const unsigned long long mag = s[k] < 0 ? 0ull - (unsigned long long)s[k] : (unsigned long long)s[k], steps = (unsigned long long)(n[k] - 1);
+            if (steps && mag > (lim - total) / steps) return "a plane's extent does not fit in 62 bits of bytes";
+            total += mag * steps;
+        }
+        const bool aligned4 = addr[i] % (4ull * e) == 0 && stride_y[i] % 4 == 0;
+        if (sc[i] == 1 && stride_x[i] == channels[i]) t.layout[i] = aligned4 ? RFX_AOV_LAYOUT_INTERLEAVED : RFX_AOV_LAYOUT_ELEMENT;
+        else if (stride_x[i] == 1) t.layout[i] = aligned4 && sc[i] % 4 == 0 ? RFX_AOV_LAYOUT_PLANAR : RFX_AOV_LAYOUT_ELEMENT;
+        else t.layout[i] = RFX_AOV_LAYOUT_ELEMENT;
+    }
+    t.groups_x = W / 4;
+    t.tail_x = t.groups_x * 4;
+    t.tail_pixels = W - t.tail_x;
+    t.lanes_x = t.groups_x + (t.tail_pixels ? 1 : 0);
+    t.grid_x = (t.lanes_x + RFX_K0_DEV_BX - 1) / RFX_K0_DEV_BX;
+    for (int k = 0; k < t.rows.nseg; k++) {
+        const rfx_aov_segment &g = t.rows.seg[k];
+        t.grid_y[k] = (g.rows + RFX_K0_DEV_BY - 1) / RFX_K0_DEV_BY;
+        t.flat[k] = 1;
+        for (int i = 0; i < RFX_AOV_PLANES; i++) {
+            if (g.offset[i] == ~0ull) continue;
+            t.seg_offset[k][i] = (long long)(g.row0 - row0) * stride_y[i];  // (inside the extent checked above)
+            const unsigned long long first = addr[i] + (unsigned long long)t.seg_offset[k][i] * (unsigned long long)t.rows.elem_bytes[i];
+            const bool tight = sc[i] == 1 && stride_x[i] == channels[i] && stride_y[i] == (long long)W * channels[i];
+            if (!tight || first % 16ull) t.flat[k] = 0;
+        }
+    }
+    *out = t;
+    return nullptr;
 }
 
 // ---------------------------------------------------------------- shared by the launchers

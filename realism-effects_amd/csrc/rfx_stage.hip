@@ -53,6 +53,20 @@ int grow_stage_area(rfx_ctx *c, void **area, size_t *cap, size_t need, const cha
     return grow_idle(c, area, cap, need, what);
 }
 
+// the conventions in use as the pack kernels read them: the setting as it stands at this call, with a segment's place in the frame
+static K0AovConv aov_conv_block(const rfx_ctx *c, int seg_row0) {
+    const rfx_aov_conventions &q = c->aov_conv;
+    K0AovConv v = {};
+    v.depth_kind = q.depth_kind; v.velocity_kind = q.velocity_kind; v.normal_space = q.normal_space; v.perspective = q.perspective;
+    v.W = c->W; v.H = c->H; v.row0 = seg_row0;
+    v.has_background = q.has_background_position != 0;
+    for (int i = 0; i < 3; i++) v.background[i] = q.background_position[i];
+    v.scale[0] = q.velocity_scale[0]; v.scale[1] = q.velocity_scale[1];
+    v.near_ = q.near_; v.far_ = q.far_;
+    memcpy(v.VM, q.velocityMatrix, sizeof v.VM); memcpy(v.PVM, q.prevVelocityMatrix, sizeof v.PVM);
+    memcpy(v.P, q.projectionMatrix, sizeof v.P); memcpy(v.Pi, q.projectionMatrixInverse, sizeof v.Pi); memcpy(v.C, q.cameraMatrixWorld, sizeof v.C);
+    return v;
+}
 hipError_t aov_pack_segment(rfx_ctx *c, const rfx_aov_plan &t, const rfx_aov_segment &g, K0AovArgs A) {
     const auto first = [&](int id) { return slot_back_row(c->slots[id], g.row0); };
     A.depth = (float *)first(RFX_TEX_DEPTH);
@@ -61,17 +75,7 @@ hipError_t aov_pack_segment(rfx_ctx *c, const rfx_aov_plan &t, const rfx_aov_seg
     if (g.full && t.write_direct) A.direct = (uint4 *)first(RFX_TEX_DIRECT_LIGHT);
     A.groups = g.groups; A.tail_start = g.tail_start; A.tail_pixels = g.tail_pixels;
     if (!c->aov_conv_on) return rfx_launch_k0_aov(A, g.blocks, c->upload_stream);
-    // conventions in use: the setting as it stands at this call, with the segment's place in the frame
-    const rfx_aov_conventions &q = c->aov_conv;
-    K0AovConv v = {};
-    v.depth_kind = q.depth_kind; v.velocity_kind = q.velocity_kind; v.normal_space = q.normal_space; v.perspective = q.perspective;
-    v.W = c->W; v.H = c->H; v.row0 = g.row0;
-    v.has_background = q.has_background_position != 0;
-    for (int i = 0; i < 3; i++) v.background[i] = q.background_position[i];
-    v.scale[0] = q.velocity_scale[0]; v.scale[1] = q.velocity_scale[1];
-    v.near_ = q.near_; v.far_ = q.far_;
-    memcpy(v.VM, q.velocityMatrix, sizeof v.VM); memcpy(v.PVM, q.prevVelocityMatrix, sizeof v.PVM);
-    memcpy(v.P, q.projectionMatrix, sizeof v.P); memcpy(v.Pi, q.projectionMatrixInverse, sizeof v.Pi); memcpy(v.C, q.cameraMatrixWorld, sizeof v.C);
+    const K0AovConv v = aov_conv_block(c, g.row0);
     return rfx_launch_k0_aov(A, g.blocks, c->upload_stream, &v);
 }
 int aov_depth_kind(const rfx_ctx *c) { return c->aov_conv_on ? c->aov_conv.depth_kind : RFX_AOV_DEPTH_FRAGCOORD; }
@@ -146,6 +150,71 @@ int rfx_stage_aov(rfx_ctx *c, const rfx_aov_frame *f, int row0, int rows) {
         HIPCHK(c, aov_pack_segment(c, t, g, A));
     }
     stage_plan_end(c, t);
+    return RFX_OK;
+}
+
+// ---- device planes (include/rfx.h): rfx_stage_aov without the copies — the pack kernels read the producer's own memory
+int rfx_stage_aov_device(rfx_ctx *c, const rfx_aov_device_frame *f, int row0, int rows, void *producer_stream) {
+    if (!c || !f) return RFX_EINVAL;
+    RFX_ENTER(c);
+    const char *fn = "rfx_stage_aov_device";
+    if (producer_stream) return fail_in(c, RFX_EUNSUPPORTED, fn, "a producer stream is not taken yet: make the planes complete before the call and pass NULL");
+    static_assert(sizeof(rfx_aov_device_frame) == RFX_AOV_PLANES * sizeof(rfx_device_plane), "rfx_aov_device_frame is eight planes");
+    const rfx_device_plane *planes = &f->diffuse;  // eight rfx_device_plane in RFX_AOV_* order
+    int type[RFX_AOV_PLANES], channels[RFX_AOV_PLANES];
+    unsigned long long addr[RFX_AOV_PLANES];
+    long long sx[RFX_AOV_PLANES], sy[RFX_AOV_PLANES], sc[RFX_AOV_PLANES];
+    for (int i = 0; i < RFX_AOV_PLANES; i++) {
+        const rfx_device_plane &p = planes[i];
+        type[i] = p.type;
+        channels[i] = p.data ? p.channels : 0;
+        if (p.data && p.channels <= 0) return fail_in(c, RFX_EINVAL, fn, "a plane's channel count");
+        addr[i] = (unsigned long long)(uintptr_t)p.data;
+        sx[i] = p.stride_x; sy[i] = p.stride_y; sc[i] = p.stride_c;
+    }
+    const Slot &held = c->slots[RFX_TEX_GBUFFER];  // (VELOCITY and DIRECT_LIGHT hold the same rows)
+    rfx_aov_device_plan t;
+    if (const char *bad = rfx_aov_device_plan_for(c->W, c->H, held.row0, held.rows, type, channels, addr, sx, sy, sc, row0, rows, aov_depth_kind(c), aov_velocity_kind(c), &t))
+        return fail_in(c, RFX_EINVAL, fn, bad);
+    int rc = stage_plan_begin(c, t.rows, fn);
+    if (rc) return rc;
+    // rfx_stage_upload's order: the back buffers were the front buffers until the last flip
+    HIPCHK(c, hipStreamWaitEvent(c->upload_stream, c->ev_frame_done, 0));
+    unsigned int half_mask = 0, layouts = 0;
+    for (int i = 0; i < RFX_AOV_PLANES; i++) {
+        if (channels[i] && type[i] == RFX_PLANE_F16) half_mask |= 1u << i;
+        layouts |= (unsigned int)t.layout[i] << (2 * i);
+    }
+    for (int k = 0; k < t.rows.nseg; k++) {
+        const rfx_aov_segment &g = t.rows.seg[k];
+        // the segment's first row of every plane it reads
+        const void *first[RFX_AOV_PLANES] = {};
+        for (int i = 0; i < RFX_AOV_PLANES; i++)
+            if (g.offset[i] != ~0ull) first[i] = (const char *)planes[i].data + t.seg_offset[k][i] * (long long)t.rows.elem_bytes[i];
+        if (t.flat[k]) {  // the staging area's own layout: rfx_stage_aov's kernel, on the caller's pointers
+            K0AovArgs A = {};
+            for (int i = 0; i < RFX_AOV_PLANES; i++) A.plane[i] = first[i];
+            A.half_mask = half_mask;
+            A.diffuse_ch = f->diffuse.channels; A.direct_ch = f->direct.channels;
+            HIPCHK(c, aov_pack_segment(c, t.rows, g, A));
+            continue;
+        }
+        K0AovStridedArgs A = {};
+        for (int i = 0; i < RFX_AOV_PLANES; i++) A.plane[i] = {first[i], sx[i], sy[i], channels[i] > 1 ? sc[i] : 0};
+        A.half_mask = half_mask; A.layouts = layouts;
+        A.diffuse_ch = f->diffuse.channels; A.direct_ch = f->direct.channels;
+        A.depth = (float *)slot_back_row(c->slots[RFX_TEX_DEPTH], g.row0);
+        if (g.full && t.rows.write_gbuffer) A.gbuffer = (uint4 *)slot_back_row(c->slots[RFX_TEX_GBUFFER], g.row0);
+        if (g.full && t.rows.write_velocity) A.velocity = (uint4 *)slot_back_row(c->slots[RFX_TEX_VELOCITY], g.row0);
+        if (g.full && t.rows.write_direct) A.direct = (uint4 *)slot_back_row(c->slots[RFX_TEX_DIRECT_LIGHT], g.row0);
+        A.W = c->W; A.rows = g.rows;
+        A.groups_x = t.groups_x; A.tail_x = t.tail_x; A.tail_pixels = t.tail_pixels; A.lanes_x = t.lanes_x;
+        if (c->aov_conv_on) {
+            const K0AovConv v = aov_conv_block(c, g.row0);
+            HIPCHK(c, rfx_launch_k0_aov_strided(A, t.grid_x, t.grid_y[k], c->upload_stream, &v));
+        } else HIPCHK(c, rfx_launch_k0_aov_strided(A, t.grid_x, t.grid_y[k], c->upload_stream));
+    }
+    stage_plan_end(c, t.rows);
     return RFX_OK;
 }
 

@@ -116,6 +116,15 @@ class AovFrame(C.Structure):
     _fields_ = [(name, Plane) for name in AOV_PLANES]
 
 
+# rfx.h "device planes": rfx_stage_aov_device's planes, addressed by element strides in device memory (additive to ABI 21)
+class DevicePlane(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("type", C.c_int32), ("channels", C.c_int32), ("stride_x", C.c_int64), ("stride_y", C.c_int64), ("stride_c", C.c_int64)]
+
+
+class AovDeviceFrame(C.Structure):
+    _fields_ = [(name, DevicePlane) for name in AOV_PLANES]
+
+
 # rfx.h "AOV conventions": the planes as engines write them (rfx_set_aov_conventions, additive to ABI 21)
 AOV_DEPTH_FRAGCOORD, AOV_DEPTH_VIEW_Z, AOV_DEPTH_POSITION = 0, 1, 2
 AOV_VELOCITY_UV, AOV_VELOCITY_SCALED, AOV_VELOCITY_CAMERAS = 0, 1, 2
@@ -205,6 +214,7 @@ EXPORTS = [
     "rfx_stage_png_ex", "rfx_png_ex", "rfx_stage_exr_ex", "rfx_exr_ex",
     "rfx_set_environment_cube", "rfx_build_environment_importance", "rfx_download_environment_importance",
     "rfx_set_aov_conventions",
+    "rfx_stage_aov_device",
 ]
 
 _lib = None
@@ -340,6 +350,8 @@ def load_library(path: str | None = None) -> C.CDLL:
         lib.rfx_download_environment_importance.argtypes = [vp, vp, vp, C.POINTER(C.c_double), C.POINTER(f), C.POINTER(f)]
     if hasattr(lib, "rfx_set_aov_conventions"):  # (additive to ABI 21: Context.has_aov_conventions)
         lib.rfx_set_aov_conventions.argtypes = [vp, C.POINTER(AovConventions)]
+    if hasattr(lib, "rfx_stage_aov_device"):  # (additive to ABI 21: Context.has_stage_aov_device)
+        lib.rfx_stage_aov_device.argtypes = [vp, C.POINTER(AovDeviceFrame), i, i, vp]
     if lib.rfx_abi_version() != RFX_ABI_VERSION:
         raise ImportError("librfx_hip.so ABI version %d != %d" % (lib.rfx_abi_version(), RFX_ABI_VERSION))
     if path is None:

@@ -24,6 +24,31 @@ def load_blue_noise_table() -> np.ndarray:
     return t.reshape(128, 128, 4)
 
 
+_TENSOR_PLANE_TYPES = {"torch.float32": (abi.PLANE_F32, 4), "torch.float16": (abi.PLANE_F16, 2)}
+
+
+def device_plane(tensor, rows: int, width: int, origin: str = "bottom") -> abi.DevicePlane:
+    """A (rows, width, C) or (rows, width) tensor, float32 or float16, with ANY strides -> the abi.DevicePlane that addresses it where it lies:
+    a permuted (C, H, W) tensor, a slice of a pitched buffer, an `expand`ed constant (strides 0).  origin "bottom": the tensor's row 0 is the
+    band's first frame row (row 0 of the frame is its bottom row); "top": row 0 is the band's LAST frame row, as images are kept — a negative
+    stride_y from the tensor's last row.  A pure function of the tensor's shape, strides, dtype and data_ptr(): it runs on CPU tensors too."""
+    if origin not in ("bottom", "top"):
+        raise ValueError("origin: \"bottom\" or \"top\"")
+    shape, strides = tuple(int(n) for n in tensor.shape), tuple(int(s) for s in tensor.stride())
+    if len(shape) == 2:
+        shape, strides = shape + (1,), strides + (0,)
+    if len(shape) != 3 or shape[:2] != (int(rows), int(width)):
+        raise ValueError("device plane: a tensor of shape (%d, %d[, C]), got %s" % (rows, width, tuple(tensor.shape)))
+    if str(tensor.dtype) not in _TENSOR_PLANE_TYPES:
+        raise TypeError("device plane: a float32 or float16 tensor, got %s" % (tensor.dtype,))
+    kind, elem = _TENSOR_PLANE_TYPES[str(tensor.dtype)]
+    sy, sx, sc = strides
+    ptr = int(tensor.data_ptr())
+    if origin == "top":
+        ptr, sy = ptr + (shape[0] - 1) * sy * elem, -sy
+    return abi.DevicePlane(ptr, kind, shape[2], sx, sy, sc)
+
+
 class Context:
     def __init__(self, width: int, height: int, device: int = 0, tile_y0: int = 0, tile_rows: int | None = None, halo_rows: int = 0):
         self.lib = abi.load_library()
@@ -126,7 +151,10 @@ class Context:
             planes["depth"] = frame.depth
             if getattr(frame, "direct", None) is not None:
                 planes["direct"] = frame.direct
-            self.stage_aov(planes)
+            if any(isinstance(v, abi.DevicePlane) for v in planes.values()):  # a frame that lives on the device
+                self.stage_aov_device(planes)
+            else:
+                self.stage_aov(planes)
             return
         for tex, plane in ((abi.TEX_DEPTH, frame.depth), (abi.TEX_GBUFFER, frame.gbuffer), (abi.TEX_VELOCITY, frame.velocity),
                            (abi.TEX_DIRECT_LIGHT, frame.direct)):
@@ -139,14 +167,7 @@ class Context:
         dtype (float32 / float16), the channel count from the size."""
         row0 = 0 if row0 is None else int(row0)
         rows = self.H - row0 if rows is None else int(rows)
-        alias = [k for k in ("depth", "position", "view_z") if planes.get(k) is not None]
-        if len(alias) > 1:
-            raise ValueError("AOV frame: %s are one plane (the depth plane under the conventions set)" % " and ".join(alias))
-        if alias and alias[0] != "depth":  # set_aov_conventions says which of the three the library takes the depth plane for
-            planes = {("depth" if k == alias[0] else k): v for k, v in planes.items() if k not in ("depth", "position", "view_z") or k == alias[0]}
-        unknown = set(planes) - set(abi.AOV_PLANES)
-        if unknown:
-            raise ValueError("AOV frame: unknown planes %s" % sorted(unknown))
+        planes = self._aov_named(planes)
         f, keep = abi.AovFrame(), []
         texels = max(rows, 0) * self.W
         for name in abi.AOV_PLANES:
@@ -161,6 +182,50 @@ class Context:
             keep.append(a)
             setattr(f, name, abi.Plane(a.ctypes.data, abi.PLANE_TYPES[a.dtype], a.size // texels))
         return f, row0, rows, keep
+
+    @staticmethod
+    def _aov_named(planes: dict) -> dict:
+        """the planes under rfx_aov_frame's names: `position` / `view_z` are the depth plane under the conventions set"""
+        alias = [k for k in ("depth", "position", "view_z") if planes.get(k) is not None]
+        if len(alias) > 1:
+            raise ValueError("AOV frame: %s are one plane (the depth plane under the conventions set)" % " and ".join(alias))
+        if alias and alias[0] != "depth":  # set_aov_conventions says which of the three the library takes the depth plane for
+            planes = {("depth" if k == alias[0] else k): v for k, v in planes.items() if k not in ("depth", "position", "view_z") or k == alias[0]}
+        unknown = set(planes) - set(abi.AOV_PLANES)
+        if unknown:
+            raise ValueError("AOV frame: unknown planes %s" % sorted(unknown))
+        return planes
+
+    # -- device planes (rfx.h "device planes"): the AOV frame of a renderer on the same device, read where it lies
+    @property
+    def has_stage_aov_device(self) -> bool:
+        """the library exports rfx_stage_aov_device (additive to ABI 21)"""
+        return hasattr(self.lib, "rfx_stage_aov_device")
+
+    def _aov_device_frame(self, planes: dict, row0, rows):
+        """-> (abi.AovDeviceFrame, row0, rows).  `planes`: name -> abi.DevicePlane of the band's rows"""
+        row0, rows = self._band(row0, rows)
+        planes = self._aov_named(planes)
+        f = abi.AovDeviceFrame()
+        for name in abi.AOV_PLANES:
+            v = planes.get(name)
+            if v is None:
+                continue
+            if not isinstance(v, abi.DevicePlane):
+                raise TypeError("device AOV plane %s: an abi.DevicePlane (context.device_plane makes one of a tensor), got %s" % (name, type(v)))
+            setattr(f, name, v)
+        return f, row0, rows
+
+    def stage_aov_device(self, planes: dict, row0: int | None = None, rows: int | None = None):
+        """rfx_stage_aov_device: stage_aov for planes that already live on the device — nothing crosses PCIe, the pack kernel reads them where
+        they lie.  Values: abi.DevicePlane records (a device address and element strides of any sign, 0 for a broadcast); device_plane() makes
+        one of a torch tensor of shape (rows, W, C) or (rows, W) with any strides.  `position=` / `view_z=` as in stage_aov.  The planes are
+        complete when the call is made (synchronise the stream that produced them) and the caller keeps them alive and unchanged until the
+        flip after the publishing one has returned."""
+        if not self.has_stage_aov_device:
+            raise RfxError("this librfx_hip.so has no rfx_stage_aov_device")
+        f, row0, rows = self._aov_device_frame(planes, row0, rows)
+        self._chk(self.lib.rfx_stage_aov_device(self._h, C.byref(f), row0, rows, None), "rfx_stage_aov_device")
 
     # -- AOV conventions (rfx.h "AOV conventions"): the planes as engines write them, converted by the pack kernel
     @property

@@ -38,7 +38,18 @@ rounds; with --parent-lib PATH (a librfx_hip.so built from the parent commit, lo
 library too, so that each round is an A/B/C triple.  Beside each: "stage_only", the wall time of stage + flip + sync without draws — the copies
 with the pack kernel behind them, where a kernel that leaves the copy's shadow shows.  Merged into --out under "conventions".
 
-    python tools/import_rate.py [--modes P0,A0,A1,A2 | E0,E1 | C2] [--out profiles/import/rates.json] [--seconds 1.0]
+--modes A2,D2,D2p: the typed frame RESIDENT in device memory (rfx.h "device planes"; hipMalloc'ed on the library's own runtime, handed over as
+abi.DevicePlane records, no torch in the process), through stage_aov_device:
+
+    D2   tight and interleaved, row 0 at the bottom: the staging area's own layout — k0_aov_pack on the caller's pointers
+    D2p  the same values as planar (C, H, W) planes, image row 0 at the top: the strided kernel's planar form
+    D2i  (--kernel-only) interleaved rows padded by four elements: the strided kernel's interleaved form
+
+each stage + flip + the chain's draws beside A2 in three alternating rounds; D2 < A2 and D2p < A2 is required in every round (A2 is the PCIe copy
+the D modes do not make).  Merged into --out under "device_planes".  With --kernel-only: A2, D2, D2p, D2i, stage + flip alone, for one kernel trace.
+
+    python tools/import_rate.py [--modes P0,A0,A1,A2 | E0,E1 | C2 | A2,D2,D2p] [--out profiles/import/rates.json] [--seconds 1.0]
+    rocprofv3 --kernel-trace --stats -d DIR -- python tools/import_rate.py --kernel-only --modes A2,D2,D2p   (... flat beside strided, device planes)
     rocprofv3 --kernel-trace --stats -d DIR -- python tools/import_rate.py --kernel-only      (the pack kernel's own time: a run of its own)
     rocprofv3 --kernel-trace --stats -d DIR -- python tools/import_rate.py --kernel-only --modes E1      (... and the K9 kernels')
     rocprofv3 --kernel-trace --stats -d DIR -- python tools/import_rate.py --kernel-only --modes C2      (... default beside converting)
@@ -260,6 +271,8 @@ def main():
     modes = tuple(a.modes.split(","))
     if "C2" in modes:
         return main_conventions(a)
+    if "D2" in modes or "D2p" in modes:
+        return main_device(a)
     if any(m in EXR_MODES for m in modes):
         return main_exr_blocks(a, modes) if a.forms else main_exr(a, modes)
     run = Run(a.seed)
@@ -292,6 +305,111 @@ def main():
         f.write("\n")
     if not result["required_A1_and_A2_below_A0_every_round"]:
         sys.exit("import_rate: stage_aov is not faster than the synchronous importer in every round: the staging does not overlap")
+
+
+def resident(v, layout, held):
+    """a plane's (H, W[, C]) values in hipMalloc'ed memory (on the runtime the library itself uses) -> the abi.DevicePlane that addresses them;
+    the layouts ("tight", "planar_top", "pitch4") and the runtime handle are the device-plane tests' own (tests/aov_device_cases.py)"""
+    import ctypes as C
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import aov_device_cases as D
+    flat, off, sx, sy, sc = D.lay(v, layout)
+    p = C.c_void_p()
+    assert D.hip().hipMalloc(C.byref(p), flat.nbytes) == 0 and p.value and p.value % 256 == 0
+    held.append(p.value)
+    assert D.hip().hipMemcpy(p, flat.ctypes.data, flat.nbytes, 1) == 0  # (host to device, complete on return)
+    return abi.DevicePlane(p.value + off * v.dtype.itemsize, abi.PLANE_TYPES[v.dtype], 1 if v.ndim == 2 else v.shape[2], sx, sy, sc)
+
+
+def device_plan_flat(f):
+    """rfx_internal_aov_device_plan's `flat` for the whole frame of DevicePlane records f: 1 = k0_aov_pack serves it, 0 = the strided kernel"""
+    import ctypes as C
+    I, U, L = C.c_int, C.c_ulonglong, C.c_longlong
+
+    class Seg(C.Structure):
+        _fields_ = [(n, I) for n in ("row0", "rows", "full", "pixels", "groups", "blocks", "tail_start", "tail_pixels")] + [("offset", U * 8)]
+
+    class Rows(C.Structure):
+        _fields_ = [("nseg", I), ("seg", Seg * 3), ("plane_row0", I * 8), ("plane_rows", I * 8), ("elem_bytes", I * 8), ("write_gbuffer", I), ("write_velocity", I),
+                    ("write_direct", I), ("copy_bytes", U), ("stage_bytes", U)]
+
+    class Plan(C.Structure):
+        _fields_ = [("rows", Rows), ("layout", I * 8), ("flat", I * 3), ("groups_x", I), ("tail_x", I), ("tail_pixels", I), ("lanes_x", I), ("grid_x", I), ("grid_y", I * 3),
+                    ("seg_offset", (L * 8) * 3)]
+    planes = [dict(f.aov, depth=f.depth, direct=f.direct)[k] for k in abi.AOV_PLANES]
+    t = Plan()
+    rc = abi.load_library().rfx_internal_aov_device_plan(
+        C.c_int(W), C.c_int(H), C.c_int(0), C.c_int(H), (I * 8)(*[p.type for p in planes]), (I * 8)(*[p.channels for p in planes]), (U * 8)(*[p.data for p in planes]),
+        (L * 8)(*[p.stride_x for p in planes]), (L * 8)(*[p.stride_y for p in planes]), (L * 8)(*[p.stride_c for p in planes]), C.c_int(0), C.c_int(H), C.c_int(0), C.c_int(0),
+        C.byref(t))
+    assert rc == 0 and t.rows.nseg == 1
+    return t.flat[0], list(t.layout)
+
+
+def main_device(a):
+    """A2 beside D2 and D2p; merged into --out under "device_planes" """
+    run = Run(a.seed)
+    ctx = run.ctx
+    assert ctx.has_stage_aov_device
+    held = []
+    layouts = dict(D2="tight", D2p="planar_top", D2i="pitch4")
+    for mode, layout in layouts.items():
+        run.frames[mode] = []
+        for f in run.frames["A2"]:
+            run.frames[mode].append(types.SimpleNamespace(camera=f.camera, static="resident", depth=resident(f.depth, layout, held), direct=resident(f.direct, layout, held),
+                                                          gbuffer=None, velocity=None, aov={k: resident(v, layout, held) for k, v in f.aov.items()}))
+    import aov_device_cases as D  # (on sys.path since resident())
+    assert D.hip().hipDeviceSynchronize() == 0
+    # D2 is the flat kernel on the caller's pointers; D2p is the strided kernel's PLANAR form, D2i its INTERLEAVED form, on every plane
+    plans = {m: device_plan_flat(run.frames[m][0]) for m in layouts}
+    multi = [i for i, k in enumerate(abi.AOV_PLANES) if k not in ("roughness", "metalness", "depth")]  # (a 1-channel plane with stride_x 1 is INTERLEAVED)
+    assert plans["D2"][0] == 1 and plans["D2p"][0] == 0 and plans["D2i"] == (0, [1] * 8), plans
+    assert all(plans["D2p"][1][i] == 2 for i in multi) and all(v in (1, 2) for v in plans["D2p"][1]), plans
+
+    def release():
+        ctx.close()
+        for p in held:
+            D.hip().hipFree(p)
+    if a.kernel_only:  # under rocprofv3 --kernel-trace --stats: 20 x k0_aov_pack<1, false> on staged copies, 20 x the same on device planes, 20 + 20 x strided
+        run.kernel_only(modes=("A2", "D2", "D2p", "D2i"))
+        release()
+        return
+    order = ["A2", "D2", "D2p"]
+    n = {}
+    for m in order:
+        run.loop(m, 5)
+        n[m] = max(20, int(math.ceil(a.seconds / (run.loop(m, 20) / 20))))
+    out = dict(width=W, height=H, seed=a.seed, seconds=a.seconds, steps=20, refineSteps=5, bytes_per_frame=BYTES_PER_PIXEL["A2"] * W * H, frames=n, rounds=[], stage_only=[])
+    for r in range(3):  # (the order rotates: no mode is always the first or the last of its round)
+        row = {m: round(run.loop(m, n[m]) / n[m] * 1e3, 4) for m in order[r:] + order[:r]}
+        row = {m: row[m] for m in order}
+        row["D2_below_A2"], row["D2p_below_A2"] = row["D2"] < row["A2"], row["D2p"] < row["A2"]
+        out["rounds"].append(row)
+        print(json.dumps(row), flush=True)
+
+    def stage_only(m, k=40):
+        ctx.sync()
+        t0 = time.perf_counter()
+        for i in range(k):
+            run.stage(run.frames[m][i & 1], i)
+            ctx.stage_flip()
+        ctx.sync()
+        return (time.perf_counter() - t0) / k
+    for r in range(3):
+        row = {m: round(stage_only(m) * 1e3, 4) for m in order + ["D2i"]}
+        out["stage_only"].append(row)
+        print("stage_only", json.dumps(row), flush=True)
+    out["required_D2_and_D2p_below_A2_every_round"] = ok = all(r["D2_below_A2"] and r["D2p_below_A2"] for r in out["rounds"])
+    assert ctx.halo_violations() == 0
+    release()
+    result = json.load(open(a.out)) if os.path.exists(a.out) else {}
+    result["device_planes"] = out
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+    if not ok:
+        sys.exit("import_rate: staging from device planes is not faster than the PCIe copy in every round")
 
 
 def _engine_band(args):
