@@ -719,6 +719,55 @@ typedef struct rfx_device_plane {
 } rfx_device_plane;
 typedef struct rfx_aov_device_frame { rfx_device_plane diffuse, normal, roughness, metalness, emissive, velocity, depth, direct; } rfx_aov_device_frame;
 int rfx_stage_aov_device(rfx_ctx *, const rfx_aov_device_frame *, int row0, int rows, void *producer_stream);
+/* (producer_stream stays reserved.  A producer that must not host-synchronise orders the upload stream itself, before the call:
+ * rfx_queue_wait_stream(ctx, RFX_QUEUE_UPLOAD, its stream) — "device images and stream ordering" below.) */
+
+/* ---- device images and stream ordering (additive to ABI 21: a host checks for the symbols): the way OUT that stays on the device, and the
+ * two calls that order a context's queues against a caller's stream without a host wait.
+ * rfx_export_device is rfx_export into a buffer in device memory that the CALLER owns and lays out — a torch tensor a denoiser reads, a video
+ * encoder's input surface, a viewer's texture.  It covers the context's tile rows [tile_y0, tile_y0 + tile_rows) of params->source and reads
+ * rfx_export_params exactly as rfx_export does: the same sources, the same 8 format / channel / operator combinations, the same RFX_EINVAL and
+ * RFX_ESTATE rules.  K7 encodes on the DRAW stream, after every draw enqueued so far, straight into the image: the element of column x, frame
+ * row y and channel ch goes to data[x stride_x + (y - tile_y0) stride_y + ch stride_c], strides in ELEMENTS of params->format (4 / 2 / 1
+ * bytes), of any sign; row 0 is the frame's BOTTOM row, so an image kept top-down has a negative stride_y and `data` at its last image row.
+ * The elements are, bit for bit, those rfx_export returns for the same parameters.  No byte the image does not address is written: row
+ * padding, plane padding and whatever lies before an offset base keep what they held.  The call takes no ticket, uses no staging buffer and no
+ * download stream, allocates nothing and waits for nothing; it does not count in the tickets of rfx_stage_export and leaves their back
+ * pressure alone.  rfx_set_row_window does not apply.  Several contexts of one process (row tiles on one device) may write their bands
+ * into one frame-sized buffer.  The encode is timed under RFX_PROF_K7.
+ * STORE FORMS (decided per call, uniform over the launch).  TIGHT — interleaved (stride_c 1, stride_x = channels), stride_y = width x channels,
+ * `data` on a 4-byte boundary: rfx_export's own kernel on the caller's pointer.  INTERLEAVED — stride_c 1, stride_x = channels, `data` and the
+ * row pitch in bytes multiples of 4: whole dwords, any row pitch.  PLANAR — stride_x 1, `data` aligned to four elements, stride_y and stride_c
+ * multiples of four elements: one 16- / 8- / 4-byte store per channel and four pixels (F32 / F16 / U8).  Everything else — a misaligned base
+ * or pitch, a mirrored x, scanline-planar (H, C, W) at a width that breaks the alignment — is written element by element.
+ * RFX_EINVAL (every check runs before anything is enqueued, and rfx_last_error names the entry point): what rfx_export refuses; dst or
+ * dst->data NULL; `data` not a multiple of the element size; an extent — (1 + the sum over the three axes of |stride| (count - 1)) elements —
+ * beyond 2^62 - 1 bytes; strides that do not NEST.  A store image must not alias itself: of the axes whose count is above 1 (width, tile_rows,
+ * channels), sorted by |stride|, the smallest |stride| must be >= 1 and every later one >= the one before it x that axis's count.  This admits
+ * interleaved, planar (C, H, W), scanline-planar (H, C, W), any row or plane pitch, a top-down image, a mirrored axis; it refuses a 0 stride.
+ * The rule is SUFFICIENT for an image without aliases, not necessary: some exotic alias-free layouts (interlocking combs) are refused too.
+ * An image that overlaps the context's own buffers is undefined.  The library does not ask the runtime what kind of memory `data` is: an
+ * address the device cannot write faults there.
+ *
+ * rfx_queue_wait_stream / rfx_stream_wait_queue: one hipEventRecord and one hipStreamWaitEvent each, on events the context owns (created at
+ * the first use, destroyed by rfx_destroy).  The host never waits and nothing is allocated at a repeated call.  `queue`: RFX_QUEUE_DRAW —
+ * whichever stream the context draws on at the call (rfx_set_stream) — or RFX_QUEUE_UPLOAD, the stream of the rfx_stage_* calls (created
+ * here if no staged call has yet).  hip_stream NULL: RFX_EINVAL — the legacy default stream cannot be named, rfx_set_stream's rule.  An
+ * unknown queue: RFX_EINVAL.  Only work enqueued BEFORE the call is ordered ("NOW").  The four uses:
+ *   a producer, before rfx_stage_aov_device reads its planes:        rfx_queue_wait_stream(ctx, RFX_QUEUE_UPLOAD, producer)
+ *   a producer, before it rewrites planes a staged call still reads: rfx_stream_wait_queue(ctx, RFX_QUEUE_UPLOAD, producer)
+ *   a consumer whose image rfx_export_device is about to rewrite:    rfx_queue_wait_stream(ctx, RFX_QUEUE_DRAW, consumer)
+ *   a consumer, before it reads the image:                           rfx_stream_wait_queue(ctx, RFX_QUEUE_DRAW, consumer) */
+typedef struct rfx_device_image {
+    void *data;                            /* device address of element (x = 0, frame row tile_y0, channel 0) */
+    int64_t stride_x, stride_y, stride_c;  /* in ELEMENTS of params->format (4 / 2 / 1 bytes), any sign;
+                                              stride_y steps to frame row + 1 (row 0 = bottom) */
+} rfx_device_image;
+int rfx_export_device(rfx_ctx *, const rfx_export_params *, const rfx_device_image *dst);
+
+enum { RFX_QUEUE_DRAW = 0, RFX_QUEUE_UPLOAD = 1 };
+int rfx_queue_wait_stream(rfx_ctx *, int queue, void *hip_stream);  /* the context's queue waits for what hip_stream holds NOW */
+int rfx_stream_wait_queue(rfx_ctx *, int queue, void *hip_stream);  /* hip_stream waits for what the context's queue holds NOW */
 
 /* ---- streamed EXR frames (additive to ABI 21: a host checks for the symbol): rfx_stage_aov for an AOV frame that is still a compressed OpenEXR
  * file.  The scanline chunks cross PCIe as they sit in the file, on the upload stream; K9 (csrc/k9_exr_import.hip) inflates them — one wave per

@@ -101,6 +101,8 @@ void rfx_destroy(rfx_ctx *c) {
         if (e) hipEventDestroy(e);
     if (c->ev_staged) hipEventDestroy(c->ev_staged);
     if (c->ev_frame_done) hipEventDestroy(c->ev_frame_done);
+    for (hipEvent_t e : c->ev_order)
+        if (e) hipEventDestroy(e);
     if (c->halo_violations) hipFree(c->halo_violations);
     if (c->viewz) hipFree(c->viewz);
     if (c->prep_stream) { hipStreamSynchronize(c->prep_stream); hipStreamDestroy(c->prep_stream); }

@@ -87,6 +87,9 @@ struct rfx_ctx {
     hipEvent_t ev_staged = nullptr, ev_frame_done = nullptr;
     hipEvent_t ev_batch[2] = {nullptr, nullptr};  // the copies published by the last two flips (recorded on upload_stream)
     unsigned int flips = 0;
+    // rfx_queue_wait_stream / rfx_stream_wait_queue (include/rfx.h "device images and stream ordering"): [0] is recorded on the caller's stream
+    // and waited for by a queue of the context, [1] the other way round; created at the first use of either call
+    hipEvent_t ev_order[2] = {nullptr, nullptr};
     // rfx_stage_aov: the staging area the planes of an AOV frame are copied into on the upload stream and its pack kernel reads (rfx_launch.h
     // rfx_aov_plan).  One is enough: the stream is in order, the next call's copies queue behind this call's kernel.  Grown on demand; neither a
     // texture slot nor checkpoint state
@@ -151,6 +154,9 @@ extern "C" int rfx_internal_blur_reach_enqueue(rfx_ctx *c, const rfx_motion_blur
 extern "C" int rfx_internal_k1_table(int W, int H, struct rfx_k1_table_plan *out);
 extern "C" int rfx_internal_scaled_rows(int W, int H, int Hs, int uv_model, int y0, int y1, int apron, int *j0, int *j1);
 extern "C" int rfx_internal_export_plan(int pixels, int format, int channels, struct rfx_export_plan *out);
+// (addr: the image's `data`; strides in elements — rfx_launch.h rfx_export_device_plan_for)
+extern "C" int rfx_internal_export_device_plan(int W, int rows, int format, int channels, unsigned long long addr, long long stride_x, long long stride_y,
+                                               long long stride_c, struct rfx_export_device_plan *out);
 // (held_row0, held_rows: the rows GBUFFER / VELOCITY / DIRECT_LIGHT hold; type, channels: eight entries in rfx_aov_frame's order, channels 0 = not given)
 extern "C" int rfx_internal_aov_plan(int W, int H, int held_row0, int held_rows, const int *type, const int *channels, int row0, int rows, struct rfx_aov_plan *out);
 // ... with the kinds of include/rfx.h "AOV conventions" (rfx_launch.h rfx_aov_plan_conv_for)

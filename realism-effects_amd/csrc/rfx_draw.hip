@@ -210,6 +210,10 @@ int rfx_internal_scaled_rows(int W, int H, int Hs, int uv_model, int y0, int y1,
 int rfx_internal_export_plan(int pixels, int format, int channels, struct rfx_export_plan *out) {
     return rfx_export_plan_for(pixels, format, channels, out) ? RFX_OK : RFX_EINVAL;
 }
+int rfx_internal_export_device_plan(int W, int rows, int format, int channels, unsigned long long addr, long long stride_x, long long stride_y, long long stride_c,
+                                    struct rfx_export_device_plan *out) {
+    return rfx_export_device_plan_for(W, rows, format, channels, addr, stride_x, stride_y, stride_c, out) ? RFX_EINVAL : RFX_OK;
+}
 int rfx_internal_aov_plan(int W, int H, int held_row0, int held_rows, const int *type, const int *channels, int row0, int rows, struct rfx_aov_plan *out) {
     return rfx_aov_plan_for(W, H, held_row0, held_rows, type, channels, row0, rows, out) ? RFX_EINVAL : RFX_OK;
 }

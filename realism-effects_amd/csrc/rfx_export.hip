@@ -157,6 +157,46 @@ int rfx_export(rfx_ctx *c, const rfx_export_params *p, void *host, size_t bytes)
     return rc ? rc : rfx_export_wait(c, ticket);
 }
 
+// ---- device images (include/rfx.h "device images and stream ordering"): K7 on the draw stream, straight into the caller's buffer.  Nothing of
+// the streamed export is touched: no ticket, no staging buffer, no download stream, no allocation, no wait
+int rfx_export_device(rfx_ctx *c, const rfx_export_params *p, const rfx_device_image *dst) {
+    if (!c) return RFX_EINVAL;
+    RFX_ENTER(c);
+    const char *fn = "rfx_export_device";
+    if (!p) return fail_in(c, RFX_EINVAL, fn, "params is NULL");
+    if (const char *bad = export_params_error(p)) return fail_in(c, RFX_EINVAL, fn, bad);
+    if (!dst) return fail_in(c, RFX_EINVAL, fn, "dst is NULL");
+    rfx_export_device_plan t;
+    if (const char *bad = rfx_export_device_plan_for(c->W, c->tile_rows, p->format, p->channels, (unsigned long long)(uintptr_t)dst->data, dst->stride_x, dst->stride_y,
+                                                     dst->stride_c, &t))
+        return fail_in(c, RFX_EINVAL, fn, bad);
+    const Slot &s = c->slots[p->source];
+    if (!slot_filled(c, p->source)) return fail_in(c, RFX_ESTATE, fn, "the source slot holds nothing yet (upload it or draw into it first)");
+    const uint4 *src = (const uint4 *)slot_row(s, c->tile_y0);
+    ProfScope prof(c, RFX_PROF_K7, c->stream);
+    if (t.form == RFX_EXPORT_FORM_TIGHT) {  // the staging buffer's own layout: rfx_export's kernel, on the caller's pointer
+        K7Args A;
+        A.src = src;
+        A.dst = dst->data;
+        A.groups = t.flat.groups;
+        A.tail_start = t.flat.tail_start;
+        A.tail_pixels = t.flat.tail_pixels;
+        A.exposure = p->exposure;
+        HIPCHK(c, rfx_launch_k7(A, t.flat.blocks, p->format, p->channels, p->tonemap, c->stream));
+        return RFX_OK;
+    }
+    K7StridedArgs A;
+    A.src = src;
+    A.dst = dst->data;
+    A.sx = dst->stride_x; A.sy = dst->stride_y; A.sc = dst->stride_c;
+    A.W = c->W; A.rows = c->tile_rows;
+    A.groups_x = t.groups_x; A.tail_x = t.tail_x; A.tail_pixels = t.tail_pixels; A.lanes_x = t.lanes_x;
+    A.form = t.form;
+    A.exposure = p->exposure;
+    HIPCHK(c, rfx_launch_k7_strided(A, t.grid_x, t.grid_y, p->format, p->channels, p->tonemap, c->stream));
+    return RFX_OK;
+}
+
 // ---- K8: the same export as a finished PNG fragment (include/rfx.h "PNG fragments"; the kernels are in k8_png.h)
 size_t rfx_png_bound(const rfx_ctx *c, const rfx_export_params *p) {
     rfx_png_plan g;

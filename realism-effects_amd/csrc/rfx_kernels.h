@@ -200,6 +200,19 @@ struct K7Args {
 };
 // format / channels / tonemap select the specialisation (hipErrorInvalidValue for a combination the export does not have); `blocks` from the plan
 hipError_t rfx_launch_k7(const K7Args &, int blocks, int format, int channels, int tonemap, hipStream_t);
+// K7 into a device image (k7_export.hip k7_export_strided): `rows` rows of W RGBA32F texels from `src` (row pitch W) -> the caller's image,
+// addressed by element strides, in one of the store forms of rfx_launch.h rfx_export_device_plan_for (never TIGHT: that is rfx_launch_k7)
+struct K7StridedArgs {
+    const uint4 *src;       // first exported texel
+    void *dst;              // the element of column 0, the first exported row, channel 0
+    long long sx, sy, sc;   // in elements of the format
+    int W, rows;
+    int groups_x, tail_x, tail_pixels, lanes_x;  // per row: lanes [0, groups_x) own four pixels each, lane groups_x the tail; lanes_x of them
+    int form;               // RFX_EXPORT_FORM_INTERLEAVED / _PLANAR / _ELEMENT
+    float exposure;
+};
+// grid_x x grid_y workgroups of RFX_K7_DEV_BX x RFX_K7_DEV_BY lanes; the specialisation as for rfx_launch_k7
+hipError_t rfx_launch_k7_strided(const K7StridedArgs &, int grid_x, int grid_y, int format, int channels, int tonemap, hipStream_t);
 
 // K8 PNG encode (k8_png.h over k8_coder.h, built into k7_export.hip): K7's staged U8 stream -> the result buffer of include/rfx.h "PNG fragments", laid out by
 // rfx_launch.h rfx_png_plan_for.  Three launches on `stream`: one wave per scanline into the scratch slots, the scan, the gather.

@@ -1,7 +1,7 @@
 // rfx_launch.h — what a launch decides on the host before it launches: K1's table layout, a scaled tile's target rows, K3's tile geometry, the
 // "whole frame" test, the step from a run-time option to a template argument, and what is remembered per kernel and device.  Host code
 // (rfx_device.h comes in for UvPlanes and the two vUv expressions the kernels and the row plan share).  The plans are pure functions of their
-// arguments (no HIP call, no context): rfx_draw.hip exports them as rfx_internal_k1_table / rfx_internal_k3_tile / rfx_internal_scaled_rows / rfx_internal_export_plan / rfx_internal_aov_plan / rfx_internal_aov_device_plan / rfx_internal_exr_piz_tables and
+// arguments (no HIP call, no context): rfx_draw.hip exports them as rfx_internal_k1_table / rfx_internal_k3_tile / rfx_internal_scaled_rows / rfx_internal_export_plan / rfx_internal_export_device_plan / rfx_internal_aov_plan / rfx_internal_aov_device_plan / rfx_internal_exr_piz_tables and
 // the CPU tests call them as built (tests/test_k1_table_layout.py, tests/test_k3_tile_geometry.py, tests/test_resolution_scale_rows_cpu.py).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -149,6 +149,82 @@ inline bool rfx_export_plan_for(int pixels, int format, int channels, rfx_export
     t.bytes = (unsigned long long)pixels * (unsigned long long)t.pixel_bytes;
     *out = t;
     return true;
+}
+
+// ---------------------------------------------------------------- K7 into a device image: rfx_export_device's store form and launch
+// The image of include/rfx.h rfx_device_image is written where the caller keeps it: the element of column x, tile row r and channel ch goes
+// stride_x x + stride_y r + stride_c ch ELEMENTS from `data`.  One form per call, uniform over the launch (k7_export.hip k7_export_strided
+// branches on it per wave):
+//   TIGHT        interleaved (stride_c == 1, stride_x == channels), stride_y == W x channels, `data` on a 4-byte boundary: the flat k7_export on
+//                the caller's pointer over the whole run (`flat` is its plan);
+//   INTERLEAVED  stride_c == 1, stride_x == channels, `data` and stride_y x element bytes multiples of 4: a lane's 4 C elements are one run of
+//                whole dwords, 16 C element bytes from its neighbour's;
+//   PLANAR       stride_x == 1, `data` aligned to four elements, stride_y and stride_c multiples of four elements: per channel, a lane's four
+//                elements are one aligned 16- / 8- / 4-byte store (F32 / F16 / U8);
+//   ELEMENT      everything else: element-wide stores.
+// The strided launch: a lane owns four consecutive pixels of ONE row — groups_x = W / 4 groups per row, the W mod 4 pixels from tail_x on go to
+// lane groups_x of the row, element by element; workgroups of RFX_K7_DEV_BX x RFX_K7_DEV_BY lanes (along the row x rows), grid_x x grid_y.
+// The block shape: 64 lanes along the row make every wave one row segment of 256 pixels — its loads are 4 KiB of consecutive texels and its
+// stores consecutive runs in every vector form, whatever the row pitch is — and 4 rows per workgroup keep the 256 lanes of k7_export, so a
+// 97 x 55 frame already has 14 workgroups along the rows and a 4K row is 15 workgroups wide.
+// Refused (the RFX_EINVAL case in words): a format or channel count the export does not have; data == 0; an address that is not a multiple of
+// the element size; an extent, (1 + sum over the axes of |stride| (count - 1)) elements, beyond 2^62 - 1 bytes (64-bit arithmetic that cannot
+// overflow); strides that do not nest — of the axes with count > 1, sorted by |stride|, the smallest must be >= 1 and every later one >= the
+// one before it x that axis's count (sufficient for an image that does not alias itself, not necessary).
+// A pure function of its arguments, exported as rfx_internal_export_device_plan (tests/test_export_device_cpu.py restates it).
+enum { RFX_EXPORT_FORM_TIGHT = 0, RFX_EXPORT_FORM_INTERLEAVED = 1, RFX_EXPORT_FORM_PLANAR = 2, RFX_EXPORT_FORM_ELEMENT = 3 };
+constexpr int RFX_K7_DEV_BX = 64, RFX_K7_DEV_BY = 4;
+struct rfx_export_device_plan {
+    int form;
+    int elem_bytes;
+    int groups_x, tail_x, tail_pixels, lanes_x;
+    int grid_x, grid_y;
+    rfx_export_plan flat;  // TIGHT: k7_export's plan over rows x W pixels (zeroed otherwise)
+};
+// addr: the image's `data` as an integer (read for alignment only); stride_*: in elements.  0, or the RFX_EINVAL case in words.
+inline const char *rfx_export_device_plan_for(int W, int rows, int format, int channels, unsigned long long addr, long long stride_x, long long stride_y,
+                                              long long stride_c, rfx_export_device_plan *out) {
+    rfx_export_device_plan t = {};
+    if (W <= 0 || rows <= 0 || (long long)W * rows > 0x7fffffffll || !rfx_export_plan_for(W * rows, format, channels, &t.flat)) return "bad format or channel count";
+    if (!addr) return "dst->data is NULL";
+    const unsigned long long e = (unsigned long long)t.flat.elem_bytes;
+    if (addr % e) return "dst->data is not aligned to the element size";
+    const unsigned long long lim = ((1ull << 62) - 1ull) / e;
+    const long long s[3] = {stride_x, stride_y, stride_c};
+    const int n[3] = {W, rows, channels};
+    unsigned long long mag[3], total = 1;
+    for (int k = 0; k < 3; k++) {
+        mag[k] = s[k] < 0 ? 0ull - (unsigned long long)s[k] : (unsigned long long)s[k];
+        const unsigned long long steps = (unsigned long long)(n[k] - 1);
+        if (steps && mag[k] > (lim - total) / steps) return "the image's extent does not fit in 62 bits of bytes";
+        total += mag[k] * steps;
+    }
+    // the nesting rule over the axes that step at all (every |stride| x count below is under 2^63: the extent above)
+    int axis[3], m = 0;
+    for (int k = 0; k < 3; k++)
+        if (n[k] > 1) axis[m++] = k;
+    for (int i = 1; i < m; i++)
+        for (int j = i; j > 0 && mag[axis[j]] < mag[axis[j - 1]]; j--) { const int q = axis[j]; axis[j] = axis[j - 1]; axis[j - 1] = q; }
+    for (int i = 0; i < m; i++) {
+        if (i == 0 ? mag[axis[0]] < 1ull : mag[axis[i]] < mag[axis[i - 1]] * (unsigned long long)n[axis[i - 1]])
+            return "the image's strides do not nest: the image would alias itself (include/rfx.h \"device images\")";
+    }
+    const long long per = (long long)(4ull / e);  // elements per dword
+    const bool interleaved = stride_c == 1 && stride_x == channels;
+    t.elem_bytes = (int)e;
+    if (interleaved && addr % 4ull == 0 && stride_y == (long long)W * channels) t.form = RFX_EXPORT_FORM_TIGHT;
+    else if (interleaved && addr % 4ull == 0 && stride_y % per == 0) t.form = RFX_EXPORT_FORM_INTERLEAVED;
+    else if (stride_x == 1 && addr % (4ull * e) == 0 && stride_y % 4 == 0 && stride_c % 4 == 0) t.form = RFX_EXPORT_FORM_PLANAR;
+    else t.form = RFX_EXPORT_FORM_ELEMENT;
+    t.groups_x = W / 4;
+    t.tail_x = t.groups_x * 4;
+    t.tail_pixels = W - t.tail_x;
+    t.lanes_x = t.groups_x + (t.tail_pixels ? 1 : 0);
+    t.grid_x = (t.lanes_x + RFX_K7_DEV_BX - 1) / RFX_K7_DEV_BX;
+    t.grid_y = (rows + RFX_K7_DEV_BY - 1) / RFX_K7_DEV_BY;
+    if (t.form != RFX_EXPORT_FORM_TIGHT) t.flat = rfx_export_plan{};
+    *out = t;
+    return nullptr;
 }
 
 // ---------------------------------------------------------------- K8: the PNG fragment's buffers

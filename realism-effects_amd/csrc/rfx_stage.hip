@@ -218,6 +218,42 @@ int rfx_stage_aov_device(rfx_ctx *c, const rfx_aov_device_frame *f, int row0, in
     return RFX_OK;
 }
 
+// ---- stream ordering (include/rfx.h "device images and stream ordering"): a queue of the context against a caller's stream, one event record
+// and one stream wait, no host wait.  -> the queue's stream, the two events in place; an RFX_* code in *rc otherwise
+static hipStream_t order_queue(rfx_ctx *c, int queue, void *hip_stream, const char *fn, int *rc) {
+    *rc = RFX_OK;
+    if (queue != RFX_QUEUE_DRAW && queue != RFX_QUEUE_UPLOAD) { *rc = fail_in(c, RFX_EINVAL, fn, "queue must be RFX_QUEUE_DRAW or RFX_QUEUE_UPLOAD"); return nullptr; }
+    if (!hip_stream) { *rc = fail_in(c, RFX_EINVAL, fn, "hip_stream is NULL (the legacy default stream cannot be named: create a stream)"); return nullptr; }
+    for (hipEvent_t &e : c->ev_order) {
+        if (e) continue;
+        const hipError_t err = hipEventCreateWithFlags(&e, hipEventDisableTiming);
+        if (err != hipSuccess) { e = nullptr; *rc = fail(c, RFX_EDEVICE, "rfx_queue_wait_stream / rfx_stream_wait_queue: event creation", err); return nullptr; }
+    }
+    if (queue == RFX_QUEUE_DRAW) return c->stream;
+    if ((*rc = stage_streams(c))) return nullptr;
+    return c->upload_stream;
+}
+int rfx_queue_wait_stream(rfx_ctx *c, int queue, void *hip_stream) {
+    if (!c) return RFX_EINVAL;
+    RFX_ENTER(c);
+    int rc;
+    hipStream_t q = order_queue(c, queue, hip_stream, "rfx_queue_wait_stream", &rc);
+    if (rc) return rc;
+    HIPCHK(c, hipEventRecord(c->ev_order[0], (hipStream_t)hip_stream));
+    HIPCHK(c, hipStreamWaitEvent(q, c->ev_order[0], 0));
+    return RFX_OK;
+}
+int rfx_stream_wait_queue(rfx_ctx *c, int queue, void *hip_stream) {
+    if (!c) return RFX_EINVAL;
+    RFX_ENTER(c);
+    int rc;
+    hipStream_t q = order_queue(c, queue, hip_stream, "rfx_stream_wait_queue", &rc);
+    if (rc) return rc;
+    HIPCHK(c, hipEventRecord(c->ev_order[1], q));
+    HIPCHK(c, hipStreamWaitEvent((hipStream_t)hip_stream, c->ev_order[1], 0));
+    return RFX_OK;
+}
+
 int rfx_set_aov_conventions(rfx_ctx *c, const rfx_aov_conventions *q) {
     if (!c) return RFX_EINVAL;
     RFX_ENTER(c);

@@ -198,6 +198,15 @@ class ExportParams(C.Structure):
     _fields_ = [("source", C.c_int32), ("format", C.c_int32), ("channels", C.c_int32), ("tonemap", C.c_int32), ("exposure", C.c_float)]
 
 
+# rfx.h "device images and stream ordering": rfx_export_device's destination, addressed by element strides in device memory, and the queues
+# rfx_queue_wait_stream / rfx_stream_wait_queue order against a caller's stream (additive to ABI 21)
+class DeviceImage(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("stride_x", C.c_int64), ("stride_y", C.c_int64), ("stride_c", C.c_int64)]
+
+
+QUEUE_DRAW, QUEUE_UPLOAD = 0, 1
+
+
 EXPORTS = [
     "rfx_abi_version", "rfx_create", "rfx_destroy", "rfx_last_error", "rfx_get_geometry", "rfx_set_stream", "rfx_tex_texel_bytes", "rfx_tex_held_rows",
     "rfx_upload", "rfx_download", "rfx_clear", "rfx_tex_device_ptr", "rfx_bind_external", "rfx_pack_gbuffer", "rfx_pack_velocity", "rfx_set_environment", "rfx_set_environment_importance", "rfx_download_environment", "rfx_cube_to_equirect", "rfx_set_row_window", "rfx_set_uv_model", "rfx_ssgi_march", "rfx_ssgi_trace", "rfx_ssgi_shade", "rfx_temporal_reproject",
@@ -215,6 +224,7 @@ EXPORTS = [
     "rfx_set_environment_cube", "rfx_build_environment_importance", "rfx_download_environment_importance",
     "rfx_set_aov_conventions",
     "rfx_stage_aov_device",
+    "rfx_export_device", "rfx_queue_wait_stream", "rfx_stream_wait_queue",
 ]
 
 _lib = None
@@ -352,6 +362,10 @@ def load_library(path: str | None = None) -> C.CDLL:
         lib.rfx_set_aov_conventions.argtypes = [vp, C.POINTER(AovConventions)]
     if hasattr(lib, "rfx_stage_aov_device"):  # (additive to ABI 21: Context.has_stage_aov_device)
         lib.rfx_stage_aov_device.argtypes = [vp, C.POINTER(AovDeviceFrame), i, i, vp]
+    if hasattr(lib, "rfx_export_device"):  # (additive to ABI 21: Context.has_export_device)
+        lib.rfx_export_device.argtypes = [vp, C.POINTER(ExportParams), C.POINTER(DeviceImage)]
+        lib.rfx_queue_wait_stream.argtypes = [vp, i, vp]
+        lib.rfx_stream_wait_queue.argtypes = [vp, i, vp]
     if lib.rfx_abi_version() != RFX_ABI_VERSION:
         raise ImportError("librfx_hip.so ABI version %d != %d" % (lib.rfx_abi_version(), RFX_ABI_VERSION))
     if path is None:

@@ -49,6 +49,34 @@ def device_plane(tensor, rows: int, width: int, origin: str = "bottom") -> abi.D
     return abi.DevicePlane(ptr, kind, shape[2], sx, sy, sc)
 
 
+_TENSOR_IMAGE_FORMATS = {"torch.float32": (abi.EXPORT_F32, 4), "torch.float16": (abi.EXPORT_F16, 2), "torch.uint8": (abi.EXPORT_U8_SRGB, 1)}
+
+
+def device_image(tensor, rows: int, width: int, origin: str = "bottom") -> abi.DeviceImage:
+    """device_plane's twin for the way out: a WRITABLE (rows, width, C) tensor — float32, float16 or uint8, C = 3 or 4, ANY strides: a permuted
+    (C, H, W) tensor, a slice of a pitched buffer — -> the abi.DeviceImage that Context.export_device writes where the tensor lies.  origin
+    "bottom": the tensor's row 0 is the tile's first frame row (row 0 of the frame is its bottom row); "top": row 0 is the tile's LAST frame
+    row, as images are kept — a negative stride_y from the tensor's last row.  The format an image is written in is export_device's `format`;
+    the record remembers the tensor's (`image.format`) and export_device refuses another.  Whether the strides can be written without the
+    image aliasing itself (an `expand`ed tensor cannot) is the library's rule: the call refuses.  A pure function of the tensor's shape,
+    strides, dtype and data_ptr(): it runs on CPU tensors too."""
+    if origin not in ("bottom", "top"):
+        raise ValueError("origin: \"bottom\" or \"top\"")
+    shape, strides = tuple(int(n) for n in tensor.shape), tuple(int(s) for s in tensor.stride())
+    if len(shape) != 3 or shape[:2] != (int(rows), int(width)) or shape[2] not in (3, 4):
+        raise ValueError("device image: a tensor of shape (%d, %d, 3 or 4), got %s" % (rows, width, tuple(tensor.shape)))
+    if str(tensor.dtype) not in _TENSOR_IMAGE_FORMATS:
+        raise TypeError("device image: a float32, float16 or uint8 tensor, got %s" % (tensor.dtype,))
+    fmt, elem = _TENSOR_IMAGE_FORMATS[str(tensor.dtype)]
+    sy, sx, sc = strides
+    ptr = int(tensor.data_ptr())
+    if origin == "top":
+        ptr, sy = ptr + (shape[0] - 1) * sy * elem, -sy
+    image = abi.DeviceImage(ptr, sx, sy, sc)
+    image.format, image.channels = fmt, shape[2]  # (python attributes, not fields: what export_device holds its arguments against)
+    return image
+
+
 class Context:
     def __init__(self, width: int, height: int, device: int = 0, tile_y0: int = 0, tile_rows: int | None = None, halo_rows: int = 0):
         self.lib = abi.load_library()
@@ -216,16 +244,70 @@ class Context:
             setattr(f, name, v)
         return f, row0, rows
 
-    def stage_aov_device(self, planes: dict, row0: int | None = None, rows: int | None = None):
+    def stage_aov_device(self, planes: dict, row0: int | None = None, rows: int | None = None, *, producer: int | None = None):
         """rfx_stage_aov_device: stage_aov for planes that already live on the device — nothing crosses PCIe, the pack kernel reads them where
         they lie.  Values: abi.DevicePlane records (a device address and element strides of any sign, 0 for a broadcast); device_plane() makes
         one of a torch tensor of shape (rows, W, C) or (rows, W) with any strides.  `position=` / `view_z=` as in stage_aov.  The planes are
-        complete when the call is made (synchronise the stream that produced them) and the caller keeps them alive and unchanged until the
-        flip after the publishing one has returned."""
+        complete when the call is made (synchronise the stream that produced them) — or `producer=` names the stream that writes them (an
+        integer hipStream_t handle, non-zero): queue_wait_stream(QUEUE_UPLOAD, producer) runs first and the host does not wait.  The caller
+        keeps the planes alive and unchanged until the flip after the publishing one has returned (stream_wait_queue(QUEUE_UPLOAD, producer)
+        orders the producer's next writes behind the pack kernel)."""
         if not self.has_stage_aov_device:
             raise RfxError("this librfx_hip.so has no rfx_stage_aov_device")
+        if producer is not None:
+            producer = self._stream_handle("stage_aov_device(producer=)", producer)
         f, row0, rows = self._aov_device_frame(planes, row0, rows)
+        if producer is not None:
+            self.queue_wait_stream(abi.QUEUE_UPLOAD, producer)
         self._chk(self.lib.rfx_stage_aov_device(self._h, C.byref(f), row0, rows, None), "rfx_stage_aov_device")
+
+    # -- device images and stream ordering (rfx.h): the export that stays on the device, the context's queues against a caller's stream
+    @property
+    def has_export_device(self) -> bool:
+        """the library exports rfx_export_device, rfx_queue_wait_stream and rfx_stream_wait_queue (additive to ABI 21)"""
+        return hasattr(self.lib, "rfx_export_device")
+
+    @staticmethod
+    def _stream_handle(what, stream) -> int:
+        """a hipStream_t as an integer, e.g. torch.cuda.current_stream().cuda_stream; 0 is the legacy default stream, which cannot be named"""
+        if isinstance(stream, bool) or not isinstance(stream, int):
+            raise TypeError("%s: an integer hipStream_t handle, got %s" % (what, type(stream)))
+        if stream == 0:
+            raise ValueError("%s: 0 is the legacy default stream, which cannot be named: create a stream" % what)
+        return stream
+
+    def _need_export_device(self, what):
+        if not self.has_export_device:
+            raise RfxError("%s: this librfx_hip.so has no rfx_export_device (Context.has_export_device)" % what)
+
+    def queue_wait_stream(self, queue: int, stream: int):
+        """rfx_queue_wait_stream: the context's queue (abi.QUEUE_DRAW / QUEUE_UPLOAD) waits for what `stream` holds now; the host does not"""
+        self._need_export_device("queue_wait_stream")
+        self._chk(self.lib.rfx_queue_wait_stream(self._h, int(queue), C.c_void_p(self._stream_handle("queue_wait_stream", stream))), "rfx_queue_wait_stream")
+
+    def stream_wait_queue(self, queue: int, stream: int):
+        """rfx_stream_wait_queue: `stream` waits for what the context's queue holds now; the host does not"""
+        self._need_export_device("stream_wait_queue")
+        self._chk(self.lib.rfx_stream_wait_queue(self._h, int(queue), C.c_void_p(self._stream_handle("stream_wait_queue", stream))), "rfx_stream_wait_queue")
+
+    def export_device(self, source: int, format, channels: int = 3, tonemap="linear", exposure: float = 1.0, *, image: abi.DeviceImage, stream: int | None = None):
+        """rfx_export_device: export()'s elements, bit for bit, encoded on the draw stream straight into `image` — an abi.DeviceImage (a device
+        address and element strides of any sign; device_image() makes one of a writable torch tensor).  Nothing crosses PCIe, no ticket is taken
+        and the host does not wait: the image is complete once the draw stream has run the encode.  `stream=` (an integer hipStream_t handle,
+        non-zero) names the consumer's stream: the encode waits for what that stream holds now (its last reads of the image) and the stream
+        waits for the encode — queue_wait_stream(QUEUE_DRAW, stream) before, stream_wait_queue(QUEUE_DRAW, stream) after."""
+        self._need_export_device("export_device")
+        if not isinstance(image, abi.DeviceImage):
+            raise TypeError("export_device: image must be an abi.DeviceImage (context.device_image makes one of a tensor), got %s" % (type(image),))
+        p = self.export_params(source, format, channels, tonemap, exposure)
+        if getattr(image, "format", p.format) != p.format or getattr(image, "channels", p.channels) != p.channels:
+            raise ValueError("export_device: the image was made of a tensor of another dtype or channel count than format %r, channels %d" % (format, channels))
+        if stream is not None:
+            stream = self._stream_handle("export_device(stream=)", stream)
+            self.queue_wait_stream(abi.QUEUE_DRAW, stream)
+        self._chk(self.lib.rfx_export_device(self._h, C.byref(p), C.byref(image)), "rfx_export_device")
+        if stream is not None:
+            self.stream_wait_queue(abi.QUEUE_DRAW, stream)
 
     # -- AOV conventions (rfx.h "AOV conventions"): the planes as engines write them, converted by the pack kernel
     @property

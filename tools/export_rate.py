@@ -36,6 +36,18 @@ and the encode alone (rfx_profile, kind K8) for PNG and EXR with matches off and
 spread from round to round stands next to the difference; the fragment bytes of the same frame off and on, and that frame through the host's
 ZIPS writer.
 
+--modes device measures the export that stays on the device (rfx.h "device images"), without the SSGI chain — a context with a 4K frame in
+RFX_TEX_EFFECT_INPUT, images in hipMalloc'ed memory — and ADDS its results to --out under the key "device":
+
+    kernels   for each of the eight K7 specialisations, the K7 time (rfx_profile, kind K7) of rfx_stage_export (the flat kernel into the staging
+              buffer) and of rfx_export_device in its four forms — tight (the flat kernel on the caller's pointer), interleaved (rows padded to a
+              multiple of four elements and four more), planar ((C, H, W) with padded rows and planes), element (a mirrored x) — in three
+              alternating rounds of 20 launches each of the SAME run; per form the median, its ratio to the flat kernel's median, and the flat
+              kernel's own spread between rounds to hold the difference against
+    handover  the whole cost per frame of getting a frame to a consumer's stream, F16 x 4 and U8 x 3 ACES: D1, export_device(stream=) and
+              the consumer's device-to-device copy of the image; H1, stage_export into pinned memory, export_wait, hipMemcpyAsync back up on
+              the consumer's stream, the same device-to-device copy; three alternating rounds, the consumer's stream synchronised inside the clock
+
 --modes matches --parent-lib PATH (a librfx_hip.so built from the parent commit) measures only those encodes alone, on that library and on
 this tree's in alternating fresh processes of one session (--processes of each), and ADDS them to --out under --key with, per encode, the
 parent's median and full range, the tree's median, and whether the tree's median is within the parent's median plus that range.
@@ -364,14 +376,144 @@ def main_matches(run, a):
         f.write("\n")
 
 
+DEVICE_SPECS = (("f32", 3, "linear", 1.0), ("f32", 4, "linear", 1.0), ("f16", 3, "linear", 1.0), ("f16", 4, "linear", 1.0),
+                ("u8_srgb", 3, "linear", 1.0), ("u8_srgb", 4, "linear", 1.0), ("u8_srgb", 3, "aces", 1.0), ("u8_srgb", 4, "aces", 1.0))
+DEVICE_FORMS = ("tight", "interleaved", "planar", "element")
+
+
+def device_image_of(form, base, ch, elem):
+    """-> (abi.DeviceImage over the buffer at `base`, the bytes it spans) for a whole frame in one of the four store forms"""
+    if form == "tight":
+        return abi.DeviceImage(base, ch, W * ch, 1), W * H * ch * elem
+    if form == "interleaved":
+        pitch = W * ch + (-W * ch) % 4 + 4
+        return abi.DeviceImage(base, ch, pitch, 1), H * pitch * elem
+    if form == "planar":
+        wp = W + (-W) % 4 + 4
+        plane = H * wp + 8
+        return abi.DeviceImage(base, 1, wp, plane), ch * plane * elem
+    return abi.DeviceImage(base + (W - 1) * ch * elem, -ch, W * ch, 1), W * H * ch * elem  # element: x mirrored
+
+
+def main_device(a):
+    """--modes device: K7 per specialisation and store form next to the flat K7 of the same run, and the hand-over to a consumer's stream;
+    merged into the file under the key "device" """
+    import statistics
+    ctx = Context(W, H)  # raises without a device
+    if not ctx.has_export_device:
+        raise SystemExit("this librfx_hip.so has no rfx_export_device")
+    with open("/proc/self/maps") as f:
+        paths = sorted({line.split()[-1] for line in f if "libamdhip64" in line})
+    hip = C.CDLL(paths[0])  # the runtime the library runs on
+    hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+    hip.hipStreamCreateWithFlags.argtypes = [C.POINTER(C.c_void_p), C.c_uint]
+    hip.hipStreamSynchronize.argtypes = [C.c_void_p]
+    hip.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+    rng = np.random.default_rng(a.seed)
+    ctx.upload(abi.TEX_EFFECT_INPUT, rng.lognormal(-1.0, 1.5, (H, W, 4)).astype(np.float32))
+    wp = W + (-W) % 4 + 4
+    cap = 4 * (H * wp + 8) * 4 + 256  # the largest image: planar F32 x 4
+    bufs = []
+    for _ in range(2):
+        p = C.c_void_p()
+        assert hip.hipMalloc(C.byref(p), cap) == 0
+        bufs.append(p.value)
+    stream = C.c_void_p()
+    assert hip.hipStreamCreateWithFlags(C.byref(stream), 1) == 0
+    consumer = stream.value
+    pinned = {}
+
+    def host(fmt, ch):
+        if (fmt, ch) not in pinned:
+            pinned[(fmt, ch)] = [ctx.host_alloc((H, W, ch), abi.EXPORT_DTYPE[abi.EXPORT_FORMATS[fmt]]) for _ in range(2)]
+        return pinned[(fmt, ch)]
+
+    def k7(fn, n=20):
+        ctx.sync()
+        ctx.profile(True)
+        for i in range(n):
+            fn(i)
+        ctx.sync()
+        ms, launches = ctx.profile_read()["k7_export"]
+        ctx.profile(False)
+        assert launches == n, (launches, n)
+        return round(ms / launches, 5)
+
+    result = dict(width=W, height=H, seed=a.seed, launches_per_round=20, rounds=3, kernels={}, handover={})
+    for fmt, ch, tm, ex in DEVICE_SPECS:
+        elem = abi.EXPORT_DTYPE[abi.EXPORT_FORMATS[fmt]]().itemsize
+        out = host(fmt, ch)
+        images = {form: device_image_of(form, bufs[0], ch, elem)[0] for form in DEVICE_FORMS}
+        runs = {"flat": lambda i: ctx.export_wait(ctx.stage_export(abi.TEX_EFFECT_INPUT, fmt, ch, tm, ex, out=out[i & 1]))}
+        for form in DEVICE_FORMS:
+            runs[form] = lambda i, form=form: ctx.export_device(abi.TEX_EFFECT_INPUT, fmt, ch, tm, ex, image=images[form])
+        for fn in runs.values():  # warm every shape
+            for i in range(3):
+                fn(i)
+        ms = {k: [] for k in runs}
+        for r in range(3):
+            for k, fn in runs.items():
+                ms[k].append(k7(fn))
+        flat = statistics.median(ms["flat"])
+        row = dict(bytes_read=W * H * 16, bytes_written=W * H * ch * elem, flat_ms_rounds=ms["flat"], flat_ms=flat, flat_spread=round(max(ms["flat"]) - min(ms["flat"]), 5))
+        for form in DEVICE_FORMS:
+            med = statistics.median(ms[form])
+            row[form] = dict(ms_rounds=ms[form], ms=med, of_flat=round(med / flat, 4), slower_than_flat_by_more_than_its_spread=bool(med - flat > row["flat_spread"]))
+        result["kernels"]["%s_x%d_%s" % (fmt, ch, tm)] = row
+        print(fmt, ch, tm, json.dumps(row), flush=True)
+    # the hand-over: a frame on a consumer's stream, from the device image and through the host
+    for fmt, ch, tm, ex in (("f16", 4, "linear", 1.0), ("u8_srgb", 3, "aces", 1.0)):
+        elem = abi.EXPORT_DTYPE[abi.EXPORT_FORMATS[fmt]]().itemsize
+        out = host(fmt, ch)
+        image, nbytes = device_image_of("tight", bufs[0], ch, elem)
+
+        def d1(n):
+            t0 = time.perf_counter()
+            for i in range(n):
+                ctx.export_device(abi.TEX_EFFECT_INPUT, fmt, ch, tm, ex, image=image, stream=consumer)
+                assert hip.hipMemcpyAsync(bufs[1], bufs[0], nbytes, 3, consumer) == 0  # the consumer reads the image
+            assert hip.hipStreamSynchronize(consumer) == 0
+            return (time.perf_counter() - t0) / n * 1e3
+
+        def h1(n):
+            t0 = time.perf_counter()
+            for i in range(n):
+                ctx.export_wait(ctx.stage_export(abi.TEX_EFFECT_INPUT, fmt, ch, tm, ex, out=out[i & 1]))
+                assert hip.hipMemcpyAsync(bufs[0], out[i & 1].ctypes.data, nbytes, 1, consumer) == 0
+                assert hip.hipMemcpyAsync(bufs[1], bufs[0], nbytes, 3, consumer) == 0
+            assert hip.hipStreamSynchronize(consumer) == 0
+            return (time.perf_counter() - t0) / n * 1e3
+
+        d1(5), h1(5)
+        rounds = []
+        for r in range(3):
+            row = dict(D1=round(d1(50), 4), H1=round(h1(50), 4))
+            row["D1_of_H1"] = round(row["D1"] / row["H1"], 4)
+            rounds.append(row)
+        result["handover"]["%s_x%d_%s" % (fmt, ch, tm)] = dict(frame_bytes=nbytes, frames_per_round=50, rounds=rounds)
+        print(fmt, ch, tm, json.dumps(rounds), flush=True)
+    ctx.sync()
+    ctx.close()
+    merged = {}
+    if os.path.exists(a.out):
+        with open(a.out) as f:
+            merged = json.load(f)
+    merged["device"] = result
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(merged, f, indent=1)
+        f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "export", "rates.json"))
     ap.add_argument("--seconds", type=float, default=1.0, help="steady state per measurement, at least")
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--size", default="3840x2160", help="frame size (the committed numbers are 4K; a small size checks the script itself)")
-    ap.add_argument("--modes", default="png", choices=("png", "exr", "matches"),
-                    help='"exr": T0 / E1 / E2 / E3, added to --out under "exr"; "matches": T0 / T3 / T3m / E3 / E3m, added under "matches"')
+    ap.add_argument("--modes", default="png", choices=("png", "exr", "matches", "device"),
+                    help='"exr": T0 / E1 / E2 / E3, added to --out under "exr"; "matches": T0 / T3 / T3m / E3 / E3m, added under "matches"; '
+                         '"device": rfx_export_device per store form against the flat K7, and the hand-over to a consumer stream, added under "device"')
     ap.add_argument("--parent-lib", default=None, help="with --modes matches: a librfx_hip.so of the parent commit; only the encodes alone are measured, "
                                                        "on it and on this tree's library in alternating processes, and added to --out under --key")
     ap.add_argument("--processes", type=int, default=2, help="with --parent-lib: processes per library")
@@ -385,6 +527,8 @@ def main():
         return main_parent_against_tree(a)
     if a.lib:
         abi.set_library_path(a.lib)
+    if a.modes == "device":
+        return main_device(a)
     run = Run(a.seed)
     if a.modes == "matches" and a.encodes_only:
         run.alloc_exr()
